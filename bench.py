@@ -2,6 +2,7 @@
 """bench.py -- ligands/sec of the TargetDiff denoising hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c1|c5|c4] [--no-cpu-baseline] [--no-full-run]
+                    [--dump-outputs DIR]
 
 `--gpus N` with no launcher around the script (no RANK / WORLD_SIZE in the environment) starts the N ranks itself, one
 process per GPU (targetdiff_amd/launch.py; the environment each rank sees is the one `python -m torch.distributed.run
@@ -18,6 +19,10 @@ skips rows the ligand cannot influence); `--initial-state` additionally times th
 the rate at which finished ligands leave a 1000-step sampler.  With N > 1 (torch.distributed.run, one
 rank per GPU over RCCL) every rank samples its own pocket replica -- pockets shard with no data-path
 collective (scripts/batch_sample_diffusion.sh:15-20) -- so scaling is "weak".
+
+`--dump-outputs DIR` writes what the last of the K timed steps computed -- the ligand positions (de-centred), atom types and log type
+distributions a caller of the sampler receives for that step -- as DIR/<name>.npy (float32, at most 64 MB).  Weights, inputs and the
+sampler's draws are seeded, so two builds run with the same arguments can be compared output for output.
 
 Extra objects on the JSON line:
   roofline     dominant kernel = edge_value16t_kernel (x2h value pass; the key pass edge_key16_kernel is its twin and is
@@ -338,6 +343,39 @@ def stateless_floor(model, batch, lpos, lv, max_nodes, steps=10, warmup=3):
     return (time.perf_counter() - t1) / steps * 1e3
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: all files of all ranks together
+
+
+def last_step_outputs(sampler):
+    """What the sampler's last step handed its caller, as ``finish()`` returns it for that step: the de-centred ligand
+    positions, the atom types and the two log type distributions (device tensors, copied)."""
+    s = sampler.s - 1
+    pos = sampler.pos_traj[s]
+    if sampler.offset is not None:
+        pos = pos + sampler.offset[sampler.batch_ligand]
+    out = {'ligand_pos': pos.clone(), 'ligand_v': sampler.v_traj[s].clone()}
+    if not sampler.pos_only:
+        out.update(log_ligand_v0=sampler.v0_traj[s].clone(), log_ligand_vt=sampler.vt_traj[s].clone())
+    return out
+
+
+def dump_outputs(directory, parts, rank, world):
+    """Write the last timed step's outputs as DIR/<name>.npy in float32 (``<name>.rank<r>.npy`` for ranks > 0); ``parts`` holds
+    one dict of :func:`last_step_outputs` per sampler, concatenated along the atoms.  Past this rank's share of DUMP_BYTES a fixed,
+    seeded sample of the atoms is written (the same rows of every array), with their indices as ``ligand_rows``."""
+    arrays = {k: torch.cat([p[k] for p in parts]).cpu().numpy().astype(np.float32) for k in parts[0]}
+    n = len(arrays['ligand_pos'])
+    row_bytes = sum(a[0].nbytes for a in arrays.values()) if n else 1
+    keep = (DUMP_BYTES // world) // (row_bytes + 8)
+    if n > keep:
+        rows = np.sort(np.random.default_rng(2021).choice(n, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays['ligand_rows'] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ('' if rank == 0 else f'.rank{rank}') + '.npy'), a)
+
+
 def graph_desc(args):
     if args.cutoff_mode == 'radius':
         return f'radius {args.radius} A, fan-out cap {args.cap}'
@@ -396,6 +434,7 @@ def run_c4(args, model, dev, rank, world, fence):
     total = args.warmup + args.steps
     samplers, nodes = [], 0
     bs = args.batch_size if args.batch_size and args.batch_size > 0 else spp       # scripts/batch_sample_diffusion.sh:2 runs BATCH_SIZE=50
+    torch.manual_seed(2021 + rank)          # the samplers' Gaussian / uniform draws: the same from run to run
     for i in mine:
         pdev = workloads.DevicePocket(pockets[i], dev)
         # the pocket's samples in batches of `bs`, one after the other as scripts/sample_diffusion.py:38-41 runs them (a session each)
@@ -422,6 +461,8 @@ def run_c4(args, model, dev, rank, world, fence):
     mine_elapsed = time.perf_counter() - t0
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [last_step_outputs(sm) for sm in samplers], rank, world)
     per_rank = [mine_elapsed]
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -475,6 +516,9 @@ def main():
     ap.add_argument('--cap', type=int, default=32, help='fan-out cap of --cutoff-mode radius (C5 sweep)')
     ap.add_argument('--option', action='append', default=[], metavar='NAME=VALUE', help='td_model_set_option (experiments)')
     ap.add_argument('--fp32-node-gemms', action='store_true', help='node-side GEMMs on fp32 MFMA instead of the exact bf16 x 3 split')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what their last step computed (ligand positions, types, log type distributions) '
+                         'as DIR/<name>.npy, float32, at most 64 MB')
     args = ap.parse_args()
     # `--gpus N` without a launcher: become the launcher (N ranks of this same command line), exit with their status
     launch.self_spawn_if_needed(args.gpus)
@@ -525,6 +569,7 @@ def main():
     total = args.warmup + args.steps + args.prof_steps
     if total > 1000:
         raise SystemExit('warmup + steps + the profiled steps must be <= 1000 (one sampling run)')
+    torch.manual_seed(2021 + rank)          # the sampler's Gaussian / uniform draws: the same from run to run
     sampler = model.begin_sampling(batch.protein_pos, batch.protein_atom_feature.float(), batch.protein_element_batch,
                                    lpos, lv, batch.ligand_element_batch, num_steps=total, center_pos_mode='protein',
                                    max_graph_nodes=max_nodes, use_session=not args.no_session, use_graph=False if args.no_graph else None)
@@ -538,6 +583,8 @@ def main():
         sampler.step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:                   # before the profiled steps below advance the same sampler
+        dump_outputs(args.dump_outputs, [last_step_outputs(sampler)], rank, world)
     step_launch = ('one hipGraph replay per step (td_session_step)' if sampler.session is not None and sampler.session.last_step_was_graph()
                    else 'launch by launch')
     # roofline leg: the next steps of the same run with HIP events around the x2h key / value launches, recorded on the

@@ -1,8 +1,8 @@
 """Import the REAL reference model code (TEST INFRASTRUCTURE; build container only).
 
 /root/reference does not exist on the GPU box, so nothing that runs there may import this module.
-It is used by ``oracle/make_golden.py`` (fixture generation) and by the optional
-``tests/test_oracle_vs_reference.py`` (skipped when the reference tree is absent).
+It is used by the ``oracle/make_golden*.py`` fixture generators and by ``oracle/check_with_reference.py`` (skipped when the
+reference tree is absent); the suite under ``tests/`` does not import it.
 
 The reference files are imported unmodified: models/molopt_score_model.py, models/uni_transformer.py,
 models/common.py, models/egnn.py.  Their third-party imports are satisfied by ``oracle.shims``.

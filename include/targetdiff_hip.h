@@ -226,6 +226,39 @@ int td_egnn_forward(const td_egnn *m, const float *d_h, const float *d_x, const 
                     const int32_t *d_node_ptr, int64_t N, int64_t B, int32_t max_graph_nodes, float *d_out_h, float *d_out_x,
                     float *d_all_h, float *d_all_x, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- binding-affinity predictor (replaces: models/property_pred/prop_model.py PropPredNet.forward / PropPredNetEnc.forward with
+ *      the EnEquiEncoder of prop_egnn.py, as utils/misc_prop.py get_model builds them; configs/prop/ (the .yml files)).  Built for hidden 256,
+ *      64 Gaussians, ReLU, no LayerNorm, no coordinate update, edge_dim 0, any 1 <= knn <= 64 and any layer count.
+ *      `host_weights`, as PyTorch stores them: protein_atom_emb.{weight [256,Fp], bias}, ligand_atom_emb.{weight [256,Fl+El], bias},
+ *      encoder.distance_expansion.offset [64]; per layer edge_mlp.net.0.{weight [256,576], bias}, edge_mlp.net.2.{weight, bias},
+ *      edge_inf.0.{weight [1,256], bias [1]}, node_mlp.net.0.{weight [256,512], bias}, node_mlp.net.2.{weight, bias};
+ *      when enc_node_dim > 0 enc_node_layer.0.{weight [256,256+En], bias}, enc_node_layer.2.{weight, bias}; then
+ *      out_block.0.{weight [256,256+Eg], bias}, out_block.2.{weight [O,256], bias [O]}.
+ *      td_prop_forward: protein / ligand atoms un-composed, each sorted by complex (d_*_ptr [B+1] int32 prefix offsets); the
+ *      composed order is the project's rule: per complex its protein atoms, then its ligand atoms, each in input order.
+ *      d_enc_ligand [N_l,El] (needed when El > 0), d_enc_node [N,En] in composed order (optional: NULL skips enc_node_layer, as the
+ *      reference does for enc_node_feature=None), d_enc_graph [B,Eg] (needed when Eg > 0).  d_output_kind [B] int64 (1 = Ki,
+ *      2 = Kd, 3 = IC50) or NULL: d_out is [B,1] or [B,O].  Optional outputs (NULL = not wanted): d_h_layers [L][N][256] (h after
+ *      every layer), d_final_h [N][256] (h after enc_node_layer), d_out_nbr [N][knn] (the graph: row i = its neighbours, ascending
+ *      (d2, index), -1 padded).  No atomics: reruns are bit-identical. */
+typedef struct td_prop td_prop;
+typedef struct td_prop_config {
+    int32_t hidden_dim, num_layers, knn, num_r_gaussian;
+    float cutoff;                      /* GaussianSmearing stop; the offsets themselves come with the weights */
+    int32_t protein_feat_dim, ligand_feat_dim;
+    int32_t enc_ligand_dim, enc_node_dim, enc_graph_dim;
+    int32_t output_dim;
+} td_prop_config;
+size_t td_prop_num_weights(const td_prop_config *cfg);
+int td_prop_create(const td_prop_config *cfg, const float *host_weights, size_t num_weights, td_prop **out);
+void td_prop_destroy(td_prop *m);
+size_t td_prop_workspace_bytes(const td_prop *m, int64_t N_p, int64_t N_l, int64_t B);
+int td_prop_forward(const td_prop *m, const float *d_protein_pos, const float *d_protein_feat, const int32_t *d_protein_ptr,
+                    int64_t N_p, const float *d_ligand_pos, const float *d_ligand_feat, const int32_t *d_ligand_ptr, int64_t N_l,
+                    int64_t B, const float *d_enc_ligand, const float *d_enc_node, const float *d_enc_graph,
+                    const int64_t *d_output_kind, int32_t max_graph_nodes, float *d_out, float *d_h_layers, float *d_final_h,
+                    int32_t *d_out_nbr, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---- other consumers of the denoiser (scripts/likelihood_est_diffusion.py; ScorePosNet3D.forward(return_all=True)).
  * They need the 8th schedule array (alphas_cumprod of the position schedule) at td_model_create.
  *

@@ -30,6 +30,13 @@ class TdConfig(ctypes.Structure):
                 ('x2h_out_fc', c_int32), ('sync_twoup', c_int32), ('num_x2h', c_int32), ('num_h2x', c_int32), ('reserved', c_int32 * 1)]
 
 
+class TdPropConfig(ctypes.Structure):
+    """td_prop_config of include/targetdiff_hip.h"""
+    _fields_ = [('hidden_dim', c_int32), ('num_layers', c_int32), ('knn', c_int32), ('num_r_gaussian', c_int32), ('cutoff', c_float),
+                ('protein_feat_dim', c_int32), ('ligand_feat_dim', c_int32), ('enc_ligand_dim', c_int32), ('enc_node_dim', c_int32),
+                ('enc_graph_dim', c_int32), ('output_dim', c_int32)]
+
+
 CUTOFF_MODES = {'knn': 0, 'hybrid': 1, 'radius': 2}      # TD_CUTOFF_* (include/targetdiff_hip.h)
 MAX_FANIN = 64
 ABI_VERSION = 5
@@ -66,6 +73,12 @@ SIGNATURES = {
     'td_egnn_destroy': (None, [_P]),
     'td_egnn_workspace_bytes': (ctypes.c_size_t, [c_int64]),
     'td_egnn_forward': (c_int32, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int32, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    'td_prop_num_weights': (ctypes.c_size_t, [_P]),
+    'td_prop_create': (c_int32, [_P, POINTER(c_float), ctypes.c_size_t, POINTER(c_void_p)]),
+    'td_prop_destroy': (None, [_P]),
+    'td_prop_workspace_bytes': (ctypes.c_size_t, [_P, c_int64, c_int64, c_int64]),
+    'td_prop_forward': (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int32, _P, _P, _P, _P,
+                                  _P, ctypes.c_size_t, _P]),
     'td_session_create': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int32, _P, POINTER(c_void_p)]),
     'td_session_destroy': (None, [_P]),
     'td_session_forward': (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P]),
@@ -648,3 +661,86 @@ class NativeEgnn:
             _ptr(node_ptr, torch.int32, 'node_ptr'), N, B, max_graph_nodes, _ptr(out_h), _ptr(out_x), _ptr(all_h), _ptr(all_x),
             _ptr(self._ws), self._ws.numel(), _stream(self.device)), 'td_egnn_forward')
         return out_h, out_x, all_h, all_x
+
+
+# ----------------------------------------------------------------------------------------- binding-affinity predictor
+PROP_HIDDEN = 256
+PROP_LAYER_KEYS = ('edge_mlp.net.0.weight', 'edge_mlp.net.0.bias', 'edge_mlp.net.2.weight', 'edge_mlp.net.2.bias',
+                   'edge_inf.0.weight', 'edge_inf.0.bias', 'node_mlp.net.0.weight', 'node_mlp.net.0.bias',
+                   'node_mlp.net.2.weight', 'node_mlp.net.2.bias')
+
+
+def prop_flat_key_order(num_layers: int, enc_node_dim: int = 0):
+    """The order td_prop_create reads the state_dict of PropPredNet / PropPredNetEnc in (include/targetdiff_hip.h)."""
+    keys = ['protein_atom_emb.weight', 'protein_atom_emb.bias', 'ligand_atom_emb.weight', 'ligand_atom_emb.bias',
+            'encoder.distance_expansion.offset']
+    keys += [f'encoder.net.{l}.{k}' for l in range(num_layers) for k in PROP_LAYER_KEYS]
+    if enc_node_dim > 0:
+        keys += ['enc_node_layer.0.weight', 'enc_node_layer.0.bias', 'enc_node_layer.2.weight', 'enc_node_layer.2.bias']
+    keys += ['out_block.0.weight', 'out_block.0.bias', 'out_block.2.weight', 'out_block.2.bias']
+    return keys
+
+
+class NativeProp:
+    """Owns a td_prop handle: PropPredNet / PropPredNetEnc (models/property_pred/prop_model.py) with packed weights on a HIP device."""
+
+    def __init__(self, cfg: dict, state_dict, device=None):
+        self.lib = load_library()
+        if not torch.cuda.is_available():
+            raise RuntimeError('no HIP device visible: targetdiff_amd needs an MI355X (gfx950); there is no CPU path')
+        self.device = _canonical_device(device)
+        self.cfg = TdPropConfig(**{k: cfg[k] for k, _ in TdPropConfig._fields_})
+        blob = np.ascontiguousarray(np.concatenate(
+            [state_dict[k].detach().cpu().numpy().astype(np.float32).reshape(-1)
+             for k in prop_flat_key_order(self.cfg.num_layers, self.cfg.enc_node_dim)]))
+        expect = int(self.lib.td_prop_num_weights(ctypes.byref(self.cfg)))
+        if blob.size != expect:
+            raise ValueError(f'weight blob has {blob.size} floats, library expects {expect}')
+        handle = c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self.lib.td_prop_create(ctypes.byref(self.cfg), blob.ctypes.data_as(POINTER(c_float)), blob.size,
+                                           ctypes.byref(handle)), 'td_prop_create')
+        self.handle = handle
+        self._ws = None
+
+    def __del__(self):
+        h, self.handle = getattr(self, 'handle', None), None
+        if h and getattr(self, 'lib', None) is not None:
+            self.lib.td_prop_destroy(h)
+
+    @_device_bound
+    def forward(self, protein_pos, protein_feat, protein_ptr, ligand_pos, ligand_feat, ligand_ptr, output_kind=None,
+                enc_ligand=None, enc_node=None, enc_graph=None, want_layers=False, want_final_h=False, want_graph=False,
+                max_graph_nodes=0):
+        """Inputs sorted by complex (``*_ptr``: [B+1] int32 offsets).  Returns (out [B, 1 or O], h_layers [L, N, 256] | None,
+        final_h [N, 256] | None, nbr [N, knn] | None); node rows in the composed order (per complex protein, then ligand)."""
+        Np, Nl, B = protein_pos.shape[0], ligand_pos.shape[0], protein_ptr.numel() - 1
+        N, dev, c = Np + Nl, protein_pos.device, self.cfg
+        out = torch.empty(B, 1 if output_kind is not None else c.output_dim, dtype=torch.float32, device=dev)
+        h_layers = torch.empty(c.num_layers, N, PROP_HIDDEN, dtype=torch.float32, device=dev) if want_layers else None
+        final_h = torch.empty(N, PROP_HIDDEN, dtype=torch.float32, device=dev) if want_final_h else None
+        nbr = torch.empty(N, c.knn, dtype=torch.int32, device=dev) if want_graph else None
+        need = int(self.lib.td_prop_workspace_bytes(self.handle, Np, Nl, B))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+
+        def opt(t, dtype, what, rows, cols):
+            if t is None:
+                return None
+            if tuple(t.shape) != (rows, cols):
+                raise ValueError(f'{what}: expected shape {(rows, cols)}, got {tuple(t.shape)}')
+            return _ptr(t, dtype, what)
+        kind = None
+        if output_kind is not None:
+            if tuple(output_kind.shape) != (B,):
+                raise ValueError(f'output_kind: expected shape {(B,)}, got {tuple(output_kind.shape)}')
+            kind = _ptr(output_kind, torch.int64, 'output_kind')
+        _check(self.lib.td_prop_forward(
+            self.handle, _ptr(protein_pos, torch.float32, 'protein_pos'), _ptr(protein_feat, torch.float32, 'protein_feat'),
+            _ptr(protein_ptr, torch.int32, 'protein_ptr'), Np, _ptr(ligand_pos, torch.float32, 'ligand_pos'),
+            _ptr(ligand_feat, torch.float32, 'ligand_feat'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
+            opt(enc_ligand, torch.float32, 'enc_ligand_feature', Nl, c.enc_ligand_dim),
+            opt(enc_node, torch.float32, 'enc_node_feature', N, c.enc_node_dim),
+            opt(enc_graph, torch.float32, 'enc_graph_feature', B, c.enc_graph_dim), kind, max_graph_nodes, _ptr(out),
+            _ptr(h_layers), _ptr(final_h), _ptr(nbr), _ptr(self._ws), self._ws.numel(), _stream(self.device)), 'td_prop_forward')
+        return out, h_layers, final_h, nbr

@@ -141,6 +141,19 @@ struct TdEgnnLayer {
     const float *nb1, *nb2;
 };
 
+// One EnBaseLayer of the binding-affinity encoder (models/property_pred/prop_egnn.py:8-45), packed by td_prop_create
+constexpr int TD_PROP_H = 256;         // hidden width the prop kernels are built for
+constexpr int TD_PROP_G = 64;          // Gaussians of the edge feature
+constexpr int TD_PROP_ACT_NONE = 0, TD_PROP_ACT_RELU = 1, TD_PROP_ACT_SSP = 2;   // prop_linear_kernel epilogues
+struct TdPropLayer {
+    const float *projW, *projB;   // [512][256] = [edge_mlp.net.0[:, 64:320]; [:, 320:576]], bias [b1 | 0]
+    const float *W1f;             // edge_mlp.net.0[:, 0:64] as 16x16x4 A fragments [ot 16][kb 4][lane] x 4 r
+    const float *W2f;             // edge_mlp.net.2 as A fragments [ot 16][hb 16][lane] x 4 r
+    const float *b2, *winf, *binf;
+    const float *offset;          // GaussianSmearing offsets [64]
+    const float *n1W, *n1b, *n2W, *n2b;   // node_mlp.net.0 [256][512], node_mlp.net.2 [256][256] (row-major, as PyTorch stores them)
+};
+
 struct TdSchedules {       // [T] each
     const float *c0, *ct, *logvar, *log_a, *log_1ma, *log_ca, *log_1mca;
     const float *abar;     // alphas_cumprod of the position schedule; nullptr when the model was created without it
@@ -314,6 +327,16 @@ int td_launch_posterior_step(const TdSchedules &sc, int T, int32_t *step, const 
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s);
 int td_launch_egnn_node(const TdEgnnLayer &L, const float *mi, float *h, int64_t N, hipStream_t s);
+// prop.hip
+int td_launch_prop_linear(const float *X1, int K1, const float *X2, int K2, const float *W, const float *bias, const float *R, float *Y,
+                          int64_t N, int O, int act, hipStream_t s);
+int td_launch_prop_compose(const float *hp, const float *hl, const float *pp, const float *pl, const int32_t *protein_ptr,
+                           const int32_t *ligand_ptr, float *h, float *x, int32_t *node_ptr, int64_t B, hipStream_t s);
+int td_launch_prop_edge(const TdPropLayer &L, const float *x, const int32_t *nbr, int k, const float *P, float *mi, int64_t N,
+                        float coeff, hipStream_t s);
+int td_launch_prop_segment_sum(const float *h, const int32_t *node_ptr, const float *enc_graph, int Eg, float *pre_out, int64_t B,
+                               hipStream_t s);
+int td_launch_prop_select(const float *y, const int64_t *kind, int O, float *out, int64_t B, hipStream_t s);
 // likelihood.hip
 int td_launch_perturb(const TdSchedules &sc, int T, const int32_t *t, const int32_t *lptr, int64_t Nl, int64_t B, int classes,
                       const float *pos, const int64_t *v, const float *noise, const float *uni, float *pos_t, int64_t *v_t,

@@ -132,7 +132,10 @@ size_t td_model_num_weights(const td_config *cfg);      /* expected length of th
  *                            products; 0 = v_mfma_f32_16x16x4_f32 on the fp32 values.  Applies to the value pass
  *                            on every graph and to the key pass on rows of one 32-slot chunk (the default k = 32 graph; the protein rows
  *                            of `hybrid`, k < 32 and capped-radius graphs); the key pass of rows that span several chunks (k > 32, the
- *                            ligand rows of `hybrid`) follows it only while "edge_first_layer_f16" is on (fp32 logits otherwise)
+ *                            ligand rows of `hybrid`) follows it only while "edge_first_layer_f16" is on (fp32 logits otherwise).
+ *                            Both f16 options apply per attention MLP only where the f16 pieces keep its precision: an MLP whose folded
+ *                            LayerNorm scale M (csrc/pack.cpp FoldedMlp) exceeds 2^16, or whose first layer could not take its full power-of-two
+ *                            scale, runs both layers in fp32 whatever these options say ("fold_fp32_mlps")
  *   "h2x_fused"              1 (default): key + value halves of the h2x stage in one launch; 0 = two launches
  *   "session_hop_levels"     1 .. 4 (default 4): receptive-field levels a sampling session prunes the last layers with
  *   "session_forward_reach"  1 (default): layer 1 of a session runs on the ligand's one-hop forward reach only
@@ -141,7 +144,13 @@ size_t td_model_num_weights(const td_config *cfg);      /* expected length of th
  *                            of the batch -- all samples of a pocket carry the same block (scripts/sample_diffusion.py:42) -- found by a hash +
  *                            bitwise comparison at td_session_create; same results bit for bit; 0 = once per graph
  *   "session_step_lists"     1 (default): the row lists of a session step come from one launch (a workgroup per graph);
- *                            0 = the separate list kernels (also used when a graph exceeds 12288 nodes) */
+ *                            0 = the separate list kernels (also used when a graph exceeds 12288 nodes)
+ * Read-only (td_model_get_option; td_model_set_option returns TD_EINVAL): decisions of the LayerNorm fold at td_model_create --
+ *   "fold_dead_units"        LayerNorm units, over every folded MLP (attention MLPs and the edge gate), replaced by their constant relu(beta):
+ *                            those whose largest possible term sqrt(hidden) |weight| max |second-Linear column| is at most 2^-30 of the MLP's
+ *                            largest unit's
+ *   "fold_fp32_mlps"         attention MLPs (hk, hv, xk, xv of every layer) that run both layers in fp32 because the f16 pieces would lose
+ *                            precision there (0 for the seeded and trained-like weight sets of the tests and the benchmark) */
 int td_model_set_option(td_model *m, const char *name, int32_t value);
 int td_model_get_option(const td_model *m, const char *name, int32_t *value);
 

@@ -238,3 +238,77 @@ def trained_like_state_dict(seed: int, gain: float):
         elif '.net.' not in key or key.startswith('refine_net.edge_pred_layer.net.3.'):
             sd[key] = base[key]
     return sd
+
+
+# ------------------------------------------------------------------------------------------ the LayerNorm fold's edges (large M, near-dead units)
+# The five MLPs whose LayerNorm the product folds into the neighbouring Linears (csrc/pack.cpp FoldedMlp): the attention MLPs of every
+# layer and the global edge gate.  The query MLPs (hq_func, xq_func) run node-side with their LayerNorm as it is.
+FOLDED_MLPS = ('.hk_func.', '.hv_func.', '.xk_func.', '.xv_func.', 'refine_net.edge_pred_layer.')
+DEAD_FLOOR = 2.0 ** -30           # the |gamma| floor, relative to the MLP's largest |gamma|, below which the fold used to drop a unit
+
+
+def folded_ln_keys(sd):
+    """(prefix, LayerNorm weight key, LayerNorm bias key, second-Linear weight key) of every folded MLP of ``sd`` (the reference builds
+    an init_h_emb_layer that its forward never calls; the product does not load it)"""
+    out = []
+    for key in sd:
+        if key.endswith('.net.1.weight') and any(t in key for t in FOLDED_MLPS) and '.init_h_emb_layer.' not in key:
+            p = key[:-len('1.weight')]
+            out.append((p, key, p + '1.bias', p + '3.weight'))
+    return out
+
+
+FOLD_SCALE_UNITS = (11, 100)      # the two units per MLP whose bias / |weight| sets the folded scale
+
+
+def fold_scale_state_dict(seed: int, m_target: float, scale_columns: bool = True):
+    """trained_like_state_dict(seed, 4) with, in every folded MLP, units 11 and 100 given LayerNorm weights +-b / m_target and bias b
+    (b = 2, or 4 once 2 / m_target would reach the 2^-30 floor, or m_target / 1e8 beyond 1e11), so that the fold's scale
+    M = (sqrt(128) + max bias / |weight|)(1 + 2^-10) is about m_target while both units stay above the floor.  Above b = 4 the units'
+    second-Linear columns are scaled by 4 / b, so that their constant relu(b) w3[:, n] stays at the size of the others' outputs; their
+    variable term sqrt(128) |gamma_n| max |w3[:, n]| is then ~1e-11, negligible against the MLP's output (at 1e12 the product's fold
+    drops such units as dead -- the round-6 2^-30 floor on |gamma| alone kept them live, at M = 1e12).  With scale_columns=False the
+    units stay live at any M, and their constants (~1e4 x w3[:, n]) saturate the edge gate: an input for the fold's decisions only."""
+    sd = trained_like_state_dict(seed, 4.0)
+    for _, wk, bk, w3k in folded_ln_keys(sd):
+        w, b, w3 = sd[wk].clone(), sd[bk].clone(), sd[w3k].clone()
+        floor = DEAD_FLOOR * float(w.abs().max())
+        beta = 2.0 if 2.0 / m_target > 4 * floor else (4.0 if m_target <= 1e11 else m_target / 1e8)
+        assert beta / m_target > floor, (wk, m_target)
+        for sign, n in zip((1.0, -1.0), FOLD_SCALE_UNITS):
+            w[n], b[n] = sign * beta / m_target, beta
+            if beta > 4.0 and scale_columns:
+                w3[:, n] *= 4.0 / beta
+        sd[wk], sd[bk], sd[w3k] = w.contiguous(), b.contiguous(), w3.contiguous()
+    return sd
+
+
+# unit: (|weight| / (2^-30 max |weight|), sign of the weight, LayerNorm bias, factor on the unit's second-Linear column)
+NEAR_DEAD_UNITS = {
+    20: (0.5, 1.0, 0.0, 1e5),      # below the floor, a large column: relu(gamma c / sigma) w3[:, n] is ~1e-3 of the output
+    21: (0.5, -1.0, 0.0, 1e5),
+    22: (0.5, 1.0, -1.0, 1e5),     # below the floor, a large column, always off
+    40: (2.0, 1.0, 1.0, 1.0),      # above the floor: live, bias / |weight| = 2^29 / max |weight| drives M to ~1e8
+    41: (2.0, -1.0, -1.0, 1e5),    # above the floor, a large column, always off
+    42: (2.0, 1.0, 0.0, 1e5),      # above the floor, a large column: ~4e-3 of the output
+    60: (0.5, 1.0, 1.0, 1.0),      # below the floor with an ordinary column: negligible (~1e-8), its constant relu(1) w3[:, n] stays
+    61: (0.5, -1.0, -1.0, 1.0),    # negligible and off
+}
+NEAR_DEAD_NEGLIGIBLE = (60, 61)
+
+
+def near_dead_state_dict(seed: int):
+    """trained_like_state_dict(seed, 4) with, in every folded MLP, LayerNorm units just below (half) and just above (twice) the floor
+    2^-30 max |weight| of the round-6 fold, with biases -1 / 0 / +1 and second-Linear columns scaled by 1e5 (NEAR_DEAD_UNITS).  A unit
+    with bias 0 and a large column contributes relu(gamma c / sigma) w3[:, n], ~1e-3, without a constant beside it: the fp32 reference
+    resolves it, and a fold that treats the unit as the constant relu(0) = 0 loses it.  (With bias +1 the constant relu(1) w3[:, n] would
+    be ~3e4 and the fp32 reference's own rounding larger than the term.)"""
+    sd = trained_like_state_dict(seed, 4.0)
+    for _, wk, bk, w3k in folded_ln_keys(sd):
+        w, b, w3 = sd[wk].clone(), sd[bk].clone(), sd[w3k].clone()
+        floor = DEAD_FLOOR * float(w.abs().max())
+        for n, (rel, sign, beta, col) in NEAR_DEAD_UNITS.items():
+            w[n], b[n] = sign * rel * floor, beta
+            w3[:, n] *= col
+        sd[wk], sd[bk], sd[w3k] = w.contiguous(), b.contiguous(), w3.contiguous()
+    return sd

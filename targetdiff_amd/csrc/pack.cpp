@@ -30,7 +30,7 @@ namespace tdapi {
 //    compute neither a mean nor a subtraction;
 //  * beta_n / a_n replaces beta, a_n goes into column n of the second Linear, and 1 / sigma (one number per edge) multiplies the
 //    second layer's per-edge result in the consumer (logit, xv, or the attention weight of the aggregation).
-// Exact algebra.
+// Exact algebra (apart from the dead units below).
 // Round 5 -- the ReLU as the FMA's own output clamp.  Dividing by sigma M instead of carrying sigma along,
 //     relu(s_n c_n / sigma + beta_n / a_n) / M = clamp_[0,1](s_n c_n (1 / (sigma M)) + beta_n / (a_n M)),
 // holds whenever the left side never exceeds 1: |c_n| <= sqrt(hid) sigma (the c_n are centred and sigma^2 >= their mean square), so
@@ -39,16 +39,20 @@ namespace tdapi {
 // second Linear instead of a_n), and the kernels keep s_e = 1 / (sigma_e M) per edge only as the FMA's multiplier.
 // Round 6 -- dead units.  beta_n / a_n enters M, and the kernels evaluate rsqrt(sum c^2 * M^2 / hid + eps M^2): a unit with a_n -> 0 and
 // beta_n > 0 used to push M to ~1e19 and the radicand past FLT_MAX (rsqrt(inf) = 0: every activation of the edge silently collapsed to
-// its bias term).  A unit whose |gamma_n| is below 2^-30 of the MLP's largest |gamma| is the constant relu(beta_n) to 1e-8 of the live
-// units' scale (|c_n / sigma| <= sqrt(hid)): its constant goes into the second Linear's bias (b3 += w3[:, n] relu(beta_n)), its column of
-// the second Linear is zero, and its FMA constant is -1 so that the clamp gives exactly 0 (|c_n / (sigma M)| < 1).  Its row of the first
-// Linear stays: LayerNorm's mean and variance run over all hidden units.  Dead units stay out of M, so M <= sqrt(hid) + 2^30 max beta /
-// max |gamma|; td_model_create refuses a model whose M^2 could still overflow the radicand (overflow_risk).
+// its bias term).  Such a unit is replaced by its constant: relu(gamma_n c_n / sigma + beta_n) w3[:, n] differs from relu(beta_n) w3[:, n] by
+// at most d_n = sqrt(hid) |gamma_n| max_o |w3[o, n]| (|c_n / sigma| <= sqrt(hid)), and a unit is DEAD when d_n is at most 2^-30 of the
+// MLP's largest d_m -- what it drops is then below the fp32 rounding of the MLP's output.  (Round 6 tested |gamma_n| alone against 2^-30
+// max |gamma|: a unit under that floor with a second-Linear column of 1e5 moved the output by ~1e-3 and was dropped all the same.)  A dead
+// unit's constant goes into the second Linear's bias (b3 += w3[:, n] relu(beta_n)), its column of the second Linear is zero, and its FMA
+// constant is -1 so that the clamp gives exactly 0 (|c_n / (sigma M)| < 1).  Its row of the first Linear stays: LayerNorm's mean and
+// variance run over all hidden units.  Dead units stay out of M; td_model_create refuses a model whose M^2 could overflow the radicand
+// (overflow_risk), so a live unit with a large beta_n / |gamma_n| is refused, never dropped.
 struct FoldedMlp {
     std::vector<float> w0, b0, g, b, w3, b3v;
     const float *b3;
     float ln_c1 = 1.f / 128.f, ln_c2 = 1e-5f;        // the kernels' variance constants (below)
     int dead_units = 0;
+    double scale = 0.0;                              // M
     bool overflow_risk = false;                      // M^2 * (pre-LayerNorm variance of 1e8) would leave the fp32 range
     // first_scale (round 6, late): the whole first Linear -- every column, the bias -- times 2^first_scale_exp, and ln_c2 times its
     // square: the normalised activations do not change (a power of two goes through every product, sum and the rsqrt exactly: the kernels
@@ -57,17 +61,24 @@ struct FoldedMlp {
     // projections, which therefore have to be in the same units
     int first_scale_exp = 0;
     bool first_scaled = false;
+    bool first_clipped = false;                      // first_scale_exp is below 13 - ilogb(wmax): the radicand needed it smaller
     FoldedMlp(const MlpSrc &m, int in, int hid, int out, bool first_scale = false)
         : w0((size_t)hid * in), b0(hid), g(hid), b(hid), w3((size_t)out * hid), b3v(m.b3, m.b3 + out), b3(nullptr) {
         std::vector<float> sg(hid);
         std::vector<char> dead(hid, 0);
-        double bmax = 0.0, amax = 0.0;
-        for (int n = 0; n < hid; ++n) amax = std::max(amax, (double)fabsf(m.g[n]));
-        const double floor_a = amax * (1.0 / 1073741824.0);          // 2^-30 of the largest |gamma|; amax = 0: every unit is dead
+        std::vector<double> drop(hid);                               // d_n = sqrt(hid) |gamma_n| max_o |w3[o, n]|
+        double bmax = 0.0, dmax = 0.0;
+        for (int n = 0; n < hid; ++n) {
+            double cmax = 0.0;
+            for (int o = 0; o < out; ++o) cmax = std::max(cmax, (double)fabsf(m.w3[(size_t)o * hid + n]));
+            drop[n] = sqrt((double)hid) * (double)fabsf(m.g[n]) * cmax;
+            dmax = std::max(dmax, drop[n]);
+        }
+        const double floor_d = dmax * (1.0 / 1073741824.0);          // 2^-30 of the largest term; dmax = 0: every unit is dead
         for (int n = 0; n < hid; ++n) {
             const double a = (double)fabsf(m.g[n]);
             sg[n] = m.g[n] < 0.f ? -1.f : 1.f;
-            if (!(a > floor_a) || !(a > 1e-30)) {
+            if (!(drop[n] > floor_d) || !(a > 0.0)) {
                 dead[n] = 1;
                 ++dead_units;
                 sg[n] = 1.f;
@@ -82,6 +93,7 @@ struct FoldedMlp {
             if ((double)b[n] > bmax) bmax = (double)b[n];
         }
         const double M = (sqrt((double)hid) + bmax) * (1.0 + 1.0 / 1024.0);
+        scale = M;
         overflow_risk = !(M * M * 1e8 < 3.0e38);
         for (int n = 0; n < hid; ++n) {
             if (dead[n]) continue;
@@ -110,8 +122,10 @@ struct FoldedMlp {
                 for (int k = 0; k < edge_cols; ++k) wmax = std::max(wmax, fabsf(w0[(size_t)n * in + k]));
             int e = (wmax > 0.f && std::isfinite(wmax)) ? 13 - ilogbf(wmax) : 0;
             e = e > 60 ? 60 : (e < -60 ? -60 : e);
+            const int wanted = e;
             while (e > -60 && !(M * M * 1e8 * ldexp(1.0, 2 * e) < 3.0e38)) --e;       // the LayerNorm's radicand stays in range
             first_scale_exp = e;
+            first_clipped = e < wanted;
             first_scaled = true;
             for (float &x : w0) x = ldexpf(x, e);
             for (float &x : b0) x = ldexpf(x, e);
@@ -257,7 +271,17 @@ size_t pack_vec(Packer &pk, const float *v, size_t n, size_t padded) {
     return off;
 }
 
-struct EdgeOff { size_t R, gamma, beta, W2, b2, Walt, R16, Walt16, R16q, R16h = 0; float ln_c1, ln_c2, w2_bound; bool z_plain; };
+struct EdgeOff { size_t R, gamma, beta, W2, b2, Walt, R16, Walt16, R16q, R16h = 0; float ln_c1, ln_c2, w2_bound; bool z_plain, f16_safe; };
+
+// The f16 piece pairs lose precision as M grows: the second layer takes the pieces of z''·2^15 with z'' ~ 1 / M, whose residual piece
+// reaches the f16 subnormal floor (2^-24) and whose first piece follows it below 2^-14 (M > 2^29); and the first layer's table loses the
+// headroom of first_scale_exp once the radicand clips it (M ~ 1e10 and above).  Measured on an MI355X against the float64 reference
+// (tests/test_gpu_fold_edges.py, forward_fold_m*.npz, final_h; the fp32 reference itself is 5e-6 away from float64): with the f16
+// pieces HIP is 4.3e-6 from float64 at M = 1e4, 8.3e-6 at 1e6 (1.1e-5 with the f16 second layer alone: over the tolerance), 6.1e-4 at 1e8,
+// 4.8e-3 at 8e8 and 3.7 at 1e12 (the pieces of z''·2^15 are 0), while the fp32 layers stay at 3.5e-6 .. 4.4e-6 throughout -- an excess of
+// about 6e-12 M.  An attention MLP with M above TD_F16_MAX_M = 2^16 (excess ~4e-7, a tenth of the single-forward tolerance), or whose
+// first_scale_exp was clipped, runs both layers in fp32 (TdEdgeMlp::f16_safe; td_model_get_option "fold_fp32_mlps" counts them).
+constexpr double TD_F16_MAX_M = 65536.0;
 
 EdgeOff pack_edge_mlp(Packer &pk, const FoldedMlp &fm, int in_dim, int out_dim, int alt) {
     const MlpSrc m = fm.src();
@@ -266,6 +290,7 @@ EdgeOff pack_edge_mlp(Packer &pk, const FoldedMlp &fm, int in_dim, int out_dim, 
     // ln_c1 = M^2 / hid: the f16 second layer takes the pieces of z'' ~ 1 / M unscaled while M <= 32 (z'' of a typical unit then sits at
     // 2^-5 or above: 20 bits over the f16 subnormal floor; beyond that the kernels scale by 2^15 first -- td_ln_relu16_pairs_*, edge16.hip)
     o.z_plain = (double)fm.ln_c1 * TD_H <= 32.0 * 32.0;
+    o.f16_safe = fm.scale <= TD_F16_MAX_M && !fm.first_clipped;
     {
         float wmax = 0.f;
         for (size_t t = 0; t < (size_t)out_dim * TD_H; ++t) wmax = std::max(wmax, fabsf(m.w3[t]));
@@ -503,6 +528,7 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
     const FoldedMlp fgate(gate, TD_NG, H, 1);          // LayerNorm folded into the two Linears, like the edge MLPs'
     gate = fgate.src();
     bool fold_overflow = fgate.overflow_risk;
+    int fold_dead = fgate.dead_units;
 
     Packer pk;
     // ---- embeddings (+ node indicator column, models/molopt_score_model.py:336-338)
@@ -558,6 +584,7 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
             const FoldedMlp fhk(hk, KV, H, H, true), fhv(hv, KV, H, H, true);
             hk = fhk.src(); hv = fhv.src();
             fold_overflow = fold_overflow || fhk.overflow_risk || fhv.overflow_risk;
+            fold_dead += fhk.dead_units + fhv.dead_units;
             if (c.ew_net_type != 0) gate_rows(o.ew_x2h, ewx);
             if (ewm) {          // u'_n = sum_o w_m[o] W2v'[o][n] on the FOLDED second Linear (its columns carry |gamma_n|), c = w_m . b2v + b_m
                 o.gate_m = pk.alloc(TD_H + 1);
@@ -592,6 +619,7 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
             const FoldedMlp fxk(xk, KV, H, H, true), fxv(xv, KV, H, c.n_heads, true);
             xk = fxk.src(); xv = fxv.src();
             fold_overflow = fold_overflow || fxk.overflow_risk || fxv.overflow_risk;
+            fold_dead += fxk.dead_units + fxv.dead_units;
             if (c.ew_net_type != 0) gate_rows(o.ew_h2x, ewh);
             o.nh = pack_node_stage(pk, xk, xv, xq, KV);
             o.xk = pack_edge_mlp(pk, fxk, KV, H, 1);
@@ -604,7 +632,7 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
     if (!cur.ok || cur.left != 0) { td_set_error("td_model_create: weight blob layout mismatch"); return TD_EINVAL; }
     if (fold_overflow) {
         td_set_error("td_model_create: an edge MLP's LayerNorm has bias / |weight| beyond 1e15 on a unit that is not negligible "
-                     "(|weight| > 2^-30 of the MLP's largest): the folded form would overflow fp32");
+                     "(sqrt(hidden) |weight| max |second-Linear column| above 2^-30 of the MLP's largest): the folded form would overflow fp32");
         return TD_EINVAL;
     }
     size_t oW0T = pk.alloc((size_t)H * H), ohb0 = pack_vec(pk, vb0, H), oW2T = pk.alloc((size_t)H * TD_MAXC),
@@ -622,6 +650,7 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
     if (!m) { td_set_error("td_model_create: out of host memory"); return TD_ENOMEM; }
     m->cfg = c;
     m->blob_floats = pk.data.size();
+    m->fold_dead_units = fold_dead;
     m->layers = new (std::nothrow) TdLayer[(size_t)L * stage_rows(c)]();
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&m->blob), m->blob_floats * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(m->blob, pk.data.data(), m->blob_floats * sizeof(float), hipMemcpyHostToDevice);
@@ -637,7 +666,9 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
     m->gate = TdGate{D + oGR, D + oGb0, D + oGg, D + oGb, D + oGw3, gate_b3, D + oGoff, gate_coeff, D + oGRp, fgate.ln_c1, fgate.ln_c2, m->opt.edge_key_split != 0};
     auto edge = [&](const EdgeOff &o, bool split = false) {
         return TdEdgeMlp{D + o.R, D + o.gamma, D + o.beta, D + o.W2, D + o.b2, D + o.R16, D + o.Walt16, D + o.Walt,
-                         D + o.R16q, o.R16h ? D + o.R16h : nullptr, o.ln_c1, o.ln_c2, o.w2_bound, m->opt.edge_second_layer_f16 != 0, m->opt.edge_first_layer_f16 != 0 && o.R16h != 0, o.z_plain, split && m->opt.edge_key_split != 0, m->opt.edge_row_dealing};
+                         D + o.R16q, o.R16h ? D + o.R16h : nullptr, o.ln_c1, o.ln_c2, o.w2_bound, m->opt.edge_second_layer_f16 != 0 && o.f16_safe,
+                         m->opt.edge_first_layer_f16 != 0 && o.R16h != 0 && o.f16_safe, o.z_plain, split && m->opt.edge_key_split != 0,
+                         m->opt.edge_row_dealing, o.f16_safe};
     };
     auto node = [&](const NodeOff &o) {
         return TdNodeStage{D + o.projB, D + o.projBias, D + o.qGamma, D + o.qBeta, D + o.q3B, D + o.q3Bias, D + o.projB3, D + o.q3B3,
@@ -650,6 +681,7 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
         if (lo[l].has_x) {
             Ly.nodeX2h = node(lo[l].nx);
             Ly.hk = edge(lo[l].hk, true); Ly.hv = edge(lo[l].hv, true);
+            m->fold_fp32_mlps += !lo[l].hk.f16_safe + !lo[l].hv.f16_safe;
             Ly.ew_x2h = c.ew_net_type != 0 ? D + lo[l].ew_x2h : nullptr;
             Ly.gate_m = c.ew_net_type == 3 ? D + lo[l].gate_m : nullptr;
             if (c.x2h_out_fc) Ly.nodeOut = TdNodeOut{D + lo[l].noB, D + lo[l].nob1, D + lo[l].nog, D + lo[l].nobeta, D + lo[l].nob2};
@@ -657,6 +689,7 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
         if (lo[l].has_h) {
             Ly.nodeH2x = node(lo[l].nh);
             Ly.xk = edge(lo[l].xk, true); Ly.xv = edge(lo[l].xv, true);
+            m->fold_fp32_mlps += !lo[l].xk.f16_safe + !lo[l].xv.f16_safe;
             Ly.ew_h2x = c.ew_net_type != 0 ? D + lo[l].ew_h2x : nullptr;
         }
     }
@@ -702,23 +735,22 @@ extern "C" int td_model_set_option(td_model *m, const char *name, int32_t value)
         }
     } else if (strcmp(name, "edge_first_layer_f16") == 0) {
         m->opt.edge_first_layer_f16 = value != 0;
-        for (int l = 0; l < m->cfg.num_layers * stage_rows(m->cfg); ++l) {
-            m->layers[l].hk.l1_f16 = m->layers[l].hk.R16h && value != 0;
-            m->layers[l].hv.l1_f16 = m->layers[l].hv.R16h && value != 0;
-            m->layers[l].xk.l1_f16 = m->layers[l].xk.R16h && value != 0;
-            m->layers[l].xv.l1_f16 = m->layers[l].xv.R16h && value != 0;
-        }
+        for (int l = 0; l < m->cfg.num_layers * stage_rows(m->cfg); ++l)
+            for (TdEdgeMlp *e : {&m->layers[l].hk, &m->layers[l].hv, &m->layers[l].xk, &m->layers[l].xv}) e->l1_f16 = e->R16h && e->f16_safe && value != 0;
     } else if (strcmp(name, "edge_second_layer_f16") == 0) {
         m->opt.edge_second_layer_f16 = value != 0;
         for (int l = 0; l < m->cfg.num_layers * stage_rows(m->cfg); ++l)
-            m->layers[l].hk.l2_f16 = m->layers[l].hv.l2_f16 = m->layers[l].xk.l2_f16 = m->layers[l].xv.l2_f16 = value != 0;
+            for (TdEdgeMlp *e : {&m->layers[l].hk, &m->layers[l].hv, &m->layers[l].xk, &m->layers[l].xv}) e->l2_f16 = e->f16_safe && value != 0;
     } else if (strcmp(name, "session_hop_levels") == 0) {
         if (value < 1 || value > TD_HOP_LEVELS) { td_set_error("td_model_set_option: session_hop_levels must be 1..%d", TD_HOP_LEVELS); return TD_EINVAL; }
         m->opt.session_hop_levels = value;
     } else if (strcmp(name, "session_forward_reach") == 0) m->opt.session_forward_reach = value != 0;
     else if (strcmp(name, "session_step_lists") == 0) m->opt.session_step_lists = value != 0;
     else if (strcmp(name, "session_share_pockets") == 0) m->opt.session_share_pockets = value != 0;
-    else { td_set_error("td_model_set_option: unknown option '%s'", name); return TD_EINVAL; }
+    else if (strcmp(name, "fold_dead_units") == 0 || strcmp(name, "fold_fp32_mlps") == 0) {
+        td_set_error("td_model_set_option: '%s' is read-only (a decision of the LayerNorm fold at td_model_create)", name);
+        return TD_EINVAL;
+    } else { td_set_error("td_model_set_option: unknown option '%s'", name); return TD_EINVAL; }
     ++m->option_epoch;          // sessions re-capture their step graph (the captured nodes copied the old variants' arguments by value)
     return TD_OK;
 }
@@ -737,6 +769,8 @@ extern "C" int td_model_get_option(const td_model *m, const char *name, int32_t 
     else if (strcmp(name, "session_forward_reach") == 0) *value = m->opt.session_forward_reach;
     else if (strcmp(name, "session_step_lists") == 0) *value = m->opt.session_step_lists;
     else if (strcmp(name, "session_share_pockets") == 0) *value = m->opt.session_share_pockets;
+    else if (strcmp(name, "fold_dead_units") == 0) *value = m->fold_dead_units;
+    else if (strcmp(name, "fold_fp32_mlps") == 0) *value = m->fold_fp32_mlps;
     else { td_set_error("td_model_get_option: unknown option '%s'", name); return TD_EINVAL; }
     return TD_OK;
 }

@@ -73,6 +73,8 @@ struct TdEdgeMlp {
     bool use_split;        // run the first layer on the piece triples where a kernel has that variant (model option "edge_key_split")
     int deal_rows;         // x2h passes: rows dealt round-robin inside an XCD's range (model option "edge_row_dealing": 0 contiguous
                            // shares, 1 dealt, 2 dealt + the workgroup's rows handed to its waves through an LDS counter)
+    bool f16_safe;         // pack time: the f16 piece pairs keep this MLP's precision (folded scale M <= TD_F16_MAX_M, first_scale_exp
+                           // not clipped; pack.cpp); false: l1_f16 and l2_f16 stay off whatever the model options say
 };
 
 // Node-side weights of one stage (x2h or h2x): 4 projections (k_i,k_j,v_i,v_j) + the query MLP.
@@ -194,6 +196,8 @@ struct td_model {
     TdHead head;
     TdSchedules sched;
     unsigned option_epoch = 0;   // bumped by td_model_set_option: sessions drop a step graph captured under older options
+    int fold_dead_units = 0;     // LayerNorm units the fold replaced by their constant, over every folded MLP (read-only option "fold_dead_units")
+    int fold_fp32_mlps = 0;      // attention MLPs kept off the f16 piece pairs by TdEdgeMlp::f16_safe (read-only option "fold_fp32_mlps")
 };
 
 // ---- kernel launchers (each defined next to its kernels) --------------------------------------------

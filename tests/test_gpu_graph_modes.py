@@ -421,7 +421,8 @@ def test_sampling_with_fp32_second_layer(state_dict, cfg, opt):
     (the radial / type first layer of the x2h passes on the exact bf16 piece triples instead of f16 piece pairs) stay tested paths: 5 reverse
     steps through the session and the stateless forward against the default -- same types, positions within the sampling tolerance, session ==
     stateless bit for bit under either setting.  On the default graph, on a `hybrid` graph (protein rows through the default graph's kernels,
-    ligand rows through the chunk walk) and at k = 48 (chunk walk: the value pass follows the option, the key pass is fp32 either way).  (That
+    ligand rows through the chunk walk) and at k = 48 (chunk walk: the value pass follows the option; the key pass takes f16 logits only while
+    edge_first_layer_f16 and edge_second_layer_f16 are both on, fp32 logits otherwise -- TD_KEY_LAUNCH_WALK, edge16.hip).  (That
     the option is live -- the two settings do not produce identical features -- is asserted in
     tests/test_gpu_weight_regimes.py::test_forward_weight_regimes_vs_reference.)"""
     from oracle import draws

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- ligands/sec of the TargetDiff denoising hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c1|c5|c4] [--no-cpu-baseline] [--no-full-run]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c1|c5|c4] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-full-run] [--no-sweep] [--no-stateless]]
 
 `--gpus N` with no launcher around the script (no RANK / WORLD_SIZE in the environment) starts the N ranks itself, one
 process per GPU (targetdiff_amd/launch.py; the environment each rank sees is the one `python -m torch.distributed.run
@@ -20,11 +20,17 @@ the rate at which finished ligands leave a 1000-step sampler.  With N > 1 (torch
 rank per GPU over RCCL) every rank samples its own pocket replica -- pockets shard with no data-path
 collective (scripts/batch_sample_diffusion.sh:15-20) -- so scaling is "weak".
 
+A plain run does what the headline figure needs and no more: it sets up, warms up, times the K steps, writes the
+outputs if `--dump-outputs` is given and prints the JSON line.  Everything else the benchmark measures runs only with
+`--full`: the roofline leg (further steps of the same run with HIP events around the x2h launches), the stateless floor,
+the geometry sweep and the complete 1000-step run (c2, N = 1), the CPU baseline.  The `--no-*` switches leave single legs
+of `--full` out; `--profile-all`, `--initial-state` and `--cpu-full` ask for a figure of their own and imply `--full`.
+
 `--dump-outputs DIR` writes what the last of the K timed steps computed -- the ligand positions (de-centred), atom types and log type
 distributions a caller of the sampler receives for that step -- as DIR/<name>.npy (float32, at most 64 MB).  Weights, inputs and the
 sampler's draws are seeded, so two builds run with the same arguments can be compared output for output.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line of a `--full` run (a plain run reports `roofline` as null):
   roofline     dominant kernel = edge_value16t_kernel (x2h value pass; the key pass edge_key16_kernel is its twin and is
                reported under roofline.key_pass);
                achieved = executed algorithmic FLOPs per launch (327,680 per dst node) / mean
@@ -495,21 +501,23 @@ def main():
     ap.add_argument('--workload', default='c2', choices=['c1', 'c2', 'c3', 'c4', 'c5'])
     ap.add_argument('--batch-size', type=int, default=0, help='c4: samples per batch of a pocket (0 = all 100 in one batch; scripts/batch_sample_diffusion.sh '
                     'runs BATCH_SIZE=50, the signature of sample_diffusion_ligand defaults to 16); the batches of a pocket run one after the other')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also measure what the headline figure does not need: the roofline leg, the '
+                    'stateless floor, the geometry sweep and the complete 1000-step run (c2, N = 1), the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--cpu-full', action='store_true', help='time the CPU baseline on BASELINE config 1 in full (4 samples x 100 '
-                    'steps, ~2-5 min of host time) instead of the bounded sample')
-    ap.add_argument('--no-full-run', action='store_true', help='skip the complete 1000-step sample_diffusion_ligand call (c2, N = 1)')
-    ap.add_argument('--profile-all', action='store_true', help='time every kernel class, print a breakdown to stderr')
+                    'steps, ~2-5 min of host time) instead of the bounded sample; implies --full')
+    ap.add_argument('--no-full-run', action='store_true', help='--full without the complete 1000-step sample_diffusion_ligand call (c2, N = 1)')
+    ap.add_argument('--profile-all', action='store_true', help='time every kernel class, print a breakdown to stderr; implies --full')
     ap.add_argument('--ligand-spread', type=float, default=LIGAND_SPREAD,
                     help='per-coordinate std (A) of the ligand cloud the timed steps start from; 1.0 = the sampler\'s '
                          'initial state N(0, I) (see --initial-state)')
     ap.add_argument('--initial-state', action='store_true',
-                    help='after the timed region, also time 10 steps from the sampler\'s initial state N(0, I)')
-    ap.add_argument('--no-sweep', action='store_true', help='skip the geometry sweep (c2, N = 1): the session\'s step time at ligand clouds of 1 / 2 / '
+                    help='after the timed region, also time 10 steps from the sampler\'s initial state N(0, I); implies --full')
+    ap.add_argument('--no-sweep', action='store_true', help='--full without the geometry sweep (c2, N = 1): the session\'s step time at ligand clouds of 1 / 2 / '
                     '3 / 4 A and at the docked pose of the reference\'s example ligand')
     ap.add_argument('--no-graph', action='store_true', help='issue the launches of a step one by one instead of replaying the captured hipGraph')
     ap.add_argument('--no-session', action='store_true', help='stateless td_model_forward per step (no static-protein caching)')
-    ap.add_argument('--no-stateless', action='store_true', help='skip the 10 stateless steps reported as stateless_ms_per_step')
+    ap.add_argument('--no-stateless', action='store_true', help='--full without the 10 stateless steps reported as stateless_ms_per_step')
     ap.add_argument('--knn', type=int, default=32, help='fan-in of the k-NN / hybrid graph (C5 sweep: 16, 32, 48, 64)')
     ap.add_argument('--cutoff-mode', default='knn', choices=['knn', 'hybrid', 'radius'])
     ap.add_argument('--radius', type=float, default=6.0, help='cut-off (A) of --cutoff-mode radius')
@@ -520,6 +528,7 @@ def main():
                     help='after the timed steps, write what their last step computed (ligand positions, types, log type distributions) '
                          'as DIR/<name>.npy, float32, at most 64 MB')
     args = ap.parse_args()
+    args.full = args.full or args.profile_all or args.initial_state or args.cpu_full
     # `--gpus N` without a launcher: become the launcher (N ranks of this same command line), exit with their status
     launch.self_spawn_if_needed(args.gpus)
 
@@ -565,6 +574,7 @@ def main():
     n_nodes = int(batch.protein_pos.shape[0] + lpos.shape[0])
     n_lig = int(lpos.shape[0])
     max_nodes = max(p.num_atoms for p in pockets) + max(sizes)
+    # the roofline leg's steps stay in the run's length with or without --full: the time steps of the timed region depend on it
     args.prof_steps = max(1, min(args.steps, 10))
     total = args.warmup + args.steps + args.prof_steps
     if total > 1000:
@@ -591,11 +601,13 @@ def main():
     # launch stream (td_profile_begin / td_profile_end); their launch times feed `roofline`, not `value`
     classes = capi.PROFILE_CLASSES if args.profile_all else ('x2h_k', 'x2h_v')
     prof_steps = args.prof_steps
-    capi.profile_begin(classes)
-    for _ in range(prof_steps):
-        sampler.step()
-    torch.cuda.synchronize()
-    prof = capi.profile_end()
+    prof = None
+    if args.full:
+        capi.profile_begin(classes)
+        for _ in range(prof_steps):
+            sampler.step()
+        torch.cuda.synchronize()
+        prof = capi.profile_end()
     my_elapsed = elapsed
     if distributed:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -706,7 +718,7 @@ def main():
     else:
         vk = 'edge_value16_kernel<true, true, false, L2, FL> (chunk-walking)' if split else 'edge_value16_kernel<false, true> (chunk-walking)'
         kk = 'edge_key16_kernel<false, 12, 0, 1, true, L2, FL> (chunk-walking)' if split else 'edge_key16_kernel<false, 16, 0, 1, false>'
-    roofline = pass_roofline('x2h_v', vk + ' (x2h value pass)', 'traffic_x2h_value.json')
+    roofline = pass_roofline('x2h_v', vk + ' (x2h value pass)', 'traffic_x2h_value.json') if prof is not None else None
     if roofline is not None:
         roofline['key_pass'] = pass_roofline('x2h_k', kk + ' (x2h key pass)', 'traffic_x2h_key.json')
     # whole step: FLOPs the launched kernels execute (from the row lists) against the fp32 peak, next to SURVEY 8d's algorithmic
@@ -770,7 +782,7 @@ def main():
         n0, d0, lv0c = s0.session.row_counts()
         out['initial_state'] = {'ligand_spread': 1.0, 'ms_per_step': ms0, 'value': world * graphs / ms0, 'steps': 10,
                                 'session_rows': {'nodes': n0, 'layer0_rows': d0, 'receptive_field_levels': lv0c}}
-    if world == 1 and sampler.session is not None and not args.no_stateless:
+    if args.full and world == 1 and sampler.session is not None and not args.no_stateless:
         ms_floor = stateless_floor(model, batch, lpos, lv, max_nodes)
         out['stateless_ms_per_step'] = ms_floor
         out['stateless_value'] = graphs / ms_floor
@@ -784,11 +796,11 @@ def main():
                     print(f'  {k:10s} {v["ms"] / prof_steps:9.3f} ms/step  ({v["launches"] // prof_steps} launches/step)',
                           file=sys.stderr)
         # a complete run the driver's own clock can witness: outside the timed region, the 20-step line above is unchanged
-        if world == 1 and args.workload == 'c2' and not args.no_sweep and not args.no_session and default_graph:
+        if args.full and world == 1 and args.workload == 'c2' and not args.no_sweep and not args.no_session and default_graph:
             out['geometry_sweep'] = geometry_sweep(model, pockets[0], sizes, dev)
-        if world == 1 and args.workload == 'c2' and not args.no_full_run and not args.no_session and default_graph:
+        if args.full and world == 1 and args.workload == 'c2' and not args.no_full_run and not args.no_session and default_graph:
             out['full_run'] = full_run(model, pockets[0], sizes, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.cpu_full:
                 c1p, c1n, c1s, _ = make_workload('c1', 0)
                 out['cpu_baseline'] = cpu_baseline(c1p[0], c1s, samples=c1n, steps=100, extrapolate=False)

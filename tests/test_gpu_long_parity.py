@@ -517,7 +517,8 @@ def test_overlapped_batches_equal_sequential_batches(model):
 
 def test_bench_through_the_launcher_initialises_rccl(tmp_path):
     """`bench.py` started by targetdiff_amd.launch (the way `--gpus N` starts N ranks) on this box's single GPU: a world of
-    one rank still goes through dist.init_process_group('nccl'), the barrier and the max-reduction, and prints one JSON line."""
+    one rank still goes through dist.init_process_group('nccl'), the barrier and the max-reduction, and prints one JSON line
+    (with `--full`, whose roofline leg runs on the same process group)."""
     import json
     import os
     import subprocess
@@ -526,12 +527,39 @@ def test_bench_through_the_launcher_initialises_rccl(tmp_path):
     _dev()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = launch.rank_env(0, 1, launch.free_port())
-    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--full',
                         '--no-cpu-baseline', '--no-full-run', '--workload', 'c1'], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith('{')][-1]
     d = json.loads(line)
     assert d['n_gpus'] == 1 and d['value'] > 0 and d['unit'] == 'ligands/s' and d['roofline'] is not None
+
+
+def test_plain_bench_runs_only_the_headline_and_computes_what_full_computes(tmp_path):
+    """A plain `bench.py` line carries the headline and none of the `--full` legs, and its timed steps compute bit for bit what
+    those of a `--full` run compute (the roofline leg's steps stay in the sampler's length either way)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    _dev()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for name, extra in (('plain', []), ('full', ['--full', '--no-cpu-baseline'])):
+        p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--workload',
+                            'c1', '--dump-outputs', str(tmp_path / name)] + extra, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines[name] = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][-1])
+    plain, full = lines['plain'], lines['full']
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in plain
+    assert plain['roofline'] is None and full['roofline'] is not None
+    assert 'stateless_ms_per_step' not in plain and 'stateless_ms_per_step' in full
+    assert not {'cpu_baseline', 'geometry_sweep', 'full_run', 'initial_state'} & set(plain)
+    files = sorted(os.listdir(tmp_path / 'plain'))
+    assert files and files == sorted(os.listdir(tmp_path / 'full'))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / 'plain' / f), np.load(tmp_path / 'full' / f)), f
 
 
 def test_c4_bench_and_batch_sample_through_the_launcher_with_the_real_model(tmp_path):

@@ -16,8 +16,8 @@ python tools/small_batch_bench.py --samples 96 --batch-size 16 > $OUT/small_batc
 python tools/small_batch_bench.py --samples 100 --batch-size 50 > $OUT/small_batch_50.json 2>/dev/null
 python bench.py --workload c4 --batch-size 50 > $OUT/bench_c4_1gpu_b50.json 2>/dev/null
 python bench.py --workload c4 > $OUT/bench_c4_1gpu.json 2>/dev/null
-python bench.py --workload c5 --no-cpu-baseline --knn 64 > $OUT/bench_c5_knn64.json 2>/dev/null
-python bench.py --workload c5 --no-cpu-baseline --cutoff-mode hybrid > $OUT/bench_c5_hybrid.json 2>/dev/null
+python bench.py --full --workload c5 --no-cpu-baseline --knn 64 > $OUT/bench_c5_knn64.json 2>/dev/null
+python bench.py --full --workload c5 --no-cpu-baseline --cutoff-mode hybrid > $OUT/bench_c5_hybrid.json 2>/dev/null
 python bench.py --no-cpu-baseline --no-full-run --no-sweep --no-stateless --option edge_second_layer_f16=0 > $OUT/bench_c2_fp32_second_layer.json 2>/dev/null
 bash tools/prof_general_graphs.sh $OUT > /dev/null 2>&1; cd "${GRAFT_REPO_ROOT:-.}"
 python - <<PY

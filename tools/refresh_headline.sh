@@ -31,9 +31,9 @@ for W in c3 c5; do
   cp profiles/traffic_x2h_value_$W.json profiles/traffic_x2h_key_$W.json $OUT/ 2>/dev/null
   rm -rf $OUT/pmc_$W
 done
-for W in c1 c3 c5; do python bench.py --workload $W --no-cpu-baseline > $OUT/bench_$W.json 2>/dev/null; done
-python bench.py --workload c5 --no-cpu-baseline --knn 48 > $OUT/bench_c5_knn48.json 2>/dev/null
-python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+for W in c1 c3 c5; do python bench.py --full --workload $W --no-cpu-baseline > $OUT/bench_$W.json 2>/dev/null; done
+python bench.py --full --workload c5 --no-cpu-baseline --knn 48 > $OUT/bench_c5_knn48.json 2>/dev/null
+python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err
 python - <<PY || exit 1
 import json, sys
 sys.path.insert(0, '.')

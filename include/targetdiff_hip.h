@@ -268,6 +268,37 @@ int td_prop_forward(const td_prop *m, const float *d_protein_pos, const float *d
                     const int64_t *d_output_kind, int32_t max_graph_nodes, float *d_out, float *d_h_layers, float *d_final_h,
                     int32_t *d_out_nbr, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- training the binding-affinity predictor (prop_model.py get_loss, then loss.backward()): gradients with respect to every
+ *      parameter; positions and input features are constants.
+ *      td_prop_train_workspace_bytes: one device buffer that holds td_prop_forward's workspace, the tape td_prop_backward reads
+ *      (per layer the input h, mi and t = ReLU(node_mlp.net.0 pre-activation): 3 x 1 KB per node and layer) and the backward's
+ *      scratch, which materialises per-edge tensors (a, dz2, dz1 [N*knn][256], rbf [N*knn][64], q [N*knn]): about 156 KB per node
+ *      at knn 48.
+ *      td_prop_forward_train: td_prop_forward's inputs (no optional outputs) plus that workspace; d_out equals td_prop_forward's bit
+ *      for bit.  Fills *tape, a host-side record; the tape's data stay in the workspace until the next forward on it.
+ *      td_prop_backward: d_grad_out shaped like d_out; overwrites d_grad_weights [td_prop_num_weights] in host_weights order (the
+ *      distance_expansion.offset slot, a buffer, is written as zeros).  Refuses a tape recorded by another handle, at another
+ *      (N_p, N_l, B), or before a later td_prop_set_weights.  No float atomics: reruns are bit-identical.
+ *      td_prop_set_weights: d_weights [td_prop_num_weights] in host_weights order, on the device; re-packs on the device, ordered on
+ *      `stream`.  The offsets are copied; the Gaussian coefficient stays the one td_prop_create derived from them. */
+typedef struct td_prop_tape {
+    const td_prop *model;
+    uint64_t weights_version;
+    int64_t N_p, N_l, B;
+    int32_t has_output_kind, has_enc_node;
+    void *d_workspace;
+    size_t workspace_bytes;
+} td_prop_tape;
+size_t td_prop_train_workspace_bytes(const td_prop *m, int64_t N_p, int64_t N_l, int64_t B);
+int td_prop_forward_train(const td_prop *m, const float *d_protein_pos, const float *d_protein_feat, const int32_t *d_protein_ptr,
+                          int64_t N_p, const float *d_ligand_pos, const float *d_ligand_feat, const int32_t *d_ligand_ptr,
+                          int64_t N_l, int64_t B, const float *d_enc_ligand, const float *d_enc_node, const float *d_enc_graph,
+                          const int64_t *d_output_kind, int32_t max_graph_nodes, float *d_out, void *d_workspace,
+                          size_t workspace_bytes, td_prop_tape *tape, void *stream);
+int td_prop_backward(const td_prop *m, const td_prop_tape *tape, int64_t N_p, int64_t N_l, int64_t B, const float *d_grad_out,
+                     float *d_grad_weights, size_t num_weights, void *stream);
+int td_prop_set_weights(td_prop *m, const float *d_weights, size_t num_weights, void *stream);
+
 /* ---- other consumers of the denoiser (scripts/likelihood_est_diffusion.py; ScorePosNet3D.forward(return_all=True)).
  * They need the 8th schedule array (alphas_cumprod of the position schedule) at td_model_create.
  *

@@ -30,6 +30,12 @@ class TdConfig(ctypes.Structure):
                 ('x2h_out_fc', c_int32), ('sync_twoup', c_int32), ('num_x2h', c_int32), ('num_h2x', c_int32), ('reserved', c_int32 * 1)]
 
 
+class TdPropTape(ctypes.Structure):
+    """td_prop_tape of include/targetdiff_hip.h: host-side record of a td_prop_forward_train"""
+    _fields_ = [('model', c_void_p), ('weights_version', ctypes.c_uint64), ('N_p', c_int64), ('N_l', c_int64), ('B', c_int64),
+                ('has_output_kind', c_int32), ('has_enc_node', c_int32), ('d_workspace', c_void_p), ('workspace_bytes', c_size_t)]
+
+
 class TdPropConfig(ctypes.Structure):
     """td_prop_config of include/targetdiff_hip.h"""
     _fields_ = [('hidden_dim', c_int32), ('num_layers', c_int32), ('knn', c_int32), ('num_r_gaussian', c_int32), ('cutoff', c_float),
@@ -79,6 +85,11 @@ SIGNATURES = {
     'td_prop_workspace_bytes': (ctypes.c_size_t, [_P, c_int64, c_int64, c_int64]),
     'td_prop_forward': (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int32, _P, _P, _P, _P,
                                   _P, ctypes.c_size_t, _P]),
+    'td_prop_train_workspace_bytes': (ctypes.c_size_t, [_P, c_int64, c_int64, c_int64]),
+    'td_prop_forward_train': (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int32, _P, _P,
+                                        ctypes.c_size_t, _P, _P]),
+    'td_prop_backward': (c_int32, [_P, _P, c_int64, c_int64, c_int64, _P, _P, ctypes.c_size_t, _P]),
+    'td_prop_set_weights': (c_int32, [_P, _P, ctypes.c_size_t, _P]),
     'td_session_create': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int32, _P, POINTER(c_void_p)]),
     'td_session_destroy': (None, [_P]),
     'td_session_forward': (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P]),
@@ -744,3 +755,52 @@ class NativeProp:
             opt(enc_graph, torch.float32, 'enc_graph_feature', B, c.enc_graph_dim), kind, max_graph_nodes, _ptr(out),
             _ptr(h_layers), _ptr(final_h), _ptr(nbr), _ptr(self._ws), self._ws.numel(), _stream(self.device)), 'td_prop_forward')
         return out, h_layers, final_h, nbr
+
+    def num_weights(self) -> int:
+        return int(self.lib.td_prop_num_weights(ctypes.byref(self.cfg)))
+
+    @_device_bound
+    def set_weights(self, flat: torch.Tensor):
+        """Re-pack the weights from ``flat`` (device, fp32, prop_flat_key_order) on the device (td_prop_set_weights)."""
+        _check(self.lib.td_prop_set_weights(self.handle, _ptr(flat, torch.float32, 'weights'), flat.numel(), _stream(self.device)),
+               'td_prop_set_weights')
+
+    @_device_bound
+    def forward_train(self, protein_pos, protein_feat, protein_ptr, ligand_pos, ligand_feat, ligand_ptr, output_kind=None,
+                      enc_ligand=None, enc_node=None, enc_graph=None, max_graph_nodes=0):
+        """td_prop_forward_train: as ``forward`` (no optional outputs); returns (out, tape).  The tape owns its workspace tensor, so
+        any number of tapes can wait for their backward."""
+        Np, Nl, B = protein_pos.shape[0], ligand_pos.shape[0], protein_ptr.numel() - 1
+        N, dev, c = Np + Nl, protein_pos.device, self.cfg
+        out = torch.empty(B, 1 if output_kind is not None else c.output_dim, dtype=torch.float32, device=dev)
+        ws = torch.empty(int(self.lib.td_prop_train_workspace_bytes(self.handle, Np, Nl, B)), dtype=torch.uint8, device=dev)
+
+        def opt(t, what, rows, cols):
+            if t is None:
+                return None
+            if tuple(t.shape) != (rows, cols):
+                raise ValueError(f'{what}: expected shape {(rows, cols)}, got {tuple(t.shape)}')
+            return _ptr(t, torch.float32, what)
+        kind = None
+        if output_kind is not None:
+            if tuple(output_kind.shape) != (B,):
+                raise ValueError(f'output_kind: expected shape {(B,)}, got {tuple(output_kind.shape)}')
+            kind = _ptr(output_kind, torch.int64, 'output_kind')
+        tape = TdPropTape()
+        _check(self.lib.td_prop_forward_train(
+            self.handle, _ptr(protein_pos, torch.float32, 'protein_pos'), _ptr(protein_feat, torch.float32, 'protein_feat'),
+            _ptr(protein_ptr, torch.int32, 'protein_ptr'), Np, _ptr(ligand_pos, torch.float32, 'ligand_pos'),
+            _ptr(ligand_feat, torch.float32, 'ligand_feat'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
+            opt(enc_ligand, 'enc_ligand_feature', Nl, c.enc_ligand_dim), opt(enc_node, 'enc_node_feature', N, c.enc_node_dim),
+            opt(enc_graph, 'enc_graph_feature', B, c.enc_graph_dim), kind, max_graph_nodes, _ptr(out), _ptr(ws), ws.numel(),
+            ctypes.byref(tape), _stream(self.device)), 'td_prop_forward_train')
+        return out, (tape, ws, (Np, Nl, B))
+
+    @_device_bound
+    def backward(self, tape, grad_out: torch.Tensor) -> torch.Tensor:
+        """td_prop_backward: the gradient of every weight, flat in prop_flat_key_order (the offset slot is zero)."""
+        rec, ws, (Np, Nl, B) = tape
+        grad = torch.empty(self.num_weights(), dtype=torch.float32, device=self.device)
+        _check(self.lib.td_prop_backward(self.handle, ctypes.byref(rec), Np, Nl, B, _ptr(grad_out, torch.float32, 'grad_out'),
+                                         _ptr(grad), grad.numel(), _stream(self.device)), 'td_prop_backward')
+        return grad

@@ -147,6 +147,8 @@ struct TdEgnnLayer {
 constexpr int TD_PROP_H = 256;         // hidden width the prop kernels are built for
 constexpr int TD_PROP_G = 64;          // Gaussians of the edge feature
 constexpr int TD_PROP_ACT_NONE = 0, TD_PROP_ACT_RELU = 1, TD_PROP_ACT_SSP = 2;   // prop_linear_kernel epilogues
+constexpr int TD_PROP_EPI_NONE = 0, TD_PROP_EPI_RELU_MASK = 1, TD_PROP_EPI_SSP_DERIV = 2;   // prop_bgemm_kernel epilogues
+constexpr int TD_PROP_XTY_CHUNKS = 64; // most split-K chunks of a weight-gradient reduction (prop_bwd.hip)
 struct TdPropLayer {
     const float *projW, *projB;   // [512][256] = [edge_mlp.net.0[:, 64:320]; [:, 320:576]], bias [b1 | 0]
     const float *W1f;             // edge_mlp.net.0[:, 0:64] as 16x16x4 A fragments [ot 16][kb 4][lane] x 4 r
@@ -341,6 +343,23 @@ int td_launch_prop_edge(const TdPropLayer &L, const float *x, const int32_t *nbr
 int td_launch_prop_segment_sum(const float *h, const int32_t *node_ptr, const float *enc_graph, int Eg, float *pre_out, int64_t B,
                                hipStream_t s);
 int td_launch_prop_select(const float *y, const int64_t *kind, int O, float *out, int64_t B, hipStream_t s);
+// prop_bwd.hip
+int td_launch_prop_bgemm(const float *X1, int ldx1, int K1, const float *X2, int ldx2, int K2, const float *W, int ldw, int trans,
+                         const float *M, int ldm, int epi, const float *R1, int ldr1, const float *R2, int ldr2, float *Y, int ldy,
+                         int64_t N, int O, hipStream_t s);
+int td_prop_xty_chunks(int64_t N);
+int td_launch_prop_xty(const float *A, int lda, int O, const float *B1, int ldb1, int K1, const float *B2, int ldb2, int K2, int64_t N,
+                       float *part, float *G, int ldg, int col0, hipStream_t s);
+int td_launch_prop_edge_bwd(const TdPropLayer &L, const float *W2Tf, const float *x, const int32_t *nbr, int k, const float *P,
+                            const float *dmi, int64_t N, float coeff, float *Ae, float *DZ2, float *DZ1, float *RBF, float *Q, float *S,
+                            float *DWP, hipStream_t s);
+int td_launch_prop_radj(const int32_t *nbr, int64_t N, int k, int32_t *cnt, int32_t *ptr, int32_t *idx, hipStream_t s);
+int td_launch_prop_gather(const float *X, const int32_t *ptr, const int32_t *idx, float *out, int64_t N, hipStream_t s);
+int td_launch_prop_select_bwd(const float *gout, const int64_t *kind, int O, float *dy, int64_t B, hipStream_t s);
+int td_launch_prop_broadcast(const float *dpre, const int32_t *node_ptr, float *dh, int64_t B, hipStream_t s);
+int td_launch_prop_uncompose(const float *dh, const int32_t *protein_ptr, const int32_t *ligand_ptr, float *dhp, float *dhl, int64_t B,
+                             hipStream_t s);
+int td_launch_prop_pack_afrag(const float *W, int ld, int col0, int kb_count, int trans, float *out, hipStream_t s);
 // likelihood.hip
 int td_launch_perturb(const TdSchedules &sc, int T, const int32_t *t, const int32_t *lptr, int64_t Nl, int64_t B, int classes,
                       const float *pos, const int64_t *v, const float *noise, const float *uni, float *pos_t, int64_t *v_t,

@@ -6,6 +6,11 @@ Built for what configs/prop/*.yml give: hidden 256, 64 Gaussians, ReLU, no Layer
 update_x=False), edge_dim 0, k <= 64, any number of layers and any enc_ligand_dim / enc_node_dim / enc_graph_dim >= 0.  Anything
 else raises NotImplementedError.  There is no CPU path.
 
+Training: ``get_loss`` (prop_model.py:76-95, 167-212) and ``forward(..., differentiable=True)`` run td_prop_forward_train and, on
+``backward()``, td_prop_backward, which hands every parameter its gradient; the optimizer is torch's.  Gradients flow to parameters
+only: an input that requires grad raises NotImplementedError.  After ``optimizer.step()`` the next call re-packs the weights on the
+device (td_prop_set_weights) instead of building a new handle.
+
 Composed order (compose_context_prop, models/common.py:140-153, argsorts the concatenated batch vector): the project's rule is the
 stable one -- per complex its protein atoms, then its ligand atoms, each in input order; unsorted batch vectors are handled the same
 way.  Only the k-NN tie rule (ascending (d^2, index)) and the order of floating-point sums depend on it.
@@ -138,19 +143,49 @@ class _PropBase(nn.Module):
                     ligand_feat_dim=self.ligand_atom_feature_dim, enc_ligand_dim=self.enc_ligand_dim, enc_node_dim=self.enc_node_dim,
                     enc_graph_dim=self.enc_graph_dim, output_dim=self.output_dim)
 
+    def _flat_keys(self):
+        return capi.prop_flat_key_order(self.encoder.num_layers, self.enc_node_dim)
+
     def native(self, device) -> capi.NativeProp:
+        """The td_prop handle on `device`.  A new handle when the device, a tensor's storage or a buffer changed; when only parameter
+        values changed (an optimizer step), the same handle, re-packed on the device from a device copy of the parameters."""
         device = torch.device(device)
         if device.type != 'cuda':
             raise RuntimeError(f'targetdiff_amd runs on HIP devices only (got {device}); there is no CPU path')
-        key = (str(device),) + tuple((t.data_ptr(), t._version) for t in self.state_dict().values())
+        sd = self.state_dict()
+        named = dict(self.named_parameters())
+        is_param = [k in named for k in sd]
+        key = (str(device),) + tuple((t.data_ptr(), None if p else t._version) for t, p in zip(sd.values(), is_param))
+        versions = tuple(t._version for t, p in zip(sd.values(), is_param) if p)
         if self._native is None or key != self._native_key:
-            self._native = capi.NativeProp(self.native_config(), self.state_dict(), device=device)
-            self._native_key = key
+            self._native = capi.NativeProp(self.native_config(), sd, device=device)
+            self._native_key, self._native_versions = key, versions
+        elif versions != self._native_versions:
+            flat = torch.cat([sd[k].reshape(-1) for k in self._flat_keys()]).to(device=device, dtype=torch.float32).contiguous()
+            self._native.set_weights(flat)
+            self._native_versions = versions
         return self._native
 
-    @torch.no_grad()
+    def _check_inputs(self, tensors):
+        for name, t in tensors.items():
+            if torch.is_tensor(t) and t.requires_grad:
+                raise NotImplementedError(f'{name} requires grad: the HIP affinity predictor gives gradients to its parameters only '
+                                          '(positions and input features are constants)')
+
     def _run(self, protein_pos, protein_atom_feature, ligand_pos, ligand_atom_feature, batch_protein, batch_ligand, output_kind,
-             enc_ligand_feature=None, enc_node_feature=None, enc_graph_feature=None, return_extra=False):
+             enc_ligand_feature=None, enc_node_feature=None, enc_graph_feature=None, return_extra=False, differentiable=False):
+        if differentiable:
+            if return_extra:
+                raise ValueError('return_extra is not available with differentiable=True')
+            self._check_inputs(dict(protein_pos=protein_pos, protein_atom_feature=protein_atom_feature, ligand_pos=ligand_pos,
+                                    ligand_atom_feature=ligand_atom_feature, enc_ligand_feature=enc_ligand_feature,
+                                    enc_node_feature=enc_node_feature, enc_graph_feature=enc_graph_feature))
+        with torch.no_grad():
+            return self._run_native(protein_pos, protein_atom_feature, ligand_pos, ligand_atom_feature, batch_protein, batch_ligand,
+                                    output_kind, enc_ligand_feature, enc_node_feature, enc_graph_feature, return_extra, differentiable)
+
+    def _run_native(self, protein_pos, protein_atom_feature, ligand_pos, ligand_atom_feature, batch_protein, batch_ligand, output_kind,
+                    enc_ligand_feature, enc_node_feature, enc_graph_feature, return_extra, differentiable):
         dev = protein_pos.device
         native = self.native(dev)
         B = int(max(int(batch_protein.max()) if batch_protein.numel() else -1,
@@ -167,6 +202,14 @@ class _PropBase(nn.Module):
             return (t[order] if order is not None else t).contiguous()
         enc_node = f32(enc_node_feature)          # rows in composed order already (the order the library composes in)
         kind = output_kind.to(torch.int64).contiguous() if output_kind is not None else None
+        if differentiable:
+            args = dict(protein_pos=f32(protein_pos, op), protein_feat=f32(protein_atom_feature, op), protein_ptr=pptr,
+                        ligand_pos=f32(ligand_pos, ol), ligand_feat=f32(ligand_atom_feature, ol), ligand_ptr=lptr, output_kind=kind,
+                        enc_ligand=f32(enc_ligand_feature, ol), enc_node=enc_node, enc_graph=f32(enc_graph_feature))
+            keys = [k for k in self._flat_keys() if k != 'encoder.distance_expansion.offset']
+            named = dict(self.named_parameters())
+            with torch.enable_grad():
+                return _PropTrain.apply(native, args, self._flat_slices(), keys, *[named[k] for k in keys])
         out, h_layers, final_h, nbr = native.forward(
             f32(protein_pos, op), f32(protein_atom_feature, op), pptr, f32(ligand_pos, ol), f32(ligand_atom_feature, ol), lptr,
             output_kind=kind, enc_ligand=f32(enc_ligand_feature, ol), enc_node=enc_node, enc_graph=f32(enc_graph_feature),
@@ -175,10 +218,62 @@ class _PropBase(nn.Module):
             return out, {'h_layers': h_layers, 'final_h': final_h, 'nbr': nbr}
         return out
 
+    def _flat_slices(self):
+        sd = self.state_dict()
+        sl, o = {}, 0
+        for k in self._flat_keys():
+            n = sd[k].numel()
+            sl[k] = (o, o + n, tuple(sd[k].shape))
+            o += n
+        return sl
+
+    def _enc_features(self, batch):
+        return None, None, None
+
+    def get_loss(self, batch, pos_noise_std, return_pred=False):
+        """prop_model.py:76-95 / 167-212: MSE of the prediction for ``batch.kind`` against ``batch.y``, positions jittered by
+        N(0, pos_noise_std^2) (protein noise drawn first, then ligand noise, with torch.randn_like on the data's device).  Under grad
+        mode the prediction is differentiable (HIP forward and backward); under torch.no_grad() it is the plain forward."""
+        enc_ligand, enc_node, enc_graph = self._enc_features(batch)
+        differentiable = torch.is_grad_enabled()
+        if differentiable:
+            self._check_inputs(dict(protein_pos=batch.protein_pos, ligand_pos=batch.ligand_pos,
+                                    protein_atom_feature=batch.protein_atom_feature, ligand_atom_feature_full=batch.ligand_atom_feature_full,
+                                    enc_ligand_feature=enc_ligand, enc_node_feature=enc_node, enc_graph_feature=enc_graph))
+        protein_noise = torch.randn_like(batch.protein_pos) * pos_noise_std
+        ligand_noise = torch.randn_like(batch.ligand_pos) * pos_noise_std
+        pred = self._run(batch.protein_pos + protein_noise, batch.protein_atom_feature.float(), batch.ligand_pos + ligand_noise,
+                         batch.ligand_atom_feature_full.float(), batch.protein_element_batch, batch.ligand_element_batch, batch.kind,
+                         enc_ligand, enc_node, enc_graph, differentiable=differentiable)
+        loss = nn.MSELoss()(pred.view(-1), batch.y)
+        if return_pred:
+            return loss, pred
+        return loss
+
     @staticmethod
     def composed_order(batch_protein, batch_ligand):
         """Index into cat([protein rows, ligand rows]) of every composed row, in the project's order (stable argsort)."""
         return torch.sort(torch.cat([batch_protein, batch_ligand]), stable=True).indices
+
+
+class _PropTrain(torch.autograd.Function):
+    """The model's output as a function of its parameters: td_prop_forward_train forward, td_prop_backward backward."""
+
+    @staticmethod
+    def forward(ctx, native, args, slices, keys, *params):
+        out, tape = native.forward_train(**args)
+        ctx.native, ctx.tape, ctx.slices, ctx.keys = native, tape, slices, keys
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        if ctx.tape is None:
+            raise RuntimeError('the HIP affinity predictor\'s tape was used already (backward twice without retain_graph)')
+        flat = ctx.native.backward(ctx.tape, grad_out.float().contiguous())
+        ctx.tape = None
+        grads = [flat[ctx.slices[k][0]:ctx.slices[k][1]].view(ctx.slices[k][2]) for k in ctx.keys]
+        return (None, None, None, None) + tuple(grads)
 
 
 class _ShiftedSoftplus(_Holder):
@@ -193,9 +288,9 @@ class PropPredNet(_PropBase):
         self._init_common(config, protein_atom_feature_dim, ligand_atom_feature_dim, output_dim, _get(config, 'hidden_channels'))
 
     def forward(self, protein_pos, protein_atom_feature, ligand_pos, ligand_atom_feature, batch_protein, batch_ligand, output_kind,
-                return_extra=False):
+                return_extra=False, differentiable=False):
         return self._run(protein_pos, protein_atom_feature, ligand_pos, ligand_atom_feature, batch_protein, batch_ligand, output_kind,
-                         return_extra=return_extra)
+                         return_extra=return_extra, differentiable=differentiable)
 
 
 class PropPredNetEnc(_PropBase):
@@ -215,7 +310,7 @@ class PropPredNetEnc(_PropBase):
                           _get(config, 'hidden_channels') + self.enc_graph_dim)
 
     def forward(self, protein_pos, protein_atom_feature, ligand_pos, ligand_atom_feature, batch_protein, batch_ligand, output_kind,
-                enc_ligand_feature, enc_node_feature, enc_graph_feature, return_extra=False):
+                enc_ligand_feature, enc_node_feature, enc_graph_feature, return_extra=False, differentiable=False):
         if enc_ligand_feature is None and self.enc_ligand_dim > 0:
             raise ValueError(f'enc_ligand_dim is {self.enc_ligand_dim}: enc_ligand_feature is needed (ligand_atom_emb takes it)')
         if enc_graph_feature is None and self.enc_graph_dim > 0:
@@ -223,7 +318,33 @@ class PropPredNetEnc(_PropBase):
         if enc_node_feature is not None and self.enc_node_dim == 0:
             raise ValueError('enc_node_feature given, but the model has no enc_node_layer (enc_node_dim 0)')
         return self._run(protein_pos, protein_atom_feature, ligand_pos, ligand_atom_feature, batch_protein, batch_ligand, output_kind,
-                         enc_ligand_feature, enc_node_feature, enc_graph_feature, return_extra=return_extra)
+                         enc_ligand_feature, enc_node_feature, enc_graph_feature, return_extra=return_extra, differentiable=differentiable)
+
+    def _enc_features(self, batch):
+        """prop_model.py:172-194: which batch fields feed enc_ligand_feature / enc_node_feature / enc_graph_feature."""
+        t = self.enc_feature_type
+        if t == 'nll_all':
+            return None, None, batch.nll_all
+        if t == 'nll':
+            return None, None, batch.nll
+        if t == 'final_h':
+            return None, batch.final_h, None
+        if t == 'pred_ligand_v':
+            return batch.pred_ligand_v, None, None
+        if t == 'pred_v_entropy_pre':
+            return batch.pred_v_entropy, None, None
+        if t == 'pred_v_entropy_post':
+            return None, None, _graph_sum(batch.pred_v_entropy, batch.ligand_element_batch, batch.kind.shape[0])
+        if t == 'full':
+            graph = torch.cat([batch.nll_all, _graph_sum(batch.pred_v_entropy, batch.ligand_element_batch, batch.kind.shape[0])], -1)
+            return torch.cat([batch.pred_ligand_v, batch.pred_v_entropy], -1), batch.final_h, graph
+        raise NotImplementedError(f'enc_feature_type {t!r}')
+
+
+def _graph_sum(x, batch, B):
+    """scatter(x, batch, dim=0, reduce='sum') with B rows, as a one-hot product (no float atomics: the same sum every run)."""
+    onehot = (batch.view(1, -1) == torch.arange(B, device=batch.device).view(-1, 1)).to(x.dtype)
+    return onehot @ x
 
 
 def get_model(config, protein_atom_feat_dim, ligand_atom_feat_dim):

@@ -217,6 +217,23 @@ int td_posterior_step(const td_model *m, const int32_t *d_t, const int32_t *d_li
                       const float *d_pred_pos, const float *d_pred_v, const float *d_noise,
                       const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
                       float *d_log_post, void *stream);
+/* ---- the same step with known ("fixed") ligand atoms: scaffold-constrained sampling by replacement conditioning (DESIGN.md,
+ *      "Scaffold-constrained sampling"; no seam in the reference, which has no such mode -- the pieces are its q_v_sample
+ *      :394-398 and the forward-process sample of :577-588).  d_fixed_mask [N_l] bytes (0 / non-0; a torch bool tensor),
+ *      d_fixed_pos [N_l,3] the known positions in the centred frame of d_ligand_pos, d_fixed_v [N_l] the known types; rows with
+ *      mask 0 are not read.  A flagged atom of a graph at time step t takes, instead of the posterior draw,
+ *        t > 0:  x' = sqrt(abar[t-1]) x0 + sqrt(1 - abar[t-1]) d_noise[atom]        (each product and the sum rounded on its own)
+ *                v' = argmax_c(gumbel(d_uniform[atom][c]) + log q(v_{t-1} = c | v0)), first maximum
+ *        t == 0: x' = x0, v' = v0
+ *      d_log_post receives that log q (t == 0: log(clamp(onehot(v0), 1e-30))), d_log_v0 the model's log-softmax as for every
+ *      atom.  No draw is added or skipped.  d_fixed_mask == NULL is td_posterior_step.  Needs a model created with
+ *      alphas_cumprod (8 or 10 schedule arrays): TD_EINVAL otherwise. */
+int td_posterior_step_fixed(const td_model *m, const int32_t *d_t, const int32_t *d_ligand_ptr, int64_t N_l,
+                            int64_t B, const float *d_ligand_pos, const int64_t *d_ligand_v,
+                            const float *d_pred_pos, const float *d_pred_v, const float *d_noise,
+                            const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
+                            float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos,
+                            const int64_t *d_fixed_v, void *stream);
 
 /* ---- standalone EGNN refine net (replaces: models/egnn.py EGNN / EnBaseLayer as get_refine_net('egnn', config) builds
  *      it, models/molopt_score_model.py:34-42: num_r_gaussian = 1, kNN rebuilt per layer, SiLU, no LayerNorm, hidden 128,
@@ -378,8 +395,12 @@ typedef struct td_step_io {
     float *d_v0_traj;
     float *d_vt_traj;
     const float *d_ligand_graph_bias;   /* [B][128] or NULL: this step's time-embedding term (see td_model_forward) */
+    const uint8_t *d_fixed_mask;        /* [N_l] or NULL: known atoms (td_posterior_step_fixed); with pos_only only their positions */
+    const float *d_fixed_pos;           /* [N_l][3] centred known positions (read where the mask is set) */
+    const int64_t *d_fixed_v;           /* [N_l] known types (read where the mask is set) */
 } td_step_io;
 int td_session_step(td_session *s, const td_step_io *io, int32_t use_graph, void *stream);
+size_t td_step_io_size(void);           /* sizeof(td_step_io) of the library: lets a binding check its own layout */
 int td_session_step_graph(const td_session *s);
 /* rows processed by the last td_session_forward: counts[0] = N, counts[1] = rows recomputed at layer 0 (ligand +
  * displaced protein rows), counts[2 + k] = size of receptive-field level k + 1 of the ligand outputs (level 1 = ligand

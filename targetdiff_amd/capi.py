@@ -68,6 +68,7 @@ SIGNATURES = {
     'td_model_forward': (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, _P, _P,
                                    _P, _P, _P, c_size_t, _P, _P]),
     'td_posterior_step': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'td_posterior_step_fixed': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_center_pos': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int32, c_int32, _P]),
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
     'td_likelihood_terms': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -96,6 +97,7 @@ SIGNATURES = {
     'td_session_row_counts': (c_int32, [_P, POINTER(c_int32), c_int32, _P]),
     'td_session_step': (c_int32, [_P, _P, c_int32, _P]),
     'td_session_step_graph': (c_int32, [_P]),
+    'td_step_io_size': (c_size_t, []),
     'td_build_tag': (ctypes.c_char_p, []),
     'td_debug_fail_alloc': (c_int32, [c_int32]),
     'td_debug_node_stage': (c_int32, [_P, c_int32, c_int32, _P, c_int64, _P, _P, _P]),
@@ -110,7 +112,25 @@ class StepIO(ctypes.Structure):
     _fields_ = [('d_step', c_void_p), ('d_t_all', c_void_p), ('num_steps', c_int32), ('pos_only', c_int32),
                 ('d_ligand_pos', c_void_p), ('d_ligand_v', c_void_p), ('d_noise', c_void_p), ('d_uniform', c_void_p),
                 ('d_pos_traj', c_void_p), ('d_v_traj', c_void_p), ('d_v0_traj', c_void_p), ('d_vt_traj', c_void_p),
-                ('d_ligand_graph_bias', c_void_p)]
+                ('d_ligand_graph_bias', c_void_p), ('d_fixed_mask', c_void_p), ('d_fixed_pos', c_void_p), ('d_fixed_v', c_void_p)]
+
+
+def _fixed_ptrs(fixed_mask, fixed_pos, fixed_v, Nl):
+    """Device pointers of the known-atom arguments (td_posterior_step_fixed): mask [N_l] bool / uint8, positions [N_l,3] fp32
+    (centred), types [N_l] int64 -- or three None when there is no mask."""
+    if fixed_mask is None:
+        if fixed_pos is not None or fixed_v is not None:
+            raise ValueError('fixed_pos / fixed_v without fixed_mask')
+        return None, None, None
+    if fixed_pos is None or fixed_v is None:
+        raise ValueError('fixed_mask needs fixed_pos and fixed_v')
+    if fixed_mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f'fixed_mask must be bool or uint8, got {fixed_mask.dtype}')
+    if tuple(fixed_mask.shape) != (Nl,) or tuple(fixed_pos.shape) != (Nl, 3) or tuple(fixed_v.shape) != (Nl,):
+        raise ValueError(f'fixed_mask / fixed_pos / fixed_v must be [{Nl}], [{Nl}, 3], [{Nl}] (got {tuple(fixed_mask.shape)}, '
+                         f'{tuple(fixed_pos.shape)}, {tuple(fixed_v.shape)})')
+    return (_ptr(fixed_mask, None, 'fixed_mask'), _ptr(fixed_pos, torch.float32, 'fixed_pos'),
+            _ptr(fixed_v, torch.int64, 'fixed_v'))
 
 
 PROFILE_CLASSES = ('knn', 'gate', 'node_proj', 'x2h_k', 'x2h_v', 'h2x_k', 'h2x_v', 'compose', 'head', 'posterior')
@@ -409,12 +429,24 @@ class NativeModel:
 
     @_device_bound
     def posterior_step(self, t, ligand_ptr, ligand_pos, ligand_v, pred_pos, pred_v, noise, uniform,
-                       pos_next=None, v_next=None, log_v0=None, log_post=None):
+                       pos_next=None, v_next=None, log_v0=None, log_post=None, fixed_mask=None, fixed_pos=None, fixed_v=None):
+        """One posterior update (td_posterior_step).  ``fixed_mask`` [N_l] bool with ``fixed_pos`` [N_l,3] (centred) and ``fixed_v``
+        [N_l]: the flagged atoms take the forward-diffused copy of their known state instead (td_posterior_step_fixed)."""
         Nl, B = ligand_pos.shape[0], ligand_ptr.numel() - 1
         if pos_next is None:
             pos_next = torch.empty_like(ligand_pos)
         if v_next is None:
             v_next = torch.empty_like(ligand_v)
+        fm, fp, fv = _fixed_ptrs(fixed_mask, fixed_pos, fixed_v, Nl)
+        if fm is not None:
+            _check(self.lib.td_posterior_step_fixed(
+                self.handle, _ptr(t, torch.int32, 't'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
+                _ptr(ligand_pos, torch.float32, 'ligand_pos'), _ptr(ligand_v, torch.int64, 'ligand_v'),
+                _ptr(pred_pos, torch.float32, 'pred_pos'), _ptr(pred_v, torch.float32, 'pred_v'),
+                _ptr(noise, torch.float32, 'noise'), _ptr(uniform, torch.float32, 'uniform'), _ptr(pos_next),
+                _ptr(v_next, torch.int64, 'v_next'), _ptr(log_v0), _ptr(log_post), fm, fp, fv, _stream(self.device)),
+                'td_posterior_step_fixed')
+            return pos_next, v_next
         _check(self.lib.td_posterior_step(
             self.handle, _ptr(t, torch.int32, 't'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
             _ptr(ligand_pos, torch.float32, 'ligand_pos'), _ptr(ligand_v, torch.int64, 'ligand_v'),
@@ -542,12 +574,13 @@ class NativeSession:
         return {'pred_ligand_pos': pred_pos, 'pred_ligand_v': pred_v, 'final_h': None, 'final_ligand_h': lig_h}
 
     def make_step_io(self, step_index, t_all, ligand_pos, ligand_v, noise, uniform, pos_traj, v_traj, v0_traj=None,
-                     vt_traj=None, pos_only=False, ligand_graph_bias=None) -> StepIO:
-        """The argument block of :meth:`step`; the tensors must stay alive (and in place) for as long as it is used."""
+                     vt_traj=None, pos_only=False, ligand_graph_bias=None, fixed_mask=None, fixed_pos=None, fixed_v=None) -> StepIO:
+        """The argument block of :meth:`step`; the tensors must stay alive (and in place) for as long as it is used.
+        ``fixed_mask`` / ``fixed_pos`` / ``fixed_v``: known atoms, see :meth:`NativeModel.posterior_step`."""
         S = int(t_all.shape[0])
         if step_index.numel() != 2 or pos_traj.shape[0] != S or v_traj.shape[0] != S:
             raise ValueError('step_index must hold 2 int32, the trajectories one slot per step')
-        io = StepIO()
+        io = StepIO()           # ctypes zero-fills it, padding included: the library compares the whole block (memcmp) to re-capture
         io.d_step = _ptr(step_index, torch.int32, 'step_index').value
         io.d_t_all = _ptr(t_all, torch.int32, 't_all').value
         io.num_steps, io.pos_only = S, int(bool(pos_only))
@@ -561,6 +594,9 @@ class NativeSession:
         io.d_vt_traj = _ptr(vt_traj, torch.float32, 'vt_traj').value if vt_traj is not None and vt_traj.numel() else None
         gb = _graph_bias_ptr(ligand_graph_bias, int(t_all.shape[1]))
         io.d_ligand_graph_bias = gb.value if gb is not None else None
+        fm, fp, fv = _fixed_ptrs(fixed_mask, fixed_pos, fixed_v, self.Nl)
+        if fm is not None:
+            io.d_fixed_mask, io.d_fixed_pos, io.d_fixed_v = fm.value, fp.value, fv.value
         return io
 
     def step(self, io: StepIO, use_graph=True):

@@ -32,6 +32,7 @@ extern "C" int td_abi_version(void) { return TD_ABI_VERSION; }
 #define TD_BUILD_TAG "untagged"
 #endif
 extern "C" const char *td_build_tag(void) { return TD_BUILD_TAG; }
+extern "C" size_t td_step_io_size(void) { return sizeof(td_step_io); }
 
 // ------------------------------------------------------------------------------------------ kernel timers
 // Optional per-kernel-class HIP-event timers (bench.py's roofline leg): events are recorded on the launch

@@ -88,6 +88,12 @@ __device__ __forceinline__ int td_find_graph_l(const int32_t *__restrict__ ptr, 
 // one ligand atom of the posterior update.  pos / v may alias pos_next / v_next (the in-place form of td_session_step): every input of
 // the atom is read before its outputs are written, and atoms do not read each other.  pos_cur / v_cur (optional): second copies
 // of x_{t-1} / v_{t-1} (the trajectory slot and the current state of td_session_step); v_frozen: pos_only, v_next = the input type.
+// FIXED (scaffold-constrained sampling): atoms flagged in fixed_mask do not take the posterior draw but a forward-diffused
+// copy of their known state (fixed_pos [N_l,3] centred, fixed_v [N_l]) at level t - 1, made from this step's own draws for the atom:
+//   t > 0:  x' = sqrt(abar[t-1]) x0 + sqrt(1 - abar[t-1]) eps,   v' = argmax_c(gumbel(u_c) + log q(v_{t-1} = c | v0))   (q_v_sample)
+//   t == 0: x' = x0, v' = v0.   log_post_out receives that log q (t == 0: the clamped log one-hot), log_v0_out the model's as ever.
+// FIXED = false compiles to the code without the feature.
+template <bool FIXED>
 __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, const int32_t *__restrict__ tg,
                                                   const int32_t *__restrict__ lptr, int B, int C, int64_t at,
                                                   const float *pos, const int64_t *v,
@@ -96,7 +102,9 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
                                                   float *pos_next, int64_t *v_next,
                                                   float *__restrict__ log_v0_out, float *__restrict__ log_post_out,
                                                   float *pos_cur = nullptr, int64_t *v_cur = nullptr, bool v_frozen = false,
-                                                  int mean_type = 0) {
+                                                  int mean_type = 0, const uint8_t *__restrict__ fixed_mask = nullptr,
+                                                  const float *__restrict__ fixed_pos = nullptr,
+                                                  const int64_t *__restrict__ fixed_v = nullptr) {
     const int g = td_find_graph_l(lptr, B, (int)at);
     int t = tg[g];
     t = t < 0 ? 0 : (t >= T ? T - 1 : t);
@@ -115,6 +123,17 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
         xn[d] = td_add_rn(td_add_rn(td_mul_rn(c0, x0), td_mul_rn(ct, xt)), td_mul_rn(sd, noise[at * 3 + d]));
     }
     const int vt = (int)v[at];
+    const bool known = FIXED && fixed_mask[at] != 0;
+    if (FIXED && known) {
+        // the products and the sum each rounded on their own, as torch's eager a.sqrt() * x0 + (1 - a).sqrt() * eps (:577-588)
+        const float a = sc.abar[t - 1 < 0 ? 0 : t - 1];
+        const float sa = sqrtf(a), sb = sqrtf(1.0f - a);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const float x0 = fixed_pos[at * 3 + d];
+            xn[d] = t == 0 ? x0 : td_add_rn(td_mul_rn(sa, x0), td_mul_rn(sb, noise[at * 3 + d]));
+        }
+    }
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         pos_next[at * 3 + d] = xn[d];
@@ -155,12 +174,15 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
 #pragma unroll
     for (int cc = 0; cc < TD_MAXC; ++cc) us += cc < C ? expf(un[cc] - umx) : 0.f;
     const float ulse = umx + logf(us);
+    const int v0k = FIXED && known ? (int)fixed_v[at] : 0;
     int best = 0;
     float bestv = -INFINITY;
 #pragma unroll
     for (int cc = 0; cc < TD_MAXC; ++cc) {
         if (cc < C) {
-            const float lp = un[cc] - ulse;
+            float lp = un[cc] - ulse;
+            if (FIXED && known)         // q(v_{t-1} | v0) (:383-392) at level t - 1; t == 0: the known type itself
+                lp = t == 0 ? (cc == v0k ? 0.f : LOG_EPS) : td_log_add_exp((cc == v0k ? 0.f : LOG_EPS) + l_ca, l_1mca);
             if (log_v0_out) log_v0_out[at * C + cc] = lg[cc];
             if (log_post_out) log_post_out[at * C + cc] = lp;
             const float gum = -logf(-logf(uni[at * C + cc] + 1e-30f) + 1e-30f);     // :160-166
@@ -168,41 +190,49 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
             if (sc2 > bestv) { bestv = sc2; best = cc; }        // first maximum, like argmax
         }
     }
+    if (FIXED && known && t == 0) best = v0k;
     if (v_frozen) best = vt;
     v_next[at] = best;
     if (v_cur) v_cur[at] = best;
 }
 
+template <bool FIXED>
 __global__ void posterior_kernel(TdSchedules sc, int T, const int32_t *__restrict__ tg,
                                  const int32_t *__restrict__ lptr, int64_t Nl, int B, int C,
                                  const float *__restrict__ pos, const int64_t *__restrict__ v,
                                  const float *__restrict__ pred_pos, const float *__restrict__ pred_v,
                                  const float *__restrict__ noise, const float *__restrict__ uni,
                                  float *__restrict__ pos_next, int64_t *__restrict__ v_next,
-                                 float *__restrict__ log_v0_out, float *__restrict__ log_post_out, int mean_type) {
+                                 float *__restrict__ log_v0_out, float *__restrict__ log_post_out, int mean_type,
+                                 const uint8_t *__restrict__ fixed_mask, const float *__restrict__ fixed_pos,
+                                 const int64_t *__restrict__ fixed_v) {
     const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (at >= Nl) return;
-    td_posterior_atom(sc, T, tg, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni, pos_next, v_next, log_v0_out, log_post_out,
-                      nullptr, nullptr, false, mean_type);
+    td_posterior_atom<FIXED>(sc, T, tg, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni, pos_next, v_next, log_v0_out,
+                             log_post_out, nullptr, nullptr, false, mean_type, fixed_mask, fixed_pos, fixed_v);
 }
 
 // td_session_step: the same update with its per-step arguments taken from device memory -- step index s = step[0] selects the
 // time-step row t_all[s] and slot s of the trajectories; the current state (pos / v) is updated in place.  The last workgroup
 // to finish advances the step index (all workgroups have read it by then): the launch is replayable as a graph node.
+template <bool FIXED>
 __global__ void posterior_step_kernel(TdSchedules sc, int T, int32_t *__restrict__ step, const int32_t *__restrict__ t_all,
                                       int num_steps, const int32_t *__restrict__ lptr, int64_t Nl, int B, int C,
                                       float *pos, int64_t *v, const float *__restrict__ pred_pos,
                                       const float *__restrict__ pred_v, const float *__restrict__ noise,
                                       const float *__restrict__ uni, float *__restrict__ pos_traj, int64_t *__restrict__ v_traj,
-                                      float *__restrict__ v0_traj, float *__restrict__ vt_traj, int pos_only, int mean_type) {
+                                      float *__restrict__ v0_traj, float *__restrict__ vt_traj, int pos_only, int mean_type,
+                                      const uint8_t *__restrict__ fixed_mask, const float *__restrict__ fixed_pos,
+                                      const int64_t *__restrict__ fixed_v) {
     int s = *reinterpret_cast<volatile int32_t *>(step);
     s = s < 0 ? 0 : (s >= num_steps ? num_steps - 1 : s);
     const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (at < Nl) {
         const size_t so = (size_t)s * (size_t)Nl;
-        td_posterior_atom(sc, T, t_all + (size_t)s * B, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni, pos_traj + so * 3,
-                          v_traj + so, v0_traj ? v0_traj + so * C : nullptr, vt_traj ? vt_traj + so * C : nullptr, pos,
-                          pos_only ? nullptr : v, pos_only != 0, mean_type);
+        td_posterior_atom<FIXED>(sc, T, t_all + (size_t)s * B, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni,
+                                 pos_traj + so * 3, v_traj + so, v0_traj ? v0_traj + so * C : nullptr,
+                                 vt_traj ? vt_traj + so * C : nullptr, pos, pos_only ? nullptr : v, pos_only != 0, mean_type,
+                                 fixed_mask, fixed_pos, fixed_v);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -218,11 +248,16 @@ __global__ void posterior_step_kernel(TdSchedules sc, int T, int32_t *__restrict
 int td_launch_posterior(const TdSchedules &sc, int T, const int32_t *t, const int32_t *lptr, int64_t Nl, int64_t B,
                         int classes, const float *pos, const int64_t *v, const float *pred_pos,
                         const float *pred_v, const float *noise, const float *uni, float *pos_next,
-                        int64_t *v_next, float *log_v0, float *log_post, hipStream_t s, int mean_type) {
+                        int64_t *v_next, float *log_v0, float *log_post, hipStream_t s, int mean_type,
+                        const uint8_t *fixed_mask, const float *fixed_pos, const int64_t *fixed_v) {
     if (Nl == 0) return TD_OK;
-    posterior_kernel<<<dim3((unsigned)((Nl + 127) / 128)), dim3(128), 0, s>>>(
-        sc, T, t, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise, uni, pos_next, v_next, log_v0,
-        log_post, mean_type);
+    const dim3 grid((unsigned)((Nl + 127) / 128)), block(128);
+    if (fixed_mask)         // known atoms present: the variant with the replacement branch (needs sc.abar, checked by the callers)
+        posterior_kernel<true><<<grid, block, 0, s>>>(sc, T, t, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise, uni,
+                                                      pos_next, v_next, log_v0, log_post, mean_type, fixed_mask, fixed_pos, fixed_v);
+    else
+        posterior_kernel<false><<<grid, block, 0, s>>>(sc, T, t, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise, uni,
+                                                       pos_next, v_next, log_v0, log_post, mean_type, nullptr, nullptr, nullptr);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
@@ -230,11 +265,18 @@ int td_launch_posterior(const TdSchedules &sc, int T, const int32_t *t, const in
 int td_launch_posterior_step(const TdSchedules &sc, int T, int32_t *step, const int32_t *t_all, int num_steps, const int32_t *lptr,
                              int64_t Nl, int64_t B, int classes, float *pos, int64_t *v, const float *pred_pos, const float *pred_v,
                              const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
-                             int pos_only, hipStream_t s, int mean_type) {
+                             int pos_only, hipStream_t s, int mean_type, const uint8_t *fixed_mask, const float *fixed_pos,
+                             const int64_t *fixed_v) {
     if (Nl == 0) return TD_OK;
-    posterior_step_kernel<<<dim3((unsigned)((Nl + 127) / 128)), dim3(128), 0, s>>>(
-        sc, T, step, t_all, num_steps, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise, uni, pos_traj, v_traj, v0_traj,
-        vt_traj, pos_only, mean_type);
+    const dim3 grid((unsigned)((Nl + 127) / 128)), block(128);
+    if (fixed_mask)
+        posterior_step_kernel<true><<<grid, block, 0, s>>>(sc, T, step, t_all, num_steps, lptr, Nl, (int)B, classes, pos, v, pred_pos,
+                                                           pred_v, noise, uni, pos_traj, v_traj, v0_traj, vt_traj, pos_only, mean_type,
+                                                           fixed_mask, fixed_pos, fixed_v);
+    else
+        posterior_step_kernel<false><<<grid, block, 0, s>>>(sc, T, step, t_all, num_steps, lptr, Nl, (int)B, classes, pos, v, pred_pos,
+                                                            pred_v, noise, uni, pos_traj, v_traj, v0_traj, vt_traj, pos_only, mean_type,
+                                                            nullptr, nullptr, nullptr);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }

@@ -475,7 +475,8 @@ int session_step_issue(td_session *S, const td_step_io &io, hipStream_t s) {
     return td_launch_posterior_step(m->sched, m->cfg.num_timesteps, io.d_step, io.d_t_all, io.num_steps, S->lptr, S->Nl, S->B,
                                     m->cfg.ligand_num_classes, io.d_ligand_pos, io.d_ligand_v, S->pred_pos, S->pred_v, io.d_noise,
                                     io.d_uniform, io.d_pos_traj, io.d_v_traj, io.d_v0_traj, io.d_vt_traj, io.pos_only, s,
-                                    m->cfg.model_mean_type);
+                                    m->cfg.model_mean_type, io.d_fixed_mask, io.d_fixed_mask ? io.d_fixed_pos : nullptr,
+                                    io.d_fixed_mask ? io.d_fixed_v : nullptr);
 }
 }  // namespace tdapi
 
@@ -483,6 +484,14 @@ extern "C" int td_session_step(td_session *S, const td_step_io *io, int32_t use_
     if (!S || !io || !io->d_step || !io->d_t_all || io->num_steps < 1 || !io->d_ligand_pos || !io->d_ligand_v || !io->d_noise ||
         !io->d_uniform || !io->d_pos_traj || !io->d_v_traj) {
         td_set_error("td_session_step: bad argument");
+        return TD_EINVAL;
+    }
+    if (io->d_fixed_mask && (!io->d_fixed_pos || !io->d_fixed_v)) {
+        td_set_error("td_session_step: d_fixed_mask needs d_fixed_pos and d_fixed_v");
+        return TD_EINVAL;
+    }
+    if (io->d_fixed_mask && !S->m->sched.abar) {
+        td_set_error("td_session_step: the model was created without alphas_cumprod (8 schedule arrays)");
         return TD_EINVAL;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);

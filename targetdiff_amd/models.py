@@ -59,6 +59,28 @@ def _check_graph_inputs(batch_protein, batch_ligand, ligand_v, num_classes, allo
     return bool(bad[0]), bool(bad[1])
 
 
+def _check_fixed(fixed_mask, fixed_pos, fixed_v, Nl, num_classes, unsorted_ligand):
+    """Argument checks of scaffold-constrained sampling (ScorePosNet3D.sample_diffusion); None when no mask was given."""
+    if fixed_mask is None:
+        if fixed_pos is not None or fixed_v is not None:
+            raise ValueError('fixed_pos / fixed_v are given without fixed_mask')
+        return None
+    if not torch.is_tensor(fixed_mask) or fixed_mask.dtype != torch.bool or tuple(fixed_mask.shape) != (Nl,):
+        raise ValueError(f'fixed_mask must be a bool tensor of shape [{Nl}] (one flag per ligand atom)')
+    if fixed_pos is None or fixed_v is None:
+        raise ValueError('fixed_mask needs fixed_pos [N_l, 3] and fixed_v [N_l]')
+    if not torch.is_tensor(fixed_pos) or tuple(fixed_pos.shape) != (Nl, 3) or not fixed_pos.is_floating_point():
+        raise ValueError(f'fixed_pos must be a floating-point tensor of shape [{Nl}, 3]')
+    if not torch.is_tensor(fixed_v) or tuple(fixed_v.shape) != (Nl,) or fixed_v.dtype != torch.int64:
+        raise ValueError(f'fixed_v must be an int64 tensor of shape [{Nl}]')
+    if unsorted_ligand:
+        raise ValueError('fixed_mask with an unsorted batch_ligand: that path keeps its state in input order and has no known-atom form')
+    m = fixed_mask.to(fixed_v.device)
+    if bool(m.any()) and bool(((fixed_v[m] < 0) | (fixed_v[m] >= num_classes)).any()):
+        raise ValueError(f'fixed_v has a type outside [0, {num_classes}) on a flagged atom')
+    return fixed_mask, fixed_pos, fixed_v
+
+
 def _stable_order(batch):
     """compose_context's order of one node kind: graphs ascending, the nodes of a graph in their original relative order
     (``torch.sort(..., stable=True)``, models/common.py:126; protein nodes precede ligand nodes inside a graph because the
@@ -270,7 +292,8 @@ class _SinusoidalPosEmb(nn.Module):
 class ScorePosNet3D(nn.Module):
     """Drop-in for models/molopt_score_model.py::ScorePosNet3D on the sampling path.
 
-    Training-only members (get_diffusion_loss, likelihood_estimation, ...) are out of scope.
+    Covered: forward, sample_diffusion (with scaffold-constrained sampling as an extra), likelihood_estimation and
+    fetch_embedding.  Training of the diffusion model (get_diffusion_loss and its helpers) is out of scope.
     """
 
     def __init__(self, config, protein_atom_feature_dim, ligand_atom_feature_dim):
@@ -525,17 +548,19 @@ class ScorePosNet3D(nn.Module):
     # ------------------------------------------------------------------------------------------ sampling
     def begin_sampling(self, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, batch_ligand,
                        num_steps=None, center_pos_mode=None, max_graph_nodes=0, noise_source=None, use_session=True,
-                       pos_only=False, generator=None, use_graph=None):
+                       pos_only=False, generator=None, use_graph=None, *, fixed_mask=None, fixed_pos=None, fixed_v=None):
         """Set up the reverse-diffusion state on the device and return a :class:`ReverseSampler`
-        (``.step()`` = one iteration of the loop at models/molopt_score_model.py:650-693)."""
+        (``.step()`` = one iteration of the loop at models/molopt_score_model.py:650-693).  ``fixed_*``: see
+        :meth:`sample_diffusion`."""
         return ReverseSampler(self, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v,
                               batch_ligand, num_steps, center_pos_mode, max_graph_nodes, noise_source, use_session,
-                              pos_only, generator, use_graph)
+                              pos_only, generator, use_graph, fixed_mask=fixed_mask, fixed_pos=fixed_pos, fixed_v=fixed_v)
 
     @torch.no_grad()
     def sample_diffusion(self, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, batch_ligand,
                          num_steps=None, center_pos_mode=None, pos_only=False, max_graph_nodes=0,
-                         noise_source=None, use_session=True, use_graph=None):
+                         noise_source=None, use_session=True, use_graph=None, *, fixed_mask=None, fixed_pos=None,
+                         fixed_v=None):
         """Ancestral sampling loop (models/molopt_score_model.py:633-703).
 
         Differences from the reference are confined to *where* things run, not what is computed: no
@@ -547,10 +572,27 @@ class ScorePosNet3D(nn.Module):
         caching); the two are bit-identical (tests/test_gpu_long_parity.py).  With a session the ~50 launches of a step are
         one replayable unit (td_session_step): ``use_graph=True`` captures them once into a hipGraph and replays it, False issues
         them one by one, None (default) replays when the caller runs on a real stream -- the same kernels with the same arguments
-        either way, hence the same bits (tests/test_gpu_step_graph.py)."""
+        either way, hence the same bits (tests/test_gpu_step_graph.py).
+
+        Scaffold-constrained sampling (not in the reference; DESIGN.md "Scaffold-constrained sampling"): ``fixed_mask`` [N_l] bool
+        flags known ligand atoms, ``fixed_pos`` [N_l, 3] holds their positions in the caller's frame (centred here with the
+        ligand's own per-graph offset) and ``fixed_v`` [N_l] their types; rows where the mask is False are ignored.  After every
+        reverse step the known atoms are overwritten with a forward-diffused copy of their known state at the new noise level,
+        made from the step's own draws for those atoms (replacement conditioning, as RePaint / DiffSBDD-inpaint without the
+        resampling jumps), and with x0 / v0 themselves at t == 0; with ``pos_only`` only their positions.  Before the first step
+        their initial position becomes sqrt(abar[T-1]) x0 + sqrt(1 - abar[T-1]) init (both centred): with the default sigmoid
+        schedule abar[T-1] = 0.3676, i.e. 0.606 x0 + 0.795 init, not pure noise.  Their initial TYPE stays the caller's uniform
+        draw -- the one approximation of the mode: q(v_{T-1} | v0) = ca * onehot(v0) + (1 - ca) / K with ca =
+        exp(log_alphas_cumprod_v[T-1]) = 4.9e-5 for the default schedule (cosine, v_beta_s = 0.01, T = 1000), so it deviates from
+        uniform by at most ca * (1 - 1 / K) = 4.5e-5 in probability.  No draw is added: the stream of random numbers, and with no
+        mask or an all-False mask every output bit, is that of the unconstrained sampler.  Raises ValueError for a mask that is
+        not bool [N_l], a mask without ``fixed_pos`` / ``fixed_v``, wrong shapes, a flagged type outside [0, K), or an unsorted
+        ``batch_ligand`` together with a mask."""
+        extra = {} if fixed_mask is None and fixed_pos is None and fixed_v is None else dict(
+            fixed_mask=fixed_mask, fixed_pos=fixed_pos, fixed_v=fixed_v)
         sampler = self.begin_sampling(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v,
                                       batch_ligand, num_steps, center_pos_mode, max_graph_nodes, noise_source,
-                                      use_session=use_session, pos_only=pos_only, use_graph=use_graph)
+                                      use_session=use_session, pos_only=pos_only, use_graph=use_graph, **extra)
         while not sampler.done:
             sampler.step()
         return sampler.finish()
@@ -562,7 +604,7 @@ class ReverseSampler:
     @torch.no_grad()
     def __init__(self, model, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, batch_ligand,
                  num_steps, center_pos_mode, max_graph_nodes, noise_source, use_session=True, pos_only=False, generator=None,
-                 use_graph=None):
+                 use_graph=None, *, fixed_mask=None, fixed_pos=None, fixed_v=None):
         self.pos_only = bool(pos_only)
         self.generator = generator          # None: torch's global generator (the reference's stream of draws)
         if center_pos_mode not in ('protein', 'none'):
@@ -571,6 +613,7 @@ class ReverseSampler:
             raise NotImplementedError(f'center_pos_mode={center_pos_mode!r}: pass \'protein\' (configs/sampling.yml) or \'none\'')
         unsorted_p, unsorted_l = _check_graph_inputs(batch_protein, batch_ligand, init_ligand_v, model.num_classes, allow_unsorted=True)
         dev = protein_pos.device
+        fixed = _check_fixed(fixed_mask, fixed_pos, fixed_v, init_ligand_pos.shape[0], model.num_classes, unsorted_l)
         self.native = native = model._native(dev)
         T = model.num_timesteps
         num_steps = T if num_steps is None else num_steps
@@ -598,6 +641,23 @@ class ReverseSampler:
                 self.lpos -= self.offset[batch_ligand]
             else:
                 self.offset = native.center_pos(self.ppos, self.pptr, self.lpos, self.lptr)   # :642
+        # known atoms (scaffold-constrained sampling): centred like the ligand; rows outside the mask are never read, zero them.
+        # self._fixed: the keyword arguments of the native layer -- empty without a mask, and then never passed down
+        self._fixed = {}
+        if fixed is not None and bool(fixed[0].any()):        # an all-False mask is no mask: the unconstrained path, same bits
+            fmask, fpos, fv = (a.to(dev) for a in fixed)
+            fpos = fpos.detach().clone().contiguous().float()
+            if self.offset is not None:
+                fpos -= self.offset[batch_ligand]
+            fpos[~fmask] = 0.0
+            fv = torch.where(fmask, fv, torch.zeros_like(fv)).contiguous()
+            self._fixed = dict(fixed_mask=fmask.contiguous(), fixed_pos=fpos, fixed_v=fv)
+            # the loop starts at t = T - 1: the known atoms enter it at that level, q(x_{T-1} | x0), with the caller's centred
+            # initial position (centroid + N(0, I) in the driver, i.e. a standard normal here) as the noise -- no new draw.
+            # torch's eager arithmetic (the forward-process sample of :577-588); set-up, not the hot path
+            a = model.alphas_cumprod[T - 1].detach().float().cpu()
+            sa, sb = float(a.sqrt()), float((1.0 - a).sqrt())             # fp32 values, as the step kernel forms them
+            self.lpos[fmask] = sa * fpos[fmask] + sb * self.lpos[fmask]
         steps = list(reversed(range(T - num_steps, T)))                                   # :649
         self.S = S = len(steps)
         Nl, C = self.Nl, self.C
@@ -633,7 +693,7 @@ class ReverseSampler:
             if S > 0:
                 self._io = self.session.make_step_io(self._step_index, self.t_all, self.lpos, self.lv, self._noise,
                                                      self._uniform, self.pos_traj, self.v_traj, self.v0_traj, self.vt_traj,
-                                                     self.pos_only, ligand_graph_bias=self._gbias)
+                                                     self.pos_only, ligand_graph_bias=self._gbias, **self._fixed)
 
     def _graph_now(self):
         """Replay the step as a captured hipGraph?  ``use_graph=None`` (default): when the caller runs on a real stream (the
@@ -686,14 +746,14 @@ class ReverseSampler:
         if self.pos_only:
             native.posterior_step(self.t_all[s], self.lptr, self.lpos, self.lv, preds['pred_ligand_pos'],
                                   preds['pred_ligand_v'], self._noise, self._half, pos_next=self.pos_traj[s],
-                                  v_next=self._v_scratch)
+                                  v_next=self._v_scratch, **self._fixed)
             self.v_traj[s].copy_(self.lv)                                                  # :689
             self.lpos = self.pos_traj[s]
             self.s += 1
             return
         native.posterior_step(self.t_all[s], self.lptr, self.lpos, self.lv, preds['pred_ligand_pos'],
                               preds['pred_ligand_v'], self._noise, self._uniform, pos_next=self.pos_traj[s],
-                              v_next=self.v_traj[s], log_v0=self.v0_traj[s], log_post=self.vt_traj[s])
+                              v_next=self.v_traj[s], log_v0=self.v0_traj[s], log_post=self.vt_traj[s], **self._fixed)
         self.lpos, self.lv = self.pos_traj[s], self.v_traj[s]
         self.s += 1
 

@@ -42,6 +42,43 @@ def _prior_sizes(pocket, n, atom_num_sampler):
     return [int(atom_num.sample_atom_num(size)) for _ in range(n)]
 
 
+def _fixed_reference(data, fixed_ligand_index, num_classes):
+    """(positions [F, 3] fp32, types [F] int64) of the reference-ligand atoms to keep, or None."""
+    if fixed_ligand_index is None:
+        return None
+    pos, full = getattr(data, 'ligand_pos', None), getattr(data, 'ligand_atom_feature_full', None)
+    if pos is None or full is None:
+        raise ValueError('fixed_ligand_index needs the reference ligand on `data` (ligand_pos and ligand_atom_feature_full)')
+    pos = torch.as_tensor(np.asarray(pos.detach().cpu() if torch.is_tensor(pos) else pos), dtype=torch.float32)
+    full = torch.as_tensor(np.asarray(full.detach().cpu() if torch.is_tensor(full) else full)).long()
+    idx = torch.as_tensor(np.asarray(fixed_ligand_index, dtype=np.int64)).reshape(-1)
+    if pos.dim() != 2 or pos.shape[1] != 3 or full.shape != (pos.shape[0],):
+        raise ValueError('data.ligand_pos must be [n, 3] and data.ligand_atom_feature_full [n]')
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= pos.shape[0]):
+        raise ValueError(f'fixed_ligand_index outside the reference ligand (0 .. {pos.shape[0] - 1})')
+    if idx.unique().numel() != idx.numel():
+        raise ValueError('fixed_ligand_index names an atom twice')
+    v = full[idx]
+    if num_classes is not None and idx.numel() and (int(v.min()) < 0 or int(v.max()) >= num_classes):
+        raise ValueError(f'a fixed atom has a type outside [0, {num_classes})')
+    return pos[idx].contiguous(), v.contiguous()
+
+
+def _fixed_arguments(fixed_ref, sizes, device):
+    """fixed_mask / fixed_pos / fixed_v of a packed sample batch: the first F atoms of every sample are the known ones."""
+    fpos, fv = fixed_ref
+    F, n = fpos.shape[0], int(sum(sizes))
+    start = np.cumsum([0] + list(sizes))[:-1]
+    rows = torch.as_tensor((start[:, None] + np.arange(F)[None, :]).reshape(-1), dtype=torch.long)
+    mask = torch.zeros(n, dtype=torch.bool)
+    pos = torch.zeros(n, 3, dtype=torch.float32)
+    v = torch.zeros(n, dtype=torch.long)
+    mask[rows] = True
+    pos[rows] = fpos.repeat(len(sizes), 1)
+    v[rows] = fv.repeat(len(sizes))
+    return dict(fixed_mask=mask.to(device), fixed_pos=pos.to(device), fixed_v=v.to(device))
+
+
 def unbatch_v_traj(ligand_v_traj, n_data, ligand_cum_atoms):
     """scripts/sample_diffusion.py:21-28, vectorised: list over samples of [num_steps, num_atoms_i, ...]."""
     arr = np.stack([v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v) for v in ligand_v_traj])
@@ -51,7 +88,7 @@ def unbatch_v_traj(ligand_v_traj, n_data, ligand_cum_atoms):
 def sample_diffusion_ligand(model, data, num_samples, batch_size=16, device='cuda:0', num_steps=None,
                             pos_only=False, center_pos_mode='protein', sample_num_atoms='prior',
                             atom_num_sampler=None, ligand_num_atoms=None, generator=None, noise_source=None,
-                            overlap_batches=False, max_resident_batches=8, use_graph=None):
+                            overlap_batches=False, max_resident_batches=8, use_graph=None, fixed_ligand_index=None):
     """Returns (pred_pos, pred_v, pred_pos_traj, pred_v_traj, pred_v0_traj, pred_vt_traj, time_list).
 
     Extra keyword arguments (not in the reference signature; all optional): ``atom_num_sampler`` / ``ligand_num_atoms``
@@ -69,8 +106,14 @@ def sample_diffusion_ligand(model, data, num_samples, batch_size=16, device='cud
     most ``max_resident_batches`` batches (sessions + trajectories) are alive at a time: the pocket's batches are processed in
     groups of that size.  ``time_list`` then holds, per batch, the wall time of its group divided evenly.  ``use_graph``: see
     ScorePosNet3D.sample_diffusion (None = a captured hipGraph per batch wherever the batch runs on a real stream, i.e. in the
-    overlapped mode)."""
+    overlapped mode).
+
+    ``fixed_ligand_index`` (scaffold-constrained sampling, see ScorePosNet3D.sample_diffusion): indices into the reference ligand on
+    ``data`` (``ligand_pos`` [n, 3] and ``ligand_atom_feature_full`` [n]).  Those atoms are kept where they are, with their types,
+    and the rest of every sample is grown around them: every returned ligand is ``[those atoms, in the given order; new atoms]``.
+    The size from the chosen rule (prior / range / ref / ligand_num_atoms) is raised to at least the number of fixed atoms."""
     pocket = _as_pocket(data)
+    fixed_ref = _fixed_reference(data, fixed_ligand_index, getattr(model, 'num_classes', None))
     pocket_dev = None
     time_list = []
     num_batch = int(np.ceil(num_samples / batch_size))
@@ -98,6 +141,8 @@ def sample_diffusion_ligand(model, data, num_samples, batch_size=16, device='cud
             sizes = [int(len(ref_lig))] * n_data
         else:
             raise ValueError(sample_num_atoms)
+        if fixed_ref is not None:
+            sizes = [max(sz, fixed_ref[0].shape[0]) for sz in sizes]
         if pocket_dev is None:
             pocket_dev = workloads.DevicePocket(pocket, device)       # one H2D copy of the pocket for all batches
         batch = workloads.pack_samples_device(pocket_dev, n_data, sizes)                          # :42
@@ -118,6 +163,8 @@ def sample_diffusion_ligand(model, data, num_samples, batch_size=16, device='cud
                   center_pos_mode=center_pos_mode, max_graph_nodes=pocket.num_atoms + max(sizes))
         if use_graph is not None:
             kw['use_graph'] = use_graph
+        if fixed_ref is not None:
+            kw.update(_fixed_arguments(fixed_ref, sizes, device))
         if noise_source is not None:
             kw['noise_source'] = (lambda st, name, like, _i=i: noise_source(_i, st, name, like))
         if overlap_batches:

@@ -235,6 +235,35 @@ int td_posterior_step_fixed(const td_model *m, const int32_t *d_t, const int32_t
                             float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos,
                             const int64_t *d_fixed_v, void *stream);
 
+/* ---- time programs ("Time programs"; no seam in the reference, whose sampler walks T-1, T-2, ... one level per
+ *      denoiser call, models/molopt_score_model.py:649).  A program is a list of slots, each a DENOISE step t -> s (s < t, any
+ *      distance; s = -1 is clean data) or a RENOISE step s -> t (t > s, the forward process).  A slot's coefficients are one row of
+ *      TD_PROG_ROW floats, computed on the host in float64 and rounded once (targetdiff_amd/schedule.py, TimeProgram.tables;
+ *      abar = alphas_cumprod, Lc = log_alphas_cumprod_v, abar(-1) = 1, Lc(-1) = 0, log1m(a) = log(1 - exp(a) + 1e-40)):
+ *        DENOISE  C0 = (1 - abar_t/abar_s) sqrt(abar_s) / (1 - abar_t), CT = (1 - abar_s) sqrt(abar_t/abar_s) / (1 - abar_t),
+ *                 LOGVAR = log var (not read when LAST), LOG_A = Lc_t - Lc_s, LOG_1MA = log1m(LOG_A), LOG_CA = Lc_s,
+ *                 LOG_1MCA = log1m(Lc_s), ABAR_TO = abar_s (the level known atoms are diffused to), LAST = 1 when s = -1 (no noise,
+ *                 known atoms take their known state); a unit step holds the model's own table entries, which makes it
+ *                 td_posterior_step bit for bit
+ *        RENOISE  RHO = abar_t / abar_s, LOG_R = Lc_t - Lc_s, LOG_1MR = log1m(LOG_R)
+ *      td_posterior_step_program = td_posterior_step_fixed with the step's coefficients read from d_prog_row (device memory, one
+ *      row); d_t is still the time the denoiser ran at (model_mean_type 'noise' reads its entries).  d_fixed_mask may be NULL.
+ *      td_renoise_step: x' = sqrt(RHO) x + sqrt(1 - RHO) d_noise (roots in fp32, each product and the sum rounded on its own);
+ *      log q_c = log_add_exp(log(clamp(onehot(v), 1e-30))_c + LOG_R, LOG_1MR - ln C), v' = argmax_c(gumbel(d_uniform_c) + log q_c),
+ *      first maximum; every atom alike.  d_uniform == NULL (pos_only): d_v_next = d_ligand_v.  d_log_v0 / d_log_q ([N_l,C], may be
+ *      NULL) receive the clamped log one-hot of the incoming type and log q.  Outputs may alias inputs. */
+enum { TD_PROG_C0 = 0, TD_PROG_CT, TD_PROG_LOGVAR, TD_PROG_LOG_A, TD_PROG_LOG_1MA, TD_PROG_LOG_CA, TD_PROG_LOG_1MCA, TD_PROG_ABAR_TO,
+       TD_PROG_LAST, TD_PROG_RHO, TD_PROG_LOG_R, TD_PROG_LOG_1MR, TD_PROG_ROW };
+enum { TD_PROG_DENOISE = 0, TD_PROG_RENOISE = 1 };
+int td_posterior_step_program(const td_model *m, const int32_t *d_t, const float *d_prog_row, const int32_t *d_ligand_ptr,
+                              int64_t N_l, int64_t B, const float *d_ligand_pos, const int64_t *d_ligand_v,
+                              const float *d_pred_pos, const float *d_pred_v, const float *d_noise, const float *d_uniform,
+                              float *d_pos_next, int64_t *d_v_next, float *d_log_v0, float *d_log_post,
+                              const uint8_t *d_fixed_mask, const float *d_fixed_pos, const int64_t *d_fixed_v, void *stream);
+int td_renoise_step(const td_model *m, const float *d_prog_row, int64_t N_l, const float *d_ligand_pos, const int64_t *d_ligand_v,
+                    const float *d_noise, const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
+                    float *d_log_q, void *stream);
+
 /* ---- standalone EGNN refine net (replaces: models/egnn.py EGNN / EnBaseLayer as get_refine_net('egnn', config) builds
  *      it, models/molopt_score_model.py:34-42: num_r_gaussian = 1, kNN rebuilt per layer, SiLU, no LayerNorm, hidden 128,
  *      4 edge types, k = 32).  `host_weights`: per layer, in this order and as PyTorch stores them: edge_mlp.net.0.{weight
@@ -402,6 +431,16 @@ typedef struct td_step_io {
 int td_session_step(td_session *s, const td_step_io *io, int32_t use_graph, void *stream);
 size_t td_step_io_size(void);           /* sizeof(td_step_io) of the library: lets a binding check its own layout */
 int td_session_step_graph(const td_session *s);
+/* ---- a time program on a session: d_prog_table [num_slots][TD_PROG_ROW] (device memory, kept alive by the caller), host_kinds
+ *      [num_slots] (TD_PROG_DENOISE / TD_PROG_RENOISE, copied).  From then on call k (counted from this call on) of td_session_step
+ *      runs slot k, which must also be the value of d_step[0]: a DENOISE slot is the step as before with row k of the table (the
+ *      captured graph reads the row through d_step, so one graph serves every denoise slot); a RENOISE slot launches only the
+ *      renoise kernel, eagerly -- never inside the captured graph, never the denoiser -- fills slot k of the trajectories
+ *      (d_vt_traj: log q, d_v0_traj: the clamped log one-hot of the incoming type) and advances d_step[0] like any step; the
+ *      captured graph stays valid across it.  io->num_steps must equal num_slots; d_t_all holds the denoiser's time per slot.
+ *      The program is an argument of its own and not a field of td_step_io: that block's layout stays as it is.
+ *      d_prog_table == NULL removes the program (today's behaviour).  Either way a captured graph is dropped. */
+int td_session_set_program(td_session *s, const float *d_prog_table, const int32_t *host_kinds, int32_t num_slots);
 /* rows processed by the last td_session_forward: counts[0] = N, counts[1] = rows recomputed at layer 0 (ligand +
  * displaced protein rows), counts[2 + k] = size of receptive-field level k + 1 of the ligand outputs (level 1 = ligand
  * atoms + their neighbours, level k + 1 = level k + its neighbours; the layer e from the end updates level e + 1 only),

@@ -69,6 +69,8 @@ SIGNATURES = {
                                    _P, _P, _P, c_size_t, _P, _P]),
     'td_posterior_step': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_posterior_step_fixed': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'td_posterior_step_program': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'td_renoise_step': (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_center_pos': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int32, c_int32, _P]),
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
     'td_likelihood_terms': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -98,6 +100,7 @@ SIGNATURES = {
     'td_session_step': (c_int32, [_P, _P, c_int32, _P]),
     'td_session_step_graph': (c_int32, [_P]),
     'td_step_io_size': (c_size_t, []),
+    'td_session_set_program': (c_int32, [_P, _P, POINTER(c_int32), c_int32]),
     'td_build_tag': (ctypes.c_char_p, []),
     'td_debug_fail_alloc': (c_int32, [c_int32]),
     'td_debug_node_stage': (c_int32, [_P, c_int32, c_int32, _P, c_int64, _P, _P, _P]),
@@ -131,6 +134,15 @@ def _fixed_ptrs(fixed_mask, fixed_pos, fixed_v, Nl):
                          f'{tuple(fixed_pos.shape)}, {tuple(fixed_v.shape)})')
     return (_ptr(fixed_mask, None, 'fixed_mask'), _ptr(fixed_pos, torch.float32, 'fixed_pos'),
             _ptr(fixed_v, torch.int64, 'fixed_v'))
+
+
+PROG_ROW = 12           # TD_PROG_ROW: floats per slot of a time program's coefficient table (schedule.ROW)
+
+
+def _prog_row_ptr(row):
+    if row.dtype != torch.float32 or row.numel() != PROG_ROW or not row.is_contiguous():
+        raise ValueError(f'a program slot is {PROG_ROW} contiguous fp32 values')
+    return _ptr(row, torch.float32, 'prog_row')
 
 
 PROFILE_CLASSES = ('knn', 'gate', 'node_proj', 'x2h_k', 'x2h_v', 'h2x_k', 'h2x_v', 'compose', 'head', 'posterior')
@@ -429,15 +441,27 @@ class NativeModel:
 
     @_device_bound
     def posterior_step(self, t, ligand_ptr, ligand_pos, ligand_v, pred_pos, pred_v, noise, uniform,
-                       pos_next=None, v_next=None, log_v0=None, log_post=None, fixed_mask=None, fixed_pos=None, fixed_v=None):
+                       pos_next=None, v_next=None, log_v0=None, log_post=None, fixed_mask=None, fixed_pos=None, fixed_v=None,
+                       prog_row=None):
         """One posterior update (td_posterior_step).  ``fixed_mask`` [N_l] bool with ``fixed_pos`` [N_l,3] (centred) and ``fixed_v``
-        [N_l]: the flagged atoms take the forward-diffused copy of their known state instead (td_posterior_step_fixed)."""
+        [N_l]: the flagged atoms take the forward-diffused copy of their known state instead (td_posterior_step_fixed).
+        ``prog_row`` [schedule.ROW] fp32 on the device: a time program's slot, the step's coefficients come from it
+        (td_posterior_step_program)."""
         Nl, B = ligand_pos.shape[0], ligand_ptr.numel() - 1
         if pos_next is None:
             pos_next = torch.empty_like(ligand_pos)
         if v_next is None:
             v_next = torch.empty_like(ligand_v)
         fm, fp, fv = _fixed_ptrs(fixed_mask, fixed_pos, fixed_v, Nl)
+        if prog_row is not None:
+            _check(self.lib.td_posterior_step_program(
+                self.handle, _ptr(t, torch.int32, 't'), _prog_row_ptr(prog_row), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
+                _ptr(ligand_pos, torch.float32, 'ligand_pos'), _ptr(ligand_v, torch.int64, 'ligand_v'),
+                _ptr(pred_pos, torch.float32, 'pred_pos'), _ptr(pred_v, torch.float32, 'pred_v'),
+                _ptr(noise, torch.float32, 'noise'), _ptr(uniform, torch.float32, 'uniform'), _ptr(pos_next),
+                _ptr(v_next, torch.int64, 'v_next'), _ptr(log_v0), _ptr(log_post), fm, fp, fv, _stream(self.device)),
+                'td_posterior_step_program')
+            return pos_next, v_next
         if fm is not None:
             _check(self.lib.td_posterior_step_fixed(
                 self.handle, _ptr(t, torch.int32, 't'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
@@ -453,6 +477,22 @@ class NativeModel:
             _ptr(pred_pos, torch.float32, 'pred_pos'), _ptr(pred_v, torch.float32, 'pred_v'),
             _ptr(noise, torch.float32, 'noise'), _ptr(uniform, torch.float32, 'uniform'), _ptr(pos_next),
             _ptr(v_next, torch.int64, 'v_next'), _ptr(log_v0), _ptr(log_post), _stream(self.device)), 'td_posterior_step')
+        return pos_next, v_next
+
+    @_device_bound
+    def renoise_step(self, prog_row, ligand_pos, ligand_v, noise, uniform=None, pos_next=None, v_next=None, log_v0=None, log_q=None):
+        """One forward-process step of a time program (td_renoise_step): ``prog_row`` is the renoise slot's row of
+        ``TimeProgram.tables`` on the device; ``uniform=None`` (pos_only) leaves the types alone."""
+        Nl = ligand_pos.shape[0]
+        if pos_next is None:
+            pos_next = torch.empty_like(ligand_pos)
+        if v_next is None:
+            v_next = torch.empty_like(ligand_v)
+        _check(self.lib.td_renoise_step(
+            self.handle, _prog_row_ptr(prog_row), Nl, _ptr(ligand_pos, torch.float32, 'ligand_pos'),
+            _ptr(ligand_v, torch.int64, 'ligand_v'), _ptr(noise, torch.float32, 'noise'),
+            _ptr(uniform, torch.float32, 'uniform') if uniform is not None else None, _ptr(pos_next),
+            _ptr(v_next, torch.int64, 'v_next'), _ptr(log_v0), _ptr(log_q), _stream(self.device)), 'td_renoise_step')
         return pos_next, v_next
 
     # ---- likelihood estimation / return_all (the other consumers of the denoiser)
@@ -598,6 +638,23 @@ class NativeSession:
         if fm is not None:
             io.d_fixed_mask, io.d_fixed_pos, io.d_fixed_v = fm.value, fp.value, fv.value
         return io
+
+    def set_program(self, table, kinds):
+        """Attach a time program (td_session_set_program): ``table`` [S, PROG_ROW] fp32 on the device (kept alive here), ``kinds``
+        [S] host integers (0 denoise, 1 renoise).  ``table=None`` removes it.  Call k of :meth:`step` after this runs slot k."""
+        if table is None:
+            self._prog_table = None
+            with _on(self.device):
+                _check(self.lib.td_session_set_program(self.handle, None, None, 0), 'td_session_set_program')
+            return
+        kinds = [int(k) for k in kinds]
+        if table.dtype != torch.float32 or tuple(table.shape) != (len(kinds), PROG_ROW) or not table.is_contiguous():
+            raise ValueError(f'the program table must be contiguous fp32 [{len(kinds)}, {PROG_ROW}]')
+        arr = (c_int32 * len(kinds))(*kinds)
+        self._prog_table = table
+        with _on(self.device):
+            _check(self.lib.td_session_set_program(self.handle, _ptr(table, torch.float32, 'table'), arr, len(kinds)),
+                   'td_session_set_program')
 
     def step(self, io: StepIO, use_graph=True):
         """One reverse-diffusion step (denoiser + posterior update + trajectory record) as one replayable unit

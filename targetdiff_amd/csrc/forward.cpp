@@ -219,7 +219,7 @@ int posterior_step_impl(const char *who, const td_model *m, const int32_t *d_t, 
                         const float *d_ligand_pos, const int64_t *d_ligand_v, const float *d_pred_pos, const float *d_pred_v,
                         const float *d_noise, const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
                         float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos, const int64_t *d_fixed_v,
-                        void *stream) {
+                        void *stream, const float *d_prog_row = nullptr) {
     if (!m || N_l < 0 || B < 0) { td_set_error("%s: bad argument", who); return TD_EINVAL; }
     if (N_l == 0) return TD_OK;
     if (!d_t || !d_ligand_ptr || !d_ligand_pos || !d_ligand_v || !d_pred_pos || !d_pred_v || !d_noise || !d_uniform ||
@@ -239,7 +239,7 @@ int posterior_step_impl(const char *who, const td_model *m, const int32_t *d_t, 
     return td_launch_posterior(m->sched, m->cfg.num_timesteps, d_t, d_ligand_ptr, N_l, B, m->cfg.ligand_num_classes,
                                d_ligand_pos, d_ligand_v, d_pred_pos, d_pred_v, d_noise, d_uniform, d_pos_next,
                                d_v_next, d_log_v0, d_log_post, static_cast<hipStream_t>(stream), m->cfg.model_mean_type,
-                               d_fixed_mask, d_fixed_mask ? d_fixed_pos : nullptr, d_fixed_mask ? d_fixed_v : nullptr);
+                               d_fixed_mask, d_fixed_mask ? d_fixed_pos : nullptr, d_fixed_mask ? d_fixed_v : nullptr, d_prog_row);
 }
 }  // namespace
 
@@ -261,6 +261,32 @@ extern "C" int td_posterior_step_fixed(const td_model *m, const int32_t *d_t, co
     return posterior_step_impl("td_posterior_step_fixed", m, d_t, d_ligand_ptr, N_l, B, d_ligand_pos, d_ligand_v, d_pred_pos,
                                d_pred_v, d_noise, d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_post, d_fixed_mask, d_fixed_pos,
                                d_fixed_v, stream);
+}
+
+extern "C" int td_posterior_step_program(const td_model *m, const int32_t *d_t, const float *d_prog_row, const int32_t *d_ligand_ptr,
+                                         int64_t N_l, int64_t B, const float *d_ligand_pos, const int64_t *d_ligand_v,
+                                         const float *d_pred_pos, const float *d_pred_v, const float *d_noise,
+                                         const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
+                                         float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos,
+                                         const int64_t *d_fixed_v, void *stream) {
+    if (!d_prog_row) { td_set_error("td_posterior_step_program: null d_prog_row"); return TD_EINVAL; }
+    return posterior_step_impl("td_posterior_step_program", m, d_t, d_ligand_ptr, N_l, B, d_ligand_pos, d_ligand_v, d_pred_pos,
+                               d_pred_v, d_noise, d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_post, d_fixed_mask, d_fixed_pos,
+                               d_fixed_v, stream, d_prog_row);
+}
+
+extern "C" int td_renoise_step(const td_model *m, const float *d_prog_row, int64_t N_l, const float *d_ligand_pos,
+                               const int64_t *d_ligand_v, const float *d_noise, const float *d_uniform, float *d_pos_next,
+                               int64_t *d_v_next, float *d_log_v0, float *d_log_q, void *stream) {
+    if (!m || N_l < 0) { td_set_error("td_renoise_step: bad argument"); return TD_EINVAL; }
+    if (N_l == 0) return TD_OK;
+    if (!d_prog_row || !d_ligand_pos || !d_ligand_v || !d_noise || !d_pos_next || !d_v_next) {
+        td_set_error("td_renoise_step: null pointer");
+        return TD_EINVAL;
+    }
+    ProfScope ps(PC_POST, static_cast<hipStream_t>(stream));
+    return td_launch_renoise(d_prog_row, N_l, m->cfg.ligand_num_classes, d_ligand_pos, d_ligand_v, d_noise, d_uniform, d_pos_next,
+                             d_v_next, d_log_v0, d_log_q, static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------------------ standalone EGNN refine net

@@ -3,6 +3,7 @@
 //                       (models/molopt_score_model.py:307-311,351-352; models/common.py:156-162)
 //   * posterior_kernel  Gaussian + categorical posterior and Gumbel-max draw
 //                       (models/molopt_score_model.py:673-685 and the helpers cited in targetdiff_hip.h)
+//   * renoise_kernel    the forward-process step of a sampling time program (no seam in the reference; its pieces are :577-588, :371-381)
 //   * center kernels    center_pos(mode='protein') (models/molopt_score_model.py:110-120)
 // The reference spends ~40 tiny launches and two host syncs per step here; each is one launch.
 #include "td_device.h"
@@ -93,7 +94,11 @@ __device__ __forceinline__ int td_find_graph_l(const int32_t *__restrict__ ptr, 
 //   t > 0:  x' = sqrt(abar[t-1]) x0 + sqrt(1 - abar[t-1]) eps,   v' = argmax_c(gumbel(u_c) + log q(v_{t-1} = c | v0))   (q_v_sample)
 //   t == 0: x' = x0, v' = v0.   log_post_out receives that log q (t == 0: the clamped log one-hot), log_v0_out the model's as ever.
 // FIXED = false compiles to the code without the feature.
-template <bool FIXED>
+// PROG (time programs): the step goes from level t to any lower level s; its coefficients come from the slot's row
+// `prow` (TD_PROG_ROW floats, td_prog_col order, built on the host by TimeProgram.tables) instead of the per-t tables, "t == 0" reads
+// "s is clean data" (prow[TD_PROG_LAST]), and the known atoms' level is s (prow[TD_PROG_ABAR_TO], log_ca / log_1mca of s).  The network
+// still ran at t: model_mean_type 'noise' takes rc[t] / rm1[t].  PROG = false compiles to the code without the feature.
+template <bool FIXED, bool PROG = false>
 __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, const int32_t *__restrict__ tg,
                                                   const int32_t *__restrict__ lptr, int B, int C, int64_t at,
                                                   const float *pos, const int64_t *v,
@@ -104,13 +109,15 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
                                                   float *pos_cur = nullptr, int64_t *v_cur = nullptr, bool v_frozen = false,
                                                   int mean_type = 0, const uint8_t *__restrict__ fixed_mask = nullptr,
                                                   const float *__restrict__ fixed_pos = nullptr,
-                                                  const int64_t *__restrict__ fixed_v = nullptr) {
+                                                  const int64_t *__restrict__ fixed_v = nullptr,
+                                                  const float *__restrict__ prow = nullptr) {
     const int g = td_find_graph_l(lptr, B, (int)at);
     int t = tg[g];
     t = t < 0 ? 0 : (t >= T ? T - 1 : t);
     // ---- positions: mean = c0[t] x0 + ct[t] x_t ; x_{t-1} = mean + [t != 0] exp(0.5 logvar[t]) eps  (:673-679)
-    const float c0 = sc.c0[t], ct = sc.ct[t];
-    const float sd = t == 0 ? 0.f : expf(0.5f * sc.logvar[t]);
+    const bool last = PROG ? prow[TD_PROG_LAST] != 0.f : t == 0;          // the step ends on clean data: no noise, known atoms as they are
+    const float c0 = PROG ? prow[TD_PROG_C0] : sc.c0[t], ct = PROG ? prow[TD_PROG_CT] : sc.ct[t];
+    const float sd = last ? 0.f : expf(0.5f * (PROG ? prow[TD_PROG_LOGVAR] : sc.logvar[t]));
     float xn[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d)       // three products, two sums, each rounded on its own -- PyTorch's eager arithmetic (:376, :679), and the
@@ -126,12 +133,12 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
     const bool known = FIXED && fixed_mask[at] != 0;
     if (FIXED && known) {
         // the products and the sum each rounded on their own, as torch's eager a.sqrt() * x0 + (1 - a).sqrt() * eps (:577-588)
-        const float a = sc.abar[t - 1 < 0 ? 0 : t - 1];
+        const float a = PROG ? prow[TD_PROG_ABAR_TO] : sc.abar[t - 1 < 0 ? 0 : t - 1];
         const float sa = sqrtf(a), sb = sqrtf(1.0f - a);
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             const float x0 = fixed_pos[at * 3 + d];
-            xn[d] = t == 0 ? x0 : td_add_rn(td_mul_rn(sa, x0), td_mul_rn(sb, noise[at * 3 + d]));
+            xn[d] = last ? x0 : td_add_rn(td_mul_rn(sa, x0), td_mul_rn(sb, noise[at * 3 + d]));
         }
     }
 #pragma unroll
@@ -153,8 +160,8 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
     const float lse = mx + logf(se);
     const int tm1 = t - 1 < 0 ? 0 : t - 1;
     const float lnK = logf((float)C);
-    const float l_ca = sc.log_ca[tm1], l_1mca = sc.log_1mca[tm1] - lnK;
-    const float l_a = sc.log_a[t], l_1ma = sc.log_1ma[t] - lnK;
+    const float l_ca = PROG ? prow[TD_PROG_LOG_CA] : sc.log_ca[tm1], l_1mca = (PROG ? prow[TD_PROG_LOG_1MCA] : sc.log_1mca[tm1]) - lnK;
+    const float l_a = PROG ? prow[TD_PROG_LOG_A] : sc.log_a[t], l_1ma = (PROG ? prow[TD_PROG_LOG_1MA] : sc.log_1ma[t]) - lnK;
     const float LOG_EPS = logf(1e-30f);                         // log(clamp(onehot, 1e-30)), :129
     float un[TD_MAXC];
     float umx = -INFINITY;
@@ -182,7 +189,7 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
         if (cc < C) {
             float lp = un[cc] - ulse;
             if (FIXED && known)         // q(v_{t-1} | v0) (:383-392) at level t - 1; t == 0: the known type itself
-                lp = t == 0 ? (cc == v0k ? 0.f : LOG_EPS) : td_log_add_exp((cc == v0k ? 0.f : LOG_EPS) + l_ca, l_1mca);
+                lp = last ? (cc == v0k ? 0.f : LOG_EPS) : td_log_add_exp((cc == v0k ? 0.f : LOG_EPS) + l_ca, l_1mca);
             if (log_v0_out) log_v0_out[at * C + cc] = lg[cc];
             if (log_post_out) log_post_out[at * C + cc] = lp;
             const float gum = -logf(-logf(uni[at * C + cc] + 1e-30f) + 1e-30f);     // :160-166
@@ -190,13 +197,13 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
             if (sc2 > bestv) { bestv = sc2; best = cc; }        // first maximum, like argmax
         }
     }
-    if (FIXED && known && t == 0) best = v0k;
+    if (FIXED && known && last) best = v0k;
     if (v_frozen) best = vt;
     v_next[at] = best;
     if (v_cur) v_cur[at] = best;
 }
 
-template <bool FIXED>
+template <bool FIXED, bool PROG = false>
 __global__ void posterior_kernel(TdSchedules sc, int T, const int32_t *__restrict__ tg,
                                  const int32_t *__restrict__ lptr, int64_t Nl, int B, int C,
                                  const float *__restrict__ pos, const int64_t *__restrict__ v,
@@ -205,35 +212,15 @@ __global__ void posterior_kernel(TdSchedules sc, int T, const int32_t *__restric
                                  float *__restrict__ pos_next, int64_t *__restrict__ v_next,
                                  float *__restrict__ log_v0_out, float *__restrict__ log_post_out, int mean_type,
                                  const uint8_t *__restrict__ fixed_mask, const float *__restrict__ fixed_pos,
-                                 const int64_t *__restrict__ fixed_v) {
+                                 const int64_t *__restrict__ fixed_v, const float *__restrict__ prow) {
     const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (at >= Nl) return;
-    td_posterior_atom<FIXED>(sc, T, tg, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni, pos_next, v_next, log_v0_out,
-                             log_post_out, nullptr, nullptr, false, mean_type, fixed_mask, fixed_pos, fixed_v);
+    td_posterior_atom<FIXED, PROG>(sc, T, tg, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni, pos_next, v_next, log_v0_out,
+                                   log_post_out, nullptr, nullptr, false, mean_type, fixed_mask, fixed_pos, fixed_v, prow);
 }
 
-// td_session_step: the same update with its per-step arguments taken from device memory -- step index s = step[0] selects the
-// time-step row t_all[s] and slot s of the trajectories; the current state (pos / v) is updated in place.  The last workgroup
-// to finish advances the step index (all workgroups have read it by then): the launch is replayable as a graph node.
-template <bool FIXED>
-__global__ void posterior_step_kernel(TdSchedules sc, int T, int32_t *__restrict__ step, const int32_t *__restrict__ t_all,
-                                      int num_steps, const int32_t *__restrict__ lptr, int64_t Nl, int B, int C,
-                                      float *pos, int64_t *v, const float *__restrict__ pred_pos,
-                                      const float *__restrict__ pred_v, const float *__restrict__ noise,
-                                      const float *__restrict__ uni, float *__restrict__ pos_traj, int64_t *__restrict__ v_traj,
-                                      float *__restrict__ v0_traj, float *__restrict__ vt_traj, int pos_only, int mean_type,
-                                      const uint8_t *__restrict__ fixed_mask, const float *__restrict__ fixed_pos,
-                                      const int64_t *__restrict__ fixed_v) {
-    int s = *reinterpret_cast<volatile int32_t *>(step);
-    s = s < 0 ? 0 : (s >= num_steps ? num_steps - 1 : s);
-    const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (at < Nl) {
-        const size_t so = (size_t)s * (size_t)Nl;
-        td_posterior_atom<FIXED>(sc, T, t_all + (size_t)s * B, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni,
-                                 pos_traj + so * 3, v_traj + so, v0_traj ? v0_traj + so * C : nullptr,
-                                 vt_traj ? vt_traj + so * C : nullptr, pos, pos_only ? nullptr : v, pos_only != 0, mean_type,
-                                 fixed_mask, fixed_pos, fixed_v);
-    }
+// the last workgroup to finish advances the step index (all workgroups have read it by then): the launch is replayable as a graph node
+__device__ __forceinline__ void td_step_handover(int32_t *__restrict__ step) {
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence();
@@ -244,20 +231,113 @@ __global__ void posterior_step_kernel(TdSchedules sc, int T, int32_t *__restrict
     }
 }
 
+// td_session_step: the same update with its per-step arguments taken from device memory -- step index s = step[0] selects the
+// time-step row t_all[s] and slot s of the trajectories (PROG: and row s of the program's coefficient table); the current state
+// (pos / v) is updated in place.
+template <bool FIXED, bool PROG = false>
+__global__ void posterior_step_kernel(TdSchedules sc, int T, int32_t *__restrict__ step, const int32_t *__restrict__ t_all,
+                                      int num_steps, const int32_t *__restrict__ lptr, int64_t Nl, int B, int C,
+                                      float *pos, int64_t *v, const float *__restrict__ pred_pos,
+                                      const float *__restrict__ pred_v, const float *__restrict__ noise,
+                                      const float *__restrict__ uni, float *__restrict__ pos_traj, int64_t *__restrict__ v_traj,
+                                      float *__restrict__ v0_traj, float *__restrict__ vt_traj, int pos_only, int mean_type,
+                                      const uint8_t *__restrict__ fixed_mask, const float *__restrict__ fixed_pos,
+                                      const int64_t *__restrict__ fixed_v, const float *__restrict__ prog_table) {
+    int s = *reinterpret_cast<volatile int32_t *>(step);
+    s = s < 0 ? 0 : (s >= num_steps ? num_steps - 1 : s);
+    const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (at < Nl) {
+        const size_t so = (size_t)s * (size_t)Nl;
+        td_posterior_atom<FIXED, PROG>(sc, T, t_all + (size_t)s * B, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni,
+                                       pos_traj + so * 3, v_traj + so, v0_traj ? v0_traj + so * C : nullptr,
+                                       vt_traj ? vt_traj + so * C : nullptr, pos, pos_only ? nullptr : v, pos_only != 0, mean_type,
+                                       fixed_mask, fixed_pos, fixed_v, PROG ? prog_table + (size_t)s * TD_PROG_ROW : nullptr);
+    }
+    td_step_handover(step);
+}
+
+// ------------------------------------------------------------------------------------------ renoise (time programs)
+// One ligand atom of a forward-process step s -> t over any number of levels: every atom alike, known ones too.
+//   x' = sqrt(rho) x + sqrt(1 - rho) eps, rho = abar[t] / abar[s]  (roots in fp32, the products and the sum each rounded on their own)
+//   log q(v_t = c | v_s) = log_add_exp(log(clamp(onehot(v_s), 1e-30))_c + l_r, log1m(l_r) - ln K), v' = argmax_c(gumbel(u_c) + log q_c)
+// uni == nullptr (pos_only): the types are not touched.  pos / v may alias pos_next / v_next.
+__device__ __forceinline__ void td_renoise_atom(const float *__restrict__ prow, int C, int64_t at, const float *pos, const int64_t *v,
+                                                const float *__restrict__ noise, const float *__restrict__ uni, float *pos_next,
+                                                int64_t *v_next, float *__restrict__ log_v0_out, float *__restrict__ log_q_out,
+                                                float *pos_cur, int64_t *v_cur) {
+    const float rho = prow[TD_PROG_RHO];
+    const float sa = sqrtf(rho), sb = sqrtf(1.0f - rho);
+    float xn[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) xn[d] = td_add_rn(td_mul_rn(sa, pos[at * 3 + d]), td_mul_rn(sb, noise[at * 3 + d]));
+    const int vs = (int)v[at];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        pos_next[at * 3 + d] = xn[d];
+        if (pos_cur) pos_cur[at * 3 + d] = xn[d];
+    }
+    int best = vs;
+    if (uni) {
+        const float l_r = prow[TD_PROG_LOG_R], l_1mr = prow[TD_PROG_LOG_1MR] - logf((float)C);
+        const float LOG_EPS = logf(1e-30f);
+        float bestv = -INFINITY;
+        best = 0;
+        for (int cc = 0; cc < C; ++cc) {
+            const float l0 = cc == vs ? 0.f : LOG_EPS;
+            const float lq = td_log_add_exp(l0 + l_r, l_1mr);
+            if (log_v0_out) log_v0_out[at * C + cc] = l0;
+            if (log_q_out) log_q_out[at * C + cc] = lq;
+            const float gum = -logf(-logf(uni[at * C + cc] + 1e-30f) + 1e-30f);
+            const float sc2 = gum + lq;
+            if (sc2 > bestv) { bestv = sc2; best = cc; }        // first maximum, like argmax
+        }
+    }
+    v_next[at] = best;
+    if (v_cur) v_cur[at] = best;
+}
+
+__global__ void renoise_kernel(const float *__restrict__ prow, int64_t Nl, int C, const float *__restrict__ pos,
+                               const int64_t *__restrict__ v, const float *__restrict__ noise, const float *__restrict__ uni,
+                               float *__restrict__ pos_next, int64_t *__restrict__ v_next, float *__restrict__ log_v0_out,
+                               float *__restrict__ log_q_out) {
+    const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (at >= Nl) return;
+    td_renoise_atom(prow, C, at, pos, v, noise, uni, pos_next, v_next, log_v0_out, log_q_out, nullptr, nullptr);
+}
+
+// the session-step form: slot s = step[0] of the trajectories and row s of the table, the state in place, the step index advanced
+__global__ void renoise_step_kernel(const float *__restrict__ prog_table, int32_t *__restrict__ step, int num_steps, int64_t Nl, int C,
+                                    float *pos, int64_t *v, const float *__restrict__ noise, const float *__restrict__ uni,
+                                    float *__restrict__ pos_traj, int64_t *__restrict__ v_traj, float *__restrict__ v0_traj,
+                                    float *__restrict__ vt_traj, int pos_only) {
+    int s = *reinterpret_cast<volatile int32_t *>(step);
+    s = s < 0 ? 0 : (s >= num_steps ? num_steps - 1 : s);
+    const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (at < Nl) {
+        const size_t so = (size_t)s * (size_t)Nl;
+        td_renoise_atom(prog_table + (size_t)s * TD_PROG_ROW, C, at, pos, v, noise, pos_only ? nullptr : uni, pos_traj + so * 3,
+                        v_traj + so, v0_traj ? v0_traj + so * C : nullptr, vt_traj ? vt_traj + so * C : nullptr, pos,
+                        pos_only ? nullptr : v);
+    }
+    td_step_handover(step);
+}
 
 int td_launch_posterior(const TdSchedules &sc, int T, const int32_t *t, const int32_t *lptr, int64_t Nl, int64_t B,
                         int classes, const float *pos, const int64_t *v, const float *pred_pos,
                         const float *pred_v, const float *noise, const float *uni, float *pos_next,
                         int64_t *v_next, float *log_v0, float *log_post, hipStream_t s, int mean_type,
-                        const uint8_t *fixed_mask, const float *fixed_pos, const int64_t *fixed_v) {
+                        const uint8_t *fixed_mask, const float *fixed_pos, const int64_t *fixed_v, const float *prow) {
     if (Nl == 0) return TD_OK;
     const dim3 grid((unsigned)((Nl + 127) / 128)), block(128);
-    if (fixed_mask)         // known atoms present: the variant with the replacement branch (needs sc.abar, checked by the callers)
-        posterior_kernel<true><<<grid, block, 0, s>>>(sc, T, t, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise, uni,
-                                                      pos_next, v_next, log_v0, log_post, mean_type, fixed_mask, fixed_pos, fixed_v);
-    else
-        posterior_kernel<false><<<grid, block, 0, s>>>(sc, T, t, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise, uni,
-                                                       pos_next, v_next, log_v0, log_post, mean_type, nullptr, nullptr, nullptr);
+#define TD_POST(F, P, fm, fp, fv, pr)                                                                                                 \
+    posterior_kernel<F, P><<<grid, block, 0, s>>>(sc, T, t, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise, uni, pos_next, \
+                                                  v_next, log_v0, log_post, mean_type, fm, fp, fv, pr)
+    // known atoms present: the variant with the replacement branch (needs sc.abar, checked by the callers); a program slot: the
+    // variant that reads the slot's row
+    if (prow) { if (fixed_mask) TD_POST(true, true, fixed_mask, fixed_pos, fixed_v, prow); else TD_POST(false, true, nullptr, nullptr, nullptr, prow); }
+    else if (fixed_mask) TD_POST(true, false, fixed_mask, fixed_pos, fixed_v, nullptr);
+    else TD_POST(false, false, nullptr, nullptr, nullptr, nullptr);
+#undef TD_POST
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
@@ -266,17 +346,36 @@ int td_launch_posterior_step(const TdSchedules &sc, int T, int32_t *step, const 
                              int64_t Nl, int64_t B, int classes, float *pos, int64_t *v, const float *pred_pos, const float *pred_v,
                              const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
                              int pos_only, hipStream_t s, int mean_type, const uint8_t *fixed_mask, const float *fixed_pos,
-                             const int64_t *fixed_v) {
+                             const int64_t *fixed_v, const float *prog_table) {
     if (Nl == 0) return TD_OK;
     const dim3 grid((unsigned)((Nl + 127) / 128)), block(128);
-    if (fixed_mask)
-        posterior_step_kernel<true><<<grid, block, 0, s>>>(sc, T, step, t_all, num_steps, lptr, Nl, (int)B, classes, pos, v, pred_pos,
-                                                           pred_v, noise, uni, pos_traj, v_traj, v0_traj, vt_traj, pos_only, mean_type,
-                                                           fixed_mask, fixed_pos, fixed_v);
-    else
-        posterior_step_kernel<false><<<grid, block, 0, s>>>(sc, T, step, t_all, num_steps, lptr, Nl, (int)B, classes, pos, v, pred_pos,
-                                                            pred_v, noise, uni, pos_traj, v_traj, v0_traj, vt_traj, pos_only, mean_type,
-                                                            nullptr, nullptr, nullptr);
+#define TD_POST(F, P, fm, fp, fv, pt)                                                                                                  \
+    posterior_step_kernel<F, P><<<grid, block, 0, s>>>(sc, T, step, t_all, num_steps, lptr, Nl, (int)B, classes, pos, v, pred_pos,      \
+                                                       pred_v, noise, uni, pos_traj, v_traj, v0_traj, vt_traj, pos_only, mean_type, fm, \
+                                                       fp, fv, pt)
+    if (prog_table) { if (fixed_mask) TD_POST(true, true, fixed_mask, fixed_pos, fixed_v, prog_table); else TD_POST(false, true, nullptr, nullptr, nullptr, prog_table); }
+    else if (fixed_mask) TD_POST(true, false, fixed_mask, fixed_pos, fixed_v, nullptr);
+    else TD_POST(false, false, nullptr, nullptr, nullptr, nullptr);
+#undef TD_POST
+    TD_CHECK_HIP(hipGetLastError());
+    return TD_OK;
+}
+
+int td_launch_renoise(const float *prow, int64_t Nl, int classes, const float *pos, const int64_t *v, const float *noise,
+                      const float *uni, float *pos_next, int64_t *v_next, float *log_v0, float *log_q, hipStream_t s) {
+    if (Nl == 0) return TD_OK;
+    renoise_kernel<<<dim3((unsigned)((Nl + 127) / 128)), dim3(128), 0, s>>>(prow, Nl, classes, pos, v, noise, uni, pos_next, v_next,
+                                                                           log_v0, log_q);
+    TD_CHECK_HIP(hipGetLastError());
+    return TD_OK;
+}
+
+int td_launch_renoise_step(const float *prog_table, int32_t *step, int num_steps, int64_t Nl, int classes, float *pos, int64_t *v,
+                           const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
+                           int pos_only, hipStream_t s) {
+    if (Nl == 0) return TD_OK;
+    renoise_step_kernel<<<dim3((unsigned)((Nl + 127) / 128)), dim3(128), 0, s>>>(prog_table, step, num_steps, Nl, classes, pos, v, noise,
+                                                                                uni, pos_traj, v_traj, v0_traj, vt_traj, pos_only);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }

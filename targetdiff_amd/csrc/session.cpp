@@ -65,6 +65,10 @@ struct td_session {
     unsigned graph_epoch = 0;    // ... and the model's option epoch at that time
     int eager_steps;             // steps issued launch by launch so far (the first one also does the one-time kernel set-up)
     bool graph_failed, last_step_graph;
+    // time program (td_session_set_program): the caller's device table, the slot kinds, and the slot the next td_session_step runs
+    const float *prog_table = nullptr;
+    std::vector<int32_t> prog_kinds;
+    size_t prog_next = 0;
 };
 
 namespace tdapi {
@@ -476,9 +480,25 @@ int session_step_issue(td_session *S, const td_step_io &io, hipStream_t s) {
                                     m->cfg.ligand_num_classes, io.d_ligand_pos, io.d_ligand_v, S->pred_pos, S->pred_v, io.d_noise,
                                     io.d_uniform, io.d_pos_traj, io.d_v_traj, io.d_v0_traj, io.d_vt_traj, io.pos_only, s,
                                     m->cfg.model_mean_type, io.d_fixed_mask, io.d_fixed_mask ? io.d_fixed_pos : nullptr,
-                                    io.d_fixed_mask ? io.d_fixed_v : nullptr);
+                                    io.d_fixed_mask ? io.d_fixed_v : nullptr, S->prog_table);
 }
 }  // namespace tdapi
+
+extern "C" int td_session_set_program(td_session *S, const float *d_prog_table, const int32_t *host_kinds, int32_t num_slots) {
+    if (!S || (d_prog_table && (!host_kinds || num_slots < 1))) { td_set_error("td_session_set_program: bad argument"); return TD_EINVAL; }
+    if (d_prog_table)
+        for (int32_t k = 0; k < num_slots; ++k)
+            if (host_kinds[k] != TD_PROG_DENOISE && host_kinds[k] != TD_PROG_RENOISE) {
+                td_set_error("td_session_set_program: slot %d has kind %d", (int)k, (int)host_kinds[k]);
+                return TD_EINVAL;
+            }
+    session_drop_graph(S);          // the captured step reads, or does not read, the table
+    S->prog_table = d_prog_table;
+    S->prog_kinds.clear();
+    if (d_prog_table) S->prog_kinds.assign(host_kinds, host_kinds + num_slots);
+    S->prog_next = 0;
+    return TD_OK;
+}
 
 extern "C" int td_session_step(td_session *S, const td_step_io *io, int32_t use_graph, void *stream) {
     if (!S || !io || !io->d_step || !io->d_t_all || io->num_steps < 1 || !io->d_ligand_pos || !io->d_ligand_v || !io->d_noise ||
@@ -496,6 +516,21 @@ extern "C" int td_session_step(td_session *S, const td_step_io *io, int32_t use_
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     S->last_step_graph = false;
+    if (S->prog_table) {
+        if ((size_t)io->num_steps != S->prog_kinds.size()) {
+            td_set_error("td_session_step: num_steps = %d, the session's program has %zu slots", (int)io->num_steps, S->prog_kinds.size());
+            return TD_EINVAL;
+        }
+        if (S->prog_next >= S->prog_kinds.size()) { td_set_error("td_session_step: the program has run to its end"); return TD_EINVAL; }
+        if (S->prog_kinds[S->prog_next++] == TD_PROG_RENOISE) {
+            // a forward-process step: one kernel, launched eagerly whatever use_graph says; no denoiser, no capture
+            S->last_stream = s;
+            ProfScope ps(PC_POST, s);
+            return td_launch_renoise_step(S->prog_table, io->d_step, io->num_steps, S->Nl, S->m->cfg.ligand_num_classes, io->d_ligand_pos,
+                                          io->d_ligand_v, io->d_noise, io->d_uniform, io->d_pos_traj, io->d_v_traj, io->d_v0_traj,
+                                          io->d_vt_traj, io->pos_only, s);
+        }
+    }
     // measurement hooks put events / trace pointers into the launch sequence: those steps are issued launch by launch
     const bool graph_ok = use_graph && !S->graph_failed && g_prof.mask == 0 && !td_wg_trace_armed();
     if (graph_ok && S->graph_exec && (memcmp(&S->graph_io, io, sizeof(td_step_io)) != 0 || S->graph_epoch != S->m->option_epoch)) session_drop_graph(S);

@@ -325,12 +325,19 @@ int td_launch_posterior(const TdSchedules &sc, int T, const int32_t *t, const in
                         int classes, const float *pos, const int64_t *v, const float *pred_pos,
                         const float *pred_v, const float *noise, const float *uni, float *pos_next,
                         int64_t *v_next, float *log_v0, float *log_post, hipStream_t s, int mean_type = 0,
-                        const uint8_t *fixed_mask = nullptr, const float *fixed_pos = nullptr, const int64_t *fixed_v = nullptr);
+                        const uint8_t *fixed_mask = nullptr, const float *fixed_pos = nullptr, const int64_t *fixed_v = nullptr,
+                        const float *prow = nullptr);
 int td_launch_posterior_step(const TdSchedules &sc, int T, int32_t *step, const int32_t *t_all, int num_steps, const int32_t *lptr,
                              int64_t Nl, int64_t B, int classes, float *pos, int64_t *v, const float *pred_pos, const float *pred_v,
                              const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
                              int pos_only, hipStream_t s, int mean_type = 0, const uint8_t *fixed_mask = nullptr,
-                             const float *fixed_pos = nullptr, const int64_t *fixed_v = nullptr);
+                             const float *fixed_pos = nullptr, const int64_t *fixed_v = nullptr, const float *prog_table = nullptr);
+// time programs: prow = one slot's TD_PROG_ROW floats, prog_table = every slot's (device memory); the renoise step of a slot
+int td_launch_renoise(const float *prow, int64_t Nl, int classes, const float *pos, const int64_t *v, const float *noise,
+                      const float *uni, float *pos_next, int64_t *v_next, float *log_v0, float *log_q, hipStream_t s);
+int td_launch_renoise_step(const float *prog_table, int32_t *step, int num_steps, int64_t Nl, int classes, float *pos, int64_t *v,
+                           const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
+                           int pos_only, hipStream_t s);
 // egnn.hip / node.hip
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s);

@@ -81,6 +81,22 @@ def _check_fixed(fixed_mask, fixed_pos, fixed_v, Nl, num_classes, unsorted_ligan
     return fixed_mask, fixed_pos, fixed_v
 
 
+def _check_program(time_program, num_steps, T, unsorted_ligand):
+    """Argument checks of a sampling time program (ScorePosNet3D.sample_diffusion); None when none was given."""
+    if time_program is None:
+        return None
+    from .schedule import TimeProgram
+    if not isinstance(time_program, TimeProgram):
+        raise ValueError(f'time_program must be a targetdiff_amd.schedule.TimeProgram, got {type(time_program).__name__}')
+    if num_steps is not None:
+        raise ValueError('time_program and num_steps exclude each other: the program says which steps run')
+    if time_program.T != int(T):
+        raise ValueError(f'time_program is for T = {time_program.T}, the model has {int(T)} levels')
+    if unsorted_ligand:
+        raise ValueError('time_program with an unsorted batch_ligand: that path keeps its state in input order and has no program form')
+    return time_program
+
+
 def _stable_order(batch):
     """compose_context's order of one node kind: graphs ascending, the nodes of a graph in their original relative order
     (``torch.sort(..., stable=True)``, models/common.py:126; protein nodes precede ligand nodes inside a graph because the
@@ -347,6 +363,8 @@ class ScorePosNet3D(nn.Module):
         self.log_one_minus_alphas_v = _const(one_minus(log_a))
         self.log_alphas_cumprod_v = _const(log_ca)
         self.log_one_minus_alphas_cumprod_v = _const(one_minus(log_ca))
+        # the float64 tables a time program's strided slots are computed from (schedule.TimeProgram.tables), before fp32 rounding
+        self._sched64 = {'alphas_cumprod': cum, 'log_alphas_cumprod_v': log_ca}
         self.register_buffer('Lt_history', torch.zeros(self.num_timesteps))
         self.register_buffer('Lt_count', torch.zeros(self.num_timesteps))
 
@@ -548,19 +566,21 @@ class ScorePosNet3D(nn.Module):
     # ------------------------------------------------------------------------------------------ sampling
     def begin_sampling(self, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, batch_ligand,
                        num_steps=None, center_pos_mode=None, max_graph_nodes=0, noise_source=None, use_session=True,
-                       pos_only=False, generator=None, use_graph=None, *, fixed_mask=None, fixed_pos=None, fixed_v=None):
+                       pos_only=False, generator=None, use_graph=None, *, fixed_mask=None, fixed_pos=None, fixed_v=None,
+                       time_program=None):
         """Set up the reverse-diffusion state on the device and return a :class:`ReverseSampler`
-        (``.step()`` = one iteration of the loop at models/molopt_score_model.py:650-693).  ``fixed_*``: see
+        (``.step()`` = one iteration of the loop at models/molopt_score_model.py:650-693).  ``fixed_*`` / ``time_program``: see
         :meth:`sample_diffusion`."""
+        extra = {} if time_program is None else dict(time_program=time_program)
         return ReverseSampler(self, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v,
                               batch_ligand, num_steps, center_pos_mode, max_graph_nodes, noise_source, use_session,
-                              pos_only, generator, use_graph, fixed_mask=fixed_mask, fixed_pos=fixed_pos, fixed_v=fixed_v)
+                              pos_only, generator, use_graph, fixed_mask=fixed_mask, fixed_pos=fixed_pos, fixed_v=fixed_v, **extra)
 
     @torch.no_grad()
     def sample_diffusion(self, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, batch_ligand,
                          num_steps=None, center_pos_mode=None, pos_only=False, max_graph_nodes=0,
                          noise_source=None, use_session=True, use_graph=None, *, fixed_mask=None, fixed_pos=None,
-                         fixed_v=None):
+                         fixed_v=None, time_program=None):
         """Ancestral sampling loop (models/molopt_score_model.py:633-703).
 
         Differences from the reference are confined to *where* things run, not what is computed: no
@@ -578,8 +598,8 @@ class ScorePosNet3D(nn.Module):
         flags known ligand atoms, ``fixed_pos`` [N_l, 3] holds their positions in the caller's frame (centred here with the
         ligand's own per-graph offset) and ``fixed_v`` [N_l] their types; rows where the mask is False are ignored.  After every
         reverse step the known atoms are overwritten with a forward-diffused copy of their known state at the new noise level,
-        made from the step's own draws for those atoms (replacement conditioning, as RePaint / DiffSBDD-inpaint without the
-        resampling jumps), and with x0 / v0 themselves at t == 0; with ``pos_only`` only their positions.  Before the first step
+        made from the step's own draws for those atoms (replacement conditioning, as RePaint / DiffSBDD-inpaint; the
+        resampling jumps come with a ``time_program``, below), and with x0 / v0 themselves at t == 0; with ``pos_only`` only their positions.  Before the first step
         their initial position becomes sqrt(abar[T-1]) x0 + sqrt(1 - abar[T-1]) init (both centred): with the default sigmoid
         schedule abar[T-1] = 0.3676, i.e. 0.606 x0 + 0.795 init, not pure noise.  Their initial TYPE stays the caller's uniform
         draw -- the one approximation of the mode: q(v_{T-1} | v0) = ca * onehot(v0) + (1 - ca) / K with ca =
@@ -587,9 +607,23 @@ class ScorePosNet3D(nn.Module):
         uniform by at most ca * (1 - 1 / K) = 4.5e-5 in probability.  No draw is added: the stream of random numbers, and with no
         mask or an all-False mask every output bit, is that of the unconstrained sampler.  Raises ValueError for a mask that is
         not bool [N_l], a mask without ``fixed_pos`` / ``fixed_v``, wrong shapes, a flagged type outside [0, K), or an unsorted
-        ``batch_ligand`` together with a mask."""
+        ``batch_ligand`` together with a mask.
+
+        Time programs (not in the reference; DESIGN.md "Time programs"): ``time_program`` is a :class:`schedule.TimeProgram` -- a
+        list of steps, each a denoise step t -> s over any number of levels (one denoiser call at time t, the posterior
+        q(x_s | x_t, x_0) exact for the pair) or a renoise step s -> t (no denoiser call, a draw from the forward process: the
+        resampling jump of RePaint, which noises the whole ligand, known atoms included).  ``TimeProgram.strided(T, K)`` spends K
+        denoiser calls on a full ligand, ``.with_resampling(j, r)`` adds the jumps that scaffold-constrained sampling lacked.
+        The trajectories get one slot per program step of either kind (on a renoise slot ``vt_traj`` holds log q(v_t | v_s) and
+        ``v0_traj`` the clamped log one-hot of the incoming type) and the result gains ``'levels'``, the level after each step.
+        A program of unit steps (``TimeProgram.reference(T, n)``) is ``num_steps=n`` bit for bit.  Every step of either kind
+        consumes one Gaussian and (unless ``pos_only``) one uniform draw of the per-step stream, renoise steps too.  Raises
+        ValueError when given together with ``num_steps``, for a program of another T, for something that is not a TimeProgram,
+        and with an unsorted ``batch_ligand``.  Sample quality under strides is not assessed here."""
         extra = {} if fixed_mask is None and fixed_pos is None and fixed_v is None else dict(
             fixed_mask=fixed_mask, fixed_pos=fixed_pos, fixed_v=fixed_v)
+        if time_program is not None:
+            extra['time_program'] = time_program
         sampler = self.begin_sampling(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v,
                                       batch_ligand, num_steps, center_pos_mode, max_graph_nodes, noise_source,
                                       use_session=use_session, pos_only=pos_only, use_graph=use_graph, **extra)
@@ -604,7 +638,7 @@ class ReverseSampler:
     @torch.no_grad()
     def __init__(self, model, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, batch_ligand,
                  num_steps, center_pos_mode, max_graph_nodes, noise_source, use_session=True, pos_only=False, generator=None,
-                 use_graph=None, *, fixed_mask=None, fixed_pos=None, fixed_v=None):
+                 use_graph=None, *, fixed_mask=None, fixed_pos=None, fixed_v=None, time_program=None):
         self.pos_only = bool(pos_only)
         self.generator = generator          # None: torch's global generator (the reference's stream of draws)
         if center_pos_mode not in ('protein', 'none'):
@@ -614,6 +648,7 @@ class ReverseSampler:
         unsorted_p, unsorted_l = _check_graph_inputs(batch_protein, batch_ligand, init_ligand_v, model.num_classes, allow_unsorted=True)
         dev = protein_pos.device
         fixed = _check_fixed(fixed_mask, fixed_pos, fixed_v, init_ligand_pos.shape[0], model.num_classes, unsorted_l)
+        self.program = program = _check_program(time_program, num_steps, model.num_timesteps, unsorted_l)
         self.native = native = model._native(dev)
         T = model.num_timesteps
         num_steps = T if num_steps is None else num_steps
@@ -659,6 +694,11 @@ class ReverseSampler:
             sa, sb = float(a.sqrt()), float((1.0 - a).sqrt())             # fp32 values, as the step kernel forms them
             self.lpos[fmask] = sa * fpos[fmask] + sb * self.lpos[fmask]
         steps = list(reversed(range(T - num_steps, T)))                                   # :649
+        self._prog_table = self._prog_kinds = None
+        if program is not None:           # one slot per program step; t_all holds the time the denoiser runs at
+            steps = program.denoiser_times().tolist()
+            self._prog_kinds = program.kind.tolist()
+            self._prog_table = torch.from_numpy(program.tables(model)).to(dev).contiguous()
         self.S = S = len(steps)
         Nl, C = self.Nl, self.C
         self.pos_traj = torch.empty(S, Nl, 3, dtype=torch.float32, device=dev)
@@ -694,6 +734,8 @@ class ReverseSampler:
                 self._io = self.session.make_step_io(self._step_index, self.t_all, self.lpos, self.lv, self._noise,
                                                      self._uniform, self.pos_traj, self.v_traj, self.v0_traj, self.vt_traj,
                                                      self.pos_only, ligand_graph_bias=self._gbias, **self._fixed)
+                if program is not None:
+                    self.session.set_program(self._prog_table, self._prog_kinds)
 
     def _graph_now(self):
         """Replay the step as a captured hipGraph?  ``use_graph=None`` (default): when the caller runs on a real stream (the
@@ -712,7 +754,7 @@ class ReverseSampler:
     def _draw(self, s):
         """This step's Gaussian / uniform draws into the fixed buffers, in the reference's order (:677, then :161); with a time
         embedding, also this step's per-graph embedding rows (:652 time_step = t for every graph)."""
-        if self._gbias is not None:
+        if self._gbias is not None and not self._renoise(s):          # (a program: t_all[s] is the denoise step's t_from)
             self._gbias.copy_(self.model._time_bias(self.t_all[s], self.B))
         if self.noise_source is None:
             # == torch.randn_like(lpos) / torch.rand(Nl, C): the same generator stream, written in place
@@ -724,12 +766,29 @@ class ReverseSampler:
             if not self.pos_only:
                 self._uniform.copy_(self.noise_source(s, 'uniform', self.v0_traj[s]))
 
+    def _renoise(self, s):
+        return self._prog_kinds is not None and self._prog_kinds[s] == 1
+
     @torch.no_grad()
     def step(self):
         s, native = self.s, self.native
         if self.session is not None and self.S > 0 and self._lig_order is None:
             self._draw(s)
             self.session.step(self._io, use_graph=self._graph_now())     # lpos / lv are updated in place, slot s of the trajectories filled
+            self.s += 1
+            return
+        prog = {} if self._prog_table is None else dict(prog_row=self._prog_table[s])
+        if self._renoise(s):              # a forward-process step (time programs): no denoiser call
+            self._draw(s)
+            if self.pos_only:
+                native.renoise_step(self._prog_table[s], self.lpos, self.lv, self._noise, None, pos_next=self.pos_traj[s],
+                                    v_next=self._v_scratch)
+                self.v_traj[s].copy_(self.lv)
+                self.lpos = self.pos_traj[s]
+            else:
+                native.renoise_step(self._prog_table[s], self.lpos, self.lv, self._noise, self._uniform, pos_next=self.pos_traj[s],
+                                    v_next=self.v_traj[s], log_v0=self.v0_traj[s], log_q=self.vt_traj[s])
+                self.lpos, self.lv = self.pos_traj[s], self.v_traj[s]
             self.s += 1
             return
         lpos_in, lv_in = self.lpos, self.lv
@@ -746,14 +805,14 @@ class ReverseSampler:
         if self.pos_only:
             native.posterior_step(self.t_all[s], self.lptr, self.lpos, self.lv, preds['pred_ligand_pos'],
                                   preds['pred_ligand_v'], self._noise, self._half, pos_next=self.pos_traj[s],
-                                  v_next=self._v_scratch, **self._fixed)
+                                  v_next=self._v_scratch, **self._fixed, **prog)
             self.v_traj[s].copy_(self.lv)                                                  # :689
             self.lpos = self.pos_traj[s]
             self.s += 1
             return
         native.posterior_step(self.t_all[s], self.lptr, self.lpos, self.lv, preds['pred_ligand_pos'],
                               preds['pred_ligand_v'], self._noise, self._uniform, pos_next=self.pos_traj[s],
-                              v_next=self.v_traj[s], log_v0=self.v0_traj[s], log_post=self.vt_traj[s], **self._fixed)
+                              v_next=self.v_traj[s], log_v0=self.v0_traj[s], log_post=self.vt_traj[s], **self._fixed, **prog)
         self.lpos, self.lv = self.pos_traj[s], self.v_traj[s]
         self.s += 1
 
@@ -768,5 +827,8 @@ class ReverseSampler:
         final_pos = pos_traj[-1].clone() if S else (self.lpos + shift if shift is not None else self.lpos.clone())
         final_v = v_traj[-1].clone() if S else self.lv
         pos_cpu, v_cpu, v0_cpu, vt_cpu = pos_traj.cpu(), v_traj.cpu(), v0_traj.cpu(), vt_traj.cpu()
-        return {'pos': final_pos, 'v': final_v, 'pos_traj': list(pos_cpu.unbind(0)), 'v_traj': list(v_cpu.unbind(0)),
-                'v0_traj': list(v0_cpu.unbind(0)), 'vt_traj': list(vt_cpu.unbind(0))}
+        out = {'pos': final_pos, 'v': final_v, 'pos_traj': list(pos_cpu.unbind(0)), 'v_traj': list(v_cpu.unbind(0)),
+               'v0_traj': list(v0_cpu.unbind(0)), 'vt_traj': list(vt_cpu.unbind(0))}
+        if self.program is not None:
+            out['levels'] = [int(l) for l in self.program.levels[:S]]
+        return out

@@ -88,7 +88,8 @@ def unbatch_v_traj(ligand_v_traj, n_data, ligand_cum_atoms):
 def sample_diffusion_ligand(model, data, num_samples, batch_size=16, device='cuda:0', num_steps=None,
                             pos_only=False, center_pos_mode='protein', sample_num_atoms='prior',
                             atom_num_sampler=None, ligand_num_atoms=None, generator=None, noise_source=None,
-                            overlap_batches=False, max_resident_batches=8, use_graph=None, fixed_ligand_index=None):
+                            overlap_batches=False, max_resident_batches=8, use_graph=None, fixed_ligand_index=None,
+                            time_program=None):
     """Returns (pred_pos, pred_v, pred_pos_traj, pred_v_traj, pred_v0_traj, pred_vt_traj, time_list).
 
     Extra keyword arguments (not in the reference signature; all optional): ``atom_num_sampler`` / ``ligand_num_atoms``
@@ -111,7 +112,13 @@ def sample_diffusion_ligand(model, data, num_samples, batch_size=16, device='cud
     ``fixed_ligand_index`` (scaffold-constrained sampling, see ScorePosNet3D.sample_diffusion): indices into the reference ligand on
     ``data`` (``ligand_pos`` [n, 3] and ``ligand_atom_feature_full`` [n]).  Those atoms are kept where they are, with their types,
     and the rest of every sample is grown around them: every returned ligand is ``[those atoms, in the given order; new atoms]``.
-    The size from the chosen rule (prior / range / ref / ligand_num_atoms) is raised to at least the number of fixed atoms."""
+    The size from the chosen rule (prior / range / ref / ligand_num_atoms) is raised to at least the number of fixed atoms.
+
+    ``time_program`` (a ``schedule.TimeProgram``, see ScorePosNet3D.sample_diffusion; excludes ``num_steps``): the one program every
+    sample batch runs, in the overlapped mode too.  The result tuple keeps its layout; the trajectories have ``len(time_program)``
+    entries, one per step of either kind."""
+    if time_program is not None and num_steps is not None:
+        raise ValueError('time_program and num_steps exclude each other')
     pocket = _as_pocket(data)
     fixed_ref = _fixed_reference(data, fixed_ligand_index, getattr(model, 'num_classes', None))
     pocket_dev = None
@@ -165,6 +172,8 @@ def sample_diffusion_ligand(model, data, num_samples, batch_size=16, device='cud
             kw['use_graph'] = use_graph
         if fixed_ref is not None:
             kw.update(_fixed_arguments(fixed_ref, sizes, device))
+        if time_program is not None:
+            kw['time_program'] = time_program
         if noise_source is not None:
             kw['noise_source'] = (lambda st, name, like, _i=i: noise_source(_i, st, name, like))
         if overlap_batches:

@@ -5,6 +5,7 @@
     python tools/batch_sample.py --pockets DIR_OF_PDB | synthetic:100 --result_path OUT [--gpus 8]
                                  [--num_samples 100] [--num_steps 1000] [--batch_size 100] [--start_idx 0]
                                  [--checkpoint ckpt.pt] [--seed 2021]
+                                 [--sample-steps K [--jump-length J --resamplings R]]
 
 * pocket i is sampled by rank i % world (scripts/batch_sample_diffusion.sh:15-17), from --start_idx on (:13);
 * every pocket ends in ``OUT/result_{i}.pt`` with the keys scripts/sample_diffusion.py:175-182 saves (consumed by
@@ -78,6 +79,10 @@ def main(argv=None, model_factory=build_model):
                     'reference\'s CUDA_VISIBLE_DEVICES recipe, instead of all GPUs + set_device(LOCAL_RANK)')
     ap.add_argument('--overlap-batches', action='store_true', help='advance the sample batches of a pocket together, one HIP stream and one '
                     'captured hipGraph each (pays when batch_size is small; per-batch generators, see sample_diffusion_ligand)')
+    ap.add_argument('--sample-steps', type=int, default=0, help='spend K denoiser calls on a full ligand: the strided time program '
+                    'TimeProgram.strided(T, K) instead of --num_steps levels of the reference chain (0: off)')
+    ap.add_argument('--jump-length', type=int, default=0, help='with --sample-steps: RePaint resampling jumps of this many program steps')
+    ap.add_argument('--resamplings', type=int, default=1, help='with --jump-length: times each stretch is sampled')
     ap.add_argument('--device', default='cuda', help="'cuda' (rank r uses GPU LOCAL_RANK) or 'cpu' (tests: gloo + stub model)")
     args = ap.parse_args(argv)
     if argv is None:
@@ -108,6 +113,15 @@ def main(argv=None, model_factory=build_model):
     pockets = load_pockets(args.pockets)
     model = model_factory(args, dev)
     sizes = [args.ligand_atoms] * args.num_samples if args.ligand_atoms > 0 else None
+    steps_kw = {'num_steps': args.num_steps}
+    if args.sample_steps > 0:
+        from targetdiff_amd.schedule import TimeProgram
+        program = TimeProgram.strided(model.num_timesteps, args.sample_steps)
+        if args.jump_length > 0:
+            program = program.with_resampling(args.jump_length, args.resamplings)
+        steps_kw = {'time_program': program}
+    elif args.jump_length > 0:
+        ap.error('--jump-length needs --sample-steps')
     log = []
 
     def on_pocket(idx, seconds, skipped):
@@ -116,7 +130,7 @@ def main(argv=None, model_factory=build_model):
     t0 = time.time()
     sampling.run_sharded(model, pockets, args.num_samples, rank=rank, world_size=world, start_idx=args.start_idx,
                          result_path=args.result_path, keep_results=False, on_pocket=on_pocket, balance=args.balance,
-                         batch_size=args.batch_size, device=dev, num_steps=args.num_steps, ligand_num_atoms=sizes,
+                         batch_size=args.batch_size, device=dev, ligand_num_atoms=sizes, **steps_kw,
                          **({'overlap_batches': True} if args.overlap_batches else {}))
     if on_gpu:
         torch.cuda.synchronize()

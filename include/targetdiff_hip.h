@@ -264,6 +264,32 @@ int td_renoise_step(const td_model *m, const float *d_prog_row, int64_t N_l, con
                     const float *d_noise, const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
                     float *d_log_q, void *stream);
 
+/* ---- clash guidance ("Clash guidance"; the reference has no such mode).  All coordinates in one frame (the
+ *      sampler's: centred).  Graph g has protein atoms p_j with contact radii sigma_j > 0 (Angstrom) and ligand points x_i:
+ *        E_g = 1/2 sum_i sum_j max(0, sigma_j - d_ij)^2,  d_ij = |x_i - p_j|
+ *        D_i = -w grad_{x_i} E_g = w sum_j max(0, sigma_j - d_ij) (x_i - p_j) / d_ij      (pairs with d_ij < 1e-6 add nothing)
+ *      and D_i is scaled to length max_shift when max_shift > 0 and |D_i| exceeds it (max_shift == 0: no cap).
+ *      td_clash_shift writes D [N_l,3] for the points d_pos [N_l,3]; td_clash_report writes per graph the number of pairs with
+ *      d_ij < sigma_j (coincident pairs included), E_g and min d_ij (+inf for a graph without pairs).  d_protein_ptr / d_ligand_ptr:
+ *      [B+1] int32 prefix offsets.  A graph's result depends on that graph alone, and the same inputs give the same bits every time
+ *      (fixed-order reductions, no atomics).  TD_EINVAL for w < 0 or max_shift < 0; the radii are not read on the host: a binding
+ *      checks sigma > 0.
+ *      td_posterior_step_guided = td_posterior_step_program whose x0 -- d_pred_pos for model_mean_type 'C0', rc[t] x_t - rm1[t]
+ *      (d_pred_pos - x_t) for 'noise' -- is replaced by fl32(x0 + d_x0_shift[atom]) (one rounded add), on every step, the last
+ *      included; atoms flagged in d_fixed_mask ignore the shift.  d_prog_row == NULL: the model's own tables (td_posterior_step_fixed);
+ *      d_x0_shift == NULL: exactly the kernels of the unguided entry points.
+ *      (These entry points are additions: no existing signature or struct changes, and TD_ABI_VERSION stays 5.) */
+int td_clash_shift(const float *d_protein_pos, const float *d_sigma, const int32_t *d_protein_ptr, const int32_t *d_ligand_ptr,
+                   int64_t B, const float *d_pos, float w, float max_shift, float *d_shift, void *stream);
+int td_clash_report(const float *d_protein_pos, const float *d_sigma, const int32_t *d_protein_ptr, const int32_t *d_ligand_ptr,
+                    int64_t B, const float *d_pos, int32_t *d_count, float *d_energy, float *d_min_dist, void *stream);
+int td_posterior_step_guided(const td_model *m, const int32_t *d_t, const float *d_prog_row, const int32_t *d_ligand_ptr,
+                             int64_t N_l, int64_t B, const float *d_ligand_pos, const int64_t *d_ligand_v,
+                             const float *d_pred_pos, const float *d_pred_v, const float *d_noise, const float *d_uniform,
+                             float *d_pos_next, int64_t *d_v_next, float *d_log_v0, float *d_log_post,
+                             const uint8_t *d_fixed_mask, const float *d_fixed_pos, const int64_t *d_fixed_v,
+                             const float *d_x0_shift, void *stream);
+
 /* ---- standalone EGNN refine net (replaces: models/egnn.py EGNN / EnBaseLayer as get_refine_net('egnn', config) builds
  *      it, models/molopt_score_model.py:34-42: num_r_gaussian = 1, kNN rebuilt per layer, SiLU, no LayerNorm, hidden 128,
  *      4 edge types, k = 32).  `host_weights`: per layer, in this order and as PyTorch stores them: edge_mlp.net.0.{weight
@@ -441,6 +467,12 @@ int td_session_step_graph(const td_session *s);
  *      The program is an argument of its own and not a field of td_step_io: that block's layout stays as it is.
  *      d_prog_table == NULL removes the program (today's behaviour).  Either way a captured graph is dropped. */
 int td_session_set_program(td_session *s, const float *d_prog_table, const int32_t *host_kinds, int32_t num_slots);
+/* ---- clash guidance on a session: d_sigma [N_p] contact radii of the session's protein atoms (device memory; read during this call,
+ *      which packs them beside the centred protein the session holds and waits for that).  From then on every denoise step of
+ *      td_session_step runs denoiser -> td_clash_shift of the predicted x0 -> td_posterior_step_guided as one replayable unit;
+ *      renoise slots of a program are not guided.  d_sigma == NULL removes guidance (today's step).  Either way a captured graph is
+ *      dropped.  TD_EINVAL for w < 0 or max_shift < 0. */
+int td_session_set_guidance(td_session *s, const float *d_sigma, float w, float max_shift);
 /* rows processed by the last td_session_forward: counts[0] = N, counts[1] = rows recomputed at layer 0 (ligand +
  * displaced protein rows), counts[2 + k] = size of receptive-field level k + 1 of the ligand outputs (level 1 = ligand
  * atoms + their neighbours, level k + 1 = level k + its neighbours; the layer e from the end updates level e + 1 only),

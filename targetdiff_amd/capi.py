@@ -71,6 +71,9 @@ SIGNATURES = {
     'td_posterior_step_fixed': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_posterior_step_program': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_renoise_step': (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'td_clash_shift': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_float, c_float, _P, _P]),
+    'td_clash_report': (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+    'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_center_pos': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int32, c_int32, _P]),
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
     'td_likelihood_terms': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -101,6 +104,7 @@ SIGNATURES = {
     'td_session_step_graph': (c_int32, [_P]),
     'td_step_io_size': (c_size_t, []),
     'td_session_set_program': (c_int32, [_P, _P, POINTER(c_int32), c_int32]),
+    'td_session_set_guidance': (c_int32, [_P, _P, c_float, c_float]),
     'td_build_tag': (ctypes.c_char_p, []),
     'td_debug_fail_alloc': (c_int32, [c_int32]),
     'td_debug_node_stage': (c_int32, [_P, c_int32, c_int32, _P, c_int64, _P, _P, _P]),
@@ -136,6 +140,7 @@ def _fixed_ptrs(fixed_mask, fixed_pos, fixed_v, Nl):
             _ptr(fixed_v, torch.int64, 'fixed_v'))
 
 
+CLASH_TILE = 1024       # TD_CLASH_TILE: protein atoms per LDS tile of the clash kernels (csrc/td_internal.h)
 PROG_ROW = 12           # TD_PROG_ROW: floats per slot of a time program's coefficient table (schedule.ROW)
 
 
@@ -442,17 +447,30 @@ class NativeModel:
     @_device_bound
     def posterior_step(self, t, ligand_ptr, ligand_pos, ligand_v, pred_pos, pred_v, noise, uniform,
                        pos_next=None, v_next=None, log_v0=None, log_post=None, fixed_mask=None, fixed_pos=None, fixed_v=None,
-                       prog_row=None):
+                       prog_row=None, x0_shift=None):
         """One posterior update (td_posterior_step).  ``fixed_mask`` [N_l] bool with ``fixed_pos`` [N_l,3] (centred) and ``fixed_v``
         [N_l]: the flagged atoms take the forward-diffused copy of their known state instead (td_posterior_step_fixed).
         ``prog_row`` [schedule.ROW] fp32 on the device: a time program's slot, the step's coefficients come from it
-        (td_posterior_step_program)."""
+        (td_posterior_step_program).  ``x0_shift`` [N_l,3] fp32: the step uses fl32(x0 + x0_shift) in place of the predicted x0
+        (td_posterior_step_guided; clash guidance, ``guidance.clash_shift``); known atoms ignore it."""
         Nl, B = ligand_pos.shape[0], ligand_ptr.numel() - 1
         if pos_next is None:
             pos_next = torch.empty_like(ligand_pos)
         if v_next is None:
             v_next = torch.empty_like(ligand_v)
         fm, fp, fv = _fixed_ptrs(fixed_mask, fixed_pos, fixed_v, Nl)
+        if x0_shift is not None:
+            if tuple(x0_shift.shape) != (Nl, 3):
+                raise ValueError(f'x0_shift must be [{Nl}, 3] (got {tuple(x0_shift.shape)})')
+            _check(self.lib.td_posterior_step_guided(
+                self.handle, _ptr(t, torch.int32, 't'), _prog_row_ptr(prog_row) if prog_row is not None else None,
+                _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
+                _ptr(ligand_pos, torch.float32, 'ligand_pos'), _ptr(ligand_v, torch.int64, 'ligand_v'),
+                _ptr(pred_pos, torch.float32, 'pred_pos'), _ptr(pred_v, torch.float32, 'pred_v'),
+                _ptr(noise, torch.float32, 'noise'), _ptr(uniform, torch.float32, 'uniform'), _ptr(pos_next),
+                _ptr(v_next, torch.int64, 'v_next'), _ptr(log_v0), _ptr(log_post), fm, fp, fv,
+                _ptr(x0_shift, torch.float32, 'x0_shift'), _stream(self.device)), 'td_posterior_step_guided')
+            return pos_next, v_next
         if prog_row is not None:
             _check(self.lib.td_posterior_step_program(
                 self.handle, _ptr(t, torch.int32, 't'), _prog_row_ptr(prog_row), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
@@ -656,6 +674,18 @@ class NativeSession:
             _check(self.lib.td_session_set_program(self.handle, _ptr(table, torch.float32, 'table'), arr, len(kinds)),
                    'td_session_set_program')
 
+    def set_guidance(self, sigma, weight=1.0, max_shift=0.0):
+        """Clash guidance for every denoise step from now on (td_session_set_guidance): ``sigma`` [N_p] fp32 contact radii of the
+        session's protein atoms, all > 0 (checked here: the library does not read them on the host).  ``sigma=None`` removes it."""
+        with _on(self.device):
+            if sigma is None:
+                _check(self.lib.td_session_set_guidance(self.handle, None, 0.0, 0.0), 'td_session_set_guidance')
+                return
+            if not bool((sigma > 0).all()):
+                raise ValueError('clash guidance: every contact radius must be > 0')
+            _check(self.lib.td_session_set_guidance(self.handle, _ptr(sigma, torch.float32, 'sigma'), float(weight), float(max_shift)),
+                   'td_session_set_guidance')
+
     def step(self, io: StepIO, use_graph=True):
         """One reverse-diffusion step (denoiser + posterior update + trajectory record) as one replayable unit
         (td_session_step): captured into a hipGraph at the second call, replayed from then on."""
@@ -712,6 +742,57 @@ def graph_ptr(batch: torch.Tensor, B: int) -> torch.Tensor:
         _check(lib.td_graph_ptr(_ptr(batch, torch.int64, 'batch'), batch.numel(), B, _ptr(ptr), _stream(batch.device)),
                'td_graph_ptr')
     return ptr
+
+
+def _clash_inputs(protein_pos, sigma, protein_ptr, ligand_ptr, pos, check=True):
+    Np, Nl, B = protein_pos.shape[0], pos.shape[0], protein_ptr.numel() - 1
+    if protein_pos.dim() != 2 or protein_pos.shape[1] != 3 or pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError(f'protein_pos / pos must be [N_p, 3] / [N_l, 3] (got {tuple(protein_pos.shape)}, {tuple(pos.shape)})')
+    if tuple(sigma.shape) != (Np,):
+        raise ValueError(f'sigma must be [{Np}] (got {tuple(sigma.shape)})')
+    if ligand_ptr.numel() != B + 1 or B < 0:
+        raise ValueError('protein_ptr and ligand_ptr must have the same length B + 1')
+    if not check:     # a sampler's per-step call: the same offsets and radii were checked when it was set up
+        return B
+    if B > 0:         # the kernels index by these offsets: check them before anything runs (set-up / reporting path, one sync)
+        pp, lp = protein_ptr.cpu(), ligand_ptr.cpu()
+        if int(pp[0]) != 0 or int(lp[0]) != 0 or int(pp[-1]) != Np or int(lp[-1]) != Nl or bool((pp[1:] < pp[:-1]).any()) or \
+                bool((lp[1:] < lp[:-1]).any()):
+            raise ValueError('protein_ptr / ligand_ptr must be non-decreasing prefix offsets from 0 to N_p / N_l')
+    if Np > 0 and not bool((sigma > 0).all()):
+        raise ValueError('every contact radius must be > 0')
+    return B
+
+
+def clash_shift(protein_pos, sigma, protein_ptr, ligand_ptr, pos, weight=1.0, max_shift=0.0, out=None, check=True):
+    """The clash-guidance shift [N_l, 3] of the points ``pos`` (td_clash_shift, include/targetdiff_hip.h); no model handle needed.
+    ``check=False`` skips the host-side look at the offsets and radii (one synchronisation)."""
+    lib = load_library()
+    B = _clash_inputs(protein_pos, sigma, protein_ptr, ligand_ptr, pos, check)
+    if out is None:
+        out = torch.empty_like(pos)
+    with _on(pos.device):
+        _check(lib.td_clash_shift(_ptr(protein_pos, torch.float32, 'protein_pos'), _ptr(sigma, torch.float32, 'sigma'),
+                                  _ptr(protein_ptr, torch.int32, 'protein_ptr'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), B,
+                                  _ptr(pos, torch.float32, 'pos'), float(weight), float(max_shift), _ptr(out, torch.float32, 'out'),
+                                  _stream(pos.device)), 'td_clash_shift')
+    return out
+
+
+def clash_report(protein_pos, sigma, protein_ptr, ligand_ptr, pos):
+    """Per graph: (pairs with d < sigma [B] int32, energy [B] fp32, smallest distance [B] fp32) (td_clash_report)."""
+    lib = load_library()
+    B = _clash_inputs(protein_pos, sigma, protein_ptr, ligand_ptr, pos)
+    dev = pos.device
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    energy = torch.empty(B, dtype=torch.float32, device=dev)
+    min_dist = torch.empty(B, dtype=torch.float32, device=dev)
+    with _on(dev):
+        _check(lib.td_clash_report(_ptr(protein_pos, torch.float32, 'protein_pos'), _ptr(sigma, torch.float32, 'sigma'),
+                                   _ptr(protein_ptr, torch.int32, 'protein_ptr'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), B,
+                                   _ptr(pos, torch.float32, 'pos'), _ptr(count), _ptr(energy), _ptr(min_dist), _stream(dev)),
+               'td_clash_report')
+    return count, energy, min_dist
 
 
 def protein_centroids(protein_pos: torch.Tensor, protein_ptr: torch.Tensor) -> torch.Tensor:

@@ -219,7 +219,7 @@ int posterior_step_impl(const char *who, const td_model *m, const int32_t *d_t, 
                         const float *d_ligand_pos, const int64_t *d_ligand_v, const float *d_pred_pos, const float *d_pred_v,
                         const float *d_noise, const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
                         float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos, const int64_t *d_fixed_v,
-                        void *stream, const float *d_prog_row = nullptr) {
+                        void *stream, const float *d_prog_row = nullptr, const float *d_x0_shift = nullptr) {
     if (!m || N_l < 0 || B < 0) { td_set_error("%s: bad argument", who); return TD_EINVAL; }
     if (N_l == 0) return TD_OK;
     if (!d_t || !d_ligand_ptr || !d_ligand_pos || !d_ligand_v || !d_pred_pos || !d_pred_v || !d_noise || !d_uniform ||
@@ -239,7 +239,8 @@ int posterior_step_impl(const char *who, const td_model *m, const int32_t *d_t, 
     return td_launch_posterior(m->sched, m->cfg.num_timesteps, d_t, d_ligand_ptr, N_l, B, m->cfg.ligand_num_classes,
                                d_ligand_pos, d_ligand_v, d_pred_pos, d_pred_v, d_noise, d_uniform, d_pos_next,
                                d_v_next, d_log_v0, d_log_post, static_cast<hipStream_t>(stream), m->cfg.model_mean_type,
-                               d_fixed_mask, d_fixed_mask ? d_fixed_pos : nullptr, d_fixed_mask ? d_fixed_v : nullptr, d_prog_row);
+                               d_fixed_mask, d_fixed_mask ? d_fixed_pos : nullptr, d_fixed_mask ? d_fixed_v : nullptr, d_prog_row,
+                               d_x0_shift);
 }
 }  // namespace
 
@@ -287,6 +288,54 @@ extern "C" int td_renoise_step(const td_model *m, const float *d_prog_row, int64
     ProfScope ps(PC_POST, static_cast<hipStream_t>(stream));
     return td_launch_renoise(d_prog_row, N_l, m->cfg.ligand_num_classes, d_ligand_pos, d_ligand_v, d_noise, d_uniform, d_pos_next,
                              d_v_next, d_log_v0, d_log_q, static_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------------------------------------------ clash guidance
+extern "C" int td_posterior_step_guided(const td_model *m, const int32_t *d_t, const float *d_prog_row, const int32_t *d_ligand_ptr,
+                                        int64_t N_l, int64_t B, const float *d_ligand_pos, const int64_t *d_ligand_v,
+                                        const float *d_pred_pos, const float *d_pred_v, const float *d_noise,
+                                        const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
+                                        float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos,
+                                        const int64_t *d_fixed_v, const float *d_x0_shift, void *stream) {
+    return posterior_step_impl("td_posterior_step_guided", m, d_t, d_ligand_ptr, N_l, B, d_ligand_pos, d_ligand_v, d_pred_pos,
+                               d_pred_v, d_noise, d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_post, d_fixed_mask, d_fixed_pos,
+                               d_fixed_v, stream, d_prog_row, d_x0_shift);
+}
+
+namespace {
+int clash_args(const char *who, const float *d_protein_pos, const float *d_sigma, const int32_t *d_protein_ptr,
+               const int32_t *d_ligand_ptr, int64_t B, const float *d_pos, float w, float max_shift, TdClashArgs &a) {
+    if (B < 0 || B > 0x7fffffff) { td_set_error("%s: bad argument", who); return TD_EINVAL; }
+    if (B > 0 && (!d_protein_pos || !d_sigma || !d_protein_ptr || !d_ligand_ptr || !d_pos)) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    if (!(w >= 0.f)) { td_set_error("%s: the weight must be >= 0 (got %g)", who, (double)w); return TD_EINVAL; }
+    if (!(max_shift >= 0.f)) { td_set_error("%s: max_shift must be >= 0 (0: no cap; got %g)", who, (double)max_shift); return TD_EINVAL; }
+    a.ppos = d_protein_pos; a.sigma = d_sigma; a.pptr = d_protein_ptr; a.lptr = d_ligand_ptr; a.B = (int)B; a.eval = d_pos;
+    a.w = w; a.max_shift = max_shift;
+    return TD_OK;
+}
+}  // namespace
+
+extern "C" int td_clash_shift(const float *d_protein_pos, const float *d_sigma, const int32_t *d_protein_ptr,
+                              const int32_t *d_ligand_ptr, int64_t B, const float *d_pos, float w, float max_shift, float *d_shift,
+                              void *stream) {
+    TdClashArgs a;
+    const int rc = clash_args("td_clash_shift", d_protein_pos, d_sigma, d_protein_ptr, d_ligand_ptr, B, d_pos, w, max_shift, a);
+    if (rc != TD_OK) return rc;
+    if (B > 0 && !d_shift) { td_set_error("td_clash_shift: null pointer"); return TD_EINVAL; }
+    return td_launch_clash_shift(a, d_shift, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int td_clash_report(const float *d_protein_pos, const float *d_sigma, const int32_t *d_protein_ptr,
+                               const int32_t *d_ligand_ptr, int64_t B, const float *d_pos, int32_t *d_count, float *d_energy,
+                               float *d_min_dist, void *stream) {
+    TdClashArgs a;
+    const int rc = clash_args("td_clash_report", d_protein_pos, d_sigma, d_protein_ptr, d_ligand_ptr, B, d_pos, 0.f, 0.f, a);
+    if (rc != TD_OK) return rc;
+    if (B > 0 && (!d_count || !d_energy || !d_min_dist)) { td_set_error("td_clash_report: null pointer"); return TD_EINVAL; }
+    return td_launch_clash_report(a, d_count, d_energy, d_min_dist, static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------------------ standalone EGNN refine net

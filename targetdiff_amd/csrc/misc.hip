@@ -98,7 +98,10 @@ __device__ __forceinline__ int td_find_graph_l(const int32_t *__restrict__ ptr, 
 // `prow` (TD_PROG_ROW floats, td_prog_col order, built on the host by TimeProgram.tables) instead of the per-t tables, "t == 0" reads
 // "s is clean data" (prow[TD_PROG_LAST]), and the known atoms' level is s (prow[TD_PROG_ABAR_TO], log_ca / log_1mca of s).  The network
 // still ran at t: model_mean_type 'noise' takes rc[t] / rm1[t].  PROG = false compiles to the code without the feature.
-template <bool FIXED, bool PROG = false>
+// GUIDED (clash guidance): the step uses x0' = fl32(x0 + x0_shift[atom]) -- one rounded add on the x0 the line below
+// forms, on every step, the last included -- in place of x0.  Known atoms ignore it (they are overwritten).  GUIDED = false compiles to the
+// code without the feature.
+template <bool FIXED, bool PROG = false, bool GUIDED = false>
 __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, const int32_t *__restrict__ tg,
                                                   const int32_t *__restrict__ lptr, int B, int C, int64_t at,
                                                   const float *pos, const int64_t *v,
@@ -110,7 +113,8 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
                                                   int mean_type = 0, const uint8_t *__restrict__ fixed_mask = nullptr,
                                                   const float *__restrict__ fixed_pos = nullptr,
                                                   const int64_t *__restrict__ fixed_v = nullptr,
-                                                  const float *__restrict__ prow = nullptr) {
+                                                  const float *__restrict__ prow = nullptr,
+                                                  const float *__restrict__ x0_shift = nullptr) {
     const int g = td_find_graph_l(lptr, B, (int)at);
     int t = tg[g];
     t = t < 0 ? 0 : (t >= T ? T - 1 : t);
@@ -124,9 +128,9 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
                                       // same bits in every kernel this function is inlined into (no compiler-chosen FMA contraction)
     {
         const float xt = pos[at * 3 + d];
-        float x0 = pred_pos[at * 3 + d];
         // model_mean_type 'noise' (:412-416, :663-666): the network's output is x_t + eps; x0 = rc[t] x_t - rm1[t] eps
-        if (mean_type == 1) x0 = td_add_rn(td_mul_rn(sc.rc[t], xt), -td_mul_rn(sc.rm1[t], td_add_rn(x0, -xt)));
+        float x0 = td_x0_of_output(sc.rc, sc.rm1, t, mean_type, pred_pos[at * 3 + d], xt);
+        if (GUIDED) x0 = td_add_rn(x0, x0_shift[at * 3 + d]);
         xn[d] = td_add_rn(td_add_rn(td_mul_rn(c0, x0), td_mul_rn(ct, xt)), td_mul_rn(sd, noise[at * 3 + d]));
     }
     const int vt = (int)v[at];
@@ -203,7 +207,7 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
     if (v_cur) v_cur[at] = best;
 }
 
-template <bool FIXED, bool PROG = false>
+template <bool FIXED, bool PROG = false, bool GUIDED = false>
 __global__ void posterior_kernel(TdSchedules sc, int T, const int32_t *__restrict__ tg,
                                  const int32_t *__restrict__ lptr, int64_t Nl, int B, int C,
                                  const float *__restrict__ pos, const int64_t *__restrict__ v,
@@ -212,11 +216,13 @@ __global__ void posterior_kernel(TdSchedules sc, int T, const int32_t *__restric
                                  float *__restrict__ pos_next, int64_t *__restrict__ v_next,
                                  float *__restrict__ log_v0_out, float *__restrict__ log_post_out, int mean_type,
                                  const uint8_t *__restrict__ fixed_mask, const float *__restrict__ fixed_pos,
-                                 const int64_t *__restrict__ fixed_v, const float *__restrict__ prow) {
+                                 const int64_t *__restrict__ fixed_v, const float *__restrict__ prow,
+                                 const float *__restrict__ x0_shift) {
     const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (at >= Nl) return;
-    td_posterior_atom<FIXED, PROG>(sc, T, tg, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni, pos_next, v_next, log_v0_out,
-                                   log_post_out, nullptr, nullptr, false, mean_type, fixed_mask, fixed_pos, fixed_v, prow);
+    td_posterior_atom<FIXED, PROG, GUIDED>(sc, T, tg, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni, pos_next, v_next, log_v0_out,
+                                           log_post_out, nullptr, nullptr, false, mean_type, fixed_mask, fixed_pos, fixed_v, prow,
+                                           x0_shift);
 }
 
 // the last workgroup to finish advances the step index (all workgroups have read it by then): the launch is replayable as a graph node
@@ -234,7 +240,7 @@ __device__ __forceinline__ void td_step_handover(int32_t *__restrict__ step) {
 // td_session_step: the same update with its per-step arguments taken from device memory -- step index s = step[0] selects the
 // time-step row t_all[s] and slot s of the trajectories (PROG: and row s of the program's coefficient table); the current state
 // (pos / v) is updated in place.
-template <bool FIXED, bool PROG = false>
+template <bool FIXED, bool PROG = false, bool GUIDED = false>
 __global__ void posterior_step_kernel(TdSchedules sc, int T, int32_t *__restrict__ step, const int32_t *__restrict__ t_all,
                                       int num_steps, const int32_t *__restrict__ lptr, int64_t Nl, int B, int C,
                                       float *pos, int64_t *v, const float *__restrict__ pred_pos,
@@ -242,16 +248,18 @@ __global__ void posterior_step_kernel(TdSchedules sc, int T, int32_t *__restrict
                                       const float *__restrict__ uni, float *__restrict__ pos_traj, int64_t *__restrict__ v_traj,
                                       float *__restrict__ v0_traj, float *__restrict__ vt_traj, int pos_only, int mean_type,
                                       const uint8_t *__restrict__ fixed_mask, const float *__restrict__ fixed_pos,
-                                      const int64_t *__restrict__ fixed_v, const float *__restrict__ prog_table) {
+                                      const int64_t *__restrict__ fixed_v, const float *__restrict__ prog_table,
+                                      const float *__restrict__ x0_shift) {
     int s = *reinterpret_cast<volatile int32_t *>(step);
     s = s < 0 ? 0 : (s >= num_steps ? num_steps - 1 : s);
     const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (at < Nl) {
         const size_t so = (size_t)s * (size_t)Nl;
-        td_posterior_atom<FIXED, PROG>(sc, T, t_all + (size_t)s * B, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni,
-                                       pos_traj + so * 3, v_traj + so, v0_traj ? v0_traj + so * C : nullptr,
-                                       vt_traj ? vt_traj + so * C : nullptr, pos, pos_only ? nullptr : v, pos_only != 0, mean_type,
-                                       fixed_mask, fixed_pos, fixed_v, PROG ? prog_table + (size_t)s * TD_PROG_ROW : nullptr);
+        td_posterior_atom<FIXED, PROG, GUIDED>(sc, T, t_all + (size_t)s * B, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni,
+                                               pos_traj + so * 3, v_traj + so, v0_traj ? v0_traj + so * C : nullptr,
+                                               vt_traj ? vt_traj + so * C : nullptr, pos, pos_only ? nullptr : v, pos_only != 0,
+                                               mean_type, fixed_mask, fixed_pos, fixed_v,
+                                               PROG ? prog_table + (size_t)s * TD_PROG_ROW : nullptr, x0_shift);
     }
     td_step_handover(step);
 }
@@ -326,14 +334,22 @@ int td_launch_posterior(const TdSchedules &sc, int T, const int32_t *t, const in
                         int classes, const float *pos, const int64_t *v, const float *pred_pos,
                         const float *pred_v, const float *noise, const float *uni, float *pos_next,
                         int64_t *v_next, float *log_v0, float *log_post, hipStream_t s, int mean_type,
-                        const uint8_t *fixed_mask, const float *fixed_pos, const int64_t *fixed_v, const float *prow) {
+                        const uint8_t *fixed_mask, const float *fixed_pos, const int64_t *fixed_v, const float *prow,
+                        const float *x0_shift) {
     if (Nl == 0) return TD_OK;
     const dim3 grid((unsigned)((Nl + 127) / 128)), block(128);
-#define TD_POST(F, P, fm, fp, fv, pr)                                                                                                 \
-    posterior_kernel<F, P><<<grid, block, 0, s>>>(sc, T, t, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise, uni, pos_next, \
-                                                  v_next, log_v0, log_post, mean_type, fm, fp, fv, pr)
+#define TD_POST(F, P, fm, fp, fv, pr)                                                                                                  \
+    do {                                                                                                                               \
+        if (x0_shift)                                                                                                                  \
+            posterior_kernel<F, P, true><<<grid, block, 0, s>>>(sc, T, t, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise,   \
+                                                                uni, pos_next, v_next, log_v0, log_post, mean_type, fm, fp, fv, pr,    \
+                                                                x0_shift);                                                             \
+        else                                                                                                                           \
+            posterior_kernel<F, P><<<grid, block, 0, s>>>(sc, T, t, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise, uni,    \
+                                                          pos_next, v_next, log_v0, log_post, mean_type, fm, fp, fv, pr, nullptr);     \
+    } while (0)
     // known atoms present: the variant with the replacement branch (needs sc.abar, checked by the callers); a program slot: the
-    // variant that reads the slot's row
+    // variant that reads the slot's row; a shift of x0 (clash guidance): the variant that adds it -- no shift, the kernels as they were
     if (prow) { if (fixed_mask) TD_POST(true, true, fixed_mask, fixed_pos, fixed_v, prow); else TD_POST(false, true, nullptr, nullptr, nullptr, prow); }
     else if (fixed_mask) TD_POST(true, false, fixed_mask, fixed_pos, fixed_v, nullptr);
     else TD_POST(false, false, nullptr, nullptr, nullptr, nullptr);
@@ -346,13 +362,20 @@ int td_launch_posterior_step(const TdSchedules &sc, int T, int32_t *step, const 
                              int64_t Nl, int64_t B, int classes, float *pos, int64_t *v, const float *pred_pos, const float *pred_v,
                              const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
                              int pos_only, hipStream_t s, int mean_type, const uint8_t *fixed_mask, const float *fixed_pos,
-                             const int64_t *fixed_v, const float *prog_table) {
+                             const int64_t *fixed_v, const float *prog_table, const float *x0_shift) {
     if (Nl == 0) return TD_OK;
     const dim3 grid((unsigned)((Nl + 127) / 128)), block(128);
 #define TD_POST(F, P, fm, fp, fv, pt)                                                                                                  \
-    posterior_step_kernel<F, P><<<grid, block, 0, s>>>(sc, T, step, t_all, num_steps, lptr, Nl, (int)B, classes, pos, v, pred_pos,      \
-                                                       pred_v, noise, uni, pos_traj, v_traj, v0_traj, vt_traj, pos_only, mean_type, fm, \
-                                                       fp, fv, pt)
+    do {                                                                                                                               \
+        if (x0_shift)                                                                                                                  \
+            posterior_step_kernel<F, P, true><<<grid, block, 0, s>>>(sc, T, step, t_all, num_steps, lptr, Nl, (int)B, classes, pos, v,  \
+                                                                     pred_pos, pred_v, noise, uni, pos_traj, v_traj, v0_traj, vt_traj, \
+                                                                     pos_only, mean_type, fm, fp, fv, pt, x0_shift);                   \
+        else                                                                                                                           \
+            posterior_step_kernel<F, P><<<grid, block, 0, s>>>(sc, T, step, t_all, num_steps, lptr, Nl, (int)B, classes, pos, v,        \
+                                                               pred_pos, pred_v, noise, uni, pos_traj, v_traj, v0_traj, vt_traj,       \
+                                                               pos_only, mean_type, fm, fp, fv, pt, nullptr);                          \
+    } while (0)
     if (prog_table) { if (fixed_mask) TD_POST(true, true, fixed_mask, fixed_pos, fixed_v, prog_table); else TD_POST(false, true, nullptr, nullptr, nullptr, prog_table); }
     else if (fixed_mask) TD_POST(true, false, fixed_mask, fixed_pos, fixed_v, nullptr);
     else TD_POST(false, false, nullptr, nullptr, nullptr, nullptr);

@@ -69,6 +69,13 @@ struct td_session {
     const float *prog_table = nullptr;
     std::vector<int32_t> prog_kinds;
     size_t prog_next = 0;
+    // clash guidance (td_session_set_guidance): the centred protein + radii as float4 and the step's shift, in a block of their own
+    // (allocated at the first call, kept until the session goes); guide = on
+    char *guide_block = nullptr;
+    float4 *guide_prot4 = nullptr;
+    float *guide_shift = nullptr;
+    bool guide = false;
+    float guide_w = 0.f, guide_max = 0.f;
 };
 
 namespace tdapi {
@@ -105,6 +112,7 @@ void session_free(td_session *S, hipStream_t s) {
     session_drop_graph(S);
     if (S->chunked) plan_destroy(S->plan, s);
     free_async_or_sync(S->block, s);
+    free_async_or_sync(S->guide_block, s);
     delete S;
 }
 }  // namespace tdapi
@@ -476,11 +484,20 @@ int session_step_issue(td_session *S, const td_step_io &io, hipStream_t s) {
     int rc = td_session_forward(S, io.d_ligand_pos, io.d_ligand_v, S->pred_pos, S->pred_v, nullptr, io.d_ligand_graph_bias, s);
     if (rc != TD_OK) return rc;
     ProfScope ps(PC_POST, s);
+    if (S->guide) {
+        // clash guidance: the shift of the predicted x0, one launch between the denoiser and the posterior update
+        TdClashArgs a;
+        a.prot4 = S->guide_prot4; a.pptr = S->pptr; a.lptr = S->lptr; a.B = (int)S->B; a.eval = S->pred_pos;
+        a.w = S->guide_w; a.max_shift = S->guide_max;
+        a.mean_type = m->cfg.model_mean_type; a.T = m->cfg.num_timesteps; a.num_steps = io.num_steps;
+        a.xt = io.d_ligand_pos; a.rc = m->sched.rc; a.rm1 = m->sched.rm1; a.t_all = io.d_t_all; a.step = io.d_step;
+        if ((rc = td_launch_clash_shift(a, S->guide_shift, s)) != TD_OK) return rc;
+    }
     return td_launch_posterior_step(m->sched, m->cfg.num_timesteps, io.d_step, io.d_t_all, io.num_steps, S->lptr, S->Nl, S->B,
                                     m->cfg.ligand_num_classes, io.d_ligand_pos, io.d_ligand_v, S->pred_pos, S->pred_v, io.d_noise,
                                     io.d_uniform, io.d_pos_traj, io.d_v_traj, io.d_v0_traj, io.d_vt_traj, io.pos_only, s,
                                     m->cfg.model_mean_type, io.d_fixed_mask, io.d_fixed_mask ? io.d_fixed_pos : nullptr,
-                                    io.d_fixed_mask ? io.d_fixed_v : nullptr, S->prog_table);
+                                    io.d_fixed_mask ? io.d_fixed_v : nullptr, S->prog_table, S->guide ? S->guide_shift : nullptr);
 }
 }  // namespace tdapi
 
@@ -500,6 +517,39 @@ extern "C" int td_session_set_program(td_session *S, const float *d_prog_table, 
     return TD_OK;
 }
 
+extern "C" int td_session_set_guidance(td_session *S, const float *d_sigma, float w, float max_shift) {
+    if (!S) { td_set_error("td_session_set_guidance: bad argument"); return TD_EINVAL; }
+    if (d_sigma && !(w >= 0.f)) { td_set_error("td_session_set_guidance: the weight must be >= 0 (got %g)", (double)w); return TD_EINVAL; }
+    if (d_sigma && !(max_shift >= 0.f)) {
+        td_set_error("td_session_set_guidance: max_shift must be >= 0 (0: no cap; got %g)", (double)max_shift);
+        return TD_EINVAL;
+    }
+    session_drop_graph(S);          // the captured step holds, or does not hold, the shift kernel and the guided posterior
+    S->guide = false;
+    if (!d_sigma) return TD_OK;
+    hipStream_t s = S->last_stream;
+    if (!S->guide_block) {
+        const size_t b4 = align_up((size_t)S->Np * sizeof(float4)), bytes = b4 + align_up((size_t)S->Nl * 12);
+        hipError_t e = td_malloc_async(reinterpret_cast<void **>(&S->guide_block), bytes, s);
+        if (e != hipSuccess) {
+            td_set_error("td_session_set_guidance: hipMallocAsync(%zu) failed: %s", bytes, hipGetErrorString(e));
+            S->guide_block = nullptr;
+            return TD_ENOMEM;
+        }
+        S->guide_prot4 = reinterpret_cast<float4 *>(S->guide_block);
+        S->guide_shift = reinterpret_cast<float *>(S->guide_block + b4);
+    }
+    // the centred protein the session holds (its rows of the packed coordinates: written at creation, never by a step) + the radii.
+    // Cold path: wait, so that the caller may step on any stream and let go of nothing early.
+    const int rc = td_launch_clash_pack(S->w.x4a, S->prot_node, d_sigma, S->Np, S->guide_prot4, s);
+    if (rc != TD_OK) return rc;
+    TD_CHECK_HIP(hipStreamSynchronize(s));
+    S->guide = true;
+    S->guide_w = w;
+    S->guide_max = max_shift;
+    return TD_OK;
+}
+
 extern "C" int td_session_step(td_session *S, const td_step_io *io, int32_t use_graph, void *stream) {
     if (!S || !io || !io->d_step || !io->d_t_all || io->num_steps < 1 || !io->d_ligand_pos || !io->d_ligand_v || !io->d_noise ||
         !io->d_uniform || !io->d_pos_traj || !io->d_v_traj) {
@@ -512,6 +562,10 @@ extern "C" int td_session_step(td_session *S, const td_step_io *io, int32_t use_
     }
     if (io->d_fixed_mask && !S->m->sched.abar) {
         td_set_error("td_session_step: the model was created without alphas_cumprod (8 schedule arrays)");
+        return TD_EINVAL;
+    }
+    if (S->guide && S->m->cfg.model_mean_type == 1 && (!S->m->sched.rc || !S->m->sched.rm1)) {
+        td_set_error("td_session_step: guidance with model_mean_type 'noise' needs the 10 schedule arrays");
         return TD_EINVAL;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);

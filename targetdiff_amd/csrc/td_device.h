@@ -151,6 +151,15 @@ __device__ __forceinline__ float td_add_rn(float a, float b) {
     return a + b;
 }
 
+// The x0 a posterior step works with, from one coordinate of the network's output: the output itself (model_mean_type 'C0', 0), or for
+// 'noise' (1; models/molopt_score_model.py:412-416, :663-666), where the output is x_t + eps, x0 = rc[t] x_t - rm1[t] eps.  One function for
+// the posterior kernels (misc.hip) and the clash shift (guidance.hip): both see the same bits.
+__device__ __forceinline__ float td_x0_of_output(const float *__restrict__ rc, const float *__restrict__ rm1, int t, int mean_type,
+                                                 float out, float xt) {
+    if (mean_type == 1) return td_add_rn(td_mul_rn(rc[t], xt), -td_mul_rn(rm1[t], td_add_rn(out, -xt)));
+    return out;
+}
+
 // distance^2 with the project's fixed association and no FMA contraction (oracle/shims.py)
 __device__ __forceinline__ float td_dist2(float dx, float dy, float dz) {
     return td_add_rn(td_add_rn(td_mul_rn(dx, dx), td_mul_rn(dy, dy)), td_mul_rn(dz, dz));

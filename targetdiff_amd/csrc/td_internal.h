@@ -326,18 +326,38 @@ int td_launch_posterior(const TdSchedules &sc, int T, const int32_t *t, const in
                         const float *pred_v, const float *noise, const float *uni, float *pos_next,
                         int64_t *v_next, float *log_v0, float *log_post, hipStream_t s, int mean_type = 0,
                         const uint8_t *fixed_mask = nullptr, const float *fixed_pos = nullptr, const int64_t *fixed_v = nullptr,
-                        const float *prow = nullptr);
+                        const float *prow = nullptr, const float *x0_shift = nullptr);
 int td_launch_posterior_step(const TdSchedules &sc, int T, int32_t *step, const int32_t *t_all, int num_steps, const int32_t *lptr,
                              int64_t Nl, int64_t B, int classes, float *pos, int64_t *v, const float *pred_pos, const float *pred_v,
                              const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
                              int pos_only, hipStream_t s, int mean_type = 0, const uint8_t *fixed_mask = nullptr,
-                             const float *fixed_pos = nullptr, const int64_t *fixed_v = nullptr, const float *prog_table = nullptr);
+                             const float *fixed_pos = nullptr, const int64_t *fixed_v = nullptr, const float *prog_table = nullptr,
+                             const float *x0_shift = nullptr);
 // time programs: prow = one slot's TD_PROG_ROW floats, prog_table = every slot's (device memory); the renoise step of a slot
 int td_launch_renoise(const float *prow, int64_t Nl, int classes, const float *pos, const int64_t *v, const float *noise,
                       const float *uni, float *pos_next, int64_t *v_next, float *log_v0, float *log_q, hipStream_t s);
 int td_launch_renoise_step(const float *prog_table, int32_t *step, int num_steps, int64_t Nl, int classes, float *pos, int64_t *v,
                            const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
                            int pos_only, hipStream_t s);
+// guidance.hip (clash guidance): the arguments of one launch over B graphs.  Protein atoms either as ppos [N_p,3] +
+// sigma [N_p] or as prot4 [N_p] (x, y, z, sigma) (a session's packed copy).  eval [N_l,3]: the positions the energy is taken at; with
+// mean_type 1 (a session step of a model_mean_type 'noise' model) it is the network's output and x0 is formed from it, xt and the
+// schedule entries of the graph's time step t_all[step[0] * B + g], as the posterior kernel forms it.
+constexpr int TD_CLASH_TILE = 1024;
+struct TdClashArgs {
+    const float *ppos = nullptr, *sigma = nullptr;
+    const float4 *prot4 = nullptr;
+    const int32_t *pptr = nullptr, *lptr = nullptr;
+    int B = 0;
+    const float *eval = nullptr;
+    float w = 0.f, max_shift = 0.f;
+    int mean_type = 0, T = 0, num_steps = 0;
+    const float *xt = nullptr, *rc = nullptr, *rm1 = nullptr;
+    const int32_t *t_all = nullptr, *step = nullptr;
+};
+int td_launch_clash_shift(const TdClashArgs &a, float *shift, hipStream_t s);
+int td_launch_clash_report(const TdClashArgs &a, int32_t *count, float *energy, float *min_dist, hipStream_t s);
+int td_launch_clash_pack(const float4 *x4, const int32_t *prot_node, const float *sigma, int64_t Np, float4 *prot4, hipStream_t s);
 // egnn.hip / node.hip
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s);

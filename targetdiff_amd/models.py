@@ -567,11 +567,13 @@ class ScorePosNet3D(nn.Module):
     def begin_sampling(self, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, batch_ligand,
                        num_steps=None, center_pos_mode=None, max_graph_nodes=0, noise_source=None, use_session=True,
                        pos_only=False, generator=None, use_graph=None, *, fixed_mask=None, fixed_pos=None, fixed_v=None,
-                       time_program=None):
+                       time_program=None, guidance=None):
         """Set up the reverse-diffusion state on the device and return a :class:`ReverseSampler`
-        (``.step()`` = one iteration of the loop at models/molopt_score_model.py:650-693).  ``fixed_*`` / ``time_program``: see
-        :meth:`sample_diffusion`."""
+        (``.step()`` = one iteration of the loop at models/molopt_score_model.py:650-693).  ``fixed_*`` / ``time_program`` /
+        ``guidance``: see :meth:`sample_diffusion`."""
         extra = {} if time_program is None else dict(time_program=time_program)
+        if guidance is not None:
+            extra['guidance'] = guidance
         return ReverseSampler(self, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v,
                               batch_ligand, num_steps, center_pos_mode, max_graph_nodes, noise_source, use_session,
                               pos_only, generator, use_graph, fixed_mask=fixed_mask, fixed_pos=fixed_pos, fixed_v=fixed_v, **extra)
@@ -580,7 +582,7 @@ class ScorePosNet3D(nn.Module):
     def sample_diffusion(self, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, batch_ligand,
                          num_steps=None, center_pos_mode=None, pos_only=False, max_graph_nodes=0,
                          noise_source=None, use_session=True, use_graph=None, *, fixed_mask=None, fixed_pos=None,
-                         fixed_v=None, time_program=None):
+                         fixed_v=None, time_program=None, guidance=None):
         """Ancestral sampling loop (models/molopt_score_model.py:633-703).
 
         Differences from the reference are confined to *where* things run, not what is computed: no
@@ -619,11 +621,23 @@ class ScorePosNet3D(nn.Module):
         A program of unit steps (``TimeProgram.reference(T, n)``) is ``num_steps=n`` bit for bit.  Every step of either kind
         consumes one Gaussian and (unless ``pos_only``) one uniform draw of the per-step stream, renoise steps too.  Raises
         ValueError when given together with ``num_steps``, for a program of another T, for something that is not a TimeProgram,
-        and with an unsorted ``batch_ligand``.  Sample quality under strides is not assessed here."""
+        and with an unsorted ``batch_ligand``.  Sample quality under strides is not assessed here.
+
+        Clash guidance (not in the reference; DESIGN.md "Clash guidance"): ``guidance`` is a :class:`guidance.ClashGuidance`.  On
+        every denoise step the predicted x0 (the network's output for model_mean_type 'C0', the x0 formed from it for 'noise') is
+        shifted out of the protein atoms' contact spheres by -w grad E, E = 1/2 sum max(0, sigma_j - d_ij)^2 over the graph's
+        protein-ligand pairs, capped at ``max_shift`` per atom and step, and the posterior update runs on the shifted x0 -- on the
+        last step too, so the emitted pose is the corrected prediction.  No network gradient, no extra draw; known atoms
+        (``fixed_mask``) ignore the shift and renoise steps of a ``time_program`` are not guided.  With a session the shift is
+        one more kernel inside the replayed step.  ``guidance=None`` runs exactly the calls of the unguided sampler.  Raises
+        ValueError for something that is not a ClashGuidance, per-atom radii whose number is not the number of protein atoms,
+        and with an unsorted ``batch_ligand``.  Sample quality under guidance is not assessed here."""
         extra = {} if fixed_mask is None and fixed_pos is None and fixed_v is None else dict(
             fixed_mask=fixed_mask, fixed_pos=fixed_pos, fixed_v=fixed_v)
         if time_program is not None:
             extra['time_program'] = time_program
+        if guidance is not None:
+            extra['guidance'] = guidance
         sampler = self.begin_sampling(protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v,
                                       batch_ligand, num_steps, center_pos_mode, max_graph_nodes, noise_source,
                                       use_session=use_session, pos_only=pos_only, use_graph=use_graph, **extra)
@@ -638,7 +652,7 @@ class ReverseSampler:
     @torch.no_grad()
     def __init__(self, model, protein_pos, protein_v, batch_protein, init_ligand_pos, init_ligand_v, batch_ligand,
                  num_steps, center_pos_mode, max_graph_nodes, noise_source, use_session=True, pos_only=False, generator=None,
-                 use_graph=None, *, fixed_mask=None, fixed_pos=None, fixed_v=None, time_program=None):
+                 use_graph=None, *, fixed_mask=None, fixed_pos=None, fixed_v=None, time_program=None, guidance=None):
         self.pos_only = bool(pos_only)
         self.generator = generator          # None: torch's global generator (the reference's stream of draws)
         if center_pos_mode not in ('protein', 'none'):
@@ -649,13 +663,20 @@ class ReverseSampler:
         dev = protein_pos.device
         fixed = _check_fixed(fixed_mask, fixed_pos, fixed_v, init_ligand_pos.shape[0], model.num_classes, unsorted_l)
         self.program = program = _check_program(time_program, num_steps, model.num_timesteps, unsorted_l)
+        from .guidance import check_guidance
+        self.guidance = guidance = check_guidance(guidance, protein_pos.shape[0], unsorted_l)
         self.native = native = model._native(dev)
         T = model.num_timesteps
         num_steps = T if num_steps is None else num_steps
         self.B = B = int(batch_protein.max().item()) + 1                                 # :638 (once, not per step)
+        # clash guidance: one radius per protein atom, in the order the protein is handed to the kernels; the stateless path keeps its
+        # own shift buffer (a session holds one inside the library)
+        self._sigma = None if guidance is None else guidance.radii(protein_pos.shape[0], dev)
         if unsorted_p:              # the protein never changes: put it in compose_context's order once
             o = _stable_order(batch_protein)
             protein_pos, protein_v, batch_protein = protein_pos[o], protein_v[o], batch_protein[o]
+            if self._sigma is not None:
+                self._sigma = self._sigma[o].contiguous()
         # Unsorted ligand vector: the reference's loop keeps its state (ligand_pos / ligand_v, :644-646) in INPUT order while every
         # forward returns its predictions in compose_context's order, and combines the two element by element (:663-685).  Reproduced
         # as it is: the state stays in input order, each step gathers it into graph order for the denoiser (the slow two-call form
@@ -736,6 +757,13 @@ class ReverseSampler:
                                                      self.pos_only, ligand_graph_bias=self._gbias, **self._fixed)
                 if program is not None:
                     self.session.set_program(self._prog_table, self._prog_kinds)
+                if guidance is not None:
+                    self.session.set_guidance(self._sigma, guidance.weight, guidance.max_shift)
+        self._shift = None
+        if guidance is not None:
+            capi._clash_inputs(self.ppos, self._sigma, self.pptr, self.lptr, self.lpos)       # offsets and radii, once
+            if self.session is None:
+                self._shift = torch.empty(Nl, 3, dtype=torch.float32, device=dev)
 
     def _graph_now(self):
         """Replay the step as a captured hipGraph?  ``use_graph=None`` (default): when the caller runs on a real stream (the
@@ -802,6 +830,16 @@ class ReverseSampler:
                                          max_graph_nodes=self.max_graph_nodes, want_final_h=False, out=self.bufs,
                                          ligand_graph_bias=self._gbias)
         self.bufs = preds
+        if self.guidance is not None:
+            # forward -> shift of the predicted x0 -> guided posterior, from the public pieces (what a session step fuses)
+            x0 = preds['pred_ligand_pos']
+            if self.model.model_mean_type == 'noise':       # the x0 the posterior kernel forms (:412-416), each operation rounded on its own
+                m, t = self.model, self.t_all[s][self.batch_ligand].long()
+                rc, rm1 = m.sqrt_recip_alphas_cumprod.float()[t].unsqueeze(-1), m.sqrt_recipm1_alphas_cumprod.float()[t].unsqueeze(-1)
+                x0 = rc * self.lpos - rm1 * (x0 - self.lpos)
+            g = self.guidance
+            prog = dict(prog, x0_shift=capi.clash_shift(self.ppos, self._sigma, self.pptr, self.lptr, x0.contiguous(), g.weight,
+                                                        g.max_shift, out=self._shift, check=False))
         if self.pos_only:
             native.posterior_step(self.t_all[s], self.lptr, self.lpos, self.lv, preds['pred_ligand_pos'],
                                   preds['pred_ligand_v'], self._noise, self._half, pos_next=self.pos_traj[s],

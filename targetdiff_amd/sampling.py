@@ -89,7 +89,7 @@ def sample_diffusion_ligand(model, data, num_samples, batch_size=16, device='cud
                             pos_only=False, center_pos_mode='protein', sample_num_atoms='prior',
                             atom_num_sampler=None, ligand_num_atoms=None, generator=None, noise_source=None,
                             overlap_batches=False, max_resident_batches=8, use_graph=None, fixed_ligand_index=None,
-                            time_program=None):
+                            time_program=None, guidance=None):
     """Returns (pred_pos, pred_v, pred_pos_traj, pred_v_traj, pred_v0_traj, pred_vt_traj, time_list).
 
     Extra keyword arguments (not in the reference signature; all optional): ``atom_num_sampler`` / ``ligand_num_atoms``
@@ -116,10 +116,16 @@ def sample_diffusion_ligand(model, data, num_samples, batch_size=16, device='cud
 
     ``time_program`` (a ``schedule.TimeProgram``, see ScorePosNet3D.sample_diffusion; excludes ``num_steps``): the one program every
     sample batch runs, in the overlapped mode too.  The result tuple keeps its layout; the trajectories have ``len(time_program)``
-    entries, one per step of either kind."""
+    entries, one per step of either kind.
+
+    ``guidance`` (a ``guidance.ClashGuidance``, see ScorePosNet3D.sample_diffusion): clash guidance for every sample batch.  A scalar
+    radius, or one radius per atom of the pocket, is replicated per sample.  The result tuple keeps its layout."""
     if time_program is not None and num_steps is not None:
         raise ValueError('time_program and num_steps exclude each other')
     pocket = _as_pocket(data)
+    if guidance is not None:
+        from .guidance import check_guidance
+        check_guidance(guidance, pocket.num_atoms, False)
     fixed_ref = _fixed_reference(data, fixed_ligand_index, getattr(model, 'num_classes', None))
     pocket_dev = None
     time_list = []
@@ -174,6 +180,8 @@ def sample_diffusion_ligand(model, data, num_samples, batch_size=16, device='cud
             kw.update(_fixed_arguments(fixed_ref, sizes, device))
         if time_program is not None:
             kw['time_program'] = time_program
+        if guidance is not None:
+            kw['guidance'] = guidance.replicated(pocket.num_atoms, n_data)
         if noise_source is not None:
             kw['noise_source'] = (lambda st, name, like, _i=i: noise_source(_i, st, name, like))
         if overlap_batches:

@@ -6,6 +6,7 @@
                                  [--num_samples 100] [--num_steps 1000] [--batch_size 100] [--start_idx 0]
                                  [--checkpoint ckpt.pt] [--seed 2021]
                                  [--sample-steps K [--jump-length J --resamplings R]]
+                                 [--clash-guidance RADIUS[:WEIGHT[:MAX_SHIFT]]]
 
 * pocket i is sampled by rank i % world (scripts/batch_sample_diffusion.sh:15-17), from --start_idx on (:13);
 * every pocket ends in ``OUT/result_{i}.pt`` with the keys scripts/sample_diffusion.py:175-182 saves (consumed by
@@ -83,6 +84,8 @@ def main(argv=None, model_factory=build_model):
                     'TimeProgram.strided(T, K) instead of --num_steps levels of the reference chain (0: off)')
     ap.add_argument('--jump-length', type=int, default=0, help='with --sample-steps: RePaint resampling jumps of this many program steps')
     ap.add_argument('--resamplings', type=int, default=1, help='with --jump-length: times each stretch is sampled')
+    ap.add_argument('--clash-guidance', default='', metavar='RADIUS[:WEIGHT[:MAX_SHIFT]]', help='shift every step\'s predicted ligand out '
+                    'of the protein atoms\' contact spheres of RADIUS Angstrom (guidance.ClashGuidance; empty: off)')
     ap.add_argument('--device', default='cuda', help="'cuda' (rank r uses GPU LOCAL_RANK) or 'cpu' (tests: gloo + stub model)")
     args = ap.parse_args(argv)
     if argv is None:
@@ -122,6 +125,12 @@ def main(argv=None, model_factory=build_model):
         steps_kw = {'time_program': program}
     elif args.jump_length > 0:
         ap.error('--jump-length needs --sample-steps')
+    if args.clash_guidance:
+        from targetdiff_amd.guidance import ClashGuidance
+        try:
+            steps_kw['guidance'] = ClashGuidance.parse(args.clash_guidance)
+        except ValueError as exc:
+            ap.error(f'--clash-guidance: {exc}')
     log = []
 
     def on_pocket(idx, seconds, skipped):

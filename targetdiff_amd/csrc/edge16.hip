@@ -35,12 +35,6 @@ __device__ __forceinline__ floatx4_t td_mfma16(float a, float b, floatx4_t c) {
 // rounds each of its 128 (32) partial sums to 24 bits, so the two differ by about one fp32 rounding of the result -- measured on the
 // goldens of the real reference incl. its float64 runs (profiles/r06*_second_layer_error.txt).  Model option "edge_second_layer_f16"
 // (default 1; 0 = the fp32 products) selects between the instantiations.
-#ifndef TD_ZPLAIN_OFF
-#define TD_ZPLAIN_OFF 0   // 1: every MLP takes the scaled pieces (A/B of the two conversions)
-#endif
-#ifndef TD_ABL
-#define TD_ABL 0          // timing ablations of the key pass (wrong results; EXPERIMENTS.md round 6): 1 no U_i FMAs, 2 no Wq reads, 3 no z'' split, 4 no first-layer products, 5 no P_j gathers, 6 no logits products
-#endif
 typedef _Float16 half8_16 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ floatx4_t td_mfma16h(uint4 a, uint4 b, floatx4_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_16, a), __builtin_bit_cast(half8_16, b), c, 0, 0, 0);
@@ -53,27 +47,15 @@ __device__ __forceinline__ void td_split_h2(float x, float y, unsigned &h1, unsi
         "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
         : "=&v"(h2) : "v"(h1), "v"(x), "v"(y));
 }
-// The same for values in [0, 1] that may sit far below 1 (z'' = activation / (|gamma| M): around 1 / M, and M grows with the largest
+// The scaled form, for values in [0, 1] that may sit far below 1 (z'' = activation / (|gamma| M): around 1 / M, and M grows with the largest
 // LayerNorm bias / |weight| of the MLP): the pieces are taken of x S with S = 2^15, exactly, so that 22 bits survive down to x = 2^-18 instead
 // of running into the f16 subnormal floor at 2^-25 -- h1 = f16(x S) (round to nearest), h2 = f16(x S - h1): two v_fma_mix per piece pair
 // member, S as a scalar operand.  The consumer takes 1 / S off its result.
 constexpr float TD_Z_SCALE = 32768.0f;
-__device__ __forceinline__ void td_split_h2_scaled(float x, float y, unsigned &h1, unsigned &h2) {
-    const float S = TD_Z_SCALE;
-    asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
-        "v_fma_mixhi_f16 %0, %3, %4, 0\n\t"
-        "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(h1), "=&v"(h2) : "v"(x), "v"(y), "s"(S));
-}
 // Four pairs at once, the sixteen instructions interleaved so that no instruction reads the register the one before it wrote (a pair's four
 // conversions are a dependent chain through the two halves of h1 and h2: issued back to back, as one statement per pair does, every one of
 // them waits out its predecessor's latency -- PMC had 7.6 cycles of SQ_ACTIVE_INST_VALU per added instruction against 4.1 for the rest).
-#ifndef TD_SPLIT_X4
-#define TD_SPLIT_X4 1
-#endif
 __device__ __forceinline__ void td_split_h2_scaled_x4(const float (&x)[4], const float (&y)[4], unsigned (&h1)[4], unsigned (&h2)[4]) {
-#if TD_SPLIT_X4
     const float S = TD_Z_SCALE;
     asm("v_fma_mixlo_f16 %0, %8, %16, 0\n\t"
         "v_fma_mixlo_f16 %1, %9, %16, 0\n\t"
@@ -93,14 +75,9 @@ __device__ __forceinline__ void td_split_h2_scaled_x4(const float (&x)[4], const
         "v_fma_mixhi_f16 %7, %15, %16, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
         : "=&v"(h1[0]), "=&v"(h1[1]), "=&v"(h1[2]), "=&v"(h1[3]), "=&v"(h2[0]), "=&v"(h2[1]), "=&v"(h2[2]), "=&v"(h2[3])
         : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]), "s"(S));
-#else
-#pragma unroll
-    for (int m = 0; m < 4; ++m) td_split_h2_scaled(x[m], y[m], h1[m], h2[m]);
-#endif
 }
 // (plain form, four pairs: the truncations by the compiler's own v_cvt_pkrtz_f16_f32, the residuals interleaved)
 __device__ __forceinline__ void td_split_h2_x4(const float (&x)[4], const float (&y)[4], unsigned (&h1)[4], unsigned (&h2)[4]) {
-#if TD_SPLIT_X4
 #pragma unroll
     for (int m = 0; m < 4; ++m) h1[m] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x[m], y[m]));
     asm("v_fma_mixlo_f16 %0, %4, -1.0, %8 op_sel_hi:[1,0,0]\n\t"
@@ -113,10 +90,6 @@ __device__ __forceinline__ void td_split_h2_x4(const float (&x)[4], const float 
         "v_fma_mixhi_f16 %3, %7, -1.0, %15 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
         : "=&v"(h2[0]), "=&v"(h2[1]), "=&v"(h2[2]), "=&v"(h2[3])
         : "v"(h1[0]), "v"(h1[1]), "v"(h1[2]), "v"(h1[3]), "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]));
-#else
-#pragma unroll
-    for (int m = 0; m < 4; ++m) td_split_h2(x[m], y[m], h1[m], h2[m]);
-#endif
 }
 
 constexpr float TD_ATT_SCALE_16 = 0.35355339059327373f;   // 1/sqrt(8)
@@ -312,7 +285,7 @@ __device__ __forceinline__ void td_row_gather16(const Args16 &a, int64_t i, int6
         const float *pj = a.P + (size_t)jj * (4 * TD_H) + a.p_off + TD_H + 4 * g;
 #pragma unroll
         for (int hb = 0; hb < 8; ++hb) {
-            const float4 v = TD_ABL == 5 ? make_float4(0.1f, 0.2f, -0.1f, 0.3f) : *reinterpret_cast<const float4 *>(pj + 16 * hb);
+            const float4 v = *reinterpret_cast<const float4 *>(pj + 16 * hb);
             acc[eb][hb][0] = v.x; acc[eb][hb][1] = v.y; acc[eb][hb][2] = v.z; acc[eb][hb][3] = v.w;
         }
     }
@@ -371,7 +344,7 @@ __device__ __forceinline__ void td_ln_relu16_skip(const float *__restrict__ KB, 
 // The same LayerNorm + ReLU with z'' leaving as f16 piece pairs for the value pass's aggregation product (td_split_h2): word r of
 // z1[hb] / z2[hb] = pieces of hidden unit 16hb + 4g + r for the lane's two edges (low half: edge lo, high half: edge 16 + lo) -- after the
 // flip through the wave's LDS tile a word is two K slots of the A operand.
-// SCALED: the pieces are taken of z'' 2^15 (td_split_h2_scaled: four conversions per pair); otherwise of z'' itself (three: a truncation and
+// SCALED: the pieces are taken of z'' 2^15 (td_split_h2_scaled_x4: four conversions per pair); otherwise of z'' itself (three: a truncation and
 // two residuals, 30 % less conversion time) -- which the caller picks for MLPs whose folded scale M is small (TdEdgeMlp::z_plain, pack.cpp):
 // z'' is around 1 / M, and only above 2^-6 do the pieces of the plain form keep 19 bits or more over the f16 subnormal floor.
 // (NEB = 1, the chunk walk's half-empty chunk: the second block's halves of the words are zero)
@@ -445,8 +418,7 @@ __device__ __forceinline__ void td_ln_relu16_pairs_k(const float *__restrict__ K
             const float y[4] = {td_clamp01(fmaf(acc[eb][2 * t][1], sc[eb], kb0.y)), td_clamp01(fmaf(acc[eb][2 * t][3], sc[eb], kb0.w)),
                                 td_clamp01(fmaf(acc[eb][2 * t + 1][1], sc[eb], kb1.y)), td_clamp01(fmaf(acc[eb][2 * t + 1][3], sc[eb], kb1.w))};
             unsigned w1[4], w2[4];
-            if (TD_ABL == 3) { for (int m = 0; m < 4; ++m) { w1[m] = __float_as_uint(x[m]); w2[m] = __float_as_uint(y[m]); } }
-            else if constexpr (SCALED) td_split_h2_scaled_x4(x, y, w1, w2);
+            if constexpr (SCALED) td_split_h2_scaled_x4(x, y, w1, w2);
             else td_split_h2_x4(x, y, w1, w2);
             z1[eb][t] = make_uint4(w1[0], w1[1], w1[2], w1[3]);
             z2[eb][t] = make_uint4(w2[0], w2[1], w2[2], w2[3]);
@@ -549,7 +521,7 @@ __device__ __forceinline__ void td_split_pair(float x, float y, unsigned &p1, un
 constexpr int E16Q_GLOBAL_CS_U4 = 512 + 512 + 256 + 512;
 template <int PK> constexpr int e16q_cs_u4() { return PK == 5 ? 512 + 512 : (PK == 1 ? 512 + 512 + 512 : 512 + 512 + 256); }     // (PK = 5: the f16 piece-pair table, pack_h2_table)
 template <int PK> constexpr int e16q_u4() { return PK == 3 ? 2 * e16q_cs_u4<2>() + 2 * e16q_cs_u4<1>() : 4 * e16q_cs_u4<PK>(); }   // all four (dst class, source class) tables
-template <int PK> constexpr int e16q_half_u4() { return PK == 4 ? e16q_cs_u4<2>() + e16q_cs_u4<1>() : 2 * e16q_cs_u4<PK>(); }      // one destination class
+template <int PK> constexpr int e16q_half_u4() { return 2 * e16q_cs_u4<PK>(); }      // one destination class
 // stage `ncs` consecutive (dst class, source class) tables from the packed blob into LDS (all waves of the workgroup; the caller's
 // barrier publishes them)
 template <int PK>
@@ -620,7 +592,7 @@ __device__ __forceinline__ void td_pk4_tiles(const uint4 *__restrict__ Rs, int l
             for (int pass = 0; pass < (kind == 2 ? 2 : 1); ++pass) {
                 const int tb = kind == 0 ? 3 : (kind == 1 ? 2 : 1 - pass);
 #pragma unroll
-                for (int eb = 0; eb < NEB; ++eb) { if (TD_ABL != 4) acc[eb][hb] = td_mfma16b(cur, bq[eb][tb], acc[eb][hb]); else acc[eb][hb][0] += __uint_as_float(cur.x ^ bq[eb][tb].y); }
+                for (int eb = 0; eb < NEB; ++eb) acc[eb][hb] = td_mfma16b(cur, bq[eb][tb], acc[eb][hb]);
             }
             cur = nxt;
         }
@@ -826,12 +798,6 @@ __device__ __forceinline__ void td_first_layer_split16(const Args16 &a, const ui
             static_assert(PK != 3 || !ONE_CLASS, "PK = 3 holds both destination classes");
             if (cls) td_pk4_tiles<1, AH, NEB>(Rp + 2 * e16q_cs_u4<2>() + (size_t)sl * e16q_cs_u4<1>() + lane, lane, bq, acc);
             else td_pk4_tiles<2, AH, NEB>(Rp + (size_t)sl * e16q_cs_u4<2>() + lane, lane, bq, acc);
-        } else if constexpr (PK == 4) {
-            // one destination class resident (12-wave value pass): its ligand-source table (mixed rows only) in the 40-byte form, its
-            // protein-source table in the 48-byte form -- 44 KiB
-            static_assert(PK != 4 || ONE_CLASS, "PK = 4 holds one destination class");
-            if (sl) td_pk4_tiles<1, AH, NEB>(Rp + e16q_cs_u4<2>() + lane, lane, bq, acc);
-            else td_pk4_tiles<2, AH, NEB>(Rp + lane, lane, bq, acc);
         } else
             td_pk4_tiles<PK, AH, NEB>(Rp + (size_t)((ONE_CLASS ? 0 : cls * 2) + sl) * e16q_cs_u4<PK>() + lane, lane, bq, acc);
         }
@@ -868,9 +834,6 @@ constexpr size_t K16_LDS_BYTES = (size_t)(E16_R_FLOATS + E16_WQ_FLOATS + TD_H + 
 #ifndef TD_KEY_WAVES
 #define TD_KEY_WAVES 12
 #endif
-#ifndef TD_KEY_WALK_F16
-#define TD_KEY_WALK_F16 1          // f16 logits in the chunk-walking key pass, where its first layer runs on f16 pairs too (td_launch_edge_key16)
-#endif
 constexpr int K16S_WAVES = TD_KEY_WAVES;     // 16-bit first layer: <= 168 VGPRs -> 3 waves per SIMD, the piece tables (88 KiB bf16 triples / 64 KiB f16 pairs) + Wq in LDS
 #ifndef TD_KEY_PK
 #define TD_KEY_PK 3
@@ -880,6 +843,7 @@ constexpr int K16S_WAVES = TD_KEY_WAVES;     // 16-bit first layer: <= 168 VGPRs
 #endif
 constexpr size_t K16S_LDS_BYTES = (size_t)(e16q_u4<TD_KEY_PK>() * 4 + E16_WQ_FLOATS + TD_H + 4 + 32) * sizeof(float);
 static_assert(K16S_LDS_BYTES <= 160 * 1024, "key pass: LDS");        // + the row counter, the Gaussian centres
+template <bool SPLIT> constexpr size_t key16_lds_bytes() { return SPLIT ? K16S_LDS_BYTES : K16_LDS_BYTES; }      // dynamic LDS of edge_key16_kernel<.., SPLIT, ..>
 
 // XV = false: key pass (logits -> softmax -> alpha).
 // XV = true : h2x value pass.  xv[e][head] = W2xv[head, :] . z_e + b has the shape of the logits product with a static
@@ -906,7 +870,7 @@ __global__ __launch_bounds__(WAVES * 64) void edge_key16_kernel(Args16 a) {
     constexpr bool CHUNKED = GRAPH == 1;       // walks the chunks of a row
     constexpr bool VIA = GRAPH == 2;           // one chunk per row, found through cptr; ligand rows are somebody else's
     // logits on v_mfma_f32_16x16x32_f16 (f16 piece pairs): the x2h key pass on rows of one chunk (the default graph, the protein rows of a
-    // `hybrid` graph) and, with the first layer on f16 pairs, the chunk walk (TD_KEY_WALK_F16).  (The unfused h2x key pass keeps the fp32
+    // `hybrid` graph) and, with the first layer on f16 pairs, the chunk walk (td_launch_edge_key16).  (The unfused h2x key pass keeps the fp32
     // product: the fused and the unfused form of that stage run different kernels on the same rows and are held bit-identical.)
     constexpr bool L2H = L2 != 0;
     static_assert(L2 == 0 || (SPLIT && !XV && STAGE == 0), "f16 logits: x2h key pass, bf16 first layer");
@@ -1111,7 +1075,6 @@ __global__ __launch_bounds__(WAVES * 64) void edge_key16_kernel(Args16 a) {
             uint4 pu1 = make_uint4(0u, 0u, 0u, 0u), pu2 = pu1;
             auto product = [&](int t, int m) {                  // product m of K block t: the small ones first, on their own accumulators
                 const int eb = m & 1, kind = m >> 1;
-                if (TD_ABL == 6) { lg[eb][0] += __uint_as_float(pu1.x ^ zk1[eb][t].x ^ pu2.y ^ zk2[eb][t].y); return; }
                 if (CHUNKED && eb == 1 && !ed.any[1]) return;          // an all-pad second block is skipped
                 if (kind == 0) lgc[eb] = td_mfma16h(pu2, zk1[eb][t], lgc[eb]);
                 else if (kind == 1) lgc[eb] = td_mfma16h(pu1, zk2[eb][t], lgc[eb]);
@@ -1122,16 +1085,14 @@ __global__ __launch_bounds__(WAVES * 64) void edge_key16_kernel(Args16 a) {
 #pragma unroll
             for (int kk = 0; kk < 32; ++kk) {
                 float4 n0 = w0, n1 = w1;
-                if (kk + 1 < 32 && TD_ABL != 2) {
+                if (kk + 1 < 32) {
                     n0 = Wq[((kk + 1) * 2 + 0) * 64 + lane];
                     n1 = Wq[((kk + 1) * 2 + 1) * 64 + lane];
                 }
                 __builtin_amdgcn_sched_barrier(0);         // the reads stay in front of this k-step's arithmetic
                 float u = w0.x * q0.x;
-                if (TD_ABL != 1) {
                 u = fmaf(w0.y, q0.y, u); u = fmaf(w0.z, q0.z, u); u = fmaf(w0.w, q0.w, u);
                 u = fmaf(w1.x, q1.x, u); u = fmaf(w1.y, q1.y, u); u = fmaf(w1.z, q1.z, u); u = fmaf(w1.w, q1.w, u);
-                } else u += w1.w;
                 uu[kk & 7] = u;
                 if (kk >= 8 && (kk & 7) < 6) product((kk >> 3) - 1, kk & 7);
                 if ((kk & 7) == 7) {
@@ -1603,6 +1564,7 @@ constexpr size_t V16_LDS_BYTES =
 constexpr size_t V16S_LDS_BYTES =
     (size_t)(e16q_half_u4<TD_VALUE_PK>() * 4 + V16_W_FLOATS + V16_WAVES * V16_WAVE_FLOATS + V16_WAVES * V16_SB_FLOATS + 2 * TD_H + 4 + 32) * sizeof(float);
 static_assert(V16S_LDS_BYTES <= 160 * 1024, "value pass: LDS");
+template <bool SPLIT> constexpr size_t value16_lds_bytes() { return SPLIT ? V16S_LDS_BYTES : V16_LDS_BYTES; }    // dynamic LDS of edge_value16_kernel<SPLIT, ..>
 
 // SPLIT = true: the first layer on bf16 piece triples.  LDS has room for one destination class of the K-packed piece table
 // (48 KiB), so the workgroups of a launch specialise: the last GL stage the ligand-destination half and walk the ligand
@@ -2175,10 +2137,7 @@ __global__ __launch_bounds__(V16T_WAVES * 64) void edge_value16t_kernel(Args16 a
     {
         if constexpr (VPK == 5)
             td_stage_lds16(reinterpret_cast<const float4 *>(a.mlp.R16h) + (size_t)my_cls * 2 * e16q_cs_u4<5>(), reinterpret_cast<float4 *>(lds), 2 * e16q_cs_u4<5>(), tid, WAVES * 64);
-        else if constexpr (V16T_PK == 4) {
-            td_stage_pk4<2>(a.mlp.R16q + (size_t)my_cls * 2 * E16Q_GLOBAL_CS_U4 * 4, lds, 1, tid, WAVES * 64);
-            td_stage_pk4<1>(a.mlp.R16q + (size_t)(my_cls * 2 + 1) * E16Q_GLOBAL_CS_U4 * 4, lds + e16q_cs_u4<2>() * 4, 1, tid, WAVES * 64);
-        } else
+        else
             td_stage_pk4<V16T_PK>(a.mlp.R16q + (size_t)my_cls * 2 * E16Q_GLOBAL_CS_U4 * 4, lds, 2, tid, WAVES * 64);
         td_stage_lds16(reinterpret_cast<const float4 *>(a.mlp.Walt), reinterpret_cast<float4 *>(lds + RF), V16_W_FLOATS / 4, tid, WAVES * 64);
         if (tid < TD_H) B2[tid] = a.mlp.b2[tid];
@@ -2426,11 +2385,80 @@ __global__ __launch_bounds__(G16_WAVES * 64) void edge_gate16_kernel(TdGate gt, 
 }
 
 // ================================================================================================ launchers
+// The kernels this file ships, in the order the module carries them.  The launchers below only choose among these.  The order is part
+// of the build: the code the compiler emits for a kernel depends on which instantiations came before it, so a new kernel goes where
+// its first launch site would have put it and the others keep their places.
+//   edge_key16_kernel<XV, WAVES, STAGE, GRAPH, SPLIT, L2, FL>
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 2, true, 0, 1>(Args16);      // x2h, protein rows of a `hybrid` graph
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 2, true, 0, 0>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 2, true, 2, 1>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 2, true, 2, 0>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 2, true, 1, 1>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 2, true, 1, 0>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 1, true, 0, 1>(Args16);      // x2h, chunk walk (no f16 logits beside the bf16 first layer)
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 1, true, 0, 0>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 1, true, 2, 1>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 1, true, 1, 1>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 1, 1, true, 0, 1>(Args16);      // unfused h2x key pass (fp32 logits)
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 1, 1, true, 0, 0>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 1, 0, true, 0, 1>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 1, 0, true, 0, 0>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 0, true, 0, 1>(Args16);      // x2h, default graph
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 0, true, 0, 0>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 0, true, 2, 1>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 0, true, 2, 0>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 0, true, 1, 1>(Args16);
+template __global__ void edge_key16_kernel<false, K16S_WAVES, 0, 0, true, 1, 0>(Args16);
+template __global__ void edge_key16_kernel<false, K16_WAVES, 1, 1, false, 0, 0>(Args16);      // fp32 first layer
+template __global__ void edge_key16_kernel<false, K16_WAVES, 0, 1, false, 0, 0>(Args16);
+template __global__ void edge_key16_kernel<false, K16_WAVES, 1, 0, false, 0, 0>(Args16);
+template __global__ void edge_key16_kernel<false, K16_WAVES, 0, 0, false, 0, 0>(Args16);
+template __global__ void edge_key16_kernel<true, XV16_WAVES, 1, 1, true, 0, 1>(Args16);       // unfused h2x value pass
+template __global__ void edge_key16_kernel<true, XV16_WAVES, 1, 0, true, 0, 1>(Args16);
+template __global__ void edge_key16_kernel<true, XV16_WAVES, 1, 1, true, 0, 0>(Args16);
+template __global__ void edge_key16_kernel<true, XV16_WAVES, 1, 0, true, 0, 0>(Args16);
+template __global__ void edge_key16_kernel<true, XV16_WAVES, 1, 1, false, 0, 0>(Args16);
+template __global__ void edge_key16_kernel<true, XV16_WAVES, 1, 0, false, 0, 0>(Args16);
+//   edge_value16t_kernel<L2, VIA, FL>, edge_value16_kernel<SPLIT, CHUNKED, GATE_M, L2, FL>
+template __global__ void edge_value16t_kernel<0, true, 1>(Args16);                            // protein rows of a `hybrid` graph
+template __global__ void edge_value16t_kernel<0, true, 0>(Args16);
+template __global__ void edge_value16t_kernel<2, true, 1>(Args16);
+template __global__ void edge_value16t_kernel<2, true, 0>(Args16);
+template __global__ void edge_value16t_kernel<1, true, 1>(Args16);
+template __global__ void edge_value16t_kernel<1, true, 0>(Args16);
+template __global__ void edge_value16_kernel<true, true, false, 0, 1>(Args16);                // chunk walk
+template __global__ void edge_value16_kernel<true, true, false, 0, 0>(Args16);
+template __global__ void edge_value16_kernel<true, true, false, 2, 1>(Args16);
+template __global__ void edge_value16_kernel<true, true, false, 2, 0>(Args16);
+template __global__ void edge_value16_kernel<true, true, false, 1, 1>(Args16);
+template __global__ void edge_value16_kernel<true, true, false, 1, 0>(Args16);
+template __global__ void edge_value16_kernel<true, false, true, 0, 1>(Args16);                // ew_net_type 'm'
+template __global__ void edge_value16_kernel<true, false, true, 0, 0>(Args16);
+template __global__ void edge_value16t_kernel<0, false, 1>(Args16);                           // default graph, rows through the LDS ticket (the default)
+template __global__ void edge_value16t_kernel<0, false, 0>(Args16);
+template __global__ void edge_value16t_kernel<2, false, 1>(Args16);
+template __global__ void edge_value16t_kernel<2, false, 0>(Args16);
+template __global__ void edge_value16t_kernel<1, false, 1>(Args16);
+template __global__ void edge_value16t_kernel<1, false, 0>(Args16);
+template __global__ void edge_value16_kernel<true, false, false, 2, 1>(Args16);               // default graph, edge_row_dealing 0 / 1
+template __global__ void edge_value16_kernel<true, false, false, 2, 0>(Args16);
+template __global__ void edge_value16_kernel<true, false, false, 1, 1>(Args16);
+template __global__ void edge_value16_kernel<true, false, false, 1, 0>(Args16);
+template __global__ void edge_value16_kernel<true, false, false, 0, 1>(Args16);
+template __global__ void edge_value16_kernel<true, false, false, 0, 0>(Args16);
+template __global__ void edge_value16_kernel<false, true, false, 0, 0>(Args16);               // fp32 first layer
+template __global__ void edge_value16_kernel<false, false, true, 0, 0>(Args16);
+template __global__ void edge_value16_kernel<false, false, false, 0, 0>(Args16);
+//   edge_h2x16_chunked_kernel<FL>, edge_h2x16_kernel<SPLIT, FL>
+template __global__ void edge_h2x16_chunked_kernel<1>(ArgsH2x);
+template __global__ void edge_h2x16_chunked_kernel<0>(ArgsH2x);
+template __global__ void edge_h2x16_kernel<true, 1>(ArgsH2x);
+template __global__ void edge_h2x16_kernel<true, 0>(ArgsH2x);
+template __global__ void edge_h2x16_kernel<false, 0>(ArgsH2x);
+
 // Workgroups of a row-loop kernel: one per CU (256) when there is a row per wave for all of them.  With fewer rows the
 // waves of a workgroup would queue on their SIMD's shared matrix / vector pipe while other CUs idle, so small launches
 // spread over as many workgroups as there are rows (up to one per CU) and leave part of each workgroup's waves without a row.
-#define TD_LDS_ONCE(fn, bytes) do { static TdLdsOnce once; int _rc = td_set_lds(once, reinterpret_cast<const void *>(fn), bytes); if (_rc != TD_OK) return _rc; } while (0)
-
 static int grid16(int64_t count, int waves) {
     int64_t g = (count + waves - 1) / waves;
     if (g < 256) g = count < 256 ? count : 256;
@@ -2455,6 +2483,50 @@ static unsigned long long *wg_trace_slot(int pass) {
     return g_wg_trace + ((size_t)n * 3 + pass) * 256 * 8;
 }
 
+// ---- run-time options -> template arguments ------------------------------------------------------------------------------------
+// The second-layer variant of an x2h pass (the kernels' L2): 0 = fp32 products, 1 = f16 piece pairs of z'' scaled by 2^15, 2 = f16
+// piece pairs of z'' itself.
+static int l2_variant(const TdEdgeMlp &mlp) { return !mlp.l2_f16 ? 0 : (mlp.z_plain ? 2 : 1); }
+
+template <int V> using Int = std::integral_constant<int, V>;
+// f(Int<L2>, Int<FL>) for the kernel families that exist in all six (L2, FL) forms
+template <class F> static int with_l2_fl(int l2, bool fl, F f) {
+    switch (2 * l2 + (fl ? 1 : 0)) {
+    case 0: return f(Int<0>{}, Int<0>{});
+    case 1: return f(Int<0>{}, Int<1>{});
+    case 2: return f(Int<1>{}, Int<0>{});
+    case 3: return f(Int<1>{}, Int<1>{});
+    case 4: return f(Int<2>{}, Int<0>{});
+    default: return f(Int<2>{}, Int<1>{});
+    }
+}
+
+template <bool XV, int WAVES, int STAGE, int GRAPH, bool SPLIT, int L2 = 0, int FL = 0>
+static int launch_key16(const Args16 &a, hipStream_t s) {
+    return td_launch<edge_key16_kernel<XV, WAVES, STAGE, GRAPH, SPLIT, L2, FL>>(dim3(grid16(a.count, WAVES)), dim3(WAVES * 64),
+                                                                                key16_lds_bytes<SPLIT>(), s, a);
+}
+// x2h key pass, 16-bit first layer, rows of one chunk (GRAPH 0: the default graph; 2: the protein rows of a `hybrid` graph)
+template <int GRAPH> static int launch_key16_x2h(int l2, bool fl, const Args16 &a, hipStream_t s) {
+    return with_l2_fl(l2, fl, [&](auto L2, auto FL) { return launch_key16<false, K16S_WAVES, 0, GRAPH, true, L2, FL>(a, s); });
+}
+// x2h key pass, 16-bit first layer, chunk walk.  It takes f16 logits only together with the f16 first layer: with the bf16 piece triples
+// the kernel spilled 9 registers at its 168 budget and lost (C5 k = 48 / k = 64 key pass 11.16 -> 11.40 / 12.78 -> 12.89 ms per step); with
+// the f16 tables it needs 158 and wins (10.54 -> 10.15 / 12.28 -> 11.65, one call each)
+static int launch_key16_walk(int l2, bool fl, const Args16 &a, hipStream_t s) {
+    if (!fl) return launch_key16<false, K16S_WAVES, 0, 1, true, 0, 0>(a, s);
+    switch (l2) {
+    case 0: return launch_key16<false, K16S_WAVES, 0, 1, true, 0, 1>(a, s);
+    case 1: return launch_key16<false, K16S_WAVES, 0, 1, true, 1, 1>(a, s);
+    default: return launch_key16<false, K16S_WAVES, 0, 1, true, 2, 1>(a, s);
+    }
+}
+// the kernels that differ in the graph form and the first layer only (L2 = 0): f(Int<GRAPH>, Int<FL>), GRAPH = 1 the chunk walk
+template <class F> static int with_graph_fl(bool chunked, bool fl, F f) {
+    if (chunked) return fl ? f(Int<1>{}, Int<1>{}) : f(Int<1>{}, Int<0>{});
+    return fl ? f(Int<0>{}, Int<1>{}) : f(Int<0>{}, Int<0>{});
+}
+
 // cptr (general graphs): chunks of dst node i = cptr[i] .. cptr[i+1]-1 of nbr / ew / alpha; nullptr: one 32-slot row per node.
 // lig_rows / lig_count / cpn_p (x2h on general graphs): the ligand rows among `rows` (all of them) and the chunks per protein row.  With one
 // chunk per protein row (`hybrid`) the protein rows run as on the default graph and the ligand rows in a second, chunk-walking launch.
@@ -2469,80 +2541,22 @@ int td_launch_edge_key16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x
     const bool h2x = h2x_stage;      // h2x key pass (unfused form): STAGE tag 1, contiguous shares, no workgroup trace
     if (!h2x) a.trace = wg_trace_slot(0);
     a.deal = h2x ? 0 : mlp.deal_rows;
-#define TD_KEY_LAUNCH(WAVES, STAGE, CH, SP, BYTES)                                                            \
-    do {                                                                                                      \
-        TD_LDS_ONCE((edge_key16_kernel<false, WAVES, STAGE, CH, SP>), BYTES);                                 \
-        edge_key16_kernel<false, WAVES, STAGE, CH, SP><<<dim3(grid16(a.count, WAVES)), dim3(WAVES * 64), BYTES, s>>>(a); \
-    } while (0)
-    // (GR: the kernel's GRAPH; L2V: its second-layer variant; the first-layer variant follows TdEdgeMlp::l1_f16)
-#define TD_KEY_LAUNCH_X2H(GR, L2V)                                                                                            \
-    do {                                                                                                                  \
-        if (mlp.l1_f16) {                                                                                                 \
-            TD_LDS_ONCE((edge_key16_kernel<false, K16S_WAVES, 0, GR, true, L2V, 1>), K16S_LDS_BYTES);                      \
-            edge_key16_kernel<false, K16S_WAVES, 0, GR, true, L2V, 1><<<dim3(grid16(a.count, K16S_WAVES)), dim3(K16S_WAVES * 64), K16S_LDS_BYTES, s>>>(a); \
-        } else {                                                                                                          \
-            TD_LDS_ONCE((edge_key16_kernel<false, K16S_WAVES, 0, GR, true, L2V, 0>), K16S_LDS_BYTES);                      \
-            edge_key16_kernel<false, K16S_WAVES, 0, GR, true, L2V, 0><<<dim3(grid16(a.count, K16S_WAVES)), dim3(K16S_WAVES * 64), K16S_LDS_BYTES, s>>>(a); \
-        }                                                                                                                 \
-    } while (0)
-#define TD_KEY_LAUNCH_WALK_L2(L2V) TD_KEY_LAUNCH_X2H(1, L2V)
-    // the chunk walk's key pass takes f16 logits only together with the f16 first layer: with the bf16 piece triples the kernel spilled 9
-    // registers at its 168 budget and lost (C5 k = 48 / k = 64 key pass 11.16 -> 11.40 / 12.78 -> 12.89 ms per step); with the f16 tables it
-    // needs 158 and wins (10.54 -> 10.15 / 12.28 -> 11.65, one call each)
-#if TD_KEY_WALK_F16
-#define TD_KEY_LAUNCH_WALK_F16(L2V)                                                                                           \
-    do {                                                                                                                  \
-        TD_LDS_ONCE((edge_key16_kernel<false, K16S_WAVES, 0, 1, true, L2V, 1>), K16S_LDS_BYTES);                          \
-        edge_key16_kernel<false, K16S_WAVES, 0, 1, true, L2V, 1><<<dim3(grid16(a.count, K16S_WAVES)), dim3(K16S_WAVES * 64), K16S_LDS_BYTES, s>>>(a); \
-    } while (0)
-#define TD_KEY_LAUNCH_WALK()                                                        \
-    do {                                                                            \
-        if (!mlp.l2_f16 || !mlp.l1_f16) TD_KEY_LAUNCH_WALK_L2(0);                   \
-        else if (mlp.z_plain && !TD_ZPLAIN_OFF) TD_KEY_LAUNCH_WALK_F16(2);          \
-        else TD_KEY_LAUNCH_WALK_F16(1);                                             \
-    } while (0)
-#else
-#define TD_KEY_LAUNCH_WALK() TD_KEY_LAUNCH_WALK_L2(0)
-#endif
-    // (the unfused h2x key pass: STAGE tag 1, fp32 logits; its first layer follows TdEdgeMlp::l1_f16 like the fused kernel's)
-#define TD_KEY_LAUNCH_H2X(GR)                                                                                                 \
-    do {                                                                                                                  \
-        if (mlp.l1_f16) {                                                                                                 \
-            TD_LDS_ONCE((edge_key16_kernel<false, K16S_WAVES, 1, GR, true, 0, 1>), K16S_LDS_BYTES);                        \
-            edge_key16_kernel<false, K16S_WAVES, 1, GR, true, 0, 1><<<dim3(grid16(a.count, K16S_WAVES)), dim3(K16S_WAVES * 64), K16S_LDS_BYTES, s>>>(a); \
-        } else TD_KEY_LAUNCH(K16S_WAVES, 1, GR, true, K16S_LDS_BYTES);                                                     \
-    } while (0)
-    if (mlp.use_split) {                      // first layer on 16-bit pieces
-        if (cptr && !h2x && cpn_p == 1) {
-#define TD_KEY_LAUNCH_VIA(L2V) TD_KEY_LAUNCH_X2H(2, L2V)
-            if (!mlp.l2_f16) TD_KEY_LAUNCH_VIA(0);
-            else if (mlp.z_plain && !TD_ZPLAIN_OFF) TD_KEY_LAUNCH_VIA(2);
-            else TD_KEY_LAUNCH_VIA(1);
-#undef TD_KEY_LAUNCH_VIA
-            if (lig_rows && lig_count > 0) {
-                a.rows = lig_rows; a.count_ptr = nullptr; a.count = lig_count; a.trace = nullptr;
-                TD_KEY_LAUNCH_WALK();
-            }
-        } else if (cptr) { if (h2x) TD_KEY_LAUNCH_H2X(1); else TD_KEY_LAUNCH_WALK(); }
-        else if (h2x) TD_KEY_LAUNCH_H2X(0);
-        else {
-#define TD_KEY_LAUNCH_L2(L2V) TD_KEY_LAUNCH_X2H(0, L2V)
-            if (!mlp.l2_f16) TD_KEY_LAUNCH_L2(0);
-            else if (mlp.z_plain && !TD_ZPLAIN_OFF) TD_KEY_LAUNCH_L2(2);
-            else TD_KEY_LAUNCH_L2(1);
-#undef TD_KEY_LAUNCH_L2
-        }
-    } else {
-        if (cptr) { if (h2x) TD_KEY_LAUNCH(K16_WAVES, 1, 1, false, K16_LDS_BYTES); else TD_KEY_LAUNCH(K16_WAVES, 0, 1, false, K16_LDS_BYTES); }
-        else { if (h2x) TD_KEY_LAUNCH(K16_WAVES, 1, 0, false, K16_LDS_BYTES); else TD_KEY_LAUNCH(K16_WAVES, 0, 0, false, K16_LDS_BYTES); }
+    const bool chunked = cptr != nullptr;
+    const bool fl = mlp.l1_f16;                              // first layer on f16 piece pairs (else: exact bf16 piece triples)
+    const int l2 = l2_variant(mlp);
+    const bool hybrid = chunked && cpn_p == 1;
+    if (!mlp.use_split) {                                     // fp32 first layer: 16 waves, fp32 logits
+        if (h2x) return chunked ? launch_key16<false, K16_WAVES, 1, 1, false>(a, s) : launch_key16<false, K16_WAVES, 1, 0, false>(a, s);
+        return chunked ? launch_key16<false, K16_WAVES, 0, 1, false>(a, s) : launch_key16<false, K16_WAVES, 0, 0, false>(a, s);
     }
-#undef TD_KEY_LAUNCH
-#undef TD_KEY_LAUNCH_WALK
-#undef TD_KEY_LAUNCH_WALK_L2
-#undef TD_KEY_LAUNCH_X2H
-#undef TD_KEY_LAUNCH_H2X
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    // the unfused h2x key pass: fp32 logits; its first layer follows TdEdgeMlp::l1_f16 like the fused kernel's
+    if (h2x) return with_graph_fl(chunked, fl, [&](auto GR, auto FL) { return launch_key16<false, K16S_WAVES, 1, GR, true, 0, FL>(a, s); });
+    if (!chunked) return launch_key16_x2h<0>(l2, fl, a, s);
+    if (!hybrid) return launch_key16_walk(l2, fl, a, s);
+    const int rc = launch_key16_x2h<2>(l2, fl, a, s);
+    if (rc != TD_OK || !lig_rows || lig_count <= 0) return rc;
+    a.rows = lig_rows; a.count_ptr = nullptr; a.count = lig_count; a.trace = nullptr;
+    return launch_key16_walk(l2, fl, a, s);
 }
 
 // h2x value pass (xv MLP + coordinate update) on the listed ligand rows; reads alpha written by the h2x key pass.
@@ -2554,24 +2568,24 @@ int td_launch_edge_xv16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4
     a.x4 = x4_in; a.nbr = nbr; a.ew = nullptr; a.P = P; a.q = nullptr; a.rows = rows; a.count_ptr = nullptr; a.h = nullptr;
     a.alpha = const_cast<float *>(alpha); a.x4_out = x4_out; a.count = count; a.mlp = mlp; a.offsets = L.offsets;
     a.coeff = L.coeff; a.p_off = 2 * TD_H; a.cptr = cptr;
-    const dim3 grid(grid16(count, XV16_WAVES)), block(XV16_WAVES * 64);
-#define TD_XV_LAUNCH(CH, SP, BYTES)                                                            \
-    do {                                                                                       \
-        TD_LDS_ONCE((edge_key16_kernel<true, XV16_WAVES, 1, CH, SP>), BYTES);                  \
-        edge_key16_kernel<true, XV16_WAVES, 1, CH, SP><<<grid, block, BYTES, s>>>(a);          \
-    } while (0)
-#define TD_XV_LAUNCH_F16(CH)                                                                   \
-    do {                                                                                       \
-        TD_LDS_ONCE((edge_key16_kernel<true, XV16_WAVES, 1, CH, true, 0, 1>), K16S_LDS_BYTES); \
-        edge_key16_kernel<true, XV16_WAVES, 1, CH, true, 0, 1><<<grid, block, K16S_LDS_BYTES, s>>>(a); \
-    } while (0)
-    if (mlp.use_split && mlp.l1_f16) { if (cptr) TD_XV_LAUNCH_F16(1); else TD_XV_LAUNCH_F16(0); }
-    else if (mlp.use_split) { if (cptr) TD_XV_LAUNCH(1, true, K16S_LDS_BYTES); else TD_XV_LAUNCH(0, true, K16S_LDS_BYTES); }
-    else { if (cptr) TD_XV_LAUNCH(1, false, K16_LDS_BYTES); else TD_XV_LAUNCH(0, false, K16_LDS_BYTES); }
-#undef TD_XV_LAUNCH
-#undef TD_XV_LAUNCH_F16
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    const bool chunked = cptr != nullptr;
+    if (!mlp.use_split) return chunked ? launch_key16<true, XV16_WAVES, 1, 1, false>(a, s) : launch_key16<true, XV16_WAVES, 1, 0, false>(a, s);
+    return with_graph_fl(chunked, mlp.l1_f16, [&](auto GR, auto FL) { return launch_key16<true, XV16_WAVES, 1, GR, true, 0, FL>(a, s); });
+}
+
+// the 8-wave value kernel: CHUNKED = chunk walk, GATE_M = gate from the value vector
+template <bool SPLIT, bool CHUNKED, bool GATE_M, int L2 = 0, int FL = 0>
+static int launch_value16(int G, const Args16 &a, hipStream_t s) {
+    return td_launch<edge_value16_kernel<SPLIT, CHUNKED, GATE_M, L2, FL>>(dim3(G), dim3(V16_WAVES * 64), value16_lds_bytes<SPLIT>(), s, a);
+}
+template <bool CHUNKED> static int launch_value16_split(int l2, bool fl, int G, const Args16 &a, hipStream_t s) {
+    return with_l2_fl(l2, fl, [&](auto L2, auto FL) { return launch_value16<true, CHUNKED, false, L2, FL>(G, a, s); });
+}
+// the 12-wave value kernel (rows of one chunk through the LDS ticket); VIA: the protein rows of a `hybrid` graph
+template <bool VIA> static int launch_value16t(int l2, bool fl, int G, const Args16 &a, hipStream_t s) {
+    return with_l2_fl(l2, fl, [&](auto L2, auto FL) {
+        return td_launch<edge_value16t_kernel<L2, VIA, FL>>(dim3(G), dim3(V16T_WAVES * 64), V16T_LDS_BYTES, s, a);
+    });
 }
 
 // lig_rows / lig_count: the ligand rows among `rows` (all of them: every row list of a forward pass or sampling step holds
@@ -2590,91 +2604,36 @@ int td_launch_edge_value16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 
     a.out = out;
     a.gate_m = cptr ? nullptr : gate_m;          // (ew_net_type 'm' is accepted on the default graph only)
     int G = grid16(count, V16_WAVES);
-    const dim3 block(V16_WAVES * 64);
     a.trace = wg_trace_slot(1);
     a.deal = mlp.deal_rows;
-    // (the 8-wave kernel, bf16-class first layer: CH = chunk walk, GM = gate from the value vector, L2V / TdEdgeMlp::l1_f16 = the layers' variants)
-#define TD_V16_LAUNCH(CH, GM, L2V)                                                                            \
-    do {                                                                                                     \
-        if (mlp.l1_f16) {                                                                                    \
-            TD_LDS_ONCE((edge_value16_kernel<true, CH, GM, L2V, 1>), V16S_LDS_BYTES);                        \
-            edge_value16_kernel<true, CH, GM, L2V, 1><<<dim3(G), block, V16S_LDS_BYTES, s>>>(a);             \
-        } else {                                                                                             \
-            TD_LDS_ONCE((edge_value16_kernel<true, CH, GM, L2V, 0>), V16S_LDS_BYTES);                        \
-            edge_value16_kernel<true, CH, GM, L2V, 0><<<dim3(G), block, V16S_LDS_BYTES, s>>>(a);             \
-        }                                                                                                    \
-    } while (0)
-#define TD_V16T_LAUNCH_ANY(L2V, VIAV)                                                                         \
-    do {                                                                                                     \
-        if (mlp.l1_f16) {                                                                                    \
-            TD_LDS_ONCE((edge_value16t_kernel<L2V, VIAV, 1>), V16T_LDS_BYTES);                               \
-            edge_value16t_kernel<L2V, VIAV, 1><<<dim3(Gt), dim3(V16T_WAVES * 64), V16T_LDS_BYTES, s>>>(a);   \
-        } else {                                                                                             \
-            TD_LDS_ONCE((edge_value16t_kernel<L2V, VIAV, 0>), V16T_LDS_BYTES);                               \
-            edge_value16t_kernel<L2V, VIAV, 0><<<dim3(Gt), dim3(V16T_WAVES * 64), V16T_LDS_BYTES, s>>>(a);   \
-        }                                                                                                    \
-    } while (0)
-#define TD_V16_LAUNCH_WALK_L2(L2V) TD_V16_LAUNCH(true, false, L2V)
-#define TD_V16_LAUNCH_WALK()                                                        \
-    do {                                                                            \
-        if (!mlp.l2_f16) TD_V16_LAUNCH_WALK_L2(0);                                  \
-        else if (mlp.z_plain && !TD_ZPLAIN_OFF) TD_V16_LAUNCH_WALK_L2(2);           \
-        else TD_V16_LAUNCH_WALK_L2(1);                                              \
-    } while (0)
-    if (mlp.use_split) {
-        a.lig_rows = lig_rows; a.lig_count = lig_rows ? lig_count : 0;
-        if (G < 2 && a.lig_count > 0) G = 2;       // a workgroup for each destination class
-        if (cptr && a.cpn_p == 1) {
-            // `hybrid`: the protein rows (one chunk, plain k-NN) through the 12-wave kernel of the default graph, whatever edge_row_dealing says;
-            // the ligand rows (several chunks) in a second, chunk-walking launch over the ligand row list
-            int Gt = grid16(count, V16T_WAVES);
-            a.lig_rows = nullptr; a.lig_count = 0;
-#define TD_V16T_LAUNCH_VIA(L2V) TD_V16T_LAUNCH_ANY(L2V, true)
-            if (!mlp.l2_f16) TD_V16T_LAUNCH_VIA(0);
-            else if (mlp.z_plain && !TD_ZPLAIN_OFF) TD_V16T_LAUNCH_VIA(2);
-            else TD_V16T_LAUNCH_VIA(1);
-#undef TD_V16T_LAUNCH_VIA
-            if (lig_rows && lig_count > 0) {
-                a.rows = lig_rows; a.count_ptr = nullptr; a.count = lig_count; a.lig_rows = lig_rows; a.lig_count = lig_count;
-                a.mixed_count = nullptr; a.trace = nullptr;
-                G = grid16(lig_count, V16_WAVES);
-                TD_V16_LAUNCH_WALK();
-            }
-        } else if (cptr) {
-            TD_V16_LAUNCH_WALK();
-        } else if (gate_m) {
-            TD_V16_LAUNCH(false, true, 0);
-        } else if (a.deal == 2) {          // (the default) rows through the LDS ticket: the 12-wave kernel
-            int Gt = grid16(count, V16T_WAVES);
-            if (Gt < 2 && a.lig_count > 0) Gt = 2;
-#define TD_V16T_LAUNCH(L2V) TD_V16T_LAUNCH_ANY(L2V, false)
-            if (!mlp.l2_f16) TD_V16T_LAUNCH(0);
-            else if (mlp.z_plain && !TD_ZPLAIN_OFF) TD_V16T_LAUNCH(2);
-            else TD_V16T_LAUNCH(1);
-#undef TD_V16T_LAUNCH
-        } else if (mlp.l2_f16 && mlp.z_plain && !TD_ZPLAIN_OFF) {
-            TD_V16_LAUNCH(false, false, 2);
-        } else if (mlp.l2_f16) {
-            TD_V16_LAUNCH(false, false, 1);
-        } else {
-            TD_V16_LAUNCH(false, false, 0);
-        }
-    } else if (cptr) {
-        TD_LDS_ONCE((edge_value16_kernel<false, true>), V16_LDS_BYTES);
-        edge_value16_kernel<false, true><<<dim3(G), block, V16_LDS_BYTES, s>>>(a);
-    } else if (gate_m) {
-        TD_LDS_ONCE((edge_value16_kernel<false, false, true>), V16_LDS_BYTES);
-        edge_value16_kernel<false, false, true><<<dim3(G), block, V16_LDS_BYTES, s>>>(a);
-    } else {
-        TD_LDS_ONCE((edge_value16_kernel<false, false>), V16_LDS_BYTES);
-        edge_value16_kernel<false, false><<<dim3(G), block, V16_LDS_BYTES, s>>>(a);
+    const bool chunked = cptr != nullptr;
+    const bool fl = mlp.l1_f16;
+    const int l2 = l2_variant(mlp);
+    const bool hybrid = chunked && a.cpn_p == 1;
+    if (!mlp.use_split) {                         // fp32 first layer
+        if (chunked) return launch_value16<false, true, false>(G, a, s);
+        return gate_m ? launch_value16<false, false, true>(G, a, s) : launch_value16<false, false, false>(G, a, s);
     }
-#undef TD_V16_LAUNCH_WALK
-#undef TD_V16_LAUNCH_WALK_L2
-#undef TD_V16T_LAUNCH_ANY
-#undef TD_V16_LAUNCH
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    a.lig_rows = lig_rows; a.lig_count = lig_rows ? lig_count : 0;
+    if (G < 2 && a.lig_count > 0) G = 2;       // a workgroup for each destination class
+    if (hybrid) {
+        // the protein rows (one chunk, plain k-NN) through the 12-wave kernel of the default graph, whatever edge_row_dealing says;
+        // the ligand rows (several chunks) in a second, chunk-walking launch over the ligand row list
+        a.lig_rows = nullptr; a.lig_count = 0;
+        const int rc = launch_value16t<true>(l2, fl, grid16(count, V16T_WAVES), a, s);
+        if (rc != TD_OK || !lig_rows || lig_count <= 0) return rc;
+        a.rows = lig_rows; a.count_ptr = nullptr; a.count = lig_count; a.lig_rows = lig_rows; a.lig_count = lig_count;
+        a.mixed_count = nullptr; a.trace = nullptr;
+        return launch_value16_split<true>(l2, fl, grid16(lig_count, V16_WAVES), a, s);
+    }
+    if (chunked) return launch_value16_split<true>(l2, fl, G, a, s);
+    if (gate_m) return fl ? launch_value16<true, false, true, 0, 1>(G, a, s) : launch_value16<true, false, true, 0, 0>(G, a, s);
+    if (a.deal == 2) {          // (the default) rows through the LDS ticket: the 12-wave kernel
+        int Gt = grid16(count, V16T_WAVES);
+        if (Gt < 2 && a.lig_count > 0) Gt = 2;
+        return launch_value16t<false>(l2, fl, Gt, a, s);
+    }
+    return launch_value16_split<false>(l2, fl, G, a, s);
 }
 
 // Fused h2x stage (keys + softmax + xv + coordinate update) on the listed ligand rows.
@@ -2691,35 +2650,21 @@ int td_launch_edge_h2x16(const TdEdgeMlp &mlp_k, const TdEdgeMlp &mlp_v, const T
     a.trace = cptr ? nullptr : wg_trace_slot(2);
     const dim3 grid(grid16(count, H2X16_WAVES)), block(H2X16_WAVES * 64);
     const bool f16_first = mlp_k.l1_f16 && mlp_v.l1_f16;          // both halves' first layers on f16 piece pairs
-    if (cptr && f16_first) {           // general graphs: the chunk-walking form (16-bit first layer; the caller checks use_split)
-        TD_LDS_ONCE((edge_h2x16_chunked_kernel<1>), h2x16_lds_bytes<true>());
-        edge_h2x16_chunked_kernel<1><<<grid, block, h2x16_lds_bytes<true>(), s>>>(ar);
-    } else if (cptr) {
-        TD_LDS_ONCE((edge_h2x16_chunked_kernel<0>), h2x16_lds_bytes<true>());
-        edge_h2x16_chunked_kernel<0><<<grid, block, h2x16_lds_bytes<true>(), s>>>(ar);
-    } else if (mlp_k.use_split && mlp_v.use_split && f16_first) {
-        TD_LDS_ONCE((edge_h2x16_kernel<true, 1>), h2x16_lds_bytes<true>());
-        edge_h2x16_kernel<true, 1><<<grid, block, h2x16_lds_bytes<true>(), s>>>(ar);
-    } else if (mlp_k.use_split && mlp_v.use_split) {
-        TD_LDS_ONCE((edge_h2x16_kernel<true>), h2x16_lds_bytes<true>());
-        edge_h2x16_kernel<true><<<grid, block, h2x16_lds_bytes<true>(), s>>>(ar);
-    } else {
-        TD_LDS_ONCE((edge_h2x16_kernel<false>), h2x16_lds_bytes<false>());
-        edge_h2x16_kernel<false><<<grid, block, h2x16_lds_bytes<false>(), s>>>(ar);
+    const bool split = mlp_k.use_split && mlp_v.use_split;
+    if (cptr) {           // general graphs: the chunk-walking form (16-bit first layer; the caller checks use_split)
+        if (f16_first) return td_launch<edge_h2x16_chunked_kernel<1>>(grid, block, h2x16_lds_bytes<true>(), s, ar);
+        return td_launch<edge_h2x16_chunked_kernel<0>>(grid, block, h2x16_lds_bytes<true>(), s, ar);
     }
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    if (split && f16_first) return td_launch<edge_h2x16_kernel<true, 1>>(grid, block, h2x16_lds_bytes<true>(), s, ar);
+    if (split) return td_launch<edge_h2x16_kernel<true, 0>>(grid, block, h2x16_lds_bytes<true>(), s, ar);
+    return td_launch<edge_h2x16_kernel<false, 0>>(grid, block, h2x16_lds_bytes<false>(), s, ar);
 }
 
 // ---- edge gate ------------------------------------------------------------------------------------------------------
 int td_launch_gate16(const TdGate &g, const float4 *x4, const int32_t *nbr, int64_t N, const int32_t *rows,
                      const int32_t *count_ptr, float *ew, hipStream_t s, const int32_t *chunk_node) {
     if (N == 0) return TD_OK;
-    TD_LDS_ONCE((edge_gate16_kernel), G16_LDS_BYTES);
     int64_t G = (N + G16_WAVES - 1) / G16_WAVES;
     if (G > TD_GATE_WGS) G = TD_GATE_WGS;              // workgroups per CU x 256
-    edge_gate16_kernel<<<dim3((unsigned)G), dim3(G16_WAVES * 64), G16_LDS_BYTES, s>>>(g, x4, nbr, N, rows, count_ptr, chunk_node, ew);
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    return td_launch<edge_gate16_kernel>(dim3((unsigned)G), dim3(G16_WAVES * 64), G16_LDS_BYTES, s, g, x4, nbr, N, rows, count_ptr, chunk_node, ew);
 }
-

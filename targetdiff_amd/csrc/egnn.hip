@@ -188,14 +188,7 @@ __global__ __launch_bounds__(EG_WAVES * 64) void egnn_edge_kernel(TdEgnnLayer L,
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s) {
     if (N == 0) return TD_OK;
-    {
-        static TdLdsOnce once;
-        int rc = td_set_lds(once, reinterpret_cast<const void *>(egnn_edge_kernel), EG_LDS_BYTES);
-        if (rc != TD_OK) return rc;
-    }
     int64_t g = (N + EG_WAVES - 1) / EG_WAVES;
     if (g > 256) g = 256;
-    egnn_edge_kernel<<<dim3((unsigned)g), dim3(EG_WAVES * 64), EG_LDS_BYTES, s>>>(L, x4, x4_out, nbr, P, mi, N);
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    return td_launch<egnn_edge_kernel>(dim3((unsigned)g), dim3(EG_WAVES * 64), EG_LDS_BYTES, s, L, x4, x4_out, nbr, P, mi, N);
 }

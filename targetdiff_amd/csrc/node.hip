@@ -498,29 +498,16 @@ static int np_fill(NpSeg &g, const TdNodeStage &st, const int32_t *rows, const i
     return g.blocks;
 }
 
-static TdLdsOnce g_np_lds, g_nps_lds, g_npsa_lds, g_npsb_lds, g_egnn_node_lds;
-
 static int np_launch(const NpArgs &a, const float *h, unsigned total_blocks, hipStream_t s) {
-    int rc;
     // bf16 x 3 operand split (exact: an fp32 significand is three 8-bit pieces; fp32 accumulation) when every stage of the
     // launch carries the pre-split weights and the model option asks for it
     bool split = true;
     for (int i = 0; i < a.nseg; ++i) split = split && a.seg[i].st.use_split && a.seg[i].st.projB3 != nullptr;
-    if (split && a.seg[0].st.async_copy && a.seg[0].st.bpipe) {
-        if ((rc = td_set_lds(g_nps_lds, reinterpret_cast<const void *>(node_proj_split_kernel<true, true>), NPS_LDS_BYTES)) != TD_OK) return rc;
-        node_proj_split_kernel<true, true><<<dim3(total_blocks), dim3(256), NPS_LDS_BYTES, s>>>(a, h);
-    } else if (split && a.seg[0].st.async_copy) {
-        if ((rc = td_set_lds(g_npsb_lds, reinterpret_cast<const void *>(node_proj_split_kernel<true, false>), NPS_LDS_BYTES)) != TD_OK) return rc;
-        node_proj_split_kernel<true, false><<<dim3(total_blocks), dim3(256), NPS_LDS_BYTES, s>>>(a, h);
-    } else if (split) {
-        if ((rc = td_set_lds(g_npsa_lds, reinterpret_cast<const void *>(node_proj_split_kernel<false, false>), NPS_LDS_BYTES)) != TD_OK) return rc;
-        node_proj_split_kernel<false, false><<<dim3(total_blocks), dim3(256), NPS_LDS_BYTES, s>>>(a, h);
-    } else {
-        if ((rc = td_set_lds(g_np_lds, reinterpret_cast<const void *>(node_proj_kernel), NP_LDS_BYTES)) != TD_OK) return rc;
-        node_proj_kernel<<<dim3(total_blocks), dim3(256), NP_LDS_BYTES, s>>>(a, h);
-    }
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    const dim3 grid(total_blocks), block(256);
+    if (split && a.seg[0].st.async_copy && a.seg[0].st.bpipe) return td_launch<node_proj_split_kernel<true, true>>(grid, block, NPS_LDS_BYTES, s, a, h);
+    if (split && a.seg[0].st.async_copy) return td_launch<node_proj_split_kernel<true, false>>(grid, block, NPS_LDS_BYTES, s, a, h);
+    if (split) return td_launch<node_proj_split_kernel<false, false>>(grid, block, NPS_LDS_BYTES, s, a, h);
+    return td_launch<node_proj_kernel>(grid, block, NP_LDS_BYTES, s, a, h);
 }
 
 int td_launch_node_proj(const TdNodeStage &st, const float *h, int64_t N, const int32_t *rows, unsigned mat_mask,
@@ -646,22 +633,13 @@ __global__ __launch_bounds__(256, 2) void egnn_node_kernel(const float4 *__restr
 
 int td_launch_egnn_node(const TdEgnnLayer &L, const float *mi, float *h, int64_t N, hipStream_t s) {
     if (N == 0) return TD_OK;
-    int rc;
-    if ((rc = td_set_lds(g_egnn_node_lds, reinterpret_cast<const void *>(egnn_node_kernel<false>), NP_LDS_BYTES)) != TD_OK) return rc;
-    egnn_node_kernel<false><<<dim3((unsigned)((N + 127) / 128)), dim3(256), NP_LDS_BYTES, s>>>(
-        reinterpret_cast<const float4 *>(L.nodeB), L.nb1, L.nb2, mi, h, N, nullptr, nullptr);
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    return td_launch<egnn_node_kernel<false>>(dim3((unsigned)((N + 127) / 128)), dim3(256), NP_LDS_BYTES, s,
+                                              reinterpret_cast<const float4 *>(L.nodeB), L.nb1, L.nb2, mi, h, N, nullptr, nullptr);
 }
 
 // node_output of an x2h stage with out_fc: h += MLP([out | h]) on every row (fp32 MFMA; a non-default configuration)
 int td_launch_node_output(const TdNodeOut &no, const float *out, float *h, int64_t N, hipStream_t s) {
     if (N == 0) return TD_OK;
-    static TdLdsOnce once;
-    int rc;
-    if ((rc = td_set_lds(once, reinterpret_cast<const void *>(egnn_node_kernel<true>), NP_LDS_BYTES)) != TD_OK) return rc;
-    egnn_node_kernel<true><<<dim3((unsigned)((N + 127) / 128)), dim3(256), NP_LDS_BYTES, s>>>(
-        reinterpret_cast<const float4 *>(no.B), no.b1, no.b2, out, h, N, no.gamma, no.beta);
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    return td_launch<egnn_node_kernel<true>>(dim3((unsigned)((N + 127) / 128)), dim3(256), NP_LDS_BYTES, s,
+                                             reinterpret_cast<const float4 *>(no.B), no.b1, no.b2, out, h, N, no.gamma, no.beta);
 }

@@ -45,6 +45,17 @@ inline int td_set_lds(TdLdsOnce &once, const void *fn, size_t bytes) {
     once.mask.fetch_or(bit, std::memory_order_release);
     return TD_OK;
 }
+// Launch of a kernel that takes dynamic LDS beyond the default limit: the kernel is the template argument, so every kernel has its
+// own TdLdsOnce here and a launch site names it once.
+template <auto Kernel, class... Args>
+int td_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args &...args) {
+    static TdLdsOnce once;
+    const int rc = td_set_lds(once, reinterpret_cast<const void *>(Kernel), lds_bytes);
+    if (rc != TD_OK) return rc;
+    Kernel<<<grid, block, lds_bytes, s>>>(args...);
+    TD_CHECK_HIP(hipGetLastError());
+    return TD_OK;
+}
 
 // ---- packed weights (device pointers) ---------------------------------------------------------------
 // One edge MLP (hk/hv/xk/xv: Linear(340,128) -> LN -> ReLU -> Linear(128,out)), re-packed:

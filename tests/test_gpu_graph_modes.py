@@ -422,7 +422,7 @@ def test_sampling_with_fp32_second_layer(state_dict, cfg, opt):
     steps through the session and the stateless forward against the default -- same types, positions within the sampling tolerance, session ==
     stateless bit for bit under either setting.  On the default graph, on a `hybrid` graph (protein rows through the default graph's kernels,
     ligand rows through the chunk walk) and at k = 48 (chunk walk: the value pass follows the option; the key pass takes f16 logits only while
-    edge_first_layer_f16 and edge_second_layer_f16 are both on, fp32 logits otherwise -- TD_KEY_LAUNCH_WALK, edge16.hip).  (That
+    edge_first_layer_f16 and edge_second_layer_f16 are both on, fp32 logits otherwise -- launch_key16_walk, edge16.hip).  (That
     the option is live -- the two settings do not produce identical features -- is asserted in
     tests/test_gpu_weight_regimes.py::test_forward_weight_regimes_vs_reference.)"""
     from oracle import draws

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build targetdiff_amd/lib/variant_NAME.so with extra compiler flags on edge16.hip (tuning macros), for tools/ab_variants.sh:
-#   tools/build_variant.sh A "-DTD_L2_F16=0"; tools/build_variant.sh B ""
+#   tools/build_variant.sh A "-DTD_KEY_AH=1"; tools/build_variant.sh B ""
 set -e
 cd "$(dirname "$0")/.."
 NAME=$1; EXTRA=$2; FILES=${3:-edge16.hip}

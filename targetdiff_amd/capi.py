@@ -459,42 +459,26 @@ class NativeModel:
         if v_next is None:
             v_next = torch.empty_like(ligand_v)
         fm, fp, fv = _fixed_ptrs(fixed_mask, fixed_pos, fixed_v, Nl)
+        if x0_shift is not None and tuple(x0_shift.shape) != (Nl, 3):
+            raise ValueError(f'x0_shift must be [{Nl}, 3] (got {tuple(x0_shift.shape)})')
+        head = (self.handle, _ptr(t, torch.int32, 't'))
+        body = (_ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
+                _ptr(ligand_pos, torch.float32, 'ligand_pos'), _ptr(ligand_v, torch.int64, 'ligand_v'),
+                _ptr(pred_pos, torch.float32, 'pred_pos'), _ptr(pred_v, torch.float32, 'pred_v'),
+                _ptr(noise, torch.float32, 'noise'), _ptr(uniform, torch.float32, 'uniform'), _ptr(pos_next),
+                _ptr(v_next, torch.int64, 'v_next'), _ptr(log_v0), _ptr(log_post))
+        prow = (_prog_row_ptr(prog_row) if prog_row is not None else None,)
+        stream = (_stream(self.device),)
+        # the entry point with the fewest optional pointers that takes the ones present
         if x0_shift is not None:
-            if tuple(x0_shift.shape) != (Nl, 3):
-                raise ValueError(f'x0_shift must be [{Nl}, 3] (got {tuple(x0_shift.shape)})')
-            _check(self.lib.td_posterior_step_guided(
-                self.handle, _ptr(t, torch.int32, 't'), _prog_row_ptr(prog_row) if prog_row is not None else None,
-                _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
-                _ptr(ligand_pos, torch.float32, 'ligand_pos'), _ptr(ligand_v, torch.int64, 'ligand_v'),
-                _ptr(pred_pos, torch.float32, 'pred_pos'), _ptr(pred_v, torch.float32, 'pred_v'),
-                _ptr(noise, torch.float32, 'noise'), _ptr(uniform, torch.float32, 'uniform'), _ptr(pos_next),
-                _ptr(v_next, torch.int64, 'v_next'), _ptr(log_v0), _ptr(log_post), fm, fp, fv,
-                _ptr(x0_shift, torch.float32, 'x0_shift'), _stream(self.device)), 'td_posterior_step_guided')
-            return pos_next, v_next
-        if prog_row is not None:
-            _check(self.lib.td_posterior_step_program(
-                self.handle, _ptr(t, torch.int32, 't'), _prog_row_ptr(prog_row), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
-                _ptr(ligand_pos, torch.float32, 'ligand_pos'), _ptr(ligand_v, torch.int64, 'ligand_v'),
-                _ptr(pred_pos, torch.float32, 'pred_pos'), _ptr(pred_v, torch.float32, 'pred_v'),
-                _ptr(noise, torch.float32, 'noise'), _ptr(uniform, torch.float32, 'uniform'), _ptr(pos_next),
-                _ptr(v_next, torch.int64, 'v_next'), _ptr(log_v0), _ptr(log_post), fm, fp, fv, _stream(self.device)),
-                'td_posterior_step_program')
-            return pos_next, v_next
-        if fm is not None:
-            _check(self.lib.td_posterior_step_fixed(
-                self.handle, _ptr(t, torch.int32, 't'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
-                _ptr(ligand_pos, torch.float32, 'ligand_pos'), _ptr(ligand_v, torch.int64, 'ligand_v'),
-                _ptr(pred_pos, torch.float32, 'pred_pos'), _ptr(pred_v, torch.float32, 'pred_v'),
-                _ptr(noise, torch.float32, 'noise'), _ptr(uniform, torch.float32, 'uniform'), _ptr(pos_next),
-                _ptr(v_next, torch.int64, 'v_next'), _ptr(log_v0), _ptr(log_post), fm, fp, fv, _stream(self.device)),
-                'td_posterior_step_fixed')
-            return pos_next, v_next
-        _check(self.lib.td_posterior_step(
-            self.handle, _ptr(t, torch.int32, 't'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
-            _ptr(ligand_pos, torch.float32, 'ligand_pos'), _ptr(ligand_v, torch.int64, 'ligand_v'),
-            _ptr(pred_pos, torch.float32, 'pred_pos'), _ptr(pred_v, torch.float32, 'pred_v'),
-            _ptr(noise, torch.float32, 'noise'), _ptr(uniform, torch.float32, 'uniform'), _ptr(pos_next),
-            _ptr(v_next, torch.int64, 'v_next'), _ptr(log_v0), _ptr(log_post), _stream(self.device)), 'td_posterior_step')
+            name, args = 'td_posterior_step_guided', head + prow + body + (fm, fp, fv, _ptr(x0_shift, torch.float32, 'x0_shift')) + stream
+        elif prog_row is not None:
+            name, args = 'td_posterior_step_program', head + prow + body + (fm, fp, fv) + stream
+        elif fm is not None:
+            name, args = 'td_posterior_step_fixed', head + body + (fm, fp, fv) + stream
+        else:
+            name, args = 'td_posterior_step', head + body + stream
+        _check(getattr(self.lib, name)(*args), name)
         return pos_next, v_next
 
     @_device_bound

@@ -214,19 +214,9 @@ extern "C" int td_model_forward(const td_model *m, const float *d_protein_pos, c
                           d_pred_ligand_v, d_final_ligand_h, s);
 }
 
-namespace {
-int posterior_step_impl(const char *who, const td_model *m, const int32_t *d_t, const int32_t *d_ligand_ptr, int64_t N_l, int64_t B,
-                        const float *d_ligand_pos, const int64_t *d_ligand_v, const float *d_pred_pos, const float *d_pred_v,
-                        const float *d_noise, const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
-                        float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos, const int64_t *d_fixed_v,
-                        void *stream, const float *d_prog_row = nullptr, const float *d_x0_shift = nullptr) {
-    if (!m || N_l < 0 || B < 0) { td_set_error("%s: bad argument", who); return TD_EINVAL; }
-    if (N_l == 0) return TD_OK;
-    if (!d_t || !d_ligand_ptr || !d_ligand_pos || !d_ligand_v || !d_pred_pos || !d_pred_v || !d_noise || !d_uniform ||
-        !d_pos_next || !d_v_next) {
-        td_set_error("%s: null pointer", who);
-        return TD_EINVAL;
-    }
+namespace tdapi {
+int check_known_atoms(const char *who, const td_model *m, const uint8_t *d_fixed_mask, const float *d_fixed_pos,
+                      const int64_t *d_fixed_v) {
     if (d_fixed_mask && (!d_fixed_pos || !d_fixed_v)) {
         td_set_error("%s: d_fixed_mask needs d_fixed_pos and d_fixed_v", who);
         return TD_EINVAL;
@@ -235,12 +225,29 @@ int posterior_step_impl(const char *who, const td_model *m, const int32_t *d_t, 
         td_set_error("%s: the model was created without alphas_cumprod (8 schedule arrays)", who);
         return TD_EINVAL;
     }
-    ProfScope ps(PC_POST, static_cast<hipStream_t>(stream));
-    return td_launch_posterior(m->sched, m->cfg.num_timesteps, d_t, d_ligand_ptr, N_l, B, m->cfg.ligand_num_classes,
-                               d_ligand_pos, d_ligand_v, d_pred_pos, d_pred_v, d_noise, d_uniform, d_pos_next,
-                               d_v_next, d_log_v0, d_log_post, static_cast<hipStream_t>(stream), m->cfg.model_mean_type,
-                               d_fixed_mask, d_fixed_mask ? d_fixed_pos : nullptr, d_fixed_mask ? d_fixed_v : nullptr, d_prog_row,
-                               d_x0_shift);
+    return TD_OK;
+}
+}  // namespace tdapi
+
+namespace {
+// validate and launch, for the stateless entry points below: each fills the pointers and N_l of `a`, the model's part is added here
+int step_run(const char *who, const td_model *m, int64_t B, TdStepArgs &a, void *stream, bool renoise = false) {
+    if (!m || a.Nl < 0 || B < 0) { td_set_error("%s: bad argument", who); return TD_EINVAL; }
+    if (a.Nl == 0) return TD_OK;
+    const bool own = renoise ? a.prow != nullptr : a.t && a.lptr && a.pred_pos && a.pred_v && a.uni;
+    if (!own || !a.pos || !a.v || !a.noise || !a.pos_next || !a.v_next) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    const int rc = check_known_atoms(who, m, a.fixed_mask, a.fixed_pos, a.fixed_v);
+    if (rc != TD_OK) return rc;
+    a.B = (int)B;
+    a.C = m->cfg.ligand_num_classes;
+    a.T = m->cfg.num_timesteps;
+    a.mean_type = m->cfg.model_mean_type;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ProfScope ps(PC_POST, s);
+    return renoise ? td_launch_renoise(a, s) : td_launch_posterior(m->sched, a, s);
 }
 }  // namespace
 
@@ -249,8 +256,11 @@ extern "C" int td_posterior_step(const td_model *m, const int32_t *d_t, const in
                                  const float *d_pred_pos, const float *d_pred_v, const float *d_noise,
                                  const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
                                  float *d_log_post, void *stream) {
-    return posterior_step_impl("td_posterior_step", m, d_t, d_ligand_ptr, N_l, B, d_ligand_pos, d_ligand_v, d_pred_pos, d_pred_v,
-                               d_noise, d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_post, nullptr, nullptr, nullptr, stream);
+    TdStepArgs a;
+    a.t = d_t; a.lptr = d_ligand_ptr; a.Nl = N_l; a.pos = d_ligand_pos; a.v = d_ligand_v;
+    a.pred_pos = d_pred_pos; a.pred_v = d_pred_v; a.noise = d_noise; a.uni = d_uniform;
+    a.pos_next = d_pos_next; a.v_next = d_v_next; a.log_v0 = d_log_v0; a.log_post = d_log_post;
+    return step_run("td_posterior_step", m, B, a, stream);
 }
 
 extern "C" int td_posterior_step_fixed(const td_model *m, const int32_t *d_t, const int32_t *d_ligand_ptr, int64_t N_l,
@@ -259,9 +269,12 @@ extern "C" int td_posterior_step_fixed(const td_model *m, const int32_t *d_t, co
                                        const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
                                        float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos,
                                        const int64_t *d_fixed_v, void *stream) {
-    return posterior_step_impl("td_posterior_step_fixed", m, d_t, d_ligand_ptr, N_l, B, d_ligand_pos, d_ligand_v, d_pred_pos,
-                               d_pred_v, d_noise, d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_post, d_fixed_mask, d_fixed_pos,
-                               d_fixed_v, stream);
+    TdStepArgs a;
+    a.t = d_t; a.lptr = d_ligand_ptr; a.Nl = N_l; a.pos = d_ligand_pos; a.v = d_ligand_v;
+    a.pred_pos = d_pred_pos; a.pred_v = d_pred_v; a.noise = d_noise; a.uni = d_uniform;
+    a.pos_next = d_pos_next; a.v_next = d_v_next; a.log_v0 = d_log_v0; a.log_post = d_log_post;
+    a.fixed_mask = d_fixed_mask; a.fixed_pos = d_fixed_pos; a.fixed_v = d_fixed_v;
+    return step_run("td_posterior_step_fixed", m, B, a, stream);
 }
 
 extern "C" int td_posterior_step_program(const td_model *m, const int32_t *d_t, const float *d_prog_row, const int32_t *d_ligand_ptr,
@@ -271,23 +284,21 @@ extern "C" int td_posterior_step_program(const td_model *m, const int32_t *d_t, 
                                          float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos,
                                          const int64_t *d_fixed_v, void *stream) {
     if (!d_prog_row) { td_set_error("td_posterior_step_program: null d_prog_row"); return TD_EINVAL; }
-    return posterior_step_impl("td_posterior_step_program", m, d_t, d_ligand_ptr, N_l, B, d_ligand_pos, d_ligand_v, d_pred_pos,
-                               d_pred_v, d_noise, d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_post, d_fixed_mask, d_fixed_pos,
-                               d_fixed_v, stream, d_prog_row);
+    TdStepArgs a;
+    a.t = d_t; a.prow = d_prog_row; a.lptr = d_ligand_ptr; a.Nl = N_l; a.pos = d_ligand_pos; a.v = d_ligand_v;
+    a.pred_pos = d_pred_pos; a.pred_v = d_pred_v; a.noise = d_noise; a.uni = d_uniform;
+    a.pos_next = d_pos_next; a.v_next = d_v_next; a.log_v0 = d_log_v0; a.log_post = d_log_post;
+    a.fixed_mask = d_fixed_mask; a.fixed_pos = d_fixed_pos; a.fixed_v = d_fixed_v;
+    return step_run("td_posterior_step_program", m, B, a, stream);
 }
 
 extern "C" int td_renoise_step(const td_model *m, const float *d_prog_row, int64_t N_l, const float *d_ligand_pos,
                                const int64_t *d_ligand_v, const float *d_noise, const float *d_uniform, float *d_pos_next,
                                int64_t *d_v_next, float *d_log_v0, float *d_log_q, void *stream) {
-    if (!m || N_l < 0) { td_set_error("td_renoise_step: bad argument"); return TD_EINVAL; }
-    if (N_l == 0) return TD_OK;
-    if (!d_prog_row || !d_ligand_pos || !d_ligand_v || !d_noise || !d_pos_next || !d_v_next) {
-        td_set_error("td_renoise_step: null pointer");
-        return TD_EINVAL;
-    }
-    ProfScope ps(PC_POST, static_cast<hipStream_t>(stream));
-    return td_launch_renoise(d_prog_row, N_l, m->cfg.ligand_num_classes, d_ligand_pos, d_ligand_v, d_noise, d_uniform, d_pos_next,
-                             d_v_next, d_log_v0, d_log_q, static_cast<hipStream_t>(stream));
+    TdStepArgs a;
+    a.prow = d_prog_row; a.Nl = N_l; a.pos = d_ligand_pos; a.v = d_ligand_v; a.noise = d_noise; a.uni = d_uniform;
+    a.pos_next = d_pos_next; a.v_next = d_v_next; a.log_v0 = d_log_v0; a.log_post = d_log_q;
+    return step_run("td_renoise_step", m, 0, a, stream, true);
 }
 
 // ------------------------------------------------------------------------------------------ clash guidance
@@ -297,9 +308,12 @@ extern "C" int td_posterior_step_guided(const td_model *m, const int32_t *d_t, c
                                         const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
                                         float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos,
                                         const int64_t *d_fixed_v, const float *d_x0_shift, void *stream) {
-    return posterior_step_impl("td_posterior_step_guided", m, d_t, d_ligand_ptr, N_l, B, d_ligand_pos, d_ligand_v, d_pred_pos,
-                               d_pred_v, d_noise, d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_post, d_fixed_mask, d_fixed_pos,
-                               d_fixed_v, stream, d_prog_row, d_x0_shift);
+    TdStepArgs a;
+    a.t = d_t; a.prow = d_prog_row; a.lptr = d_ligand_ptr; a.Nl = N_l; a.pos = d_ligand_pos; a.v = d_ligand_v;
+    a.pred_pos = d_pred_pos; a.pred_v = d_pred_v; a.noise = d_noise; a.uni = d_uniform;
+    a.pos_next = d_pos_next; a.v_next = d_v_next; a.log_v0 = d_log_v0; a.log_post = d_log_post;
+    a.fixed_mask = d_fixed_mask; a.fixed_pos = d_fixed_pos; a.fixed_v = d_fixed_v; a.x0_shift = d_x0_shift;
+    return step_run("td_posterior_step_guided", m, B, a, stream);
 }
 
 namespace {

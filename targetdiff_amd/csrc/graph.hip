@@ -29,15 +29,6 @@ int td_launch_graph_ptr(const int64_t *batch, int64_t N, int64_t B, int32_t *ptr
     return TD_OK;
 }
 
-__device__ __forceinline__ int td_find_graph(const int32_t *__restrict__ ptr, int B, int i) {
-    int lo = 0, hi = B;   // invariant: ptr[lo] <= i < ptr[hi]
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (ptr[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void node_gid_kernel(const int32_t *__restrict__ ptr, int64_t N, int B, int32_t *__restrict__ gid) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < N) gid[i] = td_find_graph(ptr, B, (int)i);

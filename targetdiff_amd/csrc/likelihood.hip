@@ -9,20 +9,6 @@
 
 namespace {
 
-__device__ __forceinline__ float lk_log_add_exp(float a, float b) {      // molopt_score_model.py:173-175
-    const float m = fmaxf(a, b);
-    return m + logf(expf(a - m) + expf(b - m));
-}
-
-__device__ __forceinline__ int lk_find_graph(const int32_t *ptr, int B, int at) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (ptr[mid] <= at) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // q(v_{t-1} | v_t, v_0) in log space (:401-409) for one atom; log_v0 / out: [C] registers
 __device__ __forceinline__ void lk_q_v_posterior(const TdSchedules &sc, int t, int C, const float (&log_v0)[TD_MAXC],
                                                  int vt, float (&out)[TD_MAXC]) {
@@ -36,7 +22,7 @@ __device__ __forceinline__ void lk_q_v_posterior(const TdSchedules &sc, int t, i
     for (int c = 0; c < TD_MAXC; ++c) {
         if (c < C) {
             const float lvt = c == vt ? 0.f : LOG_EPS;
-            out[c] = lk_log_add_exp(log_v0[c] + l_ca, l_1mca) + lk_log_add_exp(lvt + l_a, l_1ma);
+            out[c] = td_log_add_exp(log_v0[c] + l_ca, l_1mca) + td_log_add_exp(lvt + l_a, l_1ma);
             mx = fmaxf(mx, out[c]);
         } else {
             out[c] = -INFINITY;
@@ -56,7 +42,7 @@ __global__ void perturb_kernel(TdSchedules sc, int T, const int32_t *__restrict_
                                float *__restrict__ pos_t, int64_t *__restrict__ v_t) {
     const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (at >= Nl) return;
-    const int g = lk_find_graph(lptr, B, (int)at);
+    const int g = td_find_graph(lptr, B, (int)at);
     int t = tg[g];
     t = t < 0 ? 0 : (t >= T ? T - 1 : t);
     const float a = sc.abar[t];
@@ -70,8 +56,8 @@ __global__ void perturb_kernel(TdSchedules sc, int T, const int32_t *__restrict_
     int best = 0;
     float bestv = -INFINITY;
     for (int c = 0; c < C; ++c) {
-        const float lq = lk_log_add_exp((c == v0 ? 0.f : LOG_EPS) + l_ca, l_1mca);
-        const float gum = -logf(-logf(uni[at * C + c] + 1e-30f) + 1e-30f);
+        const float lq = td_log_add_exp((c == v0 ? 0.f : LOG_EPS) + l_ca, l_1mca);
+        const float gum = td_gumbel(uni[at * C + c]);
         const float s = gum + lq;
         if (s > bestv) { bestv = s; best = c; }
     }
@@ -173,7 +159,7 @@ __global__ __launch_bounds__(64) void likelihood_prior_kernel(TdSchedules sc, in
         const int vi = (int)vidx[at];
         float klv = 0.f;
         for (int c = 0; c < C; ++c) {
-            const float lq = lk_log_add_exp((c == vi ? 0.f : LOG_EPS) + l_ca, l_1mca);
+            const float lq = td_log_add_exp((c == vi ? 0.f : LOG_EPS) + l_ca, l_1mca);
             klv += expf(lq) * (lq - (-lnK));
         }
         acc_v += klv;

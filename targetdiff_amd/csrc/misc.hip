@@ -72,52 +72,29 @@ int td_launch_head(const TdHead &hd, const float *h, const float4 *x4, const int
 }
 
 // ------------------------------------------------------------------------------------------ posterior
-__device__ __forceinline__ float td_log_add_exp(float a, float b) {      // molopt_score_model.py:173-175
-    const float m = fmaxf(a, b);
-    return m + logf(expf(a - m) + expf(b - m));
-}
-
-__device__ __forceinline__ int td_find_graph_l(const int32_t *__restrict__ ptr, int B, int i) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (ptr[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// one ligand atom of the posterior update.  pos / v may alias pos_next / v_next (the in-place form of td_session_step): every input of
-// the atom is read before its outputs are written, and atoms do not read each other.  pos_cur / v_cur (optional): second copies
-// of x_{t-1} / v_{t-1} (the trajectory slot and the current state of td_session_step); v_frozen: pos_only, v_next = the input type.
+// one ligand atom of the posterior update; `a` names its inputs and outputs (TdStepArgs, td_internal.h).  a.pos / a.v may alias
+// a.pos_next / a.v_next and a.pos_cur / a.v_cur (the in-place form of td_session_step): every input of the atom is read before its
+// outputs are written, and atoms do not read each other.  pos_cur / v_cur (optional): second copies of x_{t-1} / v_{t-1} (the
+// trajectory slot and the current state of td_session_step); v_frozen: pos_only, v_next = the input type.
 // FIXED (scaffold-constrained sampling): atoms flagged in fixed_mask do not take the posterior draw but a forward-diffused
 // copy of their known state (fixed_pos [N_l,3] centred, fixed_v [N_l]) at level t - 1, made from this step's own draws for the atom:
 //   t > 0:  x' = sqrt(abar[t-1]) x0 + sqrt(1 - abar[t-1]) eps,   v' = argmax_c(gumbel(u_c) + log q(v_{t-1} = c | v0))   (q_v_sample)
-//   t == 0: x' = x0, v' = v0.   log_post_out receives that log q (t == 0: the clamped log one-hot), log_v0_out the model's as ever.
+//   t == 0: x' = x0, v' = v0.   a.log_post receives that log q (t == 0: the clamped log one-hot), a.log_v0 the model's as ever.
 // FIXED = false compiles to the code without the feature.
 // PROG (time programs): the step goes from level t to any lower level s; its coefficients come from the slot's row
-// `prow` (TD_PROG_ROW floats, td_prog_col order, built on the host by TimeProgram.tables) instead of the per-t tables, "t == 0" reads
+// `a.prow` (TD_PROG_ROW floats, td_prog_col order, built on the host by TimeProgram.tables) instead of the per-t tables, "t == 0" reads
 // "s is clean data" (prow[TD_PROG_LAST]), and the known atoms' level is s (prow[TD_PROG_ABAR_TO], log_ca / log_1mca of s).  The network
 // still ran at t: model_mean_type 'noise' takes rc[t] / rm1[t].  PROG = false compiles to the code without the feature.
-// GUIDED (clash guidance): the step uses x0' = fl32(x0 + x0_shift[atom]) -- one rounded add on the x0 the line below
+// GUIDED (clash guidance): the step uses x0' = fl32(x0 + a.x0_shift[atom]) -- one rounded add on the x0 the line below
 // forms, on every step, the last included -- in place of x0.  Known atoms ignore it (they are overwritten).  GUIDED = false compiles to the
 // code without the feature.
-template <bool FIXED, bool PROG = false, bool GUIDED = false>
-__device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, const int32_t *__restrict__ tg,
-                                                  const int32_t *__restrict__ lptr, int B, int C, int64_t at,
-                                                  const float *pos, const int64_t *v,
-                                                  const float *__restrict__ pred_pos, const float *__restrict__ pred_v,
-                                                  const float *__restrict__ noise, const float *__restrict__ uni,
-                                                  float *pos_next, int64_t *v_next,
-                                                  float *__restrict__ log_v0_out, float *__restrict__ log_post_out,
-                                                  float *pos_cur = nullptr, int64_t *v_cur = nullptr, bool v_frozen = false,
-                                                  int mean_type = 0, const uint8_t *__restrict__ fixed_mask = nullptr,
-                                                  const float *__restrict__ fixed_pos = nullptr,
-                                                  const int64_t *__restrict__ fixed_v = nullptr,
-                                                  const float *__restrict__ prow = nullptr,
-                                                  const float *__restrict__ x0_shift = nullptr) {
-    const int g = td_find_graph_l(lptr, B, (int)at);
-    int t = tg[g];
-    t = t < 0 ? 0 : (t >= T ? T - 1 : t);
+template <bool FIXED, bool PROG, bool GUIDED>
+__device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, const TdStepArgs &a, int64_t at) {
+    const int C = a.C;
+    const float *prow = a.prow;
+    const int g = td_find_graph(a.lptr, a.B, (int)at);
+    int t = a.t[g];
+    t = t < 0 ? 0 : (t >= a.T ? a.T - 1 : t);
     // ---- positions: mean = c0[t] x0 + ct[t] x_t ; x_{t-1} = mean + [t != 0] exp(0.5 logvar[t]) eps  (:673-679)
     const bool last = PROG ? prow[TD_PROG_LAST] != 0.f : t == 0;          // the step ends on clean data: no noise, known atoms as they are
     const float c0 = PROG ? prow[TD_PROG_C0] : sc.c0[t], ct = PROG ? prow[TD_PROG_CT] : sc.ct[t];
@@ -127,35 +104,35 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
     for (int d = 0; d < 3; ++d)       // three products, two sums, each rounded on its own -- PyTorch's eager arithmetic (:376, :679), and the
                                       // same bits in every kernel this function is inlined into (no compiler-chosen FMA contraction)
     {
-        const float xt = pos[at * 3 + d];
+        const float xt = a.pos[at * 3 + d];
         // model_mean_type 'noise' (:412-416, :663-666): the network's output is x_t + eps; x0 = rc[t] x_t - rm1[t] eps
-        float x0 = td_x0_of_output(sc.rc, sc.rm1, t, mean_type, pred_pos[at * 3 + d], xt);
-        if (GUIDED) x0 = td_add_rn(x0, x0_shift[at * 3 + d]);
-        xn[d] = td_add_rn(td_add_rn(td_mul_rn(c0, x0), td_mul_rn(ct, xt)), td_mul_rn(sd, noise[at * 3 + d]));
+        float x0 = td_x0_of_output(sc.rc, sc.rm1, t, a.mean_type, a.pred_pos[at * 3 + d], xt);
+        if (GUIDED) x0 = td_add_rn(x0, a.x0_shift[at * 3 + d]);
+        xn[d] = td_add_rn(td_add_rn(td_mul_rn(c0, x0), td_mul_rn(ct, xt)), td_mul_rn(sd, a.noise[at * 3 + d]));
     }
-    const int vt = (int)v[at];
-    const bool known = FIXED && fixed_mask[at] != 0;
+    const int vt = (int)a.v[at];
+    const bool known = FIXED && a.fixed_mask[at] != 0;
     if (FIXED && known) {
         // the products and the sum each rounded on their own, as torch's eager a.sqrt() * x0 + (1 - a).sqrt() * eps (:577-588)
-        const float a = PROG ? prow[TD_PROG_ABAR_TO] : sc.abar[t - 1 < 0 ? 0 : t - 1];
-        const float sa = sqrtf(a), sb = sqrtf(1.0f - a);
+        const float ab = PROG ? prow[TD_PROG_ABAR_TO] : sc.abar[t - 1 < 0 ? 0 : t - 1];
+        const float sa = sqrtf(ab), sb = sqrtf(1.0f - ab);
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            const float x0 = fixed_pos[at * 3 + d];
-            xn[d] = last ? x0 : td_add_rn(td_mul_rn(sa, x0), td_mul_rn(sb, noise[at * 3 + d]));
+            const float x0 = a.fixed_pos[at * 3 + d];
+            xn[d] = last ? x0 : td_add_rn(td_mul_rn(sa, x0), td_mul_rn(sb, a.noise[at * 3 + d]));
         }
     }
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        pos_next[at * 3 + d] = xn[d];
-        if (pos_cur) pos_cur[at * 3 + d] = xn[d];
+        a.pos_next[at * 3 + d] = xn[d];
+        if (a.pos_cur) a.pos_cur[at * 3 + d] = xn[d];
     }
     // ---- types (:682-685)
     float lg[TD_MAXC];
     float mx = -INFINITY;
 #pragma unroll
     for (int cc = 0; cc < TD_MAXC; ++cc) {
-        lg[cc] = cc < C ? pred_v[at * C + cc] : -INFINITY;
+        lg[cc] = cc < C ? a.pred_v[at * C + cc] : -INFINITY;
         mx = fmaxf(mx, lg[cc]);
     }
     float se = 0.f;
@@ -185,7 +162,7 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
 #pragma unroll
     for (int cc = 0; cc < TD_MAXC; ++cc) us += cc < C ? expf(un[cc] - umx) : 0.f;
     const float ulse = umx + logf(us);
-    const int v0k = FIXED && known ? (int)fixed_v[at] : 0;
+    const int v0k = FIXED && known ? (int)a.fixed_v[at] : 0;
     int best = 0;
     float bestv = -INFINITY;
 #pragma unroll
@@ -194,35 +171,25 @@ __device__ __forceinline__ void td_posterior_atom(const TdSchedules &sc, int T, 
             float lp = un[cc] - ulse;
             if (FIXED && known)         // q(v_{t-1} | v0) (:383-392) at level t - 1; t == 0: the known type itself
                 lp = last ? (cc == v0k ? 0.f : LOG_EPS) : td_log_add_exp((cc == v0k ? 0.f : LOG_EPS) + l_ca, l_1mca);
-            if (log_v0_out) log_v0_out[at * C + cc] = lg[cc];
-            if (log_post_out) log_post_out[at * C + cc] = lp;
-            const float gum = -logf(-logf(uni[at * C + cc] + 1e-30f) + 1e-30f);     // :160-166
+            if (a.log_v0) a.log_v0[at * C + cc] = lg[cc];
+            if (a.log_post) a.log_post[at * C + cc] = lp;
+            const float gum = td_gumbel(a.uni[at * C + cc]);
             const float sc2 = gum + lp;
             if (sc2 > bestv) { bestv = sc2; best = cc; }        // first maximum, like argmax
         }
     }
     if (FIXED && known && last) best = v0k;
-    if (v_frozen) best = vt;
-    v_next[at] = best;
-    if (v_cur) v_cur[at] = best;
+    if (a.v_frozen) best = vt;
+    a.v_next[at] = best;
+    if (a.v_cur) a.v_cur[at] = best;
 }
 
-template <bool FIXED, bool PROG = false, bool GUIDED = false>
-__global__ void posterior_kernel(TdSchedules sc, int T, const int32_t *__restrict__ tg,
-                                 const int32_t *__restrict__ lptr, int64_t Nl, int B, int C,
-                                 const float *__restrict__ pos, const int64_t *__restrict__ v,
-                                 const float *__restrict__ pred_pos, const float *__restrict__ pred_v,
-                                 const float *__restrict__ noise, const float *__restrict__ uni,
-                                 float *__restrict__ pos_next, int64_t *__restrict__ v_next,
-                                 float *__restrict__ log_v0_out, float *__restrict__ log_post_out, int mean_type,
-                                 const uint8_t *__restrict__ fixed_mask, const float *__restrict__ fixed_pos,
-                                 const int64_t *__restrict__ fixed_v, const float *__restrict__ prow,
-                                 const float *__restrict__ x0_shift) {
+template <bool FIXED, bool PROG, bool GUIDED>
+__global__ void posterior_kernel(TdSchedules sc, TdStepArgs a) {
     const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (at >= Nl) return;
-    td_posterior_atom<FIXED, PROG, GUIDED>(sc, T, tg, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni, pos_next, v_next, log_v0_out,
-                                           log_post_out, nullptr, nullptr, false, mean_type, fixed_mask, fixed_pos, fixed_v, prow,
-                                           x0_shift);
+    if (at >= a.Nl) return;
+    a.pos_cur = nullptr, a.v_cur = nullptr, a.v_frozen = false;      // the stateless form has none of them: known at compile time
+    td_posterior_atom<FIXED, PROG, GUIDED>(sc, a, at);
 }
 
 // the last workgroup to finish advances the step index (all workgroups have read it by then): the launch is replayable as a graph node
@@ -238,167 +205,120 @@ __device__ __forceinline__ void td_step_handover(int32_t *__restrict__ step) {
 }
 
 // td_session_step: the same update with its per-step arguments taken from device memory -- step index s = step[0] selects the
-// time-step row t_all[s] and slot s of the trajectories (PROG: and row s of the program's coefficient table); the current state
-// (pos / v) is updated in place.
-template <bool FIXED, bool PROG = false, bool GUIDED = false>
-__global__ void posterior_step_kernel(TdSchedules sc, int T, int32_t *__restrict__ step, const int32_t *__restrict__ t_all,
-                                      int num_steps, const int32_t *__restrict__ lptr, int64_t Nl, int B, int C,
-                                      float *pos, int64_t *v, const float *__restrict__ pred_pos,
-                                      const float *__restrict__ pred_v, const float *__restrict__ noise,
-                                      const float *__restrict__ uni, float *__restrict__ pos_traj, int64_t *__restrict__ v_traj,
-                                      float *__restrict__ v0_traj, float *__restrict__ vt_traj, int pos_only, int mean_type,
-                                      const uint8_t *__restrict__ fixed_mask, const float *__restrict__ fixed_pos,
-                                      const int64_t *__restrict__ fixed_v, const float *__restrict__ prog_table,
-                                      const float *__restrict__ x0_shift) {
-    int s = *reinterpret_cast<volatile int32_t *>(step);
-    s = s < 0 ? 0 : (s >= num_steps ? num_steps - 1 : s);
-    const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (at < Nl) {
-        const size_t so = (size_t)s * (size_t)Nl;
-        td_posterior_atom<FIXED, PROG, GUIDED>(sc, T, t_all + (size_t)s * B, lptr, B, C, at, pos, v, pred_pos, pred_v, noise, uni,
-                                               pos_traj + so * 3, v_traj + so, v0_traj ? v0_traj + so * C : nullptr,
-                                               vt_traj ? vt_traj + so * C : nullptr, pos, pos_only ? nullptr : v, pos_only != 0,
-                                               mean_type, fixed_mask, fixed_pos, fixed_v,
-                                               PROG ? prog_table + (size_t)s * TD_PROG_ROW : nullptr, x0_shift);
+// time-step row t_all[s] and slot s of the trajectories (and row s of a program's coefficient table); the current state (pos / v,
+// which the caller also names as pos_cur / v_cur) is updated in place.
+__device__ __forceinline__ void td_step_resolve(TdStepArgs &a, const TdStepSlot &sl) {
+    int s = *reinterpret_cast<volatile int32_t *>(sl.step);
+    s = s < 0 ? 0 : (s >= sl.num_steps ? sl.num_steps - 1 : s);
+    const size_t so = (size_t)s * (size_t)a.Nl;
+    a.t = sl.t_all + (size_t)s * a.B;
+    a.pos_next = sl.pos_traj + so * 3;
+    a.v_next = sl.v_traj + so;
+    a.log_v0 = sl.v0_traj ? sl.v0_traj + so * a.C : nullptr;
+    a.log_post = sl.vt_traj ? sl.vt_traj + so * a.C : nullptr;
+    a.prow = sl.prog_table ? sl.prog_table + (size_t)s * TD_PROG_ROW : nullptr;
+    if (sl.pos_only) {
+        a.v_cur = nullptr;
+        a.v_frozen = true;
     }
-    td_step_handover(step);
+}
+
+template <bool FIXED, bool PROG, bool GUIDED>
+__global__ void posterior_step_kernel(TdSchedules sc, TdStepArgs a, TdStepSlot sl) {
+    td_step_resolve(a, sl);
+    const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (at < a.Nl) td_posterior_atom<FIXED, PROG, GUIDED>(sc, a, at);
+    td_step_handover(sl.step);
 }
 
 // ------------------------------------------------------------------------------------------ renoise (time programs)
 // One ligand atom of a forward-process step s -> t over any number of levels: every atom alike, known ones too.
 //   x' = sqrt(rho) x + sqrt(1 - rho) eps, rho = abar[t] / abar[s]  (roots in fp32, the products and the sum each rounded on their own)
 //   log q(v_t = c | v_s) = log_add_exp(log(clamp(onehot(v_s), 1e-30))_c + l_r, log1m(l_r) - ln K), v' = argmax_c(gumbel(u_c) + log q_c)
-// uni == nullptr (pos_only): the types are not touched.  pos / v may alias pos_next / v_next.
-__device__ __forceinline__ void td_renoise_atom(const float *__restrict__ prow, int C, int64_t at, const float *pos, const int64_t *v,
-                                                const float *__restrict__ noise, const float *__restrict__ uni, float *pos_next,
-                                                int64_t *v_next, float *__restrict__ log_v0_out, float *__restrict__ log_q_out,
-                                                float *pos_cur, int64_t *v_cur) {
-    const float rho = prow[TD_PROG_RHO];
+// Reads a.prow (the slot's row), C, pos, v, noise, uni and writes pos_next, v_next, log_v0 (the log one-hot of v_s), log_post (log q)
+// and the second copies.  uni == nullptr (pos_only): the types are not touched.  pos / v may alias pos_next / v_next.
+__device__ __forceinline__ void td_renoise_atom(const TdStepArgs &a, int64_t at) {
+    const int C = a.C;
+    const float rho = a.prow[TD_PROG_RHO];
     const float sa = sqrtf(rho), sb = sqrtf(1.0f - rho);
     float xn[3];
 #pragma unroll
-    for (int d = 0; d < 3; ++d) xn[d] = td_add_rn(td_mul_rn(sa, pos[at * 3 + d]), td_mul_rn(sb, noise[at * 3 + d]));
-    const int vs = (int)v[at];
+    for (int d = 0; d < 3; ++d) xn[d] = td_add_rn(td_mul_rn(sa, a.pos[at * 3 + d]), td_mul_rn(sb, a.noise[at * 3 + d]));
+    const int vs = (int)a.v[at];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        pos_next[at * 3 + d] = xn[d];
-        if (pos_cur) pos_cur[at * 3 + d] = xn[d];
+        a.pos_next[at * 3 + d] = xn[d];
+        if (a.pos_cur) a.pos_cur[at * 3 + d] = xn[d];
     }
     int best = vs;
-    if (uni) {
-        const float l_r = prow[TD_PROG_LOG_R], l_1mr = prow[TD_PROG_LOG_1MR] - logf((float)C);
+    if (a.uni) {
+        const float l_r = a.prow[TD_PROG_LOG_R], l_1mr = a.prow[TD_PROG_LOG_1MR] - logf((float)C);
         const float LOG_EPS = logf(1e-30f);
         float bestv = -INFINITY;
         best = 0;
         for (int cc = 0; cc < C; ++cc) {
             const float l0 = cc == vs ? 0.f : LOG_EPS;
             const float lq = td_log_add_exp(l0 + l_r, l_1mr);
-            if (log_v0_out) log_v0_out[at * C + cc] = l0;
-            if (log_q_out) log_q_out[at * C + cc] = lq;
-            const float gum = -logf(-logf(uni[at * C + cc] + 1e-30f) + 1e-30f);
+            if (a.log_v0) a.log_v0[at * C + cc] = l0;
+            if (a.log_post) a.log_post[at * C + cc] = lq;
+            const float gum = td_gumbel(a.uni[at * C + cc]);
             const float sc2 = gum + lq;
             if (sc2 > bestv) { bestv = sc2; best = cc; }        // first maximum, like argmax
         }
     }
-    v_next[at] = best;
-    if (v_cur) v_cur[at] = best;
+    a.v_next[at] = best;
+    if (a.v_cur) a.v_cur[at] = best;
 }
 
-__global__ void renoise_kernel(const float *__restrict__ prow, int64_t Nl, int C, const float *__restrict__ pos,
-                               const int64_t *__restrict__ v, const float *__restrict__ noise, const float *__restrict__ uni,
-                               float *__restrict__ pos_next, int64_t *__restrict__ v_next, float *__restrict__ log_v0_out,
-                               float *__restrict__ log_q_out) {
+__global__ void renoise_kernel(TdStepArgs a) {
     const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (at >= Nl) return;
-    td_renoise_atom(prow, C, at, pos, v, noise, uni, pos_next, v_next, log_v0_out, log_q_out, nullptr, nullptr);
+    if (at >= a.Nl) return;
+    a.pos_cur = nullptr, a.v_cur = nullptr;
+    td_renoise_atom(a, at);
 }
 
 // the session-step form: slot s = step[0] of the trajectories and row s of the table, the state in place, the step index advanced
-__global__ void renoise_step_kernel(const float *__restrict__ prog_table, int32_t *__restrict__ step, int num_steps, int64_t Nl, int C,
-                                    float *pos, int64_t *v, const float *__restrict__ noise, const float *__restrict__ uni,
-                                    float *__restrict__ pos_traj, int64_t *__restrict__ v_traj, float *__restrict__ v0_traj,
-                                    float *__restrict__ vt_traj, int pos_only) {
-    int s = *reinterpret_cast<volatile int32_t *>(step);
-    s = s < 0 ? 0 : (s >= num_steps ? num_steps - 1 : s);
+__global__ void renoise_step_kernel(TdStepArgs a, TdStepSlot sl) {
+    td_step_resolve(a, sl);
+    if (sl.pos_only) a.uni = nullptr;
     const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (at < Nl) {
-        const size_t so = (size_t)s * (size_t)Nl;
-        td_renoise_atom(prog_table + (size_t)s * TD_PROG_ROW, C, at, pos, v, noise, pos_only ? nullptr : uni, pos_traj + so * 3,
-                        v_traj + so, v0_traj ? v0_traj + so * C : nullptr, vt_traj ? vt_traj + so * C : nullptr, pos,
-                        pos_only ? nullptr : v);
-    }
-    td_step_handover(step);
+    if (at < a.Nl) td_renoise_atom(a, at);
+    td_step_handover(sl.step);
 }
 
-int td_launch_posterior(const TdSchedules &sc, int T, const int32_t *t, const int32_t *lptr, int64_t Nl, int64_t B,
-                        int classes, const float *pos, const int64_t *v, const float *pred_pos,
-                        const float *pred_v, const float *noise, const float *uni, float *pos_next,
-                        int64_t *v_next, float *log_v0, float *log_post, hipStream_t s, int mean_type,
-                        const uint8_t *fixed_mask, const float *fixed_pos, const int64_t *fixed_v, const float *prow,
-                        const float *x0_shift) {
-    if (Nl == 0) return TD_OK;
-    const dim3 grid((unsigned)((Nl + 127) / 128)), block(128);
-#define TD_POST(F, P, fm, fp, fv, pr)                                                                                                  \
-    do {                                                                                                                               \
-        if (x0_shift)                                                                                                                  \
-            posterior_kernel<F, P, true><<<grid, block, 0, s>>>(sc, T, t, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise,   \
-                                                                uni, pos_next, v_next, log_v0, log_post, mean_type, fm, fp, fv, pr,    \
-                                                                x0_shift);                                                             \
-        else                                                                                                                           \
-            posterior_kernel<F, P><<<grid, block, 0, s>>>(sc, T, t, lptr, Nl, (int)B, classes, pos, v, pred_pos, pred_v, noise, uni,    \
-                                                          pos_next, v_next, log_v0, log_post, mean_type, fm, fp, fv, pr, nullptr);     \
-    } while (0)
-    // known atoms present: the variant with the replacement branch (needs sc.abar, checked by the callers); a program slot: the
-    // variant that reads the slot's row; a shift of x0 (clash guidance): the variant that adds it -- no shift, the kernels as they were
-    if (prow) { if (fixed_mask) TD_POST(true, true, fixed_mask, fixed_pos, fixed_v, prow); else TD_POST(false, true, nullptr, nullptr, nullptr, prow); }
-    else if (fixed_mask) TD_POST(true, false, fixed_mask, fixed_pos, fixed_v, nullptr);
-    else TD_POST(false, false, nullptr, nullptr, nullptr, nullptr);
-#undef TD_POST
+// a workgroup of 128 atoms
+static dim3 step_grid(const TdStepArgs &a) { return dim3((unsigned)((a.Nl + 127) / 128)); }
+
+// known atoms present: the variant with the replacement branch (needs sc.abar, checked by the callers); a program slot: the variant
+// that reads the slot's row; a shift of x0 (clash guidance): the variant that adds it
+int td_launch_posterior(const TdSchedules &sc, const TdStepArgs &a, hipStream_t s) {
+    if (a.Nl == 0) return TD_OK;
+    td_dispatch3(a.fixed_mask != nullptr, a.prow != nullptr, a.x0_shift != nullptr, [&](auto F, auto P, auto G) {
+        posterior_kernel<F.value, P.value, G.value><<<step_grid(a), dim3(128), 0, s>>>(sc, a);
+    });
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
 
-int td_launch_posterior_step(const TdSchedules &sc, int T, int32_t *step, const int32_t *t_all, int num_steps, const int32_t *lptr,
-                             int64_t Nl, int64_t B, int classes, float *pos, int64_t *v, const float *pred_pos, const float *pred_v,
-                             const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
-                             int pos_only, hipStream_t s, int mean_type, const uint8_t *fixed_mask, const float *fixed_pos,
-                             const int64_t *fixed_v, const float *prog_table, const float *x0_shift) {
-    if (Nl == 0) return TD_OK;
-    const dim3 grid((unsigned)((Nl + 127) / 128)), block(128);
-#define TD_POST(F, P, fm, fp, fv, pt)                                                                                                  \
-    do {                                                                                                                               \
-        if (x0_shift)                                                                                                                  \
-            posterior_step_kernel<F, P, true><<<grid, block, 0, s>>>(sc, T, step, t_all, num_steps, lptr, Nl, (int)B, classes, pos, v,  \
-                                                                     pred_pos, pred_v, noise, uni, pos_traj, v_traj, v0_traj, vt_traj, \
-                                                                     pos_only, mean_type, fm, fp, fv, pt, x0_shift);                   \
-        else                                                                                                                           \
-            posterior_step_kernel<F, P><<<grid, block, 0, s>>>(sc, T, step, t_all, num_steps, lptr, Nl, (int)B, classes, pos, v,        \
-                                                               pred_pos, pred_v, noise, uni, pos_traj, v_traj, v0_traj, vt_traj,       \
-                                                               pos_only, mean_type, fm, fp, fv, pt, nullptr);                          \
-    } while (0)
-    if (prog_table) { if (fixed_mask) TD_POST(true, true, fixed_mask, fixed_pos, fixed_v, prog_table); else TD_POST(false, true, nullptr, nullptr, nullptr, prog_table); }
-    else if (fixed_mask) TD_POST(true, false, fixed_mask, fixed_pos, fixed_v, nullptr);
-    else TD_POST(false, false, nullptr, nullptr, nullptr, nullptr);
-#undef TD_POST
+int td_launch_posterior_step(const TdSchedules &sc, const TdStepArgs &a, const TdStepSlot &sl, hipStream_t s) {
+    if (a.Nl == 0) return TD_OK;
+    td_dispatch3(a.fixed_mask != nullptr, sl.prog_table != nullptr, a.x0_shift != nullptr, [&](auto F, auto P, auto G) {
+        posterior_step_kernel<F.value, P.value, G.value><<<step_grid(a), dim3(128), 0, s>>>(sc, a, sl);
+    });
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
 
-int td_launch_renoise(const float *prow, int64_t Nl, int classes, const float *pos, const int64_t *v, const float *noise,
-                      const float *uni, float *pos_next, int64_t *v_next, float *log_v0, float *log_q, hipStream_t s) {
-    if (Nl == 0) return TD_OK;
-    renoise_kernel<<<dim3((unsigned)((Nl + 127) / 128)), dim3(128), 0, s>>>(prow, Nl, classes, pos, v, noise, uni, pos_next, v_next,
-                                                                           log_v0, log_q);
+int td_launch_renoise(const TdStepArgs &a, hipStream_t s) {
+    if (a.Nl == 0) return TD_OK;
+    renoise_kernel<<<step_grid(a), dim3(128), 0, s>>>(a);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
 
-int td_launch_renoise_step(const float *prog_table, int32_t *step, int num_steps, int64_t Nl, int classes, float *pos, int64_t *v,
-                           const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
-                           int pos_only, hipStream_t s) {
-    if (Nl == 0) return TD_OK;
-    renoise_step_kernel<<<dim3((unsigned)((Nl + 127) / 128)), dim3(128), 0, s>>>(prog_table, step, num_steps, Nl, classes, pos, v, noise,
-                                                                                uni, pos_traj, v_traj, v0_traj, vt_traj, pos_only);
+int td_launch_renoise_step(const TdStepArgs &a, const TdStepSlot &sl, hipStream_t s) {
+    if (a.Nl == 0) return TD_OK;
+    renoise_step_kernel<<<step_grid(a), dim3(128), 0, s>>>(a, sl);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }

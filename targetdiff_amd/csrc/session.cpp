@@ -477,6 +477,28 @@ extern "C" int td_session_forward(td_session *S, const float *d_ligand_pos, cons
                           d_pred_ligand_v, d_final_ligand_h, s);
 }
 
+namespace {
+// the argument blocks of a step's update kernel (posterior or renoise): the state is updated in place, slot s of the trajectories filled
+TdStepArgs step_args(const td_session *S, const td_step_io &io) {
+    const td_model *m = S->m;
+    TdStepArgs a;
+    a.lptr = S->lptr; a.Nl = S->Nl; a.B = (int)S->B;
+    a.C = m->cfg.ligand_num_classes; a.T = m->cfg.num_timesteps; a.mean_type = m->cfg.model_mean_type;
+    a.pos = io.d_ligand_pos; a.v = io.d_ligand_v; a.pos_cur = io.d_ligand_pos; a.v_cur = io.d_ligand_v;
+    a.pred_pos = S->pred_pos; a.pred_v = S->pred_v; a.noise = io.d_noise; a.uni = io.d_uniform;
+    a.fixed_mask = io.d_fixed_mask; a.fixed_pos = io.d_fixed_pos; a.fixed_v = io.d_fixed_v;
+    a.x0_shift = S->guide ? S->guide_shift : nullptr;
+    return a;
+}
+TdStepSlot step_slot(const td_session *S, const td_step_io &io) {
+    TdStepSlot sl;
+    sl.step = io.d_step; sl.t_all = io.d_t_all; sl.num_steps = io.num_steps;
+    sl.pos_traj = io.d_pos_traj; sl.v_traj = io.d_v_traj; sl.v0_traj = io.d_v0_traj; sl.vt_traj = io.d_vt_traj;
+    sl.pos_only = io.pos_only; sl.prog_table = S->prog_table;
+    return sl;
+}
+}  // namespace
+
 namespace tdapi {
 // the launches of one step, in order (eagerly or into a capturing stream)
 int session_step_issue(td_session *S, const td_step_io &io, hipStream_t s) {
@@ -493,11 +515,7 @@ int session_step_issue(td_session *S, const td_step_io &io, hipStream_t s) {
         a.xt = io.d_ligand_pos; a.rc = m->sched.rc; a.rm1 = m->sched.rm1; a.t_all = io.d_t_all; a.step = io.d_step;
         if ((rc = td_launch_clash_shift(a, S->guide_shift, s)) != TD_OK) return rc;
     }
-    return td_launch_posterior_step(m->sched, m->cfg.num_timesteps, io.d_step, io.d_t_all, io.num_steps, S->lptr, S->Nl, S->B,
-                                    m->cfg.ligand_num_classes, io.d_ligand_pos, io.d_ligand_v, S->pred_pos, S->pred_v, io.d_noise,
-                                    io.d_uniform, io.d_pos_traj, io.d_v_traj, io.d_v0_traj, io.d_vt_traj, io.pos_only, s,
-                                    m->cfg.model_mean_type, io.d_fixed_mask, io.d_fixed_mask ? io.d_fixed_pos : nullptr,
-                                    io.d_fixed_mask ? io.d_fixed_v : nullptr, S->prog_table, S->guide ? S->guide_shift : nullptr);
+    return td_launch_posterior_step(m->sched, step_args(S, io), step_slot(S, io), s);
 }
 }  // namespace tdapi
 
@@ -556,14 +574,7 @@ extern "C" int td_session_step(td_session *S, const td_step_io *io, int32_t use_
         td_set_error("td_session_step: bad argument");
         return TD_EINVAL;
     }
-    if (io->d_fixed_mask && (!io->d_fixed_pos || !io->d_fixed_v)) {
-        td_set_error("td_session_step: d_fixed_mask needs d_fixed_pos and d_fixed_v");
-        return TD_EINVAL;
-    }
-    if (io->d_fixed_mask && !S->m->sched.abar) {
-        td_set_error("td_session_step: the model was created without alphas_cumprod (8 schedule arrays)");
-        return TD_EINVAL;
-    }
+    if (const int rc = check_known_atoms("td_session_step", S->m, io->d_fixed_mask, io->d_fixed_pos, io->d_fixed_v)) return rc;
     if (S->guide && S->m->cfg.model_mean_type == 1 && (!S->m->sched.rc || !S->m->sched.rm1)) {
         td_set_error("td_session_step: guidance with model_mean_type 'noise' needs the 10 schedule arrays");
         return TD_EINVAL;
@@ -580,9 +591,7 @@ extern "C" int td_session_step(td_session *S, const td_step_io *io, int32_t use_
             // a forward-process step: one kernel, launched eagerly whatever use_graph says; no denoiser, no capture
             S->last_stream = s;
             ProfScope ps(PC_POST, s);
-            return td_launch_renoise_step(S->prog_table, io->d_step, io->num_steps, S->Nl, S->m->cfg.ligand_num_classes, io->d_ligand_pos,
-                                          io->d_ligand_v, io->d_noise, io->d_uniform, io->d_pos_traj, io->d_v_traj, io->d_v0_traj,
-                                          io->d_vt_traj, io->pos_only, s);
+            return td_launch_renoise_step(step_args(S, *io), step_slot(S, *io), s);
         }
     }
     // measurement hooks put events / trace pointers into the launch sequence: those steps are issued launch by launch

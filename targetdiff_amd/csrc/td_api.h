@@ -177,6 +177,9 @@ int run_backbone(const td_model *m, Workspace &w, const GraphTab &gt, float *h, 
                  float4 **x_final, hipStream_t s, bool init_xn, bool layer0_x2h_done = false,
                  const int32_t *hop_rows = nullptr, const int32_t *hop_count = nullptr, int hop_levels = 0,
                  const FwdReach *fwd = nullptr);
+// known atoms of a posterior step (scaffold-constrained sampling): a mask needs both arrays and a model with alphas_cumprod; `who`
+// prefixes the error (forward.cpp)
+int check_known_atoms(const char *who, const td_model *m, const uint8_t *d_fixed_mask, const float *d_fixed_pos, const int64_t *d_fixed_v);
 int build_default_graph(const td_model *m, Workspace &w, int64_t N, int max_graph_nodes, hipStream_t s);
 // stream-ordered memory: td_debug_fail_alloc makes the n-th allocation from now fail (fault injection for the error paths)
 extern std::atomic<int> g_fail_alloc;

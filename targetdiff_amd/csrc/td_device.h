@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -159,6 +160,24 @@ __device__ __forceinline__ float td_x0_of_output(const float *__restrict__ rc, c
     if (mean_type == 1) return td_add_rn(td_mul_rn(rc[t], xt), -td_mul_rn(rm1[t], td_add_rn(out, -xt)));
     return out;
 }
+
+// graph of atom / node i: the g with ptr[g] <= i < ptr[g + 1] (ptr [B + 1], ascending)
+__device__ __forceinline__ int td_find_graph(const int32_t *__restrict__ ptr, int B, int i) {
+    int lo = 0, hi = B;   // invariant: ptr[lo] <= i < ptr[hi]
+    while (hi - lo > 1) {
+        int mid = (lo + hi) >> 1;
+        if (ptr[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ float td_log_add_exp(float a, float b) {      // molopt_score_model.py:173-175
+    const float m = fmaxf(a, b);
+    return m + logf(expf(a - m) + expf(b - m));
+}
+
+// Gumbel(0, 1) draw from a uniform one (molopt_score_model.py:160-166)
+__device__ __forceinline__ float td_gumbel(float u) { return -logf(-logf(u + 1e-30f) + 1e-30f); }
 
 // distance^2 with the project's fixed association and no FMA contraction (oracle/shims.py)
 __device__ __forceinline__ float td_dist2(float dx, float dy, float dz) {

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/targetdiff_hip.h"
 
@@ -332,24 +333,58 @@ int td_launch_slots_to_dense(const int32_t *cptr, const int32_t *cnbr, int64_t N
 // misc.hip
 int td_launch_head(const TdHead &hd, const float *h, const float4 *x4, const int32_t *lig_node, int64_t Nl,
                    int classes, float *pred_pos, float *pred_v, float *lig_h, hipStream_t s);
-int td_launch_posterior(const TdSchedules &sc, int T, const int32_t *t, const int32_t *lptr, int64_t Nl, int64_t B,
-                        int classes, const float *pos, const int64_t *v, const float *pred_pos,
-                        const float *pred_v, const float *noise, const float *uni, float *pos_next,
-                        int64_t *v_next, float *log_v0, float *log_post, hipStream_t s, int mean_type = 0,
-                        const uint8_t *fixed_mask = nullptr, const float *fixed_pos = nullptr, const int64_t *fixed_v = nullptr,
-                        const float *prow = nullptr, const float *x0_shift = nullptr);
-int td_launch_posterior_step(const TdSchedules &sc, int T, int32_t *step, const int32_t *t_all, int num_steps, const int32_t *lptr,
-                             int64_t Nl, int64_t B, int classes, float *pos, int64_t *v, const float *pred_pos, const float *pred_v,
-                             const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
-                             int pos_only, hipStream_t s, int mean_type = 0, const uint8_t *fixed_mask = nullptr,
-                             const float *fixed_pos = nullptr, const int64_t *fixed_v = nullptr, const float *prog_table = nullptr,
-                             const float *x0_shift = nullptr);
-// time programs: prow = one slot's TD_PROG_ROW floats, prog_table = every slot's (device memory); the renoise step of a slot
-int td_launch_renoise(const float *prow, int64_t Nl, int classes, const float *pos, const int64_t *v, const float *noise,
-                      const float *uni, float *pos_next, int64_t *v_next, float *log_v0, float *log_q, hipStream_t s);
-int td_launch_renoise_step(const float *prog_table, int32_t *step, int num_steps, int64_t Nl, int classes, float *pos, int64_t *v,
-                           const float *noise, const float *uni, float *pos_traj, int64_t *v_traj, float *v0_traj, float *vt_traj,
-                           int pos_only, hipStream_t s);
+// The per-atom update that ends a sampling step -- the posterior draw or the renoise step of a time program (misc.hip; DESIGN.md
+// section 3) -- reads and writes what this block names, over N_l ligand atoms.  pos / v may alias pos_next / v_next and pos_cur / v_cur
+// (the in-place form of td_session_step): none of the pointers is __restrict__.  Every member is value-initialised ({}: null, 0, false).
+struct TdStepArgs {
+    const int32_t *lptr{};              // [B + 1] ligand atoms of every graph (the renoise step does not read it)
+    int64_t Nl{};                       // ligand atoms: 0 launches nothing
+    int B{}, C{}, T{};                  // graphs, ligand classes, diffusion levels
+    int mean_type{};                    // 0: pred_pos is x0 (model_mean_type 'C0'); 1: it is x_t + eps ('noise')
+    const int32_t *t{};                 // [B] time step of every graph; null only where a session slot fills it in
+    const float *pos{};                 // [N_l,3] x_t, never null
+    const int64_t *v{};                 // [N_l] v_t, never null
+    const float *pred_pos{};            // [N_l,3] the network's output, never null for the posterior (renoise: not read)
+    const float *pred_v{};              // [N_l,C] logits, likewise
+    const float *noise{};               // [N_l,3] Gaussian draws, never null
+    const float *uni{};                 // [N_l,C] uniform draws; null (renoise only): the types are not touched
+    float *pos_next{};                  // [N_l,3] x_{t-1}; null only where a session slot fills it in
+    int64_t *v_next{};                  // [N_l] v_{t-1}, likewise
+    float *log_v0{};                    // [N_l,C] log-probabilities of the predicted v0; null: not written
+    float *log_post{};                  // [N_l,C] log-probabilities the draw was taken from; null: not written
+    float *pos_cur{};                   // second copy of x_{t-1} (a session's current state); null: none
+    int64_t *v_cur{};                   // second copy of v_{t-1}; null: none
+    bool v_frozen{};                    // pos_only: v_next = the input type
+    const uint8_t *fixed_mask{};        // [N_l] known atoms (scaffold-constrained sampling); null: the kernels without the feature
+    const float *fixed_pos{};           // [N_l,3] their centred positions; read only with fixed_mask
+    const int64_t *fixed_v{};           // [N_l] their types; read only with fixed_mask
+    const float *prow{};                // TD_PROG_ROW floats, a time program's slot; null: the per-t schedule tables (renoise: never null)
+    const float *x0_shift{};            // [N_l,3] clash-guidance shift of the predicted x0; null: the kernels without the feature
+};
+// What the session-step form adds: the step's own arguments are in device memory, slot s = step[0] of each array (td_step_io)
+struct TdStepSlot {
+    int32_t *step{};                    // [2] step index and workgroup ticket, advanced by the launch; never null
+    const int32_t *t_all{};             // [num_steps,B] time steps; row s becomes TdStepArgs::t
+    int num_steps{};                    // s is clamped to num_steps - 1
+    float *pos_traj{};                  // [num_steps,N_l,3]; slot s becomes pos_next, never null
+    int64_t *v_traj{};                  // [num_steps,N_l]; slot s becomes v_next, never null
+    float *v0_traj{};                   // [num_steps,N_l,C]; slot s becomes log_v0; null: not written
+    float *vt_traj{};                   // [num_steps,N_l,C]; slot s becomes log_post; null: not written
+    int pos_only{};                     // != 0: the types stay (v_frozen, no v_cur, renoise without uniform draws)
+    const float *prog_table{};          // [num_steps,TD_PROG_ROW] a time program; row s becomes prow; null: no program
+};
+// Three runtime switches as template arguments: f(std::bool_constant<a>, std::bool_constant<b>, std::bool_constant<c>)
+template <class F>
+void td_dispatch3(bool a, bool b, bool c, F &&f) {
+    const auto pick = [](bool on, auto &&g) { on ? g(std::true_type{}) : g(std::false_type{}); };
+    pick(a, [&](auto A) { pick(b, [&](auto B) { pick(c, [&](auto C) { f(A, B, C); }); }); });
+}
+// a null fixed_mask / prow (prog_table) / x0_shift selects the kernel variant without that feature
+int td_launch_posterior(const TdSchedules &sc, const TdStepArgs &a, hipStream_t s);
+int td_launch_posterior_step(const TdSchedules &sc, const TdStepArgs &a, const TdStepSlot &sl, hipStream_t s);
+// time programs: the renoise step of a slot (reads prow, Nl, C, pos, v, noise, uni and the outputs)
+int td_launch_renoise(const TdStepArgs &a, hipStream_t s);
+int td_launch_renoise_step(const TdStepArgs &a, const TdStepSlot &sl, hipStream_t s);
 // guidance.hip (clash guidance): the arguments of one launch over B graphs.  Protein atoms either as ppos [N_p,3] +
 // sigma [N_p] or as prot4 [N_p] (x, y, z, sigma) (a session's packed copy).  eval [N_l,3]: the positions the energy is taken at; with
 // mean_type 1 (a session step of a model_mean_type 'noise' model) it is the network's output and x0 is formed from it, xt and the

@@ -806,16 +806,17 @@ class ReverseSampler:
             self.s += 1
             return
         prog = {} if self._prog_table is None else dict(prog_row=self._prog_table[s])
+        # pos_only: the types go to a scratch buffer and the two log outputs are not written
+        po = self.pos_only
+        out = dict(pos_next=self.pos_traj[s], v_next=self._v_scratch if po else self.v_traj[s], log_v0=None if po else self.v0_traj[s])
+        log_vt = None if po else self.vt_traj[s]
         if self._renoise(s):              # a forward-process step (time programs): no denoiser call
             self._draw(s)
-            if self.pos_only:
-                native.renoise_step(self._prog_table[s], self.lpos, self.lv, self._noise, None, pos_next=self.pos_traj[s],
-                                    v_next=self._v_scratch)
+            native.renoise_step(self._prog_table[s], self.lpos, self.lv, self._noise, None if po else self._uniform, log_q=log_vt, **out)
+            if po:
                 self.v_traj[s].copy_(self.lv)
                 self.lpos = self.pos_traj[s]
             else:
-                native.renoise_step(self._prog_table[s], self.lpos, self.lv, self._noise, self._uniform, pos_next=self.pos_traj[s],
-                                    v_next=self.v_traj[s], log_v0=self.v0_traj[s], log_q=self.vt_traj[s])
                 self.lpos, self.lv = self.pos_traj[s], self.v_traj[s]
             self.s += 1
             return
@@ -840,18 +841,13 @@ class ReverseSampler:
             g = self.guidance
             prog = dict(prog, x0_shift=capi.clash_shift(self.ppos, self._sigma, self.pptr, self.lptr, x0.contiguous(), g.weight,
                                                         g.max_shift, out=self._shift, check=False))
-        if self.pos_only:
-            native.posterior_step(self.t_all[s], self.lptr, self.lpos, self.lv, preds['pred_ligand_pos'],
-                                  preds['pred_ligand_v'], self._noise, self._half, pos_next=self.pos_traj[s],
-                                  v_next=self._v_scratch, **self._fixed, **prog)
+        native.posterior_step(self.t_all[s], self.lptr, self.lpos, self.lv, preds['pred_ligand_pos'], preds['pred_ligand_v'],
+                              self._noise, self._half if po else self._uniform, log_post=log_vt, **out, **self._fixed, **prog)
+        if po:
             self.v_traj[s].copy_(self.lv)                                                  # :689
             self.lpos = self.pos_traj[s]
-            self.s += 1
-            return
-        native.posterior_step(self.t_all[s], self.lptr, self.lpos, self.lv, preds['pred_ligand_pos'],
-                              preds['pred_ligand_v'], self._noise, self._uniform, pos_next=self.pos_traj[s],
-                              v_next=self.v_traj[s], log_v0=self.v0_traj[s], log_post=self.vt_traj[s], **self._fixed, **prog)
-        self.lpos, self.lv = self.pos_traj[s], self.v_traj[s]
+        else:
+            self.lpos, self.lv = self.pos_traj[s], self.v_traj[s]
         self.s += 1
 
     @torch.no_grad()

@@ -290,6 +290,36 @@ int td_posterior_step_guided(const td_model *m, const int32_t *d_t, const float 
                              const uint8_t *d_fixed_mask, const float *d_fixed_pos, const int64_t *d_fixed_v,
                              const float *d_x0_shift, void *stream);
 
+/* ---- sample quality of ligand frames ("Sample quality"; replaces the chemistry-free half of
+ *      scripts/evaluate_diffusion.py:75-87: utils/evaluation/analyze.py check_stability with hs=False, the counts behind
+ *      utils/evaluation/eval_bond_length.py get_pair_length_profile and the element Counter).  No model handle.
+ *      Input: S frames of the same B molecules: d_pos [S,N_l,3] fp32, d_v [S,N_l] int64 class indices, d_ligand_ptr [B+1] int32
+ *      prefix offsets shared by all frames.  class_atomic_number [K] (HOST memory, 1 <= K <= 64): the atomic number of every
+ *      class; TD_EINVAL when one is not H C N O F P S Cl.  An atom whose class is outside [0, K) has no element: it bonds with
+ *      nothing, is never stable and is counted nowhere (a binding refuses it).
+ *      Per pair i < j of one molecule: d = sqrt((dx dx + dy dy) + dz dz) in float64 on the widened coordinates, every product and
+ *      sum rounded once; with D = 100 d and b1, b2, b3 the single / double / triple bond length of the element pair in pm (-1:
+ *      none), the order is 0 if D >= b1 + 10, else 1 if D >= b2 + 5, else 2 if D >= b3 + 3, else 3.  nr_bonds of an atom is the
+ *      sum of its pairs' orders; an atom is stable when 0 < nr_bonds <= the bonds its element may hold (1 4 3 2 1 5 4 1); a
+ *      molecule is stable when all its atoms are (0 atoms: stable; 1 atom: not).
+ *      Output: d_nr_bonds [S,N_l] int32 (may be NULL), d_stable_atoms [S,B] int32, d_mol_stable [S,B] uint8, and per frame, over
+ *      the molecules whose d_include [S,B] byte is non-zero (NULL: all): d_hist [S,P,128] int64 pair-distance histograms and
+ *      d_counts [S,8] int64 atoms per element (H C N O F P S Cl).  Both are zeroed by the call.  Profile p (HOST array, P <= 4)
+ *      takes the pairs whose unordered elements are (z1, z2) (0: any) and whose d < cutoff, into bin numpy.searchsorted(edges, d,
+ *      'left'), found by a search of d_edges [n_edges] (DEVICE memory, float64, ascending, 1 <= n_edges <= 127; not read on the
+ *      host: a binding checks the order).  All outputs are integers summed in integer arithmetic: they do not depend on the grid
+ *      or on the order of arrival.  (An addition: TD_ABI_VERSION stays 5.) */
+typedef struct td_pair_profile {
+    int32_t z1, z2;
+    double cutoff;
+    int32_t n_edges, reserved;
+    const double *d_edges;
+} td_pair_profile;
+int td_quality_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                      const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const td_pair_profile *profiles,
+                      int32_t P, int32_t *d_nr_bonds, int32_t *d_stable_atoms, uint8_t *d_mol_stable, int64_t *d_hist,
+                      int64_t *d_counts, void *stream);
+
 /* ---- standalone EGNN refine net (replaces: models/egnn.py EGNN / EnBaseLayer as get_refine_net('egnn', config) builds
  *      it, models/molopt_score_model.py:34-42: num_r_gaussian = 1, kNN rebuilt per layer, SiLU, no LayerNorm, hidden 128,
  *      4 edge types, k = 32).  `host_weights`: per layer, in this order and as PyTorch stores them: edge_mlp.net.0.{weight

@@ -36,6 +36,12 @@ class TdPropTape(ctypes.Structure):
                 ('has_output_kind', c_int32), ('has_enc_node', c_int32), ('d_workspace', c_void_p), ('workspace_bytes', c_size_t)]
 
 
+class TdPairProfile(ctypes.Structure):
+    """td_pair_profile of include/targetdiff_hip.h"""
+    _fields_ = [('z1', c_int32), ('z2', c_int32), ('cutoff', ctypes.c_double), ('n_edges', c_int32), ('reserved', c_int32),
+                ('d_edges', c_void_p)]
+
+
 class TdPropConfig(ctypes.Structure):
     """td_prop_config of include/targetdiff_hip.h"""
     _fields_ = [('hidden_dim', c_int32), ('num_layers', c_int32), ('knn', c_int32), ('num_r_gaussian', c_int32), ('cutoff', c_float),
@@ -73,6 +79,7 @@ SIGNATURES = {
     'td_renoise_step': (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_clash_shift': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_float, c_float, _P, _P]),
     'td_clash_report': (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+    'td_quality_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, c_int32, _P, _P, _P, _P, _P, _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_center_pos': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int32, c_int32, _P]),
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
@@ -777,6 +784,79 @@ def clash_report(protein_pos, sigma, protein_ptr, ligand_ptr, pos):
                                    _ptr(pos, torch.float32, 'pos'), _ptr(count), _ptr(energy), _ptr(min_dist), _stream(dev)),
                'td_clash_report')
     return count, energy, min_dist
+
+
+QUALITY_MAX_CLASSES, QUALITY_MAX_PROFILES, QUALITY_BINS = 64, 4, 128      # TD_QUALITY_* (csrc/td_internal.h)
+QUALITY_ELEMENTS = (1, 6, 7, 8, 9, 15, 16, 17)                            # H C N O F P S Cl: the columns of the element counts
+
+
+def _quality_inputs(pos, v, ligand_ptr, class_z, include, profiles, check=True):
+    """Shapes, the class table and the profiles of a quality_report call; with ``check`` the offsets and the classes are looked at on
+    the host (one synchronisation), as _clash_inputs does.  Returns (S, N_l, B, class table as int32 numpy, [(z1, z2, cutoff, edges
+    as float64 numpy)])."""
+    if pos.dim() != 3 or pos.shape[2] != 3 or tuple(v.shape) != tuple(pos.shape[:2]):
+        raise ValueError(f'pos / v must be [S, N_l, 3] / [S, N_l] (got {tuple(pos.shape)}, {tuple(v.shape)})')
+    S, Nl, B = pos.shape[0], pos.shape[1], ligand_ptr.numel() - 1
+    if ligand_ptr.dim() != 1 or B < 0:
+        raise ValueError('ligand_ptr must be [B + 1]')
+    cz = np.asarray(class_z, dtype=np.int64).reshape(-1)
+    if not 1 <= cz.size <= QUALITY_MAX_CLASSES:
+        raise ValueError(f'the class table must have 1 .. {QUALITY_MAX_CLASSES} entries (got {cz.size})')
+    if not np.isin(cz, QUALITY_ELEMENTS).all():
+        raise ValueError(f'atomic numbers {sorted(set(cz.tolist()) - set(QUALITY_ELEMENTS))} are outside the bond-length table '
+                         f'{QUALITY_ELEMENTS}')
+    if include is not None and (tuple(include.shape) != (S, B) or include.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError(f'include must be [{S}, {B}] bool or uint8')
+    if len(profiles) > QUALITY_MAX_PROFILES:
+        raise ValueError(f'at most {QUALITY_MAX_PROFILES} pair profiles (got {len(profiles)})')
+    prof = []
+    for z1, z2, cutoff, edges in profiles:
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+        if not 1 <= e.size <= QUALITY_BINS - 1:
+            raise ValueError(f'a pair profile has 1 .. {QUALITY_BINS - 1} edges (got {e.size})')
+        if not np.isfinite(e).all() or bool((e[1:] < e[:-1]).any()):
+            raise ValueError('the edges of a pair profile must be finite and ascending')
+        if any(z != 0 and z not in QUALITY_ELEMENTS for z in (int(z1), int(z2))):
+            raise ValueError(f'a pair profile names elements of {QUALITY_ELEMENTS} or 0 for any (got {z1}, {z2})')
+        if not float(cutoff) > 0.0:
+            raise ValueError('the cutoff of a pair profile must be > 0')
+        prof.append((int(z1), int(z2), float(cutoff), e))
+    if check and B > 0:
+        lp = ligand_ptr.cpu()
+        if int(lp[0]) != 0 or int(lp[-1]) != Nl or bool((lp[1:] < lp[:-1]).any()):
+            raise ValueError('ligand_ptr must be non-decreasing prefix offsets from 0 to N_l')
+    if check and v.numel() and (int(v.min()) < 0 or int(v.max()) >= cz.size):
+        raise ValueError(f'v must be in [0, {cz.size})')
+    return S, Nl, B, cz.astype(np.int32), prof
+
+
+def quality_report(pos, v, ligand_ptr, class_z, profiles=(), include=None, return_nr_bonds=True, check=True):
+    """Stability and pair-distance counts of S frames of B molecules (td_quality_report, include/targetdiff_hip.h); no model handle
+    needed.  ``pos`` [S, N_l, 3] fp32, ``v`` [S, N_l] int64, ``ligand_ptr`` [B + 1] int32, ``class_z`` the atomic number per class,
+    ``profiles`` a sequence of (z1, z2, cutoff, edges), ``include`` [S, B] bool / uint8 or None.  Returns a dict of device tensors:
+    nr_bonds [S, N_l] int32 (None without ``return_nr_bonds``), stable_atoms [S, B] int32, mol_stable [S, B] uint8, hist [S, P, 128]
+    int64 and counts [S, 8] int64."""
+    S, Nl, B, cz, prof = _quality_inputs(pos, v, ligand_ptr, class_z, include, profiles, check)
+    lib = load_library()
+    _ptr(pos, torch.float32, 'pos')                   # a CPU tensor is refused before anything is allocated
+    dev = pos.device
+    P = len(prof)
+    edges = [torch.from_numpy(e).to(dev) for _, _, _, e in prof]            # torch's allocator reuses their memory in stream order: after the kernel
+    parr = (TdPairProfile * max(P, 1))()
+    for p, (z1, z2, cutoff, e) in enumerate(prof):
+        parr[p] = TdPairProfile(z1, z2, cutoff, e.size, 0, edges[p].data_ptr())
+    out = dict(nr_bonds=torch.empty(S, Nl, dtype=torch.int32, device=dev) if return_nr_bonds else None,
+               stable_atoms=torch.empty(S, B, dtype=torch.int32, device=dev), mol_stable=torch.empty(S, B, dtype=torch.uint8, device=dev),
+               hist=torch.empty(S, P, QUALITY_BINS, dtype=torch.int64, device=dev), counts=torch.empty(S, 8, dtype=torch.int64, device=dev))
+    if include is not None and include.dtype == torch.bool:
+        include = include.view(torch.uint8)
+    with _on(dev):
+        _check(lib.td_quality_report(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
+                                     S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _ptr(include, torch.uint8, 'include'),
+                                     ctypes.cast(parr, c_void_p), P, _ptr(out['nr_bonds']), _ptr(out['stable_atoms']),
+                                     _ptr(out['mol_stable']), _ptr(out['hist']), _ptr(out['counts']), _stream(dev)),
+               'td_quality_report')
+    return out
 
 
 def protein_centroids(protein_pos: torch.Tensor, protein_ptr: torch.Tensor) -> torch.Tensor:

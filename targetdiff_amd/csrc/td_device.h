@@ -152,6 +152,16 @@ __device__ __forceinline__ float td_add_rn(float a, float b) {
     return a + b;
 }
 
+// the float64 twins (quality.hip: a distance there is compared against a threshold to the last bit of numpy's float64)
+__device__ __forceinline__ double td_mul_rn64(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ double td_add_rn64(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
 // The x0 a posterior step works with, from one coordinate of the network's output: the output itself (model_mean_type 'C0', 0), or for
 // 'noise' (1; models/molopt_score_model.py:412-416, :663-666), where the output is x_t + eps, x0 = rc[t] x_t - rm1[t] eps.  One function for
 // the posterior kernels (misc.hip) and the clash shift (guidance.hip): both see the same bits.

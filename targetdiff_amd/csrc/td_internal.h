@@ -404,6 +404,28 @@ struct TdClashArgs {
 int td_launch_clash_shift(const TdClashArgs &a, float *shift, hipStream_t s);
 int td_launch_clash_report(const TdClashArgs &a, int32_t *count, float *energy, float *min_dist, hipStream_t s);
 int td_launch_clash_pack(const float4 *x4, const int32_t *prot_node, const float *sigma, int64_t Np, float4 *prot4, hipStream_t s);
+// quality.hip (sample quality): the arguments of one launch over S frames x B molecules.  elem: class -> element
+// index 0..7 (H C N O F P S Cl), filled by the entry point from the caller's atomic numbers; a profile's pe1 / pe2 are element indices
+// too, -1 for "any".  The launcher zeroes hist and counts on the stream before the kernel adds to them.
+constexpr int TD_QUALITY_MAX_CLASSES = 64, TD_QUALITY_MAX_PROFILES = 4, TD_QUALITY_BINS = 128;
+struct TdQualityArgs {
+    const float *pos = nullptr;              // [S,N_l,3]
+    const int64_t *v = nullptr;              // [S,N_l]
+    const int32_t *lptr = nullptr;           // [B+1]
+    const uint8_t *include = nullptr;        // [S,B] or null: every molecule enters the histograms and counts
+    int64_t Nl = 0;
+    int S = 0, B = 0, K = 0, P = 0;
+    int8_t elem[TD_QUALITY_MAX_CLASSES] = {};
+    int pe1[TD_QUALITY_MAX_PROFILES] = {}, pe2[TD_QUALITY_MAX_PROFILES] = {}, n_edges[TD_QUALITY_MAX_PROFILES] = {};
+    double cutoff[TD_QUALITY_MAX_PROFILES] = {};
+    const double *edges[TD_QUALITY_MAX_PROFILES] = {};
+    int32_t *nr_bonds = nullptr;             // [S,N_l] or null
+    int32_t *stable_atoms = nullptr;         // [S,B]
+    uint8_t *mol_stable = nullptr;           // [S,B]
+    unsigned long long *hist = nullptr;      // [S,P,TD_QUALITY_BINS]
+    unsigned long long *counts = nullptr;    // [S,8]
+};
+int td_launch_quality(const TdQualityArgs &a, hipStream_t s);
 // egnn.hip / node.hip
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s);

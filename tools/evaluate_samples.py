@@ -1,0 +1,96 @@
+"""The chemistry-free half of the reference's scripts/evaluate_diffusion.py (:54-87, :150-174) on the GPU:
+
+    python tools/evaluate_samples.py --sample_path DIR [--eval_step -1|all] [--atom_enc_mode add_aromatic] [--eval_num_examples N]
+
+Reads the ``result_{i}.pt`` files a sampling driver wrote (tools/batch_sample.py, or the reference's scripts/sample_diffusion.py),
+sorted as the reference sorts them, and prints under the reference's names: ``mol_stable`` and ``atm_stable``, the pair-distance
+Jensen-Shannon distances ``JSD_CC_2A`` and ``JSD_All_12A`` and ``Atom type JS``.  The pair profiles and the atom types are taken over
+``--include all`` samples (default) or the ``stable`` ones; the reference takes them over reconstructed complete molecules, which
+needs RDKit / OpenBabel and is not done here.  The Jensen-Shannon distances need the reference's empirical distributions: they are
+loaded from ``utils.evaluation`` when the tool runs inside the reference repository (or with it on PYTHONPATH), or from
+``--reference_npz FILE`` with arrays CC_2A, All_12A and atom_type; without them the three lines print None.
+
+Writes ``DIR/eval_results/quality.json``: the numbers above, the raw histograms and element counts, and with ``--eval_step all`` the
+per-frame curve (``curve``: one entry per frame of the trajectory).  With seeded random weights the numbers say nothing about chemistry.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+from glob import glob
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from targetdiff_amd import quality  # noqa: E402
+
+
+def result_files(sample_path, eval_num_examples=None):
+    """scripts/evaluate_diffusion.py:55-58"""
+    files = glob(os.path.join(sample_path, '*result_*.pt'))
+    files = sorted(files, key=lambda x: int(os.path.basename(x)[:-3].split('_')[-1]))
+    return files if eval_num_examples is None else files[:eval_num_examples]
+
+
+def print_dict(d):
+    """scripts/evaluate_diffusion.py:18-23"""
+    for k, v in d.items():
+        print(f'{k}:\t{v:.4f}' if v is not None else f'{k}:\tNone')
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--sample_path', type=str, required=True)
+    ap.add_argument('--eval_step', type=str, default='-1', help="a frame index (default -1: the final poses) or 'all'")
+    ap.add_argument('--eval_num_examples', type=int, default=None)
+    ap.add_argument('--atom_enc_mode', type=str, default='add_aromatic')
+    ap.add_argument('--include', type=str, default='all', choices=['all', 'stable'])
+    ap.add_argument('--reference_npz', type=str, default=None)
+    ap.add_argument('--device', type=str, default='cuda')
+    args = ap.parse_args(argv)
+    eval_step = 'all' if args.eval_step == 'all' else int(args.eval_step)
+
+    reference = None
+    if args.reference_npz is not None:
+        with np.load(args.reference_npz) as z:
+            reference = {k: z[k] for k in ('CC_2A', 'All_12A', 'atom_type')}
+    files = result_files(args.sample_path, args.eval_num_examples)
+    if not files:
+        raise SystemExit(f'no result_*.pt under {args.sample_path}')
+    print(f'Load generated data done! {len(files)} examples in total.')
+    reports = []
+    for name in files:
+        r = torch.load(name, map_location='cpu', weights_only=False)
+        reports.append(quality.sample_quality(r, eval_step, args.include, args.atom_enc_mode, reference, device=args.device))
+    rep = quality.QualityReport.merged(reports)
+    print(f'Evaluate done! {rep.n_samples} samples in total.')
+
+    def frame(s):
+        js = rep.js(s)
+        return dict(mol_stable=float(rep.mol_stable[s]), atm_stable=float(rep.atm_stable[s]), JSD_CC_2A=js['JSD_CC_2A'],
+                    JSD_All_12A=js['JSD_All_12A'], atom_type_js=js['atom_type_js'])
+
+    last = frame(-1)
+    print_dict({k: last[k] for k in ('mol_stable', 'atm_stable')})
+    print_dict({k: last[k] for k in ('JSD_CC_2A', 'JSD_All_12A')})
+    print('Atom type JS: %.4f' % last['atom_type_js'] if last['atom_type_js'] is not None else 'Atom type JS: None')
+    out = dict(num_examples=len(files), num_samples=rep.n_samples, num_atoms=rep.n_atoms, eval_step=eval_step, include=args.include,
+               atom_enc_mode=args.atom_enc_mode, **last,
+               hist={n: rep.hist[-1, p, :len(rep.profiles[p][3]) + 1].tolist() for p, n in enumerate(rep.names)},
+               element_counts=dict(zip(('H', 'C', 'N', 'O', 'F', 'P', 'S', 'Cl'), rep.counts[-1].tolist())))
+    if eval_step == 'all':
+        out['curve'] = [frame(s) for s in range(rep.num_frames)]
+    result_path = os.path.join(args.sample_path, 'eval_results')
+    os.makedirs(result_path, exist_ok=True)
+    with open(os.path.join(result_path, 'quality.json'), 'w') as f:
+        json.dump(out, f, indent=1)
+    print('wrote', os.path.join(result_path, 'quality.json'))
+    return out
+
+
+if __name__ == '__main__':
+    main()

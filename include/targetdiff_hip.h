@@ -320,6 +320,37 @@ int td_quality_report(const float *d_pos, const int64_t *d_v, const int32_t *d_l
                       int32_t P, int32_t *d_nr_bonds, int32_t *d_stable_atoms, uint8_t *d_mol_stable, int64_t *d_hist,
                       int64_t *d_counts, void *stream);
 
+/* ---- bond graph of ligand frames ("Bond graph"): the bonds the rule above implies, kept instead of summed.
+ *      No model handle.  The pack (d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, d_include) is td_quality_report's.
+ *      class_aromatic [K] (HOST bytes, NULL: no class is aromatic) flags the aromatic classes.
+ *      Bond: a pair i < j of one molecule whose order, by exactly the rule of td_quality_report, is > 0; an atom whose class is
+ *      outside [0, K) bonds with nothing.  Category of a bond: its order, except 4 (aromatic) when both atoms' classes are aromatic
+ *      and the order is 1 or 2.  Fragment: a connected component of the bond graph; an atom's label is the smallest molecule-local
+ *      atom index of its component.  A molecule of more than 512 atoms (TD_BOND_MAX_ATOMS), or one whose offsets leave [0, N_l], gets
+ *      n_bonds = n_fragments = largest_fragment = -1, counts 0 bonds in d_bond_ptr and contributes nothing else (a binding refuses it).
+ *      td_bond_graph output: d_n_bonds, d_n_fragments (0 for an empty molecule), d_largest_fragment (atoms of the largest component)
+ *      [S,B] int32; d_fragment [S,N_l] int32 labels (may be NULL); d_bond_hist [S,P,128] int64, zeroed by the call: over the molecules
+ *      whose d_include byte is non-zero (NULL: all), profile p (HOST array, P <= 16) takes the bonds whose unordered elements are
+ *      (z1, z2) (0: any) and whose category is `category` (1 .. 4, 0: any) into bin numpy.searchsorted(edges, d, 'left') of d_edges
+ *      [n_edges] (DEVICE float64, ascending, 1 <= n_edges <= 127; the last bin takes everything beyond the last edge: no cutoff);
+ *      d_bond_ptr [S*B+1] int64 (may be NULL): the exclusive prefix of n_bonds in (frame, molecule) order, summed in a fixed order.
+ *      td_bond_list writes the n_bonds = d_bond_ptr[S*B] bonds (the caller reads that entry: the one host synchronisation of the
+ *      path) in ascending (frame, molecule, i, j) order: d_bond_atoms [n_bonds,2] int32 indices along the pack's atom axis,
+ *      d_bond_order / d_bond_category [n_bonds] uint8 and d_bond_length [n_bonds] float64 (the d of the rule).  Nothing is written
+ *      at or beyond entry n_bonds, whatever d_bond_ptr holds.  All outputs are integers or float64 values formed by one lane: they
+ *      do not depend on the grid or on the order of arrival.  (Additions: TD_ABI_VERSION stays 5.) */
+typedef struct td_bond_profile {
+    int32_t z1, z2, category, n_edges;
+    const double *d_edges;
+} td_bond_profile;
+int td_bond_graph(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                  const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const uint8_t *class_aromatic,
+                  const td_bond_profile *profiles, int32_t P, int32_t *d_n_bonds, int32_t *d_n_fragments, int32_t *d_largest_fragment,
+                  int32_t *d_fragment, int64_t *d_bond_hist, int64_t *d_bond_ptr, void *stream);
+int td_bond_list(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                 const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const int64_t *d_bond_ptr, int64_t n_bonds,
+                 int32_t *d_bond_atoms, uint8_t *d_bond_order, uint8_t *d_bond_category, double *d_bond_length, void *stream);
+
 /* ---- standalone EGNN refine net (replaces: models/egnn.py EGNN / EnBaseLayer as get_refine_net('egnn', config) builds
  *      it, models/molopt_score_model.py:34-42: num_r_gaussian = 1, kNN rebuilt per layer, SiLU, no LayerNorm, hidden 128,
  *      4 edge types, k = 32).  `host_weights`: per layer, in this order and as PyTorch stores them: edge_mlp.net.0.{weight

@@ -42,6 +42,11 @@ class TdPairProfile(ctypes.Structure):
                 ('d_edges', c_void_p)]
 
 
+class TdBondProfile(ctypes.Structure):
+    """td_bond_profile of include/targetdiff_hip.h"""
+    _fields_ = [('z1', c_int32), ('z2', c_int32), ('category', c_int32), ('n_edges', c_int32), ('d_edges', c_void_p)]
+
+
 class TdPropConfig(ctypes.Structure):
     """td_prop_config of include/targetdiff_hip.h"""
     _fields_ = [('hidden_dim', c_int32), ('num_layers', c_int32), ('knn', c_int32), ('num_r_gaussian', c_int32), ('cutoff', c_float),
@@ -80,6 +85,10 @@ SIGNATURES = {
     'td_clash_shift': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_float, c_float, _P, _P]),
     'td_clash_report': (c_int32, [_P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P]),
     'td_quality_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, c_int32, _P, _P, _P, _P, _P, _P]),
+    'td_bond_graph': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, POINTER(ctypes.c_uint8), _P, c_int32, _P, _P, _P, _P,
+                                _P, _P, _P]),
+    'td_bond_list': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), _P, c_int64, _P, _P, _P, _P,
+                               _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_center_pos': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int32, c_int32, _P]),
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
@@ -856,6 +865,97 @@ def quality_report(pos, v, ligand_ptr, class_z, profiles=(), include=None, retur
                                      ctypes.cast(parr, c_void_p), P, _ptr(out['nr_bonds']), _ptr(out['stable_atoms']),
                                      _ptr(out['mol_stable']), _ptr(out['hist']), _ptr(out['counts']), _stream(dev)),
                'td_quality_report')
+    return out
+
+
+BOND_MAX_ATOMS, BOND_MAX_PROFILES, BOND_BINS = 512, 16, 128                 # TD_BOND_* (csrc/td_internal.h)
+
+
+def _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, include, profiles, check=True):
+    """Shapes, the class table, the aromatic flags and the bond profiles of a bond_graph / bond_list call; with ``check`` the offsets,
+    the classes and the molecule sizes are looked at on the host (one synchronisation).  Returns (S, N_l, B, class table as int32
+    numpy, aromatic flags as uint8 numpy or None, [(z1, z2, category, edges as float64 numpy)])."""
+    S, Nl, B, cz, _ = _quality_inputs(pos, v, ligand_ptr, class_z, include, (), check)
+    aro = None
+    if class_aromatic is not None:
+        aro = np.ascontiguousarray(np.asarray(class_aromatic).reshape(-1) != 0, dtype=np.uint8)
+        if aro.size != cz.size:
+            raise ValueError(f'class_aromatic must have one flag per class ({cz.size}; got {aro.size})')
+    if len(profiles) > BOND_MAX_PROFILES:
+        raise ValueError(f'at most {BOND_MAX_PROFILES} bond profiles (got {len(profiles)})')
+    prof = []
+    for z1, z2, category, edges in profiles:
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+        if not 1 <= e.size <= BOND_BINS - 1:
+            raise ValueError(f'a bond profile has 1 .. {BOND_BINS - 1} edges (got {e.size})')
+        if not np.isfinite(e).all() or bool((e[1:] < e[:-1]).any()):
+            raise ValueError('the edges of a bond profile must be finite and ascending')
+        if any(z != 0 and z not in QUALITY_ELEMENTS for z in (int(z1), int(z2))):
+            raise ValueError(f'a bond profile names elements of {QUALITY_ELEMENTS} or 0 for any (got {z1}, {z2})')
+        if int(category) not in (0, 1, 2, 3, 4):
+            raise ValueError(f'the category of a bond profile is 0 (any), 1, 2, 3 or 4 (got {category})')
+        prof.append((int(z1), int(z2), int(category), e))
+    if check and B > 0:
+        sizes = ligand_ptr.cpu().to(torch.int64).diff()
+        if int(sizes.max()) > BOND_MAX_ATOMS:
+            raise ValueError(f'molecule {int(sizes.argmax())} has {int(sizes.max())} atoms: the bond graph takes at most {BOND_MAX_ATOMS}')
+    return S, Nl, B, cz, aro, prof
+
+
+def _aromatic_arg(aro):
+    return None if aro is None else aro.ctypes.data_as(POINTER(ctypes.c_uint8))
+
+
+def bond_graph(pos, v, ligand_ptr, class_z, class_aromatic=None, profiles=(), include=None, return_fragments=False, return_bond_ptr=False,
+               check=True):
+    """Bonds, fragments and bond-length counts of S frames of B molecules (td_bond_graph, include/targetdiff_hip.h); no model handle
+    needed.  The pack as quality_report's; ``class_aromatic`` one flag per class or None; ``profiles`` a sequence of (z1, z2, category,
+    edges).  Returns a dict of device tensors: n_bonds, n_fragments, largest_fragment [S, B] int32, fragment [S, N_l] int32 (None
+    without ``return_fragments``), bond_hist [S, P, 128] int64 and bond_ptr [S * B + 1] int64 (None without ``return_bond_ptr``)."""
+    S, Nl, B, cz, aro, prof = _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, include, profiles, check)
+    lib = load_library()
+    _ptr(pos, torch.float32, 'pos')                   # a CPU tensor is refused before anything is allocated
+    dev = pos.device
+    P = len(prof)
+    edges = [torch.from_numpy(e).to(dev) for _, _, _, e in prof]
+    parr = (TdBondProfile * max(P, 1))()
+    for p, (z1, z2, category, e) in enumerate(prof):
+        parr[p] = TdBondProfile(z1, z2, category, e.size, edges[p].data_ptr())
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    out = dict(n_bonds=i32(S, B), n_fragments=i32(S, B), largest_fragment=i32(S, B), fragment=i32(S, Nl) if return_fragments else None,
+               bond_hist=torch.empty(S, P, BOND_BINS, dtype=torch.int64, device=dev),
+               bond_ptr=torch.empty(S * B + 1, dtype=torch.int64, device=dev) if return_bond_ptr else None)
+    if include is not None and include.dtype == torch.bool:
+        include = include.view(torch.uint8)
+    with _on(dev):
+        _check(lib.td_bond_graph(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
+                                 S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _ptr(include, torch.uint8, 'include'),
+                                 _aromatic_arg(aro), ctypes.cast(parr, c_void_p), P, _ptr(out['n_bonds']), _ptr(out['n_fragments']),
+                                 _ptr(out['largest_fragment']), _ptr(out['fragment']), _ptr(out['bond_hist']), _ptr(out['bond_ptr']),
+                                 _stream(dev)), 'td_bond_graph')
+    return out
+
+
+def bond_list(pos, v, ligand_ptr, class_z, class_aromatic, bond_ptr, check=True):
+    """The bonds of a pack in ascending (frame, molecule, i, j) order (td_bond_list); ``bond_ptr`` [S * B + 1] int64 from bond_graph on
+    the same pack.  Its last entry is read on the host to size the outputs: the one synchronisation of the path.  Returns a dict of
+    device tensors: bond_atoms [nb, 2] int32 (indices along the pack's atom axis), bond_order and bond_category [nb] uint8 and
+    bond_length [nb] float64."""
+    S, Nl, B, cz, aro, _ = _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, None, (), check)
+    if bond_ptr.dim() != 1 or bond_ptr.numel() != S * B + 1 or bond_ptr.dtype != torch.int64:
+        raise ValueError(f'bond_ptr must be [{S * B + 1}] int64, as bond_graph returns it')
+    lib = load_library()
+    _ptr(pos, torch.float32, 'pos')
+    _ptr(bond_ptr, torch.int64, 'bond_ptr')
+    dev = pos.device
+    nb = int(bond_ptr[-1])
+    out = dict(bond_atoms=torch.empty(nb, 2, dtype=torch.int32, device=dev), bond_order=torch.empty(nb, dtype=torch.uint8, device=dev),
+               bond_category=torch.empty(nb, dtype=torch.uint8, device=dev), bond_length=torch.empty(nb, dtype=torch.float64, device=dev))
+    with _on(dev):
+        _check(lib.td_bond_list(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
+                                S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _aromatic_arg(aro), _ptr(bond_ptr), nb,
+                                _ptr(out['bond_atoms']), _ptr(out['bond_order']), _ptr(out['bond_category']), _ptr(out['bond_length']),
+                                _stream(dev)), 'td_bond_list')
     return out
 
 

@@ -1,0 +1,93 @@
+// C ABI of libtargetdiff_hip.so: the bond graph of ligand frames (td_bond_graph, td_bond_list).  See include/targetdiff_hip.h for the
+// contract.
+#include "td_device.h"
+#include "td_internal.h"
+
+namespace {
+// the checks and the fields both entry points share: sizes, the class table and the aromatic flags
+int bond_pack(const char *who, TdBondArgs &a, const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l,
+              int64_t B, const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic) {
+    if (S < 0 || B < 0 || N_l < 0 || N_l > 0x7fffffff || S > 0x7fffffff || B > 0x7fffffff || S * B > 0x7fffffff) {
+        td_set_error("%s: bad argument (S = %lld, B = %lld, N_l = %lld; S * B and N_l must fit 31 bits)", who, (long long)S, (long long)B,
+                     (long long)N_l);
+        return TD_EINVAL;
+    }
+    if (K < 1 || K > TD_QUALITY_MAX_CLASSES || !class_atomic_number) {
+        td_set_error("%s: the class table must have 1 .. %d entries (got %d)", who, TD_QUALITY_MAX_CLASSES, (int)K);
+        return TD_EINVAL;
+    }
+    for (int c = 0; c < K; ++c) {
+        const int e = td_element_index(class_atomic_number[c]);
+        if (e < 0) {
+            td_set_error("%s: class %d has atomic number %d, outside the bond-length table (H C N O F P S Cl)", who, c,
+                         (int)class_atomic_number[c]);
+            return TD_EINVAL;
+        }
+        a.elem[c] = (int8_t)e;
+        if (class_aromatic && class_aromatic[c]) a.aromatic |= 1ull << c;
+    }
+    if (S > 0 && B > 0 && (!d_ligand_ptr || (N_l > 0 && (!d_pos || !d_v)))) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    a.pos = d_pos; a.v = d_v; a.lptr = d_ligand_ptr; a.Nl = N_l;
+    a.S = (int)S; a.B = (int)B; a.K = K;
+    return TD_OK;
+}
+}  // namespace
+
+extern "C" int td_bond_graph(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                             const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const uint8_t *class_aromatic,
+                             const td_bond_profile *profiles, int32_t P, int32_t *d_n_bonds, int32_t *d_n_fragments,
+                             int32_t *d_largest_fragment, int32_t *d_fragment, int64_t *d_bond_hist, int64_t *d_bond_ptr, void *stream) {
+    const char *who = "td_bond_graph";
+    TdBondArgs a;
+    if (P < 0 || P > TD_BOND_MAX_PROFILES || (P > 0 && !profiles)) {
+        td_set_error("%s: 0 .. %d bond profiles (got %d)", who, TD_BOND_MAX_PROFILES, (int)P);
+        return TD_EINVAL;
+    }
+    for (int p = 0; p < P; ++p) {
+        const td_bond_profile &pf = profiles[p];
+        const int e1 = pf.z1 == 0 ? -1 : td_element_index(pf.z1), e2 = pf.z2 == 0 ? -1 : td_element_index(pf.z2);
+        if ((pf.z1 != 0 && e1 < 0) || (pf.z2 != 0 && e2 < 0)) {
+            td_set_error("%s: profile %d names an atomic number outside the table (%d, %d; 0 = any)", who, p, (int)pf.z1, (int)pf.z2);
+            return TD_EINVAL;
+        }
+        if (pf.category < 0 || pf.category > 4) {
+            td_set_error("%s: profile %d: the category must be 0 (any), 1, 2, 3 or 4 (got %d)", who, p, (int)pf.category);
+            return TD_EINVAL;
+        }
+        if (pf.n_edges < 1 || pf.n_edges > TD_BOND_BINS - 1 || !pf.d_edges) {
+            td_set_error("%s: profile %d needs 1 .. %d edges (got %d)", who, p, TD_BOND_BINS - 1, (int)pf.n_edges);
+            return TD_EINVAL;
+        }
+        a.pe1[p] = (int8_t)e1; a.pe2[p] = (int8_t)e2; a.pcat[p] = (int8_t)pf.category; a.n_edges[p] = (int16_t)pf.n_edges;
+        a.edges[p] = pf.d_edges;
+    }
+    if (const int rc = bond_pack(who, a, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic)) return rc;
+    if ((S > 0 && P > 0 && !d_bond_hist) || (S > 0 && B > 0 && (!d_n_bonds || !d_n_fragments || !d_largest_fragment))) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    a.include = d_include; a.P = P;
+    a.n_bonds = d_n_bonds; a.n_fragments = d_n_fragments; a.largest = d_largest_fragment; a.fragment = d_fragment;
+    a.hist = reinterpret_cast<unsigned long long *>(d_bond_hist); a.bond_ptr = d_bond_ptr;
+    return td_launch_bond_graph(a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int td_bond_list(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                            const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const int64_t *d_bond_ptr,
+                            int64_t n_bonds, int32_t *d_bond_atoms, uint8_t *d_bond_order, uint8_t *d_bond_category,
+                            double *d_bond_length, void *stream) {
+    const char *who = "td_bond_list";
+    TdBondArgs a;
+    if (n_bonds < 0) { td_set_error("%s: bad argument (n_bonds = %lld)", who, (long long)n_bonds); return TD_EINVAL; }
+    if (const int rc = bond_pack(who, a, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic)) return rc;
+    if (S > 0 && B > 0 && n_bonds > 0 && (!d_bond_ptr || !d_bond_atoms || !d_bond_order || !d_bond_category || !d_bond_length)) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    a.bond_ptr = const_cast<int64_t *>(d_bond_ptr); a.capacity = n_bonds;
+    a.bond_atoms = d_bond_atoms; a.bond_order = d_bond_order; a.bond_category = d_bond_category; a.bond_length = d_bond_length;
+    return td_launch_bond_list(a, static_cast<hipStream_t>(stream));
+}

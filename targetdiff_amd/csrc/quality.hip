@@ -9,6 +9,7 @@
 // order: ((dx dx + dy dy) + dz dz), IEEE sqrt, 100 d), so an order flips exactly where the reference's flips.  Histograms and counts
 // are 64-bit integer LDS atomics inside the workgroup and one integer global atomic per non-empty bin at its end: every output is
 // independent of the grid and of the order of arrival, and there is no floating-point atomic anywhere.
+#include "td_bond_rule.h"
 #include "td_device.h"
 #include "td_internal.h"
 
@@ -16,19 +17,7 @@ constexpr int QL_TILE = 256;        // atoms per LDS tile (4 KiB) = lanes per wo
 constexpr int QL_THREADS = QL_TILE;
 constexpr int QL_BINS = TD_QUALITY_BINS, QL_MAXP = TD_QUALITY_MAX_PROFILES;
 
-// Single, double and triple bond lengths in picometres (wiredchemist.com bond energies and lengths, the table the reference cites), as
-// flat 8 x 8 matrices over H C N O F P S Cl; -1: no such bond.  The margins and the bonds an element may hold follow below.
-__constant__ const int16_t QL_BOND[3][64] = {
-    {74,  109, 101, 96,  92,  144, 134, 127,     109, 154, 147, 143, 135, 184, 182, 177,     101, 147, 145, 140, 136, 177, 168, 175,
-     96,  143, 140, 148, 142, 163, 151, 164,     92,  135, 136, 142, 142, 156, 158, 166,     144, 184, 177, 163, 156, 221, 210, 203,
-     134, 182, 168, 151, 158, 210, 204, 207,     127, 177, 175, 164, 166, 203, 207, 199},
-    {-1, -1,  -1,  -1,  -1, -1,  -1,  -1,        -1, 134, 129, 120, -1, -1,  160, -1,        -1, 129, 125, 121, -1, -1,  -1,  -1,
-     -1, 120, 121, 121, -1, 150, -1,  -1,        -1, -1,  -1,  -1,  -1, -1,  -1,  -1,        -1, -1,  -1,  150, -1, -1,  186, -1,
-     -1, 160, -1,  -1,  -1, 186, -1,  -1,        -1, -1,  -1,  -1,  -1, -1,  -1,  -1},
-    {-1, -1,  -1,  -1,  -1, -1, -1, -1,          -1, 120, 116, 113, -1, -1, -1, -1,          -1, 116, 110, -1,  -1, -1, -1, -1,
-     -1, 113, -1,  -1,  -1, -1, -1, -1,          -1, -1,  -1,  -1,  -1, -1, -1, -1,          -1, -1,  -1,  -1,  -1, -1, -1, -1,
-     -1, -1,  -1,  -1,  -1, -1, -1, -1,          -1, -1,  -1,  -1,  -1, -1, -1, -1}};
-__constant__ const int16_t QL_MARGIN[3] = {10, 5, 3};
+// the bonds an element may hold (H C N O F P S Cl); the bond-length tables and the order of a pair: td_bond_rule.h
 __constant__ const int8_t QL_ALLOWED[8] = {1, 4, 3, 2, 1, 5, 4, 1};
 
 __global__ __launch_bounds__(QL_THREADS) void quality_kernel(TdQualityArgs a) {
@@ -44,7 +33,7 @@ __global__ __launch_bounds__(QL_THREADS) void quality_kernel(TdQualityArgs a) {
     const int l0 = a.lptr[g], n = a.lptr[g + 1] - l0;
     const bool inc = !a.include || a.include[(size_t)s * a.B + g] != 0;          // workgroup-uniform
     const int P = inc ? a.P : 0;
-    if (tid < 3 * 64) s_thr[tid >> 6][tid & 63] = (double)(QL_BOND[tid >> 6][tid & 63] + QL_MARGIN[tid >> 6]);
+    td_bond_thresholds(s_thr, tid, QL_THREADS);
     if (tid < TD_QUALITY_MAX_CLASSES) s_elem[tid] = tid < a.K ? a.elem[tid] : -1;
     if (tid < 8) s_cnt[tid] = 0ull;
     if (tid == 0) s_stable = 0;
@@ -88,11 +77,8 @@ __global__ __launch_bounds__(QL_THREADS) void quality_kernel(TdQualityArgs a) {
                     const float4 q = s_at[jj];                // every lane reads the same address: an LDS broadcast
                     const int ej = __float_as_int(q.w);
                     if (j == i || ej < 0) continue;
-                    const double dx = xi - (double)q.x, dy = yi - (double)q.y, dz = zi - (double)q.z;
-                    const double d = sqrt(td_add_rn64(td_add_rn64(td_mul_rn64(dx, dx), td_mul_rn64(dy, dy)), td_mul_rn64(dz, dz)));
-                    const double D = td_mul_rn64(100.0, d);
-                    const int pr = ei * 8 + ej;
-                    if (D < s_thr[0][pr]) nb += D < s_thr[1][pr] ? (D < s_thr[2][pr] ? 3 : 2) : 1;
+                    double d;
+                    nb += td_bond_order(xi, yi, zi, q.x, q.y, q.z, ei * 8 + ej, s_thr, d);
                     if (j > i) {
 #pragma unroll
                         for (int p = 0; p < QL_MAXP; ++p) {

@@ -2,15 +2,13 @@
 #include "td_device.h"
 #include "td_internal.h"
 
-namespace {
 // element index 0..7 (H C N O F P S Cl) of an atomic number, -1 for any other
-int element_index(int z) {
+int td_element_index(int z) {
     static const int Z[8] = {1, 6, 7, 8, 9, 15, 16, 17};
     for (int e = 0; e < 8; ++e)
         if (Z[e] == z) return e;
     return -1;
 }
-}  // namespace
 
 extern "C" int td_quality_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
                                  const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include,
@@ -32,7 +30,7 @@ extern "C" int td_quality_report(const float *d_pos, const int64_t *d_v, const i
     }
     TdQualityArgs a;
     for (int c = 0; c < K; ++c) {
-        const int e = element_index(class_atomic_number[c]);
+        const int e = td_element_index(class_atomic_number[c]);
         if (e < 0) {
             td_set_error("%s: class %d has atomic number %d, outside the bond-length table (H C N O F P S Cl)", who, c,
                          (int)class_atomic_number[c]);
@@ -42,7 +40,7 @@ extern "C" int td_quality_report(const float *d_pos, const int64_t *d_v, const i
     }
     for (int p = 0; p < P; ++p) {
         const td_pair_profile &pf = profiles[p];
-        const int e1 = pf.z1 == 0 ? -1 : element_index(pf.z1), e2 = pf.z2 == 0 ? -1 : element_index(pf.z2);
+        const int e1 = pf.z1 == 0 ? -1 : td_element_index(pf.z1), e2 = pf.z2 == 0 ? -1 : td_element_index(pf.z2);
         if ((pf.z1 != 0 && e1 < 0) || (pf.z2 != 0 && e2 < 0)) {
             td_set_error("%s: profile %d names an atomic number outside the table (%d, %d; 0 = any)", who, p, (int)pf.z1, (int)pf.z2);
             return TD_EINVAL;

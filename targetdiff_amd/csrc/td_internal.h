@@ -426,6 +426,35 @@ struct TdQualityArgs {
     unsigned long long *counts = nullptr;    // [S,8]
 };
 int td_launch_quality(const TdQualityArgs &a, hipStream_t s);
+int td_element_index(int z);                 // quality_api.cpp: 0..7 (H C N O F P S Cl) of an atomic number, -1 for any other
+// bonds.hip (bond graph): the arguments of td_bond_graph / td_bond_list over S frames x B molecules.  elem and a
+// profile's pe1 / pe2 as in TdQualityArgs; aromatic: bit c set when class c is aromatic; pcat: 0 = any category.  The launcher zeroes
+// hist on the stream before the kernels add to it.  Molecules of up to TD_BOND_SMALL_ATOMS atoms run in 128-lane workgroups, larger
+// ones (up to TD_BOND_MAX_ATOMS) in 512-lane workgroups: both grids cover every molecule and each workgroup takes only its own kind.
+constexpr int TD_BOND_MAX_ATOMS = 512, TD_BOND_SMALL_ATOMS = 128, TD_BOND_MAX_PROFILES = 16, TD_BOND_BINS = 128;
+struct TdBondArgs {
+    const float *pos = nullptr;              // [S,N_l,3]
+    const int64_t *v = nullptr;              // [S,N_l]
+    const int32_t *lptr = nullptr;           // [B+1]
+    const uint8_t *include = nullptr;        // [S,B] or null: every molecule enters the histograms
+    int64_t Nl = 0;
+    int S = 0, B = 0, K = 0, P = 0;
+    unsigned long long aromatic = 0ull;
+    int8_t elem[TD_QUALITY_MAX_CLASSES] = {};
+    int8_t pe1[TD_BOND_MAX_PROFILES] = {}, pe2[TD_BOND_MAX_PROFILES] = {}, pcat[TD_BOND_MAX_PROFILES] = {};
+    int16_t n_edges[TD_BOND_MAX_PROFILES] = {};
+    const double *edges[TD_BOND_MAX_PROFILES] = {};
+    int32_t *n_bonds = nullptr, *n_fragments = nullptr, *largest = nullptr;      // [S,B]
+    int32_t *fragment = nullptr;             // [S,N_l] or null
+    unsigned long long *hist = nullptr;      // [S,P,TD_BOND_BINS]
+    int64_t *bond_ptr = nullptr;             // [S*B+1] or null (td_bond_graph: written; td_bond_list: read)
+    int64_t capacity = 0;                    // td_bond_list: entries the four outputs below hold
+    int32_t *bond_atoms = nullptr;           // [capacity,2]
+    uint8_t *bond_order = nullptr, *bond_category = nullptr;
+    double *bond_length = nullptr;
+};
+int td_launch_bond_graph(const TdBondArgs &a, hipStream_t s);
+int td_launch_bond_list(const TdBondArgs &a, hipStream_t s);
 // egnn.hip / node.hip
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s);

@@ -1,0 +1,83 @@
+"""Molecules on disk without a chemistry toolkit: a plain MDL V2000 SD-file writer for the bond graph of ``quality.bond_graph``.
+
+    g = quality.bond_graph(pos, v, ligand_ptr=ptr, return_fragments=True, return_bonds=True)
+    mols = molfile.molecules_from_graph(g, pos, v, frame=-1, largest_fragment=True)
+    molfile.write_sdf('samples.sdf', mols)
+
+A molecule is a dict: ``name``, ``symbols`` [n] element symbols, ``pos`` [n, 3], ``bonds`` [(i, j, type)] with 0-based atoms and the
+SD-file bond type 1 / 2 / 3 / 4 (aromatic) -- the bond's category ("Bond graph": a convention for export, not
+chemistry; no hydrogens, no valence repair, no kekulisation) -- and optional ``properties`` written as data items.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import quality
+
+ELEMENT_SYMBOLS = {1: 'H', 6: 'C', 7: 'N', 8: 'O', 9: 'F', 15: 'P', 16: 'S', 17: 'Cl'}
+V2000_MAX = 999                                        # the counts line holds three digits
+
+
+def _record(mol):
+    symbols, pos, bonds = list(mol['symbols']), np.asarray(mol['pos'], dtype=np.float64).reshape(-1, 3), list(mol.get('bonds', ()))
+    if len(symbols) != len(pos):
+        raise ValueError(f'{len(symbols)} symbols for {len(pos)} positions')
+    if len(symbols) > V2000_MAX or len(bonds) > V2000_MAX:
+        raise ValueError(f'a V2000 record holds at most {V2000_MAX} atoms and bonds (got {len(symbols)}, {len(bonds)})')
+    lines = [str(mol.get('name', '')), '  targetdiff_amd          3D', '',
+             f'{len(symbols):3d}{len(bonds):3d}  0  0  0  0  0  0  0  0999 V2000']
+    for sym, (x, y, z) in zip(symbols, pos):
+        lines.append(f'{x:10.4f}{y:10.4f}{z:10.4f} {sym:<3s} 0  0  0  0  0  0  0  0  0  0  0  0')
+    for i, j, t in bonds:
+        if not (0 <= int(i) < len(symbols) and 0 <= int(j) < len(symbols)) or int(t) not in (1, 2, 3, 4):
+            raise ValueError(f'bond ({i}, {j}, {t}): atoms are 0-based indices of the molecule, the type is 1, 2, 3 or 4')
+        lines.append(f'{int(i) + 1:3d}{int(j) + 1:3d}{int(t):3d}  0  0  0  0')
+    lines.append('M  END')
+    for key, val in (mol.get('properties') or {}).items():
+        lines += [f'>  <{key}>', str(val), '']
+    lines.append('$$$$')
+    return '\n'.join(lines) + '\n'
+
+
+def write_sdf(path, molecules):
+    """Write ``molecules`` (dicts as the module describes) to ``path`` as V2000 records; returns their number."""
+    records = [_record(m) for m in molecules]
+    with open(path, 'w') as f:
+        f.write(''.join(records))
+    return len(records)
+
+
+def molecules_from_graph(graph, pos, v, atom_enc_mode='add_aromatic', frame=-1, only_complete=False, largest_fragment=False, names=None):
+    """The molecules of one frame of a ``quality.BondGraph`` made with ``return_fragments=True, return_bonds=True`` on the pack
+    (``pos`` [S, N_l, 3] or [N_l, 3], ``v`` alike).  ``only_complete`` drops the molecules of more than one fragment;
+    ``largest_fragment`` keeps, of every molecule, the atoms and bonds of its largest fragment (of equal ones the one with the
+    smallest label) -- chosen here on the host from ``graph.fragment``."""
+    if graph.fragment is None or graph.bond_atoms is None:
+        raise ValueError('the graph needs return_fragments=True and return_bonds=True')
+    to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    pos, v = to_np(pos), to_np(v)
+    if pos.ndim == 2:
+        pos, v = pos[None], v[None]
+    S, B = graph.n_bonds.shape
+    frame = frame % S
+    ptr, bptr = to_np(graph.ligand_ptr), to_np(graph.bond_ptr)
+    frag, nfrag = to_np(graph.fragment)[frame], to_np(graph.n_fragments)[frame]
+    atoms, cats = to_np(graph.bond_atoms), to_np(graph.bond_category)
+    cz = np.asarray(quality.class_atomic_numbers(atom_enc_mode))
+    out = []
+    for g in range(B):
+        if only_complete and nfrag[g] != 1:
+            continue
+        a, b = int(ptr[g]), int(ptr[g + 1])
+        k0, k1 = int(bptr[frame * B + g]), int(bptr[frame * B + g + 1])
+        keep = np.ones(b - a, bool)
+        if largest_fragment and b > a:
+            sizes = np.bincount(frag[a:b], minlength=b - a)
+            keep = frag[a:b] == int(np.argmax(sizes))                 # argmax: the first of equal sizes = the smallest label
+        new = np.cumsum(keep) - 1
+        bonds = [(int(new[i - a]), int(new[j - a]), int(c)) for (i, j), c in zip(atoms[k0:k1], cats[k0:k1]) if keep[i - a] and keep[j - a]]
+        out.append(dict(name=names[g] if names is not None else f'sample_{g}', symbols=[ELEMENT_SYMBOLS[int(z)] for z in cz[v[frame, a:b][keep]]],
+                        pos=pos[frame, a:b][keep], bonds=bonds,
+                        properties=dict(n_fragments=int(nfrag[g]), n_atoms=int(keep.sum()), n_bonds=len(bonds))))
+    return out

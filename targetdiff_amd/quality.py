@@ -16,8 +16,15 @@ The kernel returns integers (bond counts, stable atoms, histogram counts, atoms 
 distributions and the Jensen-Shannon distances are float64 numpy on the host, formed in the reference's order.  The empirical
 distributions the distances are taken against are data inside the reference's Python files and are not part of this package:
 ``reference_distributions()`` loads them when the reference is importable, a caller may pass arrays, and without either a report
-carries the histograms and no distance.  Reconstruction, the bond-length profiles that need bonds, QED / SA and docking need a
-chemistry toolkit and are not here.
+carries the histograms and no distance.
+
+The bonds the table implies are kept too (``td_bond_graph`` / ``td_bond_list``, csrc/bonds.hip; DESIGN.md section 3, "Bond graph"):
+
+    g = quality.bond_graph(pos, v, batch_ligand, return_fragments=True, return_bonds=True)    # bonds, fragments, rings per molecule
+    con = quality.sample_connectivity(result, eval_step='all')    # complete fraction, fragments and bond-length profiles per frame
+    rep = quality.sample_quality(result, include='complete')      # the reference's "success_*" restriction to one-piece molecules
+
+OpenBabel's reconstruction, valence repair, QED / SA and docking need a chemistry toolkit and are not here.
 """
 from __future__ import annotations
 
@@ -30,7 +37,11 @@ ELEMENTS = capi.QUALITY_ELEMENTS                      # H C N O F P S Cl: the co
 # atomic number per class index (utils/transforms.py MAP_INDEX_TO_ATOM_TYPE_ONLY / _AROMATIC; 13 = this project's NUM_LIGAND_CLASSES)
 _CLASS_Z = {'basic': (1, 6, 7, 8, 9, 15, 16, 17),
             'add_aromatic': (1, 6, 6, 7, 7, 8, 8, 9, 15, 15, 16, 16, 17)}
+# aromatic classes (utils/transforms.py is_aromatic_from_index: the second of each (element, aromatic) pair of 'add_aromatic')
+_CLASS_AROMATIC = {'basic': (False,) * 8, 'add_aromatic': tuple(c in (2, 4, 6, 9, 11) for c in range(13))}
 PROFILE_NAMES = ('CC_2A', 'All_12A')
+# eval_bond_length_config.BOND_TYPES, (z1 <= z2, category): C-C, C-N single / double / aromatic, C-O single / double
+BOND_TYPES = ((6, 6, 1), (6, 6, 2), (6, 6, 4), (6, 7, 1), (6, 7, 2), (6, 7, 4), (6, 8, 1), (6, 8, 2))
 ATOM_TYPE_KEYS = (6, 7, 8, 9, 15, 16, 17)             # eval_atom_type.ATOM_TYPE_DISTRIBUTION's keys, in its order (no hydrogen)
 
 
@@ -45,6 +56,28 @@ def class_atomic_numbers(mode='add_aromatic'):
     if bad or not z:
         raise ValueError(f'atomic numbers {bad} are outside the bond-length table {ELEMENTS}')
     return z
+
+
+def class_aromatic(mode='add_aromatic'):
+    """One flag per ligand class: is it aromatic (utils/transforms.py ``is_aromatic_from_index``)?  ``'add_aromatic'``: classes 2, 4,
+    6, 9 and 11; ``'basic'`` and an explicit sequence of atomic numbers: none."""
+    if isinstance(mode, str):
+        if mode not in _CLASS_AROMATIC:
+            raise ValueError(f"atom_enc_mode {mode!r}: 'basic', 'add_aromatic' or an explicit sequence of atomic numbers")
+        return _CLASS_AROMATIC[mode]
+    return (False,) * len(class_atomic_numbers(mode))
+
+
+def default_bond_profiles():
+    """The reference's eight bond types as (z1, z2, category, edges), each over eval_bond_length_config.DISTANCE_BINS (formed here
+    the way the reference forms them); there is no cutoff: the last bin takes every longer bond."""
+    edges = np.arange(1.1, 1.7, 0.005)[:-1]
+    return tuple((z1, z2, c, edges) for z1, z2, c in BOND_TYPES)
+
+
+def bond_type_name(bond_type):
+    """'6-6|4' for (6, 6, 4): eval_bond_length._bond_type_str"""
+    return f'{bond_type[0]}-{bond_type[1]}|{bond_type[2]}'
 
 
 def default_profiles():
@@ -77,6 +110,16 @@ def reference_distributions():
     out = {k: np.asarray(cfg.PAIR_EMPIRICAL_DISTRIBUTIONS[k], dtype=np.float64) for k in PROFILE_NAMES}
     out['atom_type'] = np.asarray([eval_atom_type.ATOM_TYPE_DISTRIBUTION[z] for z in ATOM_TYPE_KEYS], dtype=np.float64)
     return out
+
+
+def reference_bond_distributions():
+    """{(z1, z2, category): [len(DISTANCE_BINS) + 1]} from the reference's eval_bond_length_config.EMPIRICAL_DISTRIBUTIONS when it is
+    importable, else None.  The arrays are the reference's data; this package holds no copy."""
+    try:
+        from utils.evaluation import eval_bond_length_config as cfg
+    except Exception:
+        return None
+    return {tuple(int(x) for x in k): np.asarray(d, dtype=np.float64) for k, d in cfg.EMPIRICAL_DISTRIBUTIONS.items()}
 
 
 def _fp32_positions(pos, device):
@@ -214,18 +257,9 @@ def _trajectories(result):
     return result[2], result[3]
 
 
-def sample_quality(result, eval_step=-1, include='all', atom_enc_mode='add_aromatic', reference=None, profiles=None, device='cuda'):
-    """Quality of the samples of one pocket: ``result`` is the driver's 7-tuple (``sample_diffusion_ligand``) or a loaded
-    ``result_{i}.pt`` dictionary.  ``eval_step``: a frame index as evaluate_diffusion.py's ``--eval_step`` (default -1, the final
-    poses) or ``'all'`` for every frame of the trajectory (one row each: the curve along the chain).  The chosen frames of all samples
-    go to the GPU as one pack -- samples along the molecule axis (they are of ragged size), frames along the frame axis -- and one launch.
-
-    ``include``: which molecules enter the pair profiles and the element counts: ``'all'`` (default), ``'stable'`` (the molecules
-    that are stable in that frame; stability runs first and its flags are the mask, two launches) or a bool array [frames, samples].
-    The reference takes these two from reconstructed complete molecules only (evaluate_diffusion.py:136-137, "success_pair_dist"),
-    which needs a chemistry toolkit and cannot be had here: with 'all' the numbers are those the reference would print if every
-    sample reconstructed.  ``reference``: the empirical distributions ({'CC_2A', 'All_12A', 'atom_type'} arrays); default
-    ``reference_distributions()``; without them the report has no Jensen-Shannon value.  Returns a ``QualityReport``."""
+def _pack_result(result, eval_step, device):
+    """The chosen frames of all samples of a result as one pack: (pos [S, N_l, 3], v [S, N_l], ligand_ptr [B + 1] on ``device``,
+    the sizes, S) -- samples along the molecule axis, frames along the frame axis."""
     pos_traj, v_traj = _trajectories(result)
     if len(pos_traj) != len(v_traj):
         raise ValueError('position and type trajectories of different length')
@@ -245,11 +279,28 @@ def sample_quality(result, eval_step=-1, include='all', atom_enc_mode='add_aroma
     pos = np.concatenate(pos, axis=1) if pos else np.zeros((0, 0, 3), np.float32)
     v = np.concatenate(v, axis=1) if v else np.zeros((0, 0), np.int64)
     pos, v, ptr = _pack(pos, v, None, ptr, device)
+    return pos, v, ptr, sizes, S
+
+
+def sample_quality(result, eval_step=-1, include='all', atom_enc_mode='add_aromatic', reference=None, profiles=None, device='cuda'):
+    """Quality of the samples of one pocket: ``result`` is the driver's 7-tuple (``sample_diffusion_ligand``) or a loaded
+    ``result_{i}.pt`` dictionary.  ``eval_step``: a frame index as evaluate_diffusion.py's ``--eval_step`` (default -1, the final
+    poses) or ``'all'`` for every frame of the trajectory (one row each: the curve along the chain).  The chosen frames of all samples
+    go to the GPU as one pack -- samples along the molecule axis (they are of ragged size), frames along the frame axis -- and one launch.
+
+    ``include``: which molecules enter the pair profiles and the element counts: ``'all'`` (default), ``'stable'`` (the molecules
+    that are stable in that frame; stability runs first and its flags are the mask, two launches), ``'complete'`` (the molecules
+    whose bond graph is one fragment in that frame; the bond graph runs first) or a bool array [frames, samples].
+    The reference takes these two from reconstructed complete molecules only (evaluate_diffusion.py:136-137, "success_pair_dist"):
+    'complete' is that restriction with this project's bond graph in the place of OpenBabel's reconstruction; with 'all' the
+    numbers are those the reference would print if every sample reconstructed.  ``reference``: the empirical distributions ({'CC_2A', 'All_12A', 'atom_type'} arrays); default
+    ``reference_distributions()``; without them the report has no Jensen-Shannon value.  Returns a ``QualityReport``."""
+    pos, v, ptr, sizes, S = _pack_result(result, eval_step, device)
     cz = class_atomic_numbers(atom_enc_mode)
     prof = default_profiles() if profiles is None else tuple(profiles)
     if isinstance(include, str):
-        if include not in ('all', 'stable'):
-            raise ValueError("include is 'all', 'stable' or a mask [frames, samples]")
+        if include not in ('all', 'stable', 'complete'):
+            raise ValueError("include is 'all', 'stable', 'complete' or a mask [frames, samples]")
         mask = None
     else:
         mask = torch.as_tensor(np.asarray(include)).to(device=pos.device, dtype=torch.bool).reshape(S, len(sizes)).contiguous()
@@ -257,9 +308,142 @@ def sample_quality(result, eval_step=-1, include='all', atom_enc_mode='add_aroma
         first = capi.quality_report(pos, v, ptr, cz, (), None, False)
         r = capi.quality_report(pos, v, ptr, cz, prof, first['mol_stable'].bool(), False, check=False)
         r['mol_stable'], r['stable_atoms'] = first['mol_stable'], first['stable_atoms']
+    elif isinstance(include, str) and include == 'complete':
+        first = capi.bond_graph(pos, v, ptr, cz, class_aromatic(atom_enc_mode))
+        r = capi.quality_report(pos, v, ptr, cz, prof, first['n_fragments'] == 1, False, check=False)
     else:
         r = capi.quality_report(pos, v, ptr, cz, prof, mask, False)
     if reference is None:
         reference = reference_distributions()
     return QualityReport(r['mol_stable'].sum(1).cpu().numpy(), r['stable_atoms'].sum(1).cpu().numpy(), len(sizes), sum(sizes),
                          r['hist'].cpu().numpy(), r['counts'].cpu().numpy(), prof, reference)
+
+
+class BondGraph:
+    """The bond graph of S frames of B molecules (``bond_graph``).  Device tensors, frame axis first: ``n_bonds``, ``n_fragments``,
+    ``largest_fragment``, ``rings`` [S, B] int32 (rings = n_bonds - n_atoms + n_fragments, the cyclomatic number), ``complete``
+    [S, B] bool (one fragment), ``bond_hist`` [S, P, 128] int64 over the included molecules, ``ligand_ptr`` [B + 1]; optional:
+    ``fragment`` [S, N_l] int32 (per atom, the smallest molecule-local index of its component) and the bond list in ascending
+    (frame, molecule, i, j) order: ``bond_ptr`` [S * B + 1] int64, ``bond_atoms`` [nb, 2] int32 (indices along the atom axis),
+    ``bond_order`` / ``bond_category`` [nb] uint8, ``bond_length`` [nb] float64."""
+
+    def __init__(self, r, ligand_ptr, profiles, bonds=None):
+        self.n_bonds, self.n_fragments, self.largest_fragment = r['n_bonds'], r['n_fragments'], r['largest_fragment']
+        self.bond_hist, self.fragment, self.bond_ptr = r['bond_hist'], r['fragment'], r['bond_ptr']
+        self.ligand_ptr, self.profiles = ligand_ptr, tuple(profiles)
+        self.n_atoms = ligand_ptr[1:] - ligand_ptr[:-1]
+        self.complete = self.n_fragments == 1
+        self.rings = self.n_bonds - self.n_atoms[None] + self.n_fragments
+        bonds = bonds or {}
+        self.bond_atoms, self.bond_order = bonds.get('bond_atoms'), bonds.get('bond_order')
+        self.bond_category, self.bond_length = bonds.get('bond_category'), bonds.get('bond_length')
+
+    def molecule_bonds(self, frame, molecule):
+        """(atoms [k, 2] molecule-local, order [k], category [k], length [k]) of one molecule of one frame, as numpy"""
+        if self.bond_atoms is None:
+            raise ValueError('the bond list was not asked for (return_bonds=True)')
+        B = self.n_bonds.shape[1]
+        frame = frame % self.n_bonds.shape[0]
+        a, b = (int(x) for x in self.bond_ptr[frame * B + molecule:frame * B + molecule + 2])
+        l0 = int(self.ligand_ptr[molecule])
+        return (self.bond_atoms[a:b].cpu().numpy() - l0, self.bond_order[a:b].cpu().numpy(), self.bond_category[a:b].cpu().numpy(),
+                self.bond_length[a:b].cpu().numpy())
+
+
+def bond_graph(pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic', bond_profiles=None, include=None,
+               return_fragments=False, return_bonds=False, device=None):
+    """The bond graph of every molecule of one frame ``[N_l, 3]`` or of a stack ``[S, N_l, 3]`` (arguments as ``stability``): a pair
+    is bonded when the bond-length table gives it an order > 0; fragments are the connected components.  ``bond_profiles``: a sequence
+    of (z1, z2, category, edges), default the reference's eight bond types; ``include`` [S, B] restricts ``bond_hist`` and nothing
+    else.  Molecules of more than 512 atoms are refused.  Returns a ``BondGraph`` (the frame axis is kept for a single frame)."""
+    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
+    if include is not None:
+        include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+    prof = default_bond_profiles() if bond_profiles is None else tuple(bond_profiles)
+    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
+    r = capi.bond_graph(pos, v, ligand_ptr, cz, aro, prof, include, return_fragments, return_bonds)
+    bonds = capi.bond_list(pos, v, ligand_ptr, cz, aro, r['bond_ptr'], check=False) if return_bonds else None
+    return BondGraph(r, ligand_ptr, prof, bonds)
+
+
+class ConnectivityReport:
+    """Per frame (axis 0): how many samples are one piece, and the bond-length profiles of the included molecules.
+
+    ``complete`` [S] = complete molecules / samples (evaluate_diffusion.py:154), ``mean_fragments`` [S], ``mean_largest_share`` [S]
+    (atoms of the largest fragment / atoms, averaged over the non-empty samples); ``bond_hist`` [S, P, 128] int64."""
+
+    def __init__(self, n_complete, sum_fragments, sum_share, n_samples, n_nonempty, bond_hist, profiles, reference=None):
+        self.n_complete, self.sum_fragments = np.asarray(n_complete, dtype=np.int64), np.asarray(sum_fragments, dtype=np.int64)
+        self.sum_share = np.asarray(sum_share, dtype=np.float64)
+        self.n_samples, self.n_nonempty = int(n_samples), int(n_nonempty)
+        self.bond_hist, self.profiles, self.reference = np.asarray(bond_hist, dtype=np.int64), tuple(profiles), reference
+        self.bond_types = tuple((int(z1), int(z2), int(c)) for z1, z2, c, _ in self.profiles)
+        nan = np.full(self.n_complete.shape, np.nan)
+        self.complete = self.n_complete / float(self.n_samples) if self.n_samples else nan
+        self.mean_fragments = self.sum_fragments / float(self.n_samples) if self.n_samples else nan
+        self.mean_largest_share = self.sum_share / float(self.n_nonempty) if self.n_nonempty else nan
+
+    @classmethod
+    def merged(cls, reports):
+        reports = list(reports)
+        first = reports[0]
+        if any(r.bond_hist.shape != first.bond_hist.shape for r in reports):
+            raise ValueError('reports of different frame counts or profiles do not merge')
+        return cls(sum(r.n_complete for r in reports), sum(r.sum_fragments for r in reports), sum(r.sum_share for r in reports),
+                   sum(r.n_samples for r in reports), sum(r.n_nonempty for r in reports), sum(r.bond_hist for r in reports),
+                   first.profiles, first.reference)
+
+    @property
+    def num_frames(self):
+        return self.bond_hist.shape[0]
+
+    def distribution(self, bond_type, frame=-1):
+        """``counts / counts.sum()`` of a bond type over its ``len(edges) + 1`` bins (eval_bond_length.get_distribution), or None
+        when no such bond was seen (the reference's profile has no such key then)."""
+        p = self.bond_types.index(tuple(bond_type))
+        h = self.bond_hist[frame, p, :len(self.profiles[p][3]) + 1]
+        return h / np.sum(h) if h.sum() > 0 else None
+
+    def js(self, frame=-1):
+        """{'JSD_6-6|1': ...} over the profiles, as eval_bond_length.eval_bond_length_profile names them: None where there is no
+        reference distribution or no bond of that type."""
+        ref = self.reference or {}
+        out = {}
+        for t in self.bond_types:
+            d = self.distribution(t, frame)
+            out['JSD_' + bond_type_name(t)] = float(jensenshannon(ref[t], d)) if d is not None and t in ref else None
+        return out
+
+    def summary(self, frame=-1):
+        return dict(complete=float(self.complete[frame]), mean_fragments=float(self.mean_fragments[frame]),
+                    mean_largest_share=float(self.mean_largest_share[frame]), **self.js(frame))
+
+
+def sample_connectivity(result, eval_step=-1, include='all', atom_enc_mode='add_aromatic', reference=None, bond_profiles=None,
+                        device='cuda'):
+    """Connectivity of the samples of one pocket (``result``, ``eval_step`` and the packing as ``sample_quality``): per frame the
+    complete fraction, the mean number of fragments, the mean share of atoms in the largest fragment and the bond-length
+    distributions with their Jensen-Shannon distances.  ``include``: which molecules enter the bond-length histograms: ``'all'``
+    (default), ``'complete'`` (two launches: the first call's flags are the mask) or a bool array [frames, samples].  ``reference``:
+    {(z1, z2, category): distribution}; default ``reference_bond_distributions()``.  Returns a ``ConnectivityReport``."""
+    pos, v, ptr, sizes, S = _pack_result(result, eval_step, device)
+    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
+    prof = default_bond_profiles() if bond_profiles is None else tuple(bond_profiles)
+    if isinstance(include, str):
+        if include not in ('all', 'complete'):
+            raise ValueError("include is 'all', 'complete' or a mask [frames, samples]")
+        mask = None
+    else:
+        mask = torch.as_tensor(np.asarray(include)).to(device=pos.device, dtype=torch.bool).reshape(S, len(sizes)).contiguous()
+    if isinstance(include, str) and include == 'complete':
+        first = capi.bond_graph(pos, v, ptr, cz, aro)
+        r = capi.bond_graph(pos, v, ptr, cz, aro, prof, first['n_fragments'] == 1, check=False)
+    else:
+        r = capi.bond_graph(pos, v, ptr, cz, aro, prof, mask)
+    nf, big = r['n_fragments'].cpu().numpy().astype(np.int64), r['largest_fragment'].cpu().numpy().astype(np.float64)
+    n = np.asarray(sizes, dtype=np.float64)
+    share = np.divide(big, n[None], out=np.zeros_like(big), where=n[None] > 0)
+    if reference is None:
+        reference = reference_bond_distributions()
+    return ConnectivityReport((nf == 1).sum(1), nf.sum(1), share.sum(1), len(sizes), int((n > 0).sum()), r['bond_hist'].cpu().numpy(), prof,
+                              reference)

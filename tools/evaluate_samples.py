@@ -5,8 +5,10 @@
 Reads the ``result_{i}.pt`` files a sampling driver wrote (tools/batch_sample.py, or the reference's scripts/sample_diffusion.py),
 sorted as the reference sorts them, and prints under the reference's names: ``mol_stable`` and ``atm_stable``, the pair-distance
 Jensen-Shannon distances ``JSD_CC_2A`` and ``JSD_All_12A`` and ``Atom type JS``.  The pair profiles and the atom types are taken over
-``--include all`` samples (default) or the ``stable`` ones; the reference takes them over reconstructed complete molecules, which
-needs RDKit / OpenBabel and is not done here.  The Jensen-Shannon distances need the reference's empirical distributions: they are
+``--include all`` samples (default), the ``stable`` ones or the ``complete`` ones (one fragment of the bond graph of
+quality.bond_graph; the reference takes them over the molecules OpenBabel reconstructs in one piece).  ``--connectivity`` adds, from
+that bond graph, ``complete``, ``mean_fragments``, ``mean_largest_share`` and the reference's eight bond-length Jensen-Shannon
+distances (``JSD_6-6|1`` ...; ``--reference_npz`` may carry them as ``bond_types`` [8, 3] and ``bond_distributions`` [8, bins]).  The Jensen-Shannon distances need the reference's empirical distributions: they are
 loaded from ``utils.evaluation`` when the tool runs inside the reference repository (or with it on PYTHONPATH), or from
 ``--reference_npz FILE`` with arrays CC_2A, All_12A and atom_type; without them the three lines print None.
 
@@ -48,23 +50,29 @@ def main(argv=None):
     ap.add_argument('--eval_step', type=str, default='-1', help="a frame index (default -1: the final poses) or 'all'")
     ap.add_argument('--eval_num_examples', type=int, default=None)
     ap.add_argument('--atom_enc_mode', type=str, default='add_aromatic')
-    ap.add_argument('--include', type=str, default='all', choices=['all', 'stable'])
+    ap.add_argument('--include', type=str, default='all', choices=['all', 'stable', 'complete'])
+    ap.add_argument('--connectivity', action='store_true', help='also the bond graph: complete fraction, fragments, bond-length profiles')
     ap.add_argument('--reference_npz', type=str, default=None)
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
     eval_step = 'all' if args.eval_step == 'all' else int(args.eval_step)
 
-    reference = None
+    reference = bond_reference = None
     if args.reference_npz is not None:
         with np.load(args.reference_npz) as z:
             reference = {k: z[k] for k in ('CC_2A', 'All_12A', 'atom_type')}
+            if 'bond_types' in z.files:
+                bond_reference = {tuple(int(x) for x in t): d for t, d in zip(z['bond_types'], z['bond_distributions'])}
     files = result_files(args.sample_path, args.eval_num_examples)
     if not files:
         raise SystemExit(f'no result_*.pt under {args.sample_path}')
     print(f'Load generated data done! {len(files)} examples in total.')
-    reports = []
+    reports, connectivity = [], []
     for name in files:
         r = torch.load(name, map_location='cpu', weights_only=False)
+        if args.connectivity:
+            connectivity.append(quality.sample_connectivity(r, eval_step, 'complete' if args.include == 'complete' else 'all',
+                                                            args.atom_enc_mode, bond_reference, device=args.device))
         reports.append(quality.sample_quality(r, eval_step, args.include, args.atom_enc_mode, reference, device=args.device))
     rep = quality.QualityReport.merged(reports)
     print(f'Evaluate done! {rep.n_samples} samples in total.')
@@ -84,6 +92,14 @@ def main(argv=None):
                element_counts=dict(zip(('H', 'C', 'N', 'O', 'F', 'P', 'S', 'Cl'), rep.counts[-1].tolist())))
     if eval_step == 'all':
         out['curve'] = [frame(s) for s in range(rep.num_frames)]
+    if args.connectivity:
+        con = quality.ConnectivityReport.merged(connectivity)
+        last_con = con.summary(-1)
+        print_dict(last_con)
+        out['connectivity'] = dict(last_con, bond_hist={quality.bond_type_name(t): con.bond_hist[-1, p, :len(con.profiles[p][3]) + 1].tolist()
+                                                        for p, t in enumerate(con.bond_types)})
+        if eval_step == 'all':
+            out['connectivity']['curve'] = [con.summary(s) for s in range(con.num_frames)]
     result_path = os.path.join(args.sample_path, 'eval_results')
     os.makedirs(result_path, exist_ok=True)
     with open(os.path.join(result_path, 'quality.json'), 'w') as f:

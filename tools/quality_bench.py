@@ -10,7 +10,11 @@ current stream after one untimed call, the median of ``repeats`` and every value
   * ``sample_quality_all_ms``   quality.sample_quality(result, 'all'): host packing, the copy to the device, one launch, the copy back;
   * ``sample_quality_last_ms``  quality.sample_quality(result, -1): the final poses only;
   * ``kernel_all_ms``           capi.quality_report alone on the packed device tensors of all frames (check=False: no host look at
-                                the offsets), i.e. the memsets, the kernel and the allocation of the outputs.
+                                the offsets), i.e. the memsets, the kernel and the allocation of the outputs;
+  * ``kernel_last_ms``          the same on the final poses only;
+  * ``bond_graph_all_ms`` / ``bond_graph_last_ms``  capi.bond_graph (the eight default bond profiles, fragments and bond_ptr asked
+                                for, check=False) on the same two packs, in the same process: to be read beside the two lines above;
+  * ``bond_list_last_ms``       capi.bond_list for the final poses, its one host synchronisation included.
 
 ``numpy_cpu_estimate_s``: the restated rule in vectorised numpy (tests/_quality_ref.py) on ``cpu-frames`` evenly spaced frames in the same
 process, scaled to all frames -- an estimate, labelled as one; the reference's own per-molecule Python double loop is slower still and
@@ -80,6 +84,15 @@ def main():
     ptr = torch.as_tensor(np.cumsum([0] + sizes), dtype=torch.int32, device=dev)
     cz, prof = quality.class_atomic_numbers('add_aromatic'), quality.default_profiles()
     out['kernel_all_ms'] = event_ms(lambda: capi.quality_report(pos, v, ptr, cz, prof, None, False, check=False), reps)
+    pos1, v1 = pos[-1:].contiguous(), v[-1:].contiguous()
+    out['kernel_last_ms'] = event_ms(lambda: capi.quality_report(pos1, v1, ptr, cz, prof, None, False, check=False), reps)
+    aro, bprof = quality.class_aromatic('add_aromatic'), quality.default_bond_profiles()
+    out['bond_graph_all_ms'] = event_ms(lambda: capi.bond_graph(pos, v, ptr, cz, aro, bprof, None, True, True, check=False), reps)
+    out['bond_graph_last_ms'] = event_ms(lambda: capi.bond_graph(pos1, v1, ptr, cz, aro, bprof, None, True, True, check=False), reps)
+    g1 = capi.bond_graph(pos1, v1, ptr, cz, aro, bprof, None, True, True, check=False)
+    out['bond_list_last_ms'] = event_ms(lambda: capi.bond_list(pos1, v1, ptr, cz, aro, g1['bond_ptr'], check=False), reps)
+    gall = capi.bond_graph(pos, v, ptr, cz, aro, bprof, None, True, True, check=False)
+    out['bonds_last'], out['complete_first_last'] = int(g1['bond_ptr'][-1]), [int((gall['n_fragments'][k] == 1).sum()) for k in (0, -1)]
     rep = quality.sample_quality(res, 'all', reference={})
     out['atm_stable_first_last'] = [float(rep.atm_stable[0]), float(rep.atm_stable[-1])]
 

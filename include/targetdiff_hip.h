@@ -351,6 +351,28 @@ int td_bond_list(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand
                  const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const int64_t *d_bond_ptr, int64_t n_bonds,
                  int32_t *d_bond_atoms, uint8_t *d_bond_order, uint8_t *d_bond_category, double *d_bond_length, void *stream);
 
+/* ---- rings of ligand frames ("Rings"): per (frame, molecule), on the bond graph exactly as td_bond_graph
+ *      defines it (the same pack, class table, aromatic flags and d_include bytes; an atom whose class is outside [0, K) bonds with
+ *      nothing).  Ring size of a bond (i, j): the number of atoms of the shortest cycle through it = 1 + the shortest path from i to
+ *      j in the graph without the edge (i, j); 0 when there is none (a bridge); a unique integer in {0, 3 .. n}.  Ring size of an
+ *      atom: the minimum of the non-zero ring sizes of its bonds, 0 when it has none: the smallest ring that contains the atom.  Ring
+ *      mask of a molecule: bit min(k, 31) is set when some bond has ring size k; "has a ring of size k" means that bit.  This is not a
+ *      smallest set of smallest rings: a basis ring all of whose bonds also lie in smaller rings is not seen.  Ring-aware category
+ *      of a bond: td_bond_list's, except that 4 (aromatic) also needs a ring size of 5 or 6; otherwise the category is the order.
+ *      Output: d_ring_mask [S,B] uint32; d_n_ring_bonds / d_n_ring_atoms [S,B] int32, the bonds / atoms with a non-zero ring size;
+ *      d_atom_ring [S,N_l] int32 (may be NULL); d_ring_hist [S,32] int64, zeroed by the call: entry k > 0 counts the molecules whose
+ *      d_include byte is non-zero (NULL: all) and whose mask has bit k, entry 0 those whose mask is 0 (no ring at all).  Per bond, in
+ *      td_bond_list's order and at its offsets (d_bond_ptr [S*B+1] of td_bond_graph on the same pack; n_bonds = d_bond_ptr[S*B]):
+ *      d_bond_ring [n_bonds] uint16 and d_bond_category [n_bonds] uint8, the ring-aware category; either may be NULL, d_bond_ptr may
+ *      be NULL when both are, and TD_EINVAL when one is asked for without it.  Nothing is written at or beyond entry n_bonds,
+ *      whatever d_bond_ptr holds.  A molecule of more than 512 atoms, or one whose offsets leave [0, N_l], gets n_ring_bonds =
+ *      n_ring_atoms = -1 and mask 0 and contributes nothing else (a binding refuses it).  All outputs are integers: they do not
+ *      depend on the grid or on the order of arrival.  (An addition: TD_ABI_VERSION stays 5.) */
+int td_ring_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                   const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const uint8_t *class_aromatic,
+                   const int64_t *d_bond_ptr, int64_t n_bonds, uint32_t *d_ring_mask, int32_t *d_n_ring_bonds, int32_t *d_n_ring_atoms,
+                   int32_t *d_atom_ring, int64_t *d_ring_hist, uint16_t *d_bond_ring, uint8_t *d_bond_category, void *stream);
+
 /* ---- standalone EGNN refine net (replaces: models/egnn.py EGNN / EnBaseLayer as get_refine_net('egnn', config) builds
  *      it, models/molopt_score_model.py:34-42: num_r_gaussian = 1, kNN rebuilt per layer, SiLU, no LayerNorm, hidden 128,
  *      4 edge types, k = 32).  `host_weights`: per layer, in this order and as PyTorch stores them: edge_mlp.net.0.{weight

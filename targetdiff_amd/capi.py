@@ -89,6 +89,8 @@ SIGNATURES = {
                                 _P, _P, _P]),
     'td_bond_list': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), _P, c_int64, _P, _P, _P, _P,
                                _P]),
+    'td_ring_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, POINTER(ctypes.c_uint8), _P, c_int64, _P, _P, _P,
+                                 _P, _P, _P, _P, _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_center_pos': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int32, c_int32, _P]),
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
@@ -956,6 +958,44 @@ def bond_list(pos, v, ligand_ptr, class_z, class_aromatic, bond_ptr, check=True)
                                 S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _aromatic_arg(aro), _ptr(bond_ptr), nb,
                                 _ptr(out['bond_atoms']), _ptr(out['bond_order']), _ptr(out['bond_category']), _ptr(out['bond_length']),
                                 _stream(dev)), 'td_bond_list')
+    return out
+
+
+RING_BITS = 32                                                              # TD_RING_BITS (csrc/td_internal.h)
+
+
+def ring_report(pos, v, ligand_ptr, class_z, class_aromatic=None, include=None, bond_ptr=None, return_atom_ring=True, check=True):
+    """Ring sizes of the bond graph of S frames of B molecules (td_ring_report, include/targetdiff_hip.h); the pack, the class table
+    and ``include`` as bond_graph's.  With ``bond_ptr`` [S * B + 1] int64 from bond_graph on the same pack the per-bond outputs are
+    written too, aligned with bond_list's order; its last entry is read on the host to size them (one synchronisation).  Returns a
+    dict of device tensors: ring_mask [S, B] int64 (the uint32 words, widened), n_ring_bonds and n_ring_atoms [S, B] int32, atom_ring
+    [S, N_l] int32 (None without ``return_atom_ring``), ring_hist [S, 32] int64, and bond_ring [nb] int16 / bond_category [nb] uint8
+    (the ring-aware category; both None without ``bond_ptr``)."""
+    S, Nl, B, cz, aro, _ = _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, include, (), check)
+    if bond_ptr is not None and (bond_ptr.dim() != 1 or bond_ptr.numel() != S * B + 1 or bond_ptr.dtype != torch.int64):
+        raise ValueError(f'bond_ptr must be [{S * B + 1}] int64, as bond_graph returns it')
+    lib = load_library()
+    _ptr(pos, torch.float32, 'pos')                   # a CPU tensor is refused before anything is allocated
+    dev = pos.device
+    nb = 0
+    if bond_ptr is not None:
+        _ptr(bond_ptr, torch.int64, 'bond_ptr')
+        nb = int(bond_ptr[-1])
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    mask = i32(S, B)
+    out = dict(n_ring_bonds=i32(S, B), n_ring_atoms=i32(S, B), atom_ring=i32(S, Nl) if return_atom_ring else None,
+               ring_hist=torch.empty(S, RING_BITS, dtype=torch.int64, device=dev),
+               bond_ring=torch.empty(nb, dtype=torch.int16, device=dev) if bond_ptr is not None else None,
+               bond_category=torch.empty(nb, dtype=torch.uint8, device=dev) if bond_ptr is not None else None)
+    if include is not None and include.dtype == torch.bool:
+        include = include.view(torch.uint8)
+    with _on(dev):
+        _check(lib.td_ring_report(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
+                                  S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _ptr(include, torch.uint8, 'include'),
+                                  _aromatic_arg(aro), _ptr(bond_ptr), nb, _ptr(mask), _ptr(out['n_ring_bonds']), _ptr(out['n_ring_atoms']),
+                                  _ptr(out['atom_ring']), _ptr(out['ring_hist']), _ptr(out['bond_ring']), _ptr(out['bond_category']),
+                                  _stream(dev)), 'td_ring_report')
+    out['ring_mask'] = mask.to(torch.int64) & 0xffffffff              # torch has no arithmetic on uint32: the word, widened
     return out
 
 

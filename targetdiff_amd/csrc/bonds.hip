@@ -14,51 +14,9 @@
 // Two instantiations share the grid: 128 lanes for molecules of up to TD_BOND_SMALL_ATOMS atoms (ligands), 512 lanes up to
 // TD_BOND_MAX_ATOMS; a workgroup whose molecule belongs to the other one returns at once.  A molecule above TD_BOND_MAX_ATOMS, or whose
 // offsets leave [0, N_l], is answered with -1 by the 512-lane instantiation and contributes nothing else.
-#include "td_bond_rule.h"
-#include "td_device.h"
-#include "td_internal.h"
+#include "td_bond_graph.h"
 
-constexpr int BG_BINS = TD_BOND_BINS, BG_MAXP = TD_BOND_MAX_PROFILES, BG_SMALL = TD_BOND_SMALL_ATOMS, BG_MAX = TD_BOND_MAX_ATOMS;
 constexpr int BG_SCAN_THREADS = 1024;
-
-// what a workgroup needs to know about its molecule; `mine`: this instantiation handles it
-struct BgMol {
-    int s, g, l0, n;
-    size_t mol;
-    bool bad, mine;
-};
-
-template <int MAXN>
-__device__ __forceinline__ BgMol bg_molecule(const TdBondArgs &a) {
-    BgMol m;
-    m.s = blockIdx.x / a.B;
-    m.g = blockIdx.x - m.s * a.B;
-    m.l0 = a.lptr[m.g];
-    const int l1 = a.lptr[m.g + 1];
-    m.n = l1 - m.l0;
-    m.mol = (size_t)m.s * a.B + m.g;
-    m.bad = m.n > BG_MAX || (m.n > 0 && (m.l0 < 0 || (int64_t)l1 > a.Nl));
-    const bool small = !m.bad && m.n <= BG_SMALL;             // n <= 0: an empty molecule, the small instantiation writes its zeros
-    m.mine = (MAXN == BG_SMALL) == small;
-    return m;
-}
-
-// atom tid of the molecule into LDS as (x, y, z, code): code = element | aromatic << 8, or -1 for a class outside [0, K)
-template <int MAXN>
-__device__ __forceinline__ void bg_load(const TdBondArgs &a, const BgMol &m, const int *s_elem, float4 *s_at) {
-    const int tid = threadIdx.x;
-    if (tid < m.n) {
-        const size_t at = (size_t)m.s * (size_t)a.Nl + (size_t)(m.l0 + tid);
-        const float *p = a.pos + at * 3;
-        const int64_t c = a.v[at];
-        int code = -1;
-        if (c >= 0 && c < a.K) code = s_elem[(int)c] | ((int)((a.aromatic >> (int)c) & 1ull) << 8);
-        s_at[tid] = make_float4(p[0], p[1], p[2], __int_as_float(code));
-    }
-}
-
-// category of a bond: its order, or 4 (aromatic) when both atoms' classes are aromatic and the order is 1 or 2
-__device__ __forceinline__ int bg_category(int ci, int cj, int order) { return ((ci & cj) >> 8 & 1) && order <= 2 ? 4 : order; }
 
 template <int MAXN>
 __global__ __launch_bounds__(MAXN) void bond_graph_kernel(TdBondArgs a) {
@@ -96,46 +54,26 @@ __global__ __launch_bounds__(MAXN) void bond_graph_kernel(TdBondArgs a) {
     bg_load<MAXN>(a, m, s_elem, s_at);
     __syncthreads();
 
-    // ---- the row of atom tid: order > 0 with atom j sets bit j; bonds tid < j are counted and enter the histograms
+    // ---- the row of atom tid (td_bond_graph.h); bonds tid < j are counted and enter the histograms
     int up = 0;
     if (tid < n) {
-        const float4 me = s_at[tid];
-        const int ci = __float_as_int(me.w), ei = ci & 7;
-        const double xi = (double)me.x, yi = (double)me.y, zi = (double)me.z;
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-            unsigned long long bits = 0ull;
-            const int cnt = n - w * 64 < 64 ? n - w * 64 : 64;
-            if (ci >= 0) {
-                for (int jj = 0; jj < cnt; ++jj) {
-                    const int j = w * 64 + jj;
-                    const float4 q = s_at[j];                                   // every lane reads the same address: an LDS broadcast
-                    const int cj = __float_as_int(q.w), ej = cj & 7;
-                    if (j == tid || cj < 0) continue;
-                    double d;
-                    const int order = td_bond_order(xi, yi, zi, q.x, q.y, q.z, ei * 8 + ej, s_thr, d);
-                    if (order == 0) continue;
-                    bits |= 1ull << jj;
-                    if (j < tid) continue;
-                    ++up;
-                    const int cat = bg_category(ci, cj, order);
-                    for (int p = 0; p < P; ++p) {
-                        const int e1 = s_pe1[p], e2 = s_pe2[p], pc = s_pcat[p];
-                        const bool match = ((e1 < 0 || ei == e1) && (e2 < 0 || ej == e2)) || ((e1 < 0 || ej == e1) && (e2 < 0 || ei == e2));
-                        if (match && (pc == 0 || pc == cat)) {
-                            const double *edges = s_pedges[p];
-                            int lo = 0, hi = s_pn[p];                           // numpy.searchsorted(edges, d, 'left'); <= 7 halvings
-                            while (lo < hi) {
-                                const int mid = (lo + hi) >> 1;
-                                if (edges[mid] < d) lo = mid + 1; else hi = mid;
-                            }
-                            atomicAdd(&s_hist[p][lo], 1u);
-                        }
+        const int ci = __float_as_int(s_at[tid].w), ei = ci & 7;
+        up = bg_rows<MAXN>(n, s_at, s_thr, s_row, [&](int j, int cj, int order, double d) {
+            const int ej = cj & 7, cat = bg_category(ci, cj, order);
+            for (int p = 0; p < P; ++p) {
+                const int e1 = s_pe1[p], e2 = s_pe2[p], pc = s_pcat[p];
+                const bool match = ((e1 < 0 || ei == e1) && (e2 < 0 || ej == e2)) || ((e1 < 0 || ej == e1) && (e2 < 0 || ei == e2));
+                if (match && (pc == 0 || pc == cat)) {
+                    const double *edges = s_pedges[p];
+                    int lo = 0, hi = s_pn[p];                                   // numpy.searchsorted(edges, d, 'left'); <= 7 halvings
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (edges[mid] < d) lo = mid + 1; else hi = mid;
                     }
+                    atomicAdd(&s_hist[p][lo], 1u);
                 }
             }
-            s_row[w][tid] = bits;
-        }
+        });
     }
     __syncthreads();
 
@@ -245,12 +183,7 @@ __global__ __launch_bounds__(MAXN) void bond_list_kernel(TdBondArgs a) {
     }
     s_off[tid] = up;
     __syncthreads();
-    for (int d = 1; d < MAXN; d <<= 1) {                                        // inclusive scan of the per-atom counts
-        const int t = tid >= d ? s_off[tid - d] : 0;
-        __syncthreads();
-        s_off[tid] += t;
-        __syncthreads();
-    }
+    bg_scan<MAXN>(s_off);                                                       // inclusive scan of the per-atom counts
     if (up == 0) return;
     int64_t k = a.bond_ptr[m.mol] + (int64_t)(s_off[tid] - up);
     for (int j = tid + 1; j < n; ++j) {

@@ -1,10 +1,10 @@
-// C ABI of libtargetdiff_hip.so: the bond graph of ligand frames (td_bond_graph, td_bond_list).  See include/targetdiff_hip.h for the
-// contract.
+// C ABI of libtargetdiff_hip.so: the bond graph of ligand frames and its rings (td_bond_graph, td_bond_list, td_ring_report).  See
+// include/targetdiff_hip.h for the contract.
 #include "td_device.h"
 #include "td_internal.h"
 
 namespace {
-// the checks and the fields both entry points share: sizes, the class table and the aromatic flags
+// the checks and the fields the entry points share: sizes, the class table and the aromatic flags
 int bond_pack(const char *who, TdBondArgs &a, const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l,
               int64_t B, const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic) {
     if (S < 0 || B < 0 || N_l < 0 || N_l > 0x7fffffff || S > 0x7fffffff || B > 0x7fffffff || S * B > 0x7fffffff) {
@@ -90,4 +90,28 @@ extern "C" int td_bond_list(const float *d_pos, const int64_t *d_v, const int32_
     a.bond_ptr = const_cast<int64_t *>(d_bond_ptr); a.capacity = n_bonds;
     a.bond_atoms = d_bond_atoms; a.bond_order = d_bond_order; a.bond_category = d_bond_category; a.bond_length = d_bond_length;
     return td_launch_bond_list(a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int td_ring_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                              const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const uint8_t *class_aromatic,
+                              const int64_t *d_bond_ptr, int64_t n_bonds, uint32_t *d_ring_mask, int32_t *d_n_ring_bonds,
+                              int32_t *d_n_ring_atoms, int32_t *d_atom_ring, int64_t *d_ring_hist, uint16_t *d_bond_ring,
+                              uint8_t *d_bond_category, void *stream) {
+    const char *who = "td_ring_report";
+    TdBondArgs a;
+    if (n_bonds < 0) { td_set_error("%s: bad argument (n_bonds = %lld)", who, (long long)n_bonds); return TD_EINVAL; }
+    if (const int rc = bond_pack(who, a, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic)) return rc;
+    if ((d_bond_ring || d_bond_category) && !d_bond_ptr) {
+        td_set_error("%s: the per-bond outputs need d_bond_ptr of td_bond_graph", who);
+        return TD_EINVAL;
+    }
+    if ((S > 0 && !d_ring_hist) || (S > 0 && B > 0 && (!d_ring_mask || !d_n_ring_bonds || !d_n_ring_atoms))) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    a.include = d_include;
+    a.bond_ptr = const_cast<int64_t *>(d_bond_ptr); a.capacity = n_bonds;
+    a.ring_mask = d_ring_mask; a.n_ring_bonds = d_n_ring_bonds; a.n_ring_atoms = d_n_ring_atoms; a.atom_ring = d_atom_ring;
+    a.ring_hist = reinterpret_cast<unsigned long long *>(d_ring_hist); a.bond_ring = d_bond_ring; a.bond_category = d_bond_category;
+    return td_launch_ring_report(a, static_cast<hipStream_t>(stream));
 }

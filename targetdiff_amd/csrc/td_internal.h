@@ -427,8 +427,8 @@ struct TdQualityArgs {
 };
 int td_launch_quality(const TdQualityArgs &a, hipStream_t s);
 int td_element_index(int z);                 // quality_api.cpp: 0..7 (H C N O F P S Cl) of an atomic number, -1 for any other
-// bonds.hip (bond graph): the arguments of td_bond_graph / td_bond_list over S frames x B molecules.  elem and a
-// profile's pe1 / pe2 as in TdQualityArgs; aromatic: bit c set when class c is aromatic; pcat: 0 = any category.  The launcher zeroes
+// bonds.hip, rings.hip (bond graph): the arguments of td_bond_graph / td_bond_list / td_ring_report over S
+// frames x B molecules.  elem and a profile's pe1 / pe2 as in TdQualityArgs; aromatic: bit c set when class c is aromatic; pcat: 0 = any category.  The launcher zeroes
 // hist on the stream before the kernels add to it.  Molecules of up to TD_BOND_SMALL_ATOMS atoms run in 128-lane workgroups, larger
 // ones (up to TD_BOND_MAX_ATOMS) in 512-lane workgroups: both grids cover every molecule and each workgroup takes only its own kind.
 constexpr int TD_BOND_MAX_ATOMS = 512, TD_BOND_SMALL_ATOMS = 128, TD_BOND_MAX_PROFILES = 16, TD_BOND_BINS = 128;
@@ -452,9 +452,18 @@ struct TdBondArgs {
     int32_t *bond_atoms = nullptr;           // [capacity,2]
     uint8_t *bond_order = nullptr, *bond_category = nullptr;
     double *bond_length = nullptr;
+    // rings.hip (td_ring_report, DESIGN.md section 3, "Rings"): bond_ptr is read and may be null; capacity bounds bond_ring and
+    // bond_category (here the ring-aware category), each of which may be null.  The launcher zeroes ring_hist on the stream.
+    uint32_t *ring_mask = nullptr;           // [S,B]
+    int32_t *n_ring_bonds = nullptr, *n_ring_atoms = nullptr;                    // [S,B]
+    int32_t *atom_ring = nullptr;            // [S,N_l] or null
+    unsigned long long *ring_hist = nullptr; // [S,TD_RING_BITS]
+    uint16_t *bond_ring = nullptr;           // [capacity] or null
 };
+constexpr int TD_RING_BITS = 32;
 int td_launch_bond_graph(const TdBondArgs &a, hipStream_t s);
 int td_launch_bond_list(const TdBondArgs &a, hipStream_t s);
+int td_launch_ring_report(const TdBondArgs &a, hipStream_t s);
 // egnn.hip / node.hip
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s);

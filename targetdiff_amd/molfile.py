@@ -48,11 +48,14 @@ def write_sdf(path, molecules):
     return len(records)
 
 
-def molecules_from_graph(graph, pos, v, atom_enc_mode='add_aromatic', frame=-1, only_complete=False, largest_fragment=False, names=None):
+def molecules_from_graph(graph, pos, v, atom_enc_mode='add_aromatic', frame=-1, only_complete=False, largest_fragment=False, names=None,
+                         categories=None):
     """The molecules of one frame of a ``quality.BondGraph`` made with ``return_fragments=True, return_bonds=True`` on the pack
     (``pos`` [S, N_l, 3] or [N_l, 3], ``v`` alike).  ``only_complete`` drops the molecules of more than one fragment;
     ``largest_fragment`` keeps, of every molecule, the atoms and bonds of its largest fragment (of equal ones the one with the
-    smallest label) -- chosen here on the host from ``graph.fragment``."""
+    smallest label) -- chosen here on the host from ``graph.fragment``.  ``categories``: the bond types to write, one per bond of
+    the graph's list; default ``graph.bond_category``; ``graph.ring_category`` of a graph made with ``rings=True`` keeps type 4 to
+    bonds inside a ring of 5 or 6 atoms ("Rings")."""
     if graph.fragment is None or graph.bond_atoms is None:
         raise ValueError('the graph needs return_fragments=True and return_bonds=True')
     to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
@@ -63,7 +66,9 @@ def molecules_from_graph(graph, pos, v, atom_enc_mode='add_aromatic', frame=-1, 
     frame = frame % S
     ptr, bptr = to_np(graph.ligand_ptr), to_np(graph.bond_ptr)
     frag, nfrag = to_np(graph.fragment)[frame], to_np(graph.n_fragments)[frame]
-    atoms, cats = to_np(graph.bond_atoms), to_np(graph.bond_category)
+    atoms, cats = to_np(graph.bond_atoms), to_np(graph.bond_category if categories is None else categories)
+    if len(cats) != len(atoms):
+        raise ValueError(f'{len(cats)} categories for {len(atoms)} bonds')
     cz = np.asarray(quality.class_atomic_numbers(atom_enc_mode))
     out = []
     for g in range(B):

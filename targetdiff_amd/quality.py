@@ -24,6 +24,13 @@ The bonds the table implies are kept too (``td_bond_graph`` / ``td_bond_list``, 
     con = quality.sample_connectivity(result, eval_step='all')    # complete fraction, fragments and bond-length profiles per frame
     rep = quality.sample_quality(result, include='complete')      # the reference's "success_*" restriction to one-piece molecules
 
+and so are its rings (``td_ring_report``, csrc/rings.hip; DESIGN.md section 3, "Rings"): per bond the size of the smallest cycle
+through it, per atom the smallest ring that holds it, per molecule the set of such sizes:
+
+    g = quality.bond_graph(pos, v, batch_ligand, return_bonds=True, rings=True)    # g.bond_ring, g.atom_ring, g.ring_mask, ...
+    rings = quality.sample_rings(result, eval_step='all')         # evaluate_diffusion.py's ring ratios (:26-32), per frame
+    rings.ring_ratio(-1)    # {3: ..., 4: ..., ..., 9: ...}: the share of molecules that have a ring of that size
+
 OpenBabel's reconstruction, valence repair, QED / SA and docking need a chemistry toolkit and are not here.
 """
 from __future__ import annotations
@@ -325,9 +332,12 @@ class BondGraph:
     [S, B] bool (one fragment), ``bond_hist`` [S, P, 128] int64 over the included molecules, ``ligand_ptr`` [B + 1]; optional:
     ``fragment`` [S, N_l] int32 (per atom, the smallest molecule-local index of its component) and the bond list in ascending
     (frame, molecule, i, j) order: ``bond_ptr`` [S * B + 1] int64, ``bond_atoms`` [nb, 2] int32 (indices along the atom axis),
-    ``bond_order`` / ``bond_category`` [nb] uint8, ``bond_length`` [nb] float64."""
+    ``bond_order`` / ``bond_category`` [nb] uint8, ``bond_length`` [nb] float64.  With ``rings=True``: ``ring_mask`` [S, B] int64
+    (bit min(k, 31): some bond's smallest ring has k atoms), ``n_ring_bonds`` / ``n_ring_atoms`` [S, B] int32, ``atom_ring`` [S, N_l]
+    int32 (the smallest ring that holds the atom, 0: none) and, beside the bond list, ``bond_ring`` [nb] int16 (atoms of the smallest
+    cycle through the bond, 0: a bridge) and ``ring_category`` [nb] uint8 (the category, 4 only inside a ring of 5 or 6)."""
 
-    def __init__(self, r, ligand_ptr, profiles, bonds=None):
+    def __init__(self, r, ligand_ptr, profiles, bonds=None, rings=None):
         self.n_bonds, self.n_fragments, self.largest_fragment = r['n_bonds'], r['n_fragments'], r['largest_fragment']
         self.bond_hist, self.fragment, self.bond_ptr = r['bond_hist'], r['fragment'], r['bond_ptr']
         self.ligand_ptr, self.profiles = ligand_ptr, tuple(profiles)
@@ -337,25 +347,33 @@ class BondGraph:
         bonds = bonds or {}
         self.bond_atoms, self.bond_order = bonds.get('bond_atoms'), bonds.get('bond_order')
         self.bond_category, self.bond_length = bonds.get('bond_category'), bonds.get('bond_length')
+        rings = rings or {}
+        self.ring_mask, self.n_ring_bonds, self.n_ring_atoms = rings.get('ring_mask'), rings.get('n_ring_bonds'), rings.get('n_ring_atoms')
+        self.atom_ring, self.bond_ring, self.ring_category = rings.get('atom_ring'), rings.get('bond_ring'), rings.get('bond_category')
 
     def molecule_bonds(self, frame, molecule):
-        """(atoms [k, 2] molecule-local, order [k], category [k], length [k]) of one molecule of one frame, as numpy"""
+        """(atoms [k, 2] molecule-local, order [k], category [k], length [k]) of one molecule of one frame, as numpy; of a graph with
+        rings also (ring size [k], ring-aware category [k])"""
         if self.bond_atoms is None:
             raise ValueError('the bond list was not asked for (return_bonds=True)')
         B = self.n_bonds.shape[1]
         frame = frame % self.n_bonds.shape[0]
         a, b = (int(x) for x in self.bond_ptr[frame * B + molecule:frame * B + molecule + 2])
         l0 = int(self.ligand_ptr[molecule])
-        return (self.bond_atoms[a:b].cpu().numpy() - l0, self.bond_order[a:b].cpu().numpy(), self.bond_category[a:b].cpu().numpy(),
-                self.bond_length[a:b].cpu().numpy())
+        out = (self.bond_atoms[a:b].cpu().numpy() - l0, self.bond_order[a:b].cpu().numpy(), self.bond_category[a:b].cpu().numpy(),
+               self.bond_length[a:b].cpu().numpy())
+        if self.bond_ring is not None:
+            out += (self.bond_ring[a:b].cpu().numpy(), self.ring_category[a:b].cpu().numpy())
+        return out
 
 
 def bond_graph(pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic', bond_profiles=None, include=None,
-               return_fragments=False, return_bonds=False, device=None):
+               return_fragments=False, return_bonds=False, rings=False, device=None):
     """The bond graph of every molecule of one frame ``[N_l, 3]`` or of a stack ``[S, N_l, 3]`` (arguments as ``stability``): a pair
     is bonded when the bond-length table gives it an order > 0; fragments are the connected components.  ``bond_profiles``: a sequence
     of (z1, z2, category, edges), default the reference's eight bond types; ``include`` [S, B] restricts ``bond_hist`` and nothing
-    else.  Molecules of more than 512 atoms are refused.  Returns a ``BondGraph`` (the frame axis is kept for a single frame)."""
+    else.  ``rings``: also the ring sizes (one more launch, ``td_ring_report``), per bond when ``return_bonds`` is given too.
+    Molecules of more than 512 atoms are refused.  Returns a ``BondGraph`` (the frame axis is kept for a single frame)."""
     pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
     if include is not None:
         include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
@@ -363,7 +381,8 @@ def bond_graph(pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_ar
     cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
     r = capi.bond_graph(pos, v, ligand_ptr, cz, aro, prof, include, return_fragments, return_bonds)
     bonds = capi.bond_list(pos, v, ligand_ptr, cz, aro, r['bond_ptr'], check=False) if return_bonds else None
-    return BondGraph(r, ligand_ptr, prof, bonds)
+    ring = capi.ring_report(pos, v, ligand_ptr, cz, aro, None, r['bond_ptr'], check=False) if rings else None
+    return BondGraph(r, ligand_ptr, prof, bonds, ring)
 
 
 class ConnectivityReport:
@@ -447,3 +466,78 @@ def sample_connectivity(result, eval_step=-1, include='all', atom_enc_mode='add_
         reference = reference_bond_distributions()
     return ConnectivityReport((nf == 1).sum(1), nf.sum(1), share.sum(1), len(sizes), int((n > 0).sum()), r['bond_hist'].cpu().numpy(), prof,
                               reference)
+
+
+RING_SIZES = tuple(range(3, 10))                      # evaluate_diffusion.py print_ring_ratio: range(3, 10)
+
+
+class RingReport:
+    """Per frame (axis 0): which ring sizes the included molecules have.  ``ring_hist`` [S, 32] int64: entry k > 0 counts the
+    included molecules in which some bond's smallest ring has k atoms (31: 31 or more), entry 0 those without any ring; ``n_included``
+    [S]; ``n_large`` [S] the included molecules with a ring of more than 9 atoms; ``sum_atom_share`` [S] the sum over the included
+    non-empty molecules (``n_nonempty`` [S]) of atoms in rings / atoms.  A ring here is the smallest cycle through some bond: not a
+    smallest set of smallest rings ("Rings")."""
+
+    def __init__(self, ring_hist, n_included, n_large, sum_atom_share, n_nonempty, n_samples):
+        self.ring_hist = np.asarray(ring_hist, dtype=np.int64)
+        self.n_included, self.n_large = np.asarray(n_included, dtype=np.int64), np.asarray(n_large, dtype=np.int64)
+        self.sum_atom_share, self.n_nonempty = np.asarray(sum_atom_share, dtype=np.float64), np.asarray(n_nonempty, dtype=np.int64)
+        self.n_samples = int(n_samples)
+
+    @classmethod
+    def merged(cls, reports):
+        reports = list(reports)
+        if any(r.ring_hist.shape != reports[0].ring_hist.shape for r in reports):
+            raise ValueError('reports of different frame counts do not merge')
+        return cls(sum(r.ring_hist for r in reports), sum(r.n_included for r in reports), sum(r.n_large for r in reports),
+                   sum(r.sum_atom_share for r in reports), sum(r.n_nonempty for r in reports), sum(r.n_samples for r in reports))
+
+    @property
+    def num_frames(self):
+        return self.ring_hist.shape[0]
+
+    def _share(self, count, frame):
+        n = int(self.n_included[frame])
+        return int(count) / n if n else float('nan')
+
+    def ring_ratio(self, frame=-1):
+        """{3: ..., ..., 9: ...}: molecules with a ring of that size / included molecules (print_ring_ratio's n_mol / len)"""
+        return {k: self._share(self.ring_hist[frame, k], frame) for k in RING_SIZES}
+
+    def no_ring(self, frame=-1):
+        return self._share(self.ring_hist[frame, 0], frame)
+
+    def large_ring(self, frame=-1):
+        return self._share(self.n_large[frame], frame)
+
+    def ring_atom_share(self, frame=-1):
+        n = int(self.n_nonempty[frame])
+        return float(self.sum_atom_share[frame]) / n if n else float('nan')
+
+    def summary(self, frame=-1):
+        return dict(**{f'ring_{k}': x for k, x in self.ring_ratio(frame).items()}, no_ring=self.no_ring(frame),
+                    large_ring=self.large_ring(frame), ring_atom_share=self.ring_atom_share(frame))
+
+
+def sample_rings(result, eval_step=-1, include='all', atom_enc_mode='add_aromatic', device='cuda'):
+    """Rings of the samples of one pocket (``result``, ``eval_step`` and the packing as ``sample_quality``): per frame the share of
+    molecules that have a ring of 3 .. 9 atoms as the reference's print_ring_ratio forms it, the share without any ring, the share
+    with a ring of more than 9 atoms and the mean share of atoms in rings.  ``include``: the molecules that are counted: ``'all'``
+    (default), ``'complete'`` (one fragment in that frame; the bond graph runs first and its flags are the mask) or a bool array
+    [frames, samples].  Returns a ``RingReport``."""
+    pos, v, ptr, sizes, S = _pack_result(result, eval_step, device)
+    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
+    if isinstance(include, str):
+        if include not in ('all', 'complete'):
+            raise ValueError("include is 'all', 'complete' or a mask [frames, samples]")
+        mask = capi.bond_graph(pos, v, ptr, cz, aro)['n_fragments'] == 1 if include == 'complete' else None
+    else:
+        mask = torch.as_tensor(np.asarray(include)).to(device=pos.device, dtype=torch.bool).reshape(S, len(sizes)).contiguous()
+    r = capi.ring_report(pos, v, ptr, cz, aro, mask, None, False, check=not (isinstance(include, str) and include == 'complete'))
+    inc = np.ones((S, len(sizes)), bool) if mask is None else mask.cpu().numpy().astype(bool)
+    n = np.asarray(sizes, dtype=np.float64)
+    ring_atoms = r['n_ring_atoms'].cpu().numpy().astype(np.float64)
+    share = np.divide(ring_atoms, n[None], out=np.zeros_like(ring_atoms), where=n[None] > 0)
+    large = (r['ring_mask'].cpu().numpy() >> (RING_SIZES[-1] + 1)) != 0
+    return RingReport(r['ring_hist'].cpu().numpy(), inc.sum(1), (large & inc).sum(1), np.where(inc, share, 0.0).sum(1),
+                      (inc & (n[None] > 0)).sum(1), len(sizes))

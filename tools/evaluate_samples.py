@@ -8,7 +8,10 @@ Jensen-Shannon distances ``JSD_CC_2A`` and ``JSD_All_12A`` and ``Atom type JS``.
 ``--include all`` samples (default), the ``stable`` ones or the ``complete`` ones (one fragment of the bond graph of
 quality.bond_graph; the reference takes them over the molecules OpenBabel reconstructs in one piece).  ``--connectivity`` adds, from
 that bond graph, ``complete``, ``mean_fragments``, ``mean_largest_share`` and the reference's eight bond-length Jensen-Shannon
-distances (``JSD_6-6|1`` ...; ``--reference_npz`` may carry them as ``bond_types`` [8, 3] and ``bond_distributions`` [8, bins]).  The Jensen-Shannon distances need the reference's empirical distributions: they are
+distances (``JSD_6-6|1`` ...; ``--reference_npz`` may carry them as ``bond_types`` [8, 3] and ``bond_distributions`` [8, bins]).
+``--rings`` adds the reference's ring ratios (evaluate_diffusion.py print_ring_ratio, ``ring size: k ratio: x.xxx`` for k = 3 .. 9)
+from the ring sizes of quality.sample_rings -- the smallest cycle through some bond, not a toolkit's ring set -- over ``--include
+all`` or ``complete`` samples, and the shares of molecules without a ring and with a ring of more than 9 atoms.  The Jensen-Shannon distances need the reference's empirical distributions: they are
 loaded from ``utils.evaluation`` when the tool runs inside the reference repository (or with it on PYTHONPATH), or from
 ``--reference_npz FILE`` with arrays CC_2A, All_12A and atom_type; without them the three lines print None.
 
@@ -52,6 +55,7 @@ def main(argv=None):
     ap.add_argument('--atom_enc_mode', type=str, default='add_aromatic')
     ap.add_argument('--include', type=str, default='all', choices=['all', 'stable', 'complete'])
     ap.add_argument('--connectivity', action='store_true', help='also the bond graph: complete fraction, fragments, bond-length profiles')
+    ap.add_argument('--rings', action='store_true', help='also the ring ratios: the share of molecules with a ring of 3 .. 9 atoms')
     ap.add_argument('--reference_npz', type=str, default=None)
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
@@ -67,12 +71,15 @@ def main(argv=None):
     if not files:
         raise SystemExit(f'no result_*.pt under {args.sample_path}')
     print(f'Load generated data done! {len(files)} examples in total.')
-    reports, connectivity = [], []
+    reports, connectivity, rings = [], [], []
     for name in files:
         r = torch.load(name, map_location='cpu', weights_only=False)
         if args.connectivity:
             connectivity.append(quality.sample_connectivity(r, eval_step, 'complete' if args.include == 'complete' else 'all',
                                                             args.atom_enc_mode, bond_reference, device=args.device))
+        if args.rings:
+            rings.append(quality.sample_rings(r, eval_step, 'complete' if args.include == 'complete' else 'all', args.atom_enc_mode,
+                                              device=args.device))
         reports.append(quality.sample_quality(r, eval_step, args.include, args.atom_enc_mode, reference, device=args.device))
     rep = quality.QualityReport.merged(reports)
     print(f'Evaluate done! {rep.n_samples} samples in total.')
@@ -100,6 +107,14 @@ def main(argv=None):
                                                         for p, t in enumerate(con.bond_types)})
         if eval_step == 'all':
             out['connectivity']['curve'] = [con.summary(s) for s in range(con.num_frames)]
+    if args.rings:
+        ring = quality.RingReport.merged(rings)
+        for k, x in ring.ring_ratio(-1).items():
+            print(f'ring size: {k} ratio: {x:.3f}')
+        print_dict({k: x for k, x in ring.summary(-1).items() if not k.startswith('ring_') or k == 'ring_atom_share'})
+        out['rings'] = dict(ring.summary(-1), ring_hist=ring.ring_hist[-1].tolist(), num_included=int(ring.n_included[-1]))
+        if eval_step == 'all':
+            out['rings']['curve'] = [ring.summary(s) for s in range(ring.num_frames)]
     result_path = os.path.join(args.sample_path, 'eval_results')
     os.makedirs(result_path, exist_ok=True)
     with open(os.path.join(result_path, 'quality.json'), 'w') as f:

@@ -1,12 +1,14 @@
 """Sampled ligands as SD files, without a chemistry toolkit:
 
-    python tools/export_sdf.py --sample_path DIR --out DIR [--eval_step -1] [--only-complete] [--largest-fragment]
+    python tools/export_sdf.py --sample_path DIR --out DIR [--eval_step -1] [--only-complete] [--largest-fragment] [--ring-aromatic]
 
 Reads the ``result_{i}.pt`` files a sampling driver wrote (sorted as tools/evaluate_samples.py sorts them), takes the frame
 ``--eval_step`` of every sample (default -1: the final poses), builds the bond graph on the GPU (quality.bond_graph: bonds from the
 bond-length table, fragments as connected components) and writes ``OUT/result_{i}.sdf`` with one V2000 record per sample: element
 symbols from the class table, the bond type from the bond's category (1 / 2 / 3, 4 = aromatic: both atoms of aromatic classes and
 order 1 or 2; DESIGN.md section 3, "Bond graph" -- a convention, not perceived chemistry; no hydrogens are added).
+``--ring-aromatic`` writes the ring-aware category instead (quality.bond_graph(rings=True); DESIGN.md section 3, "Rings"): type 4 only
+for a bond that also lies in a ring of 5 or 6 atoms, its order otherwise, so no atom outside a ring carries an aromatic bond.
 ``--only-complete`` writes only the samples that are one fragment; ``--largest-fragment`` writes of every sample its largest fragment.
 Prints one line per file and returns the counts.
 """
@@ -34,6 +36,7 @@ def main(argv=None):
     ap.add_argument('--atom_enc_mode', type=str, default='add_aromatic')
     ap.add_argument('--only-complete', action='store_true')
     ap.add_argument('--largest-fragment', action='store_true')
+    ap.add_argument('--ring-aromatic', action='store_true', help='bond type 4 only inside a ring of 5 or 6 atoms')
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
     files = result_files(args.sample_path, args.eval_num_examples)
@@ -45,8 +48,9 @@ def main(argv=None):
         r = torch.load(name, map_location='cpu', weights_only=False)
         pos, v, ptr, sizes, _ = quality._pack_result(r, args.eval_step, args.device)
         g = quality.bond_graph(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, bond_profiles=(), return_fragments=True,
-                               return_bonds=True, device=args.device)
-        mols = molfile.molecules_from_graph(g, pos, v, args.atom_enc_mode, 0, args.only_complete, args.largest_fragment)
+                               return_bonds=True, rings=args.ring_aromatic, device=args.device)
+        mols = molfile.molecules_from_graph(g, pos, v, args.atom_enc_mode, 0, args.only_complete, args.largest_fragment,
+                                            categories=g.ring_category if args.ring_aromatic else None)
         stem = os.path.basename(name)[:-3]
         path = os.path.join(args.out, stem + '.sdf')
         n = molfile.write_sdf(path, mols)

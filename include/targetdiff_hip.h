@@ -373,6 +373,39 @@ int td_ring_report(const float *d_pos, const int64_t *d_v, const int32_t *d_liga
                    const int64_t *d_bond_ptr, int64_t n_bonds, uint32_t *d_ring_mask, int32_t *d_n_ring_bonds, int32_t *d_n_ring_atoms,
                    int32_t *d_atom_ring, int64_t *d_ring_hist, uint16_t *d_bond_ring, uint8_t *d_bond_category, void *stream);
 
+/* ---- fingerprints of ligand frames ("Fingerprints and diversity"): per (frame, molecule), on the bond graph
+ *      exactly as td_bond_graph defines it (the same pack, class table and aromatic flags).  This is not RDKit's RDKFingerprint: it
+ *      is a circular, Morgan-style fingerprint over this project's bond graph, whose orders come from the bond-length table; its
+ *      similarities are comparable between runs of this library, not with published tables.  All arithmetic on uint64, wrapping.
+ *      mix(x), the splitmix64 finaliser: x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) *
+ *      0x94D049BB133111EB; x ^= x >> 31.  An atom whose class is in [0, K): id_0 = mix(Z | aromatic << 8 | degree << 16 | valence <<
+ *      24) with Z its atomic number, aromatic its class flag, degree its number of bonds and valence the sum of their orders; an atom
+ *      of no class takes no part anywhere.  Round r = 1, 2, ...: id_r[i] = mix(mix(id_{r-1}[i] ^ r) + sum over the bonded j of
+ *      mix(id_{r-1}[j] ^ mix(category_ij))), the category that of td_bond_list (1, 2, 3, 4 = aromatic); the sum is commutative: the
+ *      order the atoms are stored in does not matter.  Fingerprint: TD_FP_BITS = 2048 bits, bit id_r[i] mod 2048 set for every such
+ *      atom and every r = 0 .. radius (0 <= radius <= 4).  Key, after key_rounds rounds (radius <= key_rounds <= 16): mix((sum over
+ *      the atoms of mix(id[i])) ^ mix(n_valid << 32 | n_bonds)).  Equal keys: not told apart by Weisfeiler-Lehman colour refinement
+ *      with these invariants after that many rounds.  This is not a canonical form: graphs that refinement cannot separate (the
+ *      skeletons of decalin and bicyclopentyl) have equal keys.
+ *      Output: d_fp_words [S,B,32] int64, word w bit k = fingerprint bit 64 w + k; d_n_bits [S,B] int32, the number of set bits;
+ *      d_key [S,B] int64; d_atom_key [S,N_l] int64 (may be NULL), the atom's id after key_rounds rounds, 0 for an atom of no class.
+ *      A molecule of more than 512 atoms, or one whose offsets leave [0, N_l], gets n_bits = -1, words and key 0 and its atoms'
+ *      d_atom_key entries are not written (a binding refuses it).
+ *      td_fingerprint_similarity compares the molecules of each frame.  Included: d_include byte non-zero (NULL: all) and n_bits >= 0.
+ *      T(a, b) = (double)c / (double)(n_a + n_b - c), c = popcount(fp_a & fp_b); 0 when the union is empty.  d_sim_sum [S,B] float64:
+ *      the sum of T(a, b) over the included b != a, added in ascending b with one add per term (it does not depend on the grid), 0
+ *      for an a that is not included; d_sim_max [S,B] float64: the largest such T, 0 without a partner; d_first_equal [S,B] int32:
+ *      the smallest included b with key_b == key_a (a itself when none is earlier), -1 for an a that is not included; d_common
+ *      [S,B,B] int32 (may be NULL): c of every pair of the frame, whatever d_include says; with Q > 0 query fingerprints d_q_words
+ *      [Q,32] (made elsewhere by td_fingerprint), d_query_common [S,B,Q] int32: popcount(fp_a & q).  (Additions: TD_ABI_VERSION
+ *      stays 5.) */
+int td_fingerprint(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                   const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, int32_t radius, int32_t key_rounds,
+                   int64_t *d_fp_words, int32_t *d_n_bits, int64_t *d_key, int64_t *d_atom_key, void *stream);
+int td_fingerprint_similarity(const int64_t *d_fp_words, const int32_t *d_n_bits, const int64_t *d_key, int64_t S, int64_t B,
+                              const uint8_t *d_include, const int64_t *d_q_words, int64_t Q, double *d_sim_sum, double *d_sim_max,
+                              int32_t *d_first_equal, int32_t *d_common, int32_t *d_query_common, void *stream);
+
 /* ---- standalone EGNN refine net (replaces: models/egnn.py EGNN / EnBaseLayer as get_refine_net('egnn', config) builds
  *      it, models/molopt_score_model.py:34-42: num_r_gaussian = 1, kNN rebuilt per layer, SiLU, no LayerNorm, hidden 128,
  *      4 edge types, k = 32).  `host_weights`: per layer, in this order and as PyTorch stores them: edge_mlp.net.0.{weight

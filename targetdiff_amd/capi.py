@@ -91,6 +91,9 @@ SIGNATURES = {
                                _P]),
     'td_ring_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, POINTER(ctypes.c_uint8), _P, c_int64, _P, _P, _P,
                                  _P, _P, _P, _P, _P]),
+    'td_fingerprint': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), c_int32, c_int32, _P, _P, _P,
+                                 _P, _P]),
+    'td_fingerprint_similarity': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P, _P, _P, _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_center_pos': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int32, c_int32, _P]),
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
@@ -996,6 +999,86 @@ def ring_report(pos, v, ligand_ptr, class_z, class_aromatic=None, include=None, 
                                   _ptr(out['atom_ring']), _ptr(out['ring_hist']), _ptr(out['bond_ring']), _ptr(out['bond_category']),
                                   _stream(dev)), 'td_ring_report')
     out['ring_mask'] = mask.to(torch.int64) & 0xffffffff              # torch has no arithmetic on uint32: the word, widened
+    return out
+
+
+FP_BITS, FP_WORDS, FP_MAX_RADIUS, FP_MAX_ROUNDS = 2048, 32, 4, 16            # TD_FP_* (csrc/td_internal.h)
+
+
+def _fingerprint_inputs(pos, v, ligand_ptr, class_z, class_aromatic, radius, key_rounds, check=True):
+    """_bond_inputs plus the two round counts of a fingerprint call.  Returns (S, N_l, B, class table, aromatic flags, radius,
+    key_rounds)."""
+    radius, key_rounds = int(radius), int(key_rounds)
+    if not 0 <= radius <= FP_MAX_RADIUS or not radius <= key_rounds <= FP_MAX_ROUNDS:
+        raise ValueError(f'0 <= radius <= {FP_MAX_RADIUS} and radius <= key_rounds <= {FP_MAX_ROUNDS} (got {radius}, {key_rounds})')
+    S, Nl, B, cz, aro, _ = _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, None, (), check)
+    return S, Nl, B, cz, aro, radius, key_rounds
+
+
+def fingerprint(pos, v, ligand_ptr, class_z, class_aromatic=None, radius=2, key_rounds=8, return_atom_keys=False, check=True):
+    """Fingerprints of the bond graph of S frames of B molecules (td_fingerprint, include/targetdiff_hip.h); the pack and the class
+    table as bond_graph's.  This is not RDKit's RDKFingerprint: it is a circular, Morgan-style fingerprint over this project's bond
+    graph, whose orders come from the bond-length table; its similarities are comparable between runs of this tool, not with published
+    tables.  Returns a dict of device tensors: fp_words [S, B, 32] int64 (word w, bit k: fingerprint bit 64 w + k, after ``radius``
+    rounds), n_bits [S, B] int32, key [S, B] int64 (after ``key_rounds`` rounds) and atom_key [S, N_l] int64 (None without
+    ``return_atom_keys``; 0 for an atom of no class)."""
+    S, Nl, B, cz, aro, radius, key_rounds = _fingerprint_inputs(pos, v, ligand_ptr, class_z, class_aromatic, radius, key_rounds, check)
+    lib = load_library()
+    _ptr(pos, torch.float32, 'pos')                   # a CPU tensor is refused before anything is allocated
+    dev = pos.device
+    out = dict(fp_words=torch.empty(S, B, FP_WORDS, dtype=torch.int64, device=dev), n_bits=torch.empty(S, B, dtype=torch.int32, device=dev),
+               key=torch.empty(S, B, dtype=torch.int64, device=dev),
+               atom_key=torch.zeros(S, Nl, dtype=torch.int64, device=dev) if return_atom_keys else None)
+    with _on(dev):
+        _check(lib.td_fingerprint(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
+                                  S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _aromatic_arg(aro), radius, key_rounds,
+                                  _ptr(out['fp_words']), _ptr(out['n_bits']), _ptr(out['key']), _ptr(out['atom_key']), _stream(dev)),
+               'td_fingerprint')
+    return out
+
+
+def fingerprint_similarity(fp_words, n_bits, key, include=None, q_words=None, q_bits=None, return_common=False):
+    """The molecules of every frame compared (td_fingerprint_similarity): ``fp_words`` [S, B, 32] int64, ``n_bits`` [S, B] int32 and
+    ``key`` [S, B] int64 as fingerprint returns them, ``include`` [S, B] bool / uint8 or None; a query set ``q_words`` [Q, 32] int64 with
+    its ``q_bits`` [Q] int32 (one frame of another fingerprint call).  Returns a dict of device tensors: sim_sum and sim_max [S, B]
+    float64 (Tanimoto similarity to the other included molecules: summed in ascending order, and the largest), first_equal [S, B] int32
+    (the first included molecule with the same key, -1 when not included), common [S, B, B] int32 (None without ``return_common``),
+    and with a query set query_common [S, B, Q] int32 and query_sim [S, B, Q] float64 = c / (n_bits + q_bits - c), 0 for an empty
+    union (one float64 division per entry, formed by torch from the kernel's integers); both None without one."""
+    if fp_words.dim() != 3 or fp_words.shape[2] != FP_WORDS or fp_words.dtype != torch.int64:
+        raise ValueError(f'fp_words must be [S, B, {FP_WORDS}] int64 (got {tuple(fp_words.shape)} {fp_words.dtype})')
+    S, B = fp_words.shape[:2]
+    if tuple(n_bits.shape) != (S, B) or n_bits.dtype != torch.int32 or tuple(key.shape) != (S, B) or key.dtype != torch.int64:
+        raise ValueError(f'n_bits / key must be [{S}, {B}] int32 / int64')
+    if include is not None and (tuple(include.shape) != (S, B) or include.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError(f'include must be [{S}, {B}] bool or uint8')
+    Q = 0
+    if (q_words is None) != (q_bits is None):
+        raise ValueError('a query set is q_words and q_bits together')
+    if q_words is not None:
+        if q_words.dim() != 2 or q_words.shape[1] != FP_WORDS or q_words.dtype != torch.int64:
+            raise ValueError(f'q_words must be [Q, {FP_WORDS}] int64 (got {tuple(q_words.shape)} {q_words.dtype})')
+        Q = q_words.shape[0]
+        if tuple(q_bits.shape) != (Q,) or q_bits.dtype != torch.int32:
+            raise ValueError(f'q_bits must be [{Q}] int32')
+    lib = load_library()
+    _ptr(fp_words, torch.int64, 'fp_words')           # a CPU tensor is refused before anything is allocated
+    dev = fp_words.device
+    out = dict(sim_sum=torch.empty(S, B, dtype=torch.float64, device=dev), sim_max=torch.empty(S, B, dtype=torch.float64, device=dev),
+               first_equal=torch.empty(S, B, dtype=torch.int32, device=dev),
+               common=torch.empty(S, B, B, dtype=torch.int32, device=dev) if return_common else None,
+               query_common=torch.empty(S, B, Q, dtype=torch.int32, device=dev) if Q else None, query_sim=None)
+    if include is not None and include.dtype == torch.bool:
+        include = include.view(torch.uint8)
+    with _on(dev):
+        _check(lib.td_fingerprint_similarity(_ptr(fp_words), _ptr(n_bits, torch.int32, 'n_bits'), _ptr(key, torch.int64, 'key'), S, B,
+                                             _ptr(include, torch.uint8, 'include'), _ptr(q_words, torch.int64, 'q_words') if Q else None, Q,
+                                             _ptr(out['sim_sum']), _ptr(out['sim_max']), _ptr(out['first_equal']), _ptr(out['common']),
+                                             _ptr(out['query_common']), _stream(dev)), 'td_fingerprint_similarity')
+    if Q:
+        c = out['query_common'].to(torch.int64)
+        union = n_bits.to(torch.int64)[:, :, None] + q_bits.to(device=dev, dtype=torch.int64)[None, None, :] - c
+        out['query_sim'] = torch.where(union > 0, c.to(torch.float64) / union.clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev))
     return out
 
 

@@ -1,5 +1,5 @@
-// C ABI of libtargetdiff_hip.so: the bond graph of ligand frames and its rings (td_bond_graph, td_bond_list, td_ring_report).  See
-// include/targetdiff_hip.h for the contract.
+// C ABI of libtargetdiff_hip.so: the bond graph of ligand frames, its rings and its fingerprints (td_bond_graph, td_bond_list,
+// td_ring_report, td_fingerprint, td_fingerprint_similarity).  See include/targetdiff_hip.h for the contract.
 #include "td_device.h"
 #include "td_internal.h"
 
@@ -114,4 +114,54 @@ extern "C" int td_ring_report(const float *d_pos, const int64_t *d_v, const int3
     a.ring_mask = d_ring_mask; a.n_ring_bonds = d_n_ring_bonds; a.n_ring_atoms = d_n_ring_atoms; a.atom_ring = d_atom_ring;
     a.ring_hist = reinterpret_cast<unsigned long long *>(d_ring_hist); a.bond_ring = d_bond_ring; a.bond_category = d_bond_category;
     return td_launch_ring_report(a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int td_fingerprint(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                              const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, int32_t radius,
+                              int32_t key_rounds, int64_t *d_fp_words, int32_t *d_n_bits, int64_t *d_key, int64_t *d_atom_key,
+                              void *stream) {
+    const char *who = "td_fingerprint";
+    TdBondArgs a;
+    if (radius < 0 || radius > TD_FP_MAX_RADIUS || key_rounds < radius || key_rounds > TD_FP_MAX_ROUNDS) {
+        td_set_error("%s: 0 <= radius <= %d and radius <= key_rounds <= %d (got %d, %d)", who, TD_FP_MAX_RADIUS, TD_FP_MAX_ROUNDS, (int)radius,
+                     (int)key_rounds);
+        return TD_EINVAL;
+    }
+    if (const int rc = bond_pack(who, a, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic)) return rc;
+    if (S > 0 && B > 0 && (!d_fp_words || !d_n_bits || !d_key)) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    a.fp_radius = radius; a.fp_rounds = key_rounds;
+    a.fp_words = reinterpret_cast<unsigned long long *>(d_fp_words); a.fp_bits = d_n_bits;
+    a.fp_key = reinterpret_cast<unsigned long long *>(d_key); a.atom_key = reinterpret_cast<unsigned long long *>(d_atom_key);
+    return td_launch_fingerprint(a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int td_fingerprint_similarity(const int64_t *d_fp_words, const int32_t *d_n_bits, const int64_t *d_key, int64_t S, int64_t B,
+                                         const uint8_t *d_include, const int64_t *d_q_words, int64_t Q, double *d_sim_sum,
+                                         double *d_sim_max, int32_t *d_first_equal, int32_t *d_common, int32_t *d_query_common,
+                                         void *stream) {
+    const char *who = "td_fingerprint_similarity";
+    if (S < 0 || B < 0 || Q < 0 || S > 0x7fffffff || B > 0x7fffffff || Q > 0x7fffffff || S * B > 0x7fffffff) {
+        td_set_error("%s: bad argument (S = %lld, B = %lld, Q = %lld; S * B and Q must fit 31 bits)", who, (long long)S, (long long)B,
+                     (long long)Q);
+        return TD_EINVAL;
+    }
+    if (Q > 0 && (!d_q_words || (S > 0 && B > 0 && !d_query_common))) {
+        td_set_error("%s: a query set needs d_q_words and d_query_common", who);
+        return TD_EINVAL;
+    }
+    if (S > 0 && B > 0 && (!d_fp_words || !d_n_bits || !d_key || !d_sim_sum || !d_sim_max || !d_first_equal)) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    TdSimArgs a;
+    a.words = reinterpret_cast<const unsigned long long *>(d_fp_words); a.bits = d_n_bits;
+    a.key = reinterpret_cast<const unsigned long long *>(d_key); a.include = d_include;
+    a.q_words = reinterpret_cast<const unsigned long long *>(d_q_words);
+    a.S = (int)S; a.B = (int)B; a.Q = (int)Q;
+    a.sim_sum = d_sim_sum; a.sim_max = d_sim_max; a.first_equal = d_first_equal; a.common = d_common;
+    a.query_common = Q > 0 ? d_query_common : nullptr;
+    return td_launch_fingerprint_similarity(a, static_cast<hipStream_t>(stream));
 }

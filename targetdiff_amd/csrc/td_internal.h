@@ -427,7 +427,7 @@ struct TdQualityArgs {
 };
 int td_launch_quality(const TdQualityArgs &a, hipStream_t s);
 int td_element_index(int z);                 // quality_api.cpp: 0..7 (H C N O F P S Cl) of an atomic number, -1 for any other
-// bonds.hip, rings.hip (bond graph): the arguments of td_bond_graph / td_bond_list / td_ring_report over S
+// bonds.hip, rings.hip, fingerprint.hip (bond graph): the arguments of td_bond_graph / td_bond_list / td_ring_report / td_fingerprint over S
 // frames x B molecules.  elem and a profile's pe1 / pe2 as in TdQualityArgs; aromatic: bit c set when class c is aromatic; pcat: 0 = any category.  The launcher zeroes
 // hist on the stream before the kernels add to it.  Molecules of up to TD_BOND_SMALL_ATOMS atoms run in 128-lane workgroups, larger
 // ones (up to TD_BOND_MAX_ATOMS) in 512-lane workgroups: both grids cover every molecule and each workgroup takes only its own kind.
@@ -459,11 +459,34 @@ struct TdBondArgs {
     int32_t *atom_ring = nullptr;            // [S,N_l] or null
     unsigned long long *ring_hist = nullptr; // [S,TD_RING_BITS]
     uint16_t *bond_ring = nullptr;           // [capacity] or null
+    // fingerprint.hip (td_fingerprint, DESIGN.md section 3, "Fingerprints and diversity"): bits of the rounds 0 .. fp_radius, the key
+    // after fp_rounds >= fp_radius rounds
+    int fp_radius = 0, fp_rounds = 0;
+    unsigned long long *fp_words = nullptr;  // [S,B,TD_FP_WORDS]
+    int32_t *fp_bits = nullptr;              // [S,B]
+    unsigned long long *fp_key = nullptr;    // [S,B]
+    unsigned long long *atom_key = nullptr;  // [S,N_l] or null
 };
 constexpr int TD_RING_BITS = 32;
+constexpr int TD_FP_BITS = 2048, TD_FP_WORDS = TD_FP_BITS / 64, TD_FP_MAX_RADIUS = 4, TD_FP_MAX_ROUNDS = 16;
+// fingerprint.hip (td_fingerprint_similarity): the molecules of every frame against each other and against Q query fingerprints
+struct TdSimArgs {
+    const unsigned long long *words = nullptr;   // [S,B,TD_FP_WORDS]
+    const int32_t *bits = nullptr;               // [S,B]
+    const unsigned long long *key = nullptr;     // [S,B]
+    const uint8_t *include = nullptr;            // [S,B] or null: every molecule with a fingerprint
+    const unsigned long long *q_words = nullptr; // [Q,TD_FP_WORDS] or null
+    int S = 0, B = 0, Q = 0;
+    double *sim_sum = nullptr, *sim_max = nullptr;   // [S,B]
+    int32_t *first_equal = nullptr;              // [S,B]
+    int32_t *common = nullptr;                   // [S,B,B] or null
+    int32_t *query_common = nullptr;             // [S,B,Q] or null
+};
 int td_launch_bond_graph(const TdBondArgs &a, hipStream_t s);
 int td_launch_bond_list(const TdBondArgs &a, hipStream_t s);
 int td_launch_ring_report(const TdBondArgs &a, hipStream_t s);
+int td_launch_fingerprint(const TdBondArgs &a, hipStream_t s);
+int td_launch_fingerprint_similarity(const TdSimArgs &a, hipStream_t s);
 // egnn.hip / node.hip
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s);

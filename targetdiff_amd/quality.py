@@ -31,6 +31,17 @@ through it, per atom the smallest ring that holds it, per molecule the set of su
     rings = quality.sample_rings(result, eval_step='all')         # evaluate_diffusion.py's ring ratios (:26-32), per frame
     rings.ring_ratio(-1)    # {3: ..., 4: ..., ..., 9: ...}: the share of molecules that have a ring of that size
 
+and fingerprints of that graph (``td_fingerprint`` / ``td_fingerprint_similarity``, csrc/fingerprint.hip; DESIGN.md section 3,
+"Fingerprints and diversity"), for how different the samples of a pocket are from each other and how many are the same molecule twice:
+
+    fp = quality.fingerprints(pos, v, batch_ligand)               # fp.fp_words [S, B, 32], fp.n_bits, fp.key
+    div = quality.sample_diversity(result, reference_ligand=(ref_pos, ref_v))
+    div.summary()   # {'diversity': ..., 'uniqueness': ..., 'mean_nearest': ..., 'ref_sim_mean': ..., 'ref_sim_median': ..., 'ref_sim_max': ...}
+
+This is not RDKit's RDKFingerprint, which the reference's utils/evaluation/similarity.py uses: RDKit's is path-based with its own
+invariants.  This one is a circular, Morgan-style fingerprint over this project's bond graph, whose orders come from the bond-length
+table.  Its similarities are comparable between runs of this tool, not with published tables.
+
 OpenBabel's reconstruction, valence repair, QED / SA and docking need a chemistry toolkit and are not here.
 """
 from __future__ import annotations
@@ -541,3 +552,167 @@ def sample_rings(result, eval_step=-1, include='all', atom_enc_mode='add_aromati
     large = (r['ring_mask'].cpu().numpy() >> (RING_SIZES[-1] + 1)) != 0
     return RingReport(r['ring_hist'].cpu().numpy(), inc.sum(1), (large & inc).sum(1), np.where(inc, share, 0.0).sum(1),
                       (inc & (n[None] > 0)).sum(1), len(sizes))
+
+
+class Fingerprints:
+    """The fingerprints of S frames of B molecules (``fingerprints``).  Device tensors, frame axis first: ``fp_words`` [S, B, 32] int64
+    (word w, bit k: fingerprint bit 64 w + k of 2048), ``n_bits`` [S, B] int32 (the set bits), ``key`` [S, B] int64 (equal for molecules
+    that colour refinement does not tell apart), ``atom_key`` [S, N_l] int64 or None (an atom's id after the key's rounds: atoms of one
+    molecule with equal values are topologically alike; 0 for an atom of no class), ``ligand_ptr`` [B + 1]."""
+
+    def __init__(self, r, ligand_ptr, radius, key_rounds):
+        self.fp_words, self.n_bits, self.key, self.atom_key = r['fp_words'], r['n_bits'], r['key'], r['atom_key']
+        self.ligand_ptr, self.radius, self.key_rounds = ligand_ptr, int(radius), int(key_rounds)
+
+    def similarity(self, include=None, query=None, return_common=False):
+        """capi.fingerprint_similarity of these fingerprints: ``include`` [S, B] bool or None; ``query``: a one-frame ``Fingerprints``
+        whose molecules are the query set (the pocket's known ligand, a training set).  Returns its dict of device tensors."""
+        if include is not None:
+            include = torch.as_tensor(include).to(device=self.n_bits.device, dtype=torch.bool).reshape(self.n_bits.shape).contiguous()
+        qw = qb = None
+        if query is not None:
+            if query.fp_words.shape[0] != 1 or (query.radius, query.key_rounds) != (self.radius, self.key_rounds):
+                raise ValueError('the query set is one frame of fingerprints made with the same radius and key_rounds')
+            qw, qb = query.fp_words[0].contiguous(), query.n_bits[0].contiguous()
+        return capi.fingerprint_similarity(self.fp_words, self.n_bits, self.key, include, qw, qb, return_common)
+
+
+def fingerprints(pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic', radius=2, key_rounds=8, return_atom_keys=False,
+                 device=None):
+    """The fingerprint and the key of every molecule of one frame ``[N_l, 3]`` or of a stack ``[S, N_l, 3]`` (arguments as
+    ``bond_graph``), on exactly the bonds of ``bond_graph``.  Per atom an id from (atomic number, aromatic class, degree, valence),
+    refined ``radius`` times (0 .. 4) with the ids of the bonded atoms and the bonds' categories; every id of every round sets one of
+    2048 bits.  ``key``: a hash of the multiset of ids after ``key_rounds`` rounds (``radius`` .. 16): equal keys mean that
+    Weisfeiler-Lehman colour refinement with these invariants does not tell the molecules apart -- not a canonical form: the skeletons
+    of decalin and bicyclopentyl get equal keys.  This is not RDKit's RDKFingerprint: it is a circular, Morgan-style fingerprint over
+    this project's bond graph, whose orders come from the bond-length table; its similarities are comparable between runs of this tool,
+    not with published tables.  Molecules of more than 512 atoms are refused.  Returns a ``Fingerprints`` (the frame axis is kept)."""
+    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
+    r = capi.fingerprint(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode), radius, key_rounds,
+                         return_atom_keys)
+    return Fingerprints(r, ligand_ptr, radius, key_rounds)
+
+
+class DiversityReport:
+    """Per frame (axis 0): how different the included samples of a pocket are from each other, as sums over pockets.
+
+    Of one pocket with m included molecules: ``diversity`` = 1 - (sum of sim_sum) / (m (m - 1)), one minus the mean Tanimoto similarity
+    over the ordered pairs (nan for m < 2); ``uniqueness`` = distinct keys / m (nan for m = 0); ``mean_nearest`` = the mean of sim_max,
+    the similarity to the most similar other sample (nan for m < 2); with a reference ligand ``ref_sim_mean`` / ``ref_sim_median`` /
+    ``ref_sim_max`` of the similarity to it (nan for m = 0).  A merged report gives the mean over the pockets that have a value: the
+    convention of the reference's tables, which average a per-pocket number.  Kept for that: ``sum_diversity`` and ``n_diversity``
+    (pockets with m >= 2), ``sum_nearest``, ``sum_uniqueness`` and ``n_unique`` (pockets with m >= 1), ``sum_ref`` [S, 3] and
+    ``n_ref``; beside them the plain totals ``n_included``, ``n_distinct`` [S] and ``n_samples``.  The fingerprint is this project's
+    own (``fingerprints``), not RDKit's: the values compare between runs of this tool, not with published tables."""
+
+    def __init__(self, sum_diversity, n_diversity, sum_nearest, sum_uniqueness, n_unique, n_included, n_distinct, n_samples, sum_ref=None,
+                 n_ref=None):
+        f64, i64 = (lambda a: np.asarray(a, dtype=np.float64)), (lambda a: np.asarray(a, dtype=np.int64))
+        self.sum_diversity, self.n_diversity, self.sum_nearest = f64(sum_diversity), i64(n_diversity), f64(sum_nearest)
+        self.sum_uniqueness, self.n_unique = f64(sum_uniqueness), i64(n_unique)
+        self.n_included, self.n_distinct, self.n_samples = i64(n_included), i64(n_distinct), int(n_samples)
+        self.sum_ref = None if sum_ref is None else f64(sum_ref)
+        self.n_ref = None if n_ref is None else i64(n_ref)
+
+    @classmethod
+    def from_frames(cls, n_included, sum_sim, n_distinct, sum_max, n_samples, ref_sim=None, included=None):
+        """One pocket: ``n_included`` (m), the sums of sim_sum and sim_max over the included molecules and the number of distinct
+        keys, each [S]; ``ref_sim`` [S, B] with ``included`` [S, B]: the similarity of every molecule to the reference ligand."""
+        m = np.asarray(n_included, dtype=np.int64)
+        mf = m.astype(np.float64)
+        two, one = m >= 2, m >= 1
+        safe = lambda den: np.where(den > 0, den, 1.0)
+        diversity = np.where(two, 1.0 - np.asarray(sum_sim, dtype=np.float64) / safe(mf * (mf - 1.0)), 0.0)
+        nearest = np.where(two, np.asarray(sum_max, dtype=np.float64) / safe(mf), 0.0)
+        unique = np.where(one, np.asarray(n_distinct, dtype=np.float64) / safe(mf), 0.0)
+        sum_ref = n_ref = None
+        if ref_sim is not None:
+            ref_sim, included = np.asarray(ref_sim, dtype=np.float64), np.asarray(included, dtype=bool)
+            sum_ref = np.zeros((len(m), 3))
+            for s in range(len(m)):
+                x = ref_sim[s][included[s]]
+                if x.size:
+                    sum_ref[s] = (x.sum() / x.size, np.median(x), x.max())
+            n_ref = one.astype(np.int64)
+        return cls(diversity, two.astype(np.int64), nearest, unique, one.astype(np.int64), m, n_distinct, n_samples, sum_ref, n_ref)
+
+    @classmethod
+    def merged(cls, reports):
+        """Several pockets together: every sum added, frame by frame, so that each value becomes the mean of the pockets' values."""
+        reports = list(reports)
+        first = reports[0]
+        if any(r.sum_diversity.shape != first.sum_diversity.shape or (r.sum_ref is None) != (first.sum_ref is None) for r in reports):
+            raise ValueError('reports of different frame counts, or with and without a reference ligand, do not merge')
+        tot = lambda name: sum(getattr(r, name) for r in reports)
+        return cls(tot('sum_diversity'), tot('n_diversity'), tot('sum_nearest'), tot('sum_uniqueness'), tot('n_unique'), tot('n_included'),
+                   tot('n_distinct'), tot('n_samples'), None if first.sum_ref is None else tot('sum_ref'),
+                   None if first.sum_ref is None else tot('n_ref'))
+
+    @property
+    def num_frames(self):
+        return self.sum_diversity.shape[0]
+
+    @staticmethod
+    def _mean(total, count):
+        return float(total) / int(count) if int(count) else float('nan')
+
+    def diversity(self, frame=-1):
+        return self._mean(self.sum_diversity[frame], self.n_diversity[frame])
+
+    def mean_nearest(self, frame=-1):
+        return self._mean(self.sum_nearest[frame], self.n_diversity[frame])
+
+    def uniqueness(self, frame=-1):
+        return self._mean(self.sum_uniqueness[frame], self.n_unique[frame])
+
+    def reference_similarity(self, frame=-1):
+        """{'ref_sim_mean', 'ref_sim_median', 'ref_sim_max'} or {} without a reference ligand"""
+        if self.sum_ref is None:
+            return {}
+        return {k: self._mean(self.sum_ref[frame, c], self.n_ref[frame]) for c, k in enumerate(('ref_sim_mean', 'ref_sim_median', 'ref_sim_max'))}
+
+    def summary(self, frame=-1):
+        return dict(diversity=self.diversity(frame), uniqueness=self.uniqueness(frame), mean_nearest=self.mean_nearest(frame),
+                    **self.reference_similarity(frame))
+
+
+def _include_mask(include, pos, v, ptr, cz, aro, S, B):
+    """``include`` of sample_rings / sample_diversity as a device mask or None, and whether the pack was already looked at"""
+    if isinstance(include, str):
+        if include not in ('all', 'complete'):
+            raise ValueError("include is 'all', 'complete' or a mask [frames, samples]")
+        return (capi.bond_graph(pos, v, ptr, cz, aro)['n_fragments'] == 1, True) if include == 'complete' else (None, False)
+    return torch.as_tensor(np.asarray(include)).to(device=pos.device, dtype=torch.bool).reshape(S, B).contiguous(), False
+
+
+def sample_diversity(result, eval_step=-1, include='all', radius=2, key_rounds=8, reference_ligand=None, atom_enc_mode='add_aromatic',
+                     device='cuda'):
+    """Diversity of the samples of one pocket (``result``, ``eval_step`` and the packing as ``sample_quality``): per frame one minus the
+    mean pairwise Tanimoto similarity of the samples' fingerprints, the share of distinct keys (uniqueness) and the mean similarity to
+    the nearest other sample.  ``include``: the molecules that are compared, as ``sample_rings``: ``'all'`` (default), ``'complete'``
+    (one fragment in that frame; the bond graph runs first and its flags are the mask) or a bool array [frames, samples].
+    ``reference_ligand``: ``(pos [n, 3], v [n])`` of a known ligand, fingerprinted through the same kernel: the report then also holds
+    the mean, median and largest similarity of the included samples to it (the reference's tanimoto_sim_N_to_1).  ``radius`` and
+    ``key_rounds`` as ``fingerprints``.  Two launches (three with ``'complete'``).  The fingerprint is this project's own, not RDKit's:
+    the numbers compare between runs of this tool, not with published tables.  Returns a ``DiversityReport``."""
+    pos, v, ptr, sizes, S = _pack_result(result, eval_step, device)
+    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
+    mask, seen = _include_mask(include, pos, v, ptr, cz, aro, S, len(sizes))
+    fp = capi.fingerprint(pos, v, ptr, cz, aro, radius, key_rounds, False, check=not seen)
+    qw = qb = None
+    if reference_ligand is not None:
+        rpos, rv = reference_ligand
+        rpos, rv, rptr = _pack(rpos, rv, None, torch.tensor([0, len(rv)], dtype=torch.int32), pos.device)
+        if rpos.shape[0] != 1:
+            raise ValueError('the reference ligand is one molecule: pos [n, 3], v [n]')
+        q = capi.fingerprint(rpos, rv, rptr, cz, aro, radius, key_rounds, False)
+        qw, qb = q['fp_words'][0].contiguous(), q['n_bits'][0].contiguous()
+    r = capi.fingerprint_similarity(fp['fp_words'], fp['n_bits'], fp['key'], mask, qw, qb, False)
+    inc = fp['n_bits'].cpu().numpy() >= 0
+    if mask is not None:
+        inc &= mask.cpu().numpy().astype(bool)
+    first = r['first_equal'].cpu().numpy()
+    distinct = (first == np.arange(len(sizes))[None]) & inc
+    return DiversityReport.from_frames(inc.sum(1), np.where(inc, r['sim_sum'].cpu().numpy(), 0.0).sum(1), distinct.sum(1),
+                                       np.where(inc, r['sim_max'].cpu().numpy(), 0.0).sum(1), len(sizes),
+                                       None if qw is None else r['query_sim'][:, :, 0].cpu().numpy(), inc)

@@ -11,9 +11,16 @@ that bond graph, ``complete``, ``mean_fragments``, ``mean_largest_share`` and th
 distances (``JSD_6-6|1`` ...; ``--reference_npz`` may carry them as ``bond_types`` [8, 3] and ``bond_distributions`` [8, bins]).
 ``--rings`` adds the reference's ring ratios (evaluate_diffusion.py print_ring_ratio, ``ring size: k ratio: x.xxx`` for k = 3 .. 9)
 from the ring sizes of quality.sample_rings -- the smallest cycle through some bond, not a toolkit's ring set -- over ``--include
-all`` or ``complete`` samples, and the shares of molecules without a ring and with a ring of more than 9 atoms.  The Jensen-Shannon distances need the reference's empirical distributions: they are
+all`` or ``complete`` samples, and the shares of molecules without a ring and with a ring of more than 9 atoms.  ``--diversity`` adds
+``diversity`` (one minus the mean pairwise Tanimoto similarity of a pocket's samples, averaged over the pockets as the reference's
+tables do), ``uniqueness`` (distinct molecules / samples) and ``mean_nearest`` from quality.sample_diversity, over ``--include all`` or
+``complete`` samples, and with a known ligand -- ``--reference_sdf FILE`` (the first record, heavy atoms, elements of the table) or
+arrays ``ligand_pos`` [n, 3] and ``ligand_v`` [n] in ``--reference_npz`` -- the mean, median and largest similarity of the samples to
+it.  The fingerprint is this project's own circular one over its bond graph, not RDKit's RDKFingerprint: the numbers compare between
+runs of this tool, not with published tables.  The Jensen-Shannon distances need the reference's empirical distributions: they are
 loaded from ``utils.evaluation`` when the tool runs inside the reference repository (or with it on PYTHONPATH), or from
-``--reference_npz FILE`` with arrays CC_2A, All_12A and atom_type; without them the three lines print None.
+``--reference_npz FILE`` with arrays CC_2A, All_12A and atom_type (a file that holds a reference ligand may leave them out); without
+them the three lines print None.
 
 Writes ``DIR/eval_results/quality.json``: the numbers above, the raw histograms and element counts, and with ``--eval_step all`` the
 per-frame curve (``curve``: one entry per frame of the trajectory).  With seeded random weights the numbers say nothing about chemistry.
@@ -31,7 +38,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from targetdiff_amd import quality  # noqa: E402
+from targetdiff_amd import molfile, quality  # noqa: E402
 
 
 def result_files(sample_path, eval_num_examples=None):
@@ -56,22 +63,33 @@ def main(argv=None):
     ap.add_argument('--include', type=str, default='all', choices=['all', 'stable', 'complete'])
     ap.add_argument('--connectivity', action='store_true', help='also the bond graph: complete fraction, fragments, bond-length profiles')
     ap.add_argument('--rings', action='store_true', help='also the ring ratios: the share of molecules with a ring of 3 .. 9 atoms')
+    ap.add_argument('--diversity', action='store_true', help='also diversity, uniqueness and the similarity to a reference ligand '
+                    "(this project's circular fingerprint, not RDKit's)")
+    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity: a known ligand, the first V2000 record of FILE')
     ap.add_argument('--reference_npz', type=str, default=None)
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
     eval_step = 'all' if args.eval_step == 'all' else int(args.eval_step)
 
-    reference = bond_reference = None
+    reference = bond_reference = reference_ligand = None
+    if args.reference_sdf is not None:
+        mol = molfile.read_sdf(args.reference_sdf)[0]
+        reference_ligand = molfile.ligand_classes(mol, args.atom_enc_mode, drop_unknown=True)
+        if len(reference_ligand[1]) != len(mol['symbols']):
+            print(f"reference ligand: {len(mol['symbols']) - len(reference_ligand[1])} atoms of elements outside the table left out")
     if args.reference_npz is not None:
         with np.load(args.reference_npz) as z:
-            reference = {k: z[k] for k in ('CC_2A', 'All_12A', 'atom_type')}
+            if 'ligand_pos' in z.files and reference_ligand is None:
+                reference_ligand = (z['ligand_pos'].astype(np.float32), z['ligand_v'].astype(np.int64))
+            if 'CC_2A' in z.files or 'ligand_pos' not in z.files:
+                reference = {k: z[k] for k in ('CC_2A', 'All_12A', 'atom_type')}
             if 'bond_types' in z.files:
                 bond_reference = {tuple(int(x) for x in t): d for t, d in zip(z['bond_types'], z['bond_distributions'])}
     files = result_files(args.sample_path, args.eval_num_examples)
     if not files:
         raise SystemExit(f'no result_*.pt under {args.sample_path}')
     print(f'Load generated data done! {len(files)} examples in total.')
-    reports, connectivity, rings = [], [], []
+    reports, connectivity, rings, diversity = [], [], [], []
     for name in files:
         r = torch.load(name, map_location='cpu', weights_only=False)
         if args.connectivity:
@@ -80,6 +98,9 @@ def main(argv=None):
         if args.rings:
             rings.append(quality.sample_rings(r, eval_step, 'complete' if args.include == 'complete' else 'all', args.atom_enc_mode,
                                               device=args.device))
+        if args.diversity:
+            diversity.append(quality.sample_diversity(r, eval_step, 'complete' if args.include == 'complete' else 'all',
+                                                      reference_ligand=reference_ligand, atom_enc_mode=args.atom_enc_mode, device=args.device))
         reports.append(quality.sample_quality(r, eval_step, args.include, args.atom_enc_mode, reference, device=args.device))
     rep = quality.QualityReport.merged(reports)
     print(f'Evaluate done! {rep.n_samples} samples in total.')
@@ -115,6 +136,14 @@ def main(argv=None):
         out['rings'] = dict(ring.summary(-1), ring_hist=ring.ring_hist[-1].tolist(), num_included=int(ring.n_included[-1]))
         if eval_step == 'all':
             out['rings']['curve'] = [ring.summary(s) for s in range(ring.num_frames)]
+    if args.diversity:
+        div = quality.DiversityReport.merged(diversity)
+        nan_none = lambda d: {k: (None if x != x else x) for k, x in d.items()}
+        last_div = nan_none(div.summary(-1))
+        print_dict(last_div)
+        out['diversity'] = dict(last_div, num_included=int(div.n_included[-1]), num_distinct=int(div.n_distinct[-1]))
+        if eval_step == 'all':
+            out['diversity']['curve'] = [nan_none(div.summary(s)) for s in range(div.num_frames)]
     result_path = os.path.join(args.sample_path, 'eval_results')
     os.makedirs(result_path, exist_ok=True)
     with open(os.path.join(result_path, 'quality.json'), 'w') as f:

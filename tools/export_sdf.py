@@ -1,6 +1,7 @@
 """Sampled ligands as SD files, without a chemistry toolkit:
 
     python tools/export_sdf.py --sample_path DIR --out DIR [--eval_step -1] [--only-complete] [--largest-fragment] [--ring-aromatic]
+                                [--unique]
 
 Reads the ``result_{i}.pt`` files a sampling driver wrote (sorted as tools/evaluate_samples.py sorts them), takes the frame
 ``--eval_step`` of every sample (default -1: the final poses), builds the bond graph on the GPU (quality.bond_graph: bonds from the
@@ -10,6 +11,10 @@ order 1 or 2; DESIGN.md section 3, "Bond graph" -- a convention, not perceived c
 ``--ring-aromatic`` writes the ring-aware category instead (quality.bond_graph(rings=True); DESIGN.md section 3, "Rings"): type 4 only
 for a bond that also lies in a ring of 5 or 6 atoms, its order otherwise, so no atom outside a ring carries an aromatic bond.
 ``--only-complete`` writes only the samples that are one fragment; ``--largest-fragment`` writes of every sample its largest fragment.
+``--unique`` writes, of the samples with equal keys (quality.fingerprints: not told apart by colour refinement of the bond graph;
+DESIGN.md section 3, "Fingerprints and diversity"), only the first.  It applies after ``--only-complete`` has chosen the samples, and
+the keys are of the whole molecule, also under ``--largest-fragment``: two samples whose largest fragments agree and whose small
+fragments differ are both written.
 Prints one line per file and returns the counts.
 """
 from __future__ import annotations
@@ -18,6 +23,7 @@ import argparse
 import os
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,6 +43,8 @@ def main(argv=None):
     ap.add_argument('--only-complete', action='store_true')
     ap.add_argument('--largest-fragment', action='store_true')
     ap.add_argument('--ring-aromatic', action='store_true', help='bond type 4 only inside a ring of 5 or 6 atoms')
+    ap.add_argument('--unique', action='store_true', help='of the samples with equal keys only the first; the keys are of the whole '
+                    'molecule (also with --largest-fragment), taken after --only-complete')
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
     files = result_files(args.sample_path, args.eval_num_examples)
@@ -49,8 +57,14 @@ def main(argv=None):
         pos, v, ptr, sizes, _ = quality._pack_result(r, args.eval_step, args.device)
         g = quality.bond_graph(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, bond_profiles=(), return_fragments=True,
                                return_bonds=True, rings=args.ring_aromatic, device=args.device)
+        select = None
+        if args.unique:
+            fp = quality.fingerprints(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, device=args.device)
+            chosen = g.complete[0] if args.only_complete else None
+            first = fp.similarity(include=None if chosen is None else chosen[None])['first_equal'][0].cpu().numpy()
+            select = first == np.arange(len(sizes))
         mols = molfile.molecules_from_graph(g, pos, v, args.atom_enc_mode, 0, args.only_complete, args.largest_fragment,
-                                            categories=g.ring_category if args.ring_aromatic else None)
+                                            categories=g.ring_category if args.ring_aromatic else None, select=select)
         stem = os.path.basename(name)[:-3]
         path = os.path.join(args.out, stem + '.sdf')
         n = molfile.write_sdf(path, mols)

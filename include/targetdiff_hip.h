@@ -510,6 +510,34 @@ int td_likelihood_prior(const td_model *m, const int32_t *d_ligand_ptr, int64_t 
 int td_embed_ligand(const td_model *m, const int64_t *d_ligand_v, int64_t N_l, float *d_h, void *stream);
 int td_v_inference(const td_model *m, const float *d_h, int64_t n, float *d_logits, void *stream);
 
+/* ---- diffusion loss and validation, forward only (replaces: the arithmetic of ScorePosNet3D.get_diffusion_loss after the network
+ *      call, models/molopt_score_model.py:521-563, and get_auroc of scripts/train_diffusion.py:22-36).  No gradient is formed.
+ *      td_diffusion_loss: a ragged pack of B graphs, one wave per graph.  d_t [B] int32 (clamped to [0, T - 1] as td_likelihood_terms
+ *      does), d_ligand_ptr [B+1], d_pos_0 the centred x0, d_pos_t / d_v_t the perturbed state (td_perturb), d_noise the draw x_t was
+ *      made from (may be NULL for model_mean_type 'C0', where it is not read), d_pred_pos [N_l,3] / d_pred_v [N_l,C] the network's
+ *      outputs.  Per atom: d_pred_pos_noise [N_l,3] = pred_pos - pos_t (:522), d_v_recon [N_l,C] = softmax(pred_v) (:562).  Per
+ *      graph: d_loss_pos_graph [B] = mean over the graph's atoms of sum_d (pred - target)^2 (:536-542; 'C0': pred_pos against
+ *      pos_0, 'noise': pred_pos_noise against d_noise), d_loss_v_graph [B] = compute_v_Lt (:476-483): posterior KL for t > 0,
+ *      decoder NLL at t == 0 -- bit for bit td_likelihood_terms' d_kl_v of the same inputs (one body serves both kernels: the
+ *      macro TD_TYPE_TERM of csrc/td_type_term.h, a macro so that td_likelihood_terms' own compiled code did not change).  An
+ *      empty graph counts as one atom in the mean and gives 0.  d_scalars [3] = mean_g loss_pos_graph, mean_g loss_v_graph,
+ *      loss_pos + loss_v_weight * loss_v (product and sum rounded one by one, :552), taken by a second stage of one workgroup in
+ *      a fixed order over g: no float atomics, nothing depends on the grid or on the order of arrival.  B == 0: the scalars are
+ *      NaN (the mean of nothing).  TD_EINVAL: more than TD_MAXC = 16 classes, d_noise NULL with model_mean_type 'noise', a model
+ *      created without alphas_cumprod (8 or 10 schedule arrays, what td_perturb needs), negative sizes.
+ *      td_auroc: d_scores [N,C] fp32, d_labels [N] int64, no model handle.  Per class c: d_n_pos[c] = #{i: label_i = c} and
+ *      d_pairs2[c] = 2 #{(i, j): label_i = c, label_j != c, s_ic > s_jc} + #{(i, j): ..., s_ic == s_jc}, both [C] int64, so that
+ *      the one-vs-rest AUROC of class c is pairs2 / (2 n_pos (N - n_pos)).  fp32 values are compared as they are (a NaN compares
+ *      false both ways: a binding refuses it); a label outside [0, C) is in no class (a binding refuses it too).  Integer sums:
+ *      exact and independent of the order.  TD_EINVAL for N < 0, N > 2^20 (pairs2 stays below 2^41), C < 1 or C > 16.
+ *      (Additions: TD_ABI_VERSION stays 5.) */
+int td_diffusion_loss(const td_model *m, const int32_t *d_t, const int32_t *d_ligand_ptr, int64_t N_l, int64_t B,
+                      const float *d_pos_0, const float *d_pos_t, const float *d_noise, const int64_t *d_v_0, const int64_t *d_v_t,
+                      const float *d_pred_pos, const float *d_pred_v, float loss_v_weight, float *d_pred_pos_noise,
+                      float *d_v_recon, float *d_loss_pos_graph, float *d_loss_v_graph, float *d_scalars, void *stream);
+int td_auroc(const float *d_scores, const int64_t *d_labels, int64_t N, int32_t C, int64_t *d_n_pos, int64_t *d_pairs2,
+             void *stream);
+
 /* ---- centring (replaces: center_pos(mode='protein'), models/molopt_score_model.py:110-120).
  *      offset [B,3] = per-graph protein centroid; positions are shifted in place by -offset (sign = -1)
  *      or +offset (sign = +1, models/molopt_score_model.py:691,695).  d_protein_pos may be NULL to

@@ -99,6 +99,8 @@ SIGNATURES = {
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
     'td_likelihood_terms': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_likelihood_prior': (c_int32, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
+    'td_diffusion_loss': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P, _P, _P]),
+    'td_auroc': (c_int32, [_P, _P, c_int64, c_int32, _P, _P, _P]),
     'td_embed_ligand': (c_int32, [_P, _P, c_int64, _P, _P]),
     'td_v_inference': (c_int32, [_P, _P, c_int64, _P, _P]),
     'td_egnn_num_weights': (ctypes.c_size_t, [c_int32]),
@@ -552,6 +554,39 @@ class NativeModel:
         return kl_pos, kl_v
 
     @_device_bound
+    def diffusion_loss(self, t, ligand_ptr, pos_0, pos_t, noise, v_0, v_t, pred_pos, pred_v, loss_v_weight, check=True):
+        """The arithmetic of get_diffusion_loss after the network call (td_diffusion_loss; models/molopt_score_model.py:521-563), forward
+        only.  ``noise`` may be None for model_mean_type 'C0'.  Returns a dict: 'loss_pos', 'loss_v', 'loss' (0-d views of one [3] tensor),
+        'loss_pos_graph', 'loss_v_graph' [B], 'pred_pos_noise' [N_l, 3], 'ligand_v_recon' [N_l, C].  ``check`` looks at ``ligand_ptr`` on
+        the host (one synchronisation): it must be ascending prefix offsets from 0 to N_l, since the kernel reads the atoms it names."""
+        Nl, B, C = pos_0.shape[0], ligand_ptr.numel() - 1, self.num_classes
+        dev = pos_0.device
+        if tuple(pred_v.shape) != (Nl, C) or tuple(pred_pos.shape) != (Nl, 3) or tuple(pos_t.shape) != (Nl, 3) or t.numel() != B:
+            raise ValueError(f'diffusion_loss: shapes do not fit {Nl} atoms, {B} graphs, {C} classes')
+        if noise is not None and tuple(noise.shape) != (Nl, 3):
+            raise ValueError(f'noise must be [{Nl}, 3] (got {tuple(noise.shape)})')
+        if tuple(pos_0.shape) != (Nl, 3) or tuple(v_0.shape) != (Nl,) or tuple(v_t.shape) != (Nl,):
+            raise ValueError(f'diffusion_loss: pos_0 must be [{Nl}, 3] and v_0 / v_t [{Nl}] (got {tuple(pos_0.shape)}, {tuple(v_0.shape)}, '
+                             f'{tuple(v_t.shape)})')
+        if check and B >= 0:
+            p = ligand_ptr.tolist()
+            if not p or p[0] != 0 or p[-1] != Nl or any(b < a for a, b in zip(p, p[1:])):
+                raise ValueError(f'diffusion_loss: ligand_ptr must be ascending prefix offsets from 0 to N_l = {Nl}')
+        eps = torch.empty(Nl, 3, dtype=torch.float32, device=dev)
+        recon = torch.empty(Nl, C, dtype=torch.float32, device=dev)
+        lp_g = torch.empty(B, dtype=torch.float32, device=dev)
+        lv_g = torch.empty(B, dtype=torch.float32, device=dev)
+        scalars = torch.empty(3, dtype=torch.float32, device=dev)
+        _check(self.lib.td_diffusion_loss(
+            self.handle, _ptr(t, torch.int32, 't'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), Nl, B,
+            _ptr(pos_0, torch.float32, 'pos_0'), _ptr(pos_t, torch.float32, 'pos_t'), _ptr(noise, torch.float32, 'noise'),
+            _ptr(v_0, torch.int64, 'v_0'), _ptr(v_t, torch.int64, 'v_t'), _ptr(pred_pos, torch.float32, 'pred_pos'),
+            _ptr(pred_v, torch.float32, 'pred_v'), float(loss_v_weight), _ptr(eps), _ptr(recon), _ptr(lp_g), _ptr(lv_g), _ptr(scalars),
+            _stream(self.device)), 'td_diffusion_loss')
+        return {'loss_pos': scalars[0], 'loss_v': scalars[1], 'loss': scalars[2], 'loss_pos_graph': lp_g, 'loss_v_graph': lv_g,
+                'pred_pos_noise': eps, 'ligand_v_recon': recon}
+
+    @_device_bound
     def embed_ligand(self, ligand_v):
         h = torch.empty(ligand_v.shape[0], HIDDEN, dtype=torch.float32, device=ligand_v.device)
         _check(self.lib.td_embed_ligand(self.handle, _ptr(ligand_v, torch.int64, 'ligand_v'), ligand_v.shape[0], _ptr(h),
@@ -587,6 +622,58 @@ class NativeModel:
         _check(self.lib.td_debug_node_stage(self.handle, layer, stage, _ptr(h, torch.float32, 'h'), N, _ptr(P), _ptr(q),
                                             _stream(self.device)), 'td_debug_node_stage')
         return P, q
+
+
+AUROC_MAX_ROWS = 1 << 20      # td_auroc: pairs2 stays below 2^41
+
+
+def auroc_counts(scores, labels):
+    """``n_pos`` [C] and ``pairs2`` [C] int64 of td_auroc (include/targetdiff_hip.h) for ``scores`` [N, C] fp32 and ``labels`` [N] int64
+    on a HIP device: per class the positives, and 2 #{pos > neg} + #{pos == neg} over its (positive, negative) pairs.  Raises ValueError
+    for a NaN score or a label outside [0, C)."""
+    if scores.dim() != 2 or labels.dim() != 1 or labels.shape[0] != scores.shape[0]:
+        raise ValueError(f'auroc: scores [N, C] and labels [N] (got {tuple(scores.shape)}, {tuple(labels.shape)})')
+    N, C = scores.shape
+    if N > AUROC_MAX_ROWS:
+        raise ValueError(f'auroc: {N} rows, the counts are built for at most {AUROC_MAX_ROWS}')
+    if N and bool(torch.isnan(scores).any()):
+        raise ValueError('auroc: a score is NaN')
+    if N and bool(((labels < 0) | (labels >= C)).any()):
+        raise ValueError(f'auroc: labels must be in [0, {C})')
+    lib = load_library()
+    dev = scores.device
+    n_pos = torch.empty(C, dtype=torch.int64, device=dev)
+    pairs2 = torch.empty(C, dtype=torch.int64, device=dev)
+    with _on(dev):
+        _check(lib.td_auroc(_ptr(scores, torch.float32, 'scores'), _ptr(labels, torch.int64, 'labels'), N, C, _ptr(n_pos), _ptr(pairs2),
+                            _stream(dev)), 'td_auroc')
+    return n_pos, pairs2
+
+
+def auroc_from_counts(n_pos, pairs2):
+    """get_auroc's numbers (scripts/train_diffusion.py:22-36) from td_auroc's counts, in float64: ``(weighted average, {class: auroc})``
+    over the classes present; raises ValueError where a class holds every row (sklearn's roc_auc_score raises there as well)."""
+    n_pos = [int(x) for x in n_pos]
+    pairs2 = [int(x) for x in pairs2]
+    N = sum(n_pos)
+    per_class, avg = {}, 0.0
+    for c, (n, p2) in enumerate(zip(n_pos, pairs2)):
+        if n == 0:
+            continue                                            # possible_classes = set(y_true)
+        if N - n == 0:
+            raise ValueError(f'auroc: class {c} holds every row; the one-vs-rest ROC is not defined with one class present')
+        per_class[c] = float(np.float64(p2) / (2.0 * np.float64(n) * np.float64(N - n)))
+        avg += per_class[c] * n
+    if N == 0:
+        raise ValueError('auroc: no rows')
+    return avg / N, per_class
+
+
+def auroc(scores, labels):
+    """Atom-type AUROC of get_auroc (scripts/train_diffusion.py:22-36): ``(weighted average, {class: auroc})``; the N^2 comparisons run
+    in td_auroc on the device as exact integers, the divisions here in float64."""
+    n_pos, pairs2 = auroc_counts(scores, labels)
+    return auroc_from_counts(n_pos.tolist(), pairs2.tolist())
 
 
 class NativeSession:

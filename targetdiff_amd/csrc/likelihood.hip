@@ -6,35 +6,9 @@
 // One wave per graph for the reductions (scatter_mean over a graph's ligand atoms): deterministic, no atomics.
 #include "td_device.h"
 #include "td_internal.h"
+#include "td_type_term.h"
 
 namespace {
-
-// q(v_{t-1} | v_t, v_0) in log space (:401-409) for one atom; log_v0 / out: [C] registers
-__device__ __forceinline__ void lk_q_v_posterior(const TdSchedules &sc, int t, int C, const float (&log_v0)[TD_MAXC],
-                                                 int vt, float (&out)[TD_MAXC]) {
-    const int tm1 = t - 1 < 0 ? 0 : t - 1;
-    const float lnK = logf((float)C);
-    const float l_ca = sc.log_ca[tm1], l_1mca = sc.log_1mca[tm1] - lnK;
-    const float l_a = sc.log_a[t], l_1ma = sc.log_1ma[t] - lnK;
-    const float LOG_EPS = logf(1e-30f);
-    float mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < TD_MAXC; ++c) {
-        if (c < C) {
-            const float lvt = c == vt ? 0.f : LOG_EPS;
-            out[c] = td_log_add_exp(log_v0[c] + l_ca, l_1mca) + td_log_add_exp(lvt + l_a, l_1ma);
-            mx = fmaxf(mx, out[c]);
-        } else {
-            out[c] = -INFINITY;
-        }
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < TD_MAXC; ++c) s += c < C ? expf(out[c] - mx) : 0.f;
-    const float lse = mx + logf(s);
-#pragma unroll
-    for (int c = 0; c < TD_MAXC; ++c) out[c] -= lse;
-}
 
 __global__ void perturb_kernel(TdSchedules sc, int T, const int32_t *__restrict__ tg, const int32_t *__restrict__ lptr,
                                int64_t Nl, int B, int C, const float *__restrict__ pos, const int64_t *__restrict__ v,
@@ -97,34 +71,7 @@ __global__ __launch_bounds__(64) void likelihood_terms_kernel(TdSchedules sc, in
         kl = kl / 0.69314718055994531f;
         acc_pos += decoder ? -nll : kl;
         // ---- types
-        float lg[TD_MAXC], lv0[TD_MAXC], pm[TD_MAXC], pt[TD_MAXC];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < TD_MAXC; ++c) {
-            lg[c] = c < C ? pred_v[(int64_t)at * C + c] : -INFINITY;
-            mx = fmaxf(mx, lg[c]);
-        }
-        float se = 0.f;
-#pragma unroll
-        for (int c = 0; c < TD_MAXC; ++c) se += c < C ? expf(lg[c] - mx) : 0.f;
-        const float lse = mx + logf(se);
-        const int a0 = (int)v0[at], at_t = (int)vt[at];
-#pragma unroll
-        for (int c = 0; c < TD_MAXC; ++c) {
-            lg[c] = lg[c] - lse;                                        // log_softmax(pred_v)
-            lv0[c] = c == a0 ? 0.f : LOG_EPS;                           // index_to_log_onehot(v0)
-        }
-        lk_q_v_posterior(sc, t, C, lg, at_t, pm);                       // model posterior
-        lk_q_v_posterior(sc, t, C, lv0, at_t, pt);                      // true posterior
-        float klv = 0.f, nllv = 0.f;
-#pragma unroll
-        for (int c = 0; c < TD_MAXC; ++c) {
-            if (c < C) {
-                klv += expf(pt[c]) * (pt[c] - pm[c]);                   // categorical_kl(true, model)
-                nllv += expf(lv0[c]) * pm[c];                           // log_categorical(log_v0, model)
-            }
-        }
-        acc_v += decoder ? -nllv : klv;
+        TD_TYPE_TERM(acc_v, sc, t, C, decoder, LOG_EPS, pred_v, v0, vt, at);
     }
     acc_pos = td_sum64(acc_pos);
     acc_v = td_sum64(acc_v);

@@ -12,6 +12,8 @@ Seams mirrored (reference file:line):
   ScorePosNet3D.__init__            models/molopt_score_model.py:194-311
   ScorePosNet3D.forward             models/molopt_score_model.py:313-368
   ScorePosNet3D.sample_diffusion    models/molopt_score_model.py:633-703
+  ScorePosNet3D.sample_time         models/molopt_score_model.py:440-462
+  ScorePosNet3D.get_diffusion_loss  models/molopt_score_model.py:485-563  (forward only: no gradient)
   get_refine_net                    models/molopt_score_model.py:13-45
   UniTransformerO2TwoUpdateGeneral  models/uni_transformer.py:213-328  (forward :301-328)
 """
@@ -308,8 +310,10 @@ class _SinusoidalPosEmb(nn.Module):
 class ScorePosNet3D(nn.Module):
     """Drop-in for models/molopt_score_model.py::ScorePosNet3D on the sampling path.
 
-    Covered: forward, sample_diffusion (with scaffold-constrained sampling as an extra), likelihood_estimation and
-    fetch_embedding.  Training of the diffusion model (get_diffusion_loss and its helpers) is out of scope.
+    Covered: forward, sample_diffusion (with scaffold-constrained sampling as an extra), likelihood_estimation,
+    fetch_embedding, and the forward half of training: get_diffusion_loss / sample_time evaluate the loss of a batch (what the
+    [Validate] line of scripts/train_diffusion.py reports, targetdiff_amd.validation) but produce NO gradient -- the backward pass, the
+    optimiser and train() are out of scope ("Diffusion loss and validation").
     """
 
     def __init__(self, config, protein_atom_feature_dim, ligand_atom_feature_dim):
@@ -557,6 +561,74 @@ class ScorePosNet3D(nn.Module):
         preds = native.model_forward(ppos, protein_v.contiguous().float(), pptr, pos_t, v_t, lptr, want_final_h=False,
                                      ligand_graph_bias=self._time_bias(time_step, B))
         return native.likelihood_terms(t32, lptr, lpos, pos_t, lv, v_t, preds['pred_ligand_pos'], preds['pred_ligand_v'])
+
+    # ------------------------------------------------------------------------------------------ diffusion loss (forward only)
+    def sample_time(self, num_graphs, device, method, generator=None):
+        """models/molopt_score_model.py:440-462 -> ``(time_step [num_graphs] int64, pt [num_graphs] fp32)``.  'symmetric': num_graphs // 2 + 1
+        draws, mirrored with T - 1 - t, cut to num_graphs, pt = 1 / T.  'importance' falls back to 'symmetric' while not every entry of
+        ``Lt_count`` exceeds 10 -- always, in the reference, which never updates ``Lt_history`` / ``Lt_count``; past that point it raises
+        NotImplementedError here.  Anything else: ValueError."""
+        if method == 'importance':
+            if not bool((self.Lt_count > 10).all()):
+                return self.sample_time(num_graphs, device, 'symmetric', generator)
+            raise NotImplementedError("sample_time(method='importance') past the warm-up: nothing updates Lt_history (the reference never "
+                                      'does either, so its branch at :445-451 is dead)')
+        if method != 'symmetric':
+            raise ValueError(f'sample_time: method={method!r}')
+        T = self.num_timesteps
+        time_step = torch.randint(0, T, size=(num_graphs // 2 + 1,), device=device, generator=generator)
+        time_step = torch.cat([time_step, T - time_step - 1], dim=0)[:num_graphs]
+        return time_step, torch.ones_like(time_step).float() / T
+
+    @torch.no_grad()
+    def get_diffusion_loss(self, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, batch_ligand, time_step=None, *,
+                           noise_source=None, generator=None):
+        """models/molopt_score_model.py:485-563, FORWARD ONLY: the loss of one batch at ``time_step`` [B] (drawn with
+        :meth:`sample_time` and ``sample_time_method`` when None).  No gradient is produced: the call runs under torch.no_grad(), the
+        arithmetic is HIP kernels without a backward pass, and every returned tensor has ``requires_grad == False`` whatever the
+        parameters say -- ``loss.backward()`` raises.  It answers what a checkpoint's validation loss is (targetdiff_amd.validation).
+
+        center_pos with the model's ``center_pos_mode`` ('protein' / 'none') -> time steps -> td_perturb (:497-507) -> the denoiser
+        (:510-519) -> td_diffusion_loss (:521-563).  Returns the reference's dict -- 'loss_pos', 'loss_v', 'loss' (0-d), 'x0' (the
+        centred ligand), 'pred_ligand_pos', 'pred_ligand_v', 'pred_pos_noise', 'ligand_v_recon' -- and in addition 'loss_pos_graph',
+        'loss_v_graph' [B] (the per-graph terms the two means are taken over), 'time_step', 'ligand_pos_perturbed' and
+        'ligand_v_perturbed'.  ``noise_source(0, 'noise' | 'uniform', like)`` may inject the Gaussian / uniform draws as in
+        :meth:`likelihood_estimation`; default: torch's RNG (``generator``) in the reference's order.  The batch vectors must be sorted."""
+        native = self._native(protein_pos.device)
+        dev = protein_pos.device
+        if self.center_pos_mode not in ('protein', 'none'):
+            raise NotImplementedError(f'center_pos_mode={self.center_pos_mode!r}')           # center_pos raises (:110-120)
+        _check_graph_inputs(batch_protein, batch_ligand, ligand_v, self.num_classes)
+        B = int(batch_protein.max().item()) + 1                                            # :488
+        pptr = native.graph_ptr(batch_protein.contiguous(), B)
+        lptr = native.graph_ptr(batch_ligand.contiguous(), B)
+        ppos = protein_pos.detach().clone().contiguous().float()
+        lpos = ligand_pos.detach().clone().contiguous().float()
+        lv = ligand_v.detach().contiguous()
+        if self.center_pos_mode == 'protein':
+            native.center_pos(ppos, pptr, lpos, lptr)                                      # :489-490
+        if time_step is None:
+            time_step, _ = self.sample_time(B, dev, self.sample_time_method, generator)    # :493-494
+        time_step = time_step.detach().to(dev)
+        if time_step.numel() != B:
+            raise ValueError(f'time_step has {time_step.numel()} entries for {B} graphs')
+        if bool(((time_step < 0) | (time_step >= self.num_timesteps)).any()):              # index_select raises (:497)
+            raise ValueError(f'time_step must be in [0, {self.num_timesteps})')
+        t32 = time_step.to(torch.int32).contiguous()
+        if noise_source is None:
+            noise = torch.zeros_like(lpos).normal_(generator=generator)                    # :501-502
+            uniform = torch.rand(lpos.shape[0], self.num_classes, dtype=torch.float32, device=dev, generator=generator)   # :161
+        else:
+            noise = noise_source(0, 'noise', lpos).contiguous()
+            uniform = noise_source(0, 'uniform', None).contiguous()
+        pos_t, v_t = native.perturb(t32, lptr, lpos, lv, noise, uniform)                    # :504-507
+        preds = native.model_forward(ppos, protein_v.detach().contiguous().float(), pptr, pos_t, v_t, lptr, want_final_h=False,
+                                     ligand_graph_bias=self._time_bias(time_step, B))      # :510-519
+        out = native.diffusion_loss(t32, lptr, lpos, pos_t, noise, lv, v_t, preds['pred_ligand_pos'], preds['pred_ligand_v'],
+                                    self.loss_v_weight, check=False)                       # :521-563 (lptr is graph_ptr's own)
+        out.update(x0=lpos, pred_ligand_pos=preds['pred_ligand_pos'], pred_ligand_v=preds['pred_ligand_v'], time_step=time_step,
+                   ligand_pos_perturbed=pos_t, ligand_v_perturbed=v_t)
+        return out
 
     @torch.no_grad()
     def fetch_embedding(self, protein_pos, protein_v, batch_protein, ligand_pos, ligand_v, batch_ligand):

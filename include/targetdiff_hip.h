@@ -406,6 +406,48 @@ int td_fingerprint_similarity(const int64_t *d_fp_words, const int32_t *d_n_bits
                               const uint8_t *d_include, const int64_t *d_q_words, int64_t Q, double *d_sim_sum, double *d_sim_max,
                               int32_t *d_first_equal, int32_t *d_common, int32_t *d_query_common, void *stream);
 
+/* ---- local geometry of ligand frames ("Local geometry"): per (frame, molecule), on the bond graph exactly as
+ *      td_bond_graph defines it (the same pack, class table, aromatic flags and d_include bytes; an atom whose class is outside
+ *      [0, K) bonds with nothing and takes part nowhere).  Coordinates are the fp32 inputs widened to float64; every product, sum and
+ *      difference is rounded on its own, division and square root are IEEE.  Degree of an atom: the number of its bonds; an atom of
+ *      degree > 8 (TD_GEOM_MAX_DEGREE) is crowded: it is the centre of no angle, a bond with a crowded end is central to no torsion,
+ *      and a crowded atom may still be an end atom.
+ *      Bond angle (i, j, k), j the centre, i < k both bonded to j: u = p_i - p_j, w = p_k - p_j, uu = (u_x u_x + u_y u_y) + u_z u_z, ww
+ *      and uw likewise; degenerate when uu ww == 0, else c = uw / sqrt(uu ww).  Torsion (i, j, k, l): the central bond j < k, i bonded
+ *      to j with i != k, l bonded to k with l != j and l != i (no three-rings), each such quadruple once: b1 = p_j - p_i, b2 = p_k -
+ *      p_j, b3 = p_l - p_k, n1 = b1 x b2, n2 = b2 x b3 with every component formed as (a b) - (c d); degenerate when (n1.n1)(n2.n2)
+ *      == 0, else c = (n1.n2) / sqrt((n1.n1)(n2.n2)): the cosine of the unsigned torsion 0 .. 180 degrees (mirror images alike).  No
+ *      acos or atan2 runs on the device: angles are binned by their cosine.  Profile p (HOST array, P <= 16): kind 1 = angle, 2 =
+ *      torsion; z[4] atomic numbers (0: any) -- an angle matches with z[1] the centre and z[0], z[2] the ends in either order (z[3]
+ *      must be 0), a torsion with its four elements as given or reversed; category (0: any, else the central bond's category as
+ *      td_bond_list gives it, 1 .. 4) and ring (0: any, 1: the central bond is in no ring, 2: it is in one) filter torsions and must be
+ *      0 for an angle; the value enters bin numpy.searchsorted(edges, c, 'left') of d_edges [n_edges] (DEVICE float64 cosines,
+ *      ascending, 1 <= n_edges <= 127).  The ring filter reads d_bond_ring [n_bonds] of td_ring_report at the offsets d_bond_ptr
+ *      [S*B+1] of td_bond_graph on the same pack (both may be NULL otherwise; TD_EINVAL when a profile asks for the filter without
+ *      them; an offset outside [0, n_bonds) matches neither 1 nor 2 and nothing out of bounds is read).
+ *      Internal clash: a pair i < j of one molecule, both with a class, more than 3 bonds apart in the graph (pairs in different
+ *      fragments included), with d < clash_threshold[e_i * 8 + e_j]; d is the distance of the bond rule, bit for bit, e the element
+ *      index over H C N O F P S Cl; clash_threshold is a HOST float64 [64] table, NULL: no clash pass (d_n_clashes and d_atom_clash
+ *      are then not written and may be NULL).
+ *      Output: d_n_angles, d_n_torsions [S,B] int32, every non-degenerate angle / torsion whatever the profiles; d_n_degenerate [S,B]
+ *      the degenerate angles and torsions, which are counted nowhere else; d_n_crowded [S,B] the crowded atoms; d_n_clashes [S,B];
+ *      d_atom_clash [S,N_l] int32 (may be NULL), the clashes an atom takes part in; d_hist [S,P,128] int64, zeroed by the call, over
+ *      the molecules whose d_include byte is non-zero (NULL: all).  A molecule of more than 512 atoms, or one whose offsets leave
+ *      [0, N_l], gets -1 in the five per-molecule outputs and contributes nothing else (a binding refuses it).  All outputs are
+ *      integers: they do not depend on the grid or on the order of arrival.  (An addition: TD_ABI_VERSION stays 5.) */
+typedef struct td_geometry_profile {
+    int32_t kind;
+    int32_t z[4];
+    int32_t category, ring, n_edges;
+    const double *d_edges;
+} td_geometry_profile;
+int td_geometry_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                       const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const uint8_t *class_aromatic,
+                       const td_geometry_profile *profiles, int32_t P, const int64_t *d_bond_ptr, int64_t n_bonds,
+                       const uint16_t *d_bond_ring, const double *clash_threshold, int32_t *d_n_angles, int32_t *d_n_torsions,
+                       int32_t *d_n_degenerate, int32_t *d_n_crowded, int32_t *d_n_clashes, int32_t *d_atom_clash, int64_t *d_hist,
+                       void *stream);
+
 /* ---- standalone EGNN refine net (replaces: models/egnn.py EGNN / EnBaseLayer as get_refine_net('egnn', config) builds
  *      it, models/molopt_score_model.py:34-42: num_r_gaussian = 1, kNN rebuilt per layer, SiLU, no LayerNorm, hidden 128,
  *      4 edge types, k = 32).  `host_weights`: per layer, in this order and as PyTorch stores them: edge_mlp.net.0.{weight

@@ -47,6 +47,11 @@ class TdBondProfile(ctypes.Structure):
     _fields_ = [('z1', c_int32), ('z2', c_int32), ('category', c_int32), ('n_edges', c_int32), ('d_edges', c_void_p)]
 
 
+class TdGeometryProfile(ctypes.Structure):
+    """td_geometry_profile of include/targetdiff_hip.h"""
+    _fields_ = [('kind', c_int32), ('z', c_int32 * 4), ('category', c_int32), ('ring', c_int32), ('n_edges', c_int32), ('d_edges', c_void_p)]
+
+
 class TdPropConfig(ctypes.Structure):
     """td_prop_config of include/targetdiff_hip.h"""
     _fields_ = [('hidden_dim', c_int32), ('num_layers', c_int32), ('knn', c_int32), ('num_r_gaussian', c_int32), ('cutoff', c_float),
@@ -94,6 +99,8 @@ SIGNATURES = {
     'td_fingerprint': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), c_int32, c_int32, _P, _P, _P,
                                  _P, _P]),
     'td_fingerprint_similarity': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P, _P, _P, _P]),
+    'td_geometry_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, POINTER(ctypes.c_uint8), _P, c_int32, _P, c_int64,
+                                     _P, POINTER(ctypes.c_double), _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_center_pos': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int32, c_int32, _P]),
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
@@ -1086,6 +1093,87 @@ def ring_report(pos, v, ligand_ptr, class_z, class_aromatic=None, include=None, 
                                   _ptr(out['atom_ring']), _ptr(out['ring_hist']), _ptr(out['bond_ring']), _ptr(out['bond_category']),
                                   _stream(dev)), 'td_ring_report')
     out['ring_mask'] = mask.to(torch.int64) & 0xffffffff              # torch has no arithmetic on uint32: the word, widened
+    return out
+
+
+GEOM_MAX_DEGREE, GEOM_MAX_PROFILES, GEOM_BINS = 8, 16, 128                  # TD_GEOM_* (csrc/td_internal.h)
+GEOM_KINDS = {'angle': 1, 'torsion': 2}
+GEOM_RINGS = {None: 0, 'any': 0, 'chain': 1, 'ring': 2}
+
+
+def _geometry_profiles(profiles):
+    """[(kind, (z, z, z, z), category, ring, cosine edges as float64 numpy)] of a geometry call, checked"""
+    if len(profiles) > GEOM_MAX_PROFILES:
+        raise ValueError(f'at most {GEOM_MAX_PROFILES} geometry profiles (got {len(profiles)})')
+    prof = []
+    for kind, z, category, ring, edges in profiles:
+        kind = GEOM_KINDS.get(kind, kind)
+        ring = GEOM_RINGS.get(ring, ring) if ring is None or isinstance(ring, str) else int(ring)
+        if kind not in (1, 2):
+            raise ValueError(f"the kind of a geometry profile is 'angle' (1) or 'torsion' (2) (got {kind!r})")
+        z = tuple(int(x) for x in z)
+        if len(z) != 2 + kind:
+            raise ValueError(f'an angle names 3 elements and a torsion 4 (got {len(z)})')
+        if any(x != 0 and x not in QUALITY_ELEMENTS for x in z):
+            raise ValueError(f'a geometry profile names elements of {QUALITY_ELEMENTS} or 0 for any (got {z})')
+        if int(category) not in (0, 1, 2, 3, 4) or ring not in (0, 1, 2):
+            raise ValueError(f"category 0 (any) .. 4 and ring 0 / 'any', 1 / 'chain' or 2 / 'ring' (got {category}, {ring!r})")
+        if kind == 1 and (int(category) != 0 or ring != 0):
+            raise ValueError('an angle profile takes no category and no ring filter')
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+        if not 1 <= e.size <= GEOM_BINS - 1:
+            raise ValueError(f'a geometry profile has 1 .. {GEOM_BINS - 1} edges (got {e.size})')
+        if not np.isfinite(e).all() or bool((e[1:] < e[:-1]).any()):
+            raise ValueError('the cosine edges of a geometry profile must be finite and ascending')
+        prof.append((kind, z + (0,) * (4 - len(z)), int(category), ring, e))
+    return prof
+
+
+def geometry_report(pos, v, ligand_ptr, class_z, class_aromatic=None, profiles=(), include=None, clash_threshold=None, bond_ptr=None,
+                    bond_ring=None, return_atom_clash=True, check=True):
+    """Bond angles, torsions and internal clashes of S frames of B molecules (td_geometry_report, include/targetdiff_hip.h); the pack,
+    the class table and ``include`` as bond_graph's.  ``profiles``: a sequence of (kind, elements, category, ring, edges): kind 'angle'
+    or 'torsion', 3 or 4 atomic numbers (0: any), the central bond's category (0: any), ring 'any' / 'chain' / 'ring' (0 / 1 / 2) and
+    ascending **cosine** edges; the bin is numpy.searchsorted(edges, c, 'left').  A ring filter needs ``bond_ptr`` of bond_graph and
+    ``bond_ring`` of ring_report on the same pack.  ``clash_threshold``: [8, 8] float64 over H C N O F P S Cl, None: no clash pass.
+    Returns a dict of device tensors: n_angles, n_torsions, n_degenerate, n_crowded [S, B] int32, n_clashes [S, B] int32 and atom_clash
+    [S, N_l] int32 (None without a table / without ``return_atom_clash``), hist [S, P, 128] int64."""
+    S, Nl, B, cz, aro, _ = _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, include, (), check)
+    prof = _geometry_profiles(profiles)
+    need_ring = any(p[3] != 0 for p in prof)
+    if need_ring and (bond_ptr is None or bond_ring is None):
+        raise ValueError('a ring filter needs bond_ptr of bond_graph and bond_ring of ring_report on the same pack')
+    if bond_ptr is not None and (bond_ptr.dim() != 1 or bond_ptr.numel() != S * B + 1 or bond_ptr.dtype != torch.int64):
+        raise ValueError(f'bond_ptr must be [{S * B + 1}] int64, as bond_graph returns it')
+    if bond_ring is not None and (bond_ptr is None or bond_ring.dim() != 1 or bond_ring.dtype != torch.int16):
+        raise ValueError('bond_ring must be [n_bonds] int16, as ring_report returns it, and comes with bond_ptr')
+    thr = None
+    if clash_threshold is not None:
+        thr = np.ascontiguousarray(np.asarray(clash_threshold, dtype=np.float64).reshape(-1))
+        if thr.size != 64 or not np.isfinite(thr).all():
+            raise ValueError('clash_threshold is a finite [8, 8] table over H C N O F P S Cl')
+    lib = load_library()
+    _ptr(pos, torch.float32, 'pos')                   # a CPU tensor is refused before anything is allocated
+    dev = pos.device
+    P = len(prof)
+    edges = [torch.from_numpy(e).to(dev) for *_, e in prof]
+    parr = (TdGeometryProfile * max(P, 1))()
+    for p, (kind, z, category, ring, e) in enumerate(prof):
+        parr[p] = TdGeometryProfile(kind, (c_int32 * 4)(*z), category, ring, e.size, edges[p].data_ptr())
+    nb = int(bond_ring.numel()) if bond_ring is not None else 0
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    out = dict(n_angles=i32(S, B), n_torsions=i32(S, B), n_degenerate=i32(S, B), n_crowded=i32(S, B),
+               n_clashes=i32(S, B) if thr is not None else None, atom_clash=i32(S, Nl) if thr is not None and return_atom_clash else None,
+               hist=torch.empty(S, P, GEOM_BINS, dtype=torch.int64, device=dev))
+    if include is not None and include.dtype == torch.bool:
+        include = include.view(torch.uint8)
+    with _on(dev):
+        _check(lib.td_geometry_report(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
+                                      S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _ptr(include, torch.uint8, 'include'),
+                                      _aromatic_arg(aro), ctypes.cast(parr, c_void_p), P, _ptr(bond_ptr if bond_ring is not None else None), nb,
+                                      _ptr(bond_ring), None if thr is None else thr.ctypes.data_as(POINTER(ctypes.c_double)),
+                                      _ptr(out['n_angles']), _ptr(out['n_torsions']), _ptr(out['n_degenerate']), _ptr(out['n_crowded']),
+                                      _ptr(out['n_clashes']), _ptr(out['atom_clash']), _ptr(out['hist']), _stream(dev)), 'td_geometry_report')
     return out
 
 

@@ -1,5 +1,6 @@
-// C ABI of libtargetdiff_hip.so: the bond graph of ligand frames, its rings and its fingerprints (td_bond_graph, td_bond_list,
-// td_ring_report, td_fingerprint, td_fingerprint_similarity).  See include/targetdiff_hip.h for the contract.
+// C ABI of libtargetdiff_hip.so: the bond graph of ligand frames, its rings, its fingerprints and its local geometry (td_bond_graph,
+// td_bond_list, td_ring_report, td_fingerprint, td_fingerprint_similarity, td_geometry_report).  See include/targetdiff_hip.h for the
+// contract.
 #include "td_device.h"
 #include "td_internal.h"
 
@@ -164,4 +165,69 @@ extern "C" int td_fingerprint_similarity(const int64_t *d_fp_words, const int32_
     a.sim_sum = d_sim_sum; a.sim_max = d_sim_max; a.first_equal = d_first_equal; a.common = d_common;
     a.query_common = Q > 0 ? d_query_common : nullptr;
     return td_launch_fingerprint_similarity(a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int td_geometry_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                                  const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const uint8_t *class_aromatic,
+                                  const td_geometry_profile *profiles, int32_t P, const int64_t *d_bond_ptr, int64_t n_bonds,
+                                  const uint16_t *d_bond_ring, const double *clash_threshold, int32_t *d_n_angles, int32_t *d_n_torsions,
+                                  int32_t *d_n_degenerate, int32_t *d_n_crowded, int32_t *d_n_clashes, int32_t *d_atom_clash,
+                                  int64_t *d_hist, void *stream) {
+    const char *who = "td_geometry_report";
+    TdGeomArgs g;
+    if (P < 0 || P > TD_GEOM_MAX_PROFILES || (P > 0 && !profiles)) {
+        td_set_error("%s: 0 .. %d geometry profiles (got %d)", who, TD_GEOM_MAX_PROFILES, (int)P);
+        return TD_EINVAL;
+    }
+    if (n_bonds < 0) { td_set_error("%s: bad argument (n_bonds = %lld)", who, (long long)n_bonds); return TD_EINVAL; }
+    for (int p = 0; p < P; ++p) {
+        const td_geometry_profile &pf = profiles[p];
+        if (pf.kind != 1 && pf.kind != 2) {
+            td_set_error("%s: profile %d: the kind must be 1 (angle) or 2 (torsion) (got %d)", who, p, (int)pf.kind);
+            return TD_EINVAL;
+        }
+        for (int q = 0; q < 4; ++q) {
+            const int e = pf.z[q] == 0 ? -1 : td_element_index(pf.z[q]);
+            if (pf.z[q] != 0 && e < 0) {
+                td_set_error("%s: profile %d names an atomic number outside the table (%d; 0 = any)", who, p, (int)pf.z[q]);
+                return TD_EINVAL;
+            }
+            g.z[p][q] = (int8_t)e;
+        }
+        if (pf.category < 0 || pf.category > 4 || pf.ring < 0 || pf.ring > 2) {
+            td_set_error("%s: profile %d: the category must be 0 (any) .. 4 and the ring filter 0 (any), 1 or 2 (got %d, %d)", who, p,
+                         (int)pf.category, (int)pf.ring);
+            return TD_EINVAL;
+        }
+        if (pf.kind == 1 && (pf.z[3] != 0 || pf.category != 0 || pf.ring != 0)) {
+            td_set_error("%s: profile %d: an angle has three elements (z[3] = 0) and no category or ring filter", who, p);
+            return TD_EINVAL;
+        }
+        if (pf.ring != 0 && (!d_bond_ptr || !d_bond_ring)) {
+            td_set_error("%s: profile %d: the ring filter needs d_bond_ptr of td_bond_graph and d_bond_ring of td_ring_report", who, p);
+            return TD_EINVAL;
+        }
+        if (pf.n_edges < 1 || pf.n_edges > TD_GEOM_BINS - 1 || !pf.d_edges) {
+            td_set_error("%s: profile %d needs 1 .. %d edges (got %d)", who, p, TD_GEOM_BINS - 1, (int)pf.n_edges);
+            return TD_EINVAL;
+        }
+        g.kind[p] = (int8_t)pf.kind; g.cat[p] = (int8_t)pf.category; g.ring[p] = (int8_t)pf.ring; g.n_edges[p] = (int16_t)pf.n_edges;
+        g.edges[p] = pf.d_edges;
+    }
+    if (const int rc = bond_pack(who, g.b, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic)) return rc;
+    if ((S > 0 && P > 0 && !d_hist) ||
+        (S > 0 && B > 0 && (!d_n_angles || !d_n_torsions || !d_n_degenerate || !d_n_crowded || (clash_threshold && !d_n_clashes)))) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    g.b.include = d_include; g.P = P;
+    g.b.bond_ptr = const_cast<int64_t *>(d_bond_ptr); g.b.capacity = n_bonds; g.b.bond_ring = const_cast<uint16_t *>(d_bond_ring);
+    if (clash_threshold) {
+        g.clash = true;
+        for (int k = 0; k < 64; ++k) g.clash_thr[k] = clash_threshold[k];
+    }
+    g.n_angles = d_n_angles; g.n_torsions = d_n_torsions; g.n_degenerate = d_n_degenerate; g.n_crowded = d_n_crowded;
+    g.n_clashes = d_n_clashes; g.atom_clash = d_atom_clash;
+    g.hist = reinterpret_cast<unsigned long long *>(d_hist);
+    return td_launch_geometry_report(g, static_cast<hipStream_t>(stream));
 }

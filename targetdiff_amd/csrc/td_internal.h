@@ -487,6 +487,24 @@ int td_launch_bond_list(const TdBondArgs &a, hipStream_t s);
 int td_launch_ring_report(const TdBondArgs &a, hipStream_t s);
 int td_launch_fingerprint(const TdBondArgs &a, hipStream_t s);
 int td_launch_fingerprint_similarity(const TdSimArgs &a, hipStream_t s);
+// geometry.hip (td_geometry_report, DESIGN.md section 3, "Local geometry"): the pack and the include bytes in `b`; of b's bond outputs
+// only bond_ptr / capacity / bond_ring are used, and read (the ring filter of a torsion profile).  z: element index per position, -1 =
+// any; kind 1 = angle, 2 = torsion; ring 0 = any, 1 = central bond in no ring, 2 = in a ring.  The launcher zeroes hist on the stream.
+constexpr int TD_GEOM_MAX_DEGREE = 8, TD_GEOM_MAX_PROFILES = 16, TD_GEOM_BINS = 128;
+struct TdGeomArgs {
+    TdBondArgs b;
+    int P = 0;
+    int8_t kind[TD_GEOM_MAX_PROFILES] = {}, z[TD_GEOM_MAX_PROFILES][4] = {}, cat[TD_GEOM_MAX_PROFILES] = {}, ring[TD_GEOM_MAX_PROFILES] = {};
+    int16_t n_edges[TD_GEOM_MAX_PROFILES] = {};
+    const double *edges[TD_GEOM_MAX_PROFILES] = {};
+    bool clash = false;                      // clash_thr holds the table
+    double clash_thr[64] = {};
+    int32_t *n_angles = nullptr, *n_torsions = nullptr, *n_degenerate = nullptr, *n_crowded = nullptr;   // [S,B]
+    int32_t *n_clashes = nullptr;            // [S,B], written when clash
+    int32_t *atom_clash = nullptr;           // [S,N_l] or null
+    unsigned long long *hist = nullptr;      // [S,P,TD_GEOM_BINS]
+};
+int td_launch_geometry_report(const TdGeomArgs &a, hipStream_t s);
 // egnn.hip / node.hip
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s);

@@ -42,6 +42,13 @@ This is not RDKit's RDKFingerprint, which the reference's utils/evaluation/simil
 invariants.  This one is a circular, Morgan-style fingerprint over this project's bond graph, whose orders come from the bond-length
 table.  Its similarities are comparable between runs of this tool, not with published tables.
 
+And the shape the bonds make (``td_geometry_report``, csrc/geometry.hip; DESIGN.md section 3, "Local geometry"): bond angles and
+unsigned torsion angles binned per type, and internal clashes -- pairs more than 3 bonds apart that are closer than 0.7 times the sum
+of their van der Waals radii, this project's own convention (not PoseBusters' bound, not a force field):
+
+    geo = quality.sample_geometry(result, eval_step='all', reference=quality.geometry_reference(molfile.read_sdf('ligands.sdf')))
+    geo.summary()   # {'clash_free': ..., 'mean_clashes': ..., 'CCC': {'count': ..., 'mean': ..., 'js': ...}, ...}
+
 OpenBabel's reconstruction, valence repair, QED / SA and docking need a chemistry toolkit and are not here.
 """
 from __future__ import annotations
@@ -716,3 +723,251 @@ def sample_diversity(result, eval_step=-1, include='all', radius=2, key_rounds=8
     return DiversityReport.from_frames(inc.sum(1), np.where(inc, r['sim_sum'].cpu().numpy(), 0.0).sum(1), distinct.sum(1),
                                        np.where(inc, r['sim_max'].cpu().numpy(), 0.0).sum(1), len(sizes),
                                        None if qw is None else r['query_sim'][:, :, 0].cpu().numpy(), inc)
+
+
+# ---- local geometry (``td_geometry_report``, csrc/geometry.hip; DESIGN.md section 3, "Local geometry")
+# van der Waals radii in Angstrom (Bondi's, the usual table) of H C N O F P S Cl: an internal clash is a pair more than 3 bonds apart
+# that is closer than clash_scale * (r_i + r_j).  This project's own convention: not PoseBusters' distance-geometry bound, not a force field.
+GEOMETRY_RADII = {1: 1.2, 6: 1.7, 7: 1.55, 8: 1.52, 9: 1.47, 15: 1.8, 16: 1.8, 17: 1.75}
+ANGLE_TYPES = ((6, 6, 6), (6, 6, 7), (6, 6, 8), (6, 7, 6), (6, 8, 6), (7, 6, 7))
+TORSION_TYPES = (((6, 6, 6, 6), 'chain'), ((6, 6, 6, 6), 'ring'), ((6, 6, 6, 7), 'any'), ((6, 6, 6, 8), 'any'), ((6, 6, 7, 6), 'any'),
+                 ((6, 6, 8, 6), 'chain'))
+_SYMBOL = {0: '*', 1: 'H', 6: 'C', 7: 'N', 8: 'O', 9: 'F', 15: 'P', 16: 'S', 17: 'Cl'}
+_RING_CODE = {None: 'any', 0: 'any', 1: 'chain', 2: 'ring', 'any': 'any', 'chain': 'chain', 'ring': 'ring'}
+
+
+def default_geometry_profiles():
+    """The default angle and torsion types as (kind, elements, category, ring, edges in degrees): the angles C-C-C, C-C-N, C-C-O,
+    C-N-C, C-O-C and N-C-N (the centre in the middle) in 2 degree bins over 0 .. 180 (edges 2, 4, ..., 178), and the torsions C-C-C-C
+    with the central bond outside a ring and inside one, C-C-C-N, C-C-C-O, C-C-N-C and C-C-O-C outside a ring, in 5 degree bins."""
+    a, t = np.arange(2.0, 180.0, 2.0), np.arange(5.0, 180.0, 5.0)
+    return tuple(('angle', z, 0, 'any', a) for z in ANGLE_TYPES) + tuple(('torsion', z, 0, ring, t) for z, ring in TORSION_TYPES)
+
+
+def geometry_profile_name(profile):
+    """'CCN' for the angle (6, 6, 7), 'CCCC|ring' for a torsion inside a ring, 'CCNC|2' with a category, '*' for any element"""
+    _, z, category, ring, _ = profile
+    name = ''.join(_SYMBOL[int(x)] for x in z)
+    if int(category):
+        name += f'|{int(category)}'
+    return name if _RING_CODE[ring] == 'any' else f'{name}|{_RING_CODE[ring]}'
+
+
+def clash_thresholds(clash_scale=0.7, radii=None):
+    """[8, 8] float64 over H C N O F P S Cl: ``clash_scale * (r_i + r_j)``; ``radii``: {atomic number: radius in Angstrom} over
+    ``GEOMETRY_RADII`` (missing elements keep the default), or None"""
+    r = dict(GEOMETRY_RADII)
+    for z, x in (radii or {}).items():
+        if int(z) not in r or not float(x) >= 0.0:
+            raise ValueError(f'radii are non-negative and keyed by the atomic numbers {ELEMENTS} (got {z}: {x})')
+        r[int(z)] = float(x)
+    rr = np.asarray([r[z] for z in ELEMENTS], dtype=np.float64)
+    if not float(clash_scale) >= 0.0:
+        raise ValueError(f'clash_scale is non-negative (got {clash_scale})')
+    return np.float64(clash_scale) * (rr[:, None] + rr[None, :])
+
+
+def _cosine_profiles(profiles):
+    """Profiles with ascending edges in degrees (0 .. 180) as the binding's profiles with ascending cosine edges: numpy.cos of the
+    edges in float64, once, reversed.  The kernel's bin k of m edges is bin m - k by ascending angle."""
+    out = []
+    for kind, z, category, ring, edges in profiles:
+        e = np.asarray(edges, dtype=np.float64).reshape(-1)
+        if e.size == 0 or not np.isfinite(e).all() or bool((e[1:] <= e[:-1]).any()) or e[0] < 0.0 or e[-1] > 180.0:
+            raise ValueError('the edges of a geometry profile are degrees in 0 .. 180, strictly ascending')
+        out.append((kind, tuple(int(x) for x in z), int(category), _RING_CODE[ring], np.cos(np.radians(e))[::-1].copy()))
+    return out
+
+
+def _geometry_call(pos, v, ptr, cz, aro, profiles, mask, thr, return_atom_clash, check=True):
+    """capi.geometry_report under profiles in degrees, the histograms flipped back to ascending angle; the bond graph and the ring
+    report run first when a profile filters on the ring"""
+    cosp = _cosine_profiles(profiles)
+    bond_ptr = bond_ring = None
+    if any(p[3] != 'any' for p in cosp):
+        bond_ptr = capi.bond_graph(pos, v, ptr, cz, aro, (), None, False, True, check=check)['bond_ptr']
+        bond_ring = capi.ring_report(pos, v, ptr, cz, aro, None, bond_ptr, False, check=False)['bond_ring']
+        check = False
+    r = capi.geometry_report(pos, v, ptr, cz, aro, cosp, mask, thr, bond_ptr, bond_ring, return_atom_clash, check=check)
+    hist = torch.zeros_like(r['hist'])
+    for p, prof in enumerate(cosp):
+        m = len(prof[4])
+        hist[:, p, :m + 1] = r['hist'][:, p, :m + 1].flip(-1)
+    r['hist'] = hist
+    return r
+
+
+class Geometry:
+    """The local geometry of S frames of B molecules (``geometry``).  Device tensors, frame axis first: ``n_angles``, ``n_torsions``
+    (the non-degenerate ones, whatever the profiles), ``n_degenerate`` (angles and torsions whose cosine is 0 / 0), ``n_crowded`` (atoms
+    of more than 8 bonds: the centre of no angle, the end of no central bond), ``n_clashes`` [S, B] int32, ``clash_free`` [S, B] bool,
+    ``atom_clash`` [S, N_l] int32 (the clashes an atom takes part in), ``hist`` [S, P, 128] int64 over the included molecules, by
+    ascending angle: bin b of a profile with edges e holds e[b - 1] <= angle < e[b]; ``profiles``, ``names``, ``ligand_ptr``."""
+
+    def __init__(self, r, ligand_ptr, profiles):
+        self.n_angles, self.n_torsions, self.n_degenerate, self.n_crowded = r['n_angles'], r['n_torsions'], r['n_degenerate'], r['n_crowded']
+        self.n_clashes, self.atom_clash, self.hist = r['n_clashes'], r['atom_clash'], r['hist']
+        self.clash_free = self.n_clashes == 0
+        self.ligand_ptr, self.profiles = ligand_ptr, tuple(profiles)
+        self.names = tuple(geometry_profile_name(p) for p in self.profiles)
+
+
+def geometry(pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic', profiles=None, include=None, clash_scale=0.7,
+             radii=None, device=None):
+    """Bond angles, torsions and internal clashes of every molecule of one frame ``[N_l, 3]`` or of a stack ``[S, N_l, 3]`` (arguments
+    as ``bond_graph``), on exactly the bonds of ``bond_graph``.
+
+    Angle (i, j, k): j the centre, i < k bonded to it.  Torsion (i, j, k, l): the central bond j < k, i on j, l on k, all four
+    different; the unsigned angle 0 .. 180 degrees, so mirror images histogram alike.  An atom of more than 8 bonds (a collapsed cloud)
+    is the centre of no angle and the end of no central bond.  The kernel bins by the cosine in float64; no acos runs on the device.
+    ``profiles``: a sequence of (kind, elements, category, ring, edges): 'angle' with 3 atomic numbers (the centre in the middle, the
+    ends in either order) or 'torsion' with 4 (as given or reversed), 0 for any element; the central bond's category 1 .. 4 or 0 for
+    any, and ring 'any', 'chain' (the central bond is in no ring) or 'ring' -- both for torsions only; ascending edges in **degrees**.
+    Default ``default_geometry_profiles()``.  The edges become cosines once, by numpy.cos in float64, and the histogram comes back by
+    ascending angle: bin b holds edges[b - 1] <= angle < edges[b], and an angle whose cosine equals numpy.cos(numpy.radians(edge))
+    exactly lands in the bin that starts at that edge.  A ring filter costs two more launches (``td_bond_graph``, ``td_ring_report``).
+    ``include`` [S, B] restricts ``hist`` and nothing else.
+
+    Internal clash: a pair of atoms of one molecule more than 3 bonds apart (other fragments included) that is closer than
+    ``clash_scale * (r_i + r_j)``, with the van der Waals radii H 1.2, C 1.7, N 1.55, O 1.52, F 1.47, P 1.8, S 1.8, Cl 1.75 A
+    (``radii``: {atomic number: radius} to change some).  This is this project's own convention: it is not PoseBusters'
+    distance-geometry bound and not a force field.  Molecules of more than 512 atoms are refused.  Returns a ``Geometry``."""
+    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
+    if include is not None:
+        include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+    prof = default_geometry_profiles() if profiles is None else tuple(profiles)
+    r = _geometry_call(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode), prof, include,
+                       clash_thresholds(clash_scale, radii), True)
+    return Geometry(r, ligand_ptr, prof)
+
+
+class GeometryReport:
+    """Per frame (axis 0), over the included molecules (``n_included`` [S] of ``n_samples``): ``n_clash_free`` and ``sum_clashes``
+    [S], ``n_crowded``, ``n_degenerate``, ``n_angles``, ``n_torsions`` [S], and ``hist`` [S, P, 128] int64 by ascending angle under
+    ``profiles`` (edges in degrees; ``names``).  ``reference``: {name: counts or a distribution over the profile's bins}, as
+    ``geometry_reference`` makes it, or None.  The clash rule and the radii are this project's own convention (``geometry``)."""
+
+    def __init__(self, n_included, n_clash_free, sum_clashes, n_crowded, n_degenerate, n_angles, n_torsions, hist, profiles, n_samples,
+                 reference=None):
+        i64 = lambda a: np.asarray(a, dtype=np.int64)
+        self.n_included, self.n_clash_free, self.sum_clashes = i64(n_included), i64(n_clash_free), i64(sum_clashes)
+        self.n_crowded, self.n_degenerate, self.n_angles, self.n_torsions = i64(n_crowded), i64(n_degenerate), i64(n_angles), i64(n_torsions)
+        self.hist, self.profiles, self.n_samples, self.reference = i64(hist), tuple(profiles), int(n_samples), reference
+        self.names = tuple(geometry_profile_name(p) for p in self.profiles)
+
+    @classmethod
+    def merged(cls, reports):
+        """Several pockets together: every integer summed, frame by frame"""
+        reports = list(reports)
+        first = reports[0]
+        if any(r.hist.shape != first.hist.shape or r.names != first.names for r in reports):
+            raise ValueError('reports of different frame counts or profiles do not merge')
+        tot = lambda name: sum(getattr(r, name) for r in reports)
+        return cls(tot('n_included'), tot('n_clash_free'), tot('sum_clashes'), tot('n_crowded'), tot('n_degenerate'), tot('n_angles'),
+                   tot('n_torsions'), tot('hist'), first.profiles, tot('n_samples'), first.reference)
+
+    @property
+    def num_frames(self):
+        return self.hist.shape[0]
+
+    def _per_molecule(self, count, frame):
+        n = int(self.n_included[frame])
+        return int(count) / n if n else float('nan')
+
+    def clash_free(self, frame=-1):
+        """included molecules without an internal clash / included molecules"""
+        return self._per_molecule(self.n_clash_free[frame], frame)
+
+    def mean_clashes(self, frame=-1):
+        return self._per_molecule(self.sum_clashes[frame], frame)
+
+    def counts(self, name, frame=-1):
+        """the counts of a profile over its ``len(edges) + 1`` bins"""
+        p = self.names.index(name)
+        return self.hist[frame, p, :len(self.profiles[p][4]) + 1]
+
+    def count(self, name, frame=-1):
+        return int(self.counts(name, frame).sum())
+
+    def distribution(self, name, frame=-1):
+        h = self.counts(name, frame)
+        return h / np.sum(h) if h.sum() > 0 else None
+
+    def bin_centres(self, name):
+        """the middle of every bin in degrees, the outer bins running to 0 and to 180"""
+        e = np.asarray(self.profiles[self.names.index(name)][4], dtype=np.float64)
+        e = np.concatenate([[0.0], e, [180.0]])
+        return (e[:-1] + e[1:]) / 2.0
+
+    def mean_angle(self, name, frame=-1):
+        """the mean angle in degrees from the bin centres, nan when nothing was counted"""
+        h = self.counts(name, frame)
+        return float(np.sum(h * self.bin_centres(name)) / h.sum()) if h.sum() > 0 else float('nan')
+
+    def js(self, frame=-1):
+        """{'JSD_<name>': ...}: the Jensen-Shannon distance of every profile to the reference's; None where there is no reference
+        distribution or nothing was counted"""
+        ref = self.reference or {}
+        out = {}
+        for name in self.names:
+            d = self.distribution(name, frame)
+            q = ref.get(name)
+            ok = d is not None and q is not None and len(q) == len(d) and np.sum(q) > 0
+            out['JSD_' + name] = float(jensenshannon(np.asarray(q, dtype=np.float64), d)) if ok else None
+        return out
+
+    def summary(self, frame=-1):
+        out = dict(clash_free=self.clash_free(frame), mean_clashes=self.mean_clashes(frame), crowded_atoms=int(self.n_crowded[frame]),
+                   degenerate=int(self.n_degenerate[frame]), angles=int(self.n_angles[frame]), torsions=int(self.n_torsions[frame]))
+        js = self.js(frame)
+        for name in self.names:
+            out[name] = dict(count=self.count(name, frame), mean=self.mean_angle(name, frame), js=js['JSD_' + name])
+        return out
+
+    def lines(self, frame=-1):
+        """the report as printed lines"""
+        s = self.summary(frame)
+        out = [f"clash_free:\t{s['clash_free']:.4f}", f"mean_clashes:\t{s['mean_clashes']:.4f}", f"crowded_atoms:\t{s['crowded_atoms']}",
+               f"degenerate:\t{s['degenerate']}", f"angles:\t{s['angles']}", f"torsions:\t{s['torsions']}"]
+        for p, name in enumerate(self.names):
+            kind = 'angle' if len(self.profiles[p][1]) == 3 else 'torsion'
+            js = 'None' if s[name]['js'] is None else f"{s[name]['js']:.4f}"
+            out.append(f"{kind} {name}:\tcount {s[name]['count']}\tmean {s[name]['mean']:.2f}\tJSD {js}")
+        return out
+
+
+def sample_geometry(result, eval_step=-1, include='all', reference=None, profiles=None, clash_scale=0.7, radii=None,
+                    atom_enc_mode='add_aromatic', device='cuda'):
+    """Local geometry of the samples of one pocket (``result``, ``eval_step`` and the packing as ``sample_quality``): per frame the
+    share of molecules without an internal clash, the mean number of clashes, the crowded-atom and degenerate counts, and per profile
+    the count, the mean angle and -- with ``reference`` ({name: counts}, of ``geometry_reference``) -- the Jensen-Shannon distance.
+    ``include``: the molecules that are counted, as ``sample_rings``: ``'all'``, ``'complete'`` or a bool array [frames, samples].
+    ``profiles``, ``clash_scale`` and ``radii`` as ``geometry``, whose conventions these are.  Returns a ``GeometryReport``."""
+    pos, v, ptr, sizes, S = _pack_result(result, eval_step, device)
+    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
+    prof = default_geometry_profiles() if profiles is None else tuple(profiles)
+    mask, seen = _include_mask(include, pos, v, ptr, cz, aro, S, len(sizes))
+    r = _geometry_call(pos, v, ptr, cz, aro, prof, mask, clash_thresholds(clash_scale, radii), False, check=not seen)
+    inc = np.ones((S, len(sizes)), bool) if mask is None else mask.cpu().numpy().astype(bool)
+    clashes = r['n_clashes'].cpu().numpy().astype(np.int64)
+    tot = lambda k: np.where(inc, r[k].cpu().numpy().astype(np.int64), 0).sum(1)
+    return GeometryReport(inc.sum(1), (inc & (clashes == 0)).sum(1), np.where(inc, clashes, 0).sum(1), tot('n_crowded'), tot('n_degenerate'),
+                          tot('n_angles'), tot('n_torsions'), r['hist'].cpu().numpy(), prof, len(sizes), reference)
+
+
+def geometry_reference(molecules, profiles=None, atom_enc_mode='add_aromatic', device='cuda'):
+    """The reference distributions of ``sample_geometry`` from known ligands, through the same kernel and so under the same bond rule
+    (a reference made under another rule would not be comparable; no empirical distribution is part of this package).  ``molecules``:
+    a list of ``(pos [n, 3], v [n])``, or of records of ``molfile.read_sdf`` (taken through ``molfile.ligand_classes``, atoms of
+    elements outside the table left out).  Returns {name: counts [len(edges) + 1] int64} over ``profiles``."""
+    from . import molfile
+    prof = default_geometry_profiles() if profiles is None else tuple(profiles)
+    mols = [molfile.ligand_classes(m, atom_enc_mode, drop_unknown=True) if isinstance(m, dict) else m for m in molecules]
+    mols = [(np.asarray(p, dtype=np.float32).reshape(-1, 3), np.asarray(c, dtype=np.int64).reshape(-1)) for p, c in mols]
+    if not mols:
+        raise ValueError('a geometry reference needs at least one molecule')
+    ptr = torch.as_tensor(np.cumsum([0] + [len(c) for _, c in mols]), dtype=torch.int32)
+    pos, v, ptr = _pack(np.concatenate([p for p, _ in mols]), np.concatenate([c for _, c in mols]), None, ptr, device)
+    r = _geometry_call(pos, v, ptr, class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode), prof, None, None, False)
+    hist = r['hist'][0].cpu().numpy()
+    return {geometry_profile_name(p): hist[k, :len(p[4]) + 1].copy() for k, p in enumerate(prof)}

@@ -16,7 +16,12 @@ all`` or ``complete`` samples, and the shares of molecules without a ring and wi
 tables do), ``uniqueness`` (distinct molecules / samples) and ``mean_nearest`` from quality.sample_diversity, over ``--include all`` or
 ``complete`` samples, and with a known ligand -- ``--reference_sdf FILE`` (the first record, heavy atoms, elements of the table) or
 arrays ``ligand_pos`` [n, 3] and ``ligand_v`` [n] in ``--reference_npz`` -- the mean, median and largest similarity of the samples to
-it.  The fingerprint is this project's own circular one over its bond graph, not RDKit's RDKFingerprint: the numbers compare between
+it.  ``--geometry`` adds the local geometry of quality.sample_geometry over ``--include all`` or ``complete`` samples: the share of
+molecules without an internal clash (a pair more than 3 bonds apart and closer than 0.7 times the sum of the van der Waals radii: this
+project's own convention, not PoseBusters' bound and not a force field), the mean number of clashes, the crowded-atom and degenerate
+counts, and per angle and torsion type the count, the mean angle and -- with ``--reference_sdf FILE``, of which every record then makes
+up the reference (quality.geometry_reference: the same kernel, the same bond rule) -- the Jensen-Shannon distance.
+The fingerprint is this project's own circular one over its bond graph, not RDKit's RDKFingerprint: the numbers compare between
 runs of this tool, not with published tables.  The Jensen-Shannon distances need the reference's empirical distributions: they are
 loaded from ``utils.evaluation`` when the tool runs inside the reference repository (or with it on PYTHONPATH), or from
 ``--reference_npz FILE`` with arrays CC_2A, All_12A and atom_type (a file that holds a reference ligand may leave them out); without
@@ -65,15 +70,21 @@ def main(argv=None):
     ap.add_argument('--rings', action='store_true', help='also the ring ratios: the share of molecules with a ring of 3 .. 9 atoms')
     ap.add_argument('--diversity', action='store_true', help='also diversity, uniqueness and the similarity to a reference ligand '
                     "(this project's circular fingerprint, not RDKit's)")
-    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity: a known ligand, the first V2000 record of FILE')
+    ap.add_argument('--geometry', action='store_true', help='also bond angles, torsions and internal clashes (a convention of this '
+                    'project, not a pose checker)')
+    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity: a known ligand, the first V2000 record of FILE; '
+                    '--geometry: known ligands, every record of FILE')
     ap.add_argument('--reference_npz', type=str, default=None)
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
     eval_step = 'all' if args.eval_step == 'all' else int(args.eval_step)
 
-    reference = bond_reference = reference_ligand = None
+    reference = bond_reference = reference_ligand = geometry_reference = None
     if args.reference_sdf is not None:
-        mol = molfile.read_sdf(args.reference_sdf)[0]
+        records = molfile.read_sdf(args.reference_sdf)
+        mol = records[0]
+        if args.geometry:
+            geometry_reference = quality.geometry_reference(records, atom_enc_mode=args.atom_enc_mode, device=args.device)
         reference_ligand = molfile.ligand_classes(mol, args.atom_enc_mode, drop_unknown=True)
         if len(reference_ligand[1]) != len(mol['symbols']):
             print(f"reference ligand: {len(mol['symbols']) - len(reference_ligand[1])} atoms of elements outside the table left out")
@@ -89,7 +100,7 @@ def main(argv=None):
     if not files:
         raise SystemExit(f'no result_*.pt under {args.sample_path}')
     print(f'Load generated data done! {len(files)} examples in total.')
-    reports, connectivity, rings, diversity = [], [], [], []
+    reports, connectivity, rings, diversity, geometry = [], [], [], [], []
     for name in files:
         r = torch.load(name, map_location='cpu', weights_only=False)
         if args.connectivity:
@@ -101,6 +112,9 @@ def main(argv=None):
         if args.diversity:
             diversity.append(quality.sample_diversity(r, eval_step, 'complete' if args.include == 'complete' else 'all',
                                                       reference_ligand=reference_ligand, atom_enc_mode=args.atom_enc_mode, device=args.device))
+        if args.geometry:
+            geometry.append(quality.sample_geometry(r, eval_step, 'complete' if args.include == 'complete' else 'all', geometry_reference,
+                                                    atom_enc_mode=args.atom_enc_mode, device=args.device))
         reports.append(quality.sample_quality(r, eval_step, args.include, args.atom_enc_mode, reference, device=args.device))
     rep = quality.QualityReport.merged(reports)
     print(f'Evaluate done! {rep.n_samples} samples in total.')
@@ -144,6 +158,15 @@ def main(argv=None):
         out['diversity'] = dict(last_div, num_included=int(div.n_included[-1]), num_distinct=int(div.n_distinct[-1]))
         if eval_step == 'all':
             out['diversity']['curve'] = [nan_none(div.summary(s)) for s in range(div.num_frames)]
+    if args.geometry:
+        geo = quality.GeometryReport.merged(geometry)
+        print('\n'.join(geo.lines(-1)))
+        nan_none = lambda x: None if isinstance(x, float) and x != x else x
+        flat = lambda d: {k: ({q: nan_none(y) for q, y in x.items()} if isinstance(x, dict) else nan_none(x)) for k, x in d.items()}
+        out['geometry'] = dict(flat(geo.summary(-1)), num_included=int(geo.n_included[-1]),
+                               hist={n: geo.counts(n, -1).tolist() for n in geo.names})
+        if eval_step == 'all':
+            out['geometry']['curve'] = [flat(geo.summary(s)) for s in range(geo.num_frames)]
     result_path = os.path.join(args.sample_path, 'eval_results')
     os.makedirs(result_path, exist_ok=True)
     with open(os.path.join(result_path, 'quality.json'), 'w') as f:

@@ -1,7 +1,7 @@
 """Sampled ligands as SD files, without a chemistry toolkit:
 
     python tools/export_sdf.py --sample_path DIR --out DIR [--eval_step -1] [--only-complete] [--largest-fragment] [--ring-aromatic]
-                                [--unique]
+                                [--unique] [--clash-free]
 
 Reads the ``result_{i}.pt`` files a sampling driver wrote (sorted as tools/evaluate_samples.py sorts them), takes the frame
 ``--eval_step`` of every sample (default -1: the final poses), builds the bond graph on the GPU (quality.bond_graph: bonds from the
@@ -15,6 +15,9 @@ for a bond that also lies in a ring of 5 or 6 atoms, its order otherwise, so no 
 DESIGN.md section 3, "Fingerprints and diversity"), only the first.  It applies after ``--only-complete`` has chosen the samples, and
 the keys are of the whole molecule, also under ``--largest-fragment``: two samples whose largest fragments agree and whose small
 fragments differ are both written.
+``--clash-free`` writes only the samples without an internal clash (quality.geometry: no pair of atoms more than 3 bonds apart closer
+than 0.7 times the sum of their van der Waals radii; DESIGN.md section 3, "Local geometry" -- this project's convention, not a pose
+checker's); it applies before ``--unique`` chooses among what is left.
 Prints one line per file and returns the counts.
 """
 from __future__ import annotations
@@ -45,6 +48,7 @@ def main(argv=None):
     ap.add_argument('--ring-aromatic', action='store_true', help='bond type 4 only inside a ring of 5 or 6 atoms')
     ap.add_argument('--unique', action='store_true', help='of the samples with equal keys only the first; the keys are of the whole '
                     'molecule (also with --largest-fragment), taken after --only-complete')
+    ap.add_argument('--clash-free', action='store_true', help='only the samples without an internal clash')
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
     files = result_files(args.sample_path, args.eval_num_examples)
@@ -57,12 +61,17 @@ def main(argv=None):
         pos, v, ptr, sizes, _ = quality._pack_result(r, args.eval_step, args.device)
         g = quality.bond_graph(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, bond_profiles=(), return_fragments=True,
                                return_bonds=True, rings=args.ring_aromatic, device=args.device)
-        select = None
+        select = chosen = clash_free = None
+        if args.only_complete:
+            chosen = g.complete[0]
+        if args.clash_free:
+            clash_free = quality.geometry(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, profiles=(), device=args.device).clash_free[0]
+            chosen = clash_free if chosen is None else chosen & clash_free
+            select = clash_free.cpu().numpy()
         if args.unique:
             fp = quality.fingerprints(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, device=args.device)
-            chosen = g.complete[0] if args.only_complete else None
             first = fp.similarity(include=None if chosen is None else chosen[None])['first_equal'][0].cpu().numpy()
-            select = first == np.arange(len(sizes))
+            select = (first == np.arange(len(sizes))) & (True if select is None else select)
         mols = molfile.molecules_from_graph(g, pos, v, args.atom_enc_mode, 0, args.only_complete, args.largest_fragment,
                                             categories=g.ring_category if args.ring_aromatic else None, select=select)
         stem = os.path.basename(name)[:-3]
@@ -71,6 +80,8 @@ def main(argv=None):
         complete = int(g.complete[0].sum())
         print(f'{path}: {n} of {len(sizes)} samples written, {complete} complete')
         out[stem] = dict(path=path, written=n, samples=len(sizes), complete=complete)
+        if clash_free is not None:
+            out[stem]['clash_free'] = int(clash_free.sum())
     return out
 
 

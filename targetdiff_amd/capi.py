@@ -898,6 +898,45 @@ QUALITY_MAX_CLASSES, QUALITY_MAX_PROFILES, QUALITY_BINS = 64, 4, 128      # TD_Q
 QUALITY_ELEMENTS = (1, 6, 7, 8, 9, 15, 16, 17)                            # H C N O F P S Cl: the columns of the element counts
 
 
+def _hist_edges(edges, bins, what, name='edges'):
+    """The edges of one profile of a histogram of ``bins`` bins as contiguous float64 numpy: 1 .. bins - 1 of them, finite, ascending"""
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+    if not 1 <= e.size <= bins - 1:
+        raise ValueError(f'a {what} profile has 1 .. {bins - 1} edges (got {e.size})')
+    if not np.isfinite(e).all() or bool((e[1:] < e[:-1]).any()):
+        raise ValueError(f'the {name} of a {what} profile must be finite and ascending')
+    return e
+
+
+def _bond_ptr_input(bond_ptr, S, B):
+    if bond_ptr is not None and (bond_ptr.dim() != 1 or bond_ptr.numel() != S * B + 1 or bond_ptr.dtype != torch.int64):
+        raise ValueError(f'bond_ptr must be [{S * B + 1}] int64, as bond_graph returns it')
+
+
+def _include_arg(include):
+    """``include`` [S, B] bool / uint8 or None as the entry points' uint8 pointer"""
+    if include is not None and include.dtype == torch.bool:
+        include = include.view(torch.uint8)
+    return _ptr(include, torch.uint8, 'include')
+
+
+def _pack_args(pos, v, ligand_ptr, S, Nl, B, cz):
+    """The leading arguments of every entry point over a pack: (d_pos, d_v, d_ligand_ptr, S, N_l, B, class table, K).  A binding forms
+    them before it allocates anything, so a CPU tensor is refused first.  ``cz`` is the caller's: it outlives the call."""
+    return (_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'), S, Nl, B,
+            cz.ctypes.data_as(POINTER(c_int32)), cz.size)
+
+
+def _profile_args(struct, prof, dev):
+    """The checked profiles (their edges last) as the entry points' (array of ``struct``, P), the edges uploaded to ``dev``; the third
+    value keeps both alive up to the call.  torch's allocator reuses the edges' memory in stream order: after the kernel."""
+    edges = [torch.from_numpy(p[-1]).to(dev) for p in prof]
+    parr = (struct * max(len(prof), 1))()
+    for k, p in enumerate(prof):
+        parr[k] = struct(*p[:-1], n_edges=p[-1].size, d_edges=edges[k].data_ptr())
+    return ctypes.cast(parr, c_void_p), len(prof), (parr, edges)
+
+
 def _quality_inputs(pos, v, ligand_ptr, class_z, include, profiles, check=True):
     """Shapes, the class table and the profiles of a quality_report call; with ``check`` the offsets and the classes are looked at on
     the host (one synchronisation), as _clash_inputs does.  Returns (S, N_l, B, class table as int32 numpy, [(z1, z2, cutoff, edges
@@ -919,11 +958,7 @@ def _quality_inputs(pos, v, ligand_ptr, class_z, include, profiles, check=True):
         raise ValueError(f'at most {QUALITY_MAX_PROFILES} pair profiles (got {len(profiles)})')
     prof = []
     for z1, z2, cutoff, edges in profiles:
-        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
-        if not 1 <= e.size <= QUALITY_BINS - 1:
-            raise ValueError(f'a pair profile has 1 .. {QUALITY_BINS - 1} edges (got {e.size})')
-        if not np.isfinite(e).all() or bool((e[1:] < e[:-1]).any()):
-            raise ValueError('the edges of a pair profile must be finite and ascending')
+        e = _hist_edges(edges, QUALITY_BINS, 'pair')
         if any(z != 0 and z not in QUALITY_ELEMENTS for z in (int(z1), int(z2))):
             raise ValueError(f'a pair profile names elements of {QUALITY_ELEMENTS} or 0 for any (got {z1}, {z2})')
         if not float(cutoff) > 0.0:
@@ -946,24 +981,15 @@ def quality_report(pos, v, ligand_ptr, class_z, profiles=(), include=None, retur
     int64 and counts [S, 8] int64."""
     S, Nl, B, cz, prof = _quality_inputs(pos, v, ligand_ptr, class_z, include, profiles, check)
     lib = load_library()
-    _ptr(pos, torch.float32, 'pos')                   # a CPU tensor is refused before anything is allocated
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
     dev = pos.device
-    P = len(prof)
-    edges = [torch.from_numpy(e).to(dev) for _, _, _, e in prof]            # torch's allocator reuses their memory in stream order: after the kernel
-    parr = (TdPairProfile * max(P, 1))()
-    for p, (z1, z2, cutoff, e) in enumerate(prof):
-        parr[p] = TdPairProfile(z1, z2, cutoff, e.size, 0, edges[p].data_ptr())
+    parr, P, _keep = _profile_args(TdPairProfile, prof, dev)
     out = dict(nr_bonds=torch.empty(S, Nl, dtype=torch.int32, device=dev) if return_nr_bonds else None,
                stable_atoms=torch.empty(S, B, dtype=torch.int32, device=dev), mol_stable=torch.empty(S, B, dtype=torch.uint8, device=dev),
                hist=torch.empty(S, P, QUALITY_BINS, dtype=torch.int64, device=dev), counts=torch.empty(S, 8, dtype=torch.int64, device=dev))
-    if include is not None and include.dtype == torch.bool:
-        include = include.view(torch.uint8)
     with _on(dev):
-        _check(lib.td_quality_report(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
-                                     S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _ptr(include, torch.uint8, 'include'),
-                                     ctypes.cast(parr, c_void_p), P, _ptr(out['nr_bonds']), _ptr(out['stable_atoms']),
-                                     _ptr(out['mol_stable']), _ptr(out['hist']), _ptr(out['counts']), _stream(dev)),
-               'td_quality_report')
+        _check(lib.td_quality_report(*pack, _include_arg(include), parr, P, _ptr(out['nr_bonds']), _ptr(out['stable_atoms']),
+                                     _ptr(out['mol_stable']), _ptr(out['hist']), _ptr(out['counts']), _stream(dev)), 'td_quality_report')
     return out
 
 
@@ -984,11 +1010,7 @@ def _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, include, profiles,
         raise ValueError(f'at most {BOND_MAX_PROFILES} bond profiles (got {len(profiles)})')
     prof = []
     for z1, z2, category, edges in profiles:
-        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
-        if not 1 <= e.size <= BOND_BINS - 1:
-            raise ValueError(f'a bond profile has 1 .. {BOND_BINS - 1} edges (got {e.size})')
-        if not np.isfinite(e).all() or bool((e[1:] < e[:-1]).any()):
-            raise ValueError('the edges of a bond profile must be finite and ascending')
+        e = _hist_edges(edges, BOND_BINS, 'bond')
         if any(z != 0 and z not in QUALITY_ELEMENTS for z in (int(z1), int(z2))):
             raise ValueError(f'a bond profile names elements of {QUALITY_ELEMENTS} or 0 for any (got {z1}, {z2})')
         if int(category) not in (0, 1, 2, 3, 4):
@@ -1013,23 +1035,15 @@ def bond_graph(pos, v, ligand_ptr, class_z, class_aromatic=None, profiles=(), in
     without ``return_fragments``), bond_hist [S, P, 128] int64 and bond_ptr [S * B + 1] int64 (None without ``return_bond_ptr``)."""
     S, Nl, B, cz, aro, prof = _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, include, profiles, check)
     lib = load_library()
-    _ptr(pos, torch.float32, 'pos')                   # a CPU tensor is refused before anything is allocated
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
     dev = pos.device
-    P = len(prof)
-    edges = [torch.from_numpy(e).to(dev) for _, _, _, e in prof]
-    parr = (TdBondProfile * max(P, 1))()
-    for p, (z1, z2, category, e) in enumerate(prof):
-        parr[p] = TdBondProfile(z1, z2, category, e.size, edges[p].data_ptr())
+    parr, P, _keep = _profile_args(TdBondProfile, prof, dev)
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
     out = dict(n_bonds=i32(S, B), n_fragments=i32(S, B), largest_fragment=i32(S, B), fragment=i32(S, Nl) if return_fragments else None,
                bond_hist=torch.empty(S, P, BOND_BINS, dtype=torch.int64, device=dev),
                bond_ptr=torch.empty(S * B + 1, dtype=torch.int64, device=dev) if return_bond_ptr else None)
-    if include is not None and include.dtype == torch.bool:
-        include = include.view(torch.uint8)
     with _on(dev):
-        _check(lib.td_bond_graph(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
-                                 S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _ptr(include, torch.uint8, 'include'),
-                                 _aromatic_arg(aro), ctypes.cast(parr, c_void_p), P, _ptr(out['n_bonds']), _ptr(out['n_fragments']),
+        _check(lib.td_bond_graph(*pack, _include_arg(include), _aromatic_arg(aro), parr, P, _ptr(out['n_bonds']), _ptr(out['n_fragments']),
                                  _ptr(out['largest_fragment']), _ptr(out['fragment']), _ptr(out['bond_hist']), _ptr(out['bond_ptr']),
                                  _stream(dev)), 'td_bond_graph')
     return out
@@ -1041,20 +1055,17 @@ def bond_list(pos, v, ligand_ptr, class_z, class_aromatic, bond_ptr, check=True)
     device tensors: bond_atoms [nb, 2] int32 (indices along the pack's atom axis), bond_order and bond_category [nb] uint8 and
     bond_length [nb] float64."""
     S, Nl, B, cz, aro, _ = _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, None, (), check)
-    if bond_ptr.dim() != 1 or bond_ptr.numel() != S * B + 1 or bond_ptr.dtype != torch.int64:
-        raise ValueError(f'bond_ptr must be [{S * B + 1}] int64, as bond_graph returns it')
+    _bond_ptr_input(bond_ptr, S, B)
     lib = load_library()
-    _ptr(pos, torch.float32, 'pos')
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
     _ptr(bond_ptr, torch.int64, 'bond_ptr')
     dev = pos.device
     nb = int(bond_ptr[-1])
     out = dict(bond_atoms=torch.empty(nb, 2, dtype=torch.int32, device=dev), bond_order=torch.empty(nb, dtype=torch.uint8, device=dev),
                bond_category=torch.empty(nb, dtype=torch.uint8, device=dev), bond_length=torch.empty(nb, dtype=torch.float64, device=dev))
     with _on(dev):
-        _check(lib.td_bond_list(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
-                                S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _aromatic_arg(aro), _ptr(bond_ptr), nb,
-                                _ptr(out['bond_atoms']), _ptr(out['bond_order']), _ptr(out['bond_category']), _ptr(out['bond_length']),
-                                _stream(dev)), 'td_bond_list')
+        _check(lib.td_bond_list(*pack, _aromatic_arg(aro), _ptr(bond_ptr), nb, _ptr(out['bond_atoms']), _ptr(out['bond_order']),
+                                _ptr(out['bond_category']), _ptr(out['bond_length']), _stream(dev)), 'td_bond_list')
     return out
 
 
@@ -1069,10 +1080,9 @@ def ring_report(pos, v, ligand_ptr, class_z, class_aromatic=None, include=None, 
     [S, N_l] int32 (None without ``return_atom_ring``), ring_hist [S, 32] int64, and bond_ring [nb] int16 / bond_category [nb] uint8
     (the ring-aware category; both None without ``bond_ptr``)."""
     S, Nl, B, cz, aro, _ = _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, include, (), check)
-    if bond_ptr is not None and (bond_ptr.dim() != 1 or bond_ptr.numel() != S * B + 1 or bond_ptr.dtype != torch.int64):
-        raise ValueError(f'bond_ptr must be [{S * B + 1}] int64, as bond_graph returns it')
+    _bond_ptr_input(bond_ptr, S, B)
     lib = load_library()
-    _ptr(pos, torch.float32, 'pos')                   # a CPU tensor is refused before anything is allocated
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
     dev = pos.device
     nb = 0
     if bond_ptr is not None:
@@ -1084,14 +1094,10 @@ def ring_report(pos, v, ligand_ptr, class_z, class_aromatic=None, include=None, 
                ring_hist=torch.empty(S, RING_BITS, dtype=torch.int64, device=dev),
                bond_ring=torch.empty(nb, dtype=torch.int16, device=dev) if bond_ptr is not None else None,
                bond_category=torch.empty(nb, dtype=torch.uint8, device=dev) if bond_ptr is not None else None)
-    if include is not None and include.dtype == torch.bool:
-        include = include.view(torch.uint8)
     with _on(dev):
-        _check(lib.td_ring_report(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
-                                  S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _ptr(include, torch.uint8, 'include'),
-                                  _aromatic_arg(aro), _ptr(bond_ptr), nb, _ptr(mask), _ptr(out['n_ring_bonds']), _ptr(out['n_ring_atoms']),
-                                  _ptr(out['atom_ring']), _ptr(out['ring_hist']), _ptr(out['bond_ring']), _ptr(out['bond_category']),
-                                  _stream(dev)), 'td_ring_report')
+        _check(lib.td_ring_report(*pack, _include_arg(include), _aromatic_arg(aro), _ptr(bond_ptr), nb, _ptr(mask), _ptr(out['n_ring_bonds']),
+                                  _ptr(out['n_ring_atoms']), _ptr(out['atom_ring']), _ptr(out['ring_hist']), _ptr(out['bond_ring']),
+                                  _ptr(out['bond_category']), _stream(dev)), 'td_ring_report')
     out['ring_mask'] = mask.to(torch.int64) & 0xffffffff              # torch has no arithmetic on uint32: the word, widened
     return out
 
@@ -1120,12 +1126,7 @@ def _geometry_profiles(profiles):
             raise ValueError(f"category 0 (any) .. 4 and ring 0 / 'any', 1 / 'chain' or 2 / 'ring' (got {category}, {ring!r})")
         if kind == 1 and (int(category) != 0 or ring != 0):
             raise ValueError('an angle profile takes no category and no ring filter')
-        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
-        if not 1 <= e.size <= GEOM_BINS - 1:
-            raise ValueError(f'a geometry profile has 1 .. {GEOM_BINS - 1} edges (got {e.size})')
-        if not np.isfinite(e).all() or bool((e[1:] < e[:-1]).any()):
-            raise ValueError('the cosine edges of a geometry profile must be finite and ascending')
-        prof.append((kind, z + (0,) * (4 - len(z)), int(category), ring, e))
+        prof.append((kind, z + (0,) * (4 - len(z)), int(category), ring, _hist_edges(edges, GEOM_BINS, 'geometry', 'cosine edges')))
     return prof
 
 
@@ -1143,8 +1144,7 @@ def geometry_report(pos, v, ligand_ptr, class_z, class_aromatic=None, profiles=(
     need_ring = any(p[3] != 0 for p in prof)
     if need_ring and (bond_ptr is None or bond_ring is None):
         raise ValueError('a ring filter needs bond_ptr of bond_graph and bond_ring of ring_report on the same pack')
-    if bond_ptr is not None and (bond_ptr.dim() != 1 or bond_ptr.numel() != S * B + 1 or bond_ptr.dtype != torch.int64):
-        raise ValueError(f'bond_ptr must be [{S * B + 1}] int64, as bond_graph returns it')
+    _bond_ptr_input(bond_ptr, S, B)
     if bond_ring is not None and (bond_ptr is None or bond_ring.dim() != 1 or bond_ring.dtype != torch.int16):
         raise ValueError('bond_ring must be [n_bonds] int16, as ring_report returns it, and comes with bond_ptr')
     thr = None
@@ -1153,24 +1153,16 @@ def geometry_report(pos, v, ligand_ptr, class_z, class_aromatic=None, profiles=(
         if thr.size != 64 or not np.isfinite(thr).all():
             raise ValueError('clash_threshold is a finite [8, 8] table over H C N O F P S Cl')
     lib = load_library()
-    _ptr(pos, torch.float32, 'pos')                   # a CPU tensor is refused before anything is allocated
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
     dev = pos.device
-    P = len(prof)
-    edges = [torch.from_numpy(e).to(dev) for *_, e in prof]
-    parr = (TdGeometryProfile * max(P, 1))()
-    for p, (kind, z, category, ring, e) in enumerate(prof):
-        parr[p] = TdGeometryProfile(kind, (c_int32 * 4)(*z), category, ring, e.size, edges[p].data_ptr())
+    parr, P, _keep = _profile_args(TdGeometryProfile, prof, dev)
     nb = int(bond_ring.numel()) if bond_ring is not None else 0
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
     out = dict(n_angles=i32(S, B), n_torsions=i32(S, B), n_degenerate=i32(S, B), n_crowded=i32(S, B),
                n_clashes=i32(S, B) if thr is not None else None, atom_clash=i32(S, Nl) if thr is not None and return_atom_clash else None,
                hist=torch.empty(S, P, GEOM_BINS, dtype=torch.int64, device=dev))
-    if include is not None and include.dtype == torch.bool:
-        include = include.view(torch.uint8)
     with _on(dev):
-        _check(lib.td_geometry_report(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
-                                      S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _ptr(include, torch.uint8, 'include'),
-                                      _aromatic_arg(aro), ctypes.cast(parr, c_void_p), P, _ptr(bond_ptr if bond_ring is not None else None), nb,
+        _check(lib.td_geometry_report(*pack, _include_arg(include), _aromatic_arg(aro), parr, P, _ptr(bond_ptr if bond_ring is not None else None), nb,
                                       _ptr(bond_ring), None if thr is None else thr.ctypes.data_as(POINTER(ctypes.c_double)),
                                       _ptr(out['n_angles']), _ptr(out['n_torsions']), _ptr(out['n_degenerate']), _ptr(out['n_crowded']),
                                       _ptr(out['n_clashes']), _ptr(out['atom_clash']), _ptr(out['hist']), _stream(dev)), 'td_geometry_report')
@@ -1199,16 +1191,14 @@ def fingerprint(pos, v, ligand_ptr, class_z, class_aromatic=None, radius=2, key_
     ``return_atom_keys``; 0 for an atom of no class)."""
     S, Nl, B, cz, aro, radius, key_rounds = _fingerprint_inputs(pos, v, ligand_ptr, class_z, class_aromatic, radius, key_rounds, check)
     lib = load_library()
-    _ptr(pos, torch.float32, 'pos')                   # a CPU tensor is refused before anything is allocated
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
     dev = pos.device
     out = dict(fp_words=torch.empty(S, B, FP_WORDS, dtype=torch.int64, device=dev), n_bits=torch.empty(S, B, dtype=torch.int32, device=dev),
                key=torch.empty(S, B, dtype=torch.int64, device=dev),
                atom_key=torch.zeros(S, Nl, dtype=torch.int64, device=dev) if return_atom_keys else None)
     with _on(dev):
-        _check(lib.td_fingerprint(_ptr(pos, torch.float32, 'pos'), _ptr(v, torch.int64, 'v'), _ptr(ligand_ptr, torch.int32, 'ligand_ptr'),
-                                  S, Nl, B, cz.ctypes.data_as(POINTER(c_int32)), cz.size, _aromatic_arg(aro), radius, key_rounds,
-                                  _ptr(out['fp_words']), _ptr(out['n_bits']), _ptr(out['key']), _ptr(out['atom_key']), _stream(dev)),
-               'td_fingerprint')
+        _check(lib.td_fingerprint(*pack, _aromatic_arg(aro), radius, key_rounds, _ptr(out['fp_words']), _ptr(out['n_bits']), _ptr(out['key']),
+                                  _ptr(out['atom_key']), _stream(dev)), 'td_fingerprint')
     return out
 
 
@@ -1243,11 +1233,9 @@ def fingerprint_similarity(fp_words, n_bits, key, include=None, q_words=None, q_
                first_equal=torch.empty(S, B, dtype=torch.int32, device=dev),
                common=torch.empty(S, B, B, dtype=torch.int32, device=dev) if return_common else None,
                query_common=torch.empty(S, B, Q, dtype=torch.int32, device=dev) if Q else None, query_sim=None)
-    if include is not None and include.dtype == torch.bool:
-        include = include.view(torch.uint8)
     with _on(dev):
         _check(lib.td_fingerprint_similarity(_ptr(fp_words), _ptr(n_bits, torch.int32, 'n_bits'), _ptr(key, torch.int64, 'key'), S, B,
-                                             _ptr(include, torch.uint8, 'include'), _ptr(q_words, torch.int64, 'q_words') if Q else None, Q,
+                                             _include_arg(include), _ptr(q_words, torch.int64, 'q_words') if Q else None, Q,
                                              _ptr(out['sim_sum']), _ptr(out['sim_max']), _ptr(out['first_equal']), _ptr(out['common']),
                                              _ptr(out['query_common']), _stream(dev)), 'td_fingerprint_similarity')
     if Q:

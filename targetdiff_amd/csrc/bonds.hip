@@ -50,9 +50,7 @@ __global__ __launch_bounds__(MAXN) void bond_graph_kernel(TdBondArgs a) {
     s_size[tid] = 0;
     if (tid < 2) s_changed[tid] = 0;
     if (tid == 0) s_nb = s_nf = s_big = 0;
-    __syncthreads();
     bg_load<MAXN>(a, m, s_elem, s_at);
-    __syncthreads();
 
     // ---- the row of atom tid (td_bond_graph.h); bonds tid < j are counted and enter the histograms
     int up = 0;
@@ -63,15 +61,7 @@ __global__ __launch_bounds__(MAXN) void bond_graph_kernel(TdBondArgs a) {
             for (int p = 0; p < P; ++p) {
                 const int e1 = s_pe1[p], e2 = s_pe2[p], pc = s_pcat[p];
                 const bool match = ((e1 < 0 || ei == e1) && (e2 < 0 || ej == e2)) || ((e1 < 0 || ej == e1) && (e2 < 0 || ei == e2));
-                if (match && (pc == 0 || pc == cat)) {
-                    const double *edges = s_pedges[p];
-                    int lo = 0, hi = s_pn[p];                                   // numpy.searchsorted(edges, d, 'left'); <= 7 halvings
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        if (edges[mid] < d) lo = mid + 1; else hi = mid;
-                    }
-                    atomicAdd(&s_hist[p][lo], 1u);
-                }
+                if (match && (pc == 0 || pc == cat)) atomicAdd(&s_hist[p][td_searchsorted_left(s_pedges[p], s_pn[p], d)], 1u);
             }
         });
     }
@@ -123,10 +113,7 @@ __global__ __launch_bounds__(MAXN) void bond_graph_kernel(TdBondArgs a) {
         a.n_fragments[m.mol] = s_nf;
         a.largest[m.mol] = s_big;
     }
-    for (int k = tid; k < P * BG_BINS; k += MAXN) {
-        const unsigned int c = (&s_hist[0][0])[k];
-        if (c) atomicAdd(&a.hist[(size_t)m.s * a.P * BG_BINS + k], (unsigned long long)c);
-    }
+    bg_flush_hist<MAXN>(&s_hist[0][0], P * BG_BINS, a.hist + (size_t)m.s * a.P * BG_BINS);
 }
 
 // ptr[k] = sum of max(n_bonds[0 .. k), 0), k = 0 .. M: every lane sums a contiguous run, the 1024 run sums are scanned in LDS
@@ -164,9 +151,7 @@ __global__ __launch_bounds__(MAXN) void bond_list_kernel(TdBondArgs a) {
     const int n = m.n;
     td_bond_thresholds(s_thr, tid, MAXN);
     if (tid < TD_QUALITY_MAX_CLASSES) s_elem[tid] = tid < a.K ? a.elem[tid] : -1;
-    __syncthreads();
     bg_load<MAXN>(a, m, s_elem, s_at);
-    __syncthreads();
     float4 me = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
     if (tid < n) me = s_at[tid];
     const int ci = __float_as_int(me.w), ei = ci & 7;
@@ -211,10 +196,7 @@ int td_launch_bond_graph(const TdBondArgs &a, hipStream_t s) {
         if (a.bond_ptr) TD_CHECK_HIP(hipMemsetAsync(a.bond_ptr, 0, sizeof(int64_t), s));
         return TD_OK;
     }
-    bond_graph_kernel<BG_SMALL><<<dim3((unsigned)M), dim3(BG_SMALL), 0, s>>>(a);
-    TD_CHECK_HIP(hipGetLastError());
-    bond_graph_kernel<BG_MAX><<<dim3((unsigned)M), dim3(BG_MAX), 0, s>>>(a);
-    TD_CHECK_HIP(hipGetLastError());
+    if (const int rc = bg_launch_pair(bond_graph_kernel<BG_SMALL>, bond_graph_kernel<BG_MAX>, a, M, s)) return rc;
     if (a.bond_ptr) {
         bond_ptr_kernel<<<dim3(1), dim3(BG_SCAN_THREADS), 0, s>>>(a.n_bonds, M, a.bond_ptr);
         TD_CHECK_HIP(hipGetLastError());
@@ -225,9 +207,5 @@ int td_launch_bond_graph(const TdBondArgs &a, hipStream_t s) {
 int td_launch_bond_list(const TdBondArgs &a, hipStream_t s) {
     const int64_t M = (int64_t)a.S * a.B;
     if (M == 0 || a.capacity == 0) return TD_OK;
-    bond_list_kernel<BG_SMALL><<<dim3((unsigned)M), dim3(BG_SMALL), 0, s>>>(a);
-    TD_CHECK_HIP(hipGetLastError());
-    bond_list_kernel<BG_MAX><<<dim3((unsigned)M), dim3(BG_MAX), 0, s>>>(a);
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    return bg_launch_pair(bond_list_kernel<BG_SMALL>, bond_list_kernel<BG_MAX>, a, M, s);
 }

@@ -5,34 +5,20 @@
 #include "td_internal.h"
 
 namespace {
-// the checks and the fields the entry points share: sizes, the class table and the aromatic flags
+// the checks and the fields the entry points share: sizes, the class table, the aromatic flags and, of the entry points that take the
+// bond list's offsets, its length
 int bond_pack(const char *who, TdBondArgs &a, const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l,
-              int64_t B, const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic) {
-    if (S < 0 || B < 0 || N_l < 0 || N_l > 0x7fffffff || S > 0x7fffffff || B > 0x7fffffff || S * B > 0x7fffffff) {
-        td_set_error("%s: bad argument (S = %lld, B = %lld, N_l = %lld; S * B and N_l must fit 31 bits)", who, (long long)S, (long long)B,
-                     (long long)N_l);
-        return TD_EINVAL;
-    }
-    if (K < 1 || K > TD_QUALITY_MAX_CLASSES || !class_atomic_number) {
-        td_set_error("%s: the class table must have 1 .. %d entries (got %d)", who, TD_QUALITY_MAX_CLASSES, (int)K);
-        return TD_EINVAL;
-    }
-    for (int c = 0; c < K; ++c) {
-        const int e = td_element_index(class_atomic_number[c]);
-        if (e < 0) {
-            td_set_error("%s: class %d has atomic number %d, outside the bond-length table (H C N O F P S Cl)", who, c,
-                         (int)class_atomic_number[c]);
-            return TD_EINVAL;
-        }
-        a.elem[c] = (int8_t)e;
+              int64_t B, const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, int64_t n_bonds = 0) {
+    if (n_bonds < 0) { td_set_error("%s: bad argument (n_bonds = %lld)", who, (long long)n_bonds); return TD_EINVAL; }
+    if (const int rc = td_check_pack(who, S, N_l, B, class_atomic_number, K, a.elem)) return rc;
+    for (int c = 0; c < K; ++c)
         if (class_aromatic && class_aromatic[c]) a.aromatic |= 1ull << c;
-    }
     if (S > 0 && B > 0 && (!d_ligand_ptr || (N_l > 0 && (!d_pos || !d_v)))) {
         td_set_error("%s: null pointer", who);
         return TD_EINVAL;
     }
     a.pos = d_pos; a.v = d_v; a.lptr = d_ligand_ptr; a.Nl = N_l;
-    a.S = (int)S; a.B = (int)B; a.K = K;
+    a.S = (int)S; a.B = (int)B; a.K = K; a.capacity = n_bonds;
     return TD_OK;
 }
 }  // namespace
@@ -49,8 +35,8 @@ extern "C" int td_bond_graph(const float *d_pos, const int64_t *d_v, const int32
     }
     for (int p = 0; p < P; ++p) {
         const td_bond_profile &pf = profiles[p];
-        const int e1 = pf.z1 == 0 ? -1 : td_element_index(pf.z1), e2 = pf.z2 == 0 ? -1 : td_element_index(pf.z2);
-        if ((pf.z1 != 0 && e1 < 0) || (pf.z2 != 0 && e2 < 0)) {
+        const int e1 = td_profile_element(pf.z1), e2 = td_profile_element(pf.z2);
+        if (e1 < -1 || e2 < -1) {
             td_set_error("%s: profile %d names an atomic number outside the table (%d, %d; 0 = any)", who, p, (int)pf.z1, (int)pf.z2);
             return TD_EINVAL;
         }
@@ -82,13 +68,12 @@ extern "C" int td_bond_list(const float *d_pos, const int64_t *d_v, const int32_
                             double *d_bond_length, void *stream) {
     const char *who = "td_bond_list";
     TdBondArgs a;
-    if (n_bonds < 0) { td_set_error("%s: bad argument (n_bonds = %lld)", who, (long long)n_bonds); return TD_EINVAL; }
-    if (const int rc = bond_pack(who, a, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic)) return rc;
+    if (const int rc = bond_pack(who, a, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, n_bonds)) return rc;
     if (S > 0 && B > 0 && n_bonds > 0 && (!d_bond_ptr || !d_bond_atoms || !d_bond_order || !d_bond_category || !d_bond_length)) {
         td_set_error("%s: null pointer", who);
         return TD_EINVAL;
     }
-    a.bond_ptr = const_cast<int64_t *>(d_bond_ptr); a.capacity = n_bonds;
+    a.bond_ptr = const_cast<int64_t *>(d_bond_ptr);
     a.bond_atoms = d_bond_atoms; a.bond_order = d_bond_order; a.bond_category = d_bond_category; a.bond_length = d_bond_length;
     return td_launch_bond_list(a, static_cast<hipStream_t>(stream));
 }
@@ -100,8 +85,7 @@ extern "C" int td_ring_report(const float *d_pos, const int64_t *d_v, const int3
                               uint8_t *d_bond_category, void *stream) {
     const char *who = "td_ring_report";
     TdBondArgs a;
-    if (n_bonds < 0) { td_set_error("%s: bad argument (n_bonds = %lld)", who, (long long)n_bonds); return TD_EINVAL; }
-    if (const int rc = bond_pack(who, a, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic)) return rc;
+    if (const int rc = bond_pack(who, a, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, n_bonds)) return rc;
     if ((d_bond_ring || d_bond_category) && !d_bond_ptr) {
         td_set_error("%s: the per-bond outputs need d_bond_ptr of td_bond_graph", who);
         return TD_EINVAL;
@@ -111,7 +95,7 @@ extern "C" int td_ring_report(const float *d_pos, const int64_t *d_v, const int3
         return TD_EINVAL;
     }
     a.include = d_include;
-    a.bond_ptr = const_cast<int64_t *>(d_bond_ptr); a.capacity = n_bonds;
+    a.bond_ptr = const_cast<int64_t *>(d_bond_ptr);
     a.ring_mask = d_ring_mask; a.n_ring_bonds = d_n_ring_bonds; a.n_ring_atoms = d_n_ring_atoms; a.atom_ring = d_atom_ring;
     a.ring_hist = reinterpret_cast<unsigned long long *>(d_ring_hist); a.bond_ring = d_bond_ring; a.bond_category = d_bond_category;
     return td_launch_ring_report(a, static_cast<hipStream_t>(stream));
@@ -179,7 +163,6 @@ extern "C" int td_geometry_report(const float *d_pos, const int64_t *d_v, const 
         td_set_error("%s: 0 .. %d geometry profiles (got %d)", who, TD_GEOM_MAX_PROFILES, (int)P);
         return TD_EINVAL;
     }
-    if (n_bonds < 0) { td_set_error("%s: bad argument (n_bonds = %lld)", who, (long long)n_bonds); return TD_EINVAL; }
     for (int p = 0; p < P; ++p) {
         const td_geometry_profile &pf = profiles[p];
         if (pf.kind != 1 && pf.kind != 2) {
@@ -187,8 +170,8 @@ extern "C" int td_geometry_report(const float *d_pos, const int64_t *d_v, const 
             return TD_EINVAL;
         }
         for (int q = 0; q < 4; ++q) {
-            const int e = pf.z[q] == 0 ? -1 : td_element_index(pf.z[q]);
-            if (pf.z[q] != 0 && e < 0) {
+            const int e = td_profile_element(pf.z[q]);
+            if (e < -1) {
                 td_set_error("%s: profile %d names an atomic number outside the table (%d; 0 = any)", who, p, (int)pf.z[q]);
                 return TD_EINVAL;
             }
@@ -214,14 +197,14 @@ extern "C" int td_geometry_report(const float *d_pos, const int64_t *d_v, const 
         g.kind[p] = (int8_t)pf.kind; g.cat[p] = (int8_t)pf.category; g.ring[p] = (int8_t)pf.ring; g.n_edges[p] = (int16_t)pf.n_edges;
         g.edges[p] = pf.d_edges;
     }
-    if (const int rc = bond_pack(who, g.b, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic)) return rc;
+    if (const int rc = bond_pack(who, g.b, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, n_bonds)) return rc;
     if ((S > 0 && P > 0 && !d_hist) ||
         (S > 0 && B > 0 && (!d_n_angles || !d_n_torsions || !d_n_degenerate || !d_n_crowded || (clash_threshold && !d_n_clashes)))) {
         td_set_error("%s: null pointer", who);
         return TD_EINVAL;
     }
     g.b.include = d_include; g.P = P;
-    g.b.bond_ptr = const_cast<int64_t *>(d_bond_ptr); g.b.capacity = n_bonds; g.b.bond_ring = const_cast<uint16_t *>(d_bond_ring);
+    g.b.bond_ptr = const_cast<int64_t *>(d_bond_ptr); g.b.bond_ring = const_cast<uint16_t *>(d_bond_ring);
     if (clash_threshold) {
         g.clash = true;
         for (int k = 0; k < 64; ++k) g.clash_thr[k] = clash_threshold[k];

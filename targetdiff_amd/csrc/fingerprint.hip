@@ -63,9 +63,7 @@ __global__ __launch_bounds__(MAXN) void fingerprint_kernel(TdBondArgs a) {
         s_sum = 0ull;
         s_valid = s_bonds = s_pop = 0;
     }
-    __syncthreads();
     bg_load<MAXN>(a, m, s_elem, s_at);
-    __syncthreads();
     int up = 0;
     if (tid < n) up = bg_rows<MAXN>(n, s_at, s_thr, s_row, [](int, int, int, double) {});   // a lane reads back its own row only
 
@@ -148,11 +146,7 @@ __global__ __launch_bounds__(MAXN) void fingerprint_kernel(TdBondArgs a) {
 int td_launch_fingerprint(const TdBondArgs &a, hipStream_t s) {
     const int64_t M = (int64_t)a.S * a.B;
     if (M == 0) return TD_OK;
-    fingerprint_kernel<BG_SMALL><<<dim3((unsigned)M), dim3(BG_SMALL), 0, s>>>(a);
-    TD_CHECK_HIP(hipGetLastError());
-    fingerprint_kernel<BG_MAX><<<dim3((unsigned)M), dim3(BG_MAX), 0, s>>>(a);
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    return bg_launch_pair(fingerprint_kernel<BG_SMALL>, fingerprint_kernel<BG_MAX>, a, M, s);
 }
 
 __global__ __launch_bounds__(64) void similarity_kernel(TdSimArgs a) {

@@ -25,16 +25,6 @@ __device__ __forceinline__ double gm_dot(double ax, double ay, double az, double
 // (a b) - (c d), each product and the difference rounded on its own
 __device__ __forceinline__ double gm_det(double a, double b, double c, double d) { return td_add_rn64(td_mul_rn64(a, b), -td_mul_rn64(c, d)); }
 
-// numpy.searchsorted(edges, c, 'left'); <= 7 halvings
-__device__ __forceinline__ int gm_bin(const double *edges, int n, double c) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (edges[mid] < c) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ bool gm_z(int want, int e) { return want < 0 || want == e; }
 
 template <int MAXN>
@@ -75,9 +65,7 @@ __global__ __launch_bounds__(MAXN) void geometry_kernel(TdGeomArgs g) {
     }
     for (int k = tid; k < P * GM_BINS; k += MAXN) (&s_hist[0][0])[k] = 0u;
     if (tid < 5) s_cnt[tid] = 0;
-    __syncthreads();
     bg_load<MAXN>(a, m, s_elem, s_at);
-    __syncthreads();
 
     // ---- the row of atom tid, its degree and, under the cap, its neighbours in ascending order
     int up = 0, deg = 0;
@@ -127,7 +115,7 @@ __global__ __launch_bounds__(MAXN) void geometry_kernel(TdGeomArgs g) {
                     if (s_pkind[p] != 1 || !gm_z(s_pz[p][1], ej)) continue;
                     const int z0 = s_pz[p][0], z2 = s_pz[p][2];
                     if ((gm_z(z0, ei) && gm_z(z2, ek)) || (gm_z(z0, ek) && gm_z(z2, ei)))
-                        atomicAdd(&s_hist[p][gm_bin(s_pedges[p], s_pn[p], c)], 1u);
+                        atomicAdd(&s_hist[p][td_searchsorted_left(s_pedges[p], s_pn[p], c)], 1u);
                 }
             }
         }
@@ -177,7 +165,7 @@ __global__ __launch_bounds__(MAXN) void geometry_kernel(TdGeomArgs g) {
                 const bool rev = gm_z(z[0], el) && gm_z(z[1], ek) && gm_z(z[2], ej) && gm_z(z[3], ei);
                 if (!fwd && !rev) continue;
                 if ((s_pcat[p] != 0 && s_pcat[p] != cat) || (s_pring[p] != 0 && s_pring[p] != rs)) continue;
-                atomicAdd(&s_hist[p][gm_bin(s_pedges[p], s_pn[p], c)], 1u);
+                atomicAdd(&s_hist[p][td_searchsorted_left(s_pedges[p], s_pn[p], c)], 1u);
             }
         }
     }
@@ -246,19 +234,12 @@ __global__ __launch_bounds__(MAXN) void geometry_kernel(TdGeomArgs g) {
         g.n_crowded[m.mol] = s_cnt[3];
         if (g.clash) g.n_clashes[m.mol] = s_cnt[4];
     }
-    for (int k = tid; k < P * GM_BINS; k += MAXN) {
-        const unsigned int c = (&s_hist[0][0])[k];
-        if (c) atomicAdd(&g.hist[(size_t)m.s * g.P * GM_BINS + k], (unsigned long long)c);
-    }
+    bg_flush_hist<MAXN>(&s_hist[0][0], P * GM_BINS, g.hist + (size_t)m.s * g.P * GM_BINS);
 }
 
 int td_launch_geometry_report(const TdGeomArgs &g, hipStream_t s) {
     const int64_t M = (int64_t)g.b.S * g.b.B;
     if (g.b.S > 0 && g.P > 0) TD_CHECK_HIP(hipMemsetAsync(g.hist, 0, (size_t)g.b.S * g.P * GM_BINS * sizeof(unsigned long long), s));
     if (M == 0) return TD_OK;
-    geometry_kernel<BG_SMALL><<<dim3((unsigned)M), dim3(BG_SMALL), 0, s>>>(g);
-    TD_CHECK_HIP(hipGetLastError());
-    geometry_kernel<BG_MAX><<<dim3((unsigned)M), dim3(BG_MAX), 0, s>>>(g);
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    return bg_launch_pair(geometry_kernel<BG_SMALL>, geometry_kernel<BG_MAX>, g, M, s);
 }

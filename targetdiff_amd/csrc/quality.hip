@@ -85,14 +85,7 @@ __global__ __launch_bounds__(QL_THREADS) void quality_kernel(TdQualityArgs a) {
                             if (p < P) {
                                 const int e1 = a.pe1[p], e2 = a.pe2[p];
                                 const bool match = ((e1 < 0 || ei == e1) && (e2 < 0 || ej == e2)) || ((e1 < 0 || ej == e1) && (e2 < 0 || ei == e2));
-                                if (match && d < a.cutoff[p]) {
-                                    int lo = 0, hi = a.n_edges[p];    // numpy.searchsorted(edges, d, 'left'): the edges strictly below d
-                                    while (lo < hi) {
-                                        const int mid = (lo + hi) >> 1;
-                                        if (s_edges[p][mid] < d) lo = mid + 1; else hi = mid;
-                                    }
-                                    atomicAdd(&s_hist[p][lo], 1ull);
-                                }
+                                if (match && d < a.cutoff[p]) atomicAdd(&s_hist[p][td_searchsorted_left(s_edges[p], a.n_edges[p], d)], 1ull);
                             }
                         }
                     }

@@ -10,11 +10,12 @@ int td_element_index(int z) {
     return -1;
 }
 
-extern "C" int td_quality_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
-                                 const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include,
-                                 const td_pair_profile *profiles, int32_t P, int32_t *d_nr_bonds, int32_t *d_stable_atoms,
-                                 uint8_t *d_mol_stable, int64_t *d_hist, int64_t *d_counts, void *stream) {
-    const char *who = "td_quality_report";
+int td_profile_element(int z) {
+    const int e = z == 0 ? -1 : td_element_index(z);
+    return z != 0 && e < 0 ? -2 : e;
+}
+
+int td_check_pack(const char *who, int64_t S, int64_t N_l, int64_t B, const int32_t *class_atomic_number, int32_t K, int8_t *elem) {
     if (S < 0 || B < 0 || N_l < 0 || N_l > 0x7fffffff || S > 0x7fffffff || B > 0x7fffffff || S * B > 0x7fffffff) {
         td_set_error("%s: bad argument (S = %lld, B = %lld, N_l = %lld; S * B and N_l must fit 31 bits)", who, (long long)S, (long long)B,
                      (long long)N_l);
@@ -24,11 +25,6 @@ extern "C" int td_quality_report(const float *d_pos, const int64_t *d_v, const i
         td_set_error("%s: the class table must have 1 .. %d entries (got %d)", who, TD_QUALITY_MAX_CLASSES, (int)K);
         return TD_EINVAL;
     }
-    if (P < 0 || P > TD_QUALITY_MAX_PROFILES || (P > 0 && !profiles)) {
-        td_set_error("%s: 0 .. %d pair profiles (got %d)", who, TD_QUALITY_MAX_PROFILES, (int)P);
-        return TD_EINVAL;
-    }
-    TdQualityArgs a;
     for (int c = 0; c < K; ++c) {
         const int e = td_element_index(class_atomic_number[c]);
         if (e < 0) {
@@ -36,12 +32,26 @@ extern "C" int td_quality_report(const float *d_pos, const int64_t *d_v, const i
                          (int)class_atomic_number[c]);
             return TD_EINVAL;
         }
-        a.elem[c] = (int8_t)e;
+        elem[c] = (int8_t)e;
+    }
+    return TD_OK;
+}
+
+extern "C" int td_quality_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                                 const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include,
+                                 const td_pair_profile *profiles, int32_t P, int32_t *d_nr_bonds, int32_t *d_stable_atoms,
+                                 uint8_t *d_mol_stable, int64_t *d_hist, int64_t *d_counts, void *stream) {
+    const char *who = "td_quality_report";
+    TdQualityArgs a;
+    if (const int rc = td_check_pack(who, S, N_l, B, class_atomic_number, K, a.elem)) return rc;
+    if (P < 0 || P > TD_QUALITY_MAX_PROFILES || (P > 0 && !profiles)) {
+        td_set_error("%s: 0 .. %d pair profiles (got %d)", who, TD_QUALITY_MAX_PROFILES, (int)P);
+        return TD_EINVAL;
     }
     for (int p = 0; p < P; ++p) {
         const td_pair_profile &pf = profiles[p];
-        const int e1 = pf.z1 == 0 ? -1 : td_element_index(pf.z1), e2 = pf.z2 == 0 ? -1 : td_element_index(pf.z2);
-        if ((pf.z1 != 0 && e1 < 0) || (pf.z2 != 0 && e2 < 0)) {
+        const int e1 = td_profile_element(pf.z1), e2 = td_profile_element(pf.z2);
+        if (e1 < -1 || e2 < -1) {
             td_set_error("%s: profile %d names an atomic number outside the table (%d, %d; 0 = any)", who, p, (int)pf.z1, (int)pf.z2);
             return TD_EINVAL;
         }

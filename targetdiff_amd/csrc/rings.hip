@@ -90,9 +90,7 @@ __global__ __launch_bounds__(MAXN) void ring_report_kernel(TdBondArgs a) {
         s_mask = 0u;
         s_nrb = s_nra = 0;
     }
-    __syncthreads();
     bg_load<MAXN>(a, m, s_elem, s_at);
-    __syncthreads();
     int up = 0;
     if (tid < n) up = bg_rows<MAXN>(n, s_at, s_thr, s_row, [](int, int, int, double) {});
     const bool list = a.bond_ring || a.bond_category;                           // workgroup-uniform
@@ -164,9 +162,5 @@ int td_launch_ring_report(const TdBondArgs &a, hipStream_t s) {
     const int64_t M = (int64_t)a.S * a.B;
     if (a.S > 0) TD_CHECK_HIP(hipMemsetAsync(a.ring_hist, 0, (size_t)a.S * TD_RING_BITS * sizeof(unsigned long long), s));
     if (M == 0) return TD_OK;
-    ring_report_kernel<BG_SMALL><<<dim3((unsigned)M), dim3(BG_SMALL), 0, s>>>(a);
-    TD_CHECK_HIP(hipGetLastError());
-    ring_report_kernel<BG_MAX><<<dim3((unsigned)M), dim3(BG_MAX), 0, s>>>(a);
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    return bg_launch_pair(ring_report_kernel<BG_SMALL>, ring_report_kernel<BG_MAX>, a, M, s);
 }

@@ -29,10 +29,14 @@ __device__ __forceinline__ BgMol bg_molecule(const TdBondArgs &a) {
     return m;
 }
 
-// atom tid of the molecule into LDS as (x, y, z, code): code = element | aromatic << 8, or -1 for a class outside [0, K)
+// The molecule into LDS, between the two barriers every kernel needs around it: the first publishes the class table, the thresholds and
+// the kernel's own LDS initialisation, which each kernel writes just before, in the order its loads were measured in (a helper for the
+// two table lines moves their loads in the ISA, EXPERIMENTS.md "Sample evaluation: one pack").  Atom tid as (x, y, z, code): code =
+// element | aromatic << 8, or -1 for a class outside [0, K).
 template <int MAXN>
 __device__ __forceinline__ void bg_load(const TdBondArgs &a, const BgMol &m, const int *s_elem, float4 *s_at) {
     const int tid = threadIdx.x;
+    __syncthreads();
     if (tid < m.n) {
         const size_t at = (size_t)m.s * (size_t)a.Nl + (size_t)(m.l0 + tid);
         const float *p = a.pos + at * 3;
@@ -41,6 +45,7 @@ __device__ __forceinline__ void bg_load(const TdBondArgs &a, const BgMol &m, con
         if (c >= 0 && c < a.K) code = s_elem[(int)c] | ((int)((a.aromatic >> (int)c) & 1ull) << 8);
         s_at[tid] = make_float4(p[0], p[1], p[2], __int_as_float(code));
     }
+    __syncthreads();
 }
 
 // category of a bond: its order, or 4 (aromatic) when both atoms' classes are aromatic and the order is 1 or 2
@@ -80,6 +85,15 @@ __device__ __forceinline__ int bg_rows(int n, const float4 *s_at, const double (
     return up;
 }
 
+// The workgroup's LDS histogram of n bins added to the global one: one integer atomic per non-empty bin
+template <int MAXN>
+__device__ __forceinline__ void bg_flush_hist(const unsigned int *s_hist, int n, unsigned long long *hist) {
+    for (int k = threadIdx.x; k < n; k += MAXN) {
+        const unsigned int c = s_hist[k];
+        if (c) atomicAdd(&hist[k], (unsigned long long)c);
+    }
+}
+
 // Inclusive scan of s_off[0 .. MAXN) by the whole workgroup (the per-atom counts of bonds tid < j: s_off[tid] - own count is the offset
 // of atom tid's first bond within the molecule).  A barrier precedes it at the caller; one follows the last step.
 template <int MAXN>
@@ -91,4 +105,14 @@ __device__ __forceinline__ void bg_scan(int *s_off) {
         s_off[tid] += t;
         __syncthreads();
     }
+}
+
+// Both instantiations of a kernel over the M > 0 (frame, molecule) workgroups: each takes the molecules of its own size
+template <typename Args>
+int bg_launch_pair(void (*small)(Args), void (*large)(Args), const Args &a, int64_t M, hipStream_t s) {
+    small<<<dim3((unsigned)M), dim3(BG_SMALL), 0, s>>>(a);
+    TD_CHECK_HIP(hipGetLastError());
+    large<<<dim3((unsigned)M), dim3(BG_MAX), 0, s>>>(a);
+    TD_CHECK_HIP(hipGetLastError());
+    return TD_OK;
 }

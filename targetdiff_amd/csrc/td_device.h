@@ -171,6 +171,16 @@ __device__ __forceinline__ float td_x0_of_output(const float *__restrict__ rc, c
     return out;
 }
 
+// numpy.searchsorted(edges, x, 'left') over n ascending edges: the number of edges strictly below x; <= 7 halvings for a histogram's 127
+__device__ __forceinline__ int td_searchsorted_left(const double *edges, int n, double x) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (edges[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // graph of atom / node i: the g with ptr[g] <= i < ptr[g + 1] (ptr [B + 1], ascending)
 __device__ __forceinline__ int td_find_graph(const int32_t *__restrict__ ptr, int B, int i) {
     int lo = 0, hi = B;   // invariant: ptr[lo] <= i < ptr[hi]

@@ -427,6 +427,9 @@ struct TdQualityArgs {
 };
 int td_launch_quality(const TdQualityArgs &a, hipStream_t s);
 int td_element_index(int z);                 // quality_api.cpp: 0..7 (H C N O F P S Cl) of an atomic number, -1 for any other
+int td_profile_element(int z);              // quality_api.cpp: of a profile's atomic number: -1 for 0 (any), -2 outside the table
+// quality_api.cpp: the checks every entry point over a pack makes of its sizes and its class table (td_set_error under `who`); fills elem
+int td_check_pack(const char *who, int64_t S, int64_t N_l, int64_t B, const int32_t *class_atomic_number, int32_t K, int8_t *elem);
 // bonds.hip, rings.hip, fingerprint.hip (bond graph): the arguments of td_bond_graph / td_bond_list / td_ring_report / td_fingerprint over S
 // frames x B molecules.  elem and a profile's pe1 / pe2 as in TdQualityArgs; aromatic: bit c set when class c is aromatic; pcat: 0 = any category.  The launcher zeroes
 // hist on the stream before the kernels add to it.  Molecules of up to TD_BOND_SMALL_ATOMS atoms run in 128-lane workgroups, larger

@@ -49,6 +49,11 @@ of their van der Waals radii, this project's own convention (not PoseBusters' bo
     geo = quality.sample_geometry(result, eval_step='all', reference=quality.geometry_reference(molfile.read_sdf('ligands.sdf')))
     geo.summary()   # {'clash_free': ..., 'mean_clashes': ..., 'CCC': {'count': ..., 'mean': ..., 'js': ...}, ...}
 
+Several reports of one result share its pack, its host checks and its bond graph (``SamplePack``; the ``sample_*`` functions build one each):
+
+    pack = quality.SamplePack(result, eval_step='all')
+    rep, con, rings = pack.quality('complete'), pack.connectivity('complete'), pack.rings('complete')    # one upload, one plain bond graph
+
 OpenBabel's reconstruction, valence repair, QED / SA and docking need a chemistry toolkit and are not here.
 """
 from __future__ import annotations
@@ -282,29 +287,154 @@ def _trajectories(result):
     return result[2], result[3]
 
 
-def _pack_result(result, eval_step, device):
-    """The chosen frames of all samples of a result as one pack: (pos [S, N_l, 3], v [S, N_l], ligand_ptr [B + 1] on ``device``,
-    the sizes, S) -- samples along the molecule axis, frames along the frame axis."""
-    pos_traj, v_traj = _trajectories(result)
-    if len(pos_traj) != len(v_traj):
-        raise ValueError('position and type trajectories of different length')
-    if isinstance(eval_step, str):
-        if eval_step != 'all':
-            raise ValueError("eval_step is a frame index or 'all'")
-        take = lambda a: np.asarray(a)
-    else:
-        take = lambda a: np.asarray(a)[int(eval_step)][None]
-    pos = [take(p) for p in pos_traj]
-    v = [take(x) for x in v_traj]
-    sizes = [p.shape[1] for p in pos]
-    S = pos[0].shape[0] if pos else 0
-    if any(p.shape[0] != S for p in pos) or any(x.shape[:2] != p.shape[:2] for p, x in zip(pos, v)):
-        raise ValueError('every sample needs the same number of frames, positions and types alike')
-    ptr = torch.as_tensor(np.cumsum([0] + sizes), dtype=torch.int32)
-    pos = np.concatenate(pos, axis=1) if pos else np.zeros((0, 0, 3), np.float32)
-    v = np.concatenate(v, axis=1) if v else np.zeros((0, 0), np.int64)
-    pos, v, ptr = _pack(pos, v, None, ptr, device)
-    return pos, v, ptr, sizes, S
+class SamplePack:
+    """The chosen frames of all samples of a result as one pack on ``device`` -- samples along the molecule axis (they are of ragged
+    size), frames along the frame axis -- and what the reports of one result share: ``pos`` [S, N_l, 3], ``v`` [S, N_l], ``ligand_ptr``
+    [B + 1], the ``sizes``, ``S``, the class table ``class_z`` and the ``aromatic`` flags of ``atom_enc_mode``.  ``result`` and
+    ``eval_step`` as ``sample_quality``.  The pack is made and uploaded once; the host's look at it (the bindings' ``check``) runs
+    once; the stability flags, the plain bond graph (the 'complete' flags and ``bond_ptr``) and ``bond_ring`` are computed when a
+    report first needs them and kept.  The reports are its methods, so none can be taken with another frame, encoding or device."""
+
+    def __init__(self, result, eval_step=-1, atom_enc_mode='add_aromatic', device='cuda'):
+        pos_traj, v_traj = _trajectories(result)
+        if len(pos_traj) != len(v_traj):
+            raise ValueError('position and type trajectories of different length')
+        if isinstance(eval_step, str):
+            if eval_step != 'all':
+                raise ValueError("eval_step is a frame index or 'all'")
+            take = lambda a: np.asarray(a)
+        else:
+            take = lambda a: np.asarray(a)[int(eval_step)][None]
+        pos = [take(p) for p in pos_traj]
+        v = [take(x) for x in v_traj]
+        sizes = [p.shape[1] for p in pos]
+        S = pos[0].shape[0] if pos else 0
+        if any(p.shape[0] != S for p in pos) or any(x.shape[:2] != p.shape[:2] for p, x in zip(pos, v)):
+            raise ValueError('every sample needs the same number of frames, positions and types alike')
+        ptr = torch.as_tensor(np.cumsum([0] + sizes), dtype=torch.int32)
+        pos = np.concatenate(pos, axis=1) if pos else np.zeros((0, 0, 3), np.float32)
+        v = np.concatenate(v, axis=1) if v else np.zeros((0, 0), np.int64)
+        self.pos, self.v, self.ligand_ptr = _pack(pos, v, None, ptr, device)
+        self.sizes, self.S = sizes, S
+        self.class_z, self.aromatic = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
+        self._checked = self._sized = False
+        self._stable = self._graph = self._bond_ring = None
+
+    @property
+    def _args(self):
+        return self.pos, self.v, self.ligand_ptr, self.class_z
+
+    def _check(self, sized=True):
+        """``check`` of the next binding call: the first call on the pack looks at it on the host, later ones do not.  The look of
+        the bond graph's family (``sized``) also bounds the molecule sizes, which quality_report's does not: it runs once more when
+        quality_report came first."""
+        todo = not (self._sized if sized else self._checked)
+        self._checked, self._sized = True, self._sized or sized
+        return todo
+
+    @property
+    def stable(self):
+        """[S, B] bool: the molecules that are stable in that frame, from one quality_report without profiles"""
+        if self._stable is None:
+            self._stable = capi.quality_report(*self._args, (), None, False, check=self._check(False))['mol_stable'].bool()
+        return self._stable
+
+    @property
+    def graph(self):
+        """the plain bond graph (no profiles, every molecule): ``n_fragments`` -- one fragment: 'complete' -- and ``bond_ptr``"""
+        if self._graph is None:
+            self._graph = capi.bond_graph(*self._args, self.aromatic, (), None, False, True, check=self._check())
+        return self._graph
+
+    @property
+    def bond_ring(self):
+        """[n_bonds] int16 in the order of ``graph['bond_ptr']``: the smallest ring through every bond, 0 for a bridge"""
+        if self._bond_ring is None:
+            bond_ptr = self.graph['bond_ptr']
+            self._bond_ring = capi.ring_report(*self._args, self.aromatic, None, bond_ptr, False, check=self._check())['bond_ring']
+        return self._bond_ring
+
+    def mask(self, include, allowed=('all', 'complete')):
+        """``include`` as a device mask [S, B] bool, or None for every molecule: ``'all'``, ``'stable'``, ``'complete'`` -- those of
+        them that ``allowed`` names -- or a bool array [frames, samples]"""
+        if isinstance(include, str):
+            if include not in allowed:
+                raise ValueError('include is ' + ', '.join(repr(a) for a in allowed) + ' or a mask [frames, samples]')
+            if include == 'all':
+                return None
+            return self.stable if include == 'stable' else self.graph['n_fragments'] == 1
+        return torch.as_tensor(np.asarray(include)).to(device=self.pos.device, dtype=torch.bool).reshape(self.S, len(self.sizes)).contiguous()
+
+    def quality(self, include='all', reference=None, profiles=None):
+        """``sample_quality`` of the pack"""
+        prof = default_profiles() if profiles is None else tuple(profiles)
+        mask = self.mask(include, ('all', 'stable', 'complete'))
+        r = capi.quality_report(*self._args, prof, mask, False, check=self._check(False))    # stability does not depend on the mask
+        if reference is None:
+            reference = reference_distributions()
+        return QualityReport(r['mol_stable'].sum(1).cpu().numpy(), r['stable_atoms'].sum(1).cpu().numpy(), len(self.sizes), sum(self.sizes),
+                             r['hist'].cpu().numpy(), r['counts'].cpu().numpy(), prof, reference)
+
+    def connectivity(self, include='all', reference=None, bond_profiles=None):
+        """``sample_connectivity`` of the pack"""
+        prof = default_bond_profiles() if bond_profiles is None else tuple(bond_profiles)
+        mask = self.mask(include)
+        r = capi.bond_graph(*self._args, self.aromatic, prof, mask, check=self._check())
+        nf, big = r['n_fragments'].cpu().numpy().astype(np.int64), r['largest_fragment'].cpu().numpy().astype(np.float64)
+        n = np.asarray(self.sizes, dtype=np.float64)
+        share = np.divide(big, n[None], out=np.zeros_like(big), where=n[None] > 0)
+        if reference is None:
+            reference = reference_bond_distributions()
+        return ConnectivityReport((nf == 1).sum(1), nf.sum(1), share.sum(1), len(self.sizes), int((n > 0).sum()), r['bond_hist'].cpu().numpy(),
+                                  prof, reference)
+
+    def _included(self, mask):
+        return np.ones((self.S, len(self.sizes)), bool) if mask is None else mask.cpu().numpy().astype(bool)
+
+    def rings(self, include='all'):
+        """``sample_rings`` of the pack"""
+        mask = self.mask(include)
+        r = capi.ring_report(*self._args, self.aromatic, mask, None, False, check=self._check())
+        inc = self._included(mask)
+        n = np.asarray(self.sizes, dtype=np.float64)
+        ring_atoms = r['n_ring_atoms'].cpu().numpy().astype(np.float64)
+        share = np.divide(ring_atoms, n[None], out=np.zeros_like(ring_atoms), where=n[None] > 0)
+        large = (r['ring_mask'].cpu().numpy() >> (RING_SIZES[-1] + 1)) != 0
+        return RingReport(r['ring_hist'].cpu().numpy(), inc.sum(1), (large & inc).sum(1), np.where(inc, share, 0.0).sum(1),
+                          (inc & (n[None] > 0)).sum(1), len(self.sizes))
+
+    def diversity(self, include='all', radius=2, key_rounds=8, reference_ligand=None):
+        """``sample_diversity`` of the pack"""
+        mask = self.mask(include)
+        fp = capi.fingerprint(*self._args, self.aromatic, radius, key_rounds, False, check=self._check())
+        qw = qb = None
+        if reference_ligand is not None:
+            rpos, rv = reference_ligand
+            rpos, rv, rptr = _pack(rpos, rv, None, torch.tensor([0, len(rv)], dtype=torch.int32), self.pos.device)
+            if rpos.shape[0] != 1:
+                raise ValueError('the reference ligand is one molecule: pos [n, 3], v [n]')
+            q = capi.fingerprint(rpos, rv, rptr, self.class_z, self.aromatic, radius, key_rounds, False)
+            qw, qb = q['fp_words'][0].contiguous(), q['n_bits'][0].contiguous()
+        r = capi.fingerprint_similarity(fp['fp_words'], fp['n_bits'], fp['key'], mask, qw, qb, False)
+        inc = fp['n_bits'].cpu().numpy() >= 0
+        if mask is not None:
+            inc &= mask.cpu().numpy().astype(bool)
+        first = r['first_equal'].cpu().numpy()
+        distinct = (first == np.arange(len(self.sizes))[None]) & inc
+        return DiversityReport.from_frames(inc.sum(1), np.where(inc, r['sim_sum'].cpu().numpy(), 0.0).sum(1), distinct.sum(1),
+                                           np.where(inc, r['sim_max'].cpu().numpy(), 0.0).sum(1), len(self.sizes),
+                                           None if qw is None else r['query_sim'][:, :, 0].cpu().numpy(), inc)
+
+    def geometry(self, include='all', reference=None, profiles=None, clash_scale=0.7, radii=None):
+        """``sample_geometry`` of the pack"""
+        prof = default_geometry_profiles() if profiles is None else tuple(profiles)
+        mask = self.mask(include)
+        r = _geometry_call(*self._args, self.aromatic, prof, mask, clash_thresholds(clash_scale, radii), False, pack=self)
+        inc = self._included(mask)
+        clashes = r['n_clashes'].cpu().numpy().astype(np.int64)
+        tot = lambda k: np.where(inc, r[k].cpu().numpy().astype(np.int64), 0).sum(1)
+        return GeometryReport(inc.sum(1), (inc & (clashes == 0)).sum(1), np.where(inc, clashes, 0).sum(1), tot('n_crowded'), tot('n_degenerate'),
+                              tot('n_angles'), tot('n_torsions'), r['hist'].cpu().numpy(), prof, len(self.sizes), reference)
 
 
 def sample_quality(result, eval_step=-1, include='all', atom_enc_mode='add_aromatic', reference=None, profiles=None, device='cuda'):
@@ -320,28 +450,7 @@ def sample_quality(result, eval_step=-1, include='all', atom_enc_mode='add_aroma
     'complete' is that restriction with this project's bond graph in the place of OpenBabel's reconstruction; with 'all' the
     numbers are those the reference would print if every sample reconstructed.  ``reference``: the empirical distributions ({'CC_2A', 'All_12A', 'atom_type'} arrays); default
     ``reference_distributions()``; without them the report has no Jensen-Shannon value.  Returns a ``QualityReport``."""
-    pos, v, ptr, sizes, S = _pack_result(result, eval_step, device)
-    cz = class_atomic_numbers(atom_enc_mode)
-    prof = default_profiles() if profiles is None else tuple(profiles)
-    if isinstance(include, str):
-        if include not in ('all', 'stable', 'complete'):
-            raise ValueError("include is 'all', 'stable', 'complete' or a mask [frames, samples]")
-        mask = None
-    else:
-        mask = torch.as_tensor(np.asarray(include)).to(device=pos.device, dtype=torch.bool).reshape(S, len(sizes)).contiguous()
-    if isinstance(include, str) and include == 'stable':
-        first = capi.quality_report(pos, v, ptr, cz, (), None, False)
-        r = capi.quality_report(pos, v, ptr, cz, prof, first['mol_stable'].bool(), False, check=False)
-        r['mol_stable'], r['stable_atoms'] = first['mol_stable'], first['stable_atoms']
-    elif isinstance(include, str) and include == 'complete':
-        first = capi.bond_graph(pos, v, ptr, cz, class_aromatic(atom_enc_mode))
-        r = capi.quality_report(pos, v, ptr, cz, prof, first['n_fragments'] == 1, False, check=False)
-    else:
-        r = capi.quality_report(pos, v, ptr, cz, prof, mask, False)
-    if reference is None:
-        reference = reference_distributions()
-    return QualityReport(r['mol_stable'].sum(1).cpu().numpy(), r['stable_atoms'].sum(1).cpu().numpy(), len(sizes), sum(sizes),
-                         r['hist'].cpu().numpy(), r['counts'].cpu().numpy(), prof, reference)
+    return SamplePack(result, eval_step, atom_enc_mode, device).quality(include, reference, profiles)
 
 
 class BondGraph:
@@ -463,27 +572,7 @@ def sample_connectivity(result, eval_step=-1, include='all', atom_enc_mode='add_
     distributions with their Jensen-Shannon distances.  ``include``: which molecules enter the bond-length histograms: ``'all'``
     (default), ``'complete'`` (two launches: the first call's flags are the mask) or a bool array [frames, samples].  ``reference``:
     {(z1, z2, category): distribution}; default ``reference_bond_distributions()``.  Returns a ``ConnectivityReport``."""
-    pos, v, ptr, sizes, S = _pack_result(result, eval_step, device)
-    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
-    prof = default_bond_profiles() if bond_profiles is None else tuple(bond_profiles)
-    if isinstance(include, str):
-        if include not in ('all', 'complete'):
-            raise ValueError("include is 'all', 'complete' or a mask [frames, samples]")
-        mask = None
-    else:
-        mask = torch.as_tensor(np.asarray(include)).to(device=pos.device, dtype=torch.bool).reshape(S, len(sizes)).contiguous()
-    if isinstance(include, str) and include == 'complete':
-        first = capi.bond_graph(pos, v, ptr, cz, aro)
-        r = capi.bond_graph(pos, v, ptr, cz, aro, prof, first['n_fragments'] == 1, check=False)
-    else:
-        r = capi.bond_graph(pos, v, ptr, cz, aro, prof, mask)
-    nf, big = r['n_fragments'].cpu().numpy().astype(np.int64), r['largest_fragment'].cpu().numpy().astype(np.float64)
-    n = np.asarray(sizes, dtype=np.float64)
-    share = np.divide(big, n[None], out=np.zeros_like(big), where=n[None] > 0)
-    if reference is None:
-        reference = reference_bond_distributions()
-    return ConnectivityReport((nf == 1).sum(1), nf.sum(1), share.sum(1), len(sizes), int((n > 0).sum()), r['bond_hist'].cpu().numpy(), prof,
-                              reference)
+    return SamplePack(result, eval_step, atom_enc_mode, device).connectivity(include, reference, bond_profiles)
 
 
 RING_SIZES = tuple(range(3, 10))                      # evaluate_diffusion.py print_ring_ratio: range(3, 10)
@@ -543,22 +632,7 @@ def sample_rings(result, eval_step=-1, include='all', atom_enc_mode='add_aromati
     with a ring of more than 9 atoms and the mean share of atoms in rings.  ``include``: the molecules that are counted: ``'all'``
     (default), ``'complete'`` (one fragment in that frame; the bond graph runs first and its flags are the mask) or a bool array
     [frames, samples].  Returns a ``RingReport``."""
-    pos, v, ptr, sizes, S = _pack_result(result, eval_step, device)
-    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
-    if isinstance(include, str):
-        if include not in ('all', 'complete'):
-            raise ValueError("include is 'all', 'complete' or a mask [frames, samples]")
-        mask = capi.bond_graph(pos, v, ptr, cz, aro)['n_fragments'] == 1 if include == 'complete' else None
-    else:
-        mask = torch.as_tensor(np.asarray(include)).to(device=pos.device, dtype=torch.bool).reshape(S, len(sizes)).contiguous()
-    r = capi.ring_report(pos, v, ptr, cz, aro, mask, None, False, check=not (isinstance(include, str) and include == 'complete'))
-    inc = np.ones((S, len(sizes)), bool) if mask is None else mask.cpu().numpy().astype(bool)
-    n = np.asarray(sizes, dtype=np.float64)
-    ring_atoms = r['n_ring_atoms'].cpu().numpy().astype(np.float64)
-    share = np.divide(ring_atoms, n[None], out=np.zeros_like(ring_atoms), where=n[None] > 0)
-    large = (r['ring_mask'].cpu().numpy() >> (RING_SIZES[-1] + 1)) != 0
-    return RingReport(r['ring_hist'].cpu().numpy(), inc.sum(1), (large & inc).sum(1), np.where(inc, share, 0.0).sum(1),
-                      (inc & (n[None] > 0)).sum(1), len(sizes))
+    return SamplePack(result, eval_step, atom_enc_mode, device).rings(include)
 
 
 class Fingerprints:
@@ -683,15 +757,6 @@ class DiversityReport:
                     **self.reference_similarity(frame))
 
 
-def _include_mask(include, pos, v, ptr, cz, aro, S, B):
-    """``include`` of sample_rings / sample_diversity as a device mask or None, and whether the pack was already looked at"""
-    if isinstance(include, str):
-        if include not in ('all', 'complete'):
-            raise ValueError("include is 'all', 'complete' or a mask [frames, samples]")
-        return (capi.bond_graph(pos, v, ptr, cz, aro)['n_fragments'] == 1, True) if include == 'complete' else (None, False)
-    return torch.as_tensor(np.asarray(include)).to(device=pos.device, dtype=torch.bool).reshape(S, B).contiguous(), False
-
-
 def sample_diversity(result, eval_step=-1, include='all', radius=2, key_rounds=8, reference_ligand=None, atom_enc_mode='add_aromatic',
                      device='cuda'):
     """Diversity of the samples of one pocket (``result``, ``eval_step`` and the packing as ``sample_quality``): per frame one minus the
@@ -702,27 +767,7 @@ def sample_diversity(result, eval_step=-1, include='all', radius=2, key_rounds=8
     the mean, median and largest similarity of the included samples to it (the reference's tanimoto_sim_N_to_1).  ``radius`` and
     ``key_rounds`` as ``fingerprints``.  Two launches (three with ``'complete'``).  The fingerprint is this project's own, not RDKit's:
     the numbers compare between runs of this tool, not with published tables.  Returns a ``DiversityReport``."""
-    pos, v, ptr, sizes, S = _pack_result(result, eval_step, device)
-    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
-    mask, seen = _include_mask(include, pos, v, ptr, cz, aro, S, len(sizes))
-    fp = capi.fingerprint(pos, v, ptr, cz, aro, radius, key_rounds, False, check=not seen)
-    qw = qb = None
-    if reference_ligand is not None:
-        rpos, rv = reference_ligand
-        rpos, rv, rptr = _pack(rpos, rv, None, torch.tensor([0, len(rv)], dtype=torch.int32), pos.device)
-        if rpos.shape[0] != 1:
-            raise ValueError('the reference ligand is one molecule: pos [n, 3], v [n]')
-        q = capi.fingerprint(rpos, rv, rptr, cz, aro, radius, key_rounds, False)
-        qw, qb = q['fp_words'][0].contiguous(), q['n_bits'][0].contiguous()
-    r = capi.fingerprint_similarity(fp['fp_words'], fp['n_bits'], fp['key'], mask, qw, qb, False)
-    inc = fp['n_bits'].cpu().numpy() >= 0
-    if mask is not None:
-        inc &= mask.cpu().numpy().astype(bool)
-    first = r['first_equal'].cpu().numpy()
-    distinct = (first == np.arange(len(sizes))[None]) & inc
-    return DiversityReport.from_frames(inc.sum(1), np.where(inc, r['sim_sum'].cpu().numpy(), 0.0).sum(1), distinct.sum(1),
-                                       np.where(inc, r['sim_max'].cpu().numpy(), 0.0).sum(1), len(sizes),
-                                       None if qw is None else r['query_sim'][:, :, 0].cpu().numpy(), inc)
+    return SamplePack(result, eval_step, atom_enc_mode, device).diversity(include, radius, key_rounds, reference_ligand)
 
 
 # ---- local geometry (``td_geometry_report``, csrc/geometry.hip; DESIGN.md section 3, "Local geometry")
@@ -779,12 +824,18 @@ def _cosine_profiles(profiles):
     return out
 
 
-def _geometry_call(pos, v, ptr, cz, aro, profiles, mask, thr, return_atom_clash, check=True):
-    """capi.geometry_report under profiles in degrees, the histograms flipped back to ascending angle; the bond graph and the ring
-    report run first when a profile filters on the ring"""
+def _geometry_call(pos, v, ptr, cz, aro, profiles, mask, thr, return_atom_clash, check=True, pack=None):
+    """capi.geometry_report under profiles in degrees, the histograms flipped back to ascending angle; when a profile filters on the
+    ring it takes ``bond_ptr`` and ``bond_ring`` from ``pack`` (a ``SamplePack`` of these arrays), and without one the bond graph and
+    the ring report run first"""
     cosp = _cosine_profiles(profiles)
     bond_ptr = bond_ring = None
-    if any(p[3] != 'any' for p in cosp):
+    ring = any(p[3] != 'any' for p in cosp)
+    if pack is not None:
+        if ring:
+            bond_ptr, bond_ring = pack.graph['bond_ptr'], pack.bond_ring
+        check = pack._check()
+    elif ring:
         bond_ptr = capi.bond_graph(pos, v, ptr, cz, aro, (), None, False, True, check=check)['bond_ptr']
         bond_ring = capi.ring_report(pos, v, ptr, cz, aro, None, bond_ptr, False, check=False)['bond_ring']
         check = False
@@ -943,16 +994,7 @@ def sample_geometry(result, eval_step=-1, include='all', reference=None, profile
     the count, the mean angle and -- with ``reference`` ({name: counts}, of ``geometry_reference``) -- the Jensen-Shannon distance.
     ``include``: the molecules that are counted, as ``sample_rings``: ``'all'``, ``'complete'`` or a bool array [frames, samples].
     ``profiles``, ``clash_scale`` and ``radii`` as ``geometry``, whose conventions these are.  Returns a ``GeometryReport``."""
-    pos, v, ptr, sizes, S = _pack_result(result, eval_step, device)
-    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
-    prof = default_geometry_profiles() if profiles is None else tuple(profiles)
-    mask, seen = _include_mask(include, pos, v, ptr, cz, aro, S, len(sizes))
-    r = _geometry_call(pos, v, ptr, cz, aro, prof, mask, clash_thresholds(clash_scale, radii), False, check=not seen)
-    inc = np.ones((S, len(sizes)), bool) if mask is None else mask.cpu().numpy().astype(bool)
-    clashes = r['n_clashes'].cpu().numpy().astype(np.int64)
-    tot = lambda k: np.where(inc, r[k].cpu().numpy().astype(np.int64), 0).sum(1)
-    return GeometryReport(inc.sum(1), (inc & (clashes == 0)).sum(1), np.where(inc, clashes, 0).sum(1), tot('n_crowded'), tot('n_degenerate'),
-                          tot('n_angles'), tot('n_torsions'), r['hist'].cpu().numpy(), prof, len(sizes), reference)
+    return SamplePack(result, eval_step, atom_enc_mode, device).geometry(include, reference, profiles, clash_scale, radii)
 
 
 def geometry_reference(molecules, profiles=None, atom_enc_mode='add_aromatic', device='cuda'):

@@ -101,21 +101,18 @@ def main(argv=None):
         raise SystemExit(f'no result_*.pt under {args.sample_path}')
     print(f'Load generated data done! {len(files)} examples in total.')
     reports, connectivity, rings, diversity, geometry = [], [], [], [], []
+    graph_include = 'complete' if args.include == 'complete' else 'all'     # 'stable' restricts the pair profiles and atom types only
     for name in files:
-        r = torch.load(name, map_location='cpu', weights_only=False)
+        pack = quality.SamplePack(torch.load(name, map_location='cpu', weights_only=False), eval_step, args.atom_enc_mode, args.device)
         if args.connectivity:
-            connectivity.append(quality.sample_connectivity(r, eval_step, 'complete' if args.include == 'complete' else 'all',
-                                                            args.atom_enc_mode, bond_reference, device=args.device))
+            connectivity.append(pack.connectivity(graph_include, bond_reference))
         if args.rings:
-            rings.append(quality.sample_rings(r, eval_step, 'complete' if args.include == 'complete' else 'all', args.atom_enc_mode,
-                                              device=args.device))
+            rings.append(pack.rings(graph_include))
         if args.diversity:
-            diversity.append(quality.sample_diversity(r, eval_step, 'complete' if args.include == 'complete' else 'all',
-                                                      reference_ligand=reference_ligand, atom_enc_mode=args.atom_enc_mode, device=args.device))
+            diversity.append(pack.diversity(graph_include, reference_ligand=reference_ligand))
         if args.geometry:
-            geometry.append(quality.sample_geometry(r, eval_step, 'complete' if args.include == 'complete' else 'all', geometry_reference,
-                                                    atom_enc_mode=args.atom_enc_mode, device=args.device))
-        reports.append(quality.sample_quality(r, eval_step, args.include, args.atom_enc_mode, reference, device=args.device))
+            geometry.append(pack.geometry(graph_include, geometry_reference))
+        reports.append(pack.quality(args.include, reference))
     rep = quality.QualityReport.merged(reports)
     print(f'Evaluate done! {rep.n_samples} samples in total.')
 

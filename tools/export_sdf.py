@@ -57,8 +57,8 @@ def main(argv=None):
     os.makedirs(args.out, exist_ok=True)
     out = {}
     for name in files:
-        r = torch.load(name, map_location='cpu', weights_only=False)
-        pos, v, ptr, sizes, _ = quality._pack_result(r, args.eval_step, args.device)
+        pack = quality.SamplePack(torch.load(name, map_location='cpu', weights_only=False), args.eval_step, args.atom_enc_mode, args.device)
+        pos, v, ptr, sizes = pack.pos, pack.v, pack.ligand_ptr, pack.sizes
         g = quality.bond_graph(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, bond_profiles=(), return_fragments=True,
                                return_bonds=True, rings=args.ring_aromatic, device=args.device)
         select = chosen = clash_free = None

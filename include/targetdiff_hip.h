@@ -136,6 +136,14 @@ size_t td_model_num_weights(const td_config *cfg);      /* expected length of th
  *                            Both f16 options apply per attention MLP only where the f16 pieces keep its precision: an MLP whose folded
  *                            LayerNorm scale M (csrc/pack.cpp FoldedMlp) exceeds 2^16, or whose first layer could not take its full power-of-two
  *                            scale, runs both layers in fp32 whatever these options say ("fold_fp32_mlps")
+ *   "edge_row_dealing"       0 .. 2 (default 2; other values are clamped): x2h key / value passes: units of rows dealt round-robin to an
+ *                            XCD's workgroups (0: one contiguous share per workgroup; 1: a fixed row sequence per wave; 2: the workgroup's
+ *                            rows handed to its waves one at a time through an LDS counter; the value pass's protein rows on a general graph
+ *                            with one chunk per protein row always take 2: the 12-wave kernel has no other form)
+ *   "node_proj_bpipe"        0 (default): split node GEMMs: register double-buffering of the B fragments (LDS reads ahead of the MFMAs;
+ *                            measured slower, kept as a switch)
+ *   "node_proj_async"        1 (default): split node GEMMs: B chunks by inline-asm global_load_lds + an explicit wait per round
+ *                            (0: the builtin, which the compiler serialises)
  *   "h2x_fused"              1 (default): key + value halves of the h2x stage in one launch; 0 = two launches
  *   "session_hop_levels"     1 .. 4 (default 4): receptive-field levels a sampling session prunes the last layers with
  *   "session_forward_reach"  1 (default): layer 1 of a session runs on the ligand's one-hop forward reach only

@@ -230,21 +230,29 @@ int check_known_atoms(const char *who, const td_model *m, const uint8_t *d_fixed
 }  // namespace tdapi
 
 namespace {
-// validate and launch, for the stateless entry points below: each fills the pointers and N_l of `a`, the model's part is added here
-int step_run(const char *who, const td_model *m, int64_t B, TdStepArgs &a, void *stream, bool renoise = false) {
-    if (!m || a.Nl < 0 || B < 0) { td_set_error("%s: bad argument", who); return TD_EINVAL; }
-    if (a.Nl == 0) return TD_OK;
-    const bool own = renoise ? a.prow != nullptr : a.t && a.lptr && a.pred_pos && a.pred_v && a.uni;
-    if (!own || !a.pos || !a.v || !a.noise || !a.pos_next || !a.v_next) {
+// The stateless step entry points below all end here: the one place that fills a TdStepArgs from a C call.  Each passes null for the
+// pointers its signature does not have; `who` names it in the error texts.  renoise: the forward-process step of a time program, which
+// reads neither t, the offsets nor the network's outputs.
+int step_entry(const char *who, const td_model *m, const int32_t *d_t, const float *d_prog_row, const int32_t *d_ligand_ptr, int64_t N_l,
+               int64_t B, const float *d_ligand_pos, const int64_t *d_ligand_v, const float *d_pred_pos, const float *d_pred_v,
+               const float *d_noise, const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0, float *d_log_post,
+               const uint8_t *d_fixed_mask, const float *d_fixed_pos, const int64_t *d_fixed_v, const float *d_x0_shift, void *stream,
+               bool renoise = false) {
+    if (!m || N_l < 0 || B < 0) { td_set_error("%s: bad argument", who); return TD_EINVAL; }
+    if (N_l == 0) return TD_OK;
+    const bool own = renoise ? d_prog_row != nullptr : d_t && d_ligand_ptr && d_pred_pos && d_pred_v && d_uniform;
+    if (!own || !d_ligand_pos || !d_ligand_v || !d_noise || !d_pos_next || !d_v_next) {
         td_set_error("%s: null pointer", who);
         return TD_EINVAL;
     }
-    const int rc = check_known_atoms(who, m, a.fixed_mask, a.fixed_pos, a.fixed_v);
+    const int rc = check_known_atoms(who, m, d_fixed_mask, d_fixed_pos, d_fixed_v);
     if (rc != TD_OK) return rc;
-    a.B = (int)B;
-    a.C = m->cfg.ligand_num_classes;
-    a.T = m->cfg.num_timesteps;
-    a.mean_type = m->cfg.model_mean_type;
+    TdStepArgs a;
+    a.t = d_t; a.prow = d_prog_row; a.lptr = d_ligand_ptr; a.Nl = N_l; a.pos = d_ligand_pos; a.v = d_ligand_v;
+    a.pred_pos = d_pred_pos; a.pred_v = d_pred_v; a.noise = d_noise; a.uni = d_uniform;
+    a.pos_next = d_pos_next; a.v_next = d_v_next; a.log_v0 = d_log_v0; a.log_post = d_log_post;
+    a.fixed_mask = d_fixed_mask; a.fixed_pos = d_fixed_pos; a.fixed_v = d_fixed_v; a.x0_shift = d_x0_shift;
+    a.B = (int)B; a.C = m->cfg.ligand_num_classes; a.T = m->cfg.num_timesteps; a.mean_type = m->cfg.model_mean_type;
     hipStream_t s = static_cast<hipStream_t>(stream);
     ProfScope ps(PC_POST, s);
     return renoise ? td_launch_renoise(a, s) : td_launch_posterior(m->sched, a, s);
@@ -256,11 +264,8 @@ extern "C" int td_posterior_step(const td_model *m, const int32_t *d_t, const in
                                  const float *d_pred_pos, const float *d_pred_v, const float *d_noise,
                                  const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
                                  float *d_log_post, void *stream) {
-    TdStepArgs a;
-    a.t = d_t; a.lptr = d_ligand_ptr; a.Nl = N_l; a.pos = d_ligand_pos; a.v = d_ligand_v;
-    a.pred_pos = d_pred_pos; a.pred_v = d_pred_v; a.noise = d_noise; a.uni = d_uniform;
-    a.pos_next = d_pos_next; a.v_next = d_v_next; a.log_v0 = d_log_v0; a.log_post = d_log_post;
-    return step_run("td_posterior_step", m, B, a, stream);
+    return step_entry("td_posterior_step", m, d_t, nullptr, d_ligand_ptr, N_l, B, d_ligand_pos, d_ligand_v, d_pred_pos, d_pred_v, d_noise,
+                      d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_post, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int td_posterior_step_fixed(const td_model *m, const int32_t *d_t, const int32_t *d_ligand_ptr, int64_t N_l,
@@ -269,12 +274,8 @@ extern "C" int td_posterior_step_fixed(const td_model *m, const int32_t *d_t, co
                                        const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
                                        float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos,
                                        const int64_t *d_fixed_v, void *stream) {
-    TdStepArgs a;
-    a.t = d_t; a.lptr = d_ligand_ptr; a.Nl = N_l; a.pos = d_ligand_pos; a.v = d_ligand_v;
-    a.pred_pos = d_pred_pos; a.pred_v = d_pred_v; a.noise = d_noise; a.uni = d_uniform;
-    a.pos_next = d_pos_next; a.v_next = d_v_next; a.log_v0 = d_log_v0; a.log_post = d_log_post;
-    a.fixed_mask = d_fixed_mask; a.fixed_pos = d_fixed_pos; a.fixed_v = d_fixed_v;
-    return step_run("td_posterior_step_fixed", m, B, a, stream);
+    return step_entry("td_posterior_step_fixed", m, d_t, nullptr, d_ligand_ptr, N_l, B, d_ligand_pos, d_ligand_v, d_pred_pos, d_pred_v,
+                      d_noise, d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_post, d_fixed_mask, d_fixed_pos, d_fixed_v, nullptr, stream);
 }
 
 extern "C" int td_posterior_step_program(const td_model *m, const int32_t *d_t, const float *d_prog_row, const int32_t *d_ligand_ptr,
@@ -284,21 +285,15 @@ extern "C" int td_posterior_step_program(const td_model *m, const int32_t *d_t, 
                                          float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos,
                                          const int64_t *d_fixed_v, void *stream) {
     if (!d_prog_row) { td_set_error("td_posterior_step_program: null d_prog_row"); return TD_EINVAL; }
-    TdStepArgs a;
-    a.t = d_t; a.prow = d_prog_row; a.lptr = d_ligand_ptr; a.Nl = N_l; a.pos = d_ligand_pos; a.v = d_ligand_v;
-    a.pred_pos = d_pred_pos; a.pred_v = d_pred_v; a.noise = d_noise; a.uni = d_uniform;
-    a.pos_next = d_pos_next; a.v_next = d_v_next; a.log_v0 = d_log_v0; a.log_post = d_log_post;
-    a.fixed_mask = d_fixed_mask; a.fixed_pos = d_fixed_pos; a.fixed_v = d_fixed_v;
-    return step_run("td_posterior_step_program", m, B, a, stream);
+    return step_entry("td_posterior_step_program", m, d_t, d_prog_row, d_ligand_ptr, N_l, B, d_ligand_pos, d_ligand_v, d_pred_pos, d_pred_v,
+                      d_noise, d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_post, d_fixed_mask, d_fixed_pos, d_fixed_v, nullptr, stream);
 }
 
 extern "C" int td_renoise_step(const td_model *m, const float *d_prog_row, int64_t N_l, const float *d_ligand_pos,
                                const int64_t *d_ligand_v, const float *d_noise, const float *d_uniform, float *d_pos_next,
                                int64_t *d_v_next, float *d_log_v0, float *d_log_q, void *stream) {
-    TdStepArgs a;
-    a.prow = d_prog_row; a.Nl = N_l; a.pos = d_ligand_pos; a.v = d_ligand_v; a.noise = d_noise; a.uni = d_uniform;
-    a.pos_next = d_pos_next; a.v_next = d_v_next; a.log_v0 = d_log_v0; a.log_post = d_log_q;
-    return step_run("td_renoise_step", m, 0, a, stream, true);
+    return step_entry("td_renoise_step", m, nullptr, d_prog_row, nullptr, N_l, 0, d_ligand_pos, d_ligand_v, nullptr, nullptr, d_noise,
+                      d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_q, nullptr, nullptr, nullptr, nullptr, stream, true);
 }
 
 // ------------------------------------------------------------------------------------------ clash guidance
@@ -308,12 +303,9 @@ extern "C" int td_posterior_step_guided(const td_model *m, const int32_t *d_t, c
                                         const float *d_uniform, float *d_pos_next, int64_t *d_v_next, float *d_log_v0,
                                         float *d_log_post, const uint8_t *d_fixed_mask, const float *d_fixed_pos,
                                         const int64_t *d_fixed_v, const float *d_x0_shift, void *stream) {
-    TdStepArgs a;
-    a.t = d_t; a.prow = d_prog_row; a.lptr = d_ligand_ptr; a.Nl = N_l; a.pos = d_ligand_pos; a.v = d_ligand_v;
-    a.pred_pos = d_pred_pos; a.pred_v = d_pred_v; a.noise = d_noise; a.uni = d_uniform;
-    a.pos_next = d_pos_next; a.v_next = d_v_next; a.log_v0 = d_log_v0; a.log_post = d_log_post;
-    a.fixed_mask = d_fixed_mask; a.fixed_pos = d_fixed_pos; a.fixed_v = d_fixed_v; a.x0_shift = d_x0_shift;
-    return step_run("td_posterior_step_guided", m, B, a, stream);
+    return step_entry("td_posterior_step_guided", m, d_t, d_prog_row, d_ligand_ptr, N_l, B, d_ligand_pos, d_ligand_v, d_pred_pos, d_pred_v,
+                      d_noise, d_uniform, d_pos_next, d_v_next, d_log_v0, d_log_post, d_fixed_mask, d_fixed_pos, d_fixed_v, d_x0_shift,
+                      stream);
 }
 
 namespace {
@@ -463,16 +455,14 @@ namespace tdapi {
 struct EgnnWs { float4 *x4a, *x4b; int32_t *gid, *nbr; float *P, *mi; size_t bytes; };
 EgnnWs egnn_carve(char *base, int64_t N) {
     EgnnWs w;
-    size_t off = 0;
-    auto take = [&](size_t n) { char *p = base ? base + off : nullptr; off += align_up(n); return p; };
+    Carver c{base};
     const size_t n = (size_t)(N > 0 ? N : 1);
-    w.x4a = reinterpret_cast<float4 *>(take(n * sizeof(float4)));
-    w.x4b = reinterpret_cast<float4 *>(take(n * sizeof(float4)));
-    w.gid = reinterpret_cast<int32_t *>(take(n * sizeof(int32_t)));
-    w.nbr = reinterpret_cast<int32_t *>(take(n * TD_K * sizeof(int32_t)));
-    w.P = reinterpret_cast<float *>(take(n * 4 * TD_H * sizeof(float)));
-    w.mi = reinterpret_cast<float *>(take(n * TD_H * sizeof(float)));
-    w.bytes = off;
+    w.x4a = c.take<float4>(n); w.x4b = c.take<float4>(n);
+    w.gid = c.take<int32_t>(n);
+    w.nbr = c.take<int32_t>(n * TD_K);
+    w.P = c.take<float>(n * 4 * TD_H);
+    w.mi = c.take<float>(n * TD_H);
+    w.bytes = c.off;
     return w;
 }
 }  // namespace tdapi

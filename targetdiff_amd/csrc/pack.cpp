@@ -447,6 +447,55 @@ float gaussian_coeff(const float *off) {                // models/common.py:18
 
 }  // namespace tdapi
 
+// ------------------------------------------------------------------------------------------ model options
+namespace {
+// Every settable option of a model (documented in include/targetdiff_hip.h; defaults: TdOptions).  FLAG: any non-zero value is 1.
+// CLAMPED: the value is brought into lo .. hi.  RANGED: a value outside lo .. hi is refused and the option keeps its value.
+enum OptKind { OPT_FLAG, OPT_CLAMPED, OPT_RANGED };
+struct OptRow { const char *name; int TdOptions::*field; OptKind kind; int lo, hi; };
+const OptRow OPTIONS[] = {
+    {"h2x_fused", &TdOptions::h2x_fused, OPT_FLAG, 0, 1},
+    {"node_proj_split", &TdOptions::node_proj_split, OPT_FLAG, 0, 1},
+    {"node_proj_bpipe", &TdOptions::node_proj_bpipe, OPT_FLAG, 0, 1},
+    {"node_proj_async", &TdOptions::node_proj_async, OPT_FLAG, 0, 1},
+    {"edge_key_split", &TdOptions::edge_key_split, OPT_FLAG, 0, 1},
+    {"edge_first_layer_f16", &TdOptions::edge_first_layer_f16, OPT_FLAG, 0, 1},
+    {"edge_second_layer_f16", &TdOptions::edge_second_layer_f16, OPT_FLAG, 0, 1},
+    {"edge_row_dealing", &TdOptions::edge_row_dealing, OPT_CLAMPED, 0, 2},
+    {"session_hop_levels", &TdOptions::session_hop_levels, OPT_RANGED, 1, TD_HOP_LEVELS},
+    {"session_forward_reach", &TdOptions::session_forward_reach, OPT_FLAG, 0, 1},
+    {"session_step_lists", &TdOptions::session_step_lists, OPT_FLAG, 0, 1},
+    {"session_share_pockets", &TdOptions::session_share_pockets, OPT_FLAG, 0, 1},
+};
+// ... and what td_model_get_option reports besides: decisions of the LayerNorm fold at td_model_create
+struct ReadOnlyRow { const char *name; int td_model::*field; };
+const ReadOnlyRow READ_ONLY[] = {{"fold_dead_units", &td_model::fold_dead_units}, {"fold_fp32_mlps", &td_model::fold_fp32_mlps}};
+
+template <class Row, size_t N>
+const Row *find_row(const Row (&rows)[N], const char *name) {
+    for (const Row &r : rows)
+        if (strcmp(r.name, name) == 0) return &r;
+    return nullptr;
+}
+
+// The switches the launchers read from the weight structs, from the options and the packed facts (R16q, R16h, f16_safe): the only
+// writer of TdGate::use_split, TdNodeStage::use_split / bpipe / async_copy and TdEdgeMlp::use_split / l1_f16 / l2_f16 / deal_rows.
+void apply_options(td_model *m) {
+    const TdOptions &o = m->opt;
+    m->gate.use_split = o.edge_key_split != 0;
+    for (int l = 0; l < m->cfg.num_layers * stage_rows(m->cfg); ++l) {
+        TdLayer &L = m->layers[l];
+        for (TdNodeStage *n : {&L.nodeX2h, &L.nodeH2x}) { n->use_split = o.node_proj_split != 0; n->bpipe = o.node_proj_bpipe != 0; n->async_copy = o.node_proj_async != 0; }
+        for (TdEdgeMlp *e : {&L.hk, &L.hv, &L.xk, &L.xv}) {
+            e->use_split = e->R16q && o.edge_key_split != 0;
+            e->l1_f16 = e->R16h && e->f16_safe && o.edge_first_layer_f16 != 0;
+            e->l2_f16 = e->f16_safe && o.edge_second_layer_f16 != 0;
+            e->deal_rows = o.edge_row_dealing;
+        }
+    }
+}
+}  // namespace
+
 extern "C" size_t td_model_num_weights(const td_config *cfg) {
     if (!cfg) return 0;
     const td_config &c = *cfg;
@@ -663,16 +712,14 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
     }
     const float *D = m->blob;
     m->emb = TdEmbed{D + oWpT, D + obp, D + oWlT, D + obl};
-    m->gate = TdGate{D + oGR, D + oGb0, D + oGg, D + oGb, D + oGw3, gate_b3, D + oGoff, gate_coeff, D + oGRp, fgate.ln_c1, fgate.ln_c2, m->opt.edge_key_split != 0};
-    auto edge = [&](const EdgeOff &o, bool split = false) {
+    m->gate = TdGate{D + oGR, D + oGb0, D + oGg, D + oGb, D + oGw3, gate_b3, D + oGoff, gate_coeff, D + oGRp, fgate.ln_c1, fgate.ln_c2, false};
+    // the packed facts of every stage; the switches the model options select (false / 0 here) are apply_options' to write
+    auto edge = [&](const EdgeOff &o) {
         return TdEdgeMlp{D + o.R, D + o.gamma, D + o.beta, D + o.W2, D + o.b2, D + o.R16, D + o.Walt16, D + o.Walt,
-                         D + o.R16q, o.R16h ? D + o.R16h : nullptr, o.ln_c1, o.ln_c2, o.w2_bound, m->opt.edge_second_layer_f16 != 0 && o.f16_safe,
-                         m->opt.edge_first_layer_f16 != 0 && o.R16h != 0 && o.f16_safe, o.z_plain, split && m->opt.edge_key_split != 0,
-                         m->opt.edge_row_dealing, o.f16_safe};
+                         D + o.R16q, o.R16h ? D + o.R16h : nullptr, o.ln_c1, o.ln_c2, o.w2_bound, false, false, o.z_plain, false, 0, o.f16_safe};
     };
     auto node = [&](const NodeOff &o) {
-        return TdNodeStage{D + o.projB, D + o.projBias, D + o.qGamma, D + o.qBeta, D + o.q3B, D + o.q3Bias, D + o.projB3, D + o.q3B3,
-                           m->opt.node_proj_split != 0, m->opt.node_proj_bpipe != 0, m->opt.node_proj_async != 0};
+        return TdNodeStage{D + o.projB, D + o.projBias, D + o.qGamma, D + o.qBeta, D + o.q3B, D + o.q3Bias, D + o.projB3, D + o.q3B3, false, false, false};
     };
     for (size_t l = 0; l < lo.size(); ++l) {
         TdLayer &Ly = m->layers[l];
@@ -680,7 +727,7 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
         Ly.offsets = D + lo[l].off; Ly.coeff = lo[l].coeff;
         if (lo[l].has_x) {
             Ly.nodeX2h = node(lo[l].nx);
-            Ly.hk = edge(lo[l].hk, true); Ly.hv = edge(lo[l].hv, true);
+            Ly.hk = edge(lo[l].hk); Ly.hv = edge(lo[l].hv);
             m->fold_fp32_mlps += !lo[l].hk.f16_safe + !lo[l].hv.f16_safe;
             Ly.ew_x2h = c.ew_net_type != 0 ? D + lo[l].ew_x2h : nullptr;
             Ly.gate_m = c.ew_net_type == 3 ? D + lo[l].gate_m : nullptr;
@@ -688,7 +735,7 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
         }
         if (lo[l].has_h) {
             Ly.nodeH2x = node(lo[l].nh);
-            Ly.xk = edge(lo[l].xk, true); Ly.xv = edge(lo[l].xv, true);
+            Ly.xk = edge(lo[l].xk); Ly.xv = edge(lo[l].xv);
             m->fold_fp32_mlps += !lo[l].xk.f16_safe + !lo[l].xv.f16_safe;
             Ly.ew_h2x = c.ew_net_type != 0 ? D + lo[l].ew_h2x : nullptr;
         }
@@ -697,6 +744,7 @@ extern "C" int td_model_create(const td_config *cfg, const float *host_weights, 
     const float *S = D + oS;
     m->sched = TdSchedules{S, S + T, S + 2 * T, S + 3 * T, S + 4 * T, S + 5 * T, S + 6 * T, has_abar ? S + 7 * T : nullptr,
                            has_rc ? S + 8 * T : nullptr, has_rc ? S + 9 * T : nullptr};
+    apply_options(m);
     *out = m;
     return TD_OK;
 }
@@ -710,67 +758,26 @@ extern "C" void td_model_destroy(td_model *m) {
 
 extern "C" int td_model_set_option(td_model *m, const char *name, int32_t value) {
     if (!m || !name) { td_set_error("td_model_set_option: null argument"); return TD_EINVAL; }
-    if (strcmp(name, "h2x_fused") == 0) m->opt.h2x_fused = value != 0;
-    else if (strcmp(name, "node_proj_split") == 0) {
-        m->opt.node_proj_split = value != 0;
-        for (int l = 0; l < m->cfg.num_layers * stage_rows(m->cfg); ++l) m->layers[l].nodeX2h.use_split = m->layers[l].nodeH2x.use_split = value != 0;
-    } else if (strcmp(name, "edge_row_dealing") == 0) {
-        m->opt.edge_row_dealing = value < 0 ? 0 : (value > 2 ? 2 : value);
-        for (int l = 0; l < m->cfg.num_layers * stage_rows(m->cfg); ++l)
-            m->layers[l].hk.deal_rows = m->layers[l].hv.deal_rows = m->layers[l].xk.deal_rows = m->layers[l].xv.deal_rows = m->opt.edge_row_dealing;
-    } else if (strcmp(name, "node_proj_bpipe") == 0) {
-        m->opt.node_proj_bpipe = value != 0;
-        for (int l = 0; l < m->cfg.num_layers * stage_rows(m->cfg); ++l) m->layers[l].nodeX2h.bpipe = m->layers[l].nodeH2x.bpipe = value != 0;
-    } else if (strcmp(name, "node_proj_async") == 0) {
-        m->opt.node_proj_async = value != 0;
-        for (int l = 0; l < m->cfg.num_layers * stage_rows(m->cfg); ++l) m->layers[l].nodeX2h.async_copy = m->layers[l].nodeH2x.async_copy = value != 0;
-    } else if (strcmp(name, "edge_key_split") == 0) {
-        m->opt.edge_key_split = value != 0;
-        m->gate.use_split = value != 0;
-        for (int l = 0; l < m->cfg.num_layers * stage_rows(m->cfg); ++l) {
-            m->layers[l].hk.use_split = m->layers[l].hk.R16q && value != 0;
-            m->layers[l].hv.use_split = m->layers[l].hv.R16q && value != 0;
-            m->layers[l].xk.use_split = m->layers[l].xk.R16q && value != 0;
-            m->layers[l].xv.use_split = m->layers[l].xv.R16q && value != 0;
-        }
-    } else if (strcmp(name, "edge_first_layer_f16") == 0) {
-        m->opt.edge_first_layer_f16 = value != 0;
-        for (int l = 0; l < m->cfg.num_layers * stage_rows(m->cfg); ++l)
-            for (TdEdgeMlp *e : {&m->layers[l].hk, &m->layers[l].hv, &m->layers[l].xk, &m->layers[l].xv}) e->l1_f16 = e->R16h && e->f16_safe && value != 0;
-    } else if (strcmp(name, "edge_second_layer_f16") == 0) {
-        m->opt.edge_second_layer_f16 = value != 0;
-        for (int l = 0; l < m->cfg.num_layers * stage_rows(m->cfg); ++l)
-            for (TdEdgeMlp *e : {&m->layers[l].hk, &m->layers[l].hv, &m->layers[l].xk, &m->layers[l].xv}) e->l2_f16 = e->f16_safe && value != 0;
-    } else if (strcmp(name, "session_hop_levels") == 0) {
-        if (value < 1 || value > TD_HOP_LEVELS) { td_set_error("td_model_set_option: session_hop_levels must be 1..%d", TD_HOP_LEVELS); return TD_EINVAL; }
-        m->opt.session_hop_levels = value;
-    } else if (strcmp(name, "session_forward_reach") == 0) m->opt.session_forward_reach = value != 0;
-    else if (strcmp(name, "session_step_lists") == 0) m->opt.session_step_lists = value != 0;
-    else if (strcmp(name, "session_share_pockets") == 0) m->opt.session_share_pockets = value != 0;
-    else if (strcmp(name, "fold_dead_units") == 0 || strcmp(name, "fold_fp32_mlps") == 0) {
-        td_set_error("td_model_set_option: '%s' is read-only (a decision of the LayerNorm fold at td_model_create)", name);
+    const OptRow *r = find_row(OPTIONS, name);
+    if (!r) {
+        td_set_error(find_row(READ_ONLY, name) ? "td_model_set_option: '%s' is read-only (a decision of the LayerNorm fold at td_model_create)"
+                                               : "td_model_set_option: unknown option '%s'", name);
         return TD_EINVAL;
-    } else { td_set_error("td_model_set_option: unknown option '%s'", name); return TD_EINVAL; }
+    }
+    if (r->kind == OPT_RANGED && (value < r->lo || value > r->hi)) {
+        td_set_error("td_model_set_option: %s must be %d..%d", r->name, r->lo, r->hi);
+        return TD_EINVAL;
+    }
+    m->opt.*r->field = r->kind == OPT_FLAG ? value != 0 : std::min(std::max((int)value, r->lo), r->hi);
+    apply_options(m);
     ++m->option_epoch;          // sessions re-capture their step graph (the captured nodes copied the old variants' arguments by value)
     return TD_OK;
 }
 
 extern "C" int td_model_get_option(const td_model *m, const char *name, int32_t *value) {
     if (!m || !name || !value) { td_set_error("td_model_get_option: null argument"); return TD_EINVAL; }
-    if (strcmp(name, "h2x_fused") == 0) *value = m->opt.h2x_fused;
-    else if (strcmp(name, "node_proj_split") == 0) *value = m->opt.node_proj_split;
-    else if (strcmp(name, "node_proj_async") == 0) *value = m->opt.node_proj_async;
-    else if (strcmp(name, "node_proj_bpipe") == 0) *value = m->opt.node_proj_bpipe;
-    else if (strcmp(name, "edge_row_dealing") == 0) *value = m->opt.edge_row_dealing;
-    else if (strcmp(name, "edge_key_split") == 0) *value = m->opt.edge_key_split;
-    else if (strcmp(name, "edge_second_layer_f16") == 0) *value = m->opt.edge_second_layer_f16;
-    else if (strcmp(name, "edge_first_layer_f16") == 0) *value = m->opt.edge_first_layer_f16;
-    else if (strcmp(name, "session_hop_levels") == 0) *value = m->opt.session_hop_levels;
-    else if (strcmp(name, "session_forward_reach") == 0) *value = m->opt.session_forward_reach;
-    else if (strcmp(name, "session_step_lists") == 0) *value = m->opt.session_step_lists;
-    else if (strcmp(name, "session_share_pockets") == 0) *value = m->opt.session_share_pockets;
-    else if (strcmp(name, "fold_dead_units") == 0) *value = m->fold_dead_units;
-    else if (strcmp(name, "fold_fp32_mlps") == 0) *value = m->fold_fp32_mlps;
+    if (const OptRow *r = find_row(OPTIONS, name)) *value = m->opt.*r->field;
+    else if (const ReadOnlyRow *ro = find_row(READ_ONLY, name)) *value = m->*ro->field;
     else { td_set_error("td_model_get_option: unknown option '%s'", name); return TD_EINVAL; }
     return TD_OK;
 }

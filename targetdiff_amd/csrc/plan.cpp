@@ -21,23 +21,19 @@ namespace tdapi {
 
 Workspace carve(char *base, int64_t N, int64_t B, int64_t Nl) {
     Workspace w;
-    size_t off = 0;
-    auto take = [&](size_t n) { char *p = base ? base + off : nullptr; off += align_up(n); return p; };
+    Carver c{base};
     const size_t n = (size_t)(N > 0 ? N : 1), nl = (size_t)(Nl > 0 ? Nl : n);
-    w.x4a = reinterpret_cast<float4 *>(take(n * sizeof(float4)));
-    w.x4b = reinterpret_cast<float4 *>(take(n * sizeof(float4)));
-    w.gid = reinterpret_cast<int32_t *>(take(n * sizeof(int32_t)));
-    w.nbr = reinterpret_cast<int32_t *>(take(n * TD_K * sizeof(int32_t)));
-    w.lig_node = reinterpret_cast<int32_t *>(take((nl + 1) * sizeof(int32_t)));
-    w.node_ptr = reinterpret_cast<int32_t *>(take((size_t)(B + 1) * sizeof(int32_t)));
-    w.ew = reinterpret_cast<float *>(take(n * TD_K * sizeof(float)));
-    w.P = reinterpret_cast<float *>(take(n * 4 * TD_H * sizeof(float)));
-    w.q = reinterpret_cast<float *>(take(n * TD_H * sizeof(float)));
-    w.h = reinterpret_cast<float *>(take(n * TD_H * sizeof(float)));
-    w.alpha = reinterpret_cast<float *>(take(n * TD_HEADS * TD_K * sizeof(float)));
-    w.Px = reinterpret_cast<float *>(take(n * 4 * TD_H * sizeof(float)));
-    w.qx = reinterpret_cast<float *>(take(n * TD_H * sizeof(float)));
-    w.bytes = off;
+    w.x4a = c.take<float4>(n); w.x4b = c.take<float4>(n);
+    w.gid = c.take<int32_t>(n);
+    w.nbr = c.take<int32_t>(n * TD_K);
+    w.lig_node = c.take<int32_t>(nl + 1);
+    w.node_ptr = c.take<int32_t>((size_t)(B + 1));
+    w.ew = c.take<float>(n * TD_K);
+    w.P = c.take<float>(n * 4 * TD_H); w.q = c.take<float>(n * TD_H);
+    w.h = c.take<float>(n * TD_H);
+    w.alpha = c.take<float>(n * TD_HEADS * TD_K);
+    w.Px = c.take<float>(n * 4 * TD_H); w.qx = c.take<float>(n * TD_H);
+    w.bytes = c.off;
     return w;
 }
 
@@ -250,22 +246,23 @@ int plan_create(const td_config &c, const int32_t *host_pptr, const int32_t *hos
     g_cbase[B] = (int32_t)nc; g_cl[B] = 0; g_lbase[B] = (int32_t)ncl;
     if (nc > 0x7fffffff / TD_K) { td_set_error("graph plan: %lld chunks overflow the 32-bit slot index", (long long)nc); return TD_EINVAL; }
     p.NC = nc; p.NCl = ncl;
-    size_t off = 0;
-    auto reserve = [&](size_t n) { size_t o = off; off += align_up(n ? n : 4); return o; };
-    const size_t o_cptr = reserve((size_t)(p.N + 1) * 4), o_cn = reserve((size_t)nc * 4), o_lc = reserve((size_t)ncl * 4),
-                 o_nbr = reserve((size_t)nc * TD_K * 4), o_ew = reserve((size_t)nc * TD_K * 4),
-                 o_al = reserve((size_t)nc * TD_HEADS * TD_K * 4), o_pn = reserve((size_t)p.Np * 4),
-                 o_pp = reserve((size_t)(B + 1) * 4), o_meta = reserve(meta.size() * 4);
-    hipError_t e = td_malloc_async(reinterpret_cast<void **>(&p.block), off, s);
-    if (e != hipSuccess) { td_set_error("graph plan: hipMallocAsync(%zu) failed: %s", off, hipGetErrorString(e)); return TD_ENOMEM; }
-    char *b = p.block;
-    p.cptr = reinterpret_cast<int32_t *>(b + o_cptr); p.chunk_node = reinterpret_cast<int32_t *>(b + o_cn);
-    p.lig_chunks = reinterpret_cast<int32_t *>(b + o_lc); p.cnbr = reinterpret_cast<int32_t *>(b + o_nbr);
-    p.ew = reinterpret_cast<float *>(b + o_ew); p.alpha = reinterpret_cast<float *>(b + o_al);
-    p.prot_node = reinterpret_cast<int32_t *>(b + o_pn); p.pptr = reinterpret_cast<int32_t *>(b + o_pp);
-    p.meta = reinterpret_cast<int32_t *>(b + o_meta);
+    // one block, laid out twice: for its size, then bound (an empty buffer still takes 4 bytes)
+    auto layout = [&](char *base) {
+        Carver cv{base, 4};
+        p.cptr = cv.take<int32_t>((size_t)(p.N + 1));
+        p.chunk_node = cv.take<int32_t>((size_t)nc); p.lig_chunks = cv.take<int32_t>((size_t)ncl);
+        p.cnbr = cv.take<int32_t>((size_t)nc * TD_K); p.ew = cv.take<float>((size_t)nc * TD_K);
+        p.alpha = cv.take<float>((size_t)nc * TD_HEADS * TD_K);
+        p.prot_node = cv.take<int32_t>((size_t)p.Np); p.pptr = cv.take<int32_t>((size_t)(B + 1));
+        p.meta = cv.take<int32_t>(meta.size());
+        return cv.off;
+    };
+    const size_t bytes = layout(nullptr);
+    hipError_t e = td_malloc_async(reinterpret_cast<void **>(&p.block), bytes, s);
+    if (e != hipSuccess) { td_set_error("graph plan: hipMallocAsync(%zu) failed: %s", bytes, hipGetErrorString(e)); return TD_ENOMEM; }
+    layout(p.block);
     // the small per-graph tables: synchronous copies (the source vectors die with this frame)
-    e = hipMemcpyAsync(b + o_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, s);
+    e = hipMemcpyAsync(p.meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(p.pptr, host_pptr, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {

@@ -45,6 +45,7 @@ struct td_session {
     int32_t *fwd_rows, *fwd_rest, *fwd_counts;
     bool use_fwd;
     uint8_t *clean;
+    float *setup_lpos; int64_t *setup_lv; int32_t *canon_rows;          // set-up only: zero ligand atoms for the first compose, the canonical graphs' protein rows
     int graph_nodes_max;         // exact size of the largest graph -- sizes the LDS flags of td_launch_step_lists
     // Per-pocket sharing of the static tables (CACHING, default graph; model option session_share_pockets): all samples of a pocket carry the
     // same protein block (scripts/sample_diffusion.py:42 replicates one pocket n_data times), so skeys / snbr / ews / h0 / h1s / h2s are kept
@@ -117,6 +118,188 @@ void session_free(td_session *S, hipStream_t s) {
 }
 }  // namespace tdapi
 
+namespace {
+// the session object until td_session_create hands it out: whatever it owns by then goes back on every other way out
+struct SessionGuard {
+    td_session *S; hipStream_t s;
+    ~SessionGuard() { session_free(S, s); }
+};
+
+// Per-pocket sharing of the static tables: which graphs carry the same protein block, bit for bit?  cgraph[g] = the first graph of the
+// batch with graph g's block (its canonical graph), cbase[g] = where that graph's rows start in the compact tables, canon_rows = the
+// protein nodes of the canonical graphs back to back: the rows of the compact tables.
+struct PocketGroups { std::vector<int32_t> cgraph, cbase, canon_rows; int groups = 0; };
+int group_pockets(const td_model *m, const float *d_protein_pos, const float *d_protein_v, const int32_t *d_protein_ptr, int64_t B,
+                  const std::vector<int32_t> &hp, const std::vector<int32_t> &hl, hipStream_t s, PocketGroups *out) {
+    const int F = m->cfg.protein_feat_dim;
+    const size_t nb = (size_t)B;
+    unsigned long long *d_hash = nullptr;
+    int32_t *d_cand = nullptr, *d_flag = nullptr;
+    auto layout = [&](char *base) {
+        Carver c{base};
+        d_hash = c.take<unsigned long long>(nb);
+        d_cand = c.take<int32_t>(nb); d_flag = c.take<int32_t>(nb);
+        return c.off;
+    };
+    AsyncScratch tmp(s);
+    char *block = nullptr;
+    int rc;
+    if ((rc = tmp.take(&block, layout(nullptr), "td_session_create")) != TD_OK) return rc;
+    layout(block);
+    std::vector<unsigned long long> hash(nb);
+    std::vector<int32_t> flag(nb, 0);
+    out->cgraph.assign(nb, 0); out->cbase.assign(nb, 0);
+    if ((rc = td_launch_pocket_hash(d_protein_pos, d_protein_v, d_protein_ptr, B, F, d_hash, s)) != TD_OK) return rc;
+    TD_CHECK_HIP(hipMemcpyAsync(hash.data(), d_hash, nb * 8, hipMemcpyDeviceToHost, s));
+    TD_CHECK_HIP(hipStreamSynchronize(s));
+    {   // candidate = the first graph of the batch with the same (atom count, hash): an ordered map, B log B for any mix of pockets
+        std::map<std::pair<int32_t, unsigned long long>, int32_t> first;
+        for (int64_t g = 0; g < B; ++g)
+            out->cgraph[(size_t)g] = first.emplace(std::make_pair(hp[g + 1] - hp[g], hash[(size_t)g]), (int32_t)g).first->second;
+    }
+    TD_CHECK_HIP(hipMemcpyAsync(d_cand, out->cgraph.data(), nb * 4, hipMemcpyHostToDevice, s));
+    TD_CHECK_HIP(hipMemsetAsync(d_flag, 0, nb * 4, s));
+    if ((rc = td_launch_pocket_verify(d_protein_pos, d_protein_v, d_protein_ptr, B, F, d_cand, d_flag, s)) != TD_OK) return rc;
+    TD_CHECK_HIP(hipMemcpyAsync(flag.data(), d_flag, nb * 4, hipMemcpyDeviceToHost, s));
+    TD_CHECK_HIP(hipStreamSynchronize(s));
+    for (int64_t g = 0; g < B; ++g) {
+        if (flag[(size_t)g]) out->cgraph[(size_t)g] = (int32_t)g;          // same hash, different block: keeps its own tables
+        const int32_t c = out->cgraph[(size_t)g];
+        if (c == (int32_t)g) {
+            out->cbase[(size_t)g] = (int32_t)out->canon_rows.size();
+            const int32_t n0 = hp[g] + hl[g], np = hp[g + 1] - hp[g];          // the graph's nodes start at node_ptr[g]; protein atoms first
+            for (int32_t a = 0; a < np; ++a) out->canon_rows.push_back(n0 + a);
+            ++out->groups;
+        } else {
+            out->cbase[(size_t)g] = out->cbase[(size_t)c];
+        }
+    }
+    return TD_OK;
+}
+
+// The session's device block, [workspace | session-static buffers]: with base == nullptr its size, otherwise every buffer bound.  The
+// one place that knows what the block holds.  share: the static tables have S->static_rows compact rows, not one per node.
+size_t session_layout(td_session *S, char *base, bool share) {
+    S->w = carve(base, S->N, S->B, S->Nl);
+    Carver c{base ? base + S->w.bytes : nullptr, 4};
+    const size_t n = (size_t)S->N, np = (size_t)S->Np, nl = (size_t)S->Nl, nb = (size_t)S->B;
+    const size_t nc = S->chunked ? (size_t)S->plan.NC : n;          // 32-slot rows of the neighbour table
+    const size_t ks = S->chunked ? 64 : TD_K;                       // static keys kept per protein row
+    const size_t ns = share ? (size_t)S->static_rows : n, ncs = share ? (size_t)S->static_rows : nc;          // rows of the static tables
+    const size_t C = S->caching ? 1 : 0;                            // (a PLAIN session keeps none of the caching tables)
+    S->prot_node = c.take<int32_t>(np);
+    S->pptr = c.take<int32_t>(nb + 1); S->lptr = c.take<int32_t>(nb + 1);
+    S->h0 = c.take<float>(ns * TD_H);
+    S->setup_lpos = c.take<float>(nl * 3); S->setup_lv = c.take<int64_t>(nl);
+    S->snbr = c.take<int32_t>(C * ncs * TD_K);
+    S->skeys = c.take<unsigned long long>(C * ns * ks);
+    S->ews = c.take<float>(C * ncs * TD_K);
+    S->h1s = c.take<float>(C * ns * TD_H); S->h2s = c.take<float>(C * ns * TD_H);
+    S->flags2 = c.take<uint8_t>(C * n);
+    S->fwd_rows = c.take<int32_t>(C * n); S->fwd_rest = c.take<int32_t>(C * n); S->fwd_counts = c.take<int32_t>(64);
+    S->P0 = c.take<float>(C * n * 4 * TD_H); S->q0 = c.take<float>(C * n * TD_H);
+    S->clean = c.take<uint8_t>(C * n);
+    S->dirty_rows = c.take<int32_t>(C * n); S->dirty_count = c.take<int32_t>(64);          // counts: [0] rows, [1] chunks (general graphs)
+    S->hop_rows = c.take<int32_t>(C * n * TD_HOP_LEVELS); S->hop_count = c.take<int32_t>(64);
+    S->dirty_chunks = c.take<int32_t>(S->chunked ? C * nc : 0);
+    S->pred_pos = c.take<float>(nl * 3); S->pred_v = c.take<float>(nl * TD_MAXC);
+    S->cgraph = c.take<int32_t>(share ? nb : 0); S->cbase = c.take<int32_t>(share ? nb : 0);
+    S->canon_rows = c.take<int32_t>(share ? ns : 0);
+    if (!share) S->cgraph = S->cbase = S->canon_rows = nullptr;          // (nullptr: tables indexed by node)
+    return S->w.bytes + c.off;
+}
+
+// Fills a bound session block: the packed batch (ligand rows are placeholders until the first step) and, for a CACHING session, the
+// protein-only graph, its gate rows, the layer-0 projections / queries and the layer-0 / layer-1 x2h outputs.  With sharing all of it runs
+// on the canonical graphs' protein rows only, into full-size (node-indexed) scratch tables whose canonical rows are then compacted into
+// the shared tables.
+int session_build_static(td_session *S, const float *d_protein_pos, const float *d_protein_v, const int32_t *d_protein_ptr,
+                         const int32_t *d_ligand_ptr, const PocketGroups &pg, hipStream_t s) {
+    const td_model *m = S->m;
+    const int64_t N = S->N, N_p = S->Np, N_l = S->Nl, B = S->B;
+    const size_t n = (size_t)N, nb = (size_t)B;
+    const bool share = S->cgraph != nullptr;
+    Workspace &w = S->w;
+    int rc;
+    TD_CHECK_HIP(hipMemcpyAsync(S->pptr, d_protein_ptr, (nb + 1) * 4, hipMemcpyDeviceToDevice, s));
+    TD_CHECK_HIP(hipMemcpyAsync(S->lptr, d_ligand_ptr, (nb + 1) * 4, hipMemcpyDeviceToDevice, s));
+    TD_CHECK_HIP(hipMemsetAsync(S->setup_lpos, 0, (size_t)N_l * 12, s));
+    TD_CHECK_HIP(hipMemsetAsync(S->setup_lv, 0, (size_t)N_l * 8, s));
+    AsyncScratch scratch(s);          // (goes back in stream order when this function returns: after the compaction, or on an error)
+    unsigned long long *skeys_f = S->skeys;
+    int32_t *snbr_f = S->snbr;
+    float *ews_f = S->ews, *h0_f = S->h0, *h1_f = S->h1s, *h2_f = S->h2s;
+    if (share) {
+        auto layout = [&](char *base) {
+            Carver c{base};
+            skeys_f = c.take<unsigned long long>(n * TD_K);
+            snbr_f = c.take<int32_t>(n * TD_K); ews_f = c.take<float>(n * TD_K);
+            h0_f = c.take<float>(n * TD_H); h1_f = c.take<float>(n * TD_H); h2_f = c.take<float>(n * TD_H);
+            return c.off;
+        };
+        char *block = nullptr;
+        if ((rc = scratch.take(&block, layout(nullptr), "td_session_create")) != TD_OK) return rc;
+        layout(block);
+        TD_CHECK_HIP(hipMemcpyAsync(S->cgraph, pg.cgraph.data(), nb * 4, hipMemcpyHostToDevice, s));
+        TD_CHECK_HIP(hipMemcpyAsync(S->cbase, pg.cbase.data(), nb * 4, hipMemcpyHostToDevice, s));
+        TD_CHECK_HIP(hipMemcpyAsync(S->canon_rows, pg.canon_rows.data(), pg.canon_rows.size() * 4, hipMemcpyHostToDevice, s));
+        TD_CHECK_HIP(hipStreamSynchronize(s));          // (the host vectors go out of scope with td_session_create)
+    }
+    // embeddings + packed order, protein row list
+    int32_t *prot_out = S->chunked ? S->plan.prot_node : S->prot_node;
+    if ((rc = td_launch_compose(m, d_protein_pos, d_protein_v, S->pptr, N_p, S->setup_lpos, S->setup_lv, S->lptr, N_l, B, h0_f, w.x4a,
+                                w.node_ptr, w.gid, w.lig_node, prot_out, s)) != TD_OK) return rc;
+    if (S->chunked) {
+        S->prot_node = S->plan.prot_node;
+        if ((rc = plan_layout(S->plan, w.node_ptr, w.gid, s)) != TD_OK) return rc;
+    }
+    TD_CHECK_HIP(hipMemcpyAsync(w.x4b, w.x4a, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    if (!S->caching) return TD_OK;
+    // ---- protein-only graph, its gate rows, layer-0 projections / queries, layer-0 x2h output
+    const int32_t *set_rows = share ? S->canon_rows : S->prot_node;
+    const int64_t set_count = share ? S->static_rows : N_p;
+    const size_t nc = S->chunked ? (size_t)S->plan.NC : n;
+    GraphTab gt = session_tab(S);                  // the step's table (alpha is scratch here)
+    GraphTab st = gt;                              // the static table
+    st.nbr = snbr_f; st.ew = ews_f;
+    TD_CHECK_HIP(hipMemsetAsync(snbr_f, 0xff, nc * TD_K * 4, s));
+    if (S->chunked) {
+        if ((rc = td_launch_knn_general_static(w.x4a, w.node_ptr, S->pptr, w.gid, S->prot_node, N_p, m->cfg.knn, S->graph_nodes_max,
+                                               S->plan.cptr, S->snbr, S->skeys, s)) != TD_OK) return rc;
+        if ((rc = td_launch_gate(m->gate, w.x4a, S->snbr, S->plan.NC, nullptr, nullptr, S->ews, s, S->plan.chunk_node)) != TD_OK) return rc;
+        // the step's table: ligand rows start as all pads; hybrid: their ligand half never changes
+        TD_CHECK_HIP(hipMemsetAsync(S->plan.cnbr, 0xff, nc * TD_K * 4, s));
+        TD_CHECK_HIP(hipMemsetAsync(S->plan.ew, 0, nc * TD_K * 4, s));
+        if (m->cfg.cutoff_mode == TD_CUTOFF_HYBRID &&
+            (rc = td_launch_hybrid_ligand_half(w.node_ptr, S->pptr, w.gid, w.lig_node, N_l, S->plan.cptr, S->plan.cnbr, s)) != TD_OK) return rc;
+    } else {
+        if ((rc = td_launch_knn_static(w.x4a, w.node_ptr, w.gid, set_rows, set_count, S->max_graph_nodes, snbr_f, skeys_f, s, m->cfg.knn)) != TD_OK) return rc;
+        if ((rc = td_launch_gate(m->gate, w.x4a, snbr_f, set_count, set_rows, nullptr, ews_f, s)) != TD_OK) return rc;
+    }
+    const TdLayer &L0 = m->layers[0];
+    if ((rc = td_launch_node_proj(L0.nodeX2h, h0_f, N, nullptr, 0x1f, S->P0, S->q0, s)) != TD_OK) return rc;
+    if ((rc = key_pass(L0.hk, L0, w.x4a, st, st.ew, st.nbr, S->P0, S->q0, set_rows, nullptr, set_count, gt.alpha, s)) != TD_OK) return rc;
+    TD_CHECK_HIP(hipMemcpyAsync(h1_f, h0_f, n * TD_H * 4, hipMemcpyDeviceToDevice, s));
+    if ((rc = value_pass(L0.hv, L0, w.x4a, st, st.nbr, S->P0, set_rows, nullptr, set_count, h1_f, gt.alpha, nullptr, 0, s)) != TD_OK) return rc;
+    if (S->use_fwd) {      // layer-1 x2h output of the protein-only graph (valid wherever the ligand is two hops away)
+        const TdLayer &L1 = m->layers[1];
+        if ((rc = td_launch_node_proj(L1.nodeX2h, h1_f, N, nullptr, 0x1f, w.P, w.q, s)) != TD_OK) return rc;
+        if ((rc = key_pass(L1.hk, L1, w.x4a, st, st.ew, st.nbr, w.P, w.q, set_rows, nullptr, set_count, gt.alpha, s)) != TD_OK) return rc;
+        TD_CHECK_HIP(hipMemcpyAsync(h2_f, h1_f, n * TD_H * 4, hipMemcpyDeviceToDevice, s));
+        if ((rc = value_pass(L1.hv, L1, w.x4a, st, st.nbr, w.P, set_rows, nullptr, set_count, h2_f, gt.alpha, nullptr, 0, s)) != TD_OK) return rc;
+    }
+    if (share) {           // the canonical rows of the scratch tables -> the compact shared tables
+        if ((rc = td_launch_compact_rows(skeys_f, set_rows, set_count, TD_K * 8, S->skeys, s)) != TD_OK) return rc;
+        if ((rc = td_launch_compact_rows(snbr_f, set_rows, set_count, TD_K * 4, S->snbr, s)) != TD_OK) return rc;
+        if ((rc = td_launch_compact_rows(ews_f, set_rows, set_count, TD_K * 4, S->ews, s)) != TD_OK) return rc;
+        if ((rc = td_launch_compact_rows(h0_f, set_rows, set_count, TD_H * 4, S->h0, s)) != TD_OK) return rc;
+        if ((rc = td_launch_compact_rows(h1_f, set_rows, set_count, TD_H * 4, S->h1s, s)) != TD_OK) return rc;
+        if (S->use_fwd && (rc = td_launch_compact_rows(h2_f, set_rows, set_count, TD_H * 4, S->h2s, s)) != TD_OK) return rc;
+    }
+    return TD_OK;
+}
+}  // namespace
+
 extern "C" int td_session_create(const td_model *m, const float *d_protein_pos, const float *d_protein_v,
                                  const int32_t *d_protein_ptr, int64_t N_p, const int32_t *d_ligand_ptr, int64_t N_l,
                                  int64_t B, int32_t max_graph_nodes, void *stream, td_session **out) {
@@ -125,237 +308,41 @@ extern "C" int td_session_create(const td_model *m, const float *d_protein_pos, 
         return TD_EINVAL;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t N = N_p + N_l;
     td_session *S = new (std::nothrow) td_session();
     if (!S) { td_set_error("td_session_create: out of host memory"); return TD_ENOMEM; }
-    S->m = m; S->N = N; S->Np = N_p; S->Nl = N_l; S->B = B; S->max_graph_nodes = max_graph_nodes; S->last_stream = s;
-    S->chunked = !default_graph(m->cfg);
+    SessionGuard guard{S, s};
+    S->m = m; S->N = N_p + N_l; S->Np = N_p; S->Nl = N_l; S->B = B; S->max_graph_nodes = max_graph_nodes; S->last_stream = s;
     int rc;
     // per-graph atom counts: the exact size of the largest graph, and the chunk layout of a general graph
     std::vector<int32_t> hp, hl;
-    if ((rc = fetch_ptrs(d_protein_ptr, d_ligand_ptr, B, hp, hl, s)) != TD_OK) { delete S; return rc; }
+    if ((rc = fetch_ptrs(d_protein_ptr, d_ligand_ptr, B, hp, hl, s)) != TD_OK) return rc;
     int gmax = 0;
     for (int64_t g = 0; g < B; ++g) gmax = std::max(gmax, (hp[g + 1] - hp[g]) + (hl[g + 1] - hl[g]));
     S->graph_nodes_max = gmax;
+    S->chunked = !default_graph(m->cfg);
     const bool knn_like = m->cfg.cutoff_mode == TD_CUTOFF_KNN || m->cfg.cutoff_mode == TD_CUTOFF_HYBRID;
     S->caching = knn_like && (!S->chunked || gmax <= TD_STEP_LISTS_MAX_NODES) && num_blocks(m->cfg) == 1 && m->cfg.ew_net_type == 0 &&
                  !m->cfg.x2h_out_fc && !m->cfg.sync_twoup && stage_rows(m->cfg) == 1;      // (the static-protein tables hold the global gate's rows and plain x2h outputs;
                                                                  // a cached layer 0 skips the projections sync_twoup takes at its top)
-    if (S->chunked && (rc = plan_create(m->cfg, hp.data(), hl.data(), B, s, &S->plan)) != TD_OK) { delete S; return rc; }
-    const int64_t NC = S->chunked ? S->plan.NC : N;          // 32-slot rows of the neighbour table
-    const int KS = S->chunked ? 64 : TD_K;                   // static keys kept per protein row
-    // ---- per-pocket sharing of the static tables: which graphs carry the same protein block (bit for bit)?
+    S->use_fwd = S->caching && m->opt.session_forward_reach && m->cfg.num_layers >= 2;
+    // receptive-field levels tracked per step (each prunes one more layer from the end)
+    S->hop_levels = std::min(std::min(std::max(m->opt.session_hop_levels, 1), TD_HOP_LEVELS), m->cfg.num_layers);
+    if (S->chunked && (rc = plan_create(m->cfg, hp.data(), hl.data(), B, s, &S->plan)) != TD_OK) return rc;
+    // the three phases: pocket groups (default graph, model option session_share_pockets), the device block, its contents
     const bool share = S->caching && !S->chunked && m->opt.session_share_pockets != 0;
-    std::vector<int32_t> cgraph_h, cbase_h, canon_rows_h;
-    int64_t Nc = N;                                          // rows of the static tables (compact: the canonical graphs' protein atoms)
+    PocketGroups pg;
     if (share) {
-        const int F = m->cfg.protein_feat_dim;
-        char *tg = nullptr;
-        const size_t tg_bytes = align_up((size_t)B * 8) + 2 * align_up((size_t)B * 4);
-        hipError_t te = td_malloc_async(reinterpret_cast<void **>(&tg), tg_bytes, s);
-        if (te != hipSuccess) { td_set_error("td_session_create: hipMallocAsync(%zu) failed: %s", tg_bytes, hipGetErrorString(te)); delete S; return TD_ENOMEM; }
-        unsigned long long *d_hash = reinterpret_cast<unsigned long long *>(tg);
-        int32_t *d_cand = reinterpret_cast<int32_t *>(tg + align_up((size_t)B * 8)), *d_flag = reinterpret_cast<int32_t *>(tg + align_up((size_t)B * 8) + align_up((size_t)B * 4));
-        std::vector<unsigned long long> hash((size_t)B);
-        std::vector<int32_t> flag((size_t)B, 0);
-        cgraph_h.assign((size_t)B, 0); cbase_h.assign((size_t)B, 0);
-        auto bail = [&](int r) { free_async_or_sync(tg, s); delete S; return r; };
-        if ((rc = td_launch_pocket_hash(d_protein_pos, d_protein_v, d_protein_ptr, B, F, d_hash, s)) != TD_OK) return bail(rc);
-        if (hipMemcpyAsync(hash.data(), d_hash, (size_t)B * 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-            td_set_error("td_session_create: reading the pocket hashes failed"); return bail(TD_EHIP);
-        }
-        {   // candidate = the first graph of the batch with the same (atom count, hash): an ordered map, B log B for any mix of pockets
-            std::map<std::pair<int32_t, unsigned long long>, int32_t> first;
-            for (int64_t g = 0; g < B; ++g)
-                cgraph_h[(size_t)g] = first.emplace(std::make_pair(hp[g + 1] - hp[g], hash[(size_t)g]), (int32_t)g).first->second;
-        }
-        hipError_t e2 = hipMemcpyAsync(d_cand, cgraph_h.data(), (size_t)B * 4, hipMemcpyHostToDevice, s);
-        if (e2 == hipSuccess) e2 = hipMemsetAsync(d_flag, 0, (size_t)B * 4, s);
-        if (e2 != hipSuccess) { td_set_error("td_session_create: pocket grouping failed: %s", hipGetErrorString(e2)); return bail(TD_EHIP); }
-        if ((rc = td_launch_pocket_verify(d_protein_pos, d_protein_v, d_protein_ptr, B, F, d_cand, d_flag, s)) != TD_OK) return bail(rc);
-        if (hipMemcpyAsync(flag.data(), d_flag, (size_t)B * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-            td_set_error("td_session_create: reading the pocket comparison failed"); return bail(TD_EHIP);
-        }
-        free_async_or_sync(tg, s);
-        Nc = 0;
-        for (int64_t g = 0; g < B; ++g) {
-            if (flag[(size_t)g]) cgraph_h[(size_t)g] = (int32_t)g;          // same hash, different block: keeps its own tables
-            const int32_t c = cgraph_h[(size_t)g];
-            if (c == (int32_t)g) {
-                cbase_h[(size_t)g] = (int32_t)Nc;
-                const int32_t n0 = hp[g] + hl[g], np = hp[g + 1] - hp[g];          // the graph's nodes start at node_ptr[g]; protein atoms first
-                for (int32_t a = 0; a < np; ++a) canon_rows_h.push_back(n0 + a);
-                Nc += np;
-                ++S->pocket_groups;
-            } else {
-                cbase_h[(size_t)g] = cbase_h[(size_t)c];
-            }
-        }
-        S->static_rows = Nc;
+        if ((rc = group_pockets(m, d_protein_pos, d_protein_v, d_protein_ptr, B, hp, hl, s, &pg)) != TD_OK) return rc;
+        S->static_rows = (int64_t)pg.canon_rows.size();
+        S->pocket_groups = pg.groups;
     }
-
-    // ---- one device block: [workspace | session-static buffers]
-    const size_t ws_bytes = carve(nullptr, N, B, N_l).bytes;
-    size_t off = ws_bytes;
-    auto reserve = [&](size_t n) { size_t o = off; off += align_up(n ? n : 4); return o; };
-    const size_t n = (size_t)N, nc = (size_t)NC;
-    const bool C = S->caching;
-    const size_t ns = share ? (size_t)Nc : n, ncs = share ? (size_t)Nc : nc;          // rows of the static tables
-    const size_t o_prot = reserve((size_t)N_p * 4), o_pptr = reserve((size_t)(B + 1) * 4), o_lptr = reserve((size_t)(B + 1) * 4),
-                 o_h0 = reserve(ns * TD_H * 4), o_tmp_lpos = reserve((size_t)N_l * 12), o_tmp_lv = reserve((size_t)N_l * 8),
-                 o_snbr = reserve(C ? ncs * TD_K * 4 : 0), o_skeys = reserve(C ? ns * KS * 8 : 0), o_ews = reserve(C ? ncs * TD_K * 4 : 0),
-                 o_h1s = reserve(C ? ns * TD_H * 4 : 0), o_h2s = reserve(C ? ns * TD_H * 4 : 0), o_f2 = reserve(C ? n : 0),
-                 o_frows = reserve(C ? n * 4 : 0), o_frest = reserve(C ? n * 4 : 0), o_fcnt = reserve(256),
-                 o_P0 = reserve(C ? n * 4 * TD_H * 4 : 0), o_q0 = reserve(C ? n * TD_H * 4 : 0), o_clean = reserve(C ? n : 0),
-                 o_dirty = reserve(C ? n * 4 : 0), o_dcnt = reserve(256), o_hop = reserve(C ? n * 4 * TD_HOP_LEVELS : 0),
-                 o_hcnt = reserve(256), o_dchunks = reserve(C && S->chunked ? nc * 4 : 0),
-                 o_ppos = reserve((size_t)N_l * 3 * 4), o_pv = reserve((size_t)N_l * TD_MAXC * 4),
-                 o_cg = reserve(share ? (size_t)B * 4 : 0), o_cb = reserve(share ? (size_t)B * 4 : 0), o_crows = reserve(share ? (size_t)Nc * 4 : 0);
-    hipError_t e = td_malloc_async(reinterpret_cast<void **>(&S->block), off, s);
-    if (e != hipSuccess) {
-        td_set_error("td_session_create: hipMallocAsync(%zu) failed: %s", off, hipGetErrorString(e));
-        S->block = nullptr;
-        session_free(S, s);
-        return TD_ENOMEM;
-    }
-    char *b = S->block;
-    S->w = carve(b, N, B, N_l);
-    S->prot_node = reinterpret_cast<int32_t *>(b + o_prot);
-    S->pptr = reinterpret_cast<int32_t *>(b + o_pptr);
-    S->lptr = reinterpret_cast<int32_t *>(b + o_lptr);
-    S->snbr = reinterpret_cast<int32_t *>(b + o_snbr);
-    S->skeys = reinterpret_cast<unsigned long long *>(b + o_skeys);
-    S->ews = reinterpret_cast<float *>(b + o_ews);
-    S->h0 = reinterpret_cast<float *>(b + o_h0);
-    S->h1s = reinterpret_cast<float *>(b + o_h1s);
-    S->h2s = reinterpret_cast<float *>(b + o_h2s);
-    S->flags2 = reinterpret_cast<uint8_t *>(b + o_f2);
-    S->fwd_rows = reinterpret_cast<int32_t *>(b + o_frows);
-    S->fwd_rest = reinterpret_cast<int32_t *>(b + o_frest);
-    S->fwd_counts = reinterpret_cast<int32_t *>(b + o_fcnt);
-    S->use_fwd = C && m->opt.session_forward_reach && m->cfg.num_layers >= 2;
-    S->P0 = reinterpret_cast<float *>(b + o_P0);
-    S->q0 = reinterpret_cast<float *>(b + o_q0);
-    S->clean = reinterpret_cast<uint8_t *>(b + o_clean);
-    S->dirty_rows = reinterpret_cast<int32_t *>(b + o_dirty);
-    S->dirty_count = reinterpret_cast<int32_t *>(b + o_dcnt);       // [0] rows, [1] chunks (general graphs)
-    S->hop_rows = reinterpret_cast<int32_t *>(b + o_hop);
-    S->hop_count = reinterpret_cast<int32_t *>(b + o_hcnt);
-    S->dirty_chunks = reinterpret_cast<int32_t *>(b + o_dchunks);
-    S->pred_pos = reinterpret_cast<float *>(b + o_ppos);
-    S->pred_v = reinterpret_cast<float *>(b + o_pv);
-    int32_t *canon_rows = nullptr;
-    if (share) {
-        S->cgraph = reinterpret_cast<int32_t *>(b + o_cg);
-        S->cbase = reinterpret_cast<int32_t *>(b + o_cb);
-        canon_rows = reinterpret_cast<int32_t *>(b + o_crows);
-    }
-    {
-        // receptive-field levels tracked per step (each prunes one more layer from the end)
-        int lv = m->opt.session_hop_levels;
-        if (lv < 1) lv = 1;
-        if (lv > TD_HOP_LEVELS) lv = TD_HOP_LEVELS;
-        if (lv > m->cfg.num_layers) lv = m->cfg.num_layers;
-        S->hop_levels = lv;
-    }
-    float *tmp_lpos = reinterpret_cast<float *>(b + o_tmp_lpos);
-    int64_t *tmp_lv = reinterpret_cast<int64_t *>(b + o_tmp_lv);
-    Workspace &w = S->w;
-    auto fail = [&](int r) { session_free(S, s); return r; };
-#define TD_TRY(expr) do { if ((rc = (expr)) != TD_OK) return fail(rc); } while (0)
-#define TD_TRY_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { td_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); return fail(TD_EHIP); } } while (0)
-    TD_TRY_HIP(hipMemcpyAsync(S->pptr, d_protein_ptr, (size_t)(B + 1) * 4, hipMemcpyDeviceToDevice, s));
-    TD_TRY_HIP(hipMemcpyAsync(S->lptr, d_ligand_ptr, (size_t)(B + 1) * 4, hipMemcpyDeviceToDevice, s));
-    TD_TRY_HIP(hipMemsetAsync(tmp_lpos, 0, (size_t)N_l * 12, s));
-    TD_TRY_HIP(hipMemsetAsync(tmp_lv, 0, (size_t)N_l * 8, s));
-    // Sharing: the set-up below runs on the canonical graphs' protein rows only, into full-size (node-indexed) scratch tables that live in one
-    // stream-ordered block until their canonical rows have been copied into the compact shared tables
-    char *scratch = nullptr;
-    float *h0_f = S->h0, *h1_f = S->h1s, *h2_f = S->h2s, *ews_f = S->ews;
-    int32_t *snbr_f = S->snbr;
-    unsigned long long *skeys_f = S->skeys;
-    const int32_t *set_rows = S->prot_node;          // (assigned below for chunked plans)
-    int64_t set_count = N_p;
-    auto fail2 = [&](int r) { free_async_or_sync(scratch, s); return fail(r); };
-    if (share) {
-        const size_t b_keys = align_up(n * TD_K * 8), b_nbr = align_up(n * TD_K * 4), b_h = align_up(n * TD_H * 4);
-        const size_t sb = b_keys + 2 * b_nbr + 3 * b_h;
-        hipError_t se = td_malloc_async(reinterpret_cast<void **>(&scratch), sb, s);
-        if (se != hipSuccess) { td_set_error("td_session_create: hipMallocAsync(%zu) failed: %s", sb, hipGetErrorString(se)); scratch = nullptr; return fail(TD_ENOMEM); }
-        skeys_f = reinterpret_cast<unsigned long long *>(scratch);
-        snbr_f = reinterpret_cast<int32_t *>(scratch + b_keys);
-        ews_f = reinterpret_cast<float *>(scratch + b_keys + b_nbr);
-        h0_f = reinterpret_cast<float *>(scratch + b_keys + 2 * b_nbr);
-        h1_f = reinterpret_cast<float *>(scratch + b_keys + 2 * b_nbr + b_h);
-        h2_f = reinterpret_cast<float *>(scratch + b_keys + 2 * b_nbr + 2 * b_h);
-        hipError_t ue = hipMemcpyAsync(S->cgraph, cgraph_h.data(), (size_t)B * 4, hipMemcpyHostToDevice, s);
-        if (ue == hipSuccess) ue = hipMemcpyAsync(S->cbase, cbase_h.data(), (size_t)B * 4, hipMemcpyHostToDevice, s);
-        if (ue == hipSuccess) ue = hipMemcpyAsync(canon_rows, canon_rows_h.data(), (size_t)Nc * 4, hipMemcpyHostToDevice, s);
-        if (ue == hipSuccess) ue = hipStreamSynchronize(s);          // (the host vectors go out of scope with this call)
-        if (ue != hipSuccess) { td_set_error("td_session_create: uploading the pocket groups failed: %s", hipGetErrorString(ue)); return fail2(TD_EHIP); }
-    }
-#undef TD_TRY
-#undef TD_TRY_HIP
-#define TD_TRY(expr) do { if ((rc = (expr)) != TD_OK) return fail2(rc); } while (0)
-#define TD_TRY_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { td_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); return fail2(TD_EHIP); } } while (0)
-    // embeddings + packed order (ligand rows are placeholders until the first step), protein row list
-    int32_t *prot_out = S->chunked ? S->plan.prot_node : S->prot_node;
-    TD_TRY(td_launch_compose(m, d_protein_pos, d_protein_v, S->pptr, N_p, tmp_lpos, tmp_lv, S->lptr, N_l, B, h0_f, w.x4a,
-                             w.node_ptr, w.gid, w.lig_node, prot_out, s));
-    if (S->chunked) {
-        S->prot_node = S->plan.prot_node;
-        TD_TRY(plan_layout(S->plan, w.node_ptr, w.gid, s));
-    }
-    set_rows = share ? canon_rows : S->prot_node;
-    set_count = share ? Nc : N_p;
-    TD_TRY_HIP(hipMemcpyAsync(w.x4b, w.x4a, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
-    if (!S->caching) {
-        *out = S;
-        return TD_OK;
-    }
-    // ---- protein-only graph, its gate rows, layer-0 projections / queries, layer-0 x2h output
-    GraphTab gt = session_tab(S);                  // the step's table (alpha is scratch here)
-    GraphTab st = gt;                              // the static table
-    st.nbr = snbr_f; st.ew = ews_f;
-    TD_TRY_HIP(hipMemsetAsync(snbr_f, 0xff, nc * TD_K * 4, s));
-    if (S->chunked) {
-        TD_TRY(td_launch_knn_general_static(w.x4a, w.node_ptr, S->pptr, w.gid, S->prot_node, N_p, m->cfg.knn, gmax, S->plan.cptr,
-                                            S->snbr, S->skeys, s));
-        TD_TRY(td_launch_gate(m->gate, w.x4a, S->snbr, NC, nullptr, nullptr, S->ews, s, S->plan.chunk_node));
-        // the step's table: ligand rows start as all pads; hybrid: their ligand half never changes
-        TD_TRY_HIP(hipMemsetAsync(S->plan.cnbr, 0xff, nc * TD_K * 4, s));
-        TD_TRY_HIP(hipMemsetAsync(S->plan.ew, 0, nc * TD_K * 4, s));
-        if (m->cfg.cutoff_mode == TD_CUTOFF_HYBRID)
-            TD_TRY(td_launch_hybrid_ligand_half(w.node_ptr, S->pptr, w.gid, w.lig_node, N_l, S->plan.cptr, S->plan.cnbr, s));
-    } else {
-        TD_TRY(td_launch_knn_static(w.x4a, w.node_ptr, w.gid, set_rows, set_count, max_graph_nodes, snbr_f, skeys_f, s, m->cfg.knn));
-        TD_TRY(td_launch_gate(m->gate, w.x4a, snbr_f, set_count, set_rows, nullptr, ews_f, s));
-    }
-    const TdLayer &L0 = m->layers[0];
-    TD_TRY(td_launch_node_proj(L0.nodeX2h, h0_f, N, nullptr, 0x1f, S->P0, S->q0, s));
-    TD_TRY(key_pass(L0.hk, L0, w.x4a, st, st.ew, st.nbr, S->P0, S->q0, set_rows, nullptr, set_count, gt.alpha, s));
-    TD_TRY_HIP(hipMemcpyAsync(h1_f, h0_f, n * TD_H * 4, hipMemcpyDeviceToDevice, s));
-    TD_TRY(value_pass(L0.hv, L0, w.x4a, st, st.nbr, S->P0, set_rows, nullptr, set_count, h1_f, gt.alpha, nullptr, 0, s));
-    if (S->use_fwd) {      // layer-1 x2h output of the protein-only graph (valid wherever the ligand is two hops away)
-        const TdLayer &L1 = m->layers[1];
-        TD_TRY(td_launch_node_proj(L1.nodeX2h, h1_f, N, nullptr, 0x1f, w.P, w.q, s));
-        TD_TRY(key_pass(L1.hk, L1, w.x4a, st, st.ew, st.nbr, w.P, w.q, set_rows, nullptr, set_count, gt.alpha, s));
-        TD_TRY_HIP(hipMemcpyAsync(h2_f, h1_f, n * TD_H * 4, hipMemcpyDeviceToDevice, s));
-        TD_TRY(value_pass(L1.hv, L1, w.x4a, st, st.nbr, w.P, set_rows, nullptr, set_count, h2_f, gt.alpha, nullptr, 0, s));
-    }
-    if (share) {           // the canonical rows of the scratch tables -> the compact shared tables; the scratch block goes back in stream order
-        TD_TRY(td_launch_compact_rows(skeys_f, canon_rows, Nc, TD_K * 8, S->skeys, s));
-        TD_TRY(td_launch_compact_rows(snbr_f, canon_rows, Nc, TD_K * 4, S->snbr, s));
-        TD_TRY(td_launch_compact_rows(ews_f, canon_rows, Nc, TD_K * 4, S->ews, s));
-        TD_TRY(td_launch_compact_rows(h0_f, canon_rows, Nc, TD_H * 4, S->h0, s));
-        TD_TRY(td_launch_compact_rows(h1_f, canon_rows, Nc, TD_H * 4, S->h1s, s));
-        if (S->use_fwd) TD_TRY(td_launch_compact_rows(h2_f, canon_rows, Nc, TD_H * 4, S->h2s, s));
-        free_async_or_sync(scratch, s);
-        scratch = nullptr;
-    }
-#undef TD_TRY
-#undef TD_TRY_HIP
+    const size_t bytes = session_layout(S, nullptr, share);
+    hipError_t e = td_malloc_async(reinterpret_cast<void **>(&S->block), bytes, s);
+    if (e != hipSuccess) { S->block = nullptr; td_set_error("td_session_create: hipMallocAsync(%zu) failed: %s", bytes, hipGetErrorString(e)); return TD_ENOMEM; }
+    session_layout(S, S->block, share);
+    if ((rc = session_build_static(S, d_protein_pos, d_protein_v, d_protein_ptr, d_ligand_ptr, pg, s)) != TD_OK) return rc;
     *out = S;
+    guard.S = nullptr;
     return TD_OK;
 }
 
@@ -547,15 +534,16 @@ extern "C" int td_session_set_guidance(td_session *S, const float *d_sigma, floa
     if (!d_sigma) return TD_OK;
     hipStream_t s = S->last_stream;
     if (!S->guide_block) {
-        const size_t b4 = align_up((size_t)S->Np * sizeof(float4)), bytes = b4 + align_up((size_t)S->Nl * 12);
+        auto layout = [&](char *base) {
+            Carver c{base};
+            S->guide_prot4 = c.take<float4>((size_t)S->Np);
+            S->guide_shift = c.take<float>((size_t)S->Nl * 3);
+            return c.off;
+        };
+        const size_t bytes = layout(nullptr);
         hipError_t e = td_malloc_async(reinterpret_cast<void **>(&S->guide_block), bytes, s);
-        if (e != hipSuccess) {
-            td_set_error("td_session_set_guidance: hipMallocAsync(%zu) failed: %s", bytes, hipGetErrorString(e));
-            S->guide_block = nullptr;
-            return TD_ENOMEM;
-        }
-        S->guide_prot4 = reinterpret_cast<float4 *>(S->guide_block);
-        S->guide_shift = reinterpret_cast<float *>(S->guide_block + b4);
+        if (e != hipSuccess) { S->guide_block = nullptr; td_set_error("td_session_set_guidance: hipMallocAsync(%zu) failed: %s", bytes, hipGetErrorString(e)); return TD_ENOMEM; }
+        layout(S->guide_block);
     }
     // the centred protein the session holds (its rows of the packed coordinates: written at creation, never by a step) + the radii.
     // Cold path: wait, so that the caller may step on any stream and let go of nothing early.

@@ -113,6 +113,20 @@ size_t pack_vec(Packer &pk, const float *v, size_t n, size_t padded = 0);
 float gaussian_coeff(const float *off);
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
+// One device block cut into 256-byte-aligned buffers, each named once: on the line that sizes it and binds it.  A layout function
+// runs twice over the same lines -- with base == nullptr for the size (`off`; every pointer comes back null), then bound to the block.
+// empty_bytes: what a buffer of no elements still takes (the layout's zero-size rule).
+struct Carver {
+    char *base;
+    size_t empty_bytes = 0, off = 0;
+    template <class T>
+    T *take(size_t count) {
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += align_up(count ? count * sizeof(T) : empty_bytes);
+        return p;
+    }
+};
+
 // ---- workspace, graph tables, the layer sequence (plan.cpp)
 struct Workspace {
     float4 *x4a, *x4b;

@@ -276,3 +276,90 @@ def test_failing_allocations_leak_nothing(model):
         finally:
             lib.td_debug_fail_alloc(0)
     assert lib.td_knn(x.data_ptr(), ptr.data_ptr(), N, B, 32, 0, out.data_ptr(), st) == 0
+
+
+def _begin(model, batch, lpos, lv, steps=2):
+    dev = _dev()
+    b = batch.to(dev)
+    return model.begin_sampling(b.protein_pos, b.protein_atom_feature.float(), b.protein_element_batch, lpos.to(dev), lv.to(dev),
+                                b.ligand_element_batch, num_steps=steps, center_pos_mode='protein')
+
+
+def _failing_creates(begin):
+    """begin() with the n-th stream-ordered allocation of td_session_create failing, n = 1, 2, ... up to the first n at which the
+    session comes up: every failing one reports the allocation.  Returns how many failed."""
+    import gc
+    from targetdiff_amd import capi
+    lib = capi.load_library()
+    for nth in range(1, 17):
+        smp, err = None, None
+        lib.td_debug_fail_alloc(nth)
+        try:
+            smp = begin()
+        except RuntimeError as e:
+            err = str(e)
+        finally:
+            lib.td_debug_fail_alloc(0)
+        if smp is not None:
+            del smp
+            gc.collect()
+            return nth - 1
+        assert 'hipMallocAsync' in err, (nth, err)
+    raise AssertionError('td_session_create still fails with its 16th allocation armed')
+
+
+def _shared_pocket_batch():
+    from targetdiff_amd import workloads
+    pa, pb = workloads.synthetic_pocket(301, 90, 3.0, 9.0), workloads.synthetic_pocket(302, 61, 3.0, 8.0)
+    pos_c = pa.pos.copy()
+    pos_c[17, 1] += np.float32(1e-3)
+    batch = workloads.pack_samples([pa, pb, pa, workloads.Pocket(pos_c, pa.feat, 'pa_one_atom_moved'), pb], 1, [7, 9, 6, 8, 10])
+    lpos, lv = workloads.init_ligand(batch, generator=torch.Generator().manual_seed(31), spread=2.0)
+    return batch, lpos, lv
+
+
+@pytest.mark.parametrize('graph', ['knn32_shared', 'hybrid'])
+def test_every_failing_allocation_of_a_session_is_reported_and_harmless(state_dict, graph):
+    """td_session_create takes several stream-ordered blocks -- with per-pocket sharing the pocket-grouping scratch, the session block and
+    the node-indexed scratch tables; on a general graph the plan's block and the session block.  Whichever of them fails, the call
+    reports hipMallocAsync, and the next session samples the bits of a run before which nothing was armed."""
+    from oracle import weights
+    from targetdiff_amd.models import ScorePosNet3D
+    m = ScorePosNet3D(dict(weights.DEFAULT_MODEL_CONFIG, **(dict(cutoff_mode='hybrid') if graph == 'hybrid' else {})), 27, 13)
+    m.load_state_dict(state_dict, strict=False)
+    m = m.to(_dev()).eval()
+    assert m._native(_dev()).get_option('session_share_pockets') == 1
+    batch, lpos, lv = _shared_pocket_batch()
+    want, _ = _run(m, batch, lpos, lv, 4, 7800)
+    failed = _failing_creates(lambda: _begin(m, batch, lpos, lv))
+    assert failed >= 2, failed
+    got, _ = _run(m, batch, lpos, lv, 4, 7800)
+    for key in ('pos_traj', 'v_traj', 'v0_traj', 'vt_traj'):
+        assert len(got[key]) == 4 and torch.equal(torch.stack(got[key]), torch.stack(want[key])), key
+
+
+def test_failing_session_allocations_strand_no_block(model):
+    """The same at the benchmark's size, where a leak shows: 1h36 x 100 samples (N = 60,708), whose session block holds at least P and Px,
+    2 * N * 4 * 128 * 4 bytes >= 237 MiB.  After every failing td_session_create the device memory in use has grown by less than 128 MiB
+    -- half a block."""
+    import gc
+    from targetdiff_amd import workloads
+    dev = _dev()
+    pocket, sizes = pocket_1h36()
+    batch = workloads.pack_samples([pocket], 100, [int(s) for s in sizes])
+    lpos, lv = workloads.init_ligand(batch, generator=torch.Generator().manual_seed(2021), spread=2.0)
+    assert batch.protein_pos.shape[0] + lpos.shape[0] == 60708
+
+    def used():
+        gc.collect()
+        torch.cuda.synchronize()
+        free, total = torch.cuda.mem_get_info(dev)
+        return total - free
+    smp = _begin(model, batch, lpos, lv)          # one good create / destroy first: the pool's steady state
+    assert smp.session is not None
+    del smp
+    base = used()
+    failed = _failing_creates(lambda: _begin(model, batch, lpos, lv))
+    assert failed >= 2, failed
+    grown = used() - base
+    assert grown < 128 * 2 ** 20, f'{grown / 2 ** 20:.0f} MiB stranded by {failed} failing td_session_create calls'

@@ -39,6 +39,17 @@ def test_weight_blob_layout_matches_library():
     assert total - dead == blob.size + per_layer_offsets
 
 
+def test_workspace_block_sizes_are_pinned():
+    """td_workspace_bytes / td_egnn_workspace_bytes: the sizes the block layout had before every layout moved onto the shared
+    carver (tdapi::Carver) -- the order of buffers, the 256-byte alignment and the zero-size rule must not have moved with it."""
+    lib = capi.load_library()
+    want = {(0, 0, 0): 9472, (1, 1, 1): 9472, (1000, 4, 100): 7973120, (60708, 100, 2400): 483974912}
+    for (N, B, Nl), size in want.items():
+        assert lib.td_workspace_bytes(None, N, B, Nl) == size, (N, B, Nl)
+    for N, size in {0: 3584, 1: 3584, 1000: 2724352}.items():
+        assert lib.td_egnn_workspace_bytes(N) == size, N
+
+
 def test_unsupported_config_is_rejected_not_emulated():
     lib = capi.load_library()
     cfg = capi.TdConfig(hidden_dim=256, n_heads=16, knn=32, num_layers=9, num_r_gaussian=20, edge_feat_dim=4,

@@ -141,7 +141,9 @@ __global__ void prop_reduce_kernel(const float *__restrict__ part, int chunks, i
 }
 
 // Per-edge backward of one encoder layer; one wave per destination row i, its k edges in blocks of 16 (edge slot = lane column), as
-// prop_edge_kernel.  Edge e = i * k + slot.  Padded slots write zeros (a, dz2, dz1, rbf, q) and add nothing.
+// prop_edge_kernel.  Edge e = i * k + slot.  A padded slot (nbr = -1) of a live row writes zeros to dz2, dz1, rbf and q and adds
+// nothing to S or sum q m; what it writes to a is ReLU(z1) evaluated with j = i, finite and never used: a enters only dW2 = dz2^T a,
+// and dz2 is zero there.  Slots 16 * nblk > slot >= k of the last block and waves past the last row write nothing.
 __global__ __launch_bounds__(256) void prop_edge_bwd_kernel(TdPropLayer L, const float *__restrict__ W2Tf, const float *__restrict__ x,
                                                             const int32_t *__restrict__ nbr, int k, const float *__restrict__ P,
                                                             const float *__restrict__ dmi, int64_t N, float coeff,

@@ -91,10 +91,10 @@ def is_param(key):
     return not key.endswith('offset')
 
 
-def restate_loss(sd, cfg, inp, out_kind, y, enc, up=None):
+def restate_loss(sd, cfg, inp, out_kind, y, enc, up=None, trace=None):
     """Loss of the float64 restatement: MSE(out[kind], y), or sum(out * up) when `up` is given (no output_kind)."""
     r = P.restate(sd, cfg, inp, output_kind=None if up is not None else out_kind, enc_ligand=enc.get('ligand'),
-                  enc_node=enc.get('node'), enc_graph=enc.get('graph'))
+                  enc_node=enc.get('node'), enc_graph=enc.get('graph'), trace=trace)
     out = r['out']
     if up is not None:
         return (out * torch.as_tensor(up, dtype=torch.float64)).sum(), out

@@ -136,8 +136,10 @@ def composed_order(batch_protein, batch_ligand):
     return np.argsort(np.concatenate([batch_protein, batch_ligand]), kind='stable')
 
 
-def restate(sd, cfg, inp, output_kind=None, enc_ligand=None, enc_node=None, enc_graph=None):
-    """PropPredNet(Enc).forward in float64.  Returns dict(out, h_layers [L, N, 256], final_h, nbr, order)."""
+def restate(sd, cfg, inp, output_kind=None, enc_ligand=None, enc_node=None, enc_graph=None, trace=None):
+    """PropPredNet(Enc).forward in float64.  Returns dict(out, h_layers [L, N, 256], final_h, nbr, order, rbf [E, 64], out_pre [B, 256]
+    = the pre-activations of out_block.0).  A list given as `trace` receives, for every ReLU, (key of the Linear before it, that
+    Linear's input, its output = the ReLU's pre-activation, the ReLU's output)."""
     d = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
     W = {k: v.double() for k, v in sd.items()}
     lin = lambda x, p: x @ W[p + '.weight'].T + W[p + '.bias']
@@ -159,27 +161,34 @@ def restate(sd, cfg, inp, output_kind=None, enc_ligand=None, enc_node=None, enc_
     offset = W['encoder.distance_expansion.offset']
     coeff = -0.5 / (offset[1] - offset[0]).item() ** 2
     rbf = torch.exp(coeff * (length.view(-1, 1) - offset.view(1, -1)) ** 2)
-    relu = torch.relu
+    def relu_of(x, p):
+        z = lin(x, p)
+        a = torch.relu(z)
+        if trace is not None:
+            trace.append((p, x, z, a))
+        return a
     layers = []
     for l in range(enc['num_layers']):
         p = f'encoder.net.{l}.'
-        m = relu(lin(relu(lin(torch.cat([rbf, h[dst], h[src]], -1), p + 'edge_mlp.net.0')), p + 'edge_mlp.net.2'))
+        m = relu_of(relu_of(torch.cat([rbf, h[dst], h[src]], -1), p + 'edge_mlp.net.0'), p + 'edge_mlp.net.2')
         e = torch.sigmoid(lin(m, p + 'edge_inf.0'))
         mi = torch.zeros_like(h).index_add_(0, torch.from_numpy(dst), m * e)
-        h = h + lin(relu(lin(torch.cat([mi, h], -1), p + 'node_mlp.net.0')), p + 'node_mlp.net.2')
+        h = h + lin(relu_of(torch.cat([mi, h], -1), p + 'node_mlp.net.0'), p + 'node_mlp.net.2')
         layers.append(h)
     if enc_node is not None:
-        h = lin(relu(lin(torch.cat([h, d(enc_node)], -1), 'enc_node_layer.0')), 'enc_node_layer.2')
+        h = lin(relu_of(torch.cat([h, d(enc_node)], -1), 'enc_node_layer.0'), 'enc_node_layer.2')
     B = int(batch.max()) + 1
     pre = torch.zeros(B, h.shape[1], dtype=torch.float64).index_add_(0, torch.from_numpy(batch), h)
     if enc_graph is not None:
         pre = torch.cat([pre, d(enc_graph)], -1)
-    y = lin(pre, 'out_block.0')
-    y = torch.nn.functional.softplus(y) - np.log(2.0)
+    out_pre = lin(pre, 'out_block.0')
+    # ShiftedSoftplus (models/common.py:156-162): its shift is torch.log(torch.tensor(2.0)).item(), log 2 rounded to fp32, 1.9e-9 above
+    # log 2 -- in the float64 run as well
+    y = torch.nn.functional.softplus(out_pre) - float(np.float32(np.log(2.0)))
     y = lin(y, 'out_block.2')
     if output_kind is not None:
         y = y[torch.arange(B), torch.as_tensor(output_kind) - 1].view(-1, 1)
-    return dict(out=y, h_layers=torch.stack(layers), final_h=h, nbr=nbr, order=order)
+    return dict(out=y, h_layers=torch.stack(layers), final_h=h, nbr=nbr, order=order, rbf=rbf, out_pre=out_pre)
 
 
 def rel_err(a, b):

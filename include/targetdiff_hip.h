@@ -456,6 +456,36 @@ int td_geometry_report(const float *d_pos, const int64_t *d_v, const int32_t *d_
                        int32_t *d_n_degenerate, int32_t *d_n_crowded, int32_t *d_n_clashes, int32_t *d_atom_clash, int64_t *d_hist,
                        void *stream);
 
+/* ---- pocket contacts of ligand frames ("Pocket contacts"): one pocket and one pack per call; every molecule of
+ *      the pack is in that pocket.  The pack, the class table and d_include as td_geometry_report takes them.  d_protein_pos [N_p,3]
+ *      fp32 in the frame of d_pos; d_protein_elem [N_p] int32, an index over H C N O S Se, or -1; d_protein_kind [N_p] int32 in
+ *      [0, n_kinds) or -1, 1 <= n_kinds <= 64.  A protein atom whose element or kind is outside its range takes part nowhere.
+ *      Distance: the distance of the bond rule, bit for bit: fp32 inputs widened to float64, d = sqrt((dx dx + dy dy) + dz dz) with
+ *      every product and sum rounded on its own and an IEEE square root.  Pair: a ligand atom with a class inside [0, K) and a protein
+ *      atom that takes part.  Contact: a pair with d < contact_cutoff (a finite double > 0), strictly.  Clash: a pair with d <
+ *      clash_threshold[e_l * 6 + e_p], strictly; clash_threshold is a HOST float64 [8 * 6] table, ligand element over H C N O F P S Cl
+ *      by protein element; NULL: no clash pass (d_n_clashes, d_n_clash_atoms and d_atom_clash are then not written and may be NULL).
+ *      d_ref_bits [W] uint64, W = ceil(N_p / 64), may be NULL: bit j & 63 of word j >> 6 marks protein atom j.
+ *      Output per (frame, molecule), [S,B]: d_n_contacts int32, the contact pairs; d_n_contact_atoms, the ligand atoms with at least
+ *      one contact; d_n_pocket_atoms, the protein atoms with at least one contact; d_n_clashes, the clash pairs; d_n_clash_atoms, the
+ *      ligand atoms in at least one clash; d_min_dist float64, the smallest d over the molecule's pairs, +inf without pairs;
+ *      d_n_ref_common, the contacted protein atoms that d_ref_bits marks (written only with d_ref_bits).  May be NULL: d_atom_contacts
+ *      and d_atom_clash [S,N_l] int32, the pairs each ligand atom takes part in; d_bits [S,B,W] uint64, the contacted protein atoms
+ *      in the layout of d_ref_bits.  Over the molecules whose d_include byte is non-zero (NULL: all), zeroed by the call:
+ *      d_kind_hist [S,8,n_kinds] int64, the contact pairs by ligand element and protein kind; d_pocket_freq [S,N_p] int32, the number
+ *      of such molecules of the frame that contact protein atom j.  A molecule of more than 512 atoms, or one whose offsets leave
+ *      [0, N_l], gets -1 in the integer per-molecule outputs, +inf in d_min_dist and zero words in d_bits, its per-atom outputs are not
+ *      written, and it contributes nothing else (a binding refuses it).  512 N_p and S N_p must fit 31 bits.  S, B and N_p may be 0.
+ *      All outputs but d_min_dist are integers and d_min_dist is a minimum: nothing depends on the grid or on the order of arrival.
+ *      (An addition: TD_ABI_VERSION stays 5.) */
+int td_pocket_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                     const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const float *d_protein_pos,
+                     const int32_t *d_protein_elem, const int32_t *d_protein_kind, int64_t N_p, int32_t n_kinds, double contact_cutoff,
+                     const double *clash_threshold, const uint64_t *d_ref_bits, int32_t *d_n_contacts, int32_t *d_n_contact_atoms,
+                     int32_t *d_n_pocket_atoms, int32_t *d_n_clashes, int32_t *d_n_clash_atoms, double *d_min_dist,
+                     int32_t *d_n_ref_common, int32_t *d_atom_contacts, int32_t *d_atom_clash, uint64_t *d_bits, int64_t *d_kind_hist,
+                     int32_t *d_pocket_freq, void *stream);
+
 /* ---- standalone EGNN refine net (replaces: models/egnn.py EGNN / EnBaseLayer as get_refine_net('egnn', config) builds
  *      it, models/molopt_score_model.py:34-42: num_r_gaussian = 1, kNN rebuilt per layer, SiLU, no LayerNorm, hidden 128,
  *      4 edge types, k = 32).  `host_weights`: per layer, in this order and as PyTorch stores them: edge_mlp.net.0.{weight

@@ -101,6 +101,8 @@ SIGNATURES = {
     'td_fingerprint_similarity': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P, _P, _P, _P]),
     'td_geometry_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, POINTER(ctypes.c_uint8), _P, c_int32, _P, c_int64,
                                      _P, POINTER(ctypes.c_double), _P, _P, _P, _P, _P, _P, _P, _P]),
+    'td_pocket_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, _P, _P, c_int64, c_int32,
+                                   ctypes.c_double, POINTER(ctypes.c_double), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_center_pos': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int32, c_int32, _P]),
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
@@ -1166,6 +1168,80 @@ def geometry_report(pos, v, ligand_ptr, class_z, class_aromatic=None, profiles=(
                                       _ptr(bond_ring), None if thr is None else thr.ctypes.data_as(POINTER(ctypes.c_double)),
                                       _ptr(out['n_angles']), _ptr(out['n_torsions']), _ptr(out['n_degenerate']), _ptr(out['n_crowded']),
                                       _ptr(out['n_clashes']), _ptr(out['atom_clash']), _ptr(out['hist']), _stream(dev)), 'td_geometry_report')
+    return out
+
+
+POCKET_MAX_KINDS, POCKET_ELEMENTS = 64, 6                                   # TD_POCKET_* (csrc/td_internal.h)
+
+
+def _pocket_inputs(pos, protein_pos, protein_elem, protein_kind, n_kinds, contact_cutoff, clash_threshold, ref_bits, check=True):
+    """The pocket's side of a pocket_report call: shapes, dtypes and devices, the number of kinds, the cutoff, the table and the
+    reference words; with ``check`` the elements and kinds are looked at on the host (one synchronisation).  Returns (N_p, W, the
+    table as float64 numpy [48] or None)."""
+    if protein_pos.dim() != 2 or protein_pos.shape[1] != 3:
+        raise ValueError(f'protein_pos must be [N_p, 3] (got {tuple(protein_pos.shape)})')
+    Np = protein_pos.shape[0]
+    W = (Np + 63) // 64
+    if tuple(protein_elem.shape) != (Np,) or tuple(protein_kind.shape) != (Np,):
+        raise ValueError(f'protein_elem / protein_kind must be [{Np}] (got {tuple(protein_elem.shape)}, {tuple(protein_kind.shape)})')
+    if protein_pos.dtype != torch.float32 or protein_elem.dtype != torch.int32 or protein_kind.dtype != torch.int32:
+        raise ValueError(f'protein_pos / protein_elem / protein_kind must be fp32 / int32 / int32 (got {protein_pos.dtype}, '
+                         f'{protein_elem.dtype}, {protein_kind.dtype})')
+    if any(t.device != pos.device for t in (protein_pos, protein_elem, protein_kind)) or (ref_bits is not None and ref_bits.device != pos.device):
+        raise ValueError(f'the pocket must live on the device of the pack ({pos.device})')
+    if not 1 <= int(n_kinds) <= POCKET_MAX_KINDS:
+        raise ValueError(f'n_kinds is 1 .. {POCKET_MAX_KINDS} (got {n_kinds})')
+    if not (np.isfinite(float(contact_cutoff)) and float(contact_cutoff) > 0.0):
+        raise ValueError(f'the contact cutoff must be finite and > 0 (got {contact_cutoff})')
+    thr = None
+    if clash_threshold is not None:
+        thr = np.asarray(clash_threshold, dtype=np.float64)
+        if thr.shape not in ((8, POCKET_ELEMENTS), (8 * POCKET_ELEMENTS,)) or not np.isfinite(thr).all():
+            raise ValueError(f'clash_threshold is a finite [8, {POCKET_ELEMENTS}] table: H C N O F P S Cl by H C N O S Se')
+        thr = np.ascontiguousarray(thr.reshape(-1))
+    if ref_bits is not None and (tuple(ref_bits.shape) != (W,) or ref_bits.dtype != torch.int64):
+        raise ValueError(f'ref_bits must be [{W}] int64 words, as pocket_report returns bits (got {tuple(ref_bits.shape)} {ref_bits.dtype})')
+    if check and Np > 0:
+        if int(protein_elem.min()) < -1 or int(protein_elem.max()) >= POCKET_ELEMENTS:
+            raise ValueError(f'protein_elem must be in [-1, {POCKET_ELEMENTS}): an index over H C N O S Se, or -1')
+        if int(protein_kind.min()) < -1 or int(protein_kind.max()) >= int(n_kinds):
+            raise ValueError(f'protein_kind must be in [-1, {int(n_kinds)})')
+    return Np, W, thr
+
+
+def pocket_report(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, protein_kind, n_kinds, contact_cutoff, clash_threshold=None,
+                  include=None, ref_bits=None, return_atoms=True, return_bits=True, check=True):
+    """Contacts and clashes of S frames of B molecules with one pocket (td_pocket_report, include/targetdiff_hip.h); the pack, the
+    class table and ``include`` as bond_graph's.  ``protein_pos`` [N_p, 3] fp32 in the frame of ``pos``, ``protein_elem`` [N_p] int32
+    over H C N O S Se or -1, ``protein_kind`` [N_p] int32 in [0, n_kinds) or -1 (an atom with a -1 takes part nowhere).  A contact is
+    a pair with d < ``contact_cutoff``, a clash one with d < ``clash_threshold`` [8, 6] (ligand element over H C N O F P S Cl by protein
+    element; None: no clash pass), d the bond rule's float64 distance.  ``ref_bits`` [W] int64, W = ceil(N_p / 64): bit j & 63 of
+    word j >> 6 marks protein atom j.  Returns a dict of device tensors: n_contacts, n_contact_atoms, n_pocket_atoms [S, B] int32,
+    n_clashes, n_clash_atoms [S, B] int32 (None without a table), min_dist [S, B] float64, n_ref_common [S, B] int32 (None without
+    ``ref_bits``), atom_contacts / atom_clash [S, N_l] int32 (None without ``return_atoms`` / a table), bits [S, B, W] int64 (None
+    without ``return_bits``), and over the included molecules kind_hist [S, 8, n_kinds] int64 and pocket_freq [S, N_p] int32."""
+    S, Nl, B, cz, _, _ = _bond_inputs(pos, v, ligand_ptr, class_z, None, include, (), check)
+    Np, W, thr = _pocket_inputs(pos, protein_pos, protein_elem, protein_kind, n_kinds, contact_cutoff, clash_threshold, ref_bits, check)
+    lib = load_library()
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
+    dev = pos.device
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    z32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)    # an oversize molecule's atoms are not written
+    out = dict(n_contacts=i32(S, B), n_contact_atoms=i32(S, B), n_pocket_atoms=i32(S, B),
+               n_clashes=i32(S, B) if thr is not None else None, n_clash_atoms=i32(S, B) if thr is not None else None,
+               min_dist=torch.empty(S, B, dtype=torch.float64, device=dev),
+               n_ref_common=(z32 if W == 0 else i32)(S, B) if ref_bits is not None else None,      # no words: nothing is in common
+               atom_contacts=z32(S, Nl) if return_atoms else None, atom_clash=z32(S, Nl) if return_atoms and thr is not None else None,
+               bits=torch.empty(S, B, W, dtype=torch.int64, device=dev) if return_bits else None,
+               kind_hist=torch.empty(S, 8, int(n_kinds), dtype=torch.int64, device=dev), pocket_freq=i32(S, Np))
+    with _on(dev):
+        _check(lib.td_pocket_report(*pack, _include_arg(include), _ptr(protein_pos, torch.float32, 'protein_pos'),
+                                    _ptr(protein_elem, torch.int32, 'protein_elem'), _ptr(protein_kind, torch.int32, 'protein_kind'), Np,
+                                    int(n_kinds), float(contact_cutoff), None if thr is None else thr.ctypes.data_as(POINTER(ctypes.c_double)),
+                                    _ptr(ref_bits, torch.int64, 'ref_bits'), _ptr(out['n_contacts']), _ptr(out['n_contact_atoms']),
+                                    _ptr(out['n_pocket_atoms']), _ptr(out['n_clashes']), _ptr(out['n_clash_atoms']), _ptr(out['min_dist']),
+                                    _ptr(out['n_ref_common']), _ptr(out['atom_contacts']), _ptr(out['atom_clash']), _ptr(out['bits']),
+                                    _ptr(out['kind_hist']), _ptr(out['pocket_freq']), _stream(dev)), 'td_pocket_report')
     return out
 
 

@@ -1,6 +1,8 @@
-// C ABI of libtargetdiff_hip.so: the bond graph of ligand frames, its rings, its fingerprints and its local geometry (td_bond_graph,
-// td_bond_list, td_ring_report, td_fingerprint, td_fingerprint_similarity, td_geometry_report).  See include/targetdiff_hip.h for the
-// contract.
+// C ABI of libtargetdiff_hip.so: the bond graph of ligand frames, its rings, its fingerprints, its local geometry and the contacts with
+// the pocket (td_bond_graph, td_bond_list, td_ring_report, td_fingerprint, td_fingerprint_similarity, td_geometry_report,
+// td_pocket_report).  See include/targetdiff_hip.h for the contract.
+#include <cmath>
+
 #include "td_device.h"
 #include "td_internal.h"
 
@@ -213,4 +215,49 @@ extern "C" int td_geometry_report(const float *d_pos, const int64_t *d_v, const 
     g.n_clashes = d_n_clashes; g.atom_clash = d_atom_clash;
     g.hist = reinterpret_cast<unsigned long long *>(d_hist);
     return td_launch_geometry_report(g, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int td_pocket_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                                const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const float *d_protein_pos,
+                                const int32_t *d_protein_elem, const int32_t *d_protein_kind, int64_t N_p, int32_t n_kinds,
+                                double contact_cutoff, const double *clash_threshold, const uint64_t *d_ref_bits, int32_t *d_n_contacts,
+                                int32_t *d_n_contact_atoms, int32_t *d_n_pocket_atoms, int32_t *d_n_clashes, int32_t *d_n_clash_atoms,
+                                double *d_min_dist, int32_t *d_n_ref_common, int32_t *d_atom_contacts, int32_t *d_atom_clash,
+                                uint64_t *d_bits, int64_t *d_kind_hist, int32_t *d_pocket_freq, void *stream) {
+    const char *who = "td_pocket_report";
+    TdPocketArgs g;
+    if (const int rc = bond_pack(who, g.b, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, nullptr)) return rc;
+    if (N_p < 0 || N_p > 0x7fffffff / TD_BOND_MAX_ATOMS || S * N_p > 0x7fffffff) {      // a molecule's pairs are counted in an int32
+        td_set_error("%s: bad argument (N_p = %lld; 512 N_p and S * N_p must fit 31 bits)", who, (long long)N_p);
+        return TD_EINVAL;
+    }
+    if (n_kinds < 1 || n_kinds > TD_POCKET_MAX_KINDS) {
+        td_set_error("%s: 1 .. %d kinds of protein atoms (got %d)", who, TD_POCKET_MAX_KINDS, (int)n_kinds);
+        return TD_EINVAL;
+    }
+    if (!std::isfinite(contact_cutoff) || !(contact_cutoff > 0.0)) {
+        td_set_error("%s: the contact cutoff must be finite and > 0", who);
+        return TD_EINVAL;
+    }
+    if (N_p > 0 && (!d_protein_pos || !d_protein_elem || !d_protein_kind)) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
+    if ((S > 0 && (!d_kind_hist || (N_p > 0 && !d_pocket_freq))) ||
+        (S > 0 && B > 0 && (!d_n_contacts || !d_n_contact_atoms || !d_n_pocket_atoms || !d_min_dist ||
+                            (clash_threshold && (!d_n_clashes || !d_n_clash_atoms)) || (d_ref_bits && !d_n_ref_common)))) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    g.b.include = d_include;
+    g.ppos = d_protein_pos; g.pelem = d_protein_elem; g.pkind = d_protein_kind;
+    g.ref_bits = reinterpret_cast<const unsigned long long *>(d_ref_bits);
+    g.Np = (int)N_p; g.W = (int)((N_p + 63) / 64); g.n_kinds = n_kinds; g.cutoff = contact_cutoff;
+    if (clash_threshold) {
+        g.clash = true;
+        for (int k = 0; k < 8 * TD_POCKET_ELEMENTS; ++k) g.clash_thr[k] = clash_threshold[k];
+    }
+    g.n_contacts = d_n_contacts; g.n_contact_atoms = d_n_contact_atoms; g.n_pocket_atoms = d_n_pocket_atoms;
+    g.n_clashes = d_n_clashes; g.n_clash_atoms = d_n_clash_atoms; g.min_dist = d_min_dist; g.n_ref_common = d_n_ref_common;
+    g.atom_contacts = d_atom_contacts; g.atom_clash = d_atom_clash;
+    g.bits = reinterpret_cast<unsigned long long *>(d_bits); g.kind_hist = reinterpret_cast<unsigned long long *>(d_kind_hist);
+    g.pocket_freq = d_pocket_freq;
+    return td_launch_pocket_report(g, static_cast<hipStream_t>(stream));
 }

@@ -22,14 +22,21 @@ __device__ __forceinline__ void td_bond_thresholds(double (*thr)[64], int tid, i
     for (int k = tid; k < 3 * 64; k += threads) thr[k >> 6][k & 63] = (double)(TD_BOND_PM[k >> 6][k & 63] + TD_BOND_MARGIN[k >> 6]);
 }
 
+// The squared distance of the rule: atom i at float64-widened (xi, yi, zi), atom j at fp32 (xj, yj, zj), (dx dx + dy dy) + dz dz in
+// float64 with every product and sum rounded on its own.  The rule's distance is the IEEE sqrt of it; pocket.hip takes that root
+// only of the pairs that can fall below a limit, and of a minimum once (the root is monotone).
+__device__ __forceinline__ double td_pair_dist2(double xi, double yi, double zi, float xj, float yj, float zj) {
+    const double dx = xi - (double)xj, dy = yi - (double)yj, dz = zi - (double)zj;
+    return td_add_rn64(td_add_rn64(td_mul_rn64(dx, dx), td_mul_rn64(dy, dy)), td_mul_rn64(dz, dz));
+}
+
 // Order 0 / 1 / 2 / 3 of the pair (atom i at float64-widened (xi, yi, zi), atom j at fp32 (xj, yj, zj)) whose element pair is
 // pr = e_i * 8 + e_j, and its distance d = sqrt((dx dx + dy dy) + dz dz) in float64 with every product and sum rounded on its own
 // (numpy's order), IEEE sqrt, compared as D = 100 d: an order flips exactly where the reference's flips.  (i, j) and (j, i) give the
 // same bits: the differences only change sign.
 __device__ __forceinline__ int td_bond_order(double xi, double yi, double zi, float xj, float yj, float zj, int pr,
                                              const double (*thr)[64], double &d) {
-    const double dx = xi - (double)xj, dy = yi - (double)yj, dz = zi - (double)zj;
-    d = sqrt(td_add_rn64(td_add_rn64(td_mul_rn64(dx, dx), td_mul_rn64(dy, dy)), td_mul_rn64(dz, dz)));
+    d = sqrt(td_pair_dist2(xi, yi, zi, xj, yj, zj));
     const double D = td_mul_rn64(100.0, d);
     if (D < thr[0][pr]) return D < thr[1][pr] ? (D < thr[2][pr] ? 3 : 2) : 1;
     return 0;

@@ -508,6 +508,31 @@ struct TdGeomArgs {
     unsigned long long *hist = nullptr;      // [S,P,TD_GEOM_BINS]
 };
 int td_launch_geometry_report(const TdGeomArgs &a, hipStream_t s);
+// pocket.hip (td_pocket_report, DESIGN.md section 3, "Pocket contacts"): the pack and the include bytes in `b` (none of b's outputs is
+// used); one pocket of Np atoms for every molecule.  pelem: index over H C N O S Se, pkind in [0, n_kinds); an atom with either outside
+// its range takes part nowhere.  clash_thr[e_l * 6 + e_p], e_l over H C N O F P S Cl.  reject2: a pair whose squared distance is not
+// below it is below neither limit (the launcher forms it; +inf: no pair is rejected).  W = ceil(Np / 64) words of contact bits.
+// The launcher zeroes kind_hist and pocket_freq on the stream.
+constexpr int TD_POCKET_MAX_KINDS = 64, TD_POCKET_ELEMENTS = 6, TD_POCKET_THREADS = 256;
+struct TdPocketArgs {
+    TdBondArgs b;
+    const float *ppos = nullptr;             // [Np,3]
+    const int32_t *pelem = nullptr, *pkind = nullptr;                            // [Np]
+    const unsigned long long *ref_bits = nullptr;                                // [W] or null
+    int Np = 0, W = 0, n_kinds = 0;
+    double cutoff = 0.0, reject2 = 0.0;
+    bool clash = false;                      // clash_thr holds the table
+    double clash_thr[8 * TD_POCKET_ELEMENTS] = {};
+    int32_t *n_contacts = nullptr, *n_contact_atoms = nullptr, *n_pocket_atoms = nullptr;   // [S,B]
+    int32_t *n_clashes = nullptr, *n_clash_atoms = nullptr;                      // [S,B], written when clash
+    double *min_dist = nullptr;              // [S,B]
+    int32_t *n_ref_common = nullptr;         // [S,B], written when ref_bits
+    int32_t *atom_contacts = nullptr, *atom_clash = nullptr;                     // [S,N_l] or null
+    unsigned long long *bits = nullptr;      // [S,B,W] or null
+    unsigned long long *kind_hist = nullptr; // [S,8,n_kinds]
+    int32_t *pocket_freq = nullptr;          // [S,Np]
+};
+int td_launch_pocket_report(const TdPocketArgs &a, hipStream_t s);
 // egnn.hip / node.hip
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s);

@@ -49,6 +49,14 @@ of their van der Waals radii, this project's own convention (not PoseBusters' bo
     geo = quality.sample_geometry(result, eval_step='all', reference=quality.geometry_reference(molfile.read_sdf('ligands.sdf')))
     geo.summary()   # {'clash_free': ..., 'mean_clashes': ..., 'CCC': {'count': ..., 'mean': ..., 'js': ...}, ...}
 
+And where the poses sit in their pocket (``td_pocket_report``, csrc/pocket.hip; DESIGN.md section 3, "Pocket contacts"): contacts (a
+ligand atom and a protein atom closer than 4 A), clashes with the protein (closer than the sum of the van der Waals radii minus 0.5 A)
+and, with the pocket's known ligand, how many of its contacts a sample recovers -- conventions of this project, not a pose checker's:
+
+    poc = quality.sample_pocket(result, eval_step='all', reference_ligand=(ref_pos, ref_v))    # result['data'] is the pocket
+    poc.summary()   # {'pocket_clash_free': ..., 'mean_contacts': ..., 'buried_share': ..., 'no_contact': ..., 'ref_recovery_mean': ...}
+    poc.contact_profile(), poc.contact_frequency()    # contacts by residue kind ('ASP.sc', 'GLY.bb', ...), and per protein atom
+
 Several reports of one result share its pack, its host checks and its bond graph (``SamplePack``; the ``sample_*`` functions build one each):
 
     pack = quality.SamplePack(result, eval_step='all')
@@ -435,6 +443,26 @@ class SamplePack:
         tot = lambda k: np.where(inc, r[k].cpu().numpy().astype(np.int64), 0).sum(1)
         return GeometryReport(inc.sum(1), (inc & (clashes == 0)).sum(1), np.where(inc, clashes, 0).sum(1), tot('n_crowded'), tot('n_degenerate'),
                               tot('n_angles'), tot('n_torsions'), r['hist'].cpu().numpy(), prof, len(self.sizes), reference)
+
+    def pocket(self, data, include='all', reference_ligand=None, contact_cutoff=4.0, clash_tolerance=0.5, kinds='residue'):
+        """``sample_pocket`` of the pack; ``data``: the pocket every molecule of the pack is in (``_pocket_arrays``)"""
+        ppos, elem, kind, names = _pocket_arrays(data, self.pos.device, kinds)
+        mask = self.mask(include)
+        pocket = (ppos, elem, kind, len(names), contact_cutoff)
+        ref_bits = ref_size = None
+        if reference_ligand is not None:
+            rpos, rv = reference_ligand
+            rpos, rv, rptr = _pack(rpos, rv, None, torch.tensor([0, len(rv)], dtype=torch.int32), self.pos.device)
+            if rpos.shape[0] != 1:
+                raise ValueError('the reference ligand is one molecule: pos [n, 3], v [n]')
+            q = capi.pocket_report(rpos, rv, rptr, self.class_z, *pocket, None, None, None, False, True)
+            ref_bits, ref_size = q['bits'][0, 0].contiguous(), int(q['n_pocket_atoms'][0, 0])
+        r = capi.pocket_report(*self._args, *pocket, pocket_clash_thresholds(clash_tolerance), mask, ref_bits, False, False,
+                               check=self._check())
+        keys = ('n_contacts', 'n_contact_atoms', 'n_pocket_atoms', 'n_clashes', 'min_dist', 'n_ref_common', 'kind_hist', 'pocket_freq')
+        raw = {k: r[k].cpu().numpy() for k in keys if r[k] is not None}
+        return PocketReport.from_outputs(raw, self._included(mask), self.sizes, names, [n.endswith('.bb') for n in names] if kinds == 'residue'
+                                         else None, ref_size)
 
 
 def sample_quality(result, eval_step=-1, include='all', atom_enc_mode='add_aromatic', reference=None, profiles=None, device='cuda'):
@@ -1013,3 +1041,266 @@ def geometry_reference(molecules, profiles=None, atom_enc_mode='add_aromatic', d
     r = _geometry_call(pos, v, ptr, class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode), prof, None, None, False)
     hist = r['hist'][0].cpu().numpy()
     return {geometry_profile_name(p): hist[k, :len(p[4]) + 1].copy() for k, p in enumerate(prof)}
+
+
+# ---- pocket contacts (``td_pocket_report``, csrc/pocket.hip; DESIGN.md section 3, "Pocket contacts")
+# A contact is a ligand atom and a protein atom closer than 4 A; a protein clash is such a pair closer than the sum of their van der
+# Waals radii minus 0.5 A.  Both numbers are conventions of this project, stated here and not measured: the cutoff is the usual one of
+# contact fingerprints, the tolerance keeps hydrogen-bonded heavy atoms (N-O near 2.8 A against 3.07 A of radii) from counting as clashes.
+DEFAULT_CONTACT_CUTOFF = 4.0
+DEFAULT_CLASH_TOLERANCE = 0.5
+POCKET_RADII = {**GEOMETRY_RADII, 34: 1.90}           # geometry's radii and Se
+
+
+def pocket_kinds(feat, by='residue', hydrogens=False):
+    """``(elem [n] int32, kind [n] int32, names)`` of the protein feature ``[n, 27]`` (workloads.featurize_protein: 6 element bits over
+    H C N O S Se, 20 residue bits, the backbone bit).  ``elem``: the index of the element bit, -1 for a row without one.  ``kind``: by
+    ``'residue'`` 2 * residue + backbone, 40 kinds named ``ALA.sc``, ``ALA.bb``, ... (-1 for a row without a residue bit); by
+    ``'element'`` the element index, 6 kinds.  A protein hydrogen gets kind -1 unless ``hydrogens``: pockets are usually stored
+    without hydrogens, and one stored with them would otherwise count every contact twice over.  An atom of kind -1 or element -1
+    takes part in no contact and no clash."""
+    from . import workloads
+    f = feat.detach().cpu().numpy() if torch.is_tensor(feat) else np.asarray(feat)
+    ne, na = len(workloads.PROTEIN_ELEMENTS), len(workloads.AA_NAMES)
+    if f.ndim != 2 or f.shape[1] != ne + na + 1:
+        raise ValueError(f'the protein feature is [n, {ne + na + 1}] (got {tuple(f.shape)})')
+    f = f != 0
+    elem = np.where(f[:, :ne].any(1), f[:, :ne].argmax(1), -1).astype(np.int32)
+    if by == 'residue':
+        kind = np.where(f[:, ne:ne + na].any(1), 2 * f[:, ne:ne + na].argmax(1) + f[:, ne + na], -1).astype(np.int32)
+        names = tuple(f'{aa}.{part}' for aa in workloads.AA_NAMES for part in ('sc', 'bb'))
+    elif by == 'element':
+        kind, names = elem.copy(), ('H', 'C', 'N', 'O', 'S', 'Se')
+    else:
+        raise ValueError(f"kinds are by 'residue' or by 'element' (got {by!r})")
+    if not hydrogens:
+        kind[elem == 0] = -1
+    return elem, kind, names
+
+
+def pocket_clash_thresholds(tolerance=DEFAULT_CLASH_TOLERANCE, radii=None):
+    """[8, 6] float64, ligand element over H C N O F P S Cl by protein element over H C N O S Se: ``r_l + r_p - tolerance`` with
+    geometry's van der Waals radii and Se 1.90 A; ``radii``: {atomic number: radius in Angstrom} to change some.  The tolerance is a
+    convention (``DEFAULT_CLASH_TOLERANCE``), not a measurement."""
+    from . import workloads
+    r = dict(POCKET_RADII)
+    for z, x in (radii or {}).items():
+        if int(z) not in r or not float(x) >= 0.0:
+            raise ValueError(f'radii are non-negative and keyed by the atomic numbers {tuple(sorted(r))} (got {z}: {x})')
+        r[int(z)] = float(x)
+    if not np.isfinite(float(tolerance)):
+        raise ValueError(f'the clash tolerance is finite (got {tolerance})')
+    rl = np.asarray([r[z] for z in ELEMENTS], dtype=np.float64)
+    rp = np.asarray([r[z] for z in workloads.PROTEIN_ELEMENTS], dtype=np.float64)
+    return (rl[:, None] + rp[None, :]) - np.float64(tolerance)
+
+
+def pocket_of(data):
+    """``(pos [N_p, 3], feat [N_p, 27])`` of the pocket ``data``: a workloads.Pocket (``pos``, ``feat``), an object or a dictionary
+    with ``protein_pos`` and ``protein_atom_feature`` (what a result file's ``'data'`` is), or such a pair itself"""
+    get = (lambda k: data.get(k)) if isinstance(data, dict) else (lambda k: getattr(data, k, None))
+    if isinstance(data, (tuple, list)) and len(data) == 2:
+        pos, feat = data
+    else:
+        pos, feat = get('protein_pos'), get('protein_atom_feature')
+        if pos is None or feat is None:
+            pos, feat = get('pos'), get('feat')
+    if pos is None or feat is None:
+        raise ValueError('no pocket: it is a workloads.Pocket, an object with protein_pos and protein_atom_feature, or (pos, feat)')
+    return pos, feat
+
+
+def _pocket_arrays(data, device, kinds='residue', hydrogens=False):
+    """The pocket ``data`` (``pocket_of``) as (pos [N_p, 3] fp32, elem, kind [N_p] int32 on ``device``, names)"""
+    pos, feat = pocket_of(data)
+    elem, kind, names = pocket_kinds(feat, kinds, hydrogens)
+    pos = _fp32_positions(pos, device)
+    if pos.shape[0] != 1 or pos.shape[1] != len(elem):
+        raise ValueError(f'protein positions must be [{len(elem)}, 3] (got {tuple(pos.shape[1:]) if pos.shape[0] == 1 else tuple(pos.shape)})')
+    return pos[0].contiguous(), torch.from_numpy(elem).to(pos.device), torch.from_numpy(kind).to(pos.device), names
+
+
+class PocketContacts:
+    """The contacts of S frames of B molecules with one pocket (``pocket_contacts``).  Device tensors, frame axis first: ``n_contacts``,
+    ``n_contact_atoms`` (the buried atoms), ``n_pocket_atoms``, ``n_clashes``, ``n_clash_atoms`` [S, B] int32, ``clash_free`` [S, B]
+    bool, ``min_dist`` [S, B] float64 (+inf without pairs), ``n_ref_common`` [S, B] int32 or None, ``atom_contacts`` / ``atom_clash``
+    [S, N_l] int32, ``bits`` [S, B, W] int64 or None (bit j & 63 of word j >> 6: the molecule contacts protein atom j), and over the
+    included molecules ``kind_hist`` [S, 8, n_kinds] int64 (ligand element over H C N O F P S Cl by protein kind, ``names``) and
+    ``pocket_freq`` [S, N_p] int32; ``protein_elem`` / ``protein_kind`` [N_p] int32, ``ligand_ptr``."""
+
+    def __init__(self, r, ligand_ptr, protein_elem, protein_kind, names):
+        for k, t in r.items():
+            setattr(self, k, t)
+        self.clash_free = None if r['n_clashes'] is None else r['n_clashes'] == 0
+        self.ligand_ptr, self.protein_elem, self.protein_kind, self.names = ligand_ptr, protein_elem, protein_kind, tuple(names)
+
+
+def pocket_contacts(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic',
+                    contact_cutoff=DEFAULT_CONTACT_CUTOFF, clash_tolerance=DEFAULT_CLASH_TOLERANCE, radii=None, kinds='residue',
+                    hydrogens=False, include=None, ref_bits=None, return_bits=False, device=None):
+    """Contacts and clashes of every molecule of one frame ``[N_l, 3]`` or of a stack ``[S, N_l, 3]`` (arguments as ``bond_graph``)
+    with the pocket ``protein_pos`` [N_p, 3], ``protein_feat`` [N_p, 27], both in the frame of ``pos``; every molecule is in that one
+    pocket.  A pair is a ligand atom and a protein atom that takes part (``pocket_kinds``: no hydrogens unless ``hydrogens``); its
+    distance is the bond rule's float64 distance.  Contact: d < ``contact_cutoff`` (default 4 A).  Clash: d < r_l + r_p -
+    ``clash_tolerance`` (default 0.5 A; ``pocket_clash_thresholds``; None: no clash pass).  Both defaults are this project's
+    conventions, not measurements, and not a pose checker's.  ``include`` [S, B] restricts ``kind_hist`` and ``pocket_freq`` and
+    nothing else; ``ref_bits`` [W] int64: the contact words of a known ligand (``bits`` of a call on it), for ``n_ref_common``.
+    Molecules of more than 512 atoms are refused.  Returns a ``PocketContacts`` (the frame axis is kept)."""
+    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
+    ppos, elem, kind, names = _pocket_arrays((protein_pos, protein_feat), pos.device, kinds, hydrogens)
+    if include is not None:
+        include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+    if ref_bits is not None:
+        ref_bits = torch.as_tensor(ref_bits).to(device=pos.device).contiguous()
+    thr = None if clash_tolerance is None else pocket_clash_thresholds(clash_tolerance, radii)
+    r = capi.pocket_report(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), ppos, elem, kind, len(names), contact_cutoff, thr,
+                           include, ref_bits, True, return_bits)
+    return PocketContacts(r, ligand_ptr, elem, kind, names)
+
+
+class PocketReport:
+    """Per frame (axis 0), over the included molecules (``n_included`` [S] of ``n_samples``): ``n_clash_free``, ``sum_clashes``,
+    ``sum_contacts``, ``n_no_contact`` [S] int64; ``sum_buried`` [S], the sum of buried atoms / atoms over the ``n_nonempty`` [S]
+    non-empty ones; ``sum_min_dist`` [S] over the ``n_min_dist`` [S] molecules that have a pair; ``kind_hist`` [S, 8, n_kinds] int64
+    with ``names`` and ``backbone`` (one flag per kind, or None when the kinds do not tell); ``pocket_freq`` [S, N_p] int64, the
+    pocket's contact map, or None for a report merged from several pockets.  With a reference ligand ``sum_ref`` [S, 4] -- per pocket
+    the mean, the median and the largest recovery n_ref_common / |ref| and the mean Tanimoto n_common / (n_pocket_atoms + |ref| -
+    n_common) -- over the ``n_ref`` [S] pockets that have them: a reference that touches nothing gives no value, and the summary NaN.
+    The cutoff and the clash rule are this project's conventions (``pocket_contacts``)."""
+
+    def __init__(self, n_included, n_clash_free, sum_clashes, sum_contacts, n_no_contact, sum_buried, n_nonempty, sum_min_dist, n_min_dist,
+                 kind_hist, names, backbone, n_samples, pocket_freq=None, sum_ref=None, n_ref=None):
+        i64, f64 = (lambda a: np.asarray(a, dtype=np.int64)), (lambda a: np.asarray(a, dtype=np.float64))
+        self.n_included, self.n_clash_free, self.sum_clashes = i64(n_included), i64(n_clash_free), i64(sum_clashes)
+        self.sum_contacts, self.n_no_contact = i64(sum_contacts), i64(n_no_contact)
+        self.sum_buried, self.n_nonempty = f64(sum_buried), i64(n_nonempty)
+        self.sum_min_dist, self.n_min_dist = f64(sum_min_dist), i64(n_min_dist)
+        self.kind_hist, self.names = i64(kind_hist), tuple(names)
+        self.backbone = None if backbone is None else np.asarray(backbone, dtype=bool)
+        self.n_samples = int(n_samples)
+        self.pocket_freq = None if pocket_freq is None else i64(pocket_freq)
+        self.sum_ref = None if sum_ref is None else f64(sum_ref)
+        self.n_ref = None if n_ref is None else i64(n_ref)
+
+    @classmethod
+    def from_outputs(cls, raw, included, sizes, names, backbone=None, ref_size=None):
+        """One pocket: ``raw`` the numpy outputs of capi.pocket_report (n_contacts, n_contact_atoms, n_pocket_atoms, n_clashes,
+        min_dist, kind_hist, pocket_freq and, with a reference of ``ref_size`` contacted atoms, n_ref_common), ``included`` [S, B]
+        bool, ``sizes`` [B]"""
+        inc = np.asarray(included, dtype=bool)
+        n = np.asarray(sizes, dtype=np.float64)
+        con, clashes = np.asarray(raw['n_contacts'], dtype=np.int64), np.asarray(raw['n_clashes'], dtype=np.int64)
+        buried, md = np.asarray(raw['n_contact_atoms'], dtype=np.float64), np.asarray(raw['min_dist'], dtype=np.float64)
+        share = np.divide(buried, n[None], out=np.zeros_like(buried), where=n[None] > 0)
+        has = inc & np.isfinite(md)
+        sum_ref = n_ref = None
+        if ref_size is not None:
+            S = inc.shape[0]
+            sum_ref, n_ref = np.zeros((S, 4)), np.zeros(S, np.int64)
+            common, touched = np.asarray(raw['n_ref_common'], dtype=np.float64), np.asarray(raw['n_pocket_atoms'], dtype=np.float64)
+            for s in range(S):
+                if int(ref_size) > 0 and inc[s].any():
+                    rec = common[s][inc[s]] / float(ref_size)
+                    tan = common[s][inc[s]] / (touched[s][inc[s]] + float(ref_size) - common[s][inc[s]])
+                    sum_ref[s] = (rec.sum() / rec.size, np.median(rec), rec.max(), tan.sum() / tan.size)
+                    n_ref[s] = 1
+        return cls(inc.sum(1), (inc & (clashes == 0)).sum(1), np.where(inc, clashes, 0).sum(1), np.where(inc, con, 0).sum(1),
+                   (inc & (con == 0)).sum(1), np.where(inc, share, 0.0).sum(1), (inc & (n[None] > 0)).sum(1), np.where(has, md, 0.0).sum(1),
+                   has.sum(1), raw['kind_hist'], names, backbone, len(n), raw['pocket_freq'], sum_ref, n_ref)
+
+    @classmethod
+    def merged(cls, reports):
+        """Several pockets together: every sum added, frame by frame; the reference values become means over the pockets that have
+        one (the convention of DiversityReport).  A contact map belongs to one pocket: the merged report of several has none."""
+        reports = list(reports)
+        first = reports[0]
+        if any(r.kind_hist.shape != first.kind_hist.shape or r.names != first.names or (r.sum_ref is None) != (first.sum_ref is None)
+               for r in reports):
+            raise ValueError('reports of different frame counts or kinds, or with and without a reference ligand, do not merge')
+        tot = lambda name: sum(getattr(r, name) for r in reports)
+        return cls(tot('n_included'), tot('n_clash_free'), tot('sum_clashes'), tot('sum_contacts'), tot('n_no_contact'), tot('sum_buried'),
+                   tot('n_nonempty'), tot('sum_min_dist'), tot('n_min_dist'), tot('kind_hist'), first.names, first.backbone, tot('n_samples'),
+                   first.pocket_freq if len(reports) == 1 else None, None if first.sum_ref is None else tot('sum_ref'),
+                   None if first.sum_ref is None else tot('n_ref'))
+
+    @property
+    def num_frames(self):
+        return self.kind_hist.shape[0]
+
+    @staticmethod
+    def _mean(total, count):
+        return float(total) / int(count) if int(count) else float('nan')
+
+    def clash_free(self, frame=-1):
+        """included molecules without a protein clash / included molecules"""
+        return self._mean(self.n_clash_free[frame], self.n_included[frame])
+
+    def mean_clashes(self, frame=-1):
+        return self._mean(self.sum_clashes[frame], self.n_included[frame])
+
+    def mean_contacts(self, frame=-1):
+        return self._mean(self.sum_contacts[frame], self.n_included[frame])
+
+    def buried_share(self, frame=-1):
+        """the mean of atoms with a contact / atoms over the included non-empty molecules"""
+        return self._mean(self.sum_buried[frame], self.n_nonempty[frame])
+
+    def no_contact(self, frame=-1):
+        """the share of included molecules that touch nothing: poses that left the pocket"""
+        return self._mean(self.n_no_contact[frame], self.n_included[frame])
+
+    def mean_min_dist(self, frame=-1):
+        return self._mean(self.sum_min_dist[frame], self.n_min_dist[frame])
+
+    def contact_profile(self, frame=-1):
+        """{kind name: share of the contact pairs}, or None when there is no contact"""
+        h = self.kind_hist[frame].sum(0)
+        return {k: float(x) / float(h.sum()) for k, x in zip(self.names, h)} if h.sum() > 0 else None
+
+    def backbone_share(self, frame=-1):
+        """the share of the contact pairs whose protein atom is of the backbone; nan without contacts or when the kinds do not tell"""
+        h = self.kind_hist[frame].sum(0)
+        return self._mean(h[self.backbone].sum(), h.sum()) if self.backbone is not None else float('nan')
+
+    def contact_frequency(self, frame=-1):
+        """[N_p]: the share of the included molecules that contact each protein atom; None for a report of several pockets"""
+        if self.pocket_freq is None:
+            return None
+        n = int(self.n_included[frame])
+        return self.pocket_freq[frame] / float(n) if n else np.full(self.pocket_freq.shape[1], np.nan)
+
+    def reference_recovery(self, frame=-1):
+        """{'ref_recovery_mean', 'ref_recovery_median', 'ref_recovery_max', 'ref_tanimoto'} or {} without a reference ligand"""
+        if self.sum_ref is None:
+            return {}
+        keys = ('ref_recovery_mean', 'ref_recovery_median', 'ref_recovery_max', 'ref_tanimoto')
+        return {k: self._mean(self.sum_ref[frame, c], self.n_ref[frame]) for c, k in enumerate(keys)}
+
+    def summary(self, frame=-1):
+        return dict(pocket_clash_free=self.clash_free(frame), pocket_mean_clashes=self.mean_clashes(frame),
+                    mean_contacts=self.mean_contacts(frame), buried_share=self.buried_share(frame), no_contact=self.no_contact(frame),
+                    mean_min_dist=self.mean_min_dist(frame), backbone_share=self.backbone_share(frame), **self.reference_recovery(frame))
+
+    def lines(self, frame=-1, top=5):
+        """the report as printed lines: the summary, then the ``top`` kinds of the contact profile"""
+        out = [f'{k}:\t{x:.4f}' if x == x else f'{k}:\tNone' for k, x in self.summary(frame).items()]
+        prof = self.contact_profile(frame) or {}
+        for k, x in sorted(prof.items(), key=lambda kx: (-kx[1], kx[0]))[:top]:
+            if x > 0:
+                out.append(f'contacts {k}:\t{x:.4f}')
+        return out
+
+
+def sample_pocket(result, eval_step=-1, include='all', reference_ligand=None, contact_cutoff=DEFAULT_CONTACT_CUTOFF,
+                  clash_tolerance=DEFAULT_CLASH_TOLERANCE, kinds='residue', atom_enc_mode='add_aromatic', device='cuda'):
+    """Pocket contacts of the samples of one pocket (``result`` a loaded ``result_{i}.pt`` dictionary, whose ``'data'`` is the pocket;
+    ``eval_step`` and the packing as ``sample_quality``): per frame the share of molecules without a protein clash, the mean numbers of
+    clashes and contacts, the buried share, the share of poses that touch nothing, the mean smallest distance, the contact profile by
+    residue kind and the pocket's contact map; with ``reference_ligand`` ``(pos [n, 3], v [n])``, run through the same kernel, the
+    recovery of its contacts.  ``include`` as ``sample_rings``.  The cutoff and the clash rule are conventions (``pocket_contacts``).
+    A result without a pocket (the driver's bare 7-tuple) is refused.  Returns a ``PocketReport``."""
+    data = result.get('data') if isinstance(result, dict) else None
+    if data is None:
+        raise ValueError("the result carries no pocket: sample_pocket needs a result dictionary with its 'data' (results.result_dict), "
+                         'or use SamplePack.pocket(data)')
+    return SamplePack(result, eval_step, atom_enc_mode, device).pocket(data, include, reference_ligand, contact_cutoff, clash_tolerance, kinds)

@@ -21,6 +21,12 @@ molecules without an internal clash (a pair more than 3 bonds apart and closer t
 project's own convention, not PoseBusters' bound and not a force field), the mean number of clashes, the crowded-atom and degenerate
 counts, and per angle and torsion type the count, the mean angle and -- with ``--reference_sdf FILE``, of which every record then makes
 up the reference (quality.geometry_reference: the same kernel, the same bond rule) -- the Jensen-Shannon distance.
+``--pocket [--contact_cutoff X] [--clash_tolerance X]`` adds the contacts of the samples with their pocket (quality.sample_pocket; the
+pocket is the file's ``data``), over ``--include all`` or ``complete`` samples: the share of molecules without a protein clash (a ligand
+atom and a protein atom closer than the sum of their van der Waals radii minus 0.5 A), the mean numbers of clashes and of contacts
+(pairs closer than 4 A), the buried share, the share of poses that touch nothing, the mean smallest distance, the share of contacts
+with the backbone and the most frequent residue kinds -- conventions of this project, not a pose checker's -- and, with the known
+ligand of ``--reference_sdf`` / ``--reference_npz``, how many of its contacts the samples recover.
 The fingerprint is this project's own circular one over its bond graph, not RDKit's RDKFingerprint: the numbers compare between
 runs of this tool, not with published tables.  The Jensen-Shannon distances need the reference's empirical distributions: they are
 loaded from ``utils.evaluation`` when the tool runs inside the reference repository (or with it on PYTHONPATH), or from
@@ -72,8 +78,13 @@ def main(argv=None):
                     "(this project's circular fingerprint, not RDKit's)")
     ap.add_argument('--geometry', action='store_true', help='also bond angles, torsions and internal clashes (a convention of this '
                     'project, not a pose checker)')
-    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity: a known ligand, the first V2000 record of FILE; '
-                    '--geometry: known ligands, every record of FILE')
+    ap.add_argument('--pocket', action='store_true', help='also the contacts and clashes with the pocket (the result file\'s data; a '
+                    'convention of this project, not a pose checker)')
+    ap.add_argument('--contact_cutoff', type=float, default=quality.DEFAULT_CONTACT_CUTOFF, help='--pocket: a contact is a pair closer than this')
+    ap.add_argument('--clash_tolerance', type=float, default=quality.DEFAULT_CLASH_TOLERANCE,
+                    help='--pocket: a clash is a pair closer than the sum of the van der Waals radii minus this')
+    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity, --pocket: a known ligand, the first V2000 record of '
+                    'FILE; --geometry: known ligands, every record of FILE')
     ap.add_argument('--reference_npz', type=str, default=None)
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
@@ -100,10 +111,11 @@ def main(argv=None):
     if not files:
         raise SystemExit(f'no result_*.pt under {args.sample_path}')
     print(f'Load generated data done! {len(files)} examples in total.')
-    reports, connectivity, rings, diversity, geometry = [], [], [], [], []
+    reports, connectivity, rings, diversity, geometry, pocket = [], [], [], [], [], []
     graph_include = 'complete' if args.include == 'complete' else 'all'     # 'stable' restricts the pair profiles and atom types only
     for name in files:
-        pack = quality.SamplePack(torch.load(name, map_location='cpu', weights_only=False), eval_step, args.atom_enc_mode, args.device)
+        result = torch.load(name, map_location='cpu', weights_only=False)
+        pack = quality.SamplePack(result, eval_step, args.atom_enc_mode, args.device)
         if args.connectivity:
             connectivity.append(pack.connectivity(graph_include, bond_reference))
         if args.rings:
@@ -112,6 +124,10 @@ def main(argv=None):
             diversity.append(pack.diversity(graph_include, reference_ligand=reference_ligand))
         if args.geometry:
             geometry.append(pack.geometry(graph_include, geometry_reference))
+        if args.pocket:
+            if not isinstance(result, dict) or result.get('data') is None:
+                raise SystemExit(f'{name} carries no pocket (no data): --pocket needs the files of a sampling driver')
+            pocket.append(pack.pocket(result['data'], graph_include, reference_ligand, args.contact_cutoff, args.clash_tolerance))
         reports.append(pack.quality(args.include, reference))
     rep = quality.QualityReport.merged(reports)
     print(f'Evaluate done! {rep.n_samples} samples in total.')
@@ -164,6 +180,15 @@ def main(argv=None):
                                hist={n: geo.counts(n, -1).tolist() for n in geo.names})
         if eval_step == 'all':
             out['geometry']['curve'] = [flat(geo.summary(s)) for s in range(geo.num_frames)]
+    if args.pocket:
+        poc = quality.PocketReport.merged(pocket)
+        print('\n'.join(poc.lines(-1)))
+        nan_none = lambda d: {k: (None if x != x else x) for k, x in d.items()}
+        out['pocket'] = dict(nan_none(poc.summary(-1)), num_included=int(poc.n_included[-1]), contact_cutoff=args.contact_cutoff,
+                             clash_tolerance=args.clash_tolerance, contact_profile=poc.contact_profile(-1),
+                             kind_hist=dict(zip(poc.names, poc.kind_hist[-1].sum(0).tolist())))
+        if eval_step == 'all':
+            out['pocket']['curve'] = [nan_none(poc.summary(s)) for s in range(poc.num_frames)]
     result_path = os.path.join(args.sample_path, 'eval_results')
     os.makedirs(result_path, exist_ok=True)
     with open(os.path.join(result_path, 'quality.json'), 'w') as f:

@@ -1,7 +1,7 @@
 """Sampled ligands as SD files, without a chemistry toolkit:
 
     python tools/export_sdf.py --sample_path DIR --out DIR [--eval_step -1] [--only-complete] [--largest-fragment] [--ring-aromatic]
-                                [--unique] [--clash-free]
+                                [--unique] [--clash-free] [--pocket-clash-free]
 
 Reads the ``result_{i}.pt`` files a sampling driver wrote (sorted as tools/evaluate_samples.py sorts them), takes the frame
 ``--eval_step`` of every sample (default -1: the final poses), builds the bond graph on the GPU (quality.bond_graph: bonds from the
@@ -18,6 +18,9 @@ fragments differ are both written.
 ``--clash-free`` writes only the samples without an internal clash (quality.geometry: no pair of atoms more than 3 bonds apart closer
 than 0.7 times the sum of their van der Waals radii; DESIGN.md section 3, "Local geometry" -- this project's convention, not a pose
 checker's); it applies before ``--unique`` chooses among what is left.
+``--pocket-clash-free`` writes only the samples without a clash with the protein (quality.pocket_contacts on the file's pocket: no
+ligand atom closer to a protein atom than the sum of their van der Waals radii minus 0.5 A; DESIGN.md section 3, "Pocket contacts" --
+again a convention); it combines with ``--clash-free`` and applies before ``--unique`` too.
 Prints one line per file and returns the counts.
 """
 from __future__ import annotations
@@ -49,6 +52,7 @@ def main(argv=None):
     ap.add_argument('--unique', action='store_true', help='of the samples with equal keys only the first; the keys are of the whole '
                     'molecule (also with --largest-fragment), taken after --only-complete')
     ap.add_argument('--clash-free', action='store_true', help='only the samples without an internal clash')
+    ap.add_argument('--pocket-clash-free', action='store_true', help="only the samples without a clash with the protein (the file's data)")
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
     files = result_files(args.sample_path, args.eval_num_examples)
@@ -57,17 +61,25 @@ def main(argv=None):
     os.makedirs(args.out, exist_ok=True)
     out = {}
     for name in files:
-        pack = quality.SamplePack(torch.load(name, map_location='cpu', weights_only=False), args.eval_step, args.atom_enc_mode, args.device)
+        result = torch.load(name, map_location='cpu', weights_only=False)
+        pack = quality.SamplePack(result, args.eval_step, args.atom_enc_mode, args.device)
         pos, v, ptr, sizes = pack.pos, pack.v, pack.ligand_ptr, pack.sizes
         g = quality.bond_graph(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, bond_profiles=(), return_fragments=True,
                                return_bonds=True, rings=args.ring_aromatic, device=args.device)
-        select = chosen = clash_free = None
+        select = chosen = clash_free = pocket_clash_free = None
         if args.only_complete:
             chosen = g.complete[0]
         if args.clash_free:
             clash_free = quality.geometry(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, profiles=(), device=args.device).clash_free[0]
             chosen = clash_free if chosen is None else chosen & clash_free
             select = clash_free.cpu().numpy()
+        if args.pocket_clash_free:
+            if not isinstance(result, dict) or result.get('data') is None:
+                raise SystemExit(f'{name} carries no pocket (no data): --pocket-clash-free needs the files of a sampling driver')
+            pocket_clash_free = quality.pocket_contacts(*quality.pocket_of(result['data']), pos, v, ligand_ptr=ptr,
+                                                        atom_enc_mode=args.atom_enc_mode, device=args.device).clash_free[0]
+            chosen = pocket_clash_free if chosen is None else chosen & pocket_clash_free
+            select = pocket_clash_free.cpu().numpy() & (True if select is None else select)
         if args.unique:
             fp = quality.fingerprints(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, device=args.device)
             first = fp.similarity(include=None if chosen is None else chosen[None])['first_equal'][0].cpu().numpy()
@@ -82,6 +94,8 @@ def main(argv=None):
         out[stem] = dict(path=path, written=n, samples=len(sizes), complete=complete)
         if clash_free is not None:
             out[stem]['clash_free'] = int(clash_free.sum())
+        if pocket_clash_free is not None:
+            out[stem]['pocket_clash_free'] = int(pocket_clash_free.sum())
     return out
 
 

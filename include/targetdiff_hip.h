@@ -486,6 +486,45 @@ int td_pocket_report(const float *d_pos, const int64_t *d_v, const int32_t *d_li
                      int32_t *d_n_ref_common, int32_t *d_atom_contacts, int32_t *d_atom_clash, uint64_t *d_bits, int64_t *d_kind_hist,
                      int32_t *d_pocket_freq, void *stream);
 
+/* ---- typed pocket interactions of ligand frames ("Pocket interactions"): hydrogen bonds and hydrophobic
+ *      contacts, counted; no energy, no score, no float output.  The pack, the class table, d_include, d_protein_pos, d_protein_elem,
+ *      d_protein_kind, N_p and n_kinds as td_pocket_report takes them, and the distance d is the same: the bond rule's, bit for bit.
+ *      Role bits: DONOR = 1, ACCEPTOR = 2, HYDROPHOBIC = 4.  All comparisons are strict; the three cutoffs are finite doubles > 0.
+ *      Protein roles: d_protein_role [N_p] int32, the donor / acceptor bits of the caller's table (bits above 2 are ignored) or a
+ *      negative number.  A protein atom takes part when its element and kind are in range and its role is >= 0; any other takes part
+ *      nowhere.  A carbon that takes part is HYDROPHOBIC when no N or O that takes part lies at d < hetero_cutoff.
+ *      d_protein_role_out [N_p] int32: the role with that bit resolved, -1 for an atom that takes no part.
+ *      Ligand roles, per frame and molecule on the bond graph of td_bond_graph (the same pack, class table and distance; orders 1 / 2 /
+ *      3; an atom whose class is outside [0, K) bonds with nothing and has no role): val = the sum of the orders of the atom's bonds,
+ *      n_h = its bonded H, hetero = its bonded N and O, h = n_h + max(0, V - val) with V = 3 for N and 2 for O.  DONOR: N or O with
+ *      h >= 1.  ACCEPTOR: O; N with h = 0 and val <= 3.  HYDROPHOBIC: C with hetero = 0; F; Cl.  H, P, S: none.  The donors are a
+ *      valence-deficit heuristic (the sampler places no hydrogens), not perceived chemistry.
+ *      Interactions of a ligand atom that has a role with a protein atom that takes part: type 0, the ligand donates (DONOR to
+ *      ACCEPTOR, d < hbond_cutoff); type 1, the ligand accepts (ACCEPTOR to DONOR, d < hbond_cutoff); type 2, hydrophobic (both
+ *      HYDROPHOBIC, d < hydrophobic_cutoff).  A pair of type 0 and type 1 at once is one hydrogen bond.
+ *      d_ref_bits [3,W] uint64, W = ceil(N_p / 64), may be NULL: per type, bit j & 63 of word j >> 6 marks protein atom j.
+ *      Output per (frame, molecule), [S,B] int32: d_n_donated, d_n_accepted, d_n_hbonds, d_n_hydrophobic, the pairs of type 0, of
+ *      type 1, of type 0 or 1, of type 2; d_n_hb_atoms, the ligand atoms in at least one hydrogen bond; d_n_donors, d_n_acceptors,
+ *      d_n_hydrophobic_atoms, the ligand atoms that hold each role; d_n_ref_common [S,B,3], per type the protein atoms hit that
+ *      d_ref_bits marks (written only with d_ref_bits).  May be NULL: d_atom_role [S,N_l] int32, the role bits; d_atom_hbonds and
+ *      d_atom_hydrophobic [S,N_l] int32, the hydrogen bonds and the hydrophobic pairs each ligand atom takes part in; d_bits
+ *      [S,B,3,W] uint64, the protein atoms hit per type in the layout of d_ref_bits.  Over the molecules whose d_include byte is
+ *      non-zero (NULL: all), zeroed by the call: d_kind_hist [S,3,n_kinds] int64, the pairs by type and protein kind; d_pocket_freq
+ *      [S,3,N_p] int32, the number of such molecules of the frame that hit protein atom j with that type.  A molecule of more than
+ *      512 atoms, or one whose offsets leave [0, N_l], gets -1 in every per-molecule output and zero words in d_bits, its per-atom
+ *      outputs are not written, and it contributes nothing else (a binding refuses it).  512 N_p and 3 S N_p must fit 31 bits.
+ *      S, B and N_p may be 0.  Every output is an integer: nothing depends on the grid or on the order of arrival.
+ *      (An addition: TD_ABI_VERSION stays 5.) */
+int td_interaction_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                          const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const float *d_protein_pos,
+                          const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p,
+                          int32_t n_kinds, double hbond_cutoff, double hydrophobic_cutoff, double hetero_cutoff,
+                          const uint64_t *d_ref_bits, int32_t *d_protein_role_out, int32_t *d_n_donated, int32_t *d_n_accepted,
+                          int32_t *d_n_hbonds, int32_t *d_n_hydrophobic, int32_t *d_n_hb_atoms, int32_t *d_n_donors,
+                          int32_t *d_n_acceptors, int32_t *d_n_hydrophobic_atoms, int32_t *d_n_ref_common, int32_t *d_atom_role,
+                          int32_t *d_atom_hbonds, int32_t *d_atom_hydrophobic, uint64_t *d_bits, int64_t *d_kind_hist,
+                          int32_t *d_pocket_freq, void *stream);
+
 /* ---- standalone EGNN refine net (replaces: models/egnn.py EGNN / EnBaseLayer as get_refine_net('egnn', config) builds
  *      it, models/molopt_score_model.py:34-42: num_r_gaussian = 1, kNN rebuilt per layer, SiLU, no LayerNorm, hidden 128,
  *      4 edge types, k = 32).  `host_weights`: per layer, in this order and as PyTorch stores them: edge_mlp.net.0.{weight

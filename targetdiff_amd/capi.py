@@ -103,6 +103,9 @@ SIGNATURES = {
                                      _P, POINTER(ctypes.c_double), _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_pocket_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, _P, _P, c_int64, c_int32,
                                    ctypes.c_double, POINTER(ctypes.c_double), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'td_interaction_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, _P, _P, _P, c_int64, c_int32,
+                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        _P, _P, _P, _P, _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_center_pos': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int32, c_int32, _P]),
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
@@ -1245,7 +1248,68 @@ def pocket_report(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, protei
     return out
 
 
-FP_BITS, FP_WORDS, FP_MAX_RADIUS, FP_MAX_ROUNDS = 2048, 32, 4, 16            # TD_FP_* (csrc/td_internal.h)
+ROLE_DONOR, ROLE_ACCEPTOR, ROLE_HYDROPHOBIC, INTERACTION_TYPES = 1, 2, 4, 3   # TD_ROLE_*, TD_INTERACTION_TYPES (csrc/td_internal.h)
+
+
+def _interaction_inputs(pos, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, cutoffs, ref_bits, check=True):
+    """The pocket's side of an interaction_report call: what _pocket_inputs checks of the pocket, then the roles, the three cutoffs and
+    the reference words; with ``check`` the roles are looked at on the host.  Returns (N_p, W)."""
+    Np, W, _ = _pocket_inputs(pos, protein_pos, protein_elem, protein_kind, n_kinds, 1.0, None, None, check)
+    if tuple(protein_role.shape) != (Np,) or protein_role.dtype != torch.int32:
+        raise ValueError(f'protein_role must be [{Np}] int32 (got {tuple(protein_role.shape)} {protein_role.dtype})')
+    if protein_role.device != pos.device or (ref_bits is not None and ref_bits.device != pos.device):
+        raise ValueError(f'the pocket must live on the device of the pack ({pos.device})')
+    for name, c in zip(('hbond', 'hydrophobic', 'hetero'), cutoffs):
+        if not (np.isfinite(float(c)) and float(c) > 0.0):
+            raise ValueError(f'the {name} cutoff must be finite and > 0 (got {c})')
+    if ref_bits is not None and (tuple(ref_bits.shape) != (INTERACTION_TYPES, W) or ref_bits.dtype != torch.int64):
+        raise ValueError(f'ref_bits must be [{INTERACTION_TYPES}, {W}] int64 words, as interaction_report returns bits (got '
+                         f'{tuple(ref_bits.shape)} {ref_bits.dtype})')
+    if check and Np > 0 and (int(protein_role.min()) < -1 or int(protein_role.max()) > (ROLE_DONOR | ROLE_ACCEPTOR)):
+        raise ValueError('protein_role must be -1 or a sum of DONOR = 1 and ACCEPTOR = 2: the device decides which carbons are hydrophobic')
+    return Np, W
+
+
+def interaction_report(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, hbond_cutoff=3.5,
+                       hydrophobic_cutoff=4.5, hetero_cutoff=1.75, include=None, ref_bits=None, return_atoms=True, return_bits=True,
+                       check=True):
+    """Hydrogen bonds and hydrophobic contacts of S frames of B molecules with one pocket (td_interaction_report,
+    include/targetdiff_hip.h); the pack, the class table, ``include`` and the pocket as pocket_report's.  ``protein_role`` [N_p] int32:
+    DONOR = 1, ACCEPTOR = 2, their sum, 0, or -1 (the atom takes part nowhere); the device adds HYDROPHOBIC = 4 to the carbons without
+    an N or O closer than ``hetero_cutoff``.  Types: 0 the ligand donates, 1 the ligand accepts (d < ``hbond_cutoff``), 2 hydrophobic
+    (d < ``hydrophobic_cutoff``).  ``ref_bits`` [3, W] int64, W = ceil(N_p / 64).  Returns a dict of device tensors: protein_role
+    [N_p] int32; n_donated, n_accepted, n_hbonds, n_hydrophobic, n_hb_atoms, n_donors, n_acceptors, n_hydrophobic_atoms [S, B] int32;
+    n_ref_common [S, B, 3] int32 (None without ``ref_bits``); atom_role, atom_hbonds, atom_hydrophobic [S, N_l] int32 (None without
+    ``return_atoms``); bits [S, B, 3, W] int64 (None without ``return_bits``); and over the included molecules kind_hist
+    [S, 3, n_kinds] int64 and pocket_freq [S, 3, N_p] int32."""
+    S, Nl, B, cz, _, _ = _bond_inputs(pos, v, ligand_ptr, class_z, None, include, (), check)
+    cutoffs = (hbond_cutoff, hydrophobic_cutoff, hetero_cutoff)
+    Np, W = _interaction_inputs(pos, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, cutoffs, ref_bits, check)
+    lib = load_library()
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
+    dev = pos.device
+    T = INTERACTION_TYPES
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    z32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)    # an oversize molecule's atoms are not written
+    mol = ('n_donated', 'n_accepted', 'n_hbonds', 'n_hydrophobic', 'n_hb_atoms', 'n_donors', 'n_acceptors', 'n_hydrophobic_atoms')
+    out = dict(protein_role=i32(Np), **{k: i32(S, B) for k in mol},
+               n_ref_common=(z32 if W == 0 else i32)(S, B, T) if ref_bits is not None else None,   # no words: nothing is in common
+               atom_role=z32(S, Nl) if return_atoms else None, atom_hbonds=z32(S, Nl) if return_atoms else None,
+               atom_hydrophobic=z32(S, Nl) if return_atoms else None,
+               bits=torch.empty(S, B, T, W, dtype=torch.int64, device=dev) if return_bits else None,
+               kind_hist=torch.empty(S, T, int(n_kinds), dtype=torch.int64, device=dev), pocket_freq=i32(S, T, Np))
+    with _on(dev):
+        _check(lib.td_interaction_report(*pack, _include_arg(include), _ptr(protein_pos, torch.float32, 'protein_pos'),
+                                         _ptr(protein_elem, torch.int32, 'protein_elem'), _ptr(protein_kind, torch.int32, 'protein_kind'),
+                                         _ptr(protein_role, torch.int32, 'protein_role'), Np, int(n_kinds), *(float(c) for c in cutoffs),
+                                         _ptr(ref_bits, torch.int64, 'ref_bits'), _ptr(out['protein_role']), *(_ptr(out[k]) for k in mol),
+                                         _ptr(out['n_ref_common']), _ptr(out['atom_role']), _ptr(out['atom_hbonds']),
+                                         _ptr(out['atom_hydrophobic']), _ptr(out['bits']), _ptr(out['kind_hist']), _ptr(out['pocket_freq']),
+                                         _stream(dev)), 'td_interaction_report')
+    return out
+
+
+FP_BITS, FP_WORDS, FP_MAX_RADIUS, FP_MAX_ROUNDS = 2048, 32, 4, 16           # TD_FP_* (csrc/td_internal.h)
 
 
 def _fingerprint_inputs(pos, v, ligand_ptr, class_z, class_aromatic, radius, key_rounds, check=True):

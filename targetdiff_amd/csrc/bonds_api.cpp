@@ -1,7 +1,8 @@
 // C ABI of libtargetdiff_hip.so: the bond graph of ligand frames, its rings, its fingerprints, its local geometry and the contacts with
-// the pocket (td_bond_graph, td_bond_list, td_ring_report, td_fingerprint, td_fingerprint_similarity, td_geometry_report,
-// td_pocket_report).  See include/targetdiff_hip.h for the contract.
+// the pocket and the typed interactions with it (td_bond_graph, td_bond_list, td_ring_report, td_fingerprint,
+// td_fingerprint_similarity, td_geometry_report, td_pocket_report, td_interaction_report).  See include/targetdiff_hip.h for the contract.
 #include <cmath>
+#include <initializer_list>
 
 #include "td_device.h"
 #include "td_internal.h"
@@ -260,4 +261,54 @@ extern "C" int td_pocket_report(const float *d_pos, const int64_t *d_v, const in
     g.bits = reinterpret_cast<unsigned long long *>(d_bits); g.kind_hist = reinterpret_cast<unsigned long long *>(d_kind_hist);
     g.pocket_freq = d_pocket_freq;
     return td_launch_pocket_report(g, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int td_interaction_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                                     const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const float *d_protein_pos,
+                                     const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role,
+                                     int64_t N_p, int32_t n_kinds, double hbond_cutoff, double hydrophobic_cutoff, double hetero_cutoff,
+                                     const uint64_t *d_ref_bits, int32_t *d_protein_role_out, int32_t *d_n_donated, int32_t *d_n_accepted,
+                                     int32_t *d_n_hbonds, int32_t *d_n_hydrophobic, int32_t *d_n_hb_atoms, int32_t *d_n_donors,
+                                     int32_t *d_n_acceptors, int32_t *d_n_hydrophobic_atoms, int32_t *d_n_ref_common, int32_t *d_atom_role,
+                                     int32_t *d_atom_hbonds, int32_t *d_atom_hydrophobic, uint64_t *d_bits, int64_t *d_kind_hist,
+                                     int32_t *d_pocket_freq, void *stream) {
+    const char *who = "td_interaction_report";
+    TdInteractionArgs g;
+    if (const int rc = bond_pack(who, g.b, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, nullptr)) return rc;
+    if (N_p < 0 || N_p > 0x7fffffff / TD_BOND_MAX_ATOMS || S * N_p > 0x7fffffff / TD_INTERACTION_TYPES) {   // a molecule's pairs are counted in an int32
+        td_set_error("%s: bad argument (N_p = %lld; 512 N_p and 3 S * N_p must fit 31 bits)", who, (long long)N_p);
+        return TD_EINVAL;
+    }
+    if (n_kinds < 1 || n_kinds > TD_POCKET_MAX_KINDS) {
+        td_set_error("%s: 1 .. %d kinds of protein atoms (got %d)", who, TD_POCKET_MAX_KINDS, (int)n_kinds);
+        return TD_EINVAL;
+    }
+    for (const double c : {hbond_cutoff, hydrophobic_cutoff, hetero_cutoff})
+        if (!std::isfinite(c) || !(c > 0.0)) {
+            td_set_error("%s: the hbond, hydrophobic and hetero cutoffs must be finite and > 0", who);
+            return TD_EINVAL;
+        }
+    if (N_p > 0 && (!d_protein_pos || !d_protein_elem || !d_protein_kind || !d_protein_role || !d_protein_role_out)) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    if ((S > 0 && (!d_kind_hist || (N_p > 0 && !d_pocket_freq))) ||
+        (S > 0 && B > 0 && (!d_n_donated || !d_n_accepted || !d_n_hbonds || !d_n_hydrophobic || !d_n_hb_atoms || !d_n_donors ||
+                            !d_n_acceptors || !d_n_hydrophobic_atoms || (d_ref_bits && !d_n_ref_common)))) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    g.b.include = d_include;
+    g.ppos = d_protein_pos; g.pelem = d_protein_elem; g.pkind = d_protein_kind; g.prole = d_protein_role;
+    g.ref_bits = reinterpret_cast<const unsigned long long *>(d_ref_bits);
+    g.Np = (int)N_p; g.W = (int)((N_p + 63) / 64); g.n_kinds = n_kinds;
+    g.hbond_cutoff = hbond_cutoff; g.hydrophobic_cutoff = hydrophobic_cutoff; g.hetero_cutoff = hetero_cutoff;
+    g.role_out = d_protein_role_out;
+    g.n_donated = d_n_donated; g.n_accepted = d_n_accepted; g.n_hbonds = d_n_hbonds; g.n_hydrophobic = d_n_hydrophobic;
+    g.n_hb_atoms = d_n_hb_atoms; g.n_donors = d_n_donors; g.n_acceptors = d_n_acceptors; g.n_hydrophobic_atoms = d_n_hydrophobic_atoms;
+    g.n_ref_common = d_n_ref_common;
+    g.atom_role = d_atom_role; g.atom_hbonds = d_atom_hbonds; g.atom_hydrophobic = d_atom_hydrophobic;
+    g.bits = reinterpret_cast<unsigned long long *>(d_bits); g.kind_hist = reinterpret_cast<unsigned long long *>(d_kind_hist);
+    g.pocket_freq = d_pocket_freq;
+    return td_launch_interaction_report(g, static_cast<hipStream_t>(stream));
 }

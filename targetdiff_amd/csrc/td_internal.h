@@ -533,6 +533,29 @@ struct TdPocketArgs {
     int32_t *pocket_freq = nullptr;          // [S,Np]
 };
 int td_launch_pocket_report(const TdPocketArgs &a, hipStream_t s);
+// interactions.hip (td_interaction_report, DESIGN.md section 3, "Pocket interactions"): the pack and the include bytes in `b`; the pocket
+// as TdPocketArgs takes it, and prole: the donor / acceptor bits of the host's table or a negative number.  A protein atom takes part
+// when its element and its kind are in range and its role is >= 0; role_out is then its role with the hydrophobic bit resolved on the
+// device (-1 for an atom that takes no part), and the pair kernel reads role_out alone.  reject2 as TdPocketArgs.  Three planes (ligand
+// donates, ligand accepts, hydrophobic) of W = ceil(Np / 64) words.  The launcher zeroes kind_hist and pocket_freq on the stream.
+constexpr int TD_ROLE_DONOR = 1, TD_ROLE_ACCEPTOR = 2, TD_ROLE_HYDROPHOBIC = 4, TD_INTERACTION_TYPES = 3;
+struct TdInteractionArgs {
+    TdBondArgs b;
+    const float *ppos = nullptr;             // [Np,3]
+    const int32_t *pelem = nullptr, *pkind = nullptr, *prole = nullptr;          // [Np]
+    const unsigned long long *ref_bits = nullptr;                                // [3,W] or null
+    int Np = 0, W = 0, n_kinds = 0;
+    double hbond_cutoff = 0.0, hydrophobic_cutoff = 0.0, hetero_cutoff = 0.0, reject2 = 0.0;
+    int32_t *role_out = nullptr;             // [Np]
+    int32_t *n_donated = nullptr, *n_accepted = nullptr, *n_hbonds = nullptr, *n_hydrophobic = nullptr;      // [S,B] pairs
+    int32_t *n_hb_atoms = nullptr, *n_donors = nullptr, *n_acceptors = nullptr, *n_hydrophobic_atoms = nullptr;   // [S,B] ligand atoms
+    int32_t *n_ref_common = nullptr;         // [S,B,3], written when ref_bits
+    int32_t *atom_role = nullptr, *atom_hbonds = nullptr, *atom_hydrophobic = nullptr;      // [S,N_l] or null
+    unsigned long long *bits = nullptr;      // [S,B,3,W] or null
+    unsigned long long *kind_hist = nullptr; // [S,3,n_kinds]
+    int32_t *pocket_freq = nullptr;          // [S,3,Np]
+};
+int td_launch_interaction_report(const TdInteractionArgs &a, hipStream_t s);
 // egnn.hip / node.hip
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s);

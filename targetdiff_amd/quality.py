@@ -57,6 +57,15 @@ and, with the pocket's known ligand, how many of its contacts a sample recovers 
     poc.summary()   # {'pocket_clash_free': ..., 'mean_contacts': ..., 'buried_share': ..., 'no_contact': ..., 'ref_recovery_mean': ...}
     poc.contact_profile(), poc.contact_frequency()    # contacts by residue kind ('ASP.sc', 'GLY.bb', ...), and per protein atom
 
+And what kind of contacts they are (``td_interaction_report``, csrc/interactions.hip; DESIGN.md section 3, "Pocket interactions"):
+hydrogen bonds (a donor and an acceptor closer than 3.5 A, heavy atom to heavy atom, no angle) and hydrophobic contacts (closer than
+4.5 A), counted, never scored.  The ligand's donors are inferred from the valence deficit the bond rule leaves -- a heuristic of this
+project, not perceived chemistry:
+
+    ia = quality.sample_interactions(result, eval_step='all', reference_ligand=(ref_pos, ref_v))
+    ia.summary()   # {'mean_hbonds': ..., 'mean_donated': ..., 'mean_accepted': ..., 'mean_hydrophobic': ..., 'no_hbond': ..., ...}
+    ia.kind_profile('donated'), ia.interaction_frequency()    # hydrogen bonds by residue kind, and per type and protein atom
+
 Several reports of one result share its pack, its host checks and its bond graph (``SamplePack``; the ``sample_*`` functions build one each):
 
     pack = quality.SamplePack(result, eval_step='all')
@@ -463,6 +472,27 @@ class SamplePack:
         raw = {k: r[k].cpu().numpy() for k in keys if r[k] is not None}
         return PocketReport.from_outputs(raw, self._included(mask), self.sizes, names, [n.endswith('.bb') for n in names] if kinds == 'residue'
                                          else None, ref_size)
+
+    def interactions(self, data, include='all', reference_ligand=None, hbond_cutoff=3.5, hydrophobic_cutoff=4.5, hetero_cutoff=1.75):
+        """``sample_interactions`` of the pack; ``data``: the pocket every molecule of the pack is in (``_pocket_arrays``)"""
+        ppos, elem, kind, names = _pocket_arrays(data, self.pos.device)
+        role = torch.from_numpy(pocket_roles(pocket_of(data)[1])).to(self.pos.device)
+        mask = self.mask(include)
+        pocket = (ppos, elem, kind, role, len(names), hbond_cutoff, hydrophobic_cutoff, hetero_cutoff)
+        ref_bits = ref_sizes = None
+        if reference_ligand is not None:
+            rpos, rv = reference_ligand
+            rpos, rv, rptr = _pack(rpos, rv, None, torch.tensor([0, len(rv)], dtype=torch.int32), self.pos.device)
+            if rpos.shape[0] != 1:
+                raise ValueError('the reference ligand is one molecule: pos [n, 3], v [n]')
+            q = capi.interaction_report(rpos, rv, rptr, self.class_z, *pocket, None, None, False, True)
+            ref_bits = q['bits'][0, 0].contiguous()
+            ref_sizes = _popcount(ref_bits.cpu().numpy())
+        r = capi.interaction_report(*self._args, *pocket, mask, ref_bits, True, ref_bits is not None, check=self._check())
+        keys = ('n_donated', 'n_accepted', 'n_hbonds', 'n_hydrophobic', 'n_hb_atoms', 'atom_role', 'n_ref_common', 'bits', 'kind_hist',
+                'pocket_freq')
+        raw = {k: r[k].cpu().numpy() for k in keys if r[k] is not None}
+        return InteractionReport.from_outputs(raw, self._included(mask), self.sizes, names, ref_sizes)
 
 
 def sample_quality(result, eval_step=-1, include='all', atom_enc_mode='add_aromatic', reference=None, profiles=None, device='cuda'):
@@ -1304,3 +1334,240 @@ def sample_pocket(result, eval_step=-1, include='all', reference_ligand=None, co
         raise ValueError("the result carries no pocket: sample_pocket needs a result dictionary with its 'data' (results.result_dict), "
                          'or use SamplePack.pocket(data)')
     return SamplePack(result, eval_step, atom_enc_mode, device).pocket(data, include, reference_ligand, contact_cutoff, clash_tolerance, kinds)
+
+
+# ---- typed pocket interactions (``td_interaction_report``, csrc/interactions.hip; DESIGN.md section 3, "Pocket interactions")
+# Counts of hydrogen bonds and hydrophobic contacts; no energy and no score.  The roles are conventions of this project: the ligand's
+# donors are inferred from the valence deficit of N and O under the bond rule (the sampler places no hydrogens), a heuristic and not
+# perceived chemistry; the protein's come from a residue table; a hydrogen bond is a donor - acceptor pair of heavy atoms closer than
+# 3.5 A with no angle criterion, a hydrophobic contact a pair of hydrophobic atoms closer than 4.5 A.
+ROLE_DONOR, ROLE_ACCEPTOR, ROLE_HYDROPHOBIC = capi.ROLE_DONOR, capi.ROLE_ACCEPTOR, capi.ROLE_HYDROPHOBIC
+ROLE_NAMES = {ROLE_DONOR: 'donor', ROLE_ACCEPTOR: 'acceptor', ROLE_HYDROPHOBIC: 'hydrophobic'}
+INTERACTION_NAMES = ('donated', 'accepted', 'hydrophobic')      # type 0: the ligand donates; 1: the ligand accepts; 2: hydrophobic
+DEFAULT_HBOND_CUTOFF = 3.5
+DEFAULT_HYDROPHOBIC_CUTOFF = 4.5
+DEFAULT_HETERO_CUTOFF = 1.75                          # between a C-N / C-O bond and the nearest non-bonded pair
+
+
+def pocket_roles(feat, hydrogens=False):
+    """[n] int32 of the protein feature ``[n, 27]`` (``pocket_kinds``): the donor / acceptor bits of every protein atom by residue,
+    element and backbone bit.  Backbone N: DONOR, except PRO.  Backbone O: ACCEPTOR.  Side-chain O of SER, THR, TYR: DONOR | ACCEPTOR;
+    any other O (ASP, GLU, ASN, GLN, a terminal OXT): ACCEPTOR.  Side-chain N of ARG, LYS, ASN, GLN, TRP: DONOR; of HIS: DONOR |
+    ACCEPTOR.  C, S, Se, H: 0 (which carbons are hydrophobic the device decides).  -1, an atom that takes part nowhere: a row without
+    an element bit or without a residue bit, and a hydrogen unless ``hydrogens``."""
+    from . import workloads
+    f = feat.detach().cpu().numpy() if torch.is_tensor(feat) else np.asarray(feat)
+    ne, na = len(workloads.PROTEIN_ELEMENTS), len(workloads.AA_NAMES)
+    if f.ndim != 2 or f.shape[1] != ne + na + 1:
+        raise ValueError(f'the protein feature is [n, {ne + na + 1}] (got {tuple(f.shape)})')
+    f = f != 0
+    elem = np.where(f[:, :ne].any(1), f[:, :ne].argmax(1), -1)
+    aa = np.where(f[:, ne:ne + na].any(1), f[:, ne:ne + na].argmax(1), -1)
+    bb = f[:, ne + na]
+    of = lambda *names: np.isin(aa, [workloads.AA_NAMES.index(x) for x in names])
+    N, O = elem == workloads.PROTEIN_ELEMENTS.index(7), elem == workloads.PROTEIN_ELEMENTS.index(8)
+    role = np.zeros(len(f), np.int32)
+    role[N & bb & ~of('PRO')] = ROLE_DONOR
+    role[N & ~bb & of('ARG', 'LYS', 'ASN', 'GLN', 'TRP')] = ROLE_DONOR
+    role[N & ~bb & of('HIS')] = ROLE_DONOR | ROLE_ACCEPTOR
+    role[O] = ROLE_ACCEPTOR
+    role[O & ~bb & of('SER', 'THR', 'TYR')] = ROLE_DONOR | ROLE_ACCEPTOR
+    role[(elem < 0) | (aa < 0)] = -1
+    if not hydrogens:
+        role[elem == workloads.PROTEIN_ELEMENTS.index(1)] = -1
+    return role
+
+
+class Interactions:
+    """The typed interactions of S frames of B molecules with one pocket (``pocket_interactions``).  Device tensors, frame axis first:
+    ``protein_role`` [N_p] int32 (the table's bits with the hydrophobic bit resolved, -1: takes no part); ``n_donated``, ``n_accepted``,
+    ``n_hbonds``, ``n_hydrophobic`` (pairs), ``n_hb_atoms``, ``n_donors``, ``n_acceptors``, ``n_hydrophobic_atoms`` (ligand atoms)
+    [S, B] int32; ``n_ref_common`` [S, B, 3] int32 or None; ``atom_role``, ``atom_hbonds``, ``atom_hydrophobic`` [S, N_l] int32;
+    ``bits`` [S, B, 3, W] int64 or None (per type, bit j & 63 of word j >> 6: the molecule hits protein atom j); over the included
+    molecules ``kind_hist`` [S, 3, n_kinds] int64 (type by protein kind, ``names``) and ``pocket_freq`` [S, 3, N_p] int32;
+    ``protein_elem`` / ``protein_kind`` [N_p] int32, ``ligand_ptr``.  The types: ``INTERACTION_NAMES``."""
+
+    def __init__(self, r, ligand_ptr, protein_elem, protein_kind, names):
+        for k, t in r.items():
+            setattr(self, k, t)
+        self.ligand_ptr, self.protein_elem, self.protein_kind, self.names = ligand_ptr, protein_elem, protein_kind, tuple(names)
+
+
+def pocket_interactions(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic',
+                        hbond_cutoff=DEFAULT_HBOND_CUTOFF, hydrophobic_cutoff=DEFAULT_HYDROPHOBIC_CUTOFF,
+                        hetero_cutoff=DEFAULT_HETERO_CUTOFF, kinds='residue', hydrogens=False, include=None, ref_bits=None,
+                        return_bits=False, device=None):
+    """Hydrogen bonds and hydrophobic contacts of every molecule of one frame ``[N_l, 3]`` or of a stack ``[S, N_l, 3]`` (arguments as
+    ``bond_graph``) with the pocket ``protein_pos`` [N_p, 3], ``protein_feat`` [N_p, 27] (as ``pocket_contacts``).  Ligand roles: on
+    the bond graph, DONOR an N or O with at least one hydrogen, bonded or implied by its valence deficit (3 - val for N, 2 - val for O);
+    ACCEPTOR an O, or an N without hydrogens and val <= 3; HYDROPHOBIC a C without a bonded N or O, F, Cl.  Protein roles:
+    ``pocket_roles``, and HYDROPHOBIC a carbon without a protein N or O closer than ``hetero_cutoff``.  Ligand donates / accepts:
+    d < ``hbond_cutoff`` between heavy atoms, no angle; hydrophobic: d < ``hydrophobic_cutoff``; d the bond rule's float64 distance.
+    All of it is this project's convention, a heuristic and not perceived chemistry, and not a docking score.  ``include`` [S, B]
+    restricts ``kind_hist`` and ``pocket_freq`` and nothing else; ``ref_bits`` [3, W] int64: the words of a known ligand (``bits`` of
+    a call on it), for ``n_ref_common``.  Molecules of more than 512 atoms are refused.  Returns an ``Interactions``."""
+    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
+    ppos, elem, kind, names = _pocket_arrays((protein_pos, protein_feat), pos.device, kinds, hydrogens)
+    role = torch.from_numpy(pocket_roles(protein_feat, hydrogens)).to(pos.device)
+    if include is not None:
+        include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+    if ref_bits is not None:
+        ref_bits = torch.as_tensor(ref_bits).to(device=pos.device).contiguous()
+    r = capi.interaction_report(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), ppos, elem, kind, role, len(names), hbond_cutoff,
+                                hydrophobic_cutoff, hetero_cutoff, include, ref_bits, True, return_bits)
+    return Interactions(r, ligand_ptr, elem, kind, names)
+
+
+def _popcount(words):
+    """the set bits of int64 words, summed over the last axis"""
+    w = np.ascontiguousarray(words)
+    return np.unpackbits(w.view(np.uint8).reshape(w.shape + (8,)), axis=-1).sum((-1, -2)).astype(np.int64)
+
+
+class InteractionReport:
+    """Per frame (axis 0), over the included molecules (``n_included`` [S] of ``n_samples``): ``sum_hbonds``, ``sum_donated``,
+    ``sum_accepted``, ``sum_hydrophobic`` [S] int64, the pairs; ``n_no_hbond`` [S], the molecules without a hydrogen bond;
+    ``sum_hb_atoms`` of the ``sum_polar_atoms`` [S] ligand atoms that are donor or acceptor; ``kind_hist`` [S, 3, n_kinds] int64 with
+    ``names``; ``pocket_freq`` [S, 3, N_p] int64, the pocket's interaction map, or None for a report merged from several pockets.
+    With a reference ligand ``sum_ref`` [S, 3, 4] -- per pocket and type the mean, the median and the largest recovery n_ref_common /
+    |ref| and the mean Tanimoto n_common / (n_hit + |ref| - n_common) -- over the ``n_ref`` [S, 3] pockets that have them: a
+    reference without an interaction of a type gives no value there, and the summary NaN.  The roles and the cutoffs are this
+    project's conventions (``pocket_interactions``)."""
+
+    def __init__(self, n_included, sum_hbonds, sum_donated, sum_accepted, sum_hydrophobic, n_no_hbond, sum_hb_atoms, sum_polar_atoms,
+                 kind_hist, names, n_samples, pocket_freq=None, sum_ref=None, n_ref=None):
+        i64, f64 = (lambda a: np.asarray(a, dtype=np.int64)), (lambda a: np.asarray(a, dtype=np.float64))
+        self.n_included, self.sum_hbonds, self.sum_donated, self.sum_accepted = i64(n_included), i64(sum_hbonds), i64(sum_donated), i64(sum_accepted)
+        self.sum_hydrophobic, self.n_no_hbond = i64(sum_hydrophobic), i64(n_no_hbond)
+        self.sum_hb_atoms, self.sum_polar_atoms = i64(sum_hb_atoms), i64(sum_polar_atoms)
+        self.kind_hist, self.names = i64(kind_hist), tuple(names)
+        self.n_samples = int(n_samples)
+        self.pocket_freq = None if pocket_freq is None else i64(pocket_freq)
+        self.sum_ref = None if sum_ref is None else f64(sum_ref)
+        self.n_ref = None if n_ref is None else i64(n_ref)
+
+    @classmethod
+    def from_outputs(cls, raw, included, sizes, names, ref_sizes=None):
+        """One pocket: ``raw`` the numpy outputs of capi.interaction_report (n_donated, n_accepted, n_hbonds, n_hydrophobic,
+        n_hb_atoms, atom_role, kind_hist, pocket_freq and, with a reference of ``ref_sizes`` [3] protein atoms hit per type,
+        n_ref_common and bits), ``included`` [S, B] bool, ``sizes`` [B]"""
+        inc = np.asarray(included, dtype=bool)
+        S = inc.shape[0]
+        ptr = np.cumsum([0] + [int(n) for n in sizes])
+        polar = (np.asarray(raw['atom_role']) & (ROLE_DONOR | ROLE_ACCEPTOR)) != 0
+        run = np.concatenate([np.zeros((S, 1), np.int64), np.cumsum(polar, axis=1, dtype=np.int64)], axis=1)
+        n_polar = run[:, ptr[1:]] - run[:, ptr[:-1]]                                # [S, B]
+        tot = lambda x: np.where(inc, np.asarray(x, dtype=np.int64), 0).sum(1)
+        hbonds = np.asarray(raw['n_hbonds'], dtype=np.int64)
+        sum_ref = n_ref = None
+        if ref_sizes is not None:
+            sum_ref, n_ref = np.zeros((S, 3, 4)), np.zeros((S, 3), np.int64)
+            common, hit = np.asarray(raw['n_ref_common'], dtype=np.float64), _popcount(raw['bits']).astype(np.float64)
+            for s in range(S):
+                for t in range(3):
+                    size = float(ref_sizes[t])
+                    if size > 0 and inc[s].any():
+                        c, h = common[s, inc[s], t], hit[s, inc[s], t]
+                        rec, tan = c / size, c / (h + size - c)
+                        sum_ref[s, t] = (rec.sum() / rec.size, np.median(rec), rec.max(), tan.sum() / tan.size)
+                        n_ref[s, t] = 1
+        return cls(inc.sum(1), tot(hbonds), tot(raw['n_donated']), tot(raw['n_accepted']), tot(raw['n_hydrophobic']), (inc & (hbonds == 0)).sum(1),
+                   tot(raw['n_hb_atoms']), tot(n_polar), raw['kind_hist'], names, len(sizes), raw['pocket_freq'], sum_ref, n_ref)
+
+    @classmethod
+    def merged(cls, reports):
+        """Several pockets together: every sum added, frame by frame; the reference values become means over the pockets that have
+        one (the convention of PocketReport).  An interaction map belongs to one pocket: the merged report of several has none."""
+        reports = list(reports)
+        first = reports[0]
+        if any(r.kind_hist.shape != first.kind_hist.shape or r.names != first.names or (r.sum_ref is None) != (first.sum_ref is None)
+               for r in reports):
+            raise ValueError('reports of different frame counts or kinds, or with and without a reference ligand, do not merge')
+        tot = lambda name: sum(getattr(r, name) for r in reports)
+        return cls(tot('n_included'), tot('sum_hbonds'), tot('sum_donated'), tot('sum_accepted'), tot('sum_hydrophobic'), tot('n_no_hbond'),
+                   tot('sum_hb_atoms'), tot('sum_polar_atoms'), tot('kind_hist'), first.names, tot('n_samples'),
+                   first.pocket_freq if len(reports) == 1 else None, None if first.sum_ref is None else tot('sum_ref'),
+                   None if first.sum_ref is None else tot('n_ref'))
+
+    @property
+    def num_frames(self):
+        return self.kind_hist.shape[0]
+
+    @staticmethod
+    def _mean(total, count):
+        return float(total) / int(count) if int(count) else float('nan')
+
+    def mean_hbonds(self, frame=-1):
+        """hydrogen bonds per included molecule; a pair that donates and accepts at once counts once"""
+        return self._mean(self.sum_hbonds[frame], self.n_included[frame])
+
+    def mean_donated(self, frame=-1):
+        return self._mean(self.sum_donated[frame], self.n_included[frame])
+
+    def mean_accepted(self, frame=-1):
+        return self._mean(self.sum_accepted[frame], self.n_included[frame])
+
+    def mean_hydrophobic(self, frame=-1):
+        return self._mean(self.sum_hydrophobic[frame], self.n_included[frame])
+
+    def no_hbond(self, frame=-1):
+        """the share of included molecules without a hydrogen bond"""
+        return self._mean(self.n_no_hbond[frame], self.n_included[frame])
+
+    def polar_in_hbond(self, frame=-1):
+        """the share of the ligands' donor or acceptor atoms that take part in a hydrogen bond; nan without such atoms"""
+        return self._mean(self.sum_hb_atoms[frame], self.sum_polar_atoms[frame])
+
+    def kind_profile(self, kind, frame=-1):
+        """{kind name: share of the pairs of the type} (``kind`` an index or a name of ``INTERACTION_NAMES``), or None without pairs"""
+        t = INTERACTION_NAMES.index(kind) if isinstance(kind, str) else int(kind)
+        h = self.kind_hist[frame, t]
+        return {k: float(x) / float(h.sum()) for k, x in zip(self.names, h)} if h.sum() > 0 else None
+
+    def interaction_frequency(self, frame=-1):
+        """[3, N_p]: the share of the included molecules that hit each protein atom, per type; None for a report of several pockets"""
+        if self.pocket_freq is None:
+            return None
+        n = int(self.n_included[frame])
+        return self.pocket_freq[frame] / float(n) if n else np.full(self.pocket_freq.shape[1:], np.nan)
+
+    def reference_recovery(self, frame=-1):
+        """{'ref_<type>_recovery_mean', '..._recovery_median', '..._recovery_max', 'ref_<type>_tanimoto'} per type, or {} without a
+        reference ligand"""
+        if self.sum_ref is None:
+            return {}
+        keys = ('recovery_mean', 'recovery_median', 'recovery_max', 'tanimoto')
+        return {f'ref_{name}_{k}': self._mean(self.sum_ref[frame, t, c], self.n_ref[frame, t]) for t, name in enumerate(INTERACTION_NAMES)
+                for c, k in enumerate(keys)}
+
+    def summary(self, frame=-1):
+        return dict(mean_hbonds=self.mean_hbonds(frame), mean_donated=self.mean_donated(frame), mean_accepted=self.mean_accepted(frame),
+                    mean_hydrophobic=self.mean_hydrophobic(frame), no_hbond=self.no_hbond(frame), polar_in_hbond=self.polar_in_hbond(frame),
+                    **self.reference_recovery(frame))
+
+    def lines(self, frame=-1, top=3):
+        """the report as printed lines: the summary, then per type the ``top`` residue kinds"""
+        out = [f'{k}:\t{x:.4f}' if x == x else f'{k}:\tNone' for k, x in self.summary(frame).items()]
+        for name in INTERACTION_NAMES:
+            prof = self.kind_profile(name, frame) or {}
+            for k, x in sorted(prof.items(), key=lambda kx: (-kx[1], kx[0]))[:top]:
+                if x > 0:
+                    out.append(f'{name} {k}:\t{x:.4f}')
+        return out
+
+
+def sample_interactions(result, eval_step=-1, include='all', reference_ligand=None, hbond_cutoff=DEFAULT_HBOND_CUTOFF,
+                        hydrophobic_cutoff=DEFAULT_HYDROPHOBIC_CUTOFF, hetero_cutoff=DEFAULT_HETERO_CUTOFF, atom_enc_mode='add_aromatic',
+                        device='cuda'):
+    """Typed pocket interactions of the samples of one pocket (``result`` a loaded ``result_{i}.pt`` dictionary, whose ``'data'`` is
+    the pocket; ``eval_step`` and the packing as ``sample_quality``): per frame the mean hydrogen bonds per molecule and their donated /
+    accepted split, the mean hydrophobic contacts, the share of molecules without a hydrogen bond, the share of polar ligand atoms in
+    one, the residue kinds per type and the pocket's interaction map; with ``reference_ligand`` ``(pos [n, 3], v [n])``, run through
+    the same kernel, the recovery of its interactions per type.  ``include`` as ``sample_rings``.  The roles and cutoffs are
+    conventions (``pocket_interactions``).  A result without a pocket is refused.  Returns an ``InteractionReport``."""
+    data = result.get('data') if isinstance(result, dict) else None
+    if data is None:
+        raise ValueError("the result carries no pocket: sample_interactions needs a result dictionary with its 'data' "
+                         '(results.result_dict), or use SamplePack.interactions(data)')
+    return SamplePack(result, eval_step, atom_enc_mode, device).interactions(data, include, reference_ligand, hbond_cutoff, hydrophobic_cutoff,
+                                                                             hetero_cutoff)

@@ -27,6 +27,12 @@ atom and a protein atom closer than the sum of their van der Waals radii minus 0
 (pairs closer than 4 A), the buried share, the share of poses that touch nothing, the mean smallest distance, the share of contacts
 with the backbone and the most frequent residue kinds -- conventions of this project, not a pose checker's -- and, with the known
 ligand of ``--reference_sdf`` / ``--reference_npz``, how many of its contacts the samples recover.
+``--interactions [--hbond_cutoff X] [--hydrophobic_cutoff X]`` adds the typed interactions with the pocket (quality.sample_interactions),
+over ``--include all`` or ``complete`` samples: the mean hydrogen bonds per molecule (a ligand donor or acceptor and a protein acceptor
+or donor closer than 3.5 A, heavy atom to heavy atom, no angle) with the donated / accepted split, the mean hydrophobic contacts
+(hydrophobic atoms closer than 4.5 A), the share of molecules without a hydrogen bond, the share of polar ligand atoms in one and the
+most frequent residue kinds per type -- the ligand's donors are inferred from the valence deficit, a heuristic of this project and not
+perceived chemistry, and nothing here is a docking score -- and, with the known ligand, the recovery of its interactions per type.
 The fingerprint is this project's own circular one over its bond graph, not RDKit's RDKFingerprint: the numbers compare between
 runs of this tool, not with published tables.  The Jensen-Shannon distances need the reference's empirical distributions: they are
 loaded from ``utils.evaluation`` when the tool runs inside the reference repository (or with it on PYTHONPATH), or from
@@ -83,7 +89,13 @@ def main(argv=None):
     ap.add_argument('--contact_cutoff', type=float, default=quality.DEFAULT_CONTACT_CUTOFF, help='--pocket: a contact is a pair closer than this')
     ap.add_argument('--clash_tolerance', type=float, default=quality.DEFAULT_CLASH_TOLERANCE,
                     help='--pocket: a clash is a pair closer than the sum of the van der Waals radii minus this')
-    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity, --pocket: a known ligand, the first V2000 record of '
+    ap.add_argument('--interactions', action='store_true', help='also the hydrogen bonds and hydrophobic contacts with the pocket (the '
+                    "result file's data; counts under this project's role heuristic, not a score)")
+    ap.add_argument('--hbond_cutoff', type=float, default=quality.DEFAULT_HBOND_CUTOFF,
+                    help='--interactions: a hydrogen bond is a donor - acceptor pair of heavy atoms closer than this')
+    ap.add_argument('--hydrophobic_cutoff', type=float, default=quality.DEFAULT_HYDROPHOBIC_CUTOFF,
+                    help='--interactions: a hydrophobic contact is a pair of hydrophobic atoms closer than this')
+    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity, --pocket, --interactions: a known ligand, the first V2000 record of '
                     'FILE; --geometry: known ligands, every record of FILE')
     ap.add_argument('--reference_npz', type=str, default=None)
     ap.add_argument('--device', type=str, default='cuda')
@@ -111,7 +123,7 @@ def main(argv=None):
     if not files:
         raise SystemExit(f'no result_*.pt under {args.sample_path}')
     print(f'Load generated data done! {len(files)} examples in total.')
-    reports, connectivity, rings, diversity, geometry, pocket = [], [], [], [], [], []
+    reports, connectivity, rings, diversity, geometry, pocket, interactions = [], [], [], [], [], [], []
     graph_include = 'complete' if args.include == 'complete' else 'all'     # 'stable' restricts the pair profiles and atom types only
     for name in files:
         result = torch.load(name, map_location='cpu', weights_only=False)
@@ -128,6 +140,10 @@ def main(argv=None):
             if not isinstance(result, dict) or result.get('data') is None:
                 raise SystemExit(f'{name} carries no pocket (no data): --pocket needs the files of a sampling driver')
             pocket.append(pack.pocket(result['data'], graph_include, reference_ligand, args.contact_cutoff, args.clash_tolerance))
+        if args.interactions:
+            if not isinstance(result, dict) or result.get('data') is None:
+                raise SystemExit(f'{name} carries no pocket (no data): --interactions needs the files of a sampling driver')
+            interactions.append(pack.interactions(result['data'], graph_include, reference_ligand, args.hbond_cutoff, args.hydrophobic_cutoff))
         reports.append(pack.quality(args.include, reference))
     rep = quality.QualityReport.merged(reports)
     print(f'Evaluate done! {rep.n_samples} samples in total.')
@@ -189,6 +205,15 @@ def main(argv=None):
                              kind_hist=dict(zip(poc.names, poc.kind_hist[-1].sum(0).tolist())))
         if eval_step == 'all':
             out['pocket']['curve'] = [nan_none(poc.summary(s)) for s in range(poc.num_frames)]
+    if args.interactions:
+        ia = quality.InteractionReport.merged(interactions)
+        print('\n'.join(ia.lines(-1)))
+        nan_none = lambda d: {k: (None if x != x else x) for k, x in d.items()}
+        out['interactions'] = dict(nan_none(ia.summary(-1)), num_included=int(ia.n_included[-1]), hbond_cutoff=args.hbond_cutoff,
+                                   hydrophobic_cutoff=args.hydrophobic_cutoff,
+                                   kind_hist={t: dict(zip(ia.names, ia.kind_hist[-1, k].tolist())) for k, t in enumerate(quality.INTERACTION_NAMES)})
+        if eval_step == 'all':
+            out['interactions']['curve'] = [nan_none(ia.summary(s)) for s in range(ia.num_frames)]
     result_path = os.path.join(args.sample_path, 'eval_results')
     os.makedirs(result_path, exist_ok=True)
     with open(os.path.join(result_path, 'quality.json'), 'w') as f:

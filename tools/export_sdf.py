@@ -1,7 +1,7 @@
 """Sampled ligands as SD files, without a chemistry toolkit:
 
     python tools/export_sdf.py --sample_path DIR --out DIR [--eval_step -1] [--only-complete] [--largest-fragment] [--ring-aromatic]
-                                [--unique] [--clash-free] [--pocket-clash-free]
+                                [--unique] [--clash-free] [--pocket-clash-free] [--min-hbonds N]
 
 Reads the ``result_{i}.pt`` files a sampling driver wrote (sorted as tools/evaluate_samples.py sorts them), takes the frame
 ``--eval_step`` of every sample (default -1: the final poses), builds the bond graph on the GPU (quality.bond_graph: bonds from the
@@ -21,6 +21,9 @@ checker's); it applies before ``--unique`` chooses among what is left.
 ``--pocket-clash-free`` writes only the samples without a clash with the protein (quality.pocket_contacts on the file's pocket: no
 ligand atom closer to a protein atom than the sum of their van der Waals radii minus 0.5 A; DESIGN.md section 3, "Pocket contacts" --
 again a convention); it combines with ``--clash-free`` and applies before ``--unique`` too.
+``--min-hbonds N`` writes only the samples with at least N hydrogen bonds to the protein (quality.pocket_interactions on the file's
+pocket: donor - acceptor pairs of heavy atoms closer than 3.5 A, the ligand's donors inferred from the valence deficit; DESIGN.md
+section 3, "Pocket interactions" -- a heuristic count, not a score); it combines with the two above and applies before ``--unique``.
 Prints one line per file and returns the counts.
 """
 from __future__ import annotations
@@ -53,6 +56,8 @@ def main(argv=None):
                     'molecule (also with --largest-fragment), taken after --only-complete')
     ap.add_argument('--clash-free', action='store_true', help='only the samples without an internal clash')
     ap.add_argument('--pocket-clash-free', action='store_true', help="only the samples without a clash with the protein (the file's data)")
+    ap.add_argument('--min-hbonds', type=int, default=None, help="only the samples with at least N hydrogen bonds to the protein (the "
+                    "file's data; this project's role heuristic)")
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
     files = result_files(args.sample_path, args.eval_num_examples)
@@ -66,7 +71,7 @@ def main(argv=None):
         pos, v, ptr, sizes = pack.pos, pack.v, pack.ligand_ptr, pack.sizes
         g = quality.bond_graph(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, bond_profiles=(), return_fragments=True,
                                return_bonds=True, rings=args.ring_aromatic, device=args.device)
-        select = chosen = clash_free = pocket_clash_free = None
+        select = chosen = clash_free = pocket_clash_free = enough_hbonds = None
         if args.only_complete:
             chosen = g.complete[0]
         if args.clash_free:
@@ -80,6 +85,13 @@ def main(argv=None):
                                                         atom_enc_mode=args.atom_enc_mode, device=args.device).clash_free[0]
             chosen = pocket_clash_free if chosen is None else chosen & pocket_clash_free
             select = pocket_clash_free.cpu().numpy() & (True if select is None else select)
+        if args.min_hbonds is not None:
+            if not isinstance(result, dict) or result.get('data') is None:
+                raise SystemExit(f'{name} carries no pocket (no data): --min-hbonds needs the files of a sampling driver')
+            enough_hbonds = quality.pocket_interactions(*quality.pocket_of(result['data']), pos, v, ligand_ptr=ptr,
+                                                        atom_enc_mode=args.atom_enc_mode, device=args.device).n_hbonds[0] >= args.min_hbonds
+            chosen = enough_hbonds if chosen is None else chosen & enough_hbonds
+            select = enough_hbonds.cpu().numpy() & (True if select is None else select)
         if args.unique:
             fp = quality.fingerprints(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, device=args.device)
             first = fp.similarity(include=None if chosen is None else chosen[None])['first_equal'][0].cpu().numpy()
@@ -96,6 +108,8 @@ def main(argv=None):
             out[stem]['clash_free'] = int(clash_free.sum())
         if pocket_clash_free is not None:
             out[stem]['pocket_clash_free'] = int(pocket_clash_free.sum())
+        if enough_hbonds is not None:
+            out[stem]['min_hbonds'] = int(enough_hbonds.sum())
     return out
 
 

@@ -1,5 +1,6 @@
 // C ABI of libtargetdiff_hip.so, part 4 of 5: the stateless entry points (graph construction, backbone, denoiser, posterior,
-// likelihood terms, embeddings), the standalone EGNN refine net and the debug hooks.
+// likelihood terms, embeddings), the standalone EGNN refine net and the debug hooks.  td_refine_forward and td_model_forward are: checks,
+// carve, (general graphs) the call's GraphPlan under a PlanGuard, compose / pack, run_blocks (plan.cpp), head / unpack.
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -122,28 +123,16 @@ extern "C" int td_refine_forward(const td_model *m, const float *d_h, const floa
         TD_CHECK_HIP(hipStreamSynchronize(s));
     }
     if (d_out_h != d_h) TD_CHECK_HIP(hipMemcpyAsync(d_out_h, d_h, (size_t)N * TD_H * sizeof(float), hipMemcpyDeviceToDevice, s));
-    float4 *xf = nullptr;
-    if (!default_graph(m->cfg)) {
+    PlanGuard plan{GraphPlan(), s};
+    const bool general = !default_graph(m->cfg);
+    int64_t nl_all = nl;
+    if (general) {
         if (d_out_nbr || d_out_ew) { td_set_error("td_refine_forward: graph / gate outputs exist for the k = 32 kNN graph only (use td_graph_build)"); return TD_EINVAL; }
-        GraphPlan p;
-        int64_t nl_all = 0;
-        if ((rc = plan_from_mask(m->cfg, d_mask_ligand, w.node_ptr, N, B, s, &p, &nl_all)) != TD_OK) return rc;
-        rc = plan_layout(p, w.node_ptr, w.gid, s);
-        // every block: graph + gate from the current coordinates (in w.x4a), then the layer stack (models/uni_transformer.py:306-323)
-        for (int blk = 0; rc == TD_OK && blk < num_blocks(m->cfg); ++blk) {
-            rc = build_general_graph(m, p, w, N, nl_all, max_graph_nodes, s);
-            if (rc == TD_OK) rc = run_backbone(m, w, plan_tab(p), d_out_h, N, nl_all, fix_x, &xf, s, true);
-            if (rc == TD_OK && xf == w.x4b) std::swap(w.x4a, w.x4b);
-        }
-        if (rc == TD_OK) rc = td_launch_unpack_x(xf, N, d_out_x, s);
-        plan_destroy(p, s);
-        return rc;
+        if ((rc = plan_from_mask(m->cfg, d_mask_ligand, w.node_ptr, N, B, s, &plan.p, &nl_all)) != TD_OK) return rc;
+        if ((rc = plan_layout(plan.p, w.node_ptr, w.gid, s)) != TD_OK) return rc;
     }
-    for (int blk = 0; blk < num_blocks(m->cfg); ++blk) {
-        if ((rc = build_default_graph(m, w, N, max_graph_nodes, s)) != TD_OK) return rc;
-        if ((rc = run_backbone(m, w, default_tab(w), d_out_h, N, nl, fix_x, &xf, s, true)) != TD_OK) return rc;
-        if (xf == w.x4b) std::swap(w.x4a, w.x4b);
-    }
+    float4 *xf = nullptr;
+    if ((rc = run_blocks(m, w, general ? &plan.p : nullptr, d_out_h, N, nl_all, fix_x, max_graph_nodes, &xf, s)) != TD_OK) return rc;
     if ((rc = td_launch_unpack_x(xf, N, d_out_x, s)) != TD_OK) return rc;
     if (d_out_nbr) TD_CHECK_HIP(hipMemcpyAsync(d_out_nbr, w.nbr, (size_t)N * TD_K * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (d_out_ew) TD_CHECK_HIP(hipMemcpyAsync(d_out_ew, w.ew, (size_t)N * TD_K * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -172,46 +161,24 @@ extern "C" int td_model_forward(const td_model *m, const float *d_protein_pos, c
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc;
     float *h = d_final_h ? d_final_h : w.h;
-    if (!default_graph(m->cfg)) {
+    PlanGuard plan{GraphPlan(), s};
+    const bool general = !default_graph(m->cfg);
+    if (general) {
         std::vector<int32_t> hp, hl;
         if ((rc = fetch_ptrs(d_protein_ptr, d_ligand_ptr, B, hp, hl, s)) != TD_OK) return rc;
-        GraphPlan p;
-        if ((rc = plan_create(m->cfg, hp.data(), hl.data(), B, s, &p)) != TD_OK) return rc;
-        float4 *xg = nullptr;
-        {
-            ProfScope ps(PC_COMPOSE, s);
-            rc = td_launch_compose(m, d_protein_pos, d_protein_v, d_protein_ptr, N_p, d_ligand_pos, d_ligand_v, d_ligand_ptr, N_l, B,
-                                   h, w.x4a, w.node_ptr, w.gid, w.lig_node, p.prot_node, s, d_ligand_graph_bias);
-        }
-        if (rc == TD_OK) rc = plan_layout(p, w.node_ptr, w.gid, s);
-        for (int blk = 0; rc == TD_OK && blk < num_blocks(m->cfg); ++blk) {
-            rc = build_general_graph(m, p, w, N, N_l, max_graph_nodes, s);
-            if (rc == TD_OK) rc = run_backbone(m, w, plan_tab(p), h, N, N_l, fix_x, &xg, s, true);
-            if (rc == TD_OK && xg == w.x4b) std::swap(w.x4a, w.x4b);
-        }
-        if (rc == TD_OK) {
-            ProfScope ps(PC_HEAD, s);
-            rc = td_launch_head(m->head, h, xg, w.lig_node, N_l, m->cfg.ligand_num_classes, d_pred_ligand_pos, d_pred_ligand_v,
-                                d_final_ligand_h, s);
-        }
-        plan_destroy(p, s);
-        return rc;
+        if ((rc = plan_create(m->cfg, hp.data(), hl.data(), B, s, &plan.p)) != TD_OK) return rc;
     }
     {
         ProfScope ps(PC_COMPOSE, s);
-        if ((rc = td_launch_compose(m, d_protein_pos, d_protein_v, d_protein_ptr, N_p, d_ligand_pos, d_ligand_v,
-                                    d_ligand_ptr, N_l, B, h, w.x4a, w.node_ptr, w.gid, w.lig_node, nullptr, s, d_ligand_graph_bias)) != TD_OK)
-            return rc;
+        if ((rc = td_launch_compose(m, d_protein_pos, d_protein_v, d_protein_ptr, N_p, d_ligand_pos, d_ligand_v, d_ligand_ptr, N_l, B, h,
+                                    w.x4a, w.node_ptr, w.gid, w.lig_node, plan.p.prot_node, s, d_ligand_graph_bias)) != TD_OK) return rc;
     }
+    if (general && (rc = plan_layout(plan.p, w.node_ptr, w.gid, s)) != TD_OK) return rc;
     float4 *xf = nullptr;
-    for (int blk = 0; blk < num_blocks(m->cfg); ++blk) {
-        if ((rc = build_default_graph(m, w, N, max_graph_nodes, s)) != TD_OK) return rc;
-        if ((rc = run_backbone(m, w, default_tab(w), h, N, N_l, fix_x, &xf, s, true)) != TD_OK) return rc;
-        if (xf == w.x4b) std::swap(w.x4a, w.x4b);
-    }
+    if ((rc = run_blocks(m, w, general ? &plan.p : nullptr, h, N, N_l, fix_x, max_graph_nodes, &xf, s)) != TD_OK) return rc;
     ProfScope ps(PC_HEAD, s);
-    return td_launch_head(m->head, h, xf, w.lig_node, N_l, m->cfg.ligand_num_classes, d_pred_ligand_pos,
-                          d_pred_ligand_v, d_final_ligand_h, s);
+    return td_launch_head(m->head, h, xf, w.lig_node, N_l, m->cfg.ligand_num_classes, d_pred_ligand_pos, d_pred_ligand_v,
+                          d_final_ligand_h, s);
 }
 
 namespace tdapi {

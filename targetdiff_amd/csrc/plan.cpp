@@ -1,5 +1,6 @@
-// C ABI of libtargetdiff_hip.so, part 3 of 5: workspace carving, the layer sequence of one denoiser evaluation (shared by the stateless
-// entry points and the sampling session) and the chunked layout of general graphs (GraphPlan).
+// C ABI of libtargetdiff_hip.so, part 3 of 5: workspace carving, the launch sequence of one denoiser evaluation, each part written once
+// and shared by the stateless entry points and the sampling session -- run_blocks (per block: graph + gate, layers, buffer swap),
+// run_backbone (the layer loop), x2h_stage / h2x_project + h2x_attend (one stage) -- and the chunked layout of general graphs (GraphPlan).
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -37,29 +38,49 @@ Workspace carve(char *base, int64_t N, int64_t B, int64_t Nl) {
     return w;
 }
 
-
-// lig / Nl (x2h passes): the ligand rows of the batch, all of them among `rows`
-int key_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const float *ew, const int32_t *nbr,
-             const float *P, const float *q, const int32_t *rows, const int32_t *count_ptr, int64_t count, float *alpha, hipStream_t s,
-             const int32_t *lig, int64_t Nl, bool h2x_stage) {
-    return td_launch_edge_key16(mlp, L, x4, nbr, ew, P, q, rows, count_ptr, count, alpha, s, h2x_stage, gt.cptr, lig, Nl, gt.cpn_p);
+// lig / Nl (x2h passes): the ligand rows of the batch, all of them among the selected rows (every row list of a step contains the ligand atoms)
+int key_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const float *P, const float *q, const RowSel &r,
+             hipStream_t s, const int32_t *lig, int64_t Nl, bool h2x_stage) {
+    return td_launch_edge_key16(mlp, L, x4, gt.nbr, gt.ew, P, q, r.rows, r.count_ptr, r.count, gt.alpha, s, h2x_stage, gt.cptr, lig, Nl, gt.cpn_p);
 }
-// lig / Nl: the ligand rows of the batch (all of them are among `rows`: every row list of a step contains the ligand atoms)
-int value_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const int32_t *nbr, const float *P,
-               const int32_t *rows, const int32_t *count_ptr, int64_t count, float *h, const float *alpha, const int32_t *lig,
-               int64_t Nl, hipStream_t s, float *out) {
-    return td_launch_edge_value16(mlp, L, x4, nbr, P, rows, count_ptr, count, h, alpha, lig, Nl, s, gt.cptr, gt.cpn_p,
+int value_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const float *P, const RowSel &r, float *h,
+               const int32_t *lig, int64_t Nl, hipStream_t s, float *out) {
+    return td_launch_edge_value16(mlp, L, x4, gt.nbr, P, r.rows, r.count_ptr, r.count, h, gt.alpha, lig, Nl, s, gt.cptr, gt.cpn_p,
                                   lig ? gt.NCl : 0, gt.mixed, out, L.gate_m);
 }
 
-// h2x stage, projections in one launch: src-side (k_j, v_j) of the nodes a ligand atom can see -- `hop_rows` (the
-// ligand atoms and their neighbours, fixed for the step) when the caller has the list, every node otherwise -- plus, as
-// a second segment, the dst-side projections and queries of the ligand atoms
-int h2x_project(const TdLayer &L, Workspace &w, float *h, int64_t N, int64_t Nl, float *P, float *q,
-                const int32_t *hop_rows, const int32_t *hop_count, hipStream_t s) {
+// One x2h stage of layer L on the rows a.rows: the projections (unless they are in place), the stage's own gate (ew_net_type 'r' / none:
+// from the layer's coordinates, every row), key pass, value pass into h, node_output (x2h_out_fc) on every row.
+int x2h_stage(const TdLayer &L, const GraphTab &gt, const float4 *xc, float *h, int64_t N, const X2hStage &a, hipStream_t s) {
+    int rc;
+    const float *h_in = a.h_in ? a.h_in : h;
+    if (a.project) {
+        ProfScope ps(PC_NODE, s, a.scoped);
+        if ((rc = td_launch_node_proj(L.nodeX2h, h_in, a.proj.count, a.proj.rows, 0x1f, a.P, a.q, s, a.proj.count_ptr)) != TD_OK) return rc;
+    }
+    if (L.ew_x2h) {
+        ProfScope ps(PC_GATE, s, a.scoped);
+        if ((rc = td_launch_layer_gate(L.ew_x2h, L.offsets, L.coeff, xc, gt.nbr, N, gt.ew, s)) != TD_OK) return rc;
+    }
+    { ProfScope ps(PC_X2H_K, s, a.scoped); if ((rc = key_pass(L.hk, L, xc, gt, a.P, a.q, a.rows, s, a.lig, a.Nl)) != TD_OK) return rc; }
+    if (h_in != h) TD_CHECK_HIP(hipMemcpyAsync(h, h_in, (size_t)N * TD_H * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // x2h_out_fc: the attention output goes to q (the queries are spent once the key pass is done) without the residual, and
+    // node_output([output | h]) + h follows on every row
+    float *att_out = L.nodeOut.B ? a.q : nullptr;
+    { ProfScope ps(PC_X2H_V, s, a.scoped); if ((rc = value_pass(L.hv, L, xc, gt, a.P, a.rows, h, a.lig, a.Nl, s, att_out)) != TD_OK) return rc; }
+    if (att_out) {
+        ProfScope ps(PC_NODE, s, a.scoped);
+        if ((rc = td_launch_node_output(L.nodeOut, att_out, h, N, s)) != TD_OK) return rc;
+    }
+    return TD_OK;
+}
+
+// h2x stage, projections in one launch: src-side (k_j, v_j) of the nodes a ligand atom can see -- `hop` (the ligand atoms and their
+// neighbours, fixed for the step) when the caller has the list, every node otherwise -- plus, as a second segment, the dst-side
+// projections and queries of the ligand atoms
+int h2x_project(const TdLayer &L, Workspace &w, float *h, int64_t Nl, float *P, float *q, const RowSel &hop, hipStream_t s) {
     ProfScope ps(PC_NODE, s);
-    if (hop_rows) return td_launch_node_proj(L.nodeH2x, h, N, hop_rows, 0x0a, P, q, s, hop_count, w.lig_node, Nl, 0x15);
-    return td_launch_node_proj(L.nodeH2x, h, N, nullptr, 0x0a, P, q, s, nullptr, w.lig_node, Nl, 0x15);
+    return td_launch_node_proj(L.nodeH2x, h, hop.count, hop.rows, 0x0a, P, q, s, hop.count_ptr, w.lig_node, Nl, 0x15);
 }
 
 // attention over the ligand atoms' edges and the coordinate update xc -> xn.  Rows of several chunks (general graphs) take the
@@ -74,124 +95,82 @@ int h2x_attend(const td_model *m, const TdLayer &L, Workspace &w, const GraphTab
     }
     {
         ProfScope ps(PC_H2X_K, s);
-        if ((rc = key_pass(L.xk, L, xc, gt, gt.ew, gt.nbr, P, q, w.lig_node, nullptr, Nl, gt.alpha, s, nullptr, 0, true)) != TD_OK) return rc;
+        if ((rc = key_pass(L.xk, L, xc, gt, P, q, RowSel{w.lig_node, nullptr, Nl}, s, nullptr, 0, true)) != TD_OK) return rc;
     }
     ProfScope ps(PC_H2X_V, s);
     return td_launch_edge_xv16(L.xv, L, xc, xn, gt.nbr, P, w.lig_node, Nl, gt.alpha, s, gt.cptr);
 }
 
-
-int run_backbone_stages(const td_model *m, Workspace &w, const GraphTab &gt, float *h, int64_t N, int64_t Nl, int fix_x,
-                        float4 **x_final, hipStream_t s, bool init_xn);
-
-int run_backbone(const td_model *m, Workspace &w, const GraphTab &gt, float *h, int64_t N, int64_t Nl, int fix_x,
-                 float4 **x_final, hipStream_t s, bool init_xn, bool layer0_x2h_done,
-                 const int32_t *hop_rows, const int32_t *hop_count, int hop_levels, const FwdReach *fwd) {
-    int rc;
-    if (stage_rows(m->cfg) > 1 || m->cfg.num_x2h > 1 || m->cfg.num_h2x > 1) return run_backbone_stages(m, w, gt, h, N, Nl, fix_x, x_final, s, init_xn);
-    const int Lc = m->cfg.num_layers;
-    // row list of receptive-field level k (1-based); nullptr = every row
-    auto level_rows = [&](int k) -> const int32_t * { return (hop_rows && k <= hop_levels) ? hop_rows + (size_t)(k - 1) * N : nullptr; };
-    auto level_count = [&](int k) -> const int32_t * { return (hop_rows && k <= hop_levels) ? hop_count + (k - 1) : nullptr; };
-    float4 *xc = w.x4a, *xn = w.x4b;
-    const bool do_h2x = !fix_x && Nl > 0;
-    if (do_h2x && init_xn) TD_CHECK_HIP(hipMemcpyAsync(xn, xc, (size_t)N * sizeof(float4), hipMemcpyDeviceToDevice, s));
-    // Sampling session: only ligand outputs are consumed, so the layer e from the end updates receptive-field level e + 1
-    // only, and its projections are needed on level e + 2 (those rows and their neighbours).
-    auto proj_rows = [&](int l) -> const int32_t * { return l > 0 ? level_rows(Lc - 1 - l + 2) : nullptr; };
-    auto proj_count = [&](int l) -> const int32_t * { return l > 0 ? level_count(Lc - 1 - l + 2) : nullptr; };
-    bool proj_done = false;        // this layer's x2h-stage projections rode in the previous layer's paired launch
-    const bool sync = m->cfg.sync_twoup != 0;
-    for (int l = 0; l < Lc; ++l) {
-        const TdLayer &L = m->layers[l];
-        if (!(l == 0 && layer0_x2h_done)) {
-            const int e = Lc - 1 - l;
-            const int32_t *rws = l > 0 ? level_rows(e + 1) : nullptr, *cnt = l > 0 ? level_count(e + 1) : nullptr;
-            const bool use_fwd = fwd && l == 1 && !rws;
-            if (use_fwd) { rws = fwd->rows; cnt = fwd->counts; }
-            if (sync && do_h2x) {
-                // sync_twoup: the h2x stage reads the layer's input features, i.e. the h this stage's projections are taken from: both
-                // stages' projections in one launch, before the value pass overwrites h
-                ProfScope ps(PC_NODE, s);
-                if ((rc = td_launch_node_proj_pair(L.nodeH2x, level_rows(1), level_count(1), w.lig_node, Nl, w.Px, w.qx, L.nodeX2h,
-                                                   proj_rows(l), proj_count(l), w.P, w.q, h, N, s)) != TD_OK) return rc;
-            } else if (!proj_done) {
-                ProfScope ps(PC_NODE, s);
-                if ((rc = td_launch_node_proj(L.nodeX2h, h, N, proj_rows(l), 0x1f, w.P, w.q, s, proj_count(l))) != TD_OK) return rc;
-            }
-            proj_done = false;
-            if (L.ew_x2h) {          // ew_net_type 'r' / none: this stage's own gate from the layer's coordinates (no caching: every row)
-                ProfScope ps(PC_GATE, s);
-                if ((rc = td_launch_layer_gate(L.ew_x2h, L.offsets, L.coeff, xc, gt.nbr, N, gt.ew, s)) != TD_OK) return rc;
-            }
-            { ProfScope ps(PC_X2H_K, s); if ((rc = key_pass(L.hk, L, xc, gt, gt.ew, gt.nbr, w.P, w.q, rws, cnt, N, gt.alpha, s, w.lig_node, Nl)) != TD_OK) return rc; }
-            // x2h_out_fc: the attention output goes to w.q (the queries are spent once the key pass is done) without the residual, and
-            // node_output([output | h]) + h follows on every row
-            float *att_out = L.nodeOut.B ? w.q : nullptr;
-            { ProfScope ps(PC_X2H_V, s); if ((rc = value_pass(L.hv, L, xc, gt, gt.nbr, w.P, rws, cnt, N, h, gt.alpha, w.lig_node, Nl, s, att_out)) != TD_OK) return rc; }
-            if (att_out) {
-                ProfScope ps(PC_NODE, s);
-                if ((rc = td_launch_node_output(L.nodeOut, att_out, h, N, s)) != TD_OK) return rc;
-            }
-            if (use_fwd && (rc = td_launch_restore_rows(fwd->rest, fwd->counts + 1, N, fwd->hs, h, s, w.gid, w.node_ptr, fwd->cbase)) != TD_OK) return rc;
-        }
-        if (!do_h2x) continue;
-        if (sync) {
-            // (projections taken at the top of the layer)
-        } else if (l + 1 < Lc) {
-            // the h2x stage of this layer and the x2h stage of the next project the same h: one launch
-            ProfScope ps(PC_NODE, s);
-            if ((rc = td_launch_node_proj_pair(L.nodeH2x, level_rows(1), level_count(1), w.lig_node, Nl, w.Px, w.qx,
-                                               m->layers[l + 1].nodeX2h, proj_rows(l + 1), proj_count(l + 1), w.P, w.q, h, N,
-                                               s)) != TD_OK) return rc;
-            proj_done = true;
-        } else {
-            if ((rc = h2x_project(L, w, h, N, Nl, w.Px, w.qx, level_rows(1), level_count(1), s)) != TD_OK) return rc;
-        }
-        if (L.ew_h2x) {              // the h2x stage's own gate, from the same (not yet updated) coordinates
-            ProfScope ps(PC_GATE, s);
-            if ((rc = td_launch_layer_gate(L.ew_h2x, L.offsets, L.coeff, xc, gt.nbr, N, gt.ew, s)) != TD_OK) return rc;
-        }
-        if ((rc = h2x_attend(m, L, w, gt, Nl, xc, xn, w.Px, w.qx, s)) != TD_OK) return rc;
-        float4 *t = xc; xc = xn; xn = t;
-    }
-    *x_final = xc;
-    return TD_OK;
-}
-
-// The same on a model with several stages per layer (num_x2h / num_h2x != 1; models/uni_transformer.py:190-206): the x2h stages of a layer one
-// after the other on the layer's start coordinates, then its h2x stages, each on the coordinates the previous one left and all on the last
-// x2h stage's features.  Every stage takes its own projections (nothing is fused across stages); every row, no caching.
-int run_backbone_stages(const td_model *m, Workspace &w, const GraphTab &gt, float *h, int64_t N, int64_t Nl, int fix_x,
-                        float4 **x_final, hipStream_t s, bool init_xn) {
+// A layer is NX x2h stages, one after the other on the layer's start coordinates, then NH h2x stages, each on the coordinates the previous one
+// left and all on the last x2h stage's features (models/uni_transformer.py:190-206); stage i of layer l is m->layers[l * M + i].  With one
+// stage of each kind (M == 1, the live architecture) projections are fused across stages -- the h2x stage of a layer and the x2h stage of
+// the next project the same h: one pair launch; sync_twoup: both stages of a layer project its input features -- and a caching session's
+// row lists prune the layers from the end.  Several stages per layer: every stage takes its own projections, every row.
+int run_backbone(const td_model *m, Workspace &w, const GraphTab &gt, float *h, int64_t N, int64_t Nl, int fix_x, float4 **x_final,
+                 hipStream_t s, const CachedStep &cs) {
     int rc;
     const int Lc = m->cfg.num_layers, NX = num_x2h(m->cfg), NH = num_h2x(m->cfg), M = stage_rows(m->cfg);
+    const bool one = M == 1, sync = one && m->cfg.sync_twoup != 0;
+    const int32_t *hop_rows = one ? cs.hop_rows : nullptr;
+    // row list of receptive-field level k (1-based); every row without one
+    const RowSel every{nullptr, nullptr, N};
+    auto level = [&](int k) { return (hop_rows && k <= cs.hop_levels) ? RowSel{hop_rows + (size_t)(k - 1) * N, cs.hop_count + (k - 1), N} : every; };
+    // Sampling session: only ligand outputs are consumed, so the layer e from the end updates receptive-field level e + 1
+    // only, and its projections are needed on level e + 2 (those rows and their neighbours).
+    auto att_rows = [&](int l) { return l > 0 ? level(Lc - 1 - l + 1) : every; };
+    auto proj_rows = [&](int l) { return l > 0 ? level(Lc - 1 - l + 2) : every; };
     float4 *xc = w.x4a, *xn = w.x4b;
     const bool do_h2x = !fix_x && Nl > 0;
-    if (do_h2x && init_xn) TD_CHECK_HIP(hipMemcpyAsync(xn, xc, (size_t)N * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    if (do_h2x && cs.init_xn) TD_CHECK_HIP(hipMemcpyAsync(xn, xc, (size_t)N * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    const RowSel hop1 = level(1);
+    // the projections of an h2x stage (hx) and of an x2h stage (nx, on the rows pr) from the same h: one launch
+    auto project_pair = [&](const TdLayer &hx, const TdLayer &nx, const RowSel &pr) {
+        ProfScope ps(PC_NODE, s);
+        return td_launch_node_proj_pair(hx.nodeH2x, hop1.rows, hop1.count_ptr, w.lig_node, Nl, w.Px, w.qx, nx.nodeX2h, pr.rows, pr.count_ptr,
+                                        w.P, w.q, h, N, s);
+    };
+    bool proj_done = false;        // this layer's x2h-stage projections rode in the previous layer's paired launch
     for (int l = 0; l < Lc; ++l) {
         for (int i = 0; i < NX; ++i) {
+            if (l == 0 && one && cs.layer0_x2h_done) continue;
             const TdLayer &L = m->layers[(size_t)l * M + i];
-            { ProfScope ps(PC_NODE, s); if ((rc = td_launch_node_proj(L.nodeX2h, h, N, nullptr, 0x1f, w.P, w.q, s, nullptr)) != TD_OK) return rc; }
-            if (L.ew_x2h) { ProfScope ps(PC_GATE, s); if ((rc = td_launch_layer_gate(L.ew_x2h, L.offsets, L.coeff, xc, gt.nbr, N, gt.ew, s)) != TD_OK) return rc; }
-            { ProfScope ps(PC_X2H_K, s); if ((rc = key_pass(L.hk, L, xc, gt, gt.ew, gt.nbr, w.P, w.q, nullptr, nullptr, N, gt.alpha, s, w.lig_node, Nl)) != TD_OK) return rc; }
-            float *att_out = L.nodeOut.B ? w.q : nullptr;
-            { ProfScope ps(PC_X2H_V, s); if ((rc = value_pass(L.hv, L, xc, gt, gt.nbr, w.P, nullptr, nullptr, N, h, gt.alpha, w.lig_node, Nl, s, att_out)) != TD_OK) return rc; }
-            if (att_out) { ProfScope ps(PC_NODE, s); if ((rc = td_launch_node_output(L.nodeOut, att_out, h, N, s)) != TD_OK) return rc; }
+            X2hStage a;
+            a.P = w.P; a.q = w.q; a.lig = w.lig_node; a.Nl = Nl;
+            a.rows = att_rows(l);
+            a.proj = proj_rows(l);
+            const bool use_fwd = one && cs.fwd && l == 1 && !a.rows.rows;
+            if (use_fwd) a.rows = RowSel{cs.fwd->rows, cs.fwd->counts, N};
+            // sync_twoup: the h2x stage reads the layer's input features, i.e. the h this stage's projections are taken from: both
+            // stages' projections in one launch, before the value pass overwrites h
+            if (sync && do_h2x && (rc = project_pair(L, L, a.proj)) != TD_OK) return rc;
+            a.project = !proj_done && !(sync && do_h2x);
+            proj_done = false;
+            if ((rc = x2h_stage(L, gt, xc, h, N, a, s)) != TD_OK) return rc;
+            if (use_fwd && (rc = td_launch_restore_rows(cs.fwd->rest, cs.fwd->counts + 1, N, cs.fwd->hs, h, s, w.gid, w.node_ptr, cs.fwd->cbase)) != TD_OK) return rc;
         }
         if (!do_h2x) continue;
         for (int j = 0; j < NH; ++j) {
             const TdLayer &L = m->layers[(size_t)l * M + j];
-            if ((rc = h2x_project(L, w, h, N, Nl, w.Px, w.qx, nullptr, nullptr, s)) != TD_OK) return rc;
-            if (L.ew_h2x) { ProfScope ps(PC_GATE, s); if ((rc = td_launch_layer_gate(L.ew_h2x, L.offsets, L.coeff, xc, gt.nbr, N, gt.ew, s)) != TD_OK) return rc; }
+            if (sync) {
+                // (projections taken at the top of the layer)
+            } else if (one && l + 1 < Lc) {
+                // the h2x stage of this layer and the x2h stage of the next project the same h
+                if ((rc = project_pair(L, m->layers[l + 1], proj_rows(l + 1))) != TD_OK) return rc;
+                proj_done = true;
+            } else if ((rc = h2x_project(L, w, h, Nl, w.Px, w.qx, hop1, s)) != TD_OK) {
+                return rc;
+            }
+            if (L.ew_h2x) {              // the h2x stage's own gate, from the same (not yet updated) coordinates
+                ProfScope ps(PC_GATE, s);
+                if ((rc = td_launch_layer_gate(L.ew_h2x, L.offsets, L.coeff, xc, gt.nbr, N, gt.ew, s)) != TD_OK) return rc;
+            }
             if ((rc = h2x_attend(m, L, w, gt, Nl, xc, xn, w.Px, w.qx, s)) != TD_OK) return rc;
-            float4 *t = xc; xc = xn; xn = t;
+            std::swap(xc, xn);
         }
     }
     *x_final = xc;
     return TD_OK;
 }
-
 
 // graph + edge gate of a composed batch on the default graph (32-slot rows: k-NN with k <= 32, radius with cap <= 32)
 int build_default_graph(const td_model *m, Workspace &w, int64_t N, int max_graph_nodes, hipStream_t s) {
@@ -208,7 +187,6 @@ int build_default_graph(const td_model *m, Workspace &w, int64_t N, int max_grap
     ProfScope ps(PC_GATE, s);
     return td_launch_gate(m->gate, w.x4a, w.nbr, N, nullptr, nullptr, w.ew, s);
 }
-
 
 // td_debug_fail_alloc: the n-th stream-ordered allocation from now fails (fault injection for the error paths)
 std::atomic<int> g_fail_alloc{0};
@@ -281,7 +259,6 @@ int plan_layout(GraphPlan &p, const int32_t *node_ptr, const int32_t *gid, hipSt
                             p.chunk_node, p.lig_chunks, (int32_t)p.NC, s);
 }
 
-
 // graph + edge gate of a composed batch on a general graph (chunked table of the plan)
 int build_general_graph(const td_model *m, GraphPlan &p, Workspace &w, int64_t N, int64_t Nl, int max_graph_nodes, hipStream_t s) {
     int rc;
@@ -292,6 +269,22 @@ int build_general_graph(const td_model *m, GraphPlan &p, Workspace &w, int64_t N
     }
     ProfScope ps(PC_GATE, s);
     return td_launch_gate(m->gate, w.x4a, p.cnbr, p.NC, nullptr, nullptr, p.ew, s, p.chunk_node);
+}
+
+// Every block of one denoiser evaluation (models/uni_transformer.py:306-323): graph + gate from the current coordinates (in w.x4a), then
+// the layer stack.  A block that ends in x4b hands its coordinates to the next one by swapping the two buffers of `w` (the caller's own
+// copy).  plan: the chunked table of a general graph; nullptr: the workspace's default graph.
+int run_blocks(const td_model *m, Workspace &w, GraphPlan *plan, float *h, int64_t N, int64_t Nl, int fix_x, int max_graph_nodes,
+               float4 **x_final, hipStream_t s) {
+    int rc;
+    const GraphTab gt = plan ? plan_tab(*plan) : default_tab(w);
+    for (int blk = 0; blk < num_blocks(m->cfg); ++blk) {
+        rc = plan ? build_general_graph(m, *plan, w, N, Nl, max_graph_nodes, s) : build_default_graph(m, w, N, max_graph_nodes, s);
+        if (rc != TD_OK) return rc;
+        if ((rc = run_backbone(m, w, gt, h, N, Nl, fix_x, x_final, s)) != TD_OK) return rc;
+        if (*x_final == w.x4b) std::swap(w.x4a, w.x4b);
+    }
+    return TD_OK;
 }
 
 // Plan of a composed batch given as (mask_ligand, node_ptr) -- the refine_net seam: per-graph protein / ligand counts and

@@ -259,8 +259,7 @@ int session_build_static(td_session *S, const float *d_protein_pos, const float 
     const int32_t *set_rows = share ? S->canon_rows : S->prot_node;
     const int64_t set_count = share ? S->static_rows : N_p;
     const size_t nc = S->chunked ? (size_t)S->plan.NC : n;
-    GraphTab gt = session_tab(S);                  // the step's table (alpha is scratch here)
-    GraphTab st = gt;                              // the static table
+    GraphTab st = session_tab(S);                  // the static table: its own nbr / ew, the step's alpha as scratch
     st.nbr = snbr_f; st.ew = ews_f;
     TD_CHECK_HIP(hipMemsetAsync(snbr_f, 0xff, nc * TD_K * 4, s));
     if (S->chunked) {
@@ -276,17 +275,16 @@ int session_build_static(td_session *S, const float *d_protein_pos, const float 
         if ((rc = td_launch_knn_static(w.x4a, w.node_ptr, w.gid, set_rows, set_count, S->max_graph_nodes, snbr_f, skeys_f, s, m->cfg.knn)) != TD_OK) return rc;
         if ((rc = td_launch_gate(m->gate, w.x4a, snbr_f, set_count, set_rows, nullptr, ews_f, s)) != TD_OK) return rc;
     }
-    const TdLayer &L0 = m->layers[0];
-    if ((rc = td_launch_node_proj(L0.nodeX2h, h0_f, N, nullptr, 0x1f, S->P0, S->q0, s)) != TD_OK) return rc;
-    if ((rc = key_pass(L0.hk, L0, w.x4a, st, st.ew, st.nbr, S->P0, S->q0, set_rows, nullptr, set_count, gt.alpha, s)) != TD_OK) return rc;
-    TD_CHECK_HIP(hipMemcpyAsync(h1_f, h0_f, n * TD_H * 4, hipMemcpyDeviceToDevice, s));
-    if ((rc = value_pass(L0.hv, L0, w.x4a, st, st.nbr, S->P0, set_rows, nullptr, set_count, h1_f, gt.alpha, nullptr, 0, s)) != TD_OK) return rc;
+    // (no profile scopes: set-up; the rows' input features stay -- h0 / h1s are tables of their own)
+    X2hStage a;
+    a.P = S->P0; a.q = S->q0; a.scoped = false;
+    a.proj = RowSel{nullptr, nullptr, N};
+    a.rows = RowSel{set_rows, nullptr, set_count};
+    a.h_in = h0_f;
+    if ((rc = x2h_stage(m->layers[0], st, w.x4a, h1_f, N, a, s)) != TD_OK) return rc;
     if (S->use_fwd) {      // layer-1 x2h output of the protein-only graph (valid wherever the ligand is two hops away)
-        const TdLayer &L1 = m->layers[1];
-        if ((rc = td_launch_node_proj(L1.nodeX2h, h1_f, N, nullptr, 0x1f, w.P, w.q, s)) != TD_OK) return rc;
-        if ((rc = key_pass(L1.hk, L1, w.x4a, st, st.ew, st.nbr, w.P, w.q, set_rows, nullptr, set_count, gt.alpha, s)) != TD_OK) return rc;
-        TD_CHECK_HIP(hipMemcpyAsync(h2_f, h1_f, n * TD_H * 4, hipMemcpyDeviceToDevice, s));
-        if ((rc = value_pass(L1.hv, L1, w.x4a, st, st.nbr, w.P, set_rows, nullptr, set_count, h2_f, gt.alpha, nullptr, 0, s)) != TD_OK) return rc;
+        a.P = w.P; a.q = w.q; a.h_in = h1_f;
+        if ((rc = x2h_stage(m->layers[1], st, w.x4a, h2_f, N, a, s)) != TD_OK) return rc;
     }
     if (share) {           // the canonical rows of the scratch tables -> the compact shared tables
         if ((rc = td_launch_compact_rows(skeys_f, set_rows, set_count, TD_K * 8, S->skeys, s)) != TD_OK) return rc;
@@ -372,15 +370,8 @@ extern "C" int td_session_forward(td_session *S, const float *d_ligand_pos, cons
             if ((rc = td_launch_ligand_update(m, d_ligand_pos, d_ligand_v, w.lig_node, Nl, w.h, w.x4a, s, nullptr, d_ligand_graph_bias, w.gid)) != TD_OK) return rc;
         }
         float4 *xg = nullptr;
-        Workspace wb = w;             // (a block that ends in x4b hands its coordinates to the next one by swapping the two buffers)
-        rc = TD_OK;
-        for (int blk = 0; rc == TD_OK && blk < num_blocks(m->cfg); ++blk) {
-            if (S->chunked) rc = build_general_graph(m, S->plan, wb, N, Nl, S->max_graph_nodes, s);
-            else rc = build_default_graph(m, wb, N, S->max_graph_nodes, s);          // 32-slot rows
-            if (rc == TD_OK) rc = run_backbone(m, wb, gt, wb.h, N, Nl, 0, &xg, s, true);
-            if (rc == TD_OK && xg == wb.x4b) std::swap(wb.x4a, wb.x4b);
-        }
-        if (rc != TD_OK) return rc;
+        Workspace wb = w;             // (the block loop swaps x4a / x4b of its workspace: the session's own stays as it is)
+        if ((rc = run_blocks(m, wb, S->chunked ? &S->plan : nullptr, wb.h, N, Nl, 0, S->max_graph_nodes, &xg, s)) != TD_OK) return rc;
         ProfScope ps(PC_HEAD, s);
         return td_launch_head(m->head, w.h, xg, w.lig_node, Nl, m->cfg.ligand_num_classes, d_pred_ligand_pos, d_pred_ligand_v,
                               d_final_ligand_h, s);
@@ -447,18 +438,22 @@ extern "C" int td_session_forward(td_session *S, const float *d_ligand_pos, cons
             rc = td_launch_gate(m->gate, w.x4a, gt.nbr, N, S->dirty_rows, S->dirty_count, gt.ew, s);
         if (rc != TD_OK) return rc;
     }
-    const TdLayer &L0 = m->layers[0];
     {   // layer 0, x2h: only ligand rows need new projections, only dirty rows need the attention passes
-        { ProfScope ps(PC_NODE, s); if ((rc = td_launch_node_proj(L0.nodeX2h, w.h, Nl, w.lig_node, 0x1f, S->P0, S->q0, s)) != TD_OK) return rc; }
-        { ProfScope ps(PC_X2H_K, s); if ((rc = key_pass(L0.hk, L0, w.x4a, gt, gt.ew, gt.nbr, S->P0, S->q0, S->dirty_rows, S->dirty_count, N, gt.alpha, s, w.lig_node, Nl)) != TD_OK) return rc; }
-        { ProfScope ps(PC_X2H_V, s); if ((rc = value_pass(L0.hv, L0, w.x4a, gt, gt.nbr, S->P0, S->dirty_rows, S->dirty_count, N, w.h, gt.alpha, w.lig_node, Nl, s)) != TD_OK) return rc; }
+        X2hStage a;
+        a.P = S->P0; a.q = S->q0; a.lig = w.lig_node; a.Nl = Nl;
+        a.proj = RowSel{w.lig_node, nullptr, Nl};
+        a.rows = RowSel{S->dirty_rows, S->dirty_count, N};
+        if ((rc = x2h_stage(m->layers[0], gt, w.x4a, w.h, N, a, s)) != TD_OK) return rc;
     }
     // rows the last layer still has to update (S->clean is free again after the dirty-row compaction: reuse as flags)
     if (!lists_done && (rc = td_launch_hop_levels(w.lig_node, Nl, w.nbr, N, S->clean, S->hop_rows, S->hop_count, S->hop_levels, s, true)) != TD_OK) return rc;
     float4 *xf = nullptr;
     const FwdReach fwd{S->fwd_rows, S->fwd_rest, S->fwd_counts, S->h2s, S->cbase};
-    if ((rc = run_backbone(m, w, gt, w.h, N, Nl, 0, &xf, s, false, true, S->hop_rows, S->hop_count, S->hop_levels,
-                           S->use_fwd ? &fwd : nullptr)) != TD_OK) return rc;
+    CachedStep cs;
+    cs.init_xn = false; cs.layer0_x2h_done = true;
+    cs.hop_rows = S->hop_rows; cs.hop_count = S->hop_count; cs.hop_levels = S->hop_levels;
+    cs.fwd = S->use_fwd ? &fwd : nullptr;
+    if ((rc = run_backbone(m, w, gt, w.h, N, Nl, 0, &xf, s, cs)) != TD_OK) return rc;
     ProfScope ps(PC_HEAD, s);
     return td_launch_head(m->head, w.h, xf, w.lig_node, Nl, m->cfg.ligand_num_classes, d_pred_ligand_pos,
                           d_pred_ligand_v, d_final_ligand_h, s);

@@ -32,7 +32,8 @@ struct Profiler {
 extern Profiler g_prof;
 struct ProfScope {
     int cls; hipStream_t s; bool on; hipEvent_t e0 = nullptr;
-    ProfScope(int c, hipStream_t st) : cls(c), s(st), on((g_prof.mask.load(std::memory_order_relaxed) >> c) & 1u) {
+    // wanted = false: a launch site that takes no scope (the set-up of a session's static tables)
+    ProfScope(int c, hipStream_t st, bool wanted = true) : cls(c), s(st), on(wanted && ((g_prof.mask.load(std::memory_order_relaxed) >> c) & 1u)) {
         if (on) { e0 = g_prof.get(); (void)hipEventRecord(e0, s); }
     }
     ~ProfScope() {
@@ -147,12 +148,43 @@ struct GraphTab {
     const int32_t *mixed;    // device count of the rows that see both source classes (a session's dirty rows), or nullptr
 };
 
+// The rows a launch works on: a device list with its device count (at most `count` rows), a list of `count` rows (count_ptr == nullptr),
+// or every row 0 .. count - 1 (rows == nullptr).
+struct RowSel {
+    const int32_t *rows, *count_ptr;
+    int64_t count;
+};
+
 // Sampling session, layer 1: rows outside the ligand's one-hop forward reach keep the protein-only graph's layer-1
 // output (`hs`), so the attention passes run on `rows` only and `rest` is restored from the cache afterwards.
 struct FwdReach {
     const int32_t *rows, *rest, *counts;     // counts[0] = |rows|, counts[1] = |rest|
     const float *hs;
     const int32_t *cbase = nullptr;          // hs is a compact per-pocket table (session.cpp): row i of graph g = cbase[g] + (i - node_ptr[g])
+};
+
+// What only a caching session's step sets on the layer sequence; default-constructed: the stateless call.
+struct CachedStep {
+    bool init_xn = true;                     // x4b is not yet a copy of x4a
+    bool layer0_x2h_done = false;            // the session ran layer 0's x2h stage itself (dirty rows only)
+    // hop_rows: hop_levels lists of N entries each, level k = the ligand atoms and their neighbours up to k hops -- the only rows whose
+    // h2x-stage projections (level 1) and last layers' features are ever read when just the ligand outputs are consumed
+    const int32_t *hop_rows = nullptr, *hop_count = nullptr;
+    int hop_levels = 0;
+    const FwdReach *fwd = nullptr;
+};
+
+// One x2h stage (x2h_stage, plan.cpp): where its projections live and which rows it works on.
+struct X2hStage {
+    float *P, *q;                            // the projection buffer pair
+    RowSel rows;                             // rows of the attention passes
+    bool project = true;                     // false: the projections are in place (a pair launch took them, or the session's cache)
+    RowSel proj;                             // rows to project
+    const float *h_in = nullptr;             // features the projections are taken from when they are not h itself: h then starts as a
+                                             // copy of them, made between the two passes (a session's static tables keep every layer's h)
+    const int32_t *lig = nullptr;            // the ligand rows of the batch, all of them among `rows` (nullptr: a protein-only graph)
+    int64_t Nl = 0;
+    bool scoped = true;                      // take the profile scopes
 };
 
 // ------------------------------------------------------------------------------------------ general graphs
@@ -172,29 +204,26 @@ Workspace carve(char *base, int64_t N, int64_t B, int64_t Nl);
 inline GraphTab default_tab(Workspace &w) { return GraphTab{nullptr, w.nbr, w.ew, w.alpha, 1, 0, nullptr}; }
 inline GraphTab plan_tab(const GraphPlan &p) { return GraphTab{p.cptr, p.cnbr, p.ew, p.alpha, p.cpn_p, p.NCl, nullptr}; }
 inline int num_blocks(const td_config &c) { return c.num_blocks > 1 ? c.num_blocks : 1; }
-// lig / Nl (x2h passes): the ligand rows of the batch, all of them among `rows`
-int key_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const float *ew, const int32_t *nbr,
-             const float *P, const float *q, const int32_t *rows, const int32_t *count_ptr, int64_t count, float *alpha, hipStream_t s,
-             const int32_t *lig = nullptr, int64_t Nl = 0, bool h2x_stage = false);
-int value_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const int32_t *nbr, const float *P,
-               const int32_t *rows, const int32_t *count_ptr, int64_t count, float *h, const float *alpha, const int32_t *lig,
-               int64_t Nl, hipStream_t s, float *out = nullptr);
-int h2x_project(const TdLayer &L, Workspace &w, float *h, int64_t N, int64_t Nl, float *P, float *q,
-                const int32_t *hop_rows, const int32_t *hop_count, hipStream_t s);
+// the attention passes of one stage on the table gt (its nbr / ew / alpha; chunked: cptr, cpn_p, NCl); lig / Nl (x2h passes): the ligand
+// rows of the batch, all of them among the selected rows
+int key_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const float *P, const float *q, const RowSel &r,
+             hipStream_t s, const int32_t *lig = nullptr, int64_t Nl = 0, bool h2x_stage = false);
+int value_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const float *P, const RowSel &r, float *h,
+               const int32_t *lig, int64_t Nl, hipStream_t s, float *out = nullptr);
+int x2h_stage(const TdLayer &L, const GraphTab &gt, const float4 *xc, float *h, int64_t N, const X2hStage &a, hipStream_t s);
+int h2x_project(const TdLayer &L, Workspace &w, float *h, int64_t Nl, float *P, float *q, const RowSel &hop, hipStream_t s);
 int h2x_attend(const td_model *m, const TdLayer &L, Workspace &w, const GraphTab &gt, int64_t Nl, float4 *xc, float4 *xn, float *P,
                float *q, hipStream_t s);
-// L x (node_proj, x2h, node_proj, h2x) on a composed batch whose graph (gt.nbr) and edge gate (gt.ew) are in place.  h is
-// updated in place; returns the buffer holding the final coordinates through *x_final.  init_xn: x4b is not yet a copy of x4a.
-// hop_rows (optional, sampling session): the ligand atoms and their neighbours -- the only rows whose h2x-stage projections and
-// last-layer features are ever read when just the ligand outputs are consumed.
-int run_backbone(const td_model *m, Workspace &w, const GraphTab &gt, float *h, int64_t N, int64_t Nl, int fix_x,
-                 float4 **x_final, hipStream_t s, bool init_xn, bool layer0_x2h_done = false,
-                 const int32_t *hop_rows = nullptr, const int32_t *hop_count = nullptr, int hop_levels = 0,
-                 const FwdReach *fwd = nullptr);
+// num_layers x (x2h stages, h2x stages) on a composed batch whose graph (gt.nbr) and edge gate (gt.ew) are in place.  h is updated in
+// place; returns the buffer holding the final coordinates through *x_final.
+int run_backbone(const td_model *m, Workspace &w, const GraphTab &gt, float *h, int64_t N, int64_t Nl, int fix_x, float4 **x_final,
+                 hipStream_t s, const CachedStep &cs = CachedStep());
+// num_blocks x (graph + gate from w.x4a, run_backbone, buffer swap); plan == nullptr: the default graph
+int run_blocks(const td_model *m, Workspace &w, GraphPlan *plan, float *h, int64_t N, int64_t Nl, int fix_x, int max_graph_nodes,
+               float4 **x_final, hipStream_t s);
 // known atoms of a posterior step (scaffold-constrained sampling): a mask needs both arrays and a model with alphas_cumprod; `who`
 // prefixes the error (forward.cpp)
 int check_known_atoms(const char *who, const td_model *m, const uint8_t *d_fixed_mask, const float *d_fixed_pos, const int64_t *d_fixed_v);
-int build_default_graph(const td_model *m, Workspace &w, int64_t N, int max_graph_nodes, hipStream_t s);
 // stream-ordered memory: td_debug_fail_alloc makes the n-th allocation from now fail (fault injection for the error paths)
 extern std::atomic<int> g_fail_alloc;
 hipError_t td_malloc_async(void **p, size_t bytes, hipStream_t s);
@@ -202,9 +231,14 @@ void free_async_or_sync(void *p, hipStream_t s);          // (session.cpp)
 void plan_destroy(GraphPlan &p, hipStream_t s);
 int plan_create(const td_config &c, const int32_t *host_pptr, const int32_t *host_lptr, int64_t B, hipStream_t s, GraphPlan *out);
 int plan_layout(GraphPlan &p, const int32_t *node_ptr, const int32_t *gid, hipStream_t s);
-int build_general_graph(const td_model *m, GraphPlan &p, Workspace &w, int64_t N, int64_t Nl, int max_graph_nodes, hipStream_t s);
 int plan_from_mask(const td_config &c, const uint8_t *d_mask, const int32_t *d_node_ptr, int64_t N, int64_t B, hipStream_t s,
                    GraphPlan *out, int64_t *nl_out);
+// the GraphPlan of a stateless call: freed in stream order on every way out
+struct PlanGuard {
+    GraphPlan p;
+    hipStream_t s;
+    ~PlanGuard() { plan_destroy(p, s); }
+};
 int fetch_ptrs(const int32_t *d_a, const int32_t *d_b, int64_t B, std::vector<int32_t> &a, std::vector<int32_t> &b, hipStream_t s);
 // stream-ordered scratch of one call: every block taken so far is given back on every exit path (a failing second or third
 // allocation used to leak the earlier ones)

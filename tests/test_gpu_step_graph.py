@@ -338,6 +338,34 @@ def test_every_failing_allocation_of_a_session_is_reported_and_harmless(state_di
         assert len(got[key]) == 4 and torch.equal(torch.stack(got[key]), torch.stack(want[key])), key
 
 
+def test_failing_plan_allocation_of_a_stateless_forward_is_reported_and_harmless(state_dict):
+    """A stateless td_model_forward on a general graph (k = 48) builds and frees one GraphPlan per call: when the plan's block cannot be
+    allocated the call reports hipMallocAsync, and the next call gives the bits of a call before which nothing was armed."""
+    from oracle import weights
+    from oracle.make_golden import small_batch
+    from targetdiff_amd import capi
+    from targetdiff_amd.models import ScorePosNet3D
+    dev = _dev()
+    lib = capi.load_library()
+    m = ScorePosNet3D(dict(weights.DEFAULT_MODEL_CONFIG, knn=48), 27, 13)
+    m.load_state_dict(state_dict, strict=False)
+    m = m.to(dev).eval()
+    b, lpos, lv = small_batch()
+    b = b.to(dev)
+    args = (b.protein_pos, b.protein_atom_feature.float(), b.protein_element_batch, lpos.to(dev), lv.to(dev), b.ligand_element_batch)
+    want = m(*args)
+    for _ in range(3):
+        lib.td_debug_fail_alloc(1)
+        try:
+            with pytest.raises(RuntimeError, match='graph plan: hipMallocAsync'):
+                m(*args)
+        finally:
+            lib.td_debug_fail_alloc(0)
+    got = m(*args)
+    for key in ('pred_ligand_pos', 'pred_ligand_v', 'final_ligand_h', 'final_h'):
+        assert torch.equal(got[key], want[key]), key
+
+
 def test_failing_session_allocations_strand_no_block(model):
     """The same at the benchmark's size, where a leak shows: 1h36 x 100 samples (N = 60,708), whose session block holds at least P and Px,
     2 * N * 4 * 128 * 4 bytes >= 237 MiB.  After every failing td_session_create the device memory in use has grown by less than 128 MiB

@@ -525,6 +525,39 @@ int td_interaction_report(const float *d_pos, const int64_t *d_v, const int32_t 
                           int32_t *d_atom_hbonds, int32_t *d_atom_hydrophobic, uint64_t *d_bits, int64_t *d_kind_hist,
                           int32_t *d_pocket_freq, void *stream);
 
+/* ---- solvent-accessible surface of ligand frames by Shrake-Rupley point counting ("Solvent-accessible
+ *      surface"): every output is a count of sphere points; areas are formed by the caller.  One pocket and one pack per call; the
+ *      pack, the class table and d_include as td_pocket_report takes them.  d_protein_pos [N_p,3] fp32; d_protein_elem [N_p] int32, an
+ *      index over H C N O S Se, or -1: an atom outside 0 .. 5 takes part nowhere.  N_p may be 0 and the two pointers then NULL.  A
+ *      ligand atom takes part when its class is in [0, K).  ligand_reach [8] over H C N O F P S Cl and protein_reach [6] over H C N O S
+ *      Se: HOST float64, the expanded radius R = van der Waals radius + probe, each finite and > 0 (else TD_EINVAL).  d_dirs [P,3]
+ *      DEVICE float64, unit directions, 1 <= P <= 256; they are not read on the host (a binding checks that they are finite and of
+ *      unit length to 1e-6, and that no coordinate exceeds 1e5 in magnitude).
+ *      Arithmetic: float64, every product, sum and difference rounded on its own, centres the fp32 inputs widened.  Test point k of an
+ *      atom with centre c and reach R: x = c + R u_k, per coordinate one product and one add.  R2 = R R.  D2(x, c') = ((x0 - c'0)^2 +
+ *      (x1 - c'1)^2) + (x2 - c'2)^2.  Atom j occludes the point iff D2(x, c_j) < R2_j, strictly.
+ *      Free: a point of ligand atom i is exposed iff no other atom j != i of the same frame and molecule that takes part occludes it.
+ *      Bound: it is free-exposed and no protein atom that takes part occludes it.  Apo: a point of a protein atom that takes part is
+ *      exposed iff no other protein atom that takes part occludes it.  Buried pocket point: an apo-exposed point of protein atom j that
+ *      some atom of the molecule that takes part occludes.
+ *      Output per (frame, molecule): d_free and d_bound [S,B,8] int32, the exposed points by ligand element; d_pocket_buried [S,B,6]
+ *      int32, the buried pocket points by protein element.  May be NULL: d_atom_free and d_atom_bound [S,N_l] int32, the exposed
+ *      points of every ligand atom; d_bits [S,B,W] uint64, W = ceil(N_p / 64), the protein atoms with at least one point buried by
+ *      the molecule, in td_pocket_report's bit layout.  Per pocket, whatever S and B: d_pocket_free [N_p] int32, the apo-exposed
+ *      points, 0 for an atom that takes no part; d_pocket_mask [N_p,4] uint64, bit k & 63 of word k >> 6 set when point k is
+ *      apo-exposed.  Per frame, zeroed by the call: d_pocket_buried_sum [S,N_p] int64, the buried points of protein atom j summed over
+ *      the molecules whose d_include byte is non-zero (NULL: all).  A molecule of more than 512 atoms, or one whose offsets leave
+ *      [0, N_l], gets -1 in d_free, d_bound and d_pocket_buried and zero words in d_bits, its per-atom outputs are not written, and it
+ *      contributes nothing else (a binding refuses it).  512 N_p, S N_p and 8 S B must fit 31 bits.  S, B and N_p may be 0.  Every
+ *      output is an integer: nothing depends on the grid or on the order of arrival, and there is no floating-point atomic.
+ *      (An addition: TD_ABI_VERSION stays 5.) */
+int td_sasa_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                   const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const float *d_protein_pos,
+                   const int32_t *d_protein_elem, int64_t N_p, const double *ligand_reach, const double *protein_reach,
+                   const double *d_dirs, int32_t P, int32_t *d_free, int32_t *d_bound, int32_t *d_pocket_buried, int32_t *d_atom_free,
+                   int32_t *d_atom_bound, uint64_t *d_bits, int32_t *d_pocket_free, uint64_t *d_pocket_mask,
+                   int64_t *d_pocket_buried_sum, void *stream);
+
 /* ---- standalone EGNN refine net (replaces: models/egnn.py EGNN / EnBaseLayer as get_refine_net('egnn', config) builds
  *      it, models/molopt_score_model.py:34-42: num_r_gaussian = 1, kNN rebuilt per layer, SiLU, no LayerNorm, hidden 128,
  *      4 edge types, k = 32).  `host_weights`: per layer, in this order and as PyTorch stores them: edge_mlp.net.0.{weight

@@ -106,6 +106,8 @@ SIGNATURES = {
     'td_interaction_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, _P, _P, _P, c_int64, c_int32,
                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                         _P, _P, _P, _P, _P]),
+    'td_sasa_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, _P, c_int64, POINTER(ctypes.c_double),
+                                 POINTER(ctypes.c_double), _P, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_center_pos': (c_int32, [_P, _P, _P, _P, c_int64, _P, c_int32, c_int32, _P]),
     'td_perturb': (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
@@ -1306,6 +1308,81 @@ def interaction_report(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, p
                                          _ptr(out['n_ref_common']), _ptr(out['atom_role']), _ptr(out['atom_hbonds']),
                                          _ptr(out['atom_hydrophobic']), _ptr(out['bits']), _ptr(out['kind_hist']), _ptr(out['pocket_freq']),
                                          _stream(dev)), 'td_interaction_report')
+    return out
+
+
+SASA_MAX_POINTS, SASA_CHUNK = 256, 512                                      # TD_SASA_* (csrc/td_internal.h)
+SASA_CULL_REL, SASA_CULL_ABS = 1e-4, 1e-4                                   # TD_SASA_CULL_*: an occluder farther than (R_a + R_b) (1 + REL) + ABS is not looked at
+SASA_COORD_MAX = 1.0e5                                                      # |coordinate| the binding admits: csrc/sasa.hip's cull is proved up to it
+SASA_UNIT_TOL = 1.0e-6                                                      # | |u|^2 - 1 | the binding admits of a direction
+
+
+def _sasa_inputs(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, ligand_reach, protein_reach, dirs, include, check=True):
+    """Everything a sasa_report call is given: the pack as _bond_inputs checks it, the pocket's shapes, dtypes and devices, the two
+    reach tables and the directions; with ``check`` the elements, the directions and the coordinates are looked at on the host (one
+    synchronisation each).  Returns (S, N_l, B, class table, N_p, W, P, ligand reaches [8], protein reaches [6] as float64 numpy)."""
+    S, Nl, B, cz, _, _ = _bond_inputs(pos, v, ligand_ptr, class_z, None, include, (), check)
+    if protein_pos.dim() != 2 or protein_pos.shape[1] != 3:
+        raise ValueError(f'protein_pos must be [N_p, 3] (got {tuple(protein_pos.shape)})')
+    Np = protein_pos.shape[0]
+    if tuple(protein_elem.shape) != (Np,):
+        raise ValueError(f'protein_elem must be [{Np}] (got {tuple(protein_elem.shape)})')
+    if protein_pos.dtype != torch.float32 or protein_elem.dtype != torch.int32:
+        raise ValueError(f'protein_pos / protein_elem must be fp32 / int32 (got {protein_pos.dtype}, {protein_elem.dtype})')
+    if dirs.dim() != 2 or dirs.shape[1] != 3 or not 1 <= dirs.shape[0] <= SASA_MAX_POINTS:
+        raise ValueError(f'dirs must be [P, 3] with 1 <= P <= {SASA_MAX_POINTS} (got {tuple(dirs.shape)})')
+    if dirs.dtype != torch.float64:
+        raise ValueError(f'dirs must be float64 (got {dirs.dtype})')
+    if any(t.device != pos.device for t in (protein_pos, protein_elem, dirs)):
+        raise ValueError(f'the pocket and the directions must live on the device of the pack ({pos.device})')
+    if 512 * Np > 0x7fffffff or S * Np > 0x7fffffff or S * B * 8 > 0x7fffffff:
+        raise ValueError(f'512 N_p, S N_p and 8 S B must fit 31 bits (S = {S}, B = {B}, N_p = {Np})')
+    reach = []
+    for name, r, size in (('ligand_reach', ligand_reach, 8), ('protein_reach', protein_reach, POCKET_ELEMENTS)):
+        r = np.asarray(r, dtype=np.float64)
+        if r.shape != (size,) or not np.isfinite(r).all() or not (r > 0.0).all():
+            raise ValueError(f'{name} is [{size}], finite and > 0: van der Waals radius + probe per element')
+        reach.append(np.ascontiguousarray(r))
+    if check:
+        if Np > 0 and (int(protein_elem.min()) < -1 or int(protein_elem.max()) >= POCKET_ELEMENTS):
+            raise ValueError(f'protein_elem must be in [-1, {POCKET_ELEMENTS}): an index over H C N O S Se, or -1')
+        if not bool(torch.isfinite(dirs).all()) or not float(((dirs * dirs).sum(1) - 1.0).abs().max()) <= SASA_UNIT_TOL:
+            raise ValueError(f'dirs must be finite unit vectors (| |u|^2 - 1 | <= {SASA_UNIT_TOL})')
+        for name, t in (('pos', pos), ('protein_pos', protein_pos)):
+            if t.numel() and not float(t.abs().max()) <= SASA_COORD_MAX:
+                raise ValueError(f'{name} must be finite with |coordinate| <= {SASA_COORD_MAX:g}')
+    return S, Nl, B, cz, Np, (Np + 63) // 64, dirs.shape[0], reach[0], reach[1]
+
+
+def sasa_report(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, ligand_reach, protein_reach, dirs, include=None,
+                return_atoms=True, return_bits=True, check=True):
+    """Solvent-accessible surface of S frames of B molecules, alone and in one pocket, as counts of sphere points (td_sasa_report,
+    include/targetdiff_hip.h); the pack, the class table and ``include`` as bond_graph's.  ``protein_pos`` [N_p, 3] fp32 in the frame
+    of ``pos``, ``protein_elem`` [N_p] int32 over H C N O S Se or -1 (the atom takes part nowhere).  ``ligand_reach`` [8] over H C N O
+    F P S Cl and ``protein_reach`` [6]: van der Waals radius + probe, float64.  ``dirs`` [P, 3] float64 on the device, unit vectors, 1
+    <= P <= 256.  Coordinates beyond ``SASA_COORD_MAX`` are refused.  Returns a dict of device tensors: free, bound [S, B, 8] int32 (the
+    exposed points by ligand element, alone and in the pocket), pocket_buried [S, B, 6] int32 (the apo-exposed pocket points the
+    molecule covers, by protein element), atom_free / atom_bound [S, N_l] int32 (None without ``return_atoms``), bits [S, B, W] int64
+    (the protein atoms with a buried point; None without ``return_bits``), pocket_free [N_p] int32 and pocket_mask [N_p, 4] int64 (the
+    pocket alone), and over the included molecules pocket_buried_sum [S, N_p] int64."""
+    S, Nl, B, cz, Np, W, P, lr, pr = _sasa_inputs(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, ligand_reach, protein_reach, dirs,
+                                                  include, check)
+    lib = load_library()
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
+    dev = pos.device
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    z32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)    # an oversize molecule's atoms are not written
+    i64 = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
+    out = dict(free=i32(S, B, 8), bound=i32(S, B, 8), pocket_buried=i32(S, B, POCKET_ELEMENTS),
+               atom_free=z32(S, Nl) if return_atoms else None, atom_bound=z32(S, Nl) if return_atoms else None,
+               bits=i64(S, B, W) if return_bits else None, pocket_free=i32(Np), pocket_mask=i64(Np, 4), pocket_buried_sum=i64(S, Np))
+    f64p = lambda a: a.ctypes.data_as(POINTER(ctypes.c_double))
+    with _on(dev):
+        _check(lib.td_sasa_report(*pack, _include_arg(include), _ptr(protein_pos, torch.float32, 'protein_pos'),
+                                  _ptr(protein_elem, torch.int32, 'protein_elem'), Np, f64p(lr), f64p(pr), _ptr(dirs, torch.float64, 'dirs'),
+                                  P, _ptr(out['free']), _ptr(out['bound']), _ptr(out['pocket_buried']), _ptr(out['atom_free']),
+                                  _ptr(out['atom_bound']), _ptr(out['bits']), _ptr(out['pocket_free']), _ptr(out['pocket_mask']),
+                                  _ptr(out['pocket_buried_sum']), _stream(dev)), 'td_sasa_report')
     return out
 
 

@@ -1,6 +1,7 @@
 // C ABI of libtargetdiff_hip.so: the bond graph of ligand frames, its rings, its fingerprints, its local geometry and the contacts with
-// the pocket and the typed interactions with it (td_bond_graph, td_bond_list, td_ring_report, td_fingerprint,
-// td_fingerprint_similarity, td_geometry_report, td_pocket_report, td_interaction_report).  See include/targetdiff_hip.h for the contract.
+// the pocket, the typed interactions with it and the surface it buries (td_bond_graph, td_bond_list, td_ring_report, td_fingerprint,
+// td_fingerprint_similarity, td_geometry_report, td_pocket_report, td_interaction_report, td_sasa_report).  See
+// include/targetdiff_hip.h for the contract.
 #include <cmath>
 #include <initializer_list>
 
@@ -311,4 +312,46 @@ extern "C" int td_interaction_report(const float *d_pos, const int64_t *d_v, con
     g.bits = reinterpret_cast<unsigned long long *>(d_bits); g.kind_hist = reinterpret_cast<unsigned long long *>(d_kind_hist);
     g.pocket_freq = d_pocket_freq;
     return td_launch_interaction_report(g, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int td_sasa_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                              const int32_t *class_atomic_number, int32_t K, const uint8_t *d_include, const float *d_protein_pos,
+                              const int32_t *d_protein_elem, int64_t N_p, const double *ligand_reach, const double *protein_reach,
+                              const double *d_dirs, int32_t P, int32_t *d_free, int32_t *d_bound, int32_t *d_pocket_buried,
+                              int32_t *d_atom_free, int32_t *d_atom_bound, uint64_t *d_bits, int32_t *d_pocket_free,
+                              uint64_t *d_pocket_mask, int64_t *d_pocket_buried_sum, void *stream) {
+    const char *who = "td_sasa_report";
+    TdSasaArgs g;
+    if (const int rc = bond_pack(who, g.b, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, nullptr)) return rc;
+    if (N_p < 0 || N_p > 0x7fffffff / TD_BOND_MAX_ATOMS || S * N_p > 0x7fffffff || S * B > 0x7fffffff / 8) {   // points are counted in an int32
+        td_set_error("%s: bad argument (N_p = %lld; 512 N_p, S * N_p and 8 S * B must fit 31 bits)", who, (long long)N_p);
+        return TD_EINVAL;
+    }
+    if (P < 1 || P > TD_SASA_MAX_POINTS || !d_dirs) {
+        td_set_error("%s: 1 .. %d directions (got %d)", who, TD_SASA_MAX_POINTS, (int)P);
+        return TD_EINVAL;
+    }
+    if (!ligand_reach || !protein_reach) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
+    for (int e = 0; e < 8 + TD_POCKET_ELEMENTS; ++e) {
+        const double R = e < 8 ? ligand_reach[e] : protein_reach[e - 8];
+        if (!std::isfinite(R) || !(R > 0.0)) {
+            td_set_error("%s: every reach must be finite and > 0", who);
+            return TD_EINVAL;
+        }
+        (e < 8 ? g.lig_R[e] : g.prot_R[e - 8]) = R;
+    }
+    if (N_p > 0 && (!d_protein_pos || !d_protein_elem || !d_pocket_free || !d_pocket_mask || (S > 0 && !d_pocket_buried_sum))) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    if (S > 0 && B > 0 && (!d_free || !d_bound || !d_pocket_buried)) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
+    g.b.include = d_include;
+    g.ppos = d_protein_pos; g.pelem = d_protein_elem; g.dirs = d_dirs;
+    g.Np = (int)N_p; g.W = (int)((N_p + 63) / 64); g.P = P;
+    g.n_free = d_free; g.n_bound = d_bound; g.pocket_buried = d_pocket_buried;
+    g.atom_free = d_atom_free; g.atom_bound = d_atom_bound;
+    g.bits = reinterpret_cast<unsigned long long *>(d_bits);
+    g.pocket_free = d_pocket_free; g.pocket_mask = reinterpret_cast<unsigned long long *>(d_pocket_mask);
+    g.buried_sum = reinterpret_cast<unsigned long long *>(d_pocket_buried_sum);
+    return td_launch_sasa_report(g, static_cast<hipStream_t>(stream));
 }

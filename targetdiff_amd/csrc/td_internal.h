@@ -556,6 +556,29 @@ struct TdInteractionArgs {
     int32_t *pocket_freq = nullptr;          // [S,3,Np]
 };
 int td_launch_interaction_report(const TdInteractionArgs &a, hipStream_t s);
+// sasa.hip (td_sasa_report, DESIGN.md section 3, "Solvent-accessible surface"): the pack and the include bytes in `b` (none of b's
+// outputs is used); the pocket as TdPocketArgs takes it, without kinds.  lig_R over H C N O F P S Cl and prot_R over H C N O S Se: the
+// reach (van der Waals radius + probe) per element; dirs: P unit directions.  A candidate occluder is dropped only when its centre is
+// farther than (R_a + R_b) (1 + TD_SASA_CULL_REL) + TD_SASA_CULL_ABS: sasa.hip says why that changes no result.  W = ceil(Np / 64).
+// The launcher zeroes buried_sum and bits on the stream.
+constexpr int TD_SASA_THREADS = 256, TD_SASA_MAX_POINTS = 256, TD_SASA_CHUNK = 512;
+constexpr double TD_SASA_CULL_REL = 1e-4, TD_SASA_CULL_ABS = 1e-4;
+struct TdSasaArgs {
+    TdBondArgs b;
+    const float *ppos = nullptr;             // [Np,3]
+    const int32_t *pelem = nullptr;          // [Np]
+    const double *dirs = nullptr;            // [P,3]
+    int Np = 0, W = 0, P = 0;
+    double lig_R[8] = {}, prot_R[TD_POCKET_ELEMENTS] = {};
+    int32_t *n_free = nullptr, *n_bound = nullptr;                               // [S,B,8]
+    int32_t *pocket_buried = nullptr;        // [S,B,6]
+    int32_t *atom_free = nullptr, *atom_bound = nullptr;                         // [S,N_l] or null
+    unsigned long long *bits = nullptr;      // [S,B,W] or null
+    int32_t *pocket_free = nullptr;          // [Np]
+    unsigned long long *pocket_mask = nullptr;                                   // [Np,4]
+    unsigned long long *buried_sum = nullptr;                                    // [S,Np]
+};
+int td_launch_sasa_report(const TdSasaArgs &a, hipStream_t s);
 // egnn.hip / node.hip
 int td_launch_egnn_edge(const TdEgnnLayer &L, const float4 *x4, float4 *x4_out, const int32_t *nbr, const float *P, float *mi,
                         int64_t N, hipStream_t s);

@@ -66,6 +66,13 @@ project, not perceived chemistry:
     ia.summary()   # {'mean_hbonds': ..., 'mean_donated': ..., 'mean_accepted': ..., 'mean_hydrophobic': ..., 'no_hbond': ..., ...}
     ia.kind_profile('donated'), ia.interaction_frequency()    # hydrogen bonds by residue kind, and per type and protein atom
 
+And how much of a pose's surface the pocket covers (``td_sasa_report``, csrc/sasa.hip; DESIGN.md section 3, "Solvent-accessible
+surface"): Shrake-Rupley point counts of the ligand alone and in the pocket, areas formed on the host from Bondi-type radii plus a
+1.4 A probe -- comparable between runs of this tool, not with published tables; of the pocket, a cut-out, only the buried area:
+
+    sa = quality.sample_sasa(result, eval_step='all', reference_ligand=(ref_pos, ref_v))
+    sa.summary()   # {'sasa_free': ..., 'sasa_bound': ..., 'sasa_buried': ..., 'sasa_buried_share': ..., 'pocket_buried_area': ..., ...}
+
 Several reports of one result share its pack, its host checks and its bond graph (``SamplePack``; the ``sample_*`` functions build one each):
 
     pack = quality.SamplePack(result, eval_step='all')
@@ -493,6 +500,10 @@ class SamplePack:
                 'pocket_freq')
         raw = {k: r[k].cpu().numpy() for k in keys if r[k] is not None}
         return InteractionReport.from_outputs(raw, self._included(mask), self.sizes, names, ref_sizes)
+
+    def sasa(self, data, include='all', reference_ligand=None, probe=1.4, points=96):
+        """``sample_sasa`` of the pack; ``data``: the pocket every molecule of the pack is in (``_pocket_arrays``)"""
+        return _sasa_of_pack(self, data, include, reference_ligand, probe, points)
 
 
 def sample_quality(result, eval_step=-1, include='all', atom_enc_mode='add_aromatic', reference=None, profiles=None, device='cuda'):
@@ -1188,6 +1199,24 @@ def pocket_contacts(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand
     return PocketContacts(r, ligand_ptr, elem, kind, names)
 
 
+def _reference_recovery(common, touched, ref_size, included):
+    """How a pocket's molecules recover the protein atoms a known ligand marks: ``common`` [S, B] the marked atoms a molecule hits,
+    ``touched`` [S, B] the atoms it hits, ``ref_size`` the marked atoms.  Returns (``sum_ref`` [S, 4], ``n_ref`` [S]): per frame the
+    mean, the median and the largest recovery common / ref_size and the mean Tanimoto common / (touched + ref_size - common) over the
+    included molecules, and 1 where the frame has them (a reference that marks nothing, or an empty set, gives none)."""
+    inc = np.asarray(included, dtype=bool)
+    S = inc.shape[0]
+    sum_ref, n_ref = np.zeros((S, 4)), np.zeros(S, np.int64)
+    common, touched = np.asarray(common, dtype=np.float64), np.asarray(touched, dtype=np.float64)
+    for s in range(S):
+        if int(ref_size) > 0 and inc[s].any():
+            rec = common[s][inc[s]] / float(ref_size)
+            tan = common[s][inc[s]] / (touched[s][inc[s]] + float(ref_size) - common[s][inc[s]])
+            sum_ref[s] = (rec.sum() / rec.size, np.median(rec), rec.max(), tan.sum() / tan.size)
+            n_ref[s] = 1
+    return sum_ref, n_ref
+
+
 class PocketReport:
     """Per frame (axis 0), over the included molecules (``n_included`` [S] of ``n_samples``): ``n_clash_free``, ``sum_clashes``,
     ``sum_contacts``, ``n_no_contact`` [S] int64; ``sum_buried`` [S], the sum of buried atoms / atoms over the ``n_nonempty`` [S]
@@ -1225,15 +1254,7 @@ class PocketReport:
         has = inc & np.isfinite(md)
         sum_ref = n_ref = None
         if ref_size is not None:
-            S = inc.shape[0]
-            sum_ref, n_ref = np.zeros((S, 4)), np.zeros(S, np.int64)
-            common, touched = np.asarray(raw['n_ref_common'], dtype=np.float64), np.asarray(raw['n_pocket_atoms'], dtype=np.float64)
-            for s in range(S):
-                if int(ref_size) > 0 and inc[s].any():
-                    rec = common[s][inc[s]] / float(ref_size)
-                    tan = common[s][inc[s]] / (touched[s][inc[s]] + float(ref_size) - common[s][inc[s]])
-                    sum_ref[s] = (rec.sum() / rec.size, np.median(rec), rec.max(), tan.sum() / tan.size)
-                    n_ref[s] = 1
+            sum_ref, n_ref = _reference_recovery(raw['n_ref_common'], raw['n_pocket_atoms'], ref_size, inc)
         return cls(inc.sum(1), (inc & (clashes == 0)).sum(1), np.where(inc, clashes, 0).sum(1), np.where(inc, con, 0).sum(1),
                    (inc & (con == 0)).sum(1), np.where(inc, share, 0.0).sum(1), (inc & (n[None] > 0)).sum(1), np.where(has, md, 0.0).sum(1),
                    has.sum(1), raw['kind_hist'], names, backbone, len(n), raw['pocket_freq'], sum_ref, n_ref)
@@ -1571,3 +1592,276 @@ def sample_interactions(result, eval_step=-1, include='all', reference_ligand=No
                          '(results.result_dict), or use SamplePack.interactions(data)')
     return SamplePack(result, eval_step, atom_enc_mode, device).interactions(data, include, reference_ligand, hbond_cutoff, hydrophobic_cutoff,
                                                                              hetero_cutoff)
+
+
+# ---- solvent-accessible surface (``td_sasa_report``, csrc/sasa.hip; DESIGN.md section 3, "Solvent-accessible surface")
+# Shrake-Rupley point counting: every atom carries ``SASA_POINTS`` test points on the sphere of its van der Waals radius plus the probe
+# radius, and a point is exposed when no other such sphere holds it.  The kernel counts points; the areas are formed here, in float64,
+# as 4 pi R^2 n / P per element.  Conventions and limits: Bondi-type radii on heavy atoms with no united-atom correction, so the areas
+# compare between runs of this tool and not with published tables; a stored pocket is a cut-out whose rim is exposed only because the
+# rest of the protein is missing, so of the pocket only the **buried** area is reported (the apo-exposed counts are a raw output); at 96
+# points one point is about 1 % of a sphere.
+SASA_PROBE = 1.4
+SASA_POINTS = 96
+SASA_POLAR = (2, 3)                                   # N and O: their index is the same over H C N O F P S Cl and over H C N O S Se
+
+
+def sasa_directions(points=SASA_POINTS):
+    """[P, 3] float64 unit vectors on the golden-section spiral: z_k = 1 - (2 k + 1) / P, r = sqrt(1 - z^2), phi = k pi (3 - sqrt 5).
+    The only trigonometry of the report: the kernel and its restatement both read these bits."""
+    P = int(points)
+    if not 1 <= P <= capi.SASA_MAX_POINTS:
+        raise ValueError(f'1 .. {capi.SASA_MAX_POINTS} points per sphere (got {points})')
+    k = np.arange(P, dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / np.float64(P)
+    r = np.sqrt(1.0 - z * z)
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+
+
+def sasa_reaches(probe=SASA_PROBE, radii=None):
+    """([8], [6]) float64: the expanded radius ``r + probe`` of the ligand's elements H C N O F P S Cl and of the protein's H C N O S Se,
+    with geometry's van der Waals radii and Se 1.90 A; ``radii``: {atomic number: radius in Angstrom} to change some"""
+    from . import workloads
+    r = dict(POCKET_RADII)
+    for z, x in (radii or {}).items():
+        if int(z) not in r or not float(x) >= 0.0:
+            raise ValueError(f'radii are non-negative and keyed by the atomic numbers {tuple(sorted(r))} (got {z}: {x})')
+        r[int(z)] = float(x)
+    if not (np.isfinite(float(probe)) and float(probe) >= 0.0):
+        raise ValueError(f'the probe radius is finite and >= 0 (got {probe})')
+    rl = np.asarray([r[z] for z in ELEMENTS], dtype=np.float64) + np.float64(probe)
+    rp = np.asarray([r[z] for z in workloads.PROTEIN_ELEMENTS], dtype=np.float64) + np.float64(probe)
+    if not ((rl > 0.0).all() and (rp > 0.0).all()):
+        raise ValueError('every radius plus the probe must be > 0')
+    return rl, rp
+
+
+def sasa_areas(counts, reach, points):
+    """[..., 3] float64 (total, polar, apolar) in square Angstrom of point counts [..., E] by element: 4 pi R_e^2 n_e / P each, N and O
+    polar, every other element apolar"""
+    reach = np.asarray(reach, dtype=np.float64)
+    a = np.asarray(counts, dtype=np.float64) * ((4.0 * np.pi) * reach * reach / np.float64(points))
+    polar = np.zeros(len(reach), bool)
+    polar[list(SASA_POLAR)] = True
+    return np.stack([a.sum(-1), a[..., polar].sum(-1), a[..., ~polar].sum(-1)], axis=-1)
+
+
+def _buried_share(free_area, buried_area):
+    """buried / free, 0 where nothing is free"""
+    return np.divide(buried_area, free_area, out=np.zeros_like(free_area), where=free_area > 0)
+
+
+def _sasa_pocket(data, device, hydrogens=False):
+    """The pocket ``data`` (``pocket_of``) as (pos [N_p, 3] fp32, elem [N_p] int32 on ``device``): the element index over H C N O S Se,
+    -1 for a row without one and, unless ``hydrogens``, for a hydrogen (``pocket_kinds``)"""
+    ppos, _, elem, _ = _pocket_arrays(data, device, 'element', hydrogens)
+    return ppos, elem
+
+
+class Sasa:
+    """The surface of S frames of B molecules, alone and in one pocket (``pocket_sasa``).  Device tensors, frame axis first: ``free``,
+    ``bound`` [S, B, 8] int32 (exposed points by ligand element H C N O F P S Cl), ``pocket_buried`` [S, B, 6] int32 (apo-exposed pocket
+    points the molecule covers, by protein element), ``atom_free`` / ``atom_bound`` [S, N_l] int32, ``bits`` [S, B, W] int64 or None
+    (bit j & 63 of word j >> 6: the molecule buries a point of protein atom j), ``pocket_free`` [N_p] int32 and ``pocket_mask`` [N_p, 4]
+    int64 (the pocket alone; at a cut-out's rim an artefact), ``pocket_buried_sum`` [S, N_p] int64 over the included molecules.
+    Areas in square Angstrom, float64 [S, B]: ``free_area``, ``bound_area``, ``buried_area`` = free - bound, ``pocket_buried_area``,
+    and ``buried_share`` = buried / free (0 where nothing is free).  ``ligand_reach``, ``protein_reach``, ``points``, ``protein_elem``,
+    ``ligand_ptr``."""
+
+    def __init__(self, r, ligand_ptr, protein_elem, ligand_reach, protein_reach, points):
+        for k, t in r.items():
+            setattr(self, k, t)
+        self.ligand_ptr, self.protein_elem, self.points = ligand_ptr, protein_elem, int(points)
+        self.ligand_reach, self.protein_reach = ligand_reach, protein_reach
+        free, bound = r['free'].cpu().numpy().astype(np.int64), r['bound'].cpu().numpy().astype(np.int64)
+        dev = r['free'].device
+        area = lambda counts, reach: sasa_areas(counts, reach, points)[..., 0]
+        fa, ba, bu = area(free, ligand_reach), area(bound, ligand_reach), area(free - bound, ligand_reach)
+        self.free_area, self.bound_area, self.buried_area = (torch.from_numpy(x).to(dev) for x in (fa, ba, bu))
+        self.pocket_buried_area = torch.from_numpy(area(r['pocket_buried'].cpu().numpy(), protein_reach)).to(dev)
+        self.buried_share = torch.from_numpy(_buried_share(fa, bu)).to(dev)
+
+
+def pocket_sasa(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic', probe=SASA_PROBE,
+                points=SASA_POINTS, radii=None, hydrogens=False, include=None, return_bits=False, device=None):
+    """Solvent-accessible surface of every molecule of one frame ``[N_l, 3]`` or of a stack ``[S, N_l, 3]`` (arguments as
+    ``bond_graph``), alone and inside the pocket ``protein_pos`` [N_p, 3], ``protein_feat`` [N_p, 27], both in the frame of ``pos``.
+    ``probe``: the probe radius (default 1.4 A, water); ``points``: test points per sphere (default 96, 1 .. 256); ``radii`` as
+    ``sasa_reaches``.  Protein hydrogens take no part unless ``hydrogens`` (``pocket_kinds``).  ``include`` [S, B] restricts
+    ``pocket_buried_sum`` and nothing else.  Molecules of more than 512 atoms and coordinates beyond 1e5 A are refused.  Returns a
+    ``Sasa`` (the frame axis is kept)."""
+    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
+    ppos, elem = _sasa_pocket((protein_pos, protein_feat), pos.device, hydrogens)
+    if include is not None:
+        include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+    lr, pr = sasa_reaches(probe, radii)
+    dirs = torch.from_numpy(sasa_directions(points)).to(pos.device)
+    r = capi.sasa_report(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), ppos, elem, lr, pr, dirs, include, True, return_bits)
+    return Sasa(r, ligand_ptr, elem, lr, pr, points)
+
+
+class SasaReport:
+    """Per frame (axis 0), over the included molecules (``n_included`` [S] of ``n_samples``), areas in square Angstrom: ``sum_free``,
+    ``sum_bound``, ``sum_buried`` [S, 3] float64, the ligands' surface alone, in the pocket and their difference, each as (total, polar,
+    apolar; polar is N and O); ``sum_share`` [S], the sum of buried / free (0 for a molecule with nothing free); ``n_nothing`` [S], the
+    molecules of whose surface the pocket covers no point; ``sum_pocket`` [S, 3], the pocket's apo-exposed surface the ligands cover;
+    ``pocket_buried_sum`` [S, N_p] int64, the covered points per protein atom, or None for a report merged from several pockets.  With
+    a reference ligand ``sum_own`` [S, 5] -- its own free, bound and buried area, buried share and covered pocket area, from the same
+    kernel -- and ``sum_ref`` [S, 4] -- the mean, the median and the largest recovery of the protein atoms it buries and the mean
+    Tanimoto, as ``PocketReport`` forms them for contacts -- over the ``n_own`` / ``n_ref`` [S] pockets that have them.  The radii, the
+    probe and the point count are conventions (``pocket_sasa``); of the pocket only buried area is reported."""
+
+    def __init__(self, n_included, sum_free, sum_bound, sum_buried, sum_share, n_nothing, sum_pocket, n_samples, points, probe=None,
+                 pocket_buried_sum=None, sum_own=None, n_own=None, sum_ref=None, n_ref=None):
+        i64, f64 = (lambda a: np.asarray(a, dtype=np.int64)), (lambda a: np.asarray(a, dtype=np.float64))
+        self.n_included, self.n_nothing = i64(n_included), i64(n_nothing)
+        self.sum_free, self.sum_bound, self.sum_buried, self.sum_share, self.sum_pocket = (f64(x) for x in (sum_free, sum_bound, sum_buried,
+                                                                                                         sum_share, sum_pocket))
+        self.n_samples, self.points, self.probe = int(n_samples), int(points), probe
+        self.pocket_buried_sum = None if pocket_buried_sum is None else i64(pocket_buried_sum)
+        opt = lambda a, conv: None if a is None else conv(a)
+        self.sum_own, self.n_own, self.sum_ref, self.n_ref = opt(sum_own, f64), opt(n_own, i64), opt(sum_ref, f64), opt(n_ref, i64)
+
+    @classmethod
+    def from_outputs(cls, raw, included, ligand_reach, protein_reach, points, probe=None, ref=None):
+        """One pocket: ``raw`` the numpy outputs of capi.sasa_report (free, bound, pocket_buried, pocket_buried_sum and, with a
+        reference, bits), ``included`` [S, B] bool; ``ref``: the same outputs of the reference ligand's own call, one frame of one
+        molecule (free [8], bound [8], pocket_buried [6], bits [W])"""
+        inc = np.asarray(included, dtype=bool)
+        S, B = inc.shape
+        free, bound = np.asarray(raw['free'], dtype=np.int64), np.asarray(raw['bound'], dtype=np.int64)
+        fa, ba, bu = (sasa_areas(x, ligand_reach, points) for x in (free, bound, free - bound))
+        pa = sasa_areas(raw['pocket_buried'], protein_reach, points)
+        share = _buried_share(fa[..., 0], bu[..., 0])
+        tot = lambda a: np.where(inc[..., None], a, 0.0).sum(1)
+        sum_own = n_own = sum_ref = n_ref = None
+        if ref is not None:
+            rf, rb = np.asarray(ref['free'], dtype=np.int64), np.asarray(ref['bound'], dtype=np.int64)
+            own_f, own_b, own_u = (sasa_areas(x, ligand_reach, points)[0] for x in (rf, rb, rf - rb))
+            own = (own_f, own_b, own_u, float(_buried_share(np.asarray([own_f]), np.asarray([own_u]))[0]),
+                   sasa_areas(ref['pocket_buried'], protein_reach, points)[0])
+            sum_own, n_own = np.tile(np.asarray(own, dtype=np.float64), (S, 1)), np.ones(S, np.int64)
+            bits, rbits = np.asarray(raw['bits']), np.asarray(ref['bits'])
+            sum_ref, n_ref = _reference_recovery(_popcount(bits & rbits[None, None]), _popcount(bits), int(_popcount(rbits)), inc)
+        return cls(inc.sum(1), tot(fa), tot(ba), tot(bu), np.where(inc, share, 0.0).sum(1), (inc & ((free - bound).sum(-1) == 0)).sum(1),
+                   tot(pa), B, points, probe, raw['pocket_buried_sum'], sum_own, n_own, sum_ref, n_ref)
+
+    @classmethod
+    def merged(cls, reports):
+        """Several pockets together: every sum added, frame by frame; the reference values become means over the pockets that have
+        one (the convention of PocketReport).  The covered points per protein atom belong to one pocket: the merged report of several
+        has none."""
+        reports = list(reports)
+        first = reports[0]
+        if any(r.sum_free.shape != first.sum_free.shape or r.points != first.points or r.probe != first.probe or
+               (r.sum_ref is None) != (first.sum_ref is None) for r in reports):
+            raise ValueError('reports of different frame counts, point counts or probes, or with and without a reference ligand, do not merge')
+        tot = lambda name: sum(getattr(r, name) for r in reports)
+        opt = lambda name: None if first.sum_ref is None else tot(name)
+        return cls(tot('n_included'), tot('sum_free'), tot('sum_bound'), tot('sum_buried'), tot('sum_share'), tot('n_nothing'), tot('sum_pocket'),
+                   tot('n_samples'), first.points, first.probe, first.pocket_buried_sum if len(reports) == 1 else None, opt('sum_own'),
+                   opt('n_own'), opt('sum_ref'), opt('n_ref'))
+
+    @property
+    def num_frames(self):
+        return self.sum_free.shape[0]
+
+    @staticmethod
+    def _mean(total, count):
+        return float(total) / int(count) if int(count) else float('nan')
+
+    def free_area(self, frame=-1, part=0):
+        """mean surface of an included molecule alone; ``part`` 0 total, 1 polar, 2 apolar"""
+        return self._mean(self.sum_free[frame, part], self.n_included[frame])
+
+    def bound_area(self, frame=-1, part=0):
+        """mean surface of an included molecule that stays exposed inside the pocket"""
+        return self._mean(self.sum_bound[frame, part], self.n_included[frame])
+
+    def buried_area(self, frame=-1, part=0):
+        """mean surface of an included molecule that the pocket covers: free - bound"""
+        return self._mean(self.sum_buried[frame, part], self.n_included[frame])
+
+    def buried_share(self, frame=-1):
+        """the mean of buried / free over the included molecules (0 for a molecule with nothing free)"""
+        return self._mean(self.sum_share[frame], self.n_included[frame])
+
+    def pocket_buried_area(self, frame=-1):
+        """mean apo-exposed surface of the pocket that an included molecule covers"""
+        return self._mean(self.sum_pocket[frame, 0], self.n_included[frame])
+
+    def pocket_buried_polar_share(self, frame=-1):
+        """the share of that covered pocket surface that belongs to N and O; nan when nothing is covered"""
+        return float(self.sum_pocket[frame, 1]) / float(self.sum_pocket[frame, 0]) if self.sum_pocket[frame, 0] > 0 else float('nan')
+
+    def buries_nothing(self, frame=-1):
+        """the share of included molecules of whose surface the pocket covers no point: poses that left the pocket"""
+        return self._mean(self.n_nothing[frame], self.n_included[frame])
+
+    def pocket_map(self, frame=-1):
+        """[N_p]: the covered points of each protein atom per included molecule; None for a report of several pockets"""
+        if self.pocket_buried_sum is None:
+            return None
+        n = int(self.n_included[frame])
+        return self.pocket_buried_sum[frame] / float(n) if n else np.full(self.pocket_buried_sum.shape[1], np.nan)
+
+    def reference(self, frame=-1):
+        """the known ligand's own numbers and the recovery of the protein atoms it buries, or {} without a reference ligand"""
+        if self.sum_ref is None:
+            return {}
+        own = ('ref_sasa_free', 'ref_sasa_bound', 'ref_sasa_buried', 'ref_sasa_buried_share', 'ref_pocket_buried_area')
+        keys = ('ref_recovery_mean', 'ref_recovery_median', 'ref_recovery_max', 'ref_tanimoto')
+        return {**{k: self._mean(self.sum_own[frame, c], self.n_own[frame]) for c, k in enumerate(own)},
+                **{k: self._mean(self.sum_ref[frame, c], self.n_ref[frame]) for c, k in enumerate(keys)}}
+
+    def summary(self, frame=-1):
+        out = dict(sasa_free=self.free_area(frame), sasa_bound=self.bound_area(frame), sasa_buried=self.buried_area(frame),
+                   sasa_buried_share=self.buried_share(frame))
+        for part, name in ((1, 'polar'), (2, 'apolar')):
+            out.update({f'sasa_free_{name}': self.free_area(frame, part), f'sasa_bound_{name}': self.bound_area(frame, part),
+                        f'sasa_buried_{name}': self.buried_area(frame, part)})
+        out.update(pocket_buried_area=self.pocket_buried_area(frame), pocket_buried_polar_share=self.pocket_buried_polar_share(frame),
+                   buries_nothing=self.buries_nothing(frame), **self.reference(frame))
+        return out
+
+    def lines(self, frame=-1):
+        """the report as printed lines"""
+        return [f'{k}:\t{x:.4f}' if x == x else f'{k}:\tNone' for k, x in self.summary(frame).items()]
+
+
+def _sasa_of_pack(pack, data, include, reference_ligand, probe, points):
+    """``SamplePack.sasa``"""
+    ppos, elem = _sasa_pocket(data, pack.pos.device)
+    mask = pack.mask(include)
+    lr, pr = sasa_reaches(probe)
+    dirs = torch.from_numpy(sasa_directions(points)).to(pack.pos.device)
+    pocket = (ppos, elem, lr, pr, dirs)
+    ref = None
+    if reference_ligand is not None:
+        rpos, rv = reference_ligand
+        rpos, rv, rptr = _pack(rpos, rv, None, torch.tensor([0, len(rv)], dtype=torch.int32), pack.pos.device)
+        if rpos.shape[0] != 1:
+            raise ValueError('the reference ligand is one molecule: pos [n, 3], v [n]')
+        q = capi.sasa_report(rpos, rv, rptr, pack.class_z, *pocket, None, False, True)
+        ref = {k: q[k][0, 0].cpu().numpy() for k in ('free', 'bound', 'pocket_buried', 'bits')}
+    pack._check()
+    # the pack's host look runs with every call: the kernel's cull is proved for the coordinates that look admits
+    r = capi.sasa_report(*pack._args, *pocket, mask, False, ref is not None, check=True)
+    raw = {k: r[k].cpu().numpy() for k in ('free', 'bound', 'pocket_buried', 'bits', 'pocket_buried_sum') if r[k] is not None}
+    return SasaReport.from_outputs(raw, pack._included(mask), lr, pr, points, float(probe), ref)
+
+
+def sample_sasa(result, eval_step=-1, include='all', reference_ligand=None, probe=SASA_PROBE, points=SASA_POINTS,
+                atom_enc_mode='add_aromatic', device='cuda'):
+    """Solvent-accessible surface of the samples of one pocket (``result`` a loaded ``result_{i}.pt`` dictionary, whose ``'data'`` is
+    the pocket; ``eval_step`` and the packing as ``sample_quality``): per frame the mean surface of a molecule alone and in the pocket,
+    the buried area and share with their polar (N, O) and apolar parts, the pocket surface the molecule covers and its polar share, and
+    the share of poses the pocket does not cover at all; with ``reference_ligand`` ``(pos [n, 3], v [n])``, run through the same
+    kernel, its own numbers and the recovery of the protein atoms it buries.  ``include`` as ``sample_rings``.  The radii, the probe
+    and the point count are conventions (``pocket_sasa``).  A result without a pocket is refused.  Returns a ``SasaReport``."""
+    data = result.get('data') if isinstance(result, dict) else None
+    if data is None:
+        raise ValueError("the result carries no pocket: sample_sasa needs a result dictionary with its 'data' (results.result_dict), "
+                         'or use SamplePack.sasa(data)')
+    return SamplePack(result, eval_step, atom_enc_mode, device).sasa(data, include, reference_ligand, probe, points)

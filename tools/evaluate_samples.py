@@ -33,6 +33,13 @@ or donor closer than 3.5 A, heavy atom to heavy atom, no angle) with the donated
 (hydrophobic atoms closer than 4.5 A), the share of molecules without a hydrogen bond, the share of polar ligand atoms in one and the
 most frequent residue kinds per type -- the ligand's donors are inferred from the valence deficit, a heuristic of this project and not
 perceived chemistry, and nothing here is a docking score -- and, with the known ligand, the recovery of its interactions per type.
+``--sasa [--probe 1.4] [--sasa_points 96]`` adds the solvent-accessible surface of the samples alone and in their pocket
+(quality.sample_sasa: Shrake-Rupley point counts, areas in square Angstrom), over ``--include all`` or ``complete`` samples: the mean
+free, bound and buried area of a molecule with the polar (N, O) and apolar parts, the buried share, the pocket surface a molecule
+covers and its polar share, the share of poses the pocket does not cover at all and, with the known ligand, its own numbers and the
+recovery of the protein atoms it buries.  Bondi-type radii on heavy atoms without a united-atom correction: the areas compare between
+runs of this tool, not with published tables; the stored pocket is a cut-out, so of the pocket only buried area is reported; at 96
+points one point is about 1 % of a sphere.
 The fingerprint is this project's own circular one over its bond graph, not RDKit's RDKFingerprint: the numbers compare between
 runs of this tool, not with published tables.  The Jensen-Shannon distances need the reference's empirical distributions: they are
 loaded from ``utils.evaluation`` when the tool runs inside the reference repository (or with it on PYTHONPATH), or from
@@ -95,7 +102,11 @@ def main(argv=None):
                     help='--interactions: a hydrogen bond is a donor - acceptor pair of heavy atoms closer than this')
     ap.add_argument('--hydrophobic_cutoff', type=float, default=quality.DEFAULT_HYDROPHOBIC_CUTOFF,
                     help='--interactions: a hydrophobic contact is a pair of hydrophobic atoms closer than this')
-    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity, --pocket, --interactions: a known ligand, the first V2000 record of '
+    ap.add_argument('--sasa', action='store_true', help='also the solvent-accessible surface alone and in the pocket (the result '
+                    "file's data; this project's radii, comparable between runs of this tool only)")
+    ap.add_argument('--probe', type=float, default=quality.SASA_PROBE, help='--sasa: the probe radius in Angstrom')
+    ap.add_argument('--sasa_points', type=int, default=quality.SASA_POINTS, help='--sasa: test points per sphere, 1 .. 256')
+    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity, --pocket, --interactions, --sasa: a known ligand, the first V2000 record of '
                     'FILE; --geometry: known ligands, every record of FILE')
     ap.add_argument('--reference_npz', type=str, default=None)
     ap.add_argument('--device', type=str, default='cuda')
@@ -123,7 +134,7 @@ def main(argv=None):
     if not files:
         raise SystemExit(f'no result_*.pt under {args.sample_path}')
     print(f'Load generated data done! {len(files)} examples in total.')
-    reports, connectivity, rings, diversity, geometry, pocket, interactions = [], [], [], [], [], [], []
+    reports, connectivity, rings, diversity, geometry, pocket, interactions, sasa = [], [], [], [], [], [], [], []
     graph_include = 'complete' if args.include == 'complete' else 'all'     # 'stable' restricts the pair profiles and atom types only
     for name in files:
         result = torch.load(name, map_location='cpu', weights_only=False)
@@ -144,6 +155,13 @@ def main(argv=None):
             if not isinstance(result, dict) or result.get('data') is None:
                 raise SystemExit(f'{name} carries no pocket (no data): --interactions needs the files of a sampling driver')
             interactions.append(pack.interactions(result['data'], graph_include, reference_ligand, args.hbond_cutoff, args.hydrophobic_cutoff))
+        if args.sasa:
+            if not isinstance(result, dict) or result.get('data') is None:
+                raise SystemExit(f'{name} carries no pocket (no data): --sasa needs the files of a sampling driver')
+            try:
+                sasa.append(pack.sasa(result['data'], graph_include, reference_ligand, args.probe, args.sasa_points))
+            except ValueError as e:
+                raise SystemExit(f'--sasa: {e}')
         reports.append(pack.quality(args.include, reference))
     rep = quality.QualityReport.merged(reports)
     print(f'Evaluate done! {rep.n_samples} samples in total.')
@@ -214,6 +232,13 @@ def main(argv=None):
                                    kind_hist={t: dict(zip(ia.names, ia.kind_hist[-1, k].tolist())) for k, t in enumerate(quality.INTERACTION_NAMES)})
         if eval_step == 'all':
             out['interactions']['curve'] = [nan_none(ia.summary(s)) for s in range(ia.num_frames)]
+    if args.sasa:
+        sa = quality.SasaReport.merged(sasa)
+        print('\n'.join(sa.lines(-1)))
+        nan_none = lambda d: {k: (None if x != x else x) for k, x in d.items()}
+        out['sasa'] = dict(nan_none(sa.summary(-1)), num_included=int(sa.n_included[-1]), probe=args.probe, points=args.sasa_points)
+        if eval_step == 'all':
+            out['sasa']['curve'] = [nan_none(sa.summary(s)) for s in range(sa.num_frames)]
     result_path = os.path.join(args.sample_path, 'eval_results')
     os.makedirs(result_path, exist_ok=True)
     with open(os.path.join(result_path, 'quality.json'), 'w') as f:

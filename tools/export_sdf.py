@@ -2,6 +2,7 @@
 
     python tools/export_sdf.py --sample_path DIR --out DIR [--eval_step -1] [--only-complete] [--largest-fragment] [--ring-aromatic]
                                 [--unique] [--clash-free] [--pocket-clash-free] [--min-hbonds N]
+                                [--min-buried-share X]
 
 Reads the ``result_{i}.pt`` files a sampling driver wrote (sorted as tools/evaluate_samples.py sorts them), takes the frame
 ``--eval_step`` of every sample (default -1: the final poses), builds the bond graph on the GPU (quality.bond_graph: bonds from the
@@ -24,6 +25,9 @@ again a convention); it combines with ``--clash-free`` and applies before ``--un
 ``--min-hbonds N`` writes only the samples with at least N hydrogen bonds to the protein (quality.pocket_interactions on the file's
 pocket: donor - acceptor pairs of heavy atoms closer than 3.5 A, the ligand's donors inferred from the valence deficit; DESIGN.md
 section 3, "Pocket interactions" -- a heuristic count, not a score); it combines with the two above and applies before ``--unique``.
+``--min-buried-share X`` writes only the samples of whose solvent-accessible surface the pocket covers at least the share X
+(quality.pocket_sasa on the file's pocket: buried / free area by Shrake-Rupley point counting with this project's radii and a 1.4 A
+probe; DESIGN.md section 3, "Solvent-accessible surface"); it combines with the three above and applies before ``--unique``.
 Prints one line per file and returns the counts.
 """
 from __future__ import annotations
@@ -58,8 +62,12 @@ def main(argv=None):
     ap.add_argument('--pocket-clash-free', action='store_true', help="only the samples without a clash with the protein (the file's data)")
     ap.add_argument('--min-hbonds', type=int, default=None, help="only the samples with at least N hydrogen bonds to the protein (the "
                     "file's data; this project's role heuristic)")
+    ap.add_argument('--min-buried-share', type=float, default=None, help="only the samples with at least this share of their "
+                    "solvent-accessible surface covered by the pocket (the file's data; 0 .. 1)")
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
+    if args.min_buried_share is not None and not 0.0 <= args.min_buried_share <= 1.0:
+        raise SystemExit(f'--min-buried-share is a share, 0 .. 1 (got {args.min_buried_share})')
     files = result_files(args.sample_path, args.eval_num_examples)
     if not files:
         raise SystemExit(f'no result_*.pt under {args.sample_path}')
@@ -71,7 +79,7 @@ def main(argv=None):
         pos, v, ptr, sizes = pack.pos, pack.v, pack.ligand_ptr, pack.sizes
         g = quality.bond_graph(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, bond_profiles=(), return_fragments=True,
                                return_bonds=True, rings=args.ring_aromatic, device=args.device)
-        select = chosen = clash_free = pocket_clash_free = enough_hbonds = None
+        select = chosen = clash_free = pocket_clash_free = enough_hbonds = buried_enough = None
         if args.only_complete:
             chosen = g.complete[0]
         if args.clash_free:
@@ -92,6 +100,13 @@ def main(argv=None):
                                                         atom_enc_mode=args.atom_enc_mode, device=args.device).n_hbonds[0] >= args.min_hbonds
             chosen = enough_hbonds if chosen is None else chosen & enough_hbonds
             select = enough_hbonds.cpu().numpy() & (True if select is None else select)
+        if args.min_buried_share is not None:
+            if not isinstance(result, dict) or result.get('data') is None:
+                raise SystemExit(f'{name} carries no pocket (no data): --min-buried-share needs the files of a sampling driver')
+            buried_enough = quality.pocket_sasa(*quality.pocket_of(result['data']), pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode,
+                                                device=args.device).buried_share[0] >= args.min_buried_share
+            chosen = buried_enough if chosen is None else chosen & buried_enough
+            select = buried_enough.cpu().numpy() & (True if select is None else select)
         if args.unique:
             fp = quality.fingerprints(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, device=args.device)
             first = fp.similarity(include=None if chosen is None else chosen[None])['first_equal'][0].cpu().numpy()
@@ -110,6 +125,8 @@ def main(argv=None):
             out[stem]['pocket_clash_free'] = int(pocket_clash_free.sum())
         if enough_hbonds is not None:
             out[stem]['min_hbonds'] = int(enough_hbonds.sum())
+        if buried_enough is not None:
+            out[stem]['min_buried_share'] = int(buried_enough.sum())
     return out
 
 

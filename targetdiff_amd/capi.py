@@ -1179,23 +1179,53 @@ def geometry_report(pos, v, ligand_ptr, class_z, class_aromatic=None, profiles=(
 POCKET_MAX_KINDS, POCKET_ELEMENTS = 64, 6                                   # TD_POCKET_* (csrc/td_internal.h)
 
 
-def _pocket_inputs(pos, protein_pos, protein_elem, protein_kind, n_kinds, contact_cutoff, clash_threshold, ref_bits, check=True):
-    """The pocket's side of a pocket_report call: shapes, dtypes and devices, the number of kinds, the cutoff, the table and the
-    reference words; with ``check`` the elements and kinds are looked at on the host (one synchronisation).  Returns (N_p, W, the
-    table as float64 numpy [48] or None)."""
+def _protein_inputs(pos, protein_pos, protein_elem, protein_kind=None, n_kinds=None, protein_role=None, ref_bits=None, ref_lead=(),
+                    who=None, beside=(), what='the pocket', check=True):
+    """The protein side of a pocket_report, interaction_report or sasa_report call: shapes, dtypes and devices of ``protein_pos``,
+    ``protein_elem`` and, where the report takes them, ``protein_kind`` with ``n_kinds``, ``protein_role`` and the reference words
+    ``ref_bits`` [*ref_lead, W] as ``who`` returns them; ``beside``: further tensors that must live on the device of the pack.  With
+    ``check`` the elements, kinds and roles are looked at on the host (one synchronisation each).  Returns (N_p, W)."""
     if protein_pos.dim() != 2 or protein_pos.shape[1] != 3:
         raise ValueError(f'protein_pos must be [N_p, 3] (got {tuple(protein_pos.shape)})')
     Np = protein_pos.shape[0]
     W = (Np + 63) // 64
-    if tuple(protein_elem.shape) != (Np,) or tuple(protein_kind.shape) != (Np,):
-        raise ValueError(f'protein_elem / protein_kind must be [{Np}] (got {tuple(protein_elem.shape)}, {tuple(protein_kind.shape)})')
-    if protein_pos.dtype != torch.float32 or protein_elem.dtype != torch.int32 or protein_kind.dtype != torch.int32:
-        raise ValueError(f'protein_pos / protein_elem / protein_kind must be fp32 / int32 / int32 (got {protein_pos.dtype}, '
-                         f'{protein_elem.dtype}, {protein_kind.dtype})')
-    if any(t.device != pos.device for t in (protein_pos, protein_elem, protein_kind)) or (ref_bits is not None and ref_bits.device != pos.device):
-        raise ValueError(f'the pocket must live on the device of the pack ({pos.device})')
-    if not 1 <= int(n_kinds) <= POCKET_MAX_KINDS:
+    per_atom = [protein_elem] if protein_kind is None else [protein_elem, protein_kind]
+    names = 'protein_elem' if protein_kind is None else 'protein_elem / protein_kind'
+    if any(tuple(t.shape) != (Np,) for t in per_atom):
+        raise ValueError(f'{names} must be [{Np}] (got {", ".join(str(tuple(t.shape)) for t in per_atom)})')
+    if protein_pos.dtype != torch.float32 or any(t.dtype != torch.int32 for t in per_atom):
+        raise ValueError(f'protein_pos / {names} must be {" / ".join(["fp32"] + ["int32"] * len(per_atom))} (got '
+                         f'{", ".join(str(t.dtype) for t in [protein_pos] + per_atom)})')
+    if protein_role is not None and (tuple(protein_role.shape) != (Np,) or protein_role.dtype != torch.int32):
+        raise ValueError(f'protein_role must be [{Np}] int32 (got {tuple(protein_role.shape)} {protein_role.dtype})')
+    if any(t is not None and t.device != pos.device for t in [protein_pos, protein_role, ref_bits] + per_atom + list(beside)):
+        raise ValueError(f'{what} must live on the device of the pack ({pos.device})')
+    if protein_kind is not None and not 1 <= int(n_kinds) <= POCKET_MAX_KINDS:
         raise ValueError(f'n_kinds is 1 .. {POCKET_MAX_KINDS} (got {n_kinds})')
+    if ref_bits is not None and (tuple(ref_bits.shape) != tuple(ref_lead) + (W,) or ref_bits.dtype != torch.int64):
+        raise ValueError(f'ref_bits must be [{", ".join(str(n) for n in tuple(ref_lead) + (W,))}] int64 words, as {who} returns bits (got '
+                         f'{tuple(ref_bits.shape)} {ref_bits.dtype})')
+    if check and Np > 0:
+        if int(protein_elem.min()) < -1 or int(protein_elem.max()) >= POCKET_ELEMENTS:
+            raise ValueError(f'protein_elem must be in [-1, {POCKET_ELEMENTS}): an index over H C N O S Se, or -1')
+        if protein_kind is not None and (int(protein_kind.min()) < -1 or int(protein_kind.max()) >= int(n_kinds)):
+            raise ValueError(f'protein_kind must be in [-1, {int(n_kinds)})')
+        if protein_role is not None and (int(protein_role.min()) < -1 or int(protein_role.max()) > (ROLE_DONOR | ROLE_ACCEPTOR)):
+            raise ValueError('protein_role must be -1 or a sum of DONOR = 1 and ACCEPTOR = 2: the device decides which carbons are hydrophobic')
+    return Np, W
+
+
+def _allocators(dev):
+    """(i32, z32, i64) of ``dev``: outputs by shape, int32 not initialised, int32 zeroed (an oversize molecule's atoms are not
+    written) and int64 not initialised"""
+    make = lambda fn, dtype: lambda *shape: fn(*shape, dtype=dtype, device=dev)
+    return make(torch.empty, torch.int32), make(torch.zeros, torch.int32), make(torch.empty, torch.int64)
+
+
+def _pocket_inputs(pos, protein_pos, protein_elem, protein_kind, n_kinds, contact_cutoff, clash_threshold, ref_bits, check=True):
+    """The pocket's side of a pocket_report call: what _protein_inputs checks of the pocket, the kinds and the reference words, then
+    the cutoff and the table.  Returns (N_p, W, the table as float64 numpy [48] or None)."""
+    Np, W = _protein_inputs(pos, protein_pos, protein_elem, protein_kind, n_kinds, ref_bits=ref_bits, who='pocket_report', check=check)
     if not (np.isfinite(float(contact_cutoff)) and float(contact_cutoff) > 0.0):
         raise ValueError(f'the contact cutoff must be finite and > 0 (got {contact_cutoff})')
     thr = None
@@ -1204,13 +1234,6 @@ def _pocket_inputs(pos, protein_pos, protein_elem, protein_kind, n_kinds, contac
         if thr.shape not in ((8, POCKET_ELEMENTS), (8 * POCKET_ELEMENTS,)) or not np.isfinite(thr).all():
             raise ValueError(f'clash_threshold is a finite [8, {POCKET_ELEMENTS}] table: H C N O F P S Cl by H C N O S Se')
         thr = np.ascontiguousarray(thr.reshape(-1))
-    if ref_bits is not None and (tuple(ref_bits.shape) != (W,) or ref_bits.dtype != torch.int64):
-        raise ValueError(f'ref_bits must be [{W}] int64 words, as pocket_report returns bits (got {tuple(ref_bits.shape)} {ref_bits.dtype})')
-    if check and Np > 0:
-        if int(protein_elem.min()) < -1 or int(protein_elem.max()) >= POCKET_ELEMENTS:
-            raise ValueError(f'protein_elem must be in [-1, {POCKET_ELEMENTS}): an index over H C N O S Se, or -1')
-        if int(protein_kind.min()) < -1 or int(protein_kind.max()) >= int(n_kinds):
-            raise ValueError(f'protein_kind must be in [-1, {int(n_kinds)})')
     return Np, W, thr
 
 
@@ -1230,8 +1253,7 @@ def pocket_report(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, protei
     lib = load_library()
     pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
     dev = pos.device
-    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-    z32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)    # an oversize molecule's atoms are not written
+    i32, z32, _ = _allocators(dev)
     out = dict(n_contacts=i32(S, B), n_contact_atoms=i32(S, B), n_pocket_atoms=i32(S, B),
                n_clashes=i32(S, B) if thr is not None else None, n_clash_atoms=i32(S, B) if thr is not None else None,
                min_dist=torch.empty(S, B, dtype=torch.float64, device=dev),
@@ -1254,21 +1276,13 @@ ROLE_DONOR, ROLE_ACCEPTOR, ROLE_HYDROPHOBIC, INTERACTION_TYPES = 1, 2, 4, 3   # 
 
 
 def _interaction_inputs(pos, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, cutoffs, ref_bits, check=True):
-    """The pocket's side of an interaction_report call: what _pocket_inputs checks of the pocket, then the roles, the three cutoffs and
-    the reference words; with ``check`` the roles are looked at on the host.  Returns (N_p, W)."""
-    Np, W, _ = _pocket_inputs(pos, protein_pos, protein_elem, protein_kind, n_kinds, 1.0, None, None, check)
-    if tuple(protein_role.shape) != (Np,) or protein_role.dtype != torch.int32:
-        raise ValueError(f'protein_role must be [{Np}] int32 (got {tuple(protein_role.shape)} {protein_role.dtype})')
-    if protein_role.device != pos.device or (ref_bits is not None and ref_bits.device != pos.device):
-        raise ValueError(f'the pocket must live on the device of the pack ({pos.device})')
+    """The pocket's side of an interaction_report call: what _protein_inputs checks of the pocket, the kinds, the roles and the
+    reference words, then the three cutoffs.  Returns (N_p, W)."""
+    Np, W = _protein_inputs(pos, protein_pos, protein_elem, protein_kind, n_kinds, protein_role, ref_bits, (INTERACTION_TYPES,),
+                            'interaction_report', check=check)
     for name, c in zip(('hbond', 'hydrophobic', 'hetero'), cutoffs):
         if not (np.isfinite(float(c)) and float(c) > 0.0):
             raise ValueError(f'the {name} cutoff must be finite and > 0 (got {c})')
-    if ref_bits is not None and (tuple(ref_bits.shape) != (INTERACTION_TYPES, W) or ref_bits.dtype != torch.int64):
-        raise ValueError(f'ref_bits must be [{INTERACTION_TYPES}, {W}] int64 words, as interaction_report returns bits (got '
-                         f'{tuple(ref_bits.shape)} {ref_bits.dtype})')
-    if check and Np > 0 and (int(protein_role.min()) < -1 or int(protein_role.max()) > (ROLE_DONOR | ROLE_ACCEPTOR)):
-        raise ValueError('protein_role must be -1 or a sum of DONOR = 1 and ACCEPTOR = 2: the device decides which carbons are hydrophobic')
     return Np, W
 
 
@@ -1291,8 +1305,7 @@ def interaction_report(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, p
     pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
     dev = pos.device
     T = INTERACTION_TYPES
-    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-    z32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)    # an oversize molecule's atoms are not written
+    i32, z32, _ = _allocators(dev)
     mol = ('n_donated', 'n_accepted', 'n_hbonds', 'n_hydrophobic', 'n_hb_atoms', 'n_donors', 'n_acceptors', 'n_hydrophobic_atoms')
     out = dict(protein_role=i32(Np), **{k: i32(S, B) for k in mol},
                n_ref_common=(z32 if W == 0 else i32)(S, B, T) if ref_bits is not None else None,   # no words: nothing is in common
@@ -1322,19 +1335,11 @@ def _sasa_inputs(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, ligand_
     reach tables and the directions; with ``check`` the elements, the directions and the coordinates are looked at on the host (one
     synchronisation each).  Returns (S, N_l, B, class table, N_p, W, P, ligand reaches [8], protein reaches [6] as float64 numpy)."""
     S, Nl, B, cz, _, _ = _bond_inputs(pos, v, ligand_ptr, class_z, None, include, (), check)
-    if protein_pos.dim() != 2 or protein_pos.shape[1] != 3:
-        raise ValueError(f'protein_pos must be [N_p, 3] (got {tuple(protein_pos.shape)})')
-    Np = protein_pos.shape[0]
-    if tuple(protein_elem.shape) != (Np,):
-        raise ValueError(f'protein_elem must be [{Np}] (got {tuple(protein_elem.shape)})')
-    if protein_pos.dtype != torch.float32 or protein_elem.dtype != torch.int32:
-        raise ValueError(f'protein_pos / protein_elem must be fp32 / int32 (got {protein_pos.dtype}, {protein_elem.dtype})')
+    Np, W = _protein_inputs(pos, protein_pos, protein_elem, beside=(dirs,), what='the pocket and the directions', check=check)
     if dirs.dim() != 2 or dirs.shape[1] != 3 or not 1 <= dirs.shape[0] <= SASA_MAX_POINTS:
         raise ValueError(f'dirs must be [P, 3] with 1 <= P <= {SASA_MAX_POINTS} (got {tuple(dirs.shape)})')
     if dirs.dtype != torch.float64:
         raise ValueError(f'dirs must be float64 (got {dirs.dtype})')
-    if any(t.device != pos.device for t in (protein_pos, protein_elem, dirs)):
-        raise ValueError(f'the pocket and the directions must live on the device of the pack ({pos.device})')
     if 512 * Np > 0x7fffffff or S * Np > 0x7fffffff or S * B * 8 > 0x7fffffff:
         raise ValueError(f'512 N_p, S N_p and 8 S B must fit 31 bits (S = {S}, B = {B}, N_p = {Np})')
     reach = []
@@ -1344,14 +1349,12 @@ def _sasa_inputs(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, ligand_
             raise ValueError(f'{name} is [{size}], finite and > 0: van der Waals radius + probe per element')
         reach.append(np.ascontiguousarray(r))
     if check:
-        if Np > 0 and (int(protein_elem.min()) < -1 or int(protein_elem.max()) >= POCKET_ELEMENTS):
-            raise ValueError(f'protein_elem must be in [-1, {POCKET_ELEMENTS}): an index over H C N O S Se, or -1')
         if not bool(torch.isfinite(dirs).all()) or not float(((dirs * dirs).sum(1) - 1.0).abs().max()) <= SASA_UNIT_TOL:
             raise ValueError(f'dirs must be finite unit vectors (| |u|^2 - 1 | <= {SASA_UNIT_TOL})')
         for name, t in (('pos', pos), ('protein_pos', protein_pos)):
             if t.numel() and not float(t.abs().max()) <= SASA_COORD_MAX:
                 raise ValueError(f'{name} must be finite with |coordinate| <= {SASA_COORD_MAX:g}')
-    return S, Nl, B, cz, Np, (Np + 63) // 64, dirs.shape[0], reach[0], reach[1]
+    return S, Nl, B, cz, Np, W, dirs.shape[0], reach[0], reach[1]
 
 
 def sasa_report(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, ligand_reach, protein_reach, dirs, include=None,
@@ -1370,9 +1373,7 @@ def sasa_report(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, ligand_r
     lib = load_library()
     pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
     dev = pos.device
-    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-    z32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)    # an oversize molecule's atoms are not written
-    i64 = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
+    i32, z32, i64 = _allocators(dev)
     out = dict(free=i32(S, B, 8), bound=i32(S, B, 8), pocket_buried=i32(S, B, POCKET_ELEMENTS),
                atom_free=z32(S, Nl) if return_atoms else None, atom_bound=z32(S, Nl) if return_atoms else None,
                bits=i64(S, B, W) if return_bits else None, pocket_free=i32(Np), pocket_mask=i64(Np, 4), pocket_buried_sum=i64(S, Np))

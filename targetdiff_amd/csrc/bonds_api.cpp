@@ -25,6 +25,31 @@ int bond_pack(const char *who, TdBondArgs &a, const float *d_pos, const int64_t 
     a.S = (int)S; a.B = (int)B; a.K = K; a.capacity = n_bonds;
     return TD_OK;
 }
+
+// The protein side that the contact and the interaction report share, checked and filled: N_p with S * planes * N_p (`fits`: what the
+// entry point's message says must fit), the number of kinds, the pocket's arrays and the sums by kind and by protein atom.
+int protein_side(const char *who, TdProteinSide &p, int64_t S, int64_t N_p, int planes, const char *fits, const float *d_protein_pos,
+                 const int32_t *d_protein_elem, const int32_t *d_protein_kind, int32_t n_kinds, const uint64_t *d_ref_bits, uint64_t *d_bits,
+                 int64_t *d_kind_hist, int32_t *d_pocket_freq) {
+    if (N_p < 0 || N_p > 0x7fffffff / TD_BOND_MAX_ATOMS || S * planes * N_p > 0x7fffffff) {      // a molecule's pairs are counted in an int32
+        td_set_error("%s: bad argument (N_p = %lld; %s must fit 31 bits)", who, (long long)N_p, fits);
+        return TD_EINVAL;
+    }
+    if (n_kinds < 1 || n_kinds > TD_POCKET_MAX_KINDS) {
+        td_set_error("%s: 1 .. %d kinds of protein atoms (got %d)", who, TD_POCKET_MAX_KINDS, (int)n_kinds);
+        return TD_EINVAL;
+    }
+    if ((N_p > 0 && (!d_protein_pos || !d_protein_elem || !d_protein_kind)) || (S > 0 && (!d_kind_hist || (N_p > 0 && !d_pocket_freq)))) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    p.ppos = d_protein_pos; p.pelem = d_protein_elem; p.pkind = d_protein_kind;
+    p.Np = (int)N_p; p.W = (int)((N_p + 63) / 64); p.n_kinds = n_kinds;
+    p.ref_bits = reinterpret_cast<const unsigned long long *>(d_ref_bits);
+    p.bits = reinterpret_cast<unsigned long long *>(d_bits); p.kind_hist = reinterpret_cast<unsigned long long *>(d_kind_hist);
+    p.pocket_freq = d_pocket_freq;
+    return TD_OK;
+}
 }  // namespace
 
 extern "C" int td_bond_graph(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
@@ -229,29 +254,19 @@ extern "C" int td_pocket_report(const float *d_pos, const int64_t *d_v, const in
     const char *who = "td_pocket_report";
     TdPocketArgs g;
     if (const int rc = bond_pack(who, g.b, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, nullptr)) return rc;
-    if (N_p < 0 || N_p > 0x7fffffff / TD_BOND_MAX_ATOMS || S * N_p > 0x7fffffff) {      // a molecule's pairs are counted in an int32
-        td_set_error("%s: bad argument (N_p = %lld; 512 N_p and S * N_p must fit 31 bits)", who, (long long)N_p);
-        return TD_EINVAL;
-    }
-    if (n_kinds < 1 || n_kinds > TD_POCKET_MAX_KINDS) {
-        td_set_error("%s: 1 .. %d kinds of protein atoms (got %d)", who, TD_POCKET_MAX_KINDS, (int)n_kinds);
-        return TD_EINVAL;
-    }
+    if (const int rc = protein_side(who, g.p, S, N_p, 1, "512 N_p and S * N_p", d_protein_pos, d_protein_elem, d_protein_kind, n_kinds,
+                                    d_ref_bits, d_bits, d_kind_hist, d_pocket_freq)) return rc;
     if (!std::isfinite(contact_cutoff) || !(contact_cutoff > 0.0)) {
         td_set_error("%s: the contact cutoff must be finite and > 0", who);
         return TD_EINVAL;
     }
-    if (N_p > 0 && (!d_protein_pos || !d_protein_elem || !d_protein_kind)) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
-    if ((S > 0 && (!d_kind_hist || (N_p > 0 && !d_pocket_freq))) ||
-        (S > 0 && B > 0 && (!d_n_contacts || !d_n_contact_atoms || !d_n_pocket_atoms || !d_min_dist ||
-                            (clash_threshold && (!d_n_clashes || !d_n_clash_atoms)) || (d_ref_bits && !d_n_ref_common)))) {
+    if (S > 0 && B > 0 && (!d_n_contacts || !d_n_contact_atoms || !d_n_pocket_atoms || !d_min_dist ||
+                           (clash_threshold && (!d_n_clashes || !d_n_clash_atoms)) || (d_ref_bits && !d_n_ref_common))) {
         td_set_error("%s: null pointer", who);
         return TD_EINVAL;
     }
     g.b.include = d_include;
-    g.ppos = d_protein_pos; g.pelem = d_protein_elem; g.pkind = d_protein_kind;
-    g.ref_bits = reinterpret_cast<const unsigned long long *>(d_ref_bits);
-    g.Np = (int)N_p; g.W = (int)((N_p + 63) / 64); g.n_kinds = n_kinds; g.cutoff = contact_cutoff;
+    g.cutoff = contact_cutoff;
     if (clash_threshold) {
         g.clash = true;
         for (int k = 0; k < 8 * TD_POCKET_ELEMENTS; ++k) g.clash_thr[k] = clash_threshold[k];
@@ -259,8 +274,6 @@ extern "C" int td_pocket_report(const float *d_pos, const int64_t *d_v, const in
     g.n_contacts = d_n_contacts; g.n_contact_atoms = d_n_contact_atoms; g.n_pocket_atoms = d_n_pocket_atoms;
     g.n_clashes = d_n_clashes; g.n_clash_atoms = d_n_clash_atoms; g.min_dist = d_min_dist; g.n_ref_common = d_n_ref_common;
     g.atom_contacts = d_atom_contacts; g.atom_clash = d_atom_clash;
-    g.bits = reinterpret_cast<unsigned long long *>(d_bits); g.kind_hist = reinterpret_cast<unsigned long long *>(d_kind_hist);
-    g.pocket_freq = d_pocket_freq;
     return td_launch_pocket_report(g, static_cast<hipStream_t>(stream));
 }
 
@@ -276,41 +289,27 @@ extern "C" int td_interaction_report(const float *d_pos, const int64_t *d_v, con
     const char *who = "td_interaction_report";
     TdInteractionArgs g;
     if (const int rc = bond_pack(who, g.b, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, nullptr)) return rc;
-    if (N_p < 0 || N_p > 0x7fffffff / TD_BOND_MAX_ATOMS || S * N_p > 0x7fffffff / TD_INTERACTION_TYPES) {   // a molecule's pairs are counted in an int32
-        td_set_error("%s: bad argument (N_p = %lld; 512 N_p and 3 S * N_p must fit 31 bits)", who, (long long)N_p);
-        return TD_EINVAL;
-    }
-    if (n_kinds < 1 || n_kinds > TD_POCKET_MAX_KINDS) {
-        td_set_error("%s: 1 .. %d kinds of protein atoms (got %d)", who, TD_POCKET_MAX_KINDS, (int)n_kinds);
-        return TD_EINVAL;
-    }
+    if (const int rc = protein_side(who, g.p, S, N_p, TD_INTERACTION_TYPES, "512 N_p and 3 S * N_p", d_protein_pos, d_protein_elem,
+                                    d_protein_kind, n_kinds, d_ref_bits, d_bits, d_kind_hist, d_pocket_freq)) return rc;
     for (const double c : {hbond_cutoff, hydrophobic_cutoff, hetero_cutoff})
         if (!std::isfinite(c) || !(c > 0.0)) {
             td_set_error("%s: the hbond, hydrophobic and hetero cutoffs must be finite and > 0", who);
             return TD_EINVAL;
         }
-    if (N_p > 0 && (!d_protein_pos || !d_protein_elem || !d_protein_kind || !d_protein_role || !d_protein_role_out)) {
-        td_set_error("%s: null pointer", who);
-        return TD_EINVAL;
-    }
-    if ((S > 0 && (!d_kind_hist || (N_p > 0 && !d_pocket_freq))) ||
+    if ((N_p > 0 && (!d_protein_role || !d_protein_role_out)) ||
         (S > 0 && B > 0 && (!d_n_donated || !d_n_accepted || !d_n_hbonds || !d_n_hydrophobic || !d_n_hb_atoms || !d_n_donors ||
                             !d_n_acceptors || !d_n_hydrophobic_atoms || (d_ref_bits && !d_n_ref_common)))) {
         td_set_error("%s: null pointer", who);
         return TD_EINVAL;
     }
     g.b.include = d_include;
-    g.ppos = d_protein_pos; g.pelem = d_protein_elem; g.pkind = d_protein_kind; g.prole = d_protein_role;
-    g.ref_bits = reinterpret_cast<const unsigned long long *>(d_ref_bits);
-    g.Np = (int)N_p; g.W = (int)((N_p + 63) / 64); g.n_kinds = n_kinds;
+    g.prole = d_protein_role;
     g.hbond_cutoff = hbond_cutoff; g.hydrophobic_cutoff = hydrophobic_cutoff; g.hetero_cutoff = hetero_cutoff;
     g.role_out = d_protein_role_out;
     g.n_donated = d_n_donated; g.n_accepted = d_n_accepted; g.n_hbonds = d_n_hbonds; g.n_hydrophobic = d_n_hydrophobic;
     g.n_hb_atoms = d_n_hb_atoms; g.n_donors = d_n_donors; g.n_acceptors = d_n_acceptors; g.n_hydrophobic_atoms = d_n_hydrophobic_atoms;
     g.n_ref_common = d_n_ref_common;
     g.atom_role = d_atom_role; g.atom_hbonds = d_atom_hbonds; g.atom_hydrophobic = d_atom_hydrophobic;
-    g.bits = reinterpret_cast<unsigned long long *>(d_bits); g.kind_hist = reinterpret_cast<unsigned long long *>(d_kind_hist);
-    g.pocket_freq = d_pocket_freq;
     return td_launch_interaction_report(g, static_cast<hipStream_t>(stream));
 }
 

@@ -17,30 +17,25 @@
 //                          atom it hits.
 // Every loop is bounded by the molecule's size or the pocket's.  All outputs are integers: nothing depends on the grid or on the order
 // of arrival.  No floating-point atomic.  The answer to an oversize molecule (-1) is that of bonds.hip.
-#include "td_bond_graph.h"
+#include "td_pocket_walk.h"
 
-#include <cmath>
-#include <limits>
-
-constexpr int IX_T = TD_POCKET_THREADS, IX_WAVES = IX_T / 64, IX_K = TD_POCKET_MAX_KINDS, IX_TYPES = TD_INTERACTION_TYPES;
+constexpr int IX_T = PW_T, IX_WAVES = PW_WAVES, IX_K = TD_POCKET_MAX_KINDS, IX_TYPES = TD_INTERACTION_TYPES;
 constexpr int IX_H = 0, IX_C = 1, IX_N = 2, IX_O = 3, IX_F = 4, IX_CL = 7;      // element indices of the ligand (H C N O F P S Cl)
 constexpr int IX_PC = 1, IX_PN = 2, IX_PO = 3;                                  // and of the protein (H C N O S Se)
 
 __global__ __launch_bounds__(IX_T) void protein_role_kernel(TdInteractionArgs g) {
     __shared__ float4 s_tile[IX_T];
-    const int tid = threadIdx.x, Np = g.Np, nk = g.n_kinds;
+    const TdProteinSide &ps = g.p;
+    const int tid = threadIdx.x, Np = ps.Np, nk = ps.n_kinds;
     const int j = blockIdx.x * IX_T + tid;
-    auto takes_part = [&](int at) {
-        const int e = g.pelem[at], k = g.pkind[at];
-        return e >= 0 && e < TD_POCKET_ELEMENTS && k >= 0 && k < nk && g.prole[at] >= 0;
-    };
+    auto takes_part = [&](int at) { return pw_takes_part(ps.pelem[at], ps.pkind[at], nk) && g.prole[at] >= 0; };
     int role = -1;
     bool carbon = false;
     double X = 0.0, Y = 0.0, Z = 0.0;
     if (j < Np && takes_part(j)) {
         role = g.prole[j] & (TD_ROLE_DONOR | TD_ROLE_ACCEPTOR);
-        carbon = g.pelem[j] == IX_PC;
-        const float *p = g.ppos + (size_t)j * 3;
+        carbon = ps.pelem[j] == IX_PC;
+        const float *p = ps.ppos + (size_t)j * 3;
         X = (double)p[0]; Y = (double)p[1]; Z = (double)p[2];
     }
     bool polar_near = false;
@@ -48,8 +43,8 @@ __global__ __launch_bounds__(IX_T) void protein_role_kernel(TdInteractionArgs g)
         const int k = t0 + tid;
         float4 q = make_float4(0.f, 0.f, 0.f, __int_as_float(0));
         if (k < Np) {
-            const int e = g.pelem[k];
-            const float *p = g.ppos + (size_t)k * 3;
+            const int e = ps.pelem[k];
+            const float *p = ps.ppos + (size_t)k * 3;
             q = make_float4(p[0], p[1], p[2], __int_as_float((e == IX_PN || e == IX_PO) && takes_part(k) ? 1 : 0));
         }
         __syncthreads();                                                        // the last tile has been read
@@ -101,17 +96,17 @@ __global__ __launch_bounds__(IX_T) void interaction_kernel(TdInteractionArgs g) 
     __shared__ int s_elem[TD_QUALITY_MAX_CLASSES];
     // donated, accepted, hbonds, hydrophobic pairs; atoms in an H-bond; donors, acceptors, hydrophobic atoms; common per type
     __shared__ int s_cnt[8 + IX_TYPES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, wave = tid >> 6;
     const BgMol m = bg_molecule<BG_MAX>(a);                                     // one instantiation takes every size: m.mine is not used
-    const int Np = g.Np, W = g.W, nk = g.n_kinds;
+    const TdProteinSide &ps = g.p;
+    const int Np = ps.Np, nk = ps.n_kinds;
     if (m.bad) {                                                                // workgroup-uniform
         if (tid == 0) {
             g.n_donated[m.mol] = g.n_accepted[m.mol] = g.n_hbonds[m.mol] = g.n_hydrophobic[m.mol] = g.n_hb_atoms[m.mol] = -1;
             g.n_donors[m.mol] = g.n_acceptors[m.mol] = g.n_hydrophobic_atoms[m.mol] = -1;
         }
-        if (g.ref_bits && tid < IX_TYPES) g.n_ref_common[m.mol * IX_TYPES + tid] = -1;
-        if (g.bits)
-            for (int w = tid; w < IX_TYPES * W; w += IX_T) g.bits[m.mol * (size_t)(IX_TYPES * W) + w] = 0ull;
+        if (ps.ref_bits && tid < IX_TYPES) g.n_ref_common[m.mol * IX_TYPES + tid] = -1;
+        pw_no_bits<IX_TYPES>(ps, m.mol);
         return;
     }
     const int n = m.n;
@@ -122,12 +117,7 @@ __global__ __launch_bounds__(IX_T) void interaction_kernel(TdInteractionArgs g) 
     for (int i = tid; i < n; i += IX_T) s_ahb[i] = s_ahy[i] = 0;
     if (tid < 8 + IX_TYPES) s_cnt[tid] = 0;
     __syncthreads();
-    for (int i = tid; i < n; i += IX_T) {                                       // atom i as (x, y, z, element index or -1 for a class outside [0, K))
-        const size_t at = (size_t)m.s * (size_t)a.Nl + (size_t)(m.l0 + i);
-        const float *p = a.pos + at * 3;
-        const int64_t c = a.v[at];
-        s_at[i] = make_float4(p[0], p[1], p[2], __int_as_float(c >= 0 && c < a.K ? s_elem[(int)c] : -1));
-    }
+    pw_stage(a, m, s_elem, s_at);
     __syncthreads();
     for (int i = tid; i < n; i += IX_T) {
         const int role = ix_ligand_role(i, n, s_at, s_thr);
@@ -145,12 +135,7 @@ __global__ __launch_bounds__(IX_T) void interaction_kernel(TdInteractionArgs g) 
         const int j = r * IX_T + tid;
         int pr = -1, kp = 0, touched = 0;                                       // touched: bit t, hit by an interaction of type t
         double X = 0.0, Y = 0.0, Z = 0.0;
-        if (j < Np) {
-            pr = g.role_out[j];                                                 // >= 0: the atom takes part, so its kind is in range
-            kp = g.pkind[j];
-            const float *p = g.ppos + (size_t)j * 3;
-            X = (double)p[0]; Y = (double)p[1]; Z = (double)p[2];
-        }
+        if (pw_protein_atom(ps, j, kp, X, Y, Z)) pr = g.role_out[j];            // >= 0: the atom takes part, so its kind is in range
         if (__ballot(pr > 0) != 0ull) {                                         // wave-uniform: an atom without a role bit hits nothing
             for (int i = 0; i < n; ++i) {
                 const int lr = s_role[i];                                       // every lane reads the same address: an LDS broadcast
@@ -189,12 +174,9 @@ __global__ __launch_bounds__(IX_T) void interaction_kernel(TdInteractionArgs g) 
 #pragma unroll
         for (int t = 0; t < IX_TYPES; ++t) {
             const bool hit = (touched >> t) & 1;
-            const unsigned long long word = __ballot(hit);
-            if (lane == 0 && wi < W) {                                          // wi >= W: no atom of the pocket, the word is 0
-                if (g.bits) g.bits[(m.mol * IX_TYPES + t) * (size_t)W + wi] = word;
-                if (g.ref_bits) common[t] += __popcll(word & g.ref_bits[(size_t)t * W + wi]);
-            }
-            if (inc && hit) atomicAdd(&g.pocket_freq[((size_t)m.s * IX_TYPES + t) * (size_t)Np + j], 1);
+            int hits = 0;                                                       // the atoms hit are not reported
+            pw_word<IX_TYPES>(ps, m.mol, t, wi, hit, hits, common[t]);
+            if (inc && hit) atomicAdd(&ps.pocket_freq[((size_t)m.s * IX_TYPES + t) * (size_t)Np + j], 1);
         }
     }
     if (nd) atomicAdd(&s_cnt[0], nd);
@@ -212,11 +194,7 @@ __global__ __launch_bounds__(IX_T) void interaction_kernel(TdInteractionArgs g) 
         if (g.atom_hydrophobic) g.atom_hydrophobic[at] = s_ahy[i];
         if (hb) atomicAdd(&s_cnt[4], 1);
     }
-    if (inc)
-        for (int k = tid; k < IX_TYPES * nk; k += IX_T) {
-            const unsigned int c = s_hist[k];
-            if (c) atomicAdd(&g.kind_hist[(size_t)m.s * (size_t)(IX_TYPES * nk) + k], (unsigned long long)c);
-        }
+    if (inc) bg_flush_hist<IX_T>(s_hist, IX_TYPES * nk, ps.kind_hist + (size_t)m.s * (size_t)(IX_TYPES * nk));
     __syncthreads();
     if (tid == 0) {
         g.n_donated[m.mol] = s_cnt[0];
@@ -228,27 +206,17 @@ __global__ __launch_bounds__(IX_T) void interaction_kernel(TdInteractionArgs g) 
         g.n_acceptors[m.mol] = s_cnt[6];
         g.n_hydrophobic_atoms[m.mol] = s_cnt[7];
     }
-    if (g.ref_bits && tid < IX_TYPES) g.n_ref_common[m.mol * IX_TYPES + tid] = s_cnt[8 + tid];
+    if (ps.ref_bits && tid < IX_TYPES) g.n_ref_common[m.mol * IX_TYPES + tid] = s_cnt[8 + tid];
 }
 
-// The limit of the root is that of td_launch_pocket_report, with L the larger of the two pair cutoffs: reject2 is the float64 above
-// rn(L L), a pair with d2 >= reject2 has a rounded root >= L and is below neither cutoff, so skipping its root removes no interaction.
-// The protein roles are resolved first, on the same stream; the pair kernel reads them.
+// The limit of the root (pw_reject2) is taken of the larger of the two pair cutoffs.  The protein roles are resolved first, on the
+// same stream; the pair kernel reads them.
 int td_launch_interaction_report(const TdInteractionArgs &args, hipStream_t s) {
     TdInteractionArgs g = args;
-    const double L = std::fmax(g.hbond_cutoff, g.hydrophobic_cutoff);
-    g.reject2 = std::nextafter(L * L, std::numeric_limits<double>::infinity());
-    const int64_t M = (int64_t)g.b.S * g.b.B;
-    if (g.b.S > 0) {
-        TD_CHECK_HIP(hipMemsetAsync(g.kind_hist, 0, (size_t)g.b.S * IX_TYPES * g.n_kinds * sizeof(unsigned long long), s));
-        if (g.Np > 0) TD_CHECK_HIP(hipMemsetAsync(g.pocket_freq, 0, (size_t)g.b.S * IX_TYPES * g.Np * sizeof(int32_t), s));
-    }
-    if (g.Np > 0) {
-        protein_role_kernel<<<dim3((unsigned)((g.Np + IX_T - 1) / IX_T)), dim3(IX_T), 0, s>>>(g);
+    g.reject2 = pw_reject2(std::fmax(g.hbond_cutoff, g.hydrophobic_cutoff));
+    if (g.p.Np > 0) {
+        protein_role_kernel<<<dim3((unsigned)((g.p.Np + IX_T - 1) / IX_T)), dim3(IX_T), 0, s>>>(g);
         TD_CHECK_HIP(hipGetLastError());
     }
-    if (M == 0) return TD_OK;
-    interaction_kernel<<<dim3((unsigned)M), dim3(IX_T), 0, s>>>(g);
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    return pw_launch(interaction_kernel, g, IX_TYPES, IX_TYPES, s);
 }

@@ -14,12 +14,9 @@
 // Every loop is bounded by the molecule's size or the pocket's.  All outputs but min_dist are integers and min_dist is a minimum:
 // nothing depends on the grid or on the order of arrival.  No floating-point atomic.  The answer to an oversize molecule (-1) is that
 // of bonds.hip.
-#include "td_bond_graph.h"
+#include "td_pocket_walk.h"
 
-#include <cmath>
-#include <limits>
-
-constexpr int PK_T = TD_POCKET_THREADS, PK_WAVES = PK_T / 64, PK_E = TD_POCKET_ELEMENTS, PK_K = TD_POCKET_MAX_KINDS;
+constexpr int PK_T = PW_T, PK_WAVES = PW_WAVES, PK_E = TD_POCKET_ELEMENTS, PK_K = TD_POCKET_MAX_KINDS;
 
 __global__ __launch_bounds__(PK_T) void pocket_kernel(TdPocketArgs g) {
     const TdBondArgs &a = g.b;
@@ -31,16 +28,16 @@ __global__ __launch_bounds__(PK_T) void pocket_kernel(TdPocketArgs g) {
     __shared__ int s_cnt[6];                                                    // contacts, clashes, pocket atoms, common, contact atoms, clash atoms
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const BgMol m = bg_molecule<BG_MAX>(a);                                     // one instantiation takes every size: m.mine is not used
-    const int Np = g.Np, W = g.W, nk = g.n_kinds;
+    const TdProteinSide &ps = g.p;
+    const int Np = ps.Np, nk = ps.n_kinds;
     if (m.bad) {                                                                // workgroup-uniform
         if (tid == 0) {
             g.n_contacts[m.mol] = g.n_contact_atoms[m.mol] = g.n_pocket_atoms[m.mol] = -1;
             if (g.clash) g.n_clashes[m.mol] = g.n_clash_atoms[m.mol] = -1;
-            if (g.ref_bits) g.n_ref_common[m.mol] = -1;
+            if (ps.ref_bits) g.n_ref_common[m.mol] = -1;
             g.min_dist[m.mol] = std::numeric_limits<double>::infinity();
         }
-        if (g.bits)
-            for (int w = tid; w < W; w += PK_T) g.bits[m.mol * (size_t)W + w] = 0ull;
+        pw_no_bits<1>(ps, m.mol);
         return;
     }
     const int n = m.n;
@@ -51,12 +48,7 @@ __global__ __launch_bounds__(PK_T) void pocket_kernel(TdPocketArgs g) {
     for (int i = tid; i < n; i += PK_T) s_acon[i] = s_acl[i] = 0;
     if (tid < 6) s_cnt[tid] = 0;
     __syncthreads();
-    for (int i = tid; i < n; i += PK_T) {                                       // atom i as (x, y, z, element index or -1 for a class outside [0, K))
-        const size_t at = (size_t)m.s * (size_t)a.Nl + (size_t)(m.l0 + i);
-        const float *p = a.pos + at * 3;
-        const int64_t c = a.v[at];
-        s_at[i] = make_float4(p[0], p[1], p[2], __int_as_float(c >= 0 && c < a.K ? s_elem[(int)c] : -1));
-    }
+    pw_stage(a, m, s_elem, s_at);
     __syncthreads();
 
     int nc = 0, ncl = 0, pocket = 0, common = 0;
@@ -67,12 +59,9 @@ __global__ __launch_bounds__(PK_T) void pocket_kernel(TdPocketArgs g) {
         bool act = false, touched = false;
         int ep = 0, kp = 0;
         double X = 0.0, Y = 0.0, Z = 0.0;
-        if (j < Np) {
-            ep = g.pelem[j];
-            kp = g.pkind[j];
-            act = ep >= 0 && ep < PK_E && kp >= 0 && kp < nk;
-            const float *p = g.ppos + (size_t)j * 3;
-            X = (double)p[0]; Y = (double)p[1]; Z = (double)p[2];
+        if (pw_protein_atom(ps, j, kp, X, Y, Z)) {
+            ep = ps.pelem[j];
+            act = pw_takes_part(ep, kp, nk);
         }
         if (__ballot(act) != 0ull) {                                            // wave-uniform: the last round leaves whole waves without an atom
             for (int i = 0; i < n; ++i) {
@@ -98,14 +87,8 @@ __global__ __launch_bounds__(PK_T) void pocket_kernel(TdPocketArgs g) {
                 }
             }
         }
-        const unsigned long long word = __ballot(touched);                      // protein atoms 64 (4 r + wave) .. + 63; every lane is here
-        const int wi = PK_WAVES * r + wave;
-        if (lane == 0 && wi < W) {                                              // wi >= W: no atom of the pocket, the word is 0
-            if (g.bits) g.bits[m.mol * (size_t)W + wi] = word;
-            pocket += __popcll(word);
-            if (g.ref_bits) common += __popcll(word & g.ref_bits[wi]);
-        }
-        if (inc && touched) atomicAdd(&g.pocket_freq[(size_t)m.s * (size_t)Np + j], 1);
+        pw_word<1>(ps, m.mol, 0, PK_WAVES * r + wave, touched, pocket, common);
+        if (inc && touched) atomicAdd(&ps.pocket_freq[(size_t)m.s * (size_t)Np + j], 1);
     }
     for (int off = 32; off > 0; off >>= 1) {
         const double o = __shfl_xor(min2, off);
@@ -125,11 +108,7 @@ __global__ __launch_bounds__(PK_T) void pocket_kernel(TdPocketArgs g) {
         if (c) atomicAdd(&s_cnt[4], 1);
         if (k) atomicAdd(&s_cnt[5], 1);
     }
-    if (inc)
-        for (int k = tid; k < 8 * nk; k += PK_T) {
-            const unsigned int c = s_hist[k];
-            if (c) atomicAdd(&g.kind_hist[(size_t)m.s * (size_t)(8 * nk) + k], (unsigned long long)c);
-        }
+    if (inc) bg_flush_hist<PK_T>(s_hist, 8 * nk, ps.kind_hist + (size_t)m.s * (size_t)(8 * nk));
     __syncthreads();
     if (tid == 0) {
         g.n_contacts[m.mol] = s_cnt[0];
@@ -139,17 +118,15 @@ __global__ __launch_bounds__(PK_T) void pocket_kernel(TdPocketArgs g) {
             g.n_clashes[m.mol] = s_cnt[1];
             g.n_clash_atoms[m.mol] = s_cnt[5];
         }
-        if (g.ref_bits) g.n_ref_common[m.mol] = s_cnt[3];
+        if (ps.ref_bits) g.n_ref_common[m.mol] = s_cnt[3];
         double lo = s_min[0];
         for (int w = 1; w < PK_WAVES; ++w) lo = s_min[w] < lo ? s_min[w] : lo;
         g.min_dist[m.mol] = sqrt(lo);                                           // +inf without pairs
     }
 }
 
-// The limit of the root: with L the larger of the contact cutoff and the table's largest threshold, reject2 is the float64 above
-// rn(L L), which is >= L^2 in the reals (rn(L L) is within half an ulp of it).  A pair with d2 >= reject2 has sqrt(d2) >= L in the reals,
-// so its rounded root is >= L too (rounding is monotone and L is a float64): it is below neither limit, and skipping its root removes
-// no contact and no clash.  float64 throughout; an infinite limit rejects nothing.  EXPERIMENTS.md "Pocket contacts" has what it saves.
+// The limit of the root (pw_reject2) is taken of L, the larger of the contact cutoff and the table's largest threshold; an infinite
+// limit rejects nothing.
 #ifndef TD_POCKET_EARLY_REJECT
 #define TD_POCKET_EARLY_REJECT 1
 #endif
@@ -159,15 +136,6 @@ int td_launch_pocket_report(const TdPocketArgs &args, hipStream_t s) {
     double L = g.cutoff;
     if (g.clash)
         for (int k = 0; k < 8 * PK_E; ++k) L = std::fmax(L, g.clash_thr[k]);
-    const double inf = std::numeric_limits<double>::infinity();
-    g.reject2 = TD_POCKET_EARLY_REJECT ? std::nextafter(L * L, inf) : inf;
-    const int64_t M = (int64_t)g.b.S * g.b.B;
-    if (g.b.S > 0) {
-        TD_CHECK_HIP(hipMemsetAsync(g.kind_hist, 0, (size_t)g.b.S * 8 * g.n_kinds * sizeof(unsigned long long), s));
-        if (g.Np > 0) TD_CHECK_HIP(hipMemsetAsync(g.pocket_freq, 0, (size_t)g.b.S * g.Np * sizeof(int32_t), s));
-    }
-    if (M == 0) return TD_OK;
-    pocket_kernel<<<dim3((unsigned)M), dim3(PK_T), 0, s>>>(g);
-    TD_CHECK_HIP(hipGetLastError());
-    return TD_OK;
+    g.reject2 = TD_POCKET_EARLY_REJECT ? pw_reject2(L) : std::numeric_limits<double>::infinity();
+    return pw_launch(pocket_kernel, g, 8, 1, s);
 }

@@ -511,15 +511,23 @@ int td_launch_geometry_report(const TdGeomArgs &a, hipStream_t s);
 // pocket.hip (td_pocket_report, DESIGN.md section 3, "Pocket contacts"): the pack and the include bytes in `b` (none of b's outputs is
 // used); one pocket of Np atoms for every molecule.  pelem: index over H C N O S Se, pkind in [0, n_kinds); an atom with either outside
 // its range takes part nowhere.  clash_thr[e_l * 6 + e_p], e_l over H C N O F P S Cl.  reject2: a pair whose squared distance is not
-// below it is below neither limit (the launcher forms it; +inf: no pair is rejected).  W = ceil(Np / 64) words of contact bits.
+// below it is below neither limit (the launcher forms it; +inf: no pair is rejected).  One plane of contact bits.
 // The launcher zeroes kind_hist and pocket_freq on the stream.
 constexpr int TD_POCKET_MAX_KINDS = 64, TD_POCKET_ELEMENTS = 6, TD_POCKET_THREADS = 256;
-struct TdPocketArgs {
-    TdBondArgs b;
+// The protein side of a pocket report, said once for the contacts and the interactions: the pocket, and the outputs that are indexed by
+// protein atom or by kind.  T is the report's number of bit planes (contacts 1, interactions 3).
+struct TdProteinSide {
     const float *ppos = nullptr;             // [Np,3]
     const int32_t *pelem = nullptr, *pkind = nullptr;                            // [Np]
-    const unsigned long long *ref_bits = nullptr;                                // [W] or null
-    int Np = 0, W = 0, n_kinds = 0;
+    int Np = 0, W = 0, n_kinds = 0;          // W = ceil(Np / 64)
+    const unsigned long long *ref_bits = nullptr;                                // [T,W] or null
+    unsigned long long *bits = nullptr;      // [S,B,T,W] or null
+    unsigned long long *kind_hist = nullptr; // [S,rows,n_kinds]: rows = 8 ligand elements (contacts), T (interactions)
+    int32_t *pocket_freq = nullptr;          // [S,T,Np]
+};
+struct TdPocketArgs {
+    TdBondArgs b;
+    TdProteinSide p;
     double cutoff = 0.0, reject2 = 0.0;
     bool clash = false;                      // clash_thr holds the table
     double clash_thr[8 * TD_POCKET_ELEMENTS] = {};
@@ -528,36 +536,29 @@ struct TdPocketArgs {
     double *min_dist = nullptr;              // [S,B]
     int32_t *n_ref_common = nullptr;         // [S,B], written when ref_bits
     int32_t *atom_contacts = nullptr, *atom_clash = nullptr;                     // [S,N_l] or null
-    unsigned long long *bits = nullptr;      // [S,B,W] or null
-    unsigned long long *kind_hist = nullptr; // [S,8,n_kinds]
-    int32_t *pocket_freq = nullptr;          // [S,Np]
 };
 int td_launch_pocket_report(const TdPocketArgs &a, hipStream_t s);
 // interactions.hip (td_interaction_report, DESIGN.md section 3, "Pocket interactions"): the pack and the include bytes in `b`; the pocket
-// as TdPocketArgs takes it, and prole: the donor / acceptor bits of the host's table or a negative number.  A protein atom takes part
+// as TdProteinSide holds it, and prole: the donor / acceptor bits of the host's table or a negative number.  A protein atom takes part
 // when its element and its kind are in range and its role is >= 0; role_out is then its role with the hydrophobic bit resolved on the
 // device (-1 for an atom that takes no part), and the pair kernel reads role_out alone.  reject2 as TdPocketArgs.  Three planes (ligand
 // donates, ligand accepts, hydrophobic) of W = ceil(Np / 64) words.  The launcher zeroes kind_hist and pocket_freq on the stream.
 constexpr int TD_ROLE_DONOR = 1, TD_ROLE_ACCEPTOR = 2, TD_ROLE_HYDROPHOBIC = 4, TD_INTERACTION_TYPES = 3;
 struct TdInteractionArgs {
     TdBondArgs b;
-    const float *ppos = nullptr;             // [Np,3]
-    const int32_t *pelem = nullptr, *pkind = nullptr, *prole = nullptr;          // [Np]
-    const unsigned long long *ref_bits = nullptr;                                // [3,W] or null
-    int Np = 0, W = 0, n_kinds = 0;
+    TdProteinSide p;
+    const int32_t *prole = nullptr;          // [Np]
     double hbond_cutoff = 0.0, hydrophobic_cutoff = 0.0, hetero_cutoff = 0.0, reject2 = 0.0;
     int32_t *role_out = nullptr;             // [Np]
     int32_t *n_donated = nullptr, *n_accepted = nullptr, *n_hbonds = nullptr, *n_hydrophobic = nullptr;      // [S,B] pairs
     int32_t *n_hb_atoms = nullptr, *n_donors = nullptr, *n_acceptors = nullptr, *n_hydrophobic_atoms = nullptr;   // [S,B] ligand atoms
     int32_t *n_ref_common = nullptr;         // [S,B,3], written when ref_bits
     int32_t *atom_role = nullptr, *atom_hbonds = nullptr, *atom_hydrophobic = nullptr;      // [S,N_l] or null
-    unsigned long long *bits = nullptr;      // [S,B,3,W] or null
-    unsigned long long *kind_hist = nullptr; // [S,3,n_kinds]
-    int32_t *pocket_freq = nullptr;          // [S,3,Np]
 };
 int td_launch_interaction_report(const TdInteractionArgs &a, hipStream_t s);
 // sasa.hip (td_sasa_report, DESIGN.md section 3, "Solvent-accessible surface"): the pack and the include bytes in `b` (none of b's
-// outputs is used); the pocket as TdPocketArgs takes it, without kinds.  lig_R over H C N O F P S Cl and prot_R over H C N O S Se: the
+// outputs is used); the pocket as TdProteinSide holds it, without kinds, in fields of its own (its kernels keep the argument block they
+// were measured with: EXPERIMENTS.md "Pocket reports").  lig_R over H C N O F P S Cl and prot_R over H C N O S Se: the
 // reach (van der Waals radius + probe) per element; dirs: P unit directions.  A candidate occluder is dropped only when its centre is
 // farther than (R_a + R_b) (1 + TD_SASA_CULL_REL) + TD_SASA_CULL_ABS: sasa.hip says why that changes no result.  W = ceil(Np / 64).
 // The launcher zeroes buried_sum and bits on the stream.

@@ -77,6 +77,8 @@ Several reports of one result share its pack, its host checks and its bond graph
 
     pack = quality.SamplePack(result, eval_step='all')
     rep, con, rings = pack.quality('complete'), pack.connectivity('complete'), pack.rings('complete')    # one upload, one plain bond graph
+    side = quality.PocketSide(result['data'])                       # the pocket decoded once and uploaded once
+    poc, ia, sa = pack.pocket(side), pack.interactions(side), pack.sasa(side)
 
 OpenBabel's reconstruction, valence repair, QED / SA and docking need a chemistry toolkit and are not here.
 """
@@ -217,6 +219,32 @@ def _pack(pos, v, batch_ligand, ligand_ptr, device):
     return pos, v, ligand_ptr
 
 
+def _frame_mask(include, pos):
+    """``include`` [S, B] as a bool mask on the device of ``pos`` [S, N_l, 3], or None for every molecule"""
+    if include is None:
+        return None
+    return torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+
+
+def _reference_pack(reference_ligand, device):
+    """``(pos [n, 3], v [n])`` of a known ligand as a pack of one frame of one molecule on ``device``"""
+    rpos, rv = reference_ligand
+    rpos, rv, rptr = _pack(rpos, rv, None, torch.tensor([0, len(rv)], dtype=torch.int32), device)
+    if rpos.shape[0] != 1:
+        raise ValueError('the reference ligand is one molecule: pos [n, 3], v [n]')
+    return rpos, rv, rptr
+
+
+def _radii(table, radii):
+    """a copy of ``table`` ({atomic number: radius in Angstrom}) with the entries of ``radii`` in their place"""
+    r = dict(table)
+    for z, x in (radii or {}).items():
+        if int(z) not in r or not float(x) >= 0.0:
+            raise ValueError(f'radii are non-negative and keyed by the atomic numbers {tuple(sorted(r))} (got {z}: {x})')
+        r[int(z)] = float(x)
+    return r
+
+
 def stability(pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic', return_nr_bonds=False, device=None):
     """check_stability of every molecule of one frame ``[N_l, 3]`` or of a stack ``[S, N_l, 3]`` (classes ``v`` alike; the molecules
     by a sorted ``batch_ligand`` [N_l] or by ``ligand_ptr`` [B + 1], shared by the frames).  Returns ``(mol_stable [S, B] bool,
@@ -234,8 +262,7 @@ def pair_profiles(pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add
     ``len(edges)`` stay 0) and the element counts ``[S, 8] int64`` over the molecules of ``include`` ([S, B] bool, default all);
     ``profiles``: a sequence of (z1, z2, cutoff, edges), default the reference's two."""
     pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
-    if include is not None:
-        include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+    include = _frame_mask(include, pos)
     r = capi.quality_report(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), default_profiles() if profiles is None else profiles,
                             include, False)
     return r['hist'], r['counts']
@@ -342,7 +369,7 @@ class SamplePack:
         self.sizes, self.S = sizes, S
         self.class_z, self.aromatic = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
         self._checked = self._sized = False
-        self._stable = self._graph = self._bond_ring = None
+        self._stable = self._graph = self._bond_ring = self._ref = None
 
     @property
     def _args(self):
@@ -433,11 +460,7 @@ class SamplePack:
         fp = capi.fingerprint(*self._args, self.aromatic, radius, key_rounds, False, check=self._check())
         qw = qb = None
         if reference_ligand is not None:
-            rpos, rv = reference_ligand
-            rpos, rv, rptr = _pack(rpos, rv, None, torch.tensor([0, len(rv)], dtype=torch.int32), self.pos.device)
-            if rpos.shape[0] != 1:
-                raise ValueError('the reference ligand is one molecule: pos [n, 3], v [n]')
-            q = capi.fingerprint(rpos, rv, rptr, self.class_z, self.aromatic, radius, key_rounds, False)
+            q = capi.fingerprint(*self._reference(reference_ligand), self.aromatic, radius, key_rounds, False)
             qw, qb = q['fp_words'][0].contiguous(), q['n_bits'][0].contiguous()
         r = capi.fingerprint_similarity(fp['fp_words'], fp['n_bits'], fp['key'], mask, qw, qb, False)
         inc = fp['n_bits'].cpu().numpy() >= 0
@@ -460,18 +483,26 @@ class SamplePack:
         return GeometryReport(inc.sum(1), (inc & (clashes == 0)).sum(1), np.where(inc, clashes, 0).sum(1), tot('n_crowded'), tot('n_degenerate'),
                               tot('n_angles'), tot('n_torsions'), r['hist'].cpu().numpy(), prof, len(self.sizes), reference)
 
+    def _reference(self, reference_ligand):
+        """the known ligand as the leading arguments of a binding call, packed once for the reports that share it.  Kept by the
+        identity of the ``reference_ligand`` object: arrays changed in place between two reports are not packed again -- pass a new
+        tuple for another ligand"""
+        if self._ref is None or self._ref[0] is not reference_ligand:
+            self._ref = (reference_ligand, _reference_pack(reference_ligand, self.pos.device) + (self.class_z,))
+        return self._ref[1]
+
+    def _side(self, data):
+        return data if isinstance(data, PocketSide) else PocketSide(data, self.pos.device)
+
     def pocket(self, data, include='all', reference_ligand=None, contact_cutoff=4.0, clash_tolerance=0.5, kinds='residue'):
-        """``sample_pocket`` of the pack; ``data``: the pocket every molecule of the pack is in (``_pocket_arrays``)"""
-        ppos, elem, kind, names = _pocket_arrays(data, self.pos.device, kinds)
+        """``sample_pocket`` of the pack; ``data``: the pocket every molecule of the pack is in (``pocket_of``), or its ``PocketSide``"""
+        side = self._side(data)
+        kind, names = side.kinds(kinds)
         mask = self.mask(include)
-        pocket = (ppos, elem, kind, len(names), contact_cutoff)
+        pocket = (side.pos, side.elem, kind, len(names), contact_cutoff)
         ref_bits = ref_size = None
         if reference_ligand is not None:
-            rpos, rv = reference_ligand
-            rpos, rv, rptr = _pack(rpos, rv, None, torch.tensor([0, len(rv)], dtype=torch.int32), self.pos.device)
-            if rpos.shape[0] != 1:
-                raise ValueError('the reference ligand is one molecule: pos [n, 3], v [n]')
-            q = capi.pocket_report(rpos, rv, rptr, self.class_z, *pocket, None, None, None, False, True)
+            q = capi.pocket_report(*self._reference(reference_ligand), *pocket, None, None, None, False, True)
             ref_bits, ref_size = q['bits'][0, 0].contiguous(), int(q['n_pocket_atoms'][0, 0])
         r = capi.pocket_report(*self._args, *pocket, pocket_clash_thresholds(clash_tolerance), mask, ref_bits, False, False,
                                check=self._check())
@@ -481,18 +512,14 @@ class SamplePack:
                                          else None, ref_size)
 
     def interactions(self, data, include='all', reference_ligand=None, hbond_cutoff=3.5, hydrophobic_cutoff=4.5, hetero_cutoff=1.75):
-        """``sample_interactions`` of the pack; ``data``: the pocket every molecule of the pack is in (``_pocket_arrays``)"""
-        ppos, elem, kind, names = _pocket_arrays(data, self.pos.device)
-        role = torch.from_numpy(pocket_roles(pocket_of(data)[1])).to(self.pos.device)
+        """``sample_interactions`` of the pack; ``data`` as ``pocket``"""
+        side = self._side(data)
+        kind, names = side.kinds()
         mask = self.mask(include)
-        pocket = (ppos, elem, kind, role, len(names), hbond_cutoff, hydrophobic_cutoff, hetero_cutoff)
+        pocket = (side.pos, side.elem, kind, side.roles(), len(names), hbond_cutoff, hydrophobic_cutoff, hetero_cutoff)
         ref_bits = ref_sizes = None
         if reference_ligand is not None:
-            rpos, rv = reference_ligand
-            rpos, rv, rptr = _pack(rpos, rv, None, torch.tensor([0, len(rv)], dtype=torch.int32), self.pos.device)
-            if rpos.shape[0] != 1:
-                raise ValueError('the reference ligand is one molecule: pos [n, 3], v [n]')
-            q = capi.interaction_report(rpos, rv, rptr, self.class_z, *pocket, None, None, False, True)
+            q = capi.interaction_report(*self._reference(reference_ligand), *pocket, None, None, False, True)
             ref_bits = q['bits'][0, 0].contiguous()
             ref_sizes = _popcount(ref_bits.cpu().numpy())
         r = capi.interaction_report(*self._args, *pocket, mask, ref_bits, True, ref_bits is not None, check=self._check())
@@ -502,8 +529,21 @@ class SamplePack:
         return InteractionReport.from_outputs(raw, self._included(mask), self.sizes, names, ref_sizes)
 
     def sasa(self, data, include='all', reference_ligand=None, probe=1.4, points=96):
-        """``sample_sasa`` of the pack; ``data``: the pocket every molecule of the pack is in (``_pocket_arrays``)"""
-        return _sasa_of_pack(self, data, include, reference_ligand, probe, points)
+        """``sample_sasa`` of the pack; ``data`` as ``pocket``"""
+        side = self._side(data)
+        mask = self.mask(include)
+        lr, pr = sasa_reaches(probe)
+        dirs = torch.from_numpy(sasa_directions(points)).to(self.pos.device)
+        pocket = (side.pos, side.kinds('element')[0], lr, pr, dirs)
+        ref = None
+        if reference_ligand is not None:
+            q = capi.sasa_report(*self._reference(reference_ligand), *pocket, None, False, True)
+            ref = {k: q[k][0, 0].cpu().numpy() for k in ('free', 'bound', 'pocket_buried', 'bits')}
+        self._check()
+        # the pack's host look runs with every call: the kernel's cull is proved for the coordinates that look admits
+        r = capi.sasa_report(*self._args, *pocket, mask, False, ref is not None, check=True)
+        raw = {k: r[k].cpu().numpy() for k in ('free', 'bound', 'pocket_buried', 'bits', 'pocket_buried_sum') if r[k] is not None}
+        return SasaReport.from_outputs(raw, self._included(mask), lr, pr, points, float(probe), ref)
 
 
 def sample_quality(result, eval_step=-1, include='all', atom_enc_mode='add_aromatic', reference=None, profiles=None, device='cuda'):
@@ -571,8 +611,7 @@ def bond_graph(pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_ar
     else.  ``rings``: also the ring sizes (one more launch, ``td_ring_report``), per bond when ``return_bonds`` is given too.
     Molecules of more than 512 atoms are refused.  Returns a ``BondGraph`` (the frame axis is kept for a single frame)."""
     pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
-    if include is not None:
-        include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+    include = _frame_mask(include, pos)
     prof = default_bond_profiles() if bond_profiles is None else tuple(bond_profiles)
     cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
     r = capi.bond_graph(pos, v, ligand_ptr, cz, aro, prof, include, return_fragments, return_bonds)
@@ -644,33 +683,75 @@ def sample_connectivity(result, eval_step=-1, include='all', atom_enc_mode='add_
     return SamplePack(result, eval_step, atom_enc_mode, device).connectivity(include, reference, bond_profiles)
 
 
+_i64, _f64 = (lambda a: np.asarray(a, dtype=np.int64)), (lambda a: np.asarray(a, dtype=np.float64))
+# the kinds of a report's fields as (how a constructor argument is taken, how ``merged`` combines it): summed over the reports; carried
+# from the first; a per-pocket map, kept only for a single report; a sum that exists only with a reference ligand
+_FIELD_KINDS = {'i64': (_i64, 'sum'), 'f64': (_f64, 'sum'), 'int_sum': (int, 'sum'), 'int_carried': (int, 'carried'), 'tuple': (tuple, 'carried'),
+                'value': (lambda x: x, 'carried'), 'flags': (lambda a: np.asarray(a, dtype=bool), 'carried'), 'map': (_i64, 'map'),
+                'ref_i64': (_i64, 'ref'), 'ref_f64': (_f64, 'ref')}
+
+
+class _SumReport:
+    """What the per-frame reports that are sums over molecules share.  A class names its ``FIELDS`` once, (name, kind) in the order of
+    its constructor's arguments (``_FIELD_KINDS``; the last ``OPTIONAL`` of them default to None and stay None), what must agree for
+    two reports to merge (``_merge_key``) and the ``MISMATCH`` message.  From that: the converting constructor, ``merged``,
+    ``num_frames``, ``_mean`` and the ``key:\tvalue`` lines of the summary."""
+    FIELDS, OPTIONAL, MISMATCH = (), 0, ''
+
+    def __init__(self, *args, **kw):
+        names = [name for name, _ in self.FIELDS]
+        if len(args) > len(names) or not set(kw) <= set(names[len(args):]):
+            raise TypeError(f'{type(self).__name__}({", ".join(names)})')
+        given = dict(zip(names, args), **kw)
+        missing = [name for name in names[:len(names) - self.OPTIONAL] if name not in given]
+        if missing:
+            raise TypeError(f'{type(self).__name__}() needs {", ".join(missing)}')
+        for name, kind in self.FIELDS:
+            x = given.get(name)
+            setattr(self, name, None if x is None else _FIELD_KINDS[kind][0](x))
+
+    @classmethod
+    def merged(cls, reports):
+        """Several pockets together: every sum added, frame by frame; the reference values become means over the pockets that have
+        one (the reference's tables average a per-pocket number).  A per-pocket map belongs to one pocket: the merged report of several
+        has none."""
+        reports = list(reports)
+        first = reports[0]
+        if any(r._merge_key() != first._merge_key() for r in reports):
+            raise ValueError(cls.MISMATCH)
+        tot = lambda name: sum(getattr(r, name) for r in reports)
+        how = {'sum': tot, 'carried': lambda name: getattr(first, name), 'map': lambda name: getattr(first, name) if len(reports) == 1 else None,
+               'ref': lambda name: None if first.sum_ref is None else tot(name)}
+        return cls(*(how[_FIELD_KINDS[kind][1]](name) for name, kind in cls.FIELDS))
+
+    @property
+    def num_frames(self):
+        return getattr(self, self.FIELDS[0][0]).shape[0]
+
+    @staticmethod
+    def _mean(total, count):
+        return float(total) / int(count) if int(count) else float('nan')
+
+    def lines(self, frame=-1):
+        """the summary as printed lines"""
+        return [f'{k}:\t{x:.4f}' if x == x else f'{k}:\tNone' for k, x in self.summary(frame).items()]
+
+
 RING_SIZES = tuple(range(3, 10))                      # evaluate_diffusion.py print_ring_ratio: range(3, 10)
 
 
-class RingReport:
+class RingReport(_SumReport):
     """Per frame (axis 0): which ring sizes the included molecules have.  ``ring_hist`` [S, 32] int64: entry k > 0 counts the
     included molecules in which some bond's smallest ring has k atoms (31: 31 or more), entry 0 those without any ring; ``n_included``
     [S]; ``n_large`` [S] the included molecules with a ring of more than 9 atoms; ``sum_atom_share`` [S] the sum over the included
     non-empty molecules (``n_nonempty`` [S]) of atoms in rings / atoms.  A ring here is the smallest cycle through some bond: not a
     smallest set of smallest rings ("Rings")."""
 
-    def __init__(self, ring_hist, n_included, n_large, sum_atom_share, n_nonempty, n_samples):
-        self.ring_hist = np.asarray(ring_hist, dtype=np.int64)
-        self.n_included, self.n_large = np.asarray(n_included, dtype=np.int64), np.asarray(n_large, dtype=np.int64)
-        self.sum_atom_share, self.n_nonempty = np.asarray(sum_atom_share, dtype=np.float64), np.asarray(n_nonempty, dtype=np.int64)
-        self.n_samples = int(n_samples)
+    FIELDS = (('ring_hist', 'i64'), ('n_included', 'i64'), ('n_large', 'i64'), ('sum_atom_share', 'f64'), ('n_nonempty', 'i64'), ('n_samples', 'int_sum'))
+    MISMATCH = 'reports of different frame counts do not merge'
 
-    @classmethod
-    def merged(cls, reports):
-        reports = list(reports)
-        if any(r.ring_hist.shape != reports[0].ring_hist.shape for r in reports):
-            raise ValueError('reports of different frame counts do not merge')
-        return cls(sum(r.ring_hist for r in reports), sum(r.n_included for r in reports), sum(r.n_large for r in reports),
-                   sum(r.sum_atom_share for r in reports), sum(r.n_nonempty for r in reports), sum(r.n_samples for r in reports))
-
-    @property
-    def num_frames(self):
-        return self.ring_hist.shape[0]
+    def _merge_key(self):
+        return self.ring_hist.shape
 
     def _share(self, count, frame):
         n = int(self.n_included[frame])
@@ -743,7 +824,7 @@ def fingerprints(pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_
     return Fingerprints(r, ligand_ptr, radius, key_rounds)
 
 
-class DiversityReport:
+class DiversityReport(_SumReport):
     """Per frame (axis 0): how different the included samples of a pocket are from each other, as sums over pockets.
 
     Of one pocket with m included molecules: ``diversity`` = 1 - (sum of sim_sum) / (m (m - 1)), one minus the mean Tanimoto similarity
@@ -755,14 +836,12 @@ class DiversityReport:
     ``n_ref``; beside them the plain totals ``n_included``, ``n_distinct`` [S] and ``n_samples``.  The fingerprint is this project's
     own (``fingerprints``), not RDKit's: the values compare between runs of this tool, not with published tables."""
 
-    def __init__(self, sum_diversity, n_diversity, sum_nearest, sum_uniqueness, n_unique, n_included, n_distinct, n_samples, sum_ref=None,
-                 n_ref=None):
-        f64, i64 = (lambda a: np.asarray(a, dtype=np.float64)), (lambda a: np.asarray(a, dtype=np.int64))
-        self.sum_diversity, self.n_diversity, self.sum_nearest = f64(sum_diversity), i64(n_diversity), f64(sum_nearest)
-        self.sum_uniqueness, self.n_unique = f64(sum_uniqueness), i64(n_unique)
-        self.n_included, self.n_distinct, self.n_samples = i64(n_included), i64(n_distinct), int(n_samples)
-        self.sum_ref = None if sum_ref is None else f64(sum_ref)
-        self.n_ref = None if n_ref is None else i64(n_ref)
+    FIELDS = (('sum_diversity', 'f64'), ('n_diversity', 'i64'), ('sum_nearest', 'f64'), ('sum_uniqueness', 'f64'), ('n_unique', 'i64'),
+              ('n_included', 'i64'), ('n_distinct', 'i64'), ('n_samples', 'int_sum'), ('sum_ref', 'ref_f64'), ('n_ref', 'ref_i64'))
+    OPTIONAL, MISMATCH = 2, 'reports of different frame counts, or with and without a reference ligand, do not merge'
+
+    def _merge_key(self):
+        return self.sum_diversity.shape, self.sum_ref is None
 
     @classmethod
     def from_frames(cls, n_included, sum_sim, n_distinct, sum_max, n_samples, ref_sim=None, included=None):
@@ -785,26 +864,6 @@ class DiversityReport:
                     sum_ref[s] = (x.sum() / x.size, np.median(x), x.max())
             n_ref = one.astype(np.int64)
         return cls(diversity, two.astype(np.int64), nearest, unique, one.astype(np.int64), m, n_distinct, n_samples, sum_ref, n_ref)
-
-    @classmethod
-    def merged(cls, reports):
-        """Several pockets together: every sum added, frame by frame, so that each value becomes the mean of the pockets' values."""
-        reports = list(reports)
-        first = reports[0]
-        if any(r.sum_diversity.shape != first.sum_diversity.shape or (r.sum_ref is None) != (first.sum_ref is None) for r in reports):
-            raise ValueError('reports of different frame counts, or with and without a reference ligand, do not merge')
-        tot = lambda name: sum(getattr(r, name) for r in reports)
-        return cls(tot('sum_diversity'), tot('n_diversity'), tot('sum_nearest'), tot('sum_uniqueness'), tot('n_unique'), tot('n_included'),
-                   tot('n_distinct'), tot('n_samples'), None if first.sum_ref is None else tot('sum_ref'),
-                   None if first.sum_ref is None else tot('n_ref'))
-
-    @property
-    def num_frames(self):
-        return self.sum_diversity.shape[0]
-
-    @staticmethod
-    def _mean(total, count):
-        return float(total) / int(count) if int(count) else float('nan')
 
     def diversity(self, frame=-1):
         return self._mean(self.sum_diversity[frame], self.n_diversity[frame])
@@ -870,11 +929,7 @@ def geometry_profile_name(profile):
 def clash_thresholds(clash_scale=0.7, radii=None):
     """[8, 8] float64 over H C N O F P S Cl: ``clash_scale * (r_i + r_j)``; ``radii``: {atomic number: radius in Angstrom} over
     ``GEOMETRY_RADII`` (missing elements keep the default), or None"""
-    r = dict(GEOMETRY_RADII)
-    for z, x in (radii or {}).items():
-        if int(z) not in r or not float(x) >= 0.0:
-            raise ValueError(f'radii are non-negative and keyed by the atomic numbers {ELEMENTS} (got {z}: {x})')
-        r[int(z)] = float(x)
+    r = _radii(GEOMETRY_RADII, radii)
     rr = np.asarray([r[z] for z in ELEMENTS], dtype=np.float64)
     if not float(clash_scale) >= 0.0:
         raise ValueError(f'clash_scale is non-negative (got {clash_scale})')
@@ -953,8 +1008,7 @@ def geometry(pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_arom
     (``radii``: {atomic number: radius} to change some).  This is this project's own convention: it is not PoseBusters'
     distance-geometry bound and not a force field.  Molecules of more than 512 atoms are refused.  Returns a ``Geometry``."""
     pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
-    if include is not None:
-        include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+    include = _frame_mask(include, pos)
     prof = default_geometry_profiles() if profiles is None else tuple(profiles)
     r = _geometry_call(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode), prof, include,
                        clash_thresholds(clash_scale, radii), True)
@@ -1100,6 +1154,12 @@ def pocket_kinds(feat, by='residue', hydrogens=False):
     ``'element'`` the element index, 6 kinds.  A protein hydrogen gets kind -1 unless ``hydrogens``: pockets are usually stored
     without hydrogens, and one stored with them would otherwise count every contact twice over.  An atom of kind -1 or element -1
     takes part in no contact and no clash."""
+    return _kinds(_decode_features(feat), by, hydrogens)
+
+
+def _decode_features(feat):
+    """``(elem [n] int32, residue [n], backbone [n] bool)`` of the protein feature ``[n, 27]``: the index of the element bit and of the
+    residue bit, -1 for a row without one, and the backbone bit.  The one decode that ``pocket_kinds`` and ``pocket_roles`` read."""
     from . import workloads
     f = feat.detach().cpu().numpy() if torch.is_tensor(feat) else np.asarray(feat)
     ne, na = len(workloads.PROTEIN_ELEMENTS), len(workloads.AA_NAMES)
@@ -1107,8 +1167,15 @@ def pocket_kinds(feat, by='residue', hydrogens=False):
         raise ValueError(f'the protein feature is [n, {ne + na + 1}] (got {tuple(f.shape)})')
     f = f != 0
     elem = np.where(f[:, :ne].any(1), f[:, :ne].argmax(1), -1).astype(np.int32)
+    return elem, np.where(f[:, ne:ne + na].any(1), f[:, ne:ne + na].argmax(1), -1), f[:, ne + na]
+
+
+def _kinds(decoded, by, hydrogens):
+    """``pocket_kinds`` of a decoded feature"""
+    from . import workloads
+    elem, aa, bb = decoded
     if by == 'residue':
-        kind = np.where(f[:, ne:ne + na].any(1), 2 * f[:, ne:ne + na].argmax(1) + f[:, ne + na], -1).astype(np.int32)
+        kind = np.where(aa >= 0, 2 * aa + bb, -1).astype(np.int32)
         names = tuple(f'{aa}.{part}' for aa in workloads.AA_NAMES for part in ('sc', 'bb'))
     elif by == 'element':
         kind, names = elem.copy(), ('H', 'C', 'N', 'O', 'S', 'Se')
@@ -1124,11 +1191,7 @@ def pocket_clash_thresholds(tolerance=DEFAULT_CLASH_TOLERANCE, radii=None):
     geometry's van der Waals radii and Se 1.90 A; ``radii``: {atomic number: radius in Angstrom} to change some.  The tolerance is a
     convention (``DEFAULT_CLASH_TOLERANCE``), not a measurement."""
     from . import workloads
-    r = dict(POCKET_RADII)
-    for z, x in (radii or {}).items():
-        if int(z) not in r or not float(x) >= 0.0:
-            raise ValueError(f'radii are non-negative and keyed by the atomic numbers {tuple(sorted(r))} (got {z}: {x})')
-        r[int(z)] = float(x)
+    r = _radii(POCKET_RADII, radii)
     if not np.isfinite(float(tolerance)):
         raise ValueError(f'the clash tolerance is finite (got {tolerance})')
     rl = np.asarray([r[z] for z in ELEMENTS], dtype=np.float64)
@@ -1151,14 +1214,46 @@ def pocket_of(data):
     return pos, feat
 
 
-def _pocket_arrays(data, device, kinds='residue', hydrogens=False):
-    """The pocket ``data`` (``pocket_of``) as (pos [N_p, 3] fp32, elem, kind [N_p] int32 on ``device``, names)"""
-    pos, feat = pocket_of(data)
-    elem, kind, names = pocket_kinds(feat, kinds, hydrogens)
-    pos = _fp32_positions(pos, device)
-    if pos.shape[0] != 1 or pos.shape[1] != len(elem):
-        raise ValueError(f'protein positions must be [{len(elem)}, 3] (got {tuple(pos.shape[1:]) if pos.shape[0] == 1 else tuple(pos.shape)})')
-    return pos[0].contiguous(), torch.from_numpy(elem).to(pos.device), torch.from_numpy(kind).to(pos.device), names
+def _pocket_data(result, who):
+    """the pocket a result dictionary carries, for ``sample_<who>``; the driver's bare 7-tuple carries none"""
+    data = result.get('data') if isinstance(result, dict) else None
+    if data is None:
+        raise ValueError(f"the result carries no pocket: sample_{who} needs a result dictionary with its 'data' (results.result_dict), "
+                         f'or use SamplePack.{who}(data)')
+    return data
+
+
+class PocketSide:
+    """The protein side of the pocket reports, said once: the pocket ``data`` (``pocket_of``) decoded once and its positions uploaded
+    once to ``device``.  ``pos`` [N_p, 3] fp32 and ``elem`` [N_p] int32 are device tensors; ``kinds(by, hydrogens)`` gives ``(kind [N_p]
+    int32 on the device, names)`` as ``pocket_kinds`` -- by ``'element'`` the element index that the surface report takes --, and
+    ``roles(hydrogens)`` the table of ``pocket_roles``; both are made when a report first asks and kept.  ``SamplePack.pocket``,
+    ``.interactions`` and ``.sasa`` take one in the place of ``data``, so that several reports of one result file share it."""
+
+    def __init__(self, data, device='cuda'):
+        pos, feat = pocket_of(data)
+        self._decoded = _decode_features(feat)
+        pos = _fp32_positions(pos, device)
+        n = len(self._decoded[0])
+        if pos.shape[0] != 1 or pos.shape[1] != n:
+            raise ValueError(f'protein positions must be [{n}, 3] (got {tuple(pos.shape[1:]) if pos.shape[0] == 1 else tuple(pos.shape)})')
+        self.pos = pos[0].contiguous()
+        self.elem = torch.from_numpy(self._decoded[0]).to(self.pos.device)
+        self._kept = {}
+
+    def _keep(self, key, make):
+        if key not in self._kept:
+            self._kept[key] = make()
+        return self._kept[key]
+
+    def kinds(self, by='residue', hydrogens=False):
+        def make():
+            _, kind, names = _kinds(self._decoded, by, hydrogens)
+            return torch.from_numpy(kind).to(self.pos.device), names
+        return self._keep((by, bool(hydrogens)), make)
+
+    def roles(self, hydrogens=False):
+        return self._keep(('role', bool(hydrogens)), lambda: torch.from_numpy(_roles(self._decoded, hydrogens)).to(self.pos.device))
 
 
 class PocketContacts:
@@ -1188,13 +1283,13 @@ def pocket_contacts(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand
     nothing else; ``ref_bits`` [W] int64: the contact words of a known ligand (``bits`` of a call on it), for ``n_ref_common``.
     Molecules of more than 512 atoms are refused.  Returns a ``PocketContacts`` (the frame axis is kept)."""
     pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
-    ppos, elem, kind, names = _pocket_arrays((protein_pos, protein_feat), pos.device, kinds, hydrogens)
-    if include is not None:
-        include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+    side = PocketSide((protein_pos, protein_feat), pos.device)
+    (kind, names), elem = side.kinds(kinds, hydrogens), side.elem
+    include = _frame_mask(include, pos)
     if ref_bits is not None:
         ref_bits = torch.as_tensor(ref_bits).to(device=pos.device).contiguous()
     thr = None if clash_tolerance is None else pocket_clash_thresholds(clash_tolerance, radii)
-    r = capi.pocket_report(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), ppos, elem, kind, len(names), contact_cutoff, thr,
+    r = capi.pocket_report(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), side.pos, elem, kind, len(names), contact_cutoff, thr,
                            include, ref_bits, True, return_bits)
     return PocketContacts(r, ligand_ptr, elem, kind, names)
 
@@ -1217,7 +1312,7 @@ def _reference_recovery(common, touched, ref_size, included):
     return sum_ref, n_ref
 
 
-class PocketReport:
+class PocketReport(_SumReport):
     """Per frame (axis 0), over the included molecules (``n_included`` [S] of ``n_samples``): ``n_clash_free``, ``sum_clashes``,
     ``sum_contacts``, ``n_no_contact`` [S] int64; ``sum_buried`` [S], the sum of buried atoms / atoms over the ``n_nonempty`` [S]
     non-empty ones; ``sum_min_dist`` [S] over the ``n_min_dist`` [S] molecules that have a pair; ``kind_hist`` [S, 8, n_kinds] int64
@@ -1227,19 +1322,13 @@ class PocketReport:
     n_common) -- over the ``n_ref`` [S] pockets that have them: a reference that touches nothing gives no value, and the summary NaN.
     The cutoff and the clash rule are this project's conventions (``pocket_contacts``)."""
 
-    def __init__(self, n_included, n_clash_free, sum_clashes, sum_contacts, n_no_contact, sum_buried, n_nonempty, sum_min_dist, n_min_dist,
-                 kind_hist, names, backbone, n_samples, pocket_freq=None, sum_ref=None, n_ref=None):
-        i64, f64 = (lambda a: np.asarray(a, dtype=np.int64)), (lambda a: np.asarray(a, dtype=np.float64))
-        self.n_included, self.n_clash_free, self.sum_clashes = i64(n_included), i64(n_clash_free), i64(sum_clashes)
-        self.sum_contacts, self.n_no_contact = i64(sum_contacts), i64(n_no_contact)
-        self.sum_buried, self.n_nonempty = f64(sum_buried), i64(n_nonempty)
-        self.sum_min_dist, self.n_min_dist = f64(sum_min_dist), i64(n_min_dist)
-        self.kind_hist, self.names = i64(kind_hist), tuple(names)
-        self.backbone = None if backbone is None else np.asarray(backbone, dtype=bool)
-        self.n_samples = int(n_samples)
-        self.pocket_freq = None if pocket_freq is None else i64(pocket_freq)
-        self.sum_ref = None if sum_ref is None else f64(sum_ref)
-        self.n_ref = None if n_ref is None else i64(n_ref)
+    FIELDS = (('n_included', 'i64'), ('n_clash_free', 'i64'), ('sum_clashes', 'i64'), ('sum_contacts', 'i64'), ('n_no_contact', 'i64'),
+              ('sum_buried', 'f64'), ('n_nonempty', 'i64'), ('sum_min_dist', 'f64'), ('n_min_dist', 'i64'), ('kind_hist', 'i64'), ('names', 'tuple'),
+              ('backbone', 'flags'), ('n_samples', 'int_sum'), ('pocket_freq', 'map'), ('sum_ref', 'ref_f64'), ('n_ref', 'ref_i64'))
+    OPTIONAL, MISMATCH = 3, 'reports of different frame counts or kinds, or with and without a reference ligand, do not merge'
+
+    def _merge_key(self):
+        return self.kind_hist.shape, self.names, self.sum_ref is None
 
     @classmethod
     def from_outputs(cls, raw, included, sizes, names, backbone=None, ref_size=None):
@@ -1258,29 +1347,6 @@ class PocketReport:
         return cls(inc.sum(1), (inc & (clashes == 0)).sum(1), np.where(inc, clashes, 0).sum(1), np.where(inc, con, 0).sum(1),
                    (inc & (con == 0)).sum(1), np.where(inc, share, 0.0).sum(1), (inc & (n[None] > 0)).sum(1), np.where(has, md, 0.0).sum(1),
                    has.sum(1), raw['kind_hist'], names, backbone, len(n), raw['pocket_freq'], sum_ref, n_ref)
-
-    @classmethod
-    def merged(cls, reports):
-        """Several pockets together: every sum added, frame by frame; the reference values become means over the pockets that have
-        one (the convention of DiversityReport).  A contact map belongs to one pocket: the merged report of several has none."""
-        reports = list(reports)
-        first = reports[0]
-        if any(r.kind_hist.shape != first.kind_hist.shape or r.names != first.names or (r.sum_ref is None) != (first.sum_ref is None)
-               for r in reports):
-            raise ValueError('reports of different frame counts or kinds, or with and without a reference ligand, do not merge')
-        tot = lambda name: sum(getattr(r, name) for r in reports)
-        return cls(tot('n_included'), tot('n_clash_free'), tot('sum_clashes'), tot('sum_contacts'), tot('n_no_contact'), tot('sum_buried'),
-                   tot('n_nonempty'), tot('sum_min_dist'), tot('n_min_dist'), tot('kind_hist'), first.names, first.backbone, tot('n_samples'),
-                   first.pocket_freq if len(reports) == 1 else None, None if first.sum_ref is None else tot('sum_ref'),
-                   None if first.sum_ref is None else tot('n_ref'))
-
-    @property
-    def num_frames(self):
-        return self.kind_hist.shape[0]
-
-    @staticmethod
-    def _mean(total, count):
-        return float(total) / int(count) if int(count) else float('nan')
 
     def clash_free(self, frame=-1):
         """included molecules without a protein clash / included molecules"""
@@ -1334,7 +1400,7 @@ class PocketReport:
 
     def lines(self, frame=-1, top=5):
         """the report as printed lines: the summary, then the ``top`` kinds of the contact profile"""
-        out = [f'{k}:\t{x:.4f}' if x == x else f'{k}:\tNone' for k, x in self.summary(frame).items()]
+        out = super().lines(frame)
         prof = self.contact_profile(frame) or {}
         for k, x in sorted(prof.items(), key=lambda kx: (-kx[1], kx[0]))[:top]:
             if x > 0:
@@ -1350,11 +1416,7 @@ def sample_pocket(result, eval_step=-1, include='all', reference_ligand=None, co
     residue kind and the pocket's contact map; with ``reference_ligand`` ``(pos [n, 3], v [n])``, run through the same kernel, the
     recovery of its contacts.  ``include`` as ``sample_rings``.  The cutoff and the clash rule are conventions (``pocket_contacts``).
     A result without a pocket (the driver's bare 7-tuple) is refused.  Returns a ``PocketReport``."""
-    data = result.get('data') if isinstance(result, dict) else None
-    if data is None:
-        raise ValueError("the result carries no pocket: sample_pocket needs a result dictionary with its 'data' (results.result_dict), "
-                         'or use SamplePack.pocket(data)')
-    return SamplePack(result, eval_step, atom_enc_mode, device).pocket(data, include, reference_ligand, contact_cutoff, clash_tolerance, kinds)
+    return SamplePack(result, eval_step, atom_enc_mode, device).pocket(_pocket_data(result, 'pocket'), include, reference_ligand, contact_cutoff, clash_tolerance, kinds)
 
 
 # ---- typed pocket interactions (``td_interaction_report``, csrc/interactions.hip; DESIGN.md section 3, "Pocket interactions")
@@ -1376,18 +1438,16 @@ def pocket_roles(feat, hydrogens=False):
     any other O (ASP, GLU, ASN, GLN, a terminal OXT): ACCEPTOR.  Side-chain N of ARG, LYS, ASN, GLN, TRP: DONOR; of HIS: DONOR |
     ACCEPTOR.  C, S, Se, H: 0 (which carbons are hydrophobic the device decides).  -1, an atom that takes part nowhere: a row without
     an element bit or without a residue bit, and a hydrogen unless ``hydrogens``."""
+    return _roles(_decode_features(feat), hydrogens)
+
+
+def _roles(decoded, hydrogens):
+    """``pocket_roles`` of a decoded feature"""
     from . import workloads
-    f = feat.detach().cpu().numpy() if torch.is_tensor(feat) else np.asarray(feat)
-    ne, na = len(workloads.PROTEIN_ELEMENTS), len(workloads.AA_NAMES)
-    if f.ndim != 2 or f.shape[1] != ne + na + 1:
-        raise ValueError(f'the protein feature is [n, {ne + na + 1}] (got {tuple(f.shape)})')
-    f = f != 0
-    elem = np.where(f[:, :ne].any(1), f[:, :ne].argmax(1), -1)
-    aa = np.where(f[:, ne:ne + na].any(1), f[:, ne:ne + na].argmax(1), -1)
-    bb = f[:, ne + na]
+    elem, aa, bb = decoded
     of = lambda *names: np.isin(aa, [workloads.AA_NAMES.index(x) for x in names])
     N, O = elem == workloads.PROTEIN_ELEMENTS.index(7), elem == workloads.PROTEIN_ELEMENTS.index(8)
-    role = np.zeros(len(f), np.int32)
+    role = np.zeros(len(elem), np.int32)
     role[N & bb & ~of('PRO')] = ROLE_DONOR
     role[N & ~bb & of('ARG', 'LYS', 'ASN', 'GLN', 'TRP')] = ROLE_DONOR
     role[N & ~bb & of('HIS')] = ROLE_DONOR | ROLE_ACCEPTOR
@@ -1428,13 +1488,12 @@ def pocket_interactions(protein_pos, protein_feat, pos, v, batch_ligand=None, li
     restricts ``kind_hist`` and ``pocket_freq`` and nothing else; ``ref_bits`` [3, W] int64: the words of a known ligand (``bits`` of
     a call on it), for ``n_ref_common``.  Molecules of more than 512 atoms are refused.  Returns an ``Interactions``."""
     pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
-    ppos, elem, kind, names = _pocket_arrays((protein_pos, protein_feat), pos.device, kinds, hydrogens)
-    role = torch.from_numpy(pocket_roles(protein_feat, hydrogens)).to(pos.device)
-    if include is not None:
-        include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+    side = PocketSide((protein_pos, protein_feat), pos.device)
+    (kind, names), elem = side.kinds(kinds, hydrogens), side.elem
+    include = _frame_mask(include, pos)
     if ref_bits is not None:
         ref_bits = torch.as_tensor(ref_bits).to(device=pos.device).contiguous()
-    r = capi.interaction_report(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), ppos, elem, kind, role, len(names), hbond_cutoff,
+    r = capi.interaction_report(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), side.pos, elem, kind, side.roles(hydrogens), len(names), hbond_cutoff,
                                 hydrophobic_cutoff, hetero_cutoff, include, ref_bits, True, return_bits)
     return Interactions(r, ligand_ptr, elem, kind, names)
 
@@ -1445,7 +1504,7 @@ def _popcount(words):
     return np.unpackbits(w.view(np.uint8).reshape(w.shape + (8,)), axis=-1).sum((-1, -2)).astype(np.int64)
 
 
-class InteractionReport:
+class InteractionReport(_SumReport):
     """Per frame (axis 0), over the included molecules (``n_included`` [S] of ``n_samples``): ``sum_hbonds``, ``sum_donated``,
     ``sum_accepted``, ``sum_hydrophobic`` [S] int64, the pairs; ``n_no_hbond`` [S], the molecules without a hydrogen bond;
     ``sum_hb_atoms`` of the ``sum_polar_atoms`` [S] ligand atoms that are donor or acceptor; ``kind_hist`` [S, 3, n_kinds] int64 with
@@ -1455,17 +1514,13 @@ class InteractionReport:
     reference without an interaction of a type gives no value there, and the summary NaN.  The roles and the cutoffs are this
     project's conventions (``pocket_interactions``)."""
 
-    def __init__(self, n_included, sum_hbonds, sum_donated, sum_accepted, sum_hydrophobic, n_no_hbond, sum_hb_atoms, sum_polar_atoms,
-                 kind_hist, names, n_samples, pocket_freq=None, sum_ref=None, n_ref=None):
-        i64, f64 = (lambda a: np.asarray(a, dtype=np.int64)), (lambda a: np.asarray(a, dtype=np.float64))
-        self.n_included, self.sum_hbonds, self.sum_donated, self.sum_accepted = i64(n_included), i64(sum_hbonds), i64(sum_donated), i64(sum_accepted)
-        self.sum_hydrophobic, self.n_no_hbond = i64(sum_hydrophobic), i64(n_no_hbond)
-        self.sum_hb_atoms, self.sum_polar_atoms = i64(sum_hb_atoms), i64(sum_polar_atoms)
-        self.kind_hist, self.names = i64(kind_hist), tuple(names)
-        self.n_samples = int(n_samples)
-        self.pocket_freq = None if pocket_freq is None else i64(pocket_freq)
-        self.sum_ref = None if sum_ref is None else f64(sum_ref)
-        self.n_ref = None if n_ref is None else i64(n_ref)
+    FIELDS = (('n_included', 'i64'), ('sum_hbonds', 'i64'), ('sum_donated', 'i64'), ('sum_accepted', 'i64'), ('sum_hydrophobic', 'i64'),
+              ('n_no_hbond', 'i64'), ('sum_hb_atoms', 'i64'), ('sum_polar_atoms', 'i64'), ('kind_hist', 'i64'), ('names', 'tuple'),
+              ('n_samples', 'int_sum'), ('pocket_freq', 'map'), ('sum_ref', 'ref_f64'), ('n_ref', 'ref_i64'))
+    OPTIONAL, MISMATCH = 3, PocketReport.MISMATCH
+
+    def _merge_key(self):
+        return self.kind_hist.shape, self.names, self.sum_ref is None
 
     @classmethod
     def from_outputs(cls, raw, included, sizes, names, ref_sizes=None):
@@ -1482,41 +1537,11 @@ class InteractionReport:
         hbonds = np.asarray(raw['n_hbonds'], dtype=np.int64)
         sum_ref = n_ref = None
         if ref_sizes is not None:
-            sum_ref, n_ref = np.zeros((S, 3, 4)), np.zeros((S, 3), np.int64)
-            common, hit = np.asarray(raw['n_ref_common'], dtype=np.float64), _popcount(raw['bits']).astype(np.float64)
-            for s in range(S):
-                for t in range(3):
-                    size = float(ref_sizes[t])
-                    if size > 0 and inc[s].any():
-                        c, h = common[s, inc[s], t], hit[s, inc[s], t]
-                        rec, tan = c / size, c / (h + size - c)
-                        sum_ref[s, t] = (rec.sum() / rec.size, np.median(rec), rec.max(), tan.sum() / tan.size)
-                        n_ref[s, t] = 1
+            common, hit = np.asarray(raw['n_ref_common']), _popcount(raw['bits'])
+            per_type = [_reference_recovery(common[..., t], hit[..., t], ref_sizes[t], inc) for t in range(3)]
+            sum_ref, n_ref = (np.stack(x, axis=1) for x in zip(*per_type))
         return cls(inc.sum(1), tot(hbonds), tot(raw['n_donated']), tot(raw['n_accepted']), tot(raw['n_hydrophobic']), (inc & (hbonds == 0)).sum(1),
                    tot(raw['n_hb_atoms']), tot(n_polar), raw['kind_hist'], names, len(sizes), raw['pocket_freq'], sum_ref, n_ref)
-
-    @classmethod
-    def merged(cls, reports):
-        """Several pockets together: every sum added, frame by frame; the reference values become means over the pockets that have
-        one (the convention of PocketReport).  An interaction map belongs to one pocket: the merged report of several has none."""
-        reports = list(reports)
-        first = reports[0]
-        if any(r.kind_hist.shape != first.kind_hist.shape or r.names != first.names or (r.sum_ref is None) != (first.sum_ref is None)
-               for r in reports):
-            raise ValueError('reports of different frame counts or kinds, or with and without a reference ligand, do not merge')
-        tot = lambda name: sum(getattr(r, name) for r in reports)
-        return cls(tot('n_included'), tot('sum_hbonds'), tot('sum_donated'), tot('sum_accepted'), tot('sum_hydrophobic'), tot('n_no_hbond'),
-                   tot('sum_hb_atoms'), tot('sum_polar_atoms'), tot('kind_hist'), first.names, tot('n_samples'),
-                   first.pocket_freq if len(reports) == 1 else None, None if first.sum_ref is None else tot('sum_ref'),
-                   None if first.sum_ref is None else tot('n_ref'))
-
-    @property
-    def num_frames(self):
-        return self.kind_hist.shape[0]
-
-    @staticmethod
-    def _mean(total, count):
-        return float(total) / int(count) if int(count) else float('nan')
 
     def mean_hbonds(self, frame=-1):
         """hydrogen bonds per included molecule; a pair that donates and accepts at once counts once"""
@@ -1568,7 +1593,7 @@ class InteractionReport:
 
     def lines(self, frame=-1, top=3):
         """the report as printed lines: the summary, then per type the ``top`` residue kinds"""
-        out = [f'{k}:\t{x:.4f}' if x == x else f'{k}:\tNone' for k, x in self.summary(frame).items()]
+        out = super().lines(frame)
         for name in INTERACTION_NAMES:
             prof = self.kind_profile(name, frame) or {}
             for k, x in sorted(prof.items(), key=lambda kx: (-kx[1], kx[0]))[:top]:
@@ -1586,12 +1611,8 @@ def sample_interactions(result, eval_step=-1, include='all', reference_ligand=No
     one, the residue kinds per type and the pocket's interaction map; with ``reference_ligand`` ``(pos [n, 3], v [n])``, run through
     the same kernel, the recovery of its interactions per type.  ``include`` as ``sample_rings``.  The roles and cutoffs are
     conventions (``pocket_interactions``).  A result without a pocket is refused.  Returns an ``InteractionReport``."""
-    data = result.get('data') if isinstance(result, dict) else None
-    if data is None:
-        raise ValueError("the result carries no pocket: sample_interactions needs a result dictionary with its 'data' "
-                         '(results.result_dict), or use SamplePack.interactions(data)')
-    return SamplePack(result, eval_step, atom_enc_mode, device).interactions(data, include, reference_ligand, hbond_cutoff, hydrophobic_cutoff,
-                                                                             hetero_cutoff)
+    return SamplePack(result, eval_step, atom_enc_mode, device).interactions(_pocket_data(result, 'interactions'), include, reference_ligand,
+                                                                             hbond_cutoff, hydrophobic_cutoff, hetero_cutoff)
 
 
 # ---- solvent-accessible surface (``td_sasa_report``, csrc/sasa.hip; DESIGN.md section 3, "Solvent-accessible surface")
@@ -1623,11 +1644,7 @@ def sasa_reaches(probe=SASA_PROBE, radii=None):
     """([8], [6]) float64: the expanded radius ``r + probe`` of the ligand's elements H C N O F P S Cl and of the protein's H C N O S Se,
     with geometry's van der Waals radii and Se 1.90 A; ``radii``: {atomic number: radius in Angstrom} to change some"""
     from . import workloads
-    r = dict(POCKET_RADII)
-    for z, x in (radii or {}).items():
-        if int(z) not in r or not float(x) >= 0.0:
-            raise ValueError(f'radii are non-negative and keyed by the atomic numbers {tuple(sorted(r))} (got {z}: {x})')
-        r[int(z)] = float(x)
+    r = _radii(POCKET_RADII, radii)
     if not (np.isfinite(float(probe)) and float(probe) >= 0.0):
         raise ValueError(f'the probe radius is finite and >= 0 (got {probe})')
     rl = np.asarray([r[z] for z in ELEMENTS], dtype=np.float64) + np.float64(probe)
@@ -1650,13 +1667,6 @@ def sasa_areas(counts, reach, points):
 def _buried_share(free_area, buried_area):
     """buried / free, 0 where nothing is free"""
     return np.divide(buried_area, free_area, out=np.zeros_like(free_area), where=free_area > 0)
-
-
-def _sasa_pocket(data, device, hydrogens=False):
-    """The pocket ``data`` (``pocket_of``) as (pos [N_p, 3] fp32, elem [N_p] int32 on ``device``): the element index over H C N O S Se,
-    -1 for a row without one and, unless ``hydrogens``, for a hydrogen (``pocket_kinds``)"""
-    ppos, _, elem, _ = _pocket_arrays(data, device, 'element', hydrogens)
-    return ppos, elem
 
 
 class Sasa:
@@ -1692,16 +1702,16 @@ def pocket_sasa(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_ptr
     ``pocket_buried_sum`` and nothing else.  Molecules of more than 512 atoms and coordinates beyond 1e5 A are refused.  Returns a
     ``Sasa`` (the frame axis is kept)."""
     pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
-    ppos, elem = _sasa_pocket((protein_pos, protein_feat), pos.device, hydrogens)
-    if include is not None:
-        include = torch.as_tensor(include).to(device=pos.device, dtype=torch.bool).reshape(pos.shape[0], -1).contiguous()
+    side = PocketSide((protein_pos, protein_feat), pos.device)
+    elem = side.kinds('element', hydrogens)[0]
+    include = _frame_mask(include, pos)
     lr, pr = sasa_reaches(probe, radii)
     dirs = torch.from_numpy(sasa_directions(points)).to(pos.device)
-    r = capi.sasa_report(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), ppos, elem, lr, pr, dirs, include, True, return_bits)
+    r = capi.sasa_report(pos, v, ligand_ptr, class_atomic_numbers(atom_enc_mode), side.pos, elem, lr, pr, dirs, include, True, return_bits)
     return Sasa(r, ligand_ptr, elem, lr, pr, points)
 
 
-class SasaReport:
+class SasaReport(_SumReport):
     """Per frame (axis 0), over the included molecules (``n_included`` [S] of ``n_samples``), areas in square Angstrom: ``sum_free``,
     ``sum_bound``, ``sum_buried`` [S, 3] float64, the ligands' surface alone, in the pocket and their difference, each as (total, polar,
     apolar; polar is N and O); ``sum_share`` [S], the sum of buried / free (0 for a molecule with nothing free); ``n_nothing`` [S], the
@@ -1712,16 +1722,14 @@ class SasaReport:
     Tanimoto, as ``PocketReport`` forms them for contacts -- over the ``n_own`` / ``n_ref`` [S] pockets that have them.  The radii, the
     probe and the point count are conventions (``pocket_sasa``); of the pocket only buried area is reported."""
 
-    def __init__(self, n_included, sum_free, sum_bound, sum_buried, sum_share, n_nothing, sum_pocket, n_samples, points, probe=None,
-                 pocket_buried_sum=None, sum_own=None, n_own=None, sum_ref=None, n_ref=None):
-        i64, f64 = (lambda a: np.asarray(a, dtype=np.int64)), (lambda a: np.asarray(a, dtype=np.float64))
-        self.n_included, self.n_nothing = i64(n_included), i64(n_nothing)
-        self.sum_free, self.sum_bound, self.sum_buried, self.sum_share, self.sum_pocket = (f64(x) for x in (sum_free, sum_bound, sum_buried,
-                                                                                                         sum_share, sum_pocket))
-        self.n_samples, self.points, self.probe = int(n_samples), int(points), probe
-        self.pocket_buried_sum = None if pocket_buried_sum is None else i64(pocket_buried_sum)
-        opt = lambda a, conv: None if a is None else conv(a)
-        self.sum_own, self.n_own, self.sum_ref, self.n_ref = opt(sum_own, f64), opt(n_own, i64), opt(sum_ref, f64), opt(n_ref, i64)
+    FIELDS = (('n_included', 'i64'), ('sum_free', 'f64'), ('sum_bound', 'f64'), ('sum_buried', 'f64'), ('sum_share', 'f64'), ('n_nothing', 'i64'),
+              ('sum_pocket', 'f64'), ('n_samples', 'int_sum'), ('points', 'int_carried'), ('probe', 'value'), ('pocket_buried_sum', 'map'), ('sum_own', 'ref_f64'),
+              ('n_own', 'ref_i64'), ('sum_ref', 'ref_f64'), ('n_ref', 'ref_i64'))
+    OPTIONAL = 6
+    MISMATCH = 'reports of different frame counts, point counts or probes, or with and without a reference ligand, do not merge'
+
+    def _merge_key(self):
+        return self.sum_free.shape, self.points, self.probe, self.sum_ref is None
 
     @classmethod
     def from_outputs(cls, raw, included, ligand_reach, protein_reach, points, probe=None, ref=None):
@@ -1746,30 +1754,6 @@ class SasaReport:
             sum_ref, n_ref = _reference_recovery(_popcount(bits & rbits[None, None]), _popcount(bits), int(_popcount(rbits)), inc)
         return cls(inc.sum(1), tot(fa), tot(ba), tot(bu), np.where(inc, share, 0.0).sum(1), (inc & ((free - bound).sum(-1) == 0)).sum(1),
                    tot(pa), B, points, probe, raw['pocket_buried_sum'], sum_own, n_own, sum_ref, n_ref)
-
-    @classmethod
-    def merged(cls, reports):
-        """Several pockets together: every sum added, frame by frame; the reference values become means over the pockets that have
-        one (the convention of PocketReport).  The covered points per protein atom belong to one pocket: the merged report of several
-        has none."""
-        reports = list(reports)
-        first = reports[0]
-        if any(r.sum_free.shape != first.sum_free.shape or r.points != first.points or r.probe != first.probe or
-               (r.sum_ref is None) != (first.sum_ref is None) for r in reports):
-            raise ValueError('reports of different frame counts, point counts or probes, or with and without a reference ligand, do not merge')
-        tot = lambda name: sum(getattr(r, name) for r in reports)
-        opt = lambda name: None if first.sum_ref is None else tot(name)
-        return cls(tot('n_included'), tot('sum_free'), tot('sum_bound'), tot('sum_buried'), tot('sum_share'), tot('n_nothing'), tot('sum_pocket'),
-                   tot('n_samples'), first.points, first.probe, first.pocket_buried_sum if len(reports) == 1 else None, opt('sum_own'),
-                   opt('n_own'), opt('sum_ref'), opt('n_ref'))
-
-    @property
-    def num_frames(self):
-        return self.sum_free.shape[0]
-
-    @staticmethod
-    def _mean(total, count):
-        return float(total) / int(count) if int(count) else float('nan')
 
     def free_area(self, frame=-1, part=0):
         """mean surface of an included molecule alone; ``part`` 0 total, 1 polar, 2 apolar"""
@@ -1825,32 +1809,6 @@ class SasaReport:
                    buries_nothing=self.buries_nothing(frame), **self.reference(frame))
         return out
 
-    def lines(self, frame=-1):
-        """the report as printed lines"""
-        return [f'{k}:\t{x:.4f}' if x == x else f'{k}:\tNone' for k, x in self.summary(frame).items()]
-
-
-def _sasa_of_pack(pack, data, include, reference_ligand, probe, points):
-    """``SamplePack.sasa``"""
-    ppos, elem = _sasa_pocket(data, pack.pos.device)
-    mask = pack.mask(include)
-    lr, pr = sasa_reaches(probe)
-    dirs = torch.from_numpy(sasa_directions(points)).to(pack.pos.device)
-    pocket = (ppos, elem, lr, pr, dirs)
-    ref = None
-    if reference_ligand is not None:
-        rpos, rv = reference_ligand
-        rpos, rv, rptr = _pack(rpos, rv, None, torch.tensor([0, len(rv)], dtype=torch.int32), pack.pos.device)
-        if rpos.shape[0] != 1:
-            raise ValueError('the reference ligand is one molecule: pos [n, 3], v [n]')
-        q = capi.sasa_report(rpos, rv, rptr, pack.class_z, *pocket, None, False, True)
-        ref = {k: q[k][0, 0].cpu().numpy() for k in ('free', 'bound', 'pocket_buried', 'bits')}
-    pack._check()
-    # the pack's host look runs with every call: the kernel's cull is proved for the coordinates that look admits
-    r = capi.sasa_report(*pack._args, *pocket, mask, False, ref is not None, check=True)
-    raw = {k: r[k].cpu().numpy() for k in ('free', 'bound', 'pocket_buried', 'bits', 'pocket_buried_sum') if r[k] is not None}
-    return SasaReport.from_outputs(raw, pack._included(mask), lr, pr, points, float(probe), ref)
-
 
 def sample_sasa(result, eval_step=-1, include='all', reference_ligand=None, probe=SASA_PROBE, points=SASA_POINTS,
                 atom_enc_mode='add_aromatic', device='cuda'):
@@ -1860,8 +1818,4 @@ def sample_sasa(result, eval_step=-1, include='all', reference_ligand=None, prob
     the share of poses the pocket does not cover at all; with ``reference_ligand`` ``(pos [n, 3], v [n])``, run through the same
     kernel, its own numbers and the recovery of the protein atoms it buries.  ``include`` as ``sample_rings``.  The radii, the probe
     and the point count are conventions (``pocket_sasa``).  A result without a pocket is refused.  Returns a ``SasaReport``."""
-    data = result.get('data') if isinstance(result, dict) else None
-    if data is None:
-        raise ValueError("the result carries no pocket: sample_sasa needs a result dictionary with its 'data' (results.result_dict), "
-                         'or use SamplePack.sasa(data)')
-    return SamplePack(result, eval_step, atom_enc_mode, device).sasa(data, include, reference_ligand, probe, points)
+    return SamplePack(result, eval_step, atom_enc_mode, device).sasa(_pocket_data(result, 'sasa'), include, reference_ligand, probe, points)

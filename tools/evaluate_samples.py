@@ -78,6 +78,25 @@ def print_dict(d):
         print(f'{k}:\t{v:.4f}' if v is not None else f'{k}:\tNone')
 
 
+def nan_none(d):
+    """a summary with None in the place of NaN, as JSON wants it"""
+    return {k: (None if x != x else x) for k, x in d.items()}
+
+
+def pocket_sections(args):
+    """The reports against the pocket that ``args`` asks for, as (flag -- also the name of the SamplePack method and of the JSON
+    section --, report class, the method's arguments after the reference ligand, extra JSON fields of the merged report)"""
+    all_three = (
+        ('pocket', quality.PocketReport, (args.contact_cutoff, args.clash_tolerance),
+         lambda r: dict(contact_cutoff=args.contact_cutoff, clash_tolerance=args.clash_tolerance, contact_profile=r.contact_profile(-1),
+                        kind_hist=dict(zip(r.names, r.kind_hist[-1].sum(0).tolist())))),
+        ('interactions', quality.InteractionReport, (args.hbond_cutoff, args.hydrophobic_cutoff),
+         lambda r: dict(hbond_cutoff=args.hbond_cutoff, hydrophobic_cutoff=args.hydrophobic_cutoff,
+                        kind_hist={t: dict(zip(r.names, r.kind_hist[-1, k].tolist())) for k, t in enumerate(quality.INTERACTION_NAMES)})),
+        ('sasa', quality.SasaReport, (args.probe, args.sasa_points), lambda r: dict(probe=args.probe, points=args.sasa_points)))
+    return [section for section in all_three if getattr(args, section[0])]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--sample_path', type=str, required=True)
@@ -134,7 +153,9 @@ def main(argv=None):
     if not files:
         raise SystemExit(f'no result_*.pt under {args.sample_path}')
     print(f'Load generated data done! {len(files)} examples in total.')
-    reports, connectivity, rings, diversity, geometry, pocket, interactions, sasa = [], [], [], [], [], [], [], []
+    reports, connectivity, rings, diversity, geometry = [], [], [], [], []
+    sections = pocket_sections(args)
+    against_pocket = {flag: [] for flag, _, _, _ in sections}
     graph_include = 'complete' if args.include == 'complete' else 'all'     # 'stable' restricts the pair profiles and atom types only
     for name in files:
         result = torch.load(name, map_location='cpu', weights_only=False)
@@ -147,20 +168,16 @@ def main(argv=None):
             diversity.append(pack.diversity(graph_include, reference_ligand=reference_ligand))
         if args.geometry:
             geometry.append(pack.geometry(graph_include, geometry_reference))
-        if args.pocket:
+        side = None                                                             # the file's pocket, decoded and uploaded once
+        for flag, _, extra, _ in sections:
             if not isinstance(result, dict) or result.get('data') is None:
-                raise SystemExit(f'{name} carries no pocket (no data): --pocket needs the files of a sampling driver')
-            pocket.append(pack.pocket(result['data'], graph_include, reference_ligand, args.contact_cutoff, args.clash_tolerance))
-        if args.interactions:
-            if not isinstance(result, dict) or result.get('data') is None:
-                raise SystemExit(f'{name} carries no pocket (no data): --interactions needs the files of a sampling driver')
-            interactions.append(pack.interactions(result['data'], graph_include, reference_ligand, args.hbond_cutoff, args.hydrophobic_cutoff))
-        if args.sasa:
-            if not isinstance(result, dict) or result.get('data') is None:
-                raise SystemExit(f'{name} carries no pocket (no data): --sasa needs the files of a sampling driver')
+                raise SystemExit(f'{name} carries no pocket (no data): --{flag} needs the files of a sampling driver')
             try:
-                sasa.append(pack.sasa(result['data'], graph_include, reference_ligand, args.probe, args.sasa_points))
+                side = side or quality.PocketSide(result['data'], args.device)
+                against_pocket[flag].append(getattr(pack, flag)(side, graph_include, reference_ligand, *extra))
             except ValueError as e:
+                if flag != 'sasa':
+                    raise
                 raise SystemExit(f'--sasa: {e}')
         reports.append(pack.quality(args.include, reference))
     rep = quality.QualityReport.merged(reports)
@@ -199,7 +216,6 @@ def main(argv=None):
             out['rings']['curve'] = [ring.summary(s) for s in range(ring.num_frames)]
     if args.diversity:
         div = quality.DiversityReport.merged(diversity)
-        nan_none = lambda d: {k: (None if x != x else x) for k, x in d.items()}
         last_div = nan_none(div.summary(-1))
         print_dict(last_div)
         out['diversity'] = dict(last_div, num_included=int(div.n_included[-1]), num_distinct=int(div.n_distinct[-1]))
@@ -208,37 +224,18 @@ def main(argv=None):
     if args.geometry:
         geo = quality.GeometryReport.merged(geometry)
         print('\n'.join(geo.lines(-1)))
-        nan_none = lambda x: None if isinstance(x, float) and x != x else x
-        flat = lambda d: {k: ({q: nan_none(y) for q, y in x.items()} if isinstance(x, dict) else nan_none(x)) for k, x in d.items()}
+        scalar = lambda x: None if isinstance(x, float) and x != x else x
+        flat = lambda d: {k: ({q: scalar(y) for q, y in x.items()} if isinstance(x, dict) else scalar(x)) for k, x in d.items()}
         out['geometry'] = dict(flat(geo.summary(-1)), num_included=int(geo.n_included[-1]),
                                hist={n: geo.counts(n, -1).tolist() for n in geo.names})
         if eval_step == 'all':
             out['geometry']['curve'] = [flat(geo.summary(s)) for s in range(geo.num_frames)]
-    if args.pocket:
-        poc = quality.PocketReport.merged(pocket)
-        print('\n'.join(poc.lines(-1)))
-        nan_none = lambda d: {k: (None if x != x else x) for k, x in d.items()}
-        out['pocket'] = dict(nan_none(poc.summary(-1)), num_included=int(poc.n_included[-1]), contact_cutoff=args.contact_cutoff,
-                             clash_tolerance=args.clash_tolerance, contact_profile=poc.contact_profile(-1),
-                             kind_hist=dict(zip(poc.names, poc.kind_hist[-1].sum(0).tolist())))
+    for flag, report_class, _, fields in sections:
+        total = report_class.merged(against_pocket[flag])
+        print('\n'.join(total.lines(-1)))
+        out[flag] = dict(nan_none(total.summary(-1)), num_included=int(total.n_included[-1]), **fields(total))
         if eval_step == 'all':
-            out['pocket']['curve'] = [nan_none(poc.summary(s)) for s in range(poc.num_frames)]
-    if args.interactions:
-        ia = quality.InteractionReport.merged(interactions)
-        print('\n'.join(ia.lines(-1)))
-        nan_none = lambda d: {k: (None if x != x else x) for k, x in d.items()}
-        out['interactions'] = dict(nan_none(ia.summary(-1)), num_included=int(ia.n_included[-1]), hbond_cutoff=args.hbond_cutoff,
-                                   hydrophobic_cutoff=args.hydrophobic_cutoff,
-                                   kind_hist={t: dict(zip(ia.names, ia.kind_hist[-1, k].tolist())) for k, t in enumerate(quality.INTERACTION_NAMES)})
-        if eval_step == 'all':
-            out['interactions']['curve'] = [nan_none(ia.summary(s)) for s in range(ia.num_frames)]
-    if args.sasa:
-        sa = quality.SasaReport.merged(sasa)
-        print('\n'.join(sa.lines(-1)))
-        nan_none = lambda d: {k: (None if x != x else x) for k, x in d.items()}
-        out['sasa'] = dict(nan_none(sa.summary(-1)), num_included=int(sa.n_included[-1]), probe=args.probe, points=args.sasa_points)
-        if eval_step == 'all':
-            out['sasa']['curve'] = [nan_none(sa.summary(s)) for s in range(sa.num_frames)]
+            out[flag]['curve'] = [nan_none(total.summary(s)) for s in range(total.num_frames)]
     result_path = os.path.join(args.sample_path, 'eval_results')
     os.makedirs(result_path, exist_ok=True)
     with open(os.path.join(result_path, 'quality.json'), 'w') as f:

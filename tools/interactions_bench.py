@@ -64,8 +64,8 @@ def main():
     ptr = torch.as_tensor(np.cumsum([0] + sizes), dtype=torch.int32, device=dev)
     pos1, v1 = pos[-1:].contiguous(), v[-1:].contiguous()
     cz = quality.class_atomic_numbers('add_aromatic')
-    ppos, elem, kind, names = quality._pocket_arrays((ppos_np, feat), dev)
-    role = torch.from_numpy(quality.pocket_roles(feat)).to(dev)
+    side = quality.PocketSide((ppos_np, feat), dev)
+    ppos, elem, (kind, names), role = side.pos, side.elem, side.kinds(), side.roles()
     thr = quality.pocket_clash_thresholds()
     act = lambda p, c, full=False: capi.interaction_report(p, c, ptr, cz, ppos, elem, kind, role, len(names), return_atoms=full,
                                                            return_bits=full, check=False)

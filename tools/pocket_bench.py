@@ -68,7 +68,8 @@ def main():
     ptr = torch.as_tensor(np.cumsum([0] + sizes), dtype=torch.int32, device=dev)
     pos1, v1 = pos[-1:].contiguous(), v[-1:].contiguous()
     cz, aro = quality.class_atomic_numbers('add_aromatic'), quality.class_aromatic('add_aromatic')
-    ppos, elem, kind, names = quality._pocket_arrays((ppos_np, feat), dev)
+    side = quality.PocketSide((ppos_np, feat), dev)
+    ppos, elem, (kind, names) = side.pos, side.elem, side.kinds()
     thr = quality.pocket_clash_thresholds()
     poc = lambda p, c, t=thr, full=False: capi.pocket_report(p, c, ptr, cz, ppos, elem, kind, len(names), quality.DEFAULT_CONTACT_CUTOFF, t,
                                                               None, None, full, full, check=False)

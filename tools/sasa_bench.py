@@ -77,11 +77,12 @@ def main():
     v = torch.from_numpy(np.concatenate(res[3], axis=1)).to(dev)
     ptr = torch.as_tensor(np.cumsum([0] + sizes), dtype=torch.int32, device=dev)
     cz = quality.class_atomic_numbers('add_aromatic')
-    ppos, selem = quality._sasa_pocket((ppos_np, feat), dev)
+    side = quality.PocketSide((ppos_np, feat), dev)
+    ppos, selem = side.pos, side.kinds('element')[0]
     lr, pr = quality.sasa_reaches(args.probe)
     dirs = torch.from_numpy(quality.sasa_directions(args.points)).to(dev)
     sasa = lambda p, c, q=ptr, full=False: capi.sasa_report(p, c, q, cz, ppos, selem, lr, pr, dirs, None, full, full, check=False)
-    _, elem, kind, names = quality._pocket_arrays((ppos_np, feat), dev)
+    elem, (kind, names) = side.elem, side.kinds()
     thr = quality.pocket_clash_thresholds()
     poc = lambda p, c: capi.pocket_report(p, c, ptr, cz, ppos, elem, kind, len(names), quality.DEFAULT_CONTACT_CUTOFF, thr, None, None, False,
                                           False, check=False)

@@ -525,6 +525,49 @@ int td_interaction_report(const float *d_pos, const int64_t *d_v, const int32_t 
                           int32_t *d_atom_hbonds, int32_t *d_atom_hydrophobic, uint64_t *d_bits, int64_t *d_kind_hist,
                           int32_t *d_pocket_freq, void *stream);
 
+/* ---- docking-style score of ligand frames ("Docking-style score"): per molecule the five unweighted term sums
+ *      of a Vina-style pair energy with one pocket, as integers, and the rotatable bonds.  No energy is formed here: the weights and
+ *      the rotor normalisation are the caller's.  It is a score on this project's heuristic typing -- no hydrogens are placed, the
+ *      roles come from valence deficits, there is no intramolecular term -- and NOT AutoDock Vina's number: comparable between runs of
+ *      this library, not with published tables.  The pack, the class table, d_protein_pos, d_protein_elem, d_protein_kind,
+ *      d_protein_role, N_p, n_kinds and hetero_cutoff as td_interaction_report takes them; there is no d_include (nothing is summed
+ *      over molecules).  class_aromatic as td_bond_graph's, read by the rotor kernel's bond graph only.
+ *      Who takes part: a ligand atom whose class is in [0, K) and whose element is not H; a protein atom that takes part in
+ *      td_interaction_report (element and kind in range, role >= 0) and whose element is not H.  Roles: the ligand's and the
+ *      protein's resolved roles of td_interaction_report, bit for bit; d_protein_role_out [N_p] int32 is written as there.
+ *      Distance: r, the bond rule's float64 distance (td_pocket_report's d).  A pair counts when r < cutoff, strictly (finite, > 0;
+ *      8.0 by convention).  Surface distance d = r - rsum[e_l * 6 + e_p], one rounding; rsum: HOST float64 [8 * 6], ligand element
+ *      over H C N O F P S Cl by protein element over H C N O S Se, R_l + R_p formed by the caller, every entry in (0, 6] (else
+ *      TD_EINVAL; the H entries are never read).
+ *      Terms of a pair, float64 with every product, sum and difference rounded on its own (no FMA contraction):
+ *        0 gauss1      exp(-(d 2)^2)                                             every pair
+ *        1 gauss2      exp(-((d - 3) / 2)^2)                                     every pair
+ *        2 repulsion   d d if d < 0, else 0                                      every pair
+ *        3 hydrophobic 1 if d < 0.5; 1.5 - d if d < 1.5; else 0                  both atoms HYDROPHOBIC
+ *        4 hbond       1 if d < -0.7; (-d) / 0.7 if d < 0; else 0                ligand DONOR with protein ACCEPTOR, or ligand
+ *                                                                                ACCEPTOR with protein DONOR; once per pair
+ *      Each value becomes llrint(ldexp(value, 24)) (nearest, ties to even) and is added as int64: d_terms [S,B,5] int64 in units of
+ *      2^-24, exact whatever the order of arrival; d_n_pairs [S,B] int32, the pairs with r < cutoff.  Only exp can differ from a
+ *      float64 restatement: terms 2, 3, 4 are exact, terms 0 and 1 differ by at most one unit per pair.  A value is at most 36, 512
+ *      N_p must fit 31 bits, so a molecule's sum stays below 2^61.
+ *      Rotatable bonds, d_n_rot [S,B] int32, on the bond graph of td_bond_graph (the same pack, class table and aromatic flags): a
+ *      bond i < j whose order is 1, whose ring size is 0 -- d_bond_ring [n_bonds] of td_ring_report at the bond's index in
+ *      td_bond_list's order, d_bond_ptr [S * B + 1] of td_bond_graph; an index outside [0, n_bonds) reads nothing and the bond counts
+ *      as not rotatable -- and whose two ends each have at least two bonded heavy atoms (a class in the table, an element other than
+ *      H; the other end counts).  Amide bonds and single bonds next to a triple bond are NOT excluded: a convention.  d_bond_ptr,
+ *      n_bonds and d_bond_ring may all be NULL / 0: no rotor kernel runs and d_n_rot is not written; only some of them: TD_EINVAL
+ *      (d_bond_ring may be NULL when n_bonds is 0).
+ *      A molecule of more than 512 atoms, or one whose offsets leave [0, N_l], gets -1 in d_n_pairs and d_n_rot and INT64_MIN in its
+ *      five terms, and contributes nothing else (a binding refuses it).  S, B and N_p may be 0; with N_p = 0 every term and
+ *      d_n_pairs are 0.  Every output is an integer: two runs give identical bytes, and there is no floating-point atomic.
+ *      (An addition: TD_ABI_VERSION stays 5.) */
+int td_score_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                    const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+                    const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p,
+                    int32_t n_kinds, double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr,
+                    int64_t n_bonds, const uint16_t *d_bond_ring, int32_t *d_protein_role_out, int64_t *d_terms, int32_t *d_n_pairs,
+                    int32_t *d_n_rot, void *stream);
+
 /* ---- solvent-accessible surface of ligand frames by Shrake-Rupley point counting ("Solvent-accessible
  *      surface"): every output is a count of sphere points; areas are formed by the caller.  One pocket and one pack per call; the
  *      pack, the class table and d_include as td_pocket_report takes them.  d_protein_pos [N_p,3] fp32; d_protein_elem [N_p] int32, an

@@ -106,6 +106,8 @@ SIGNATURES = {
     'td_interaction_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, _P, _P, _P, c_int64, c_int32,
                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                         _P, _P, _P, _P, _P]),
+    'td_score_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), _P, _P, _P, _P, c_int64,
+                                  c_int32, ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double), _P, c_int64, _P, _P, _P, _P, _P, _P]),
     'td_sasa_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, _P, c_int64, POINTER(ctypes.c_double),
                                  POINTER(ctypes.c_double), _P, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -1321,6 +1323,66 @@ def interaction_report(pos, v, ligand_ptr, class_z, protein_pos, protein_elem, p
                                          _ptr(out['n_ref_common']), _ptr(out['atom_role']), _ptr(out['atom_hbonds']),
                                          _ptr(out['atom_hydrophobic']), _ptr(out['bits']), _ptr(out['kind_hist']), _ptr(out['pocket_freq']),
                                          _stream(dev)), 'td_interaction_report')
+    return out
+
+
+SCORE_TERMS, SCORE_FRAC_BITS = 5, 24                                        # TD_SCORE_* (csrc/td_internal.h)
+SCORE_TERM_NAMES = ('gauss1', 'gauss2', 'repulsion', 'hydrophobic', 'hbond')
+SCORE_MAX_RADIUS_SUM = 6.0
+
+
+def _score_inputs(pos, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, rsum, cutoff, hetero_cutoff, bond_ptr, bond_ring,
+                  S, B, check=True):
+    """The pocket's side of a score_report call (_protein_inputs), the two cutoffs, the radius-sum table and the rotor inputs.  Returns
+    (N_p, the table as float64 numpy [48], n_bonds)."""
+    Np, _ = _protein_inputs(pos, protein_pos, protein_elem, protein_kind, n_kinds, protein_role, who='score_report',
+                            beside=(bond_ptr, bond_ring), what='the pocket and the bond arguments', check=check)
+    for name, c in (('score', cutoff), ('hetero', hetero_cutoff)):
+        if not (np.isfinite(float(c)) and float(c) > 0.0):
+            raise ValueError(f'the {name} cutoff must be finite and > 0 (got {c})')
+    if 512 * Np > 0x7fffffff:
+        raise ValueError(f'512 N_p must fit 31 bits (N_p = {Np})')
+    rs = np.asarray(rsum, dtype=np.float64)
+    if rs.shape not in ((8, POCKET_ELEMENTS), (8 * POCKET_ELEMENTS,)):
+        raise ValueError(f'rsum is an [8, {POCKET_ELEMENTS}] table of radius sums: H C N O F P S Cl by H C N O S Se')
+    if not np.isfinite(rs).all() or not ((rs > 0.0) & (rs <= SCORE_MAX_RADIUS_SUM)).all():
+        raise ValueError(f'every entry of rsum must be finite and in (0, {SCORE_MAX_RADIUS_SUM:g}]')
+    if (bond_ptr is None) != (bond_ring is None):
+        raise ValueError('bond_ptr of bond_graph and bond_ring of ring_report come together, or neither')
+    _bond_ptr_input(bond_ptr, S, B)
+    if bond_ring is not None and (bond_ring.dim() != 1 or bond_ring.dtype != torch.int16):
+        raise ValueError('bond_ring must be [n_bonds] int16, as ring_report returns it')
+    return Np, np.ascontiguousarray(rs.reshape(-1)), 0 if bond_ring is None else int(bond_ring.numel())
+
+
+def score_report(pos, v, ligand_ptr, class_z, class_aromatic, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, rsum,
+                 cutoff=8.0, hetero_cutoff=1.75, bond_ptr=None, bond_ring=None, check=True):
+    """The five unweighted term sums of a Vina-style pair score of S frames of B molecules with one pocket, and their rotatable bonds
+    (td_score_report, include/targetdiff_hip.h).  A score on this project's heuristic typing -- no hydrogens, roles from valence
+    deficits, no intramolecular term -- and not AutoDock Vina's number: comparable between runs of this tool, not with published
+    tables.  The pack, the class table and ``class_aromatic`` as bond_graph's; the pocket, ``protein_role`` and ``hetero_cutoff`` as
+    interaction_report's.  ``rsum`` [8, 6] float64: R_l + R_p, ligand element over H C N O F P S Cl by protein element over H C N O S
+    Se, every entry in (0, 6]; a pair counts when the bond rule's distance r < ``cutoff`` and its surface distance is r - rsum.
+    ``bond_ptr`` [S * B + 1] int64 of bond_graph and ``bond_ring`` [n_bonds] int16 of ring_report on the same pack: with both the
+    rotatable bonds are counted (order 1, in no ring, both ends with at least two bonded heavy atoms; amides are not excluded).
+    Returns a dict of device tensors: protein_role [N_p] int32, terms [S, B, 5] int64 in units of 2^-24 (``SCORE_TERM_NAMES``),
+    n_pairs [S, B] int32 and n_rot [S, B] int32 (None without the bond arguments).  An oversize molecule, refused under ``check``,
+    gets -1 / INT64_MIN."""
+    S, Nl, B, cz, aro, _ = _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, None, (), check)
+    Np, rs, nb = _score_inputs(pos, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, rsum, cutoff, hetero_cutoff, bond_ptr,
+                               bond_ring, S, B, check)
+    lib = load_library()
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
+    dev = pos.device
+    i32, _, i64 = _allocators(dev)
+    out = dict(protein_role=i32(Np), terms=i64(S, B, SCORE_TERMS), n_pairs=i32(S, B), n_rot=i32(S, B) if bond_ptr is not None else None)
+    with _on(dev):
+        _check(lib.td_score_report(*pack, _aromatic_arg(aro), _ptr(protein_pos, torch.float32, 'protein_pos'),
+                                   _ptr(protein_elem, torch.int32, 'protein_elem'), _ptr(protein_kind, torch.int32, 'protein_kind'),
+                                   _ptr(protein_role, torch.int32, 'protein_role'), Np, int(n_kinds), float(cutoff), float(hetero_cutoff),
+                                   rs.ctypes.data_as(POINTER(ctypes.c_double)), _ptr(bond_ptr, torch.int64, 'bond_ptr'), nb,
+                                   _ptr(bond_ring, torch.int16, 'bond_ring') if nb else None, _ptr(out['protein_role']), _ptr(out['terms']),
+                                   _ptr(out['n_pairs']), _ptr(out['n_rot']), _stream(dev)), 'td_score_report')
     return out
 
 

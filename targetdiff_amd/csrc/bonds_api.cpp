@@ -1,6 +1,7 @@
 // C ABI of libtargetdiff_hip.so: the bond graph of ligand frames, its rings, its fingerprints, its local geometry and the contacts with
-// the pocket, the typed interactions with it and the surface it buries (td_bond_graph, td_bond_list, td_ring_report, td_fingerprint,
-// td_fingerprint_similarity, td_geometry_report, td_pocket_report, td_interaction_report, td_sasa_report).  See
+// the pocket, the typed interactions with it, the docking-style score and the surface it buries (td_bond_graph, td_bond_list,
+// td_ring_report, td_fingerprint, td_fingerprint_similarity, td_geometry_report, td_pocket_report, td_interaction_report,
+// td_score_report, td_sasa_report).  See
 // include/targetdiff_hip.h for the contract.
 #include <cmath>
 #include <initializer_list>
@@ -311,6 +312,61 @@ extern "C" int td_interaction_report(const float *d_pos, const int64_t *d_v, con
     g.n_ref_common = d_n_ref_common;
     g.atom_role = d_atom_role; g.atom_hbonds = d_atom_hbonds; g.atom_hydrophobic = d_atom_hydrophobic;
     return td_launch_interaction_report(g, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int td_score_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                               const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+                               const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p,
+                               int32_t n_kinds, double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr,
+                               int64_t n_bonds, const uint16_t *d_bond_ring, int32_t *d_protein_role_out, int64_t *d_terms,
+                               int32_t *d_n_pairs, int32_t *d_n_rot, void *stream) {
+    const char *who = "td_score_report";
+    TdScoreArgs g;
+    if (const int rc = bond_pack(who, g.b, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, n_bonds)) return rc;
+    if (N_p < 0 || N_p > 0x7fffffff / TD_BOND_MAX_ATOMS) {                      // a molecule's pairs are counted in an int32
+        td_set_error("%s: bad argument (N_p = %lld; 512 N_p must fit 31 bits)", who, (long long)N_p);
+        return TD_EINVAL;
+    }
+    if (n_kinds < 1 || n_kinds > TD_POCKET_MAX_KINDS) {
+        td_set_error("%s: 1 .. %d kinds of protein atoms (got %d)", who, TD_POCKET_MAX_KINDS, (int)n_kinds);
+        return TD_EINVAL;
+    }
+    for (const double c : {cutoff, hetero_cutoff})
+        if (!std::isfinite(c) || !(c > 0.0)) {
+            td_set_error("%s: the cutoff and the hetero cutoff must be finite and > 0", who);
+            return TD_EINVAL;
+        }
+    if (!rsum) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
+    for (int k = 0; k < 8 * TD_POCKET_ELEMENTS; ++k) {
+        if (!std::isfinite(rsum[k]) || !(rsum[k] > 0.0) || !(rsum[k] <= 6.0)) {
+            td_set_error("%s: every radius sum must be in (0, 6] (entry %d)", who, k);
+            return TD_EINVAL;
+        }
+        g.rsum[k] = rsum[k];
+    }
+    // the rotor inputs come together: the offsets of td_bond_graph, the length of the list and, where it has entries, the ring sizes
+    const bool rotors = d_bond_ptr != nullptr;
+    if ((!rotors && (d_bond_ring || n_bonds != 0)) || (rotors && n_bonds > 0 && !d_bond_ring)) {
+        td_set_error("%s: d_bond_ptr, n_bonds and d_bond_ring are given together or not at all", who);
+        return TD_EINVAL;
+    }
+    if ((N_p > 0 && (!d_protein_pos || !d_protein_elem || !d_protein_kind || !d_protein_role || !d_protein_role_out)) ||
+        (S > 0 && B > 0 && (!d_terms || !d_n_pairs || (rotors && !d_n_rot)))) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    TdInteractionArgs roles;
+    TdProteinSide &p = roles.p;
+    p.ppos = d_protein_pos; p.pelem = d_protein_elem; p.pkind = d_protein_kind;
+    p.Np = (int)N_p; p.W = (int)((N_p + 63) / 64); p.n_kinds = n_kinds;
+    roles.prole = d_protein_role; roles.hetero_cutoff = hetero_cutoff; roles.role_out = d_protein_role_out;
+    if (const int rc = td_launch_protein_roles(roles, static_cast<hipStream_t>(stream))) return rc;
+    g.p = p;
+    g.role = d_protein_role_out;
+    g.cutoff = cutoff;
+    g.b.bond_ptr = const_cast<int64_t *>(d_bond_ptr); g.b.bond_ring = const_cast<uint16_t *>(d_bond_ring);
+    g.terms = reinterpret_cast<long long *>(d_terms); g.n_pairs = d_n_pairs; g.n_rot = d_n_rot;
+    return td_launch_score_report(g, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int td_sasa_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,

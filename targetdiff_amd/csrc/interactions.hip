@@ -20,7 +20,6 @@
 #include "td_pocket_walk.h"
 
 constexpr int IX_T = PW_T, IX_WAVES = PW_WAVES, IX_K = TD_POCKET_MAX_KINDS, IX_TYPES = TD_INTERACTION_TYPES;
-constexpr int IX_H = 0, IX_C = 1, IX_N = 2, IX_O = 3, IX_F = 4, IX_CL = 7;      // element indices of the ligand (H C N O F P S Cl)
 constexpr int IX_PC = 1, IX_PN = 2, IX_PO = 3;                                  // and of the protein (H C N O S Se)
 
 __global__ __launch_bounds__(IX_T) void protein_role_kernel(TdInteractionArgs g) {
@@ -58,33 +57,6 @@ __global__ __launch_bounds__(IX_T) void protein_role_kernel(TdInteractionArgs g)
             }
     }
     if (j < Np) g.role_out[j] = carbon && !polar_near ? role | TD_ROLE_HYDROPHOBIC : role;
-}
-
-// The role of ligand atom i (element index el >= 0) from its bonds: val the sum of the orders, n_h the bonded hydrogens, hetero the
-// bonded N / O.  Only C, N and O need their bonds.
-__device__ __forceinline__ int ix_ligand_role(int i, int n, const float4 *s_at, const double (*s_thr)[64]) {
-    const float4 me = s_at[i];
-    const int el = __float_as_int(me.w);
-    if (el == IX_F || el == IX_CL) return TD_ROLE_HYDROPHOBIC;
-    if (el != IX_C && el != IX_N && el != IX_O) return 0;                       // H, P, S, and a class outside the table (-1)
-    const double xi = (double)me.x, yi = (double)me.y, zi = (double)me.z;
-    int val = 0, n_h = 0, hetero = 0;
-    for (int j = 0; j < n; ++j) {
-        const float4 q = s_at[j];
-        const int ej = __float_as_int(q.w);
-        if (j == i || ej < 0) continue;
-        double d;
-        const int order = td_bond_order(xi, yi, zi, q.x, q.y, q.z, el * 8 + ej, s_thr, d);
-        if (order == 0) continue;
-        val += order;
-        n_h += ej == IX_H;
-        hetero += ej == IX_N || ej == IX_O;
-    }
-    if (el == IX_C) return hetero == 0 ? TD_ROLE_HYDROPHOBIC : 0;
-    const int implicit = (el == IX_N ? 3 : 2) - val, h = n_h + (implicit > 0 ? implicit : 0);
-    int role = h >= 1 ? TD_ROLE_DONOR : 0;
-    if (el == IX_O || (h == 0 && val <= 3)) role |= TD_ROLE_ACCEPTOR;
-    return role;
 }
 
 __global__ __launch_bounds__(IX_T) void interaction_kernel(TdInteractionArgs g) {
@@ -214,9 +186,15 @@ __global__ __launch_bounds__(IX_T) void interaction_kernel(TdInteractionArgs g) 
 int td_launch_interaction_report(const TdInteractionArgs &args, hipStream_t s) {
     TdInteractionArgs g = args;
     g.reject2 = pw_reject2(std::fmax(g.hbond_cutoff, g.hydrophobic_cutoff));
+    if (const int rc = td_launch_protein_roles(g, s)) return rc;
+    return pw_launch(interaction_kernel, g, IX_TYPES, IX_TYPES, s);
+}
+
+// The protein roles alone, for the reports that read them (score.hip): nothing is launched for an empty pocket
+int td_launch_protein_roles(const TdInteractionArgs &g, hipStream_t s) {
     if (g.p.Np > 0) {
         protein_role_kernel<<<dim3((unsigned)((g.p.Np + IX_T - 1) / IX_T)), dim3(IX_T), 0, s>>>(g);
         TD_CHECK_HIP(hipGetLastError());
     }
-    return pw_launch(interaction_kernel, g, IX_TYPES, IX_TYPES, s);
+    return TD_OK;
 }

@@ -556,6 +556,24 @@ struct TdInteractionArgs {
     int32_t *atom_role = nullptr, *atom_hbonds = nullptr, *atom_hydrophobic = nullptr;      // [S,N_l] or null
 };
 int td_launch_interaction_report(const TdInteractionArgs &a, hipStream_t s);
+// the protein roles alone (protein_role_kernel: reads p, prole and hetero_cutoff, writes role_out); score.hip resolves them with it
+int td_launch_protein_roles(const TdInteractionArgs &a, hipStream_t s);
+// score.hip (td_score_report, DESIGN.md section 3, "Docking-style score"): the pack in `b` (its include bytes are not used; bond_ptr /
+// capacity / bond_ring are read by the rotor kernel, all null: no rotor kernel); of the pocket ppos, pelem, pkind, Np and n_kinds; role:
+// the resolved protein roles (role_out of td_launch_protein_roles).  rsum[e_l * 6 + e_p] = R_l + R_p, e_l over H C N O F P S Cl.
+// reject2 as TdPocketArgs, of the cutoff.  terms: per molecule the five unweighted term sums in units of 2^-TD_SCORE_FRAC_BITS.
+constexpr int TD_SCORE_TERMS = 5, TD_SCORE_FRAC_BITS = 24;
+struct TdScoreArgs {
+    TdBondArgs b;
+    TdProteinSide p;
+    const int32_t *role = nullptr;           // [Np]
+    double cutoff = 0.0, reject2 = 0.0;
+    double rsum[8 * TD_POCKET_ELEMENTS] = {};
+    long long *terms = nullptr;              // [S,B,TD_SCORE_TERMS]
+    int32_t *n_pairs = nullptr;              // [S,B]
+    int32_t *n_rot = nullptr;                // [S,B], written when bond_ptr
+};
+int td_launch_score_report(const TdScoreArgs &a, hipStream_t s);
 // sasa.hip (td_sasa_report, DESIGN.md section 3, "Solvent-accessible surface"): the pack and the include bytes in `b` (none of b's
 // outputs is used); the pocket as TdProteinSide holds it, without kinds, in fields of its own (its kernels keep the argument block they
 // were measured with: EXPERIMENTS.md "Pocket reports").  lig_R over H C N O F P S Cl and prot_R over H C N O S Se: the

@@ -1,4 +1,4 @@
-// What the kernels that walk a pocket share (pocket.hip, interactions.hip; sasa.hip keeps its own walk and its own argument block;
+// What the kernels that walk a pocket share (pocket.hip, interactions.hip, score.hip; sasa.hip keeps its own walk and its own argument block;
 // DESIGN.md section 3, "Pocket contacts"): one workgroup of four waves per (frame, molecule), the molecule staged in LDS, threads that
 // own protein atoms at stride 256, and per bit plane the word of 64 protein atoms as a wave ballot.  One copy, so that the reports say
 // the protein side alike.
@@ -22,6 +22,35 @@ __device__ __forceinline__ void pw_stage(const TdBondArgs &a, const BgMol &m, co
         const int64_t c = a.v[at];
         s_at[i] = make_float4(p[0], p[1], p[2], __int_as_float(c >= 0 && c < a.K ? s_elem[(int)c] : -1));
     }
+}
+
+constexpr int IX_H = 0, IX_C = 1, IX_N = 2, IX_O = 3, IX_F = 4, IX_CL = 7;      // element indices of the ligand (H C N O F P S Cl)
+
+// The role of ligand atom i (element index el >= 0) from its bonds: val the sum of the orders, n_h the bonded hydrogens, hetero the
+// bonded N / O.  Only C, N and O need their bonds.
+__device__ __forceinline__ int ix_ligand_role(int i, int n, const float4 *s_at, const double (*s_thr)[64]) {
+    const float4 me = s_at[i];
+    const int el = __float_as_int(me.w);
+    if (el == IX_F || el == IX_CL) return TD_ROLE_HYDROPHOBIC;
+    if (el != IX_C && el != IX_N && el != IX_O) return 0;                       // H, P, S, and a class outside the table (-1)
+    const double xi = (double)me.x, yi = (double)me.y, zi = (double)me.z;
+    int val = 0, n_h = 0, hetero = 0;
+    for (int j = 0; j < n; ++j) {
+        const float4 q = s_at[j];
+        const int ej = __float_as_int(q.w);
+        if (j == i || ej < 0) continue;
+        double d;
+        const int order = td_bond_order(xi, yi, zi, q.x, q.y, q.z, el * 8 + ej, s_thr, d);
+        if (order == 0) continue;
+        val += order;
+        n_h += ej == IX_H;
+        hetero += ej == IX_N || ej == IX_O;
+    }
+    if (el == IX_C) return hetero == 0 ? TD_ROLE_HYDROPHOBIC : 0;
+    const int implicit = (el == IX_N ? 3 : 2) - val, h = n_h + (implicit > 0 ? implicit : 0);
+    int role = h >= 1 ? TD_ROLE_DONOR : 0;
+    if (el == IX_O || (h == 0 && val <= 3)) role |= TD_ROLE_ACCEPTOR;
+    return role;
 }
 
 // the answer to an oversize molecule for its T planes of bit words: none set

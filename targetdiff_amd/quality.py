@@ -66,6 +66,15 @@ project, not perceived chemistry:
     ia.summary()   # {'mean_hbonds': ..., 'mean_donated': ..., 'mean_accepted': ..., 'mean_hydrophobic': ..., 'no_hbond': ..., ...}
     ia.kind_profile('donated'), ia.interaction_frequency()    # hydrogen bonds by residue kind, and per type and protein atom
 
+And a docking-style score of the poses (``td_score_report``, csrc/score.hip; DESIGN.md section 3, "Docking-style score"): the five
+Vina-style terms (two Gaussians, repulsion, hydrophobic, hydrogen bond) summed over the ligand - pocket heavy-atom pairs within 8 A,
+weighted on the host and divided by 1 + 0.0585 rotatable bonds.  It runs on this project's heuristic typing -- no hydrogens are placed,
+the roles come from valence deficits, there is no intramolecular term -- so it is NOT AutoDock Vina's number: comparable between runs
+of this tool, not with published tables:
+
+    sc = quality.sample_score(result, eval_step='all', reference_ligand=(ref_pos, ref_v))
+    sc.summary()   # {'mean_score': ..., 'median_score': ..., 'best_score': ..., 'share_negative': ..., 'better_than_ref': ..., ...}
+
 And how much of a pose's surface the pocket covers (``td_sasa_report``, csrc/sasa.hip; DESIGN.md section 3, "Solvent-accessible
 surface"): Shrake-Rupley point counts of the ligand alone and in the pocket, areas formed on the host from Bondi-type radii plus a
 1.4 A probe -- comparable between runs of this tool, not with published tables; of the pocket, a cut-out, only the buried area:
@@ -78,9 +87,9 @@ Several reports of one result share its pack, its host checks and its bond graph
     pack = quality.SamplePack(result, eval_step='all')
     rep, con, rings = pack.quality('complete'), pack.connectivity('complete'), pack.rings('complete')    # one upload, one plain bond graph
     side = quality.PocketSide(result['data'])                       # the pocket decoded once and uploaded once
-    poc, ia, sa = pack.pocket(side), pack.interactions(side), pack.sasa(side)
+    poc, ia, sa, sc = pack.pocket(side), pack.interactions(side), pack.sasa(side), pack.score(side)
 
-OpenBabel's reconstruction, valence repair, QED / SA and docking need a chemistry toolkit and are not here.
+OpenBabel's reconstruction, valence repair, QED / SA and AutoDock Vina's own docking need a chemistry toolkit and are not here.
 """
 from __future__ import annotations
 
@@ -528,6 +537,28 @@ class SamplePack:
         raw = {k: r[k].cpu().numpy() for k in keys if r[k] is not None}
         return InteractionReport.from_outputs(raw, self._included(mask), self.sizes, names, ref_sizes)
 
+    def score(self, data, include='all', reference_ligand=None, weights=None, rot_weight=None, cutoff=None):
+        """``sample_score`` of the pack; ``data`` as ``pocket``.  The rotatable bonds are counted on the pack's bond graph and ring sizes."""
+        weights = SCORE_WEIGHTS if weights is None else weights
+        rot_weight = SCORE_ROT_WEIGHT if rot_weight is None else rot_weight
+        side = self._side(data)
+        kind, names = side.kinds()
+        mask = self.mask(include)
+        pocket = (side.pos, side.elem, kind, side.roles(), len(names), score_radius_sums(), SCORE_CUTOFF if cutoff is None else cutoff,
+                  DEFAULT_HETERO_CUTOFF)
+        ref_score = None
+        if reference_ligand is not None:
+            ref = self._reference(reference_ligand)
+            bond_ptr = capi.bond_graph(*ref, self.aromatic, (), None, False, True)['bond_ptr']
+            ring = capi.ring_report(*ref, self.aromatic, None, bond_ptr, False)['bond_ring']
+            q = capi.score_report(*ref, self.aromatic, *pocket, bond_ptr, ring)
+            if int(q['n_pairs'][0, 0]) >= 0:
+                ref_score = float(score_energies(q['terms'].cpu().numpy(), q['n_rot'].cpu().numpy(), weights, rot_weight)[2][0, 0])
+        r = capi.score_report(*self._args, self.aromatic, *pocket, self.graph['bond_ptr'], self.bond_ring, check=self._check())
+        raw = {k: r[k].cpu().numpy() for k in ('terms', 'n_pairs', 'n_rot')}
+        heavy = _heavy_atoms(self.v.cpu().numpy(), self.class_z, self.sizes)
+        return ScoreReport.from_outputs(raw, self._included(mask), heavy, weights, rot_weight, ref_score)
+
     def sasa(self, data, include='all', reference_ligand=None, probe=1.4, points=96):
         """``sample_sasa`` of the pack; ``data`` as ``pocket``"""
         side = self._side(data)
@@ -685,8 +716,9 @@ def sample_connectivity(result, eval_step=-1, include='all', atom_enc_mode='add_
 
 _i64, _f64 = (lambda a: np.asarray(a, dtype=np.int64)), (lambda a: np.asarray(a, dtype=np.float64))
 # the kinds of a report's fields as (how a constructor argument is taken, how ``merged`` combines it): summed over the reports; carried
-# from the first; a per-pocket map, kept only for a single report; a sum that exists only with a reference ligand
-_FIELD_KINDS = {'i64': (_i64, 'sum'), 'f64': (_f64, 'sum'), 'int_sum': (int, 'sum'), 'int_carried': (int, 'carried'), 'tuple': (tuple, 'carried'),
+# from the first; a per-pocket map, kept only for a single report; a sum that exists only with a reference ligand; a per-molecule array
+# [S, B, ...], joined along the molecule axis
+_FIELD_KINDS = {'per_mol': (np.asarray, 'mol'), 'i64': (_i64, 'sum'), 'f64': (_f64, 'sum'), 'int_sum': (int, 'sum'), 'int_carried': (int, 'carried'), 'tuple': (tuple, 'carried'),
                 'value': (lambda x: x, 'carried'), 'flags': (lambda a: np.asarray(a, dtype=bool), 'carried'), 'map': (_i64, 'map'),
                 'ref_i64': (_i64, 'ref'), 'ref_f64': (_f64, 'ref')}
 
@@ -721,7 +753,8 @@ class _SumReport:
             raise ValueError(cls.MISMATCH)
         tot = lambda name: sum(getattr(r, name) for r in reports)
         how = {'sum': tot, 'carried': lambda name: getattr(first, name), 'map': lambda name: getattr(first, name) if len(reports) == 1 else None,
-               'ref': lambda name: None if first.sum_ref is None else tot(name)}
+               'ref': lambda name: None if first.sum_ref is None else tot(name),
+               'mol': lambda name: np.concatenate([getattr(r, name) for r in reports], axis=1)}
         return cls(*(how[_FIELD_KINDS[kind][1]](name) for name, kind in cls.FIELDS))
 
     @property
@@ -1613,6 +1646,192 @@ def sample_interactions(result, eval_step=-1, include='all', reference_ligand=No
     conventions (``pocket_interactions``).  A result without a pocket is refused.  Returns an ``InteractionReport``."""
     return SamplePack(result, eval_step, atom_enc_mode, device).interactions(_pocket_data(result, 'interactions'), include, reference_ligand,
                                                                              hbond_cutoff, hydrophobic_cutoff, hetero_cutoff)
+
+
+# ---- docking-style score (``td_score_report``, csrc/score.hip; DESIGN.md section 3, "Docking-style score")
+# A Vina-style score on this project's heuristic typing: the functional form and the weights are those of the AutoDock Vina paper
+# (Trott & Olson 2010), but no hydrogens are placed, the donor / acceptor / hydrophobic roles are those of ``pocket_interactions`` (valence
+# deficits and a residue table), the radii are one per element, and there is no intramolecular term.  It is NOT AutoDock Vina's number:
+# comparable between runs of this tool, not with published tables.  The kernel returns the five unweighted term sums as integers in
+# units of 2^-24; the weights and the rotor normalisation are applied here, so a caller may re-weight without a rebuild.
+SCORE_TERM_NAMES = capi.SCORE_TERM_NAMES              # gauss1, gauss2, repulsion, hydrophobic, hbond
+SCORE_WEIGHTS = (-0.035579, -0.005156, 0.840245, -0.035069, -0.587439)
+SCORE_ROT_WEIGHT = 0.0585
+SCORE_CUTOFF = 8.0
+SCORE_LIGAND_RADII = (0.0, 1.9, 1.8, 1.7, 1.5, 2.1, 2.0, 1.8)      # H C N O F P S Cl; H never takes part
+SCORE_PROTEIN_RADII = (0.0, 1.9, 1.8, 1.7, 2.0, 2.0)               # H C N O S Se
+
+
+def score_radius_sums(ligand_radii=None, protein_radii=None):
+    """[8, 6] float64, ligand element over H C N O F P S Cl by protein element over H C N O S Se: ``R_l + R_p`` of
+    ``SCORE_LIGAND_RADII`` and ``SCORE_PROTEIN_RADII`` or of the tables given.  The H row and column hold 1: hydrogens never take part,
+    so the entries are never read, and the entry point admits only sums in (0, 6]."""
+    rl = np.asarray(SCORE_LIGAND_RADII if ligand_radii is None else ligand_radii, dtype=np.float64)
+    rp = np.asarray(SCORE_PROTEIN_RADII if protein_radii is None else protein_radii, dtype=np.float64)
+    if rl.shape != (8,) or rp.shape != (6,):
+        raise ValueError('the radii are [8] over H C N O F P S Cl and [6] over H C N O S Se')
+    rs = rl[:, None] + rp[None, :]
+    rs[0, :] = 1.0
+    rs[:, 0] = 1.0
+    return rs
+
+
+def score_energies(terms, n_rot, weights=SCORE_WEIGHTS, rot_weight=SCORE_ROT_WEIGHT):
+    """``(terms, inter, score)`` as float64 numpy of the integer ``terms`` [..., 5] of td_score_report and ``n_rot`` [...] (None: no
+    rotors): the terms / 2^24, ``inter`` = weights . terms, ``score`` = inter / (1 + rot_weight n_rot)"""
+    t = np.asarray(terms, dtype=np.float64) / float(1 << capi.SCORE_FRAC_BITS)
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape != (capi.SCORE_TERMS,):
+        raise ValueError(f'the weights are {capi.SCORE_TERMS}: {", ".join(SCORE_TERM_NAMES)}')
+    inter = (t * w).sum(-1)
+    rot = np.zeros(inter.shape) if n_rot is None else np.asarray(n_rot, dtype=np.float64)
+    return t, inter, inter / (1.0 + np.float64(rot_weight) * rot)
+
+
+def _heavy_atoms(v, class_z, sizes):
+    """[S, B] int64: per molecule the atoms with a class in the table and an element other than H; ``v`` [S, N_l] numpy"""
+    z = np.asarray(class_z, dtype=np.int64)
+    v = np.asarray(v)
+    ok = (v >= 0) & (v < len(z))
+    heavy = ok & (z[np.where(ok, v, 0)] != 1)
+    ptr = np.cumsum([0] + [int(n) for n in sizes])
+    run = np.concatenate([np.zeros((v.shape[0], 1), np.int64), np.cumsum(heavy, axis=1, dtype=np.int64)], axis=1)
+    return run[:, ptr[1:]] - run[:, ptr[:-1]]
+
+
+class Score:
+    """The docking-style score of S frames of B molecules with one pocket (``pocket_score``).  ``protein_role`` [N_p] int32 on the
+    device; numpy, frame axis first: ``terms`` [S, B, 5] float64 (the unweighted sums, ``SCORE_TERM_NAMES``), ``n_pairs`` [S, B] int32,
+    ``n_rot`` [S, B] int32 or None, ``heavy_atoms`` [S, B], ``inter`` = weights . terms, ``score`` = inter / (1 + rot_weight n_rot) and
+    ``efficiency`` = score / heavy atoms (NaN without heavy atoms) [S, B] float64; ``raw_terms`` [S, B, 5] int64, the kernel's integers.
+    A molecule the kernel refused (n_pairs = -1) has NaN in the float outputs.  Not AutoDock Vina's number (``pocket_score``)."""
+
+    def __init__(self, r, ligand_ptr, heavy, weights, rot_weight):
+        self.protein_role, self.ligand_ptr = r['protein_role'], ligand_ptr
+        self.raw_terms, self.n_pairs = r['terms'].cpu().numpy(), r['n_pairs'].cpu().numpy()
+        self.n_rot = None if r['n_rot'] is None else r['n_rot'].cpu().numpy()
+        self.heavy_atoms = heavy
+        bad = self.n_pairs < 0
+        self.terms, self.inter, self.score = score_energies(np.where(bad[..., None], 0, self.raw_terms), self.n_rot, weights, rot_weight)
+        self.terms[bad], self.inter[bad], self.score[bad] = np.nan, np.nan, np.nan
+        self.efficiency = np.divide(self.score, heavy, out=np.full(self.score.shape, np.nan), where=heavy > 0)
+
+
+def pocket_score(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic', weights=SCORE_WEIGHTS,
+                 rot_weight=SCORE_ROT_WEIGHT, cutoff=SCORE_CUTOFF, hetero_cutoff=DEFAULT_HETERO_CUTOFF, ligand_radii=None, protein_radii=None,
+                 hydrogens=False, rotors=True, device=None):
+    """A Vina-style score of every molecule of one frame ``[N_l, 3]`` or of a stack ``[S, N_l, 3]`` (arguments as ``bond_graph``) in
+    the pocket ``protein_pos`` [N_p, 3], ``protein_feat`` [N_p, 27] (as ``pocket_contacts``).  Pairs: ligand heavy atoms with protein
+    heavy atoms that take part, at a bond-rule distance r < ``cutoff`` (8 A); surface distance d = r - R_l - R_p (``score_radius_sums``).
+    Terms: gauss1 exp(-(2 d)^2), gauss2 exp(-((d - 3) / 2)^2), repulsion d^2 for d < 0, hydrophobic (1 below 0.5 A, linear to 0 at
+    1.5 A, between HYDROPHOBIC atoms) and hbond (1 below -0.7 A, linear to 0 at 0, donor with acceptor), the roles those of
+    ``pocket_interactions``.  ``inter`` = ``weights`` . terms and ``score`` = inter / (1 + ``rot_weight`` n_rot); a rotatable bond has
+    order 1, lies in no ring and has two bonded heavy atoms at each end (amides and bonds next to a triple bond are not excluded: a
+    convention).  This runs ``td_bond_graph`` and ``td_ring_report`` for the rotors (``rotors=False``: none, score = inter), then
+    ``td_score_report``.  This is NOT AutoDock Vina's number: no hydrogens are placed, the roles are a valence-deficit heuristic and
+    there is no intramolecular term; it compares between runs of this tool, not with published tables.  Molecules of more than 512
+    atoms are refused.  Returns a ``Score``."""
+    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
+    side = PocketSide((protein_pos, protein_feat), pos.device)
+    (kind, names), elem = side.kinds('residue', hydrogens), side.elem
+    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
+    bond_ptr = bond_ring = None
+    if rotors:
+        bond_ptr = capi.bond_graph(pos, v, ligand_ptr, cz, aro, (), None, False, True)['bond_ptr']
+        bond_ring = capi.ring_report(pos, v, ligand_ptr, cz, aro, None, bond_ptr, False, check=False)['bond_ring']
+    r = capi.score_report(pos, v, ligand_ptr, cz, aro, side.pos, elem, kind, side.roles(hydrogens), len(names),
+                          score_radius_sums(ligand_radii, protein_radii), cutoff, hetero_cutoff, bond_ptr, bond_ring, check=not rotors)
+    sizes = ligand_ptr.cpu().to(torch.int64).diff().tolist()
+    return Score(r, ligand_ptr, _heavy_atoms(v.cpu().numpy(), cz, sizes), weights, rot_weight)
+
+
+class ScoreReport(_SumReport):
+    """Per frame (axis 0), over the included molecules that the kernel scored (``n_included`` [S] of ``n_samples``; a molecule with
+    n_pairs = -1 is excluded everywhere): ``sum_inter`` [S] and ``sum_terms`` [S, 5] float64, the weighted terms; ``sum_rotors`` and
+    ``sum_pairs`` [S] int64; ``n_no_pairs`` [S], the poses with no pair inside the cutoff; ``sum_efficiency`` [S] over the
+    ``n_efficiency`` [S] molecules with heavy atoms; ``scores`` [S, B] float64 with ``scored`` [S, B] bool, the per-molecule values that
+    the median and the best need (joined along the molecule axis by ``merged``).  With a reference ligand ``sum_ref`` [S, 2] -- per
+    pocket the reference's score and the share of molecules with a score below it, the reference's "high affinity" -- over the
+    ``n_ref`` [S] pockets that have them.  Not AutoDock Vina's number (``pocket_score``)."""
+
+    FIELDS = (('n_included', 'i64'), ('sum_inter', 'f64'), ('sum_terms', 'f64'), ('sum_rotors', 'i64'), ('sum_pairs', 'i64'),
+              ('n_no_pairs', 'i64'), ('sum_efficiency', 'f64'), ('n_efficiency', 'i64'), ('scores', 'per_mol'), ('scored', 'per_mol'),
+              ('n_samples', 'int_sum'), ('sum_ref', 'ref_f64'), ('n_ref', 'ref_i64'))
+    OPTIONAL, MISMATCH = 2, 'the reports differ in their frames or in whether they have a reference ligand'
+
+    def _merge_key(self):
+        return self.n_included.shape, self.sum_ref is None
+
+    @classmethod
+    def from_outputs(cls, raw, included, heavy, weights=SCORE_WEIGHTS, rot_weight=SCORE_ROT_WEIGHT, ref_score=None):
+        """One pocket: ``raw`` the numpy outputs of capi.score_report (terms, n_pairs, n_rot), ``included`` [S, B] bool, ``heavy``
+        [S, B] the heavy atoms; ``ref_score``: the known ligand's score or None"""
+        n_pairs = np.asarray(raw['n_pairs'], dtype=np.int64)
+        inc = np.asarray(included, dtype=bool) & (n_pairs >= 0)
+        n_rot = np.zeros_like(n_pairs) if raw.get('n_rot') is None else np.asarray(raw['n_rot'], dtype=np.int64)
+        terms, inter, score = score_energies(np.where(inc[..., None], raw['terms'], 0), np.where(inc, n_rot, 0), weights, rot_weight)
+        heavy = np.asarray(heavy, dtype=np.int64)
+        has = inc & (heavy > 0)
+        eff = np.divide(score, heavy, out=np.zeros(score.shape), where=has)
+        tot = lambda x: np.where(inc, x, 0).sum(1)
+        sum_ref = n_ref = None
+        if ref_score is not None:
+            S = inc.shape[0]
+            sum_ref, n_ref = np.zeros((S, 2)), np.zeros(S, np.int64)
+            for s in range(S):
+                if inc[s].any():
+                    sum_ref[s] = (ref_score, float((score[s][inc[s]] < ref_score).sum()) / float(inc[s].sum()))
+                    n_ref[s] = 1
+        return cls(inc.sum(1), tot(inter), np.where(inc[..., None], terms * np.asarray(weights, dtype=np.float64), 0.0).sum(1), tot(n_rot),
+                   tot(n_pairs), (inc & (n_pairs == 0)).sum(1), np.where(has, eff, 0.0).sum(1), has.sum(1), np.where(inc, score, np.nan), inc,
+                   inc.shape[1], sum_ref, n_ref)
+
+    def _scores(self, frame):
+        return self.scores[frame][self.scored[frame]]
+
+    def mean_score(self, frame=-1):
+        x = self._scores(frame)
+        return float(x.sum()) / x.size if x.size else float('nan')
+
+    def median_score(self, frame=-1):
+        x = self._scores(frame)
+        return float(np.median(x)) if x.size else float('nan')
+
+    def best_score(self, frame=-1):
+        """the lowest score of the frame"""
+        x = self._scores(frame)
+        return float(x.min()) if x.size else float('nan')
+
+    def share_negative(self, frame=-1):
+        return self._mean((self._scores(frame) < 0.0).sum(), self.n_included[frame])
+
+    def reference(self, frame=-1):
+        """{'ref_score', 'better_than_ref'}: the known ligand's score and the share of molecules that score below it (means over the
+        pockets of a merged report), or {} without a reference ligand"""
+        if self.sum_ref is None:
+            return {}
+        return {k: self._mean(self.sum_ref[frame, c], self.n_ref[frame]) for c, k in enumerate(('ref_score', 'better_than_ref'))}
+
+    def summary(self, frame=-1):
+        n = self.n_included[frame]
+        return dict(mean_score=self.mean_score(frame), median_score=self.median_score(frame), best_score=self.best_score(frame),
+                    share_negative=self.share_negative(frame), mean_inter=self._mean(self.sum_inter[frame], n),
+                    **{f'mean_{name}': self._mean(self.sum_terms[frame, t], n) for t, name in enumerate(SCORE_TERM_NAMES)},
+                    mean_rotors=self._mean(self.sum_rotors[frame], n), mean_efficiency=self._mean(self.sum_efficiency[frame], self.n_efficiency[frame]),
+                    mean_pairs=self._mean(self.sum_pairs[frame], n), no_pairs=self._mean(self.n_no_pairs[frame], n), **self.reference(frame))
+
+
+def sample_score(result, eval_step=-1, include='all', reference_ligand=None, weights=SCORE_WEIGHTS, rot_weight=SCORE_ROT_WEIGHT,
+                 cutoff=SCORE_CUTOFF, atom_enc_mode='add_aromatic', device='cuda'):
+    """The docking-style score of the samples of one pocket (``result`` a loaded ``result_{i}.pt`` dictionary, whose ``'data'`` is the
+    pocket; ``eval_step`` and the packing as ``sample_quality``): per frame the mean, the median and the best score, the share of
+    negative scores, the weighted terms, the rotatable bonds, the score per heavy atom and the poses with no pair inside the cutoff;
+    with ``reference_ligand`` ``(pos [n, 3], v [n])``, run through the same kernel, its score and the share of samples that score
+    below it (the reference's "high affinity").  ``include`` as ``sample_rings``.  A Vina-style score on this project's heuristic
+    typing, NOT AutoDock Vina's number (``pocket_score``): comparable between runs of this tool, not with published tables.  A result
+    without a pocket is refused.  Returns a ``ScoreReport``."""
+    return SamplePack(result, eval_step, atom_enc_mode, device).score(_pocket_data(result, 'score'), include, reference_ligand, weights,
+                                                                      rot_weight, cutoff)
 
 
 # ---- solvent-accessible surface (``td_sasa_report``, csrc/sasa.hip; DESIGN.md section 3, "Solvent-accessible surface")

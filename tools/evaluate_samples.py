@@ -32,7 +32,8 @@ over ``--include all`` or ``complete`` samples: the mean hydrogen bonds per mole
 or donor closer than 3.5 A, heavy atom to heavy atom, no angle) with the donated / accepted split, the mean hydrophobic contacts
 (hydrophobic atoms closer than 4.5 A), the share of molecules without a hydrogen bond, the share of polar ligand atoms in one and the
 most frequent residue kinds per type -- the ligand's donors are inferred from the valence deficit, a heuristic of this project and not
-perceived chemistry, and nothing here is a docking score -- and, with the known ligand, the recovery of its interactions per type.
+perceived chemistry, and nothing here is a docking score (``--score`` is this tool's) -- and, with the known ligand, the recovery of
+its interactions per type.
 ``--sasa [--probe 1.4] [--sasa_points 96]`` adds the solvent-accessible surface of the samples alone and in their pocket
 (quality.sample_sasa: Shrake-Rupley point counts, areas in square Angstrom), over ``--include all`` or ``complete`` samples: the mean
 free, bound and buried area of a molecule with the polar (N, O) and apolar parts, the buried share, the pocket surface a molecule
@@ -40,6 +41,13 @@ covers and its polar share, the share of poses the pocket does not cover at all 
 recovery of the protein atoms it buries.  Bondi-type radii on heavy atoms without a united-atom correction: the areas compare between
 runs of this tool, not with published tables; the stored pocket is a cut-out, so of the pocket only buried area is reported; at 96
 points one point is about 1 % of a sphere.
+``--score [--score_cutoff 8.0]`` adds a docking-style score of the samples in their pocket (quality.sample_score), over ``--include all``
+or ``complete`` samples: the mean, the median and the best score, the share of negative scores, the weighted terms (two Gaussians,
+repulsion, hydrophobic, hydrogen bond) summed over the heavy-atom pairs closer than the cutoff, the mean rotatable bonds, the score per
+heavy atom, the share of poses with no pair inside the cutoff and, with the known ligand run through the same kernel, its score and
+the share of samples that score below it (the reference's "high affinity").  It is a Vina-style score on this project's heuristic typing
+-- no hydrogens are placed, the roles come from valence deficits, there is no intramolecular term -- and NOT AutoDock Vina's number:
+it compares between runs of this tool, not with published tables.  QED and SA are still not here.
 The fingerprint is this project's own circular one over its bond graph, not RDKit's RDKFingerprint: the numbers compare between
 runs of this tool, not with published tables.  The Jensen-Shannon distances need the reference's empirical distributions: they are
 loaded from ``utils.evaluation`` when the tool runs inside the reference repository (or with it on PYTHONPATH), or from
@@ -86,15 +94,18 @@ def nan_none(d):
 def pocket_sections(args):
     """The reports against the pocket that ``args`` asks for, as (flag -- also the name of the SamplePack method and of the JSON
     section --, report class, the method's arguments after the reference ligand, extra JSON fields of the merged report)"""
-    all_three = (
+    every = (
         ('pocket', quality.PocketReport, (args.contact_cutoff, args.clash_tolerance),
          lambda r: dict(contact_cutoff=args.contact_cutoff, clash_tolerance=args.clash_tolerance, contact_profile=r.contact_profile(-1),
                         kind_hist=dict(zip(r.names, r.kind_hist[-1].sum(0).tolist())))),
         ('interactions', quality.InteractionReport, (args.hbond_cutoff, args.hydrophobic_cutoff),
          lambda r: dict(hbond_cutoff=args.hbond_cutoff, hydrophobic_cutoff=args.hydrophobic_cutoff,
                         kind_hist={t: dict(zip(r.names, r.kind_hist[-1, k].tolist())) for k, t in enumerate(quality.INTERACTION_NAMES)})),
-        ('sasa', quality.SasaReport, (args.probe, args.sasa_points), lambda r: dict(probe=args.probe, points=args.sasa_points)))
-    return [section for section in all_three if getattr(args, section[0])]
+        ('sasa', quality.SasaReport, (args.probe, args.sasa_points), lambda r: dict(probe=args.probe, points=args.sasa_points)),
+        ('score', quality.ScoreReport, (None, None, args.score_cutoff),
+         lambda r: dict(score_cutoff=args.score_cutoff, weights=dict(zip(quality.SCORE_TERM_NAMES, quality.SCORE_WEIGHTS)),
+                        rot_weight=quality.SCORE_ROT_WEIGHT)))
+    return [section for section in every if getattr(args, section[0])]
 
 
 def main(argv=None):
@@ -125,7 +136,11 @@ def main(argv=None):
                     "file's data; this project's radii, comparable between runs of this tool only)")
     ap.add_argument('--probe', type=float, default=quality.SASA_PROBE, help='--sasa: the probe radius in Angstrom')
     ap.add_argument('--sasa_points', type=int, default=quality.SASA_POINTS, help='--sasa: test points per sphere, 1 .. 256')
-    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity, --pocket, --interactions, --sasa: a known ligand, the first V2000 record of '
+    ap.add_argument('--score', action='store_true', help="also a docking-style score of the samples in their pocket (the result file's "
+                    "data): a Vina-style score on this project's heuristic typing, NOT AutoDock Vina's number -- comparable between runs "
+                    'of this tool, not with published tables')
+    ap.add_argument('--score_cutoff', type=float, default=quality.SCORE_CUTOFF, help='--score: a pair counts when it is closer than this')
+    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity, --pocket, --interactions, --sasa, --score: a known ligand, the first V2000 record of '
                     'FILE; --geometry: known ligands, every record of FILE')
     ap.add_argument('--reference_npz', type=str, default=None)
     ap.add_argument('--device', type=str, default='cuda')

@@ -2,7 +2,7 @@
 
     python tools/export_sdf.py --sample_path DIR --out DIR [--eval_step -1] [--only-complete] [--largest-fragment] [--ring-aromatic]
                                 [--unique] [--clash-free] [--pocket-clash-free] [--min-hbonds N]
-                                [--min-buried-share X]
+                                [--min-buried-share X] [--max-score X] [--sort-by-score]
 
 Reads the ``result_{i}.pt`` files a sampling driver wrote (sorted as tools/evaluate_samples.py sorts them), takes the frame
 ``--eval_step`` of every sample (default -1: the final poses), builds the bond graph on the GPU (quality.bond_graph: bonds from the
@@ -28,6 +28,10 @@ section 3, "Pocket interactions" -- a heuristic count, not a score); it combines
 ``--min-buried-share X`` writes only the samples of whose solvent-accessible surface the pocket covers at least the share X
 (quality.pocket_sasa on the file's pocket: buried / free area by Shrake-Rupley point counting with this project's radii and a 1.4 A
 probe; DESIGN.md section 3, "Solvent-accessible surface"); it combines with the three above and applies before ``--unique``.
+``--max-score X`` writes only the samples whose docking-style score is at most X (quality.pocket_score on the file's pocket: a
+Vina-style score on this project's heuristic typing -- no hydrogens, roles from valence deficits, no intramolecular term -- and NOT
+AutoDock Vina's number; DESIGN.md section 3, "Docking-style score"); it combines with the four above and applies before ``--unique``.
+``--sort-by-score`` writes the samples of a file best (lowest) score first.  With either, every record carries a ``> <score>`` data item.
 Prints one line per file and returns the counts.
 """
 from __future__ import annotations
@@ -64,6 +68,9 @@ def main(argv=None):
                     "file's data; this project's role heuristic)")
     ap.add_argument('--min-buried-share', type=float, default=None, help="only the samples with at least this share of their "
                     "solvent-accessible surface covered by the pocket (the file's data; 0 .. 1)")
+    ap.add_argument('--max-score', type=float, default=None, help="only the samples with a docking-style score of at most this (the file's "
+                    "data; a Vina-style score on this project's heuristic typing, NOT AutoDock Vina's number)")
+    ap.add_argument('--sort-by-score', action='store_true', help='the samples of a file best (lowest) docking-style score first')
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
     if args.min_buried_share is not None and not 0.0 <= args.min_buried_share <= 1.0:
@@ -107,12 +114,28 @@ def main(argv=None):
                                                 device=args.device).buried_share[0] >= args.min_buried_share
             chosen = buried_enough if chosen is None else chosen & buried_enough
             select = buried_enough.cpu().numpy() & (True if select is None else select)
+        score = good_score = None
+        if args.max_score is not None or args.sort_by_score:
+            if not isinstance(result, dict) or result.get('data') is None:
+                raise SystemExit(f'{name} carries no pocket (no data): --max-score and --sort-by-score need the files of a sampling driver')
+            score = quality.pocket_score(*quality.pocket_of(result['data']), pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode,
+                                         device=args.device).score[0]
+        if args.max_score is not None:
+            good_score = torch.from_numpy(score <= args.max_score).to(pos.device)
+            chosen = good_score if chosen is None else chosen & good_score
+            select = good_score.cpu().numpy() & (True if select is None else select)
         if args.unique:
             fp = quality.fingerprints(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, device=args.device)
             first = fp.similarity(include=None if chosen is None else chosen[None])['first_equal'][0].cpu().numpy()
             select = (first == np.arange(len(sizes))) & (True if select is None else select)
         mols = molfile.molecules_from_graph(g, pos, v, args.atom_enc_mode, 0, args.only_complete, args.largest_fragment,
                                             categories=g.ring_category if args.ring_aromatic else None, select=select)
+        if score is not None:
+            of = lambda m: float(score[int(m['name'].rsplit('_', 1)[1])])          # molecules_from_graph names them sample_{g}
+            for m in mols:
+                m['properties']['score'] = f'{of(m):.4f}'
+            if args.sort_by_score:
+                mols.sort(key=of)
         stem = os.path.basename(name)[:-3]
         path = os.path.join(args.out, stem + '.sdf')
         n = molfile.write_sdf(path, mols)
@@ -127,6 +150,8 @@ def main(argv=None):
             out[stem]['min_hbonds'] = int(enough_hbonds.sum())
         if buried_enough is not None:
             out[stem]['min_buried_share'] = int(buried_enough.sum())
+        if good_score is not None:
+            out[stem]['max_score'] = int(good_score.sum())
     return out
 
 

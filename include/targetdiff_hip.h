@@ -568,6 +568,49 @@ int td_score_report(const float *d_pos, const int64_t *d_v, const int32_t *d_lig
                     int64_t n_bonds, const uint16_t *d_bond_ring, int32_t *d_protein_role_out, int64_t *d_terms, int32_t *d_n_pairs,
                     int32_t *d_n_rot, void *stream);
 
+/* ---- rigid-body relaxation of ligand frames under the docking-style score ("Pose relaxation"): per (frame,
+ *      molecule) the pose after a local optimisation of inter = weights . terms, the five term sums of td_score_report, over rigid
+ *      motions of the molecule.  It is a local optimisation under this project's heuristic score, NOT AutoDock Vina's `minimize`, and
+ *      it is rigid-body only: three translations and three rotations, no torsions.  No global search, no intramolecular term, no
+ *      hydrogens.  Inputs as td_score_report takes them (the rotor inputs too: d_n_rot is the INPUT pose's; the caller forms
+ *      score = inter / (1 + w_rot n_rot)), plus weights: HOST float64 [5], finite; max_steps >= 0 accepted steps (64 by convention),
+ *      max_evals >= 1 evaluations, max_shift finite and > 0 (3.0 by convention), else TD_EINVAL.
+ *      Typing: the ligand roles are those of the INPUT pose and are held fixed.  Pairs, r, d and the term values as td_score_report,
+ *      with the same rounding of each value to units of 2^-24.
+ *      State: c0, the centroid of the scored atoms (class in [0, K), not H) in float64, summed in index order; x0 = x - c0 for ALL
+ *      atoms of the molecule (hydrogens and atoms outside the table ride along); a unit quaternion q = (w, x, y, z) and a shift t, the
+ *      centre being c = c0 + t.  A pose is fp32(R(q) x0 + c): row k as ((R_k0 x0 + R_k1 y0) + R_k2 z0) + c_k with R_00 =
+ *      1 - 2 (yy + zz), R_01 = 2 (xy - wz), R_02 = 2 (xz + wy), R_10 = 2 (xy + wz), R_11 = 1 - 2 (xx + zz), R_12 = 2 (yz - wx),
+ *      R_20 = 2 (xz - wy), R_21 = 2 (yz + wx), R_22 = 1 - 2 (xx + yy), every product and sum rounded on its own.  Energies and
+ *      gradients are always taken at the fp32-rounded pose: the final terms are exactly the score of the coordinates written.
+ *      Gradient: per counted pair f = dE/dd = (((w0 (-4 t e1) + w1 (-u e2)) + w2 [d < 0] 2 d) + w3 [0.5 <= d < 1.5] (-1)) +
+ *      w4 [-0.7 <= d < 0] (-1 / 0.7), with t = 2 d, e1 = exp(-t t), u = (d - 3) / 2, e2 = exp(-u u) and the role conditions of terms
+ *      3 and 4: zero on the flat pieces, at a breakpoint the piece that the term value takes, no derivative of the cutoff.
+ *      g = f (x_l - x_p) / r; the six components are sum g and sum (x_l - c) x g; each component of each pair is rounded to units of
+ *      2^-24 and added as int64, so the sums are exact whatever the order of arrival.  There is no floating-point atomic.
+ *      Step: BFGS on the 6-vector with an Armijo backtracking line search (f1 - f0 < 1e-4 alpha g.p; alpha = 1, halved, at most 10
+ *      trials); H0 is the identity on translation and 1 / mean |x0|^2 (over the scored atoms) on rotation; H is reset to H0 when -H g
+ *      is no descent direction and updated only when s.y > 0.  The rotation increment of omega is the normalised quaternion
+ *      (1, omega / 2), composed on the left and renormalised.  A trial with |t| > max_shift fails without an evaluation.  The kernel
+ *      stops when a line search fails, after max_steps accepted steps or after max_evals evaluations.
+ *      Outputs: d_pos_out [S,N_l,3] fp32 (may not be d_pos; an atom of no molecule and a molecule that took no step keep the input's
+ *      bytes); d_terms_in / d_terms_out [S,B,5] int64, the term sums at the input and at the written pose; d_n_pairs_out [S,B] int32
+ *      at the written pose; d_n_steps, d_n_evals [S,B] int32; d_status [S,B] int32: bit 1 a line search ended (converged), 2 out of
+ *      steps or evaluations, 4 some trial hit max_shift; d_transform [S,B,7] float64: q, then t = c - c0; d_grad_in [S,B,6] int64:
+ *      the gradient at the input pose in units of 2^-24.  d_protein_role_out and d_n_rot as td_score_report.
+ *      A molecule of more than 512 atoms, or one whose offsets leave [0, N_l]: positions copied through, INT64_MIN in both terms,
+ *      -1 in d_n_pairs_out and d_status (and d_n_rot), zero steps.  No scored atom, or N_p = 0: positions copied through, zero steps.
+ *      max_steps = 0: one evaluation, d_terms_out == d_terms_in.  Two runs give identical bytes.  (An addition: TD_ABI_VERSION
+ *      stays 5.) */
+int td_score_minimize(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                      const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+                      const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p,
+                      int32_t n_kinds, double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr,
+                      int64_t n_bonds, const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals,
+                      double max_shift, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in,
+                      int64_t *d_terms_out, int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status,
+                      double *d_transform, int64_t *d_grad_in, void *stream);
+
 /* ---- solvent-accessible surface of ligand frames by Shrake-Rupley point counting ("Solvent-accessible
  *      surface"): every output is a count of sphere points; areas are formed by the caller.  One pocket and one pack per call; the
  *      pack, the class table and d_include as td_pocket_report takes them.  d_protein_pos [N_p,3] fp32; d_protein_elem [N_p] int32, an

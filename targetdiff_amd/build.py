@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 OBJDIR = os.path.join(HERE, 'build')
 LIB = os.path.join(LIBDIR, 'libtargetdiff_hip.so')
-SOURCES = ['entry.cpp', 'pack.cpp', 'plan.cpp', 'forward.cpp', 'session.cpp', 'graph.hip', 'node.hip', 'gate.hip', 'edge16.hip', 'misc.hip', 'guidance.hip', 'quality.hip', 'quality_api.cpp', 'bonds.hip', 'rings.hip', 'fingerprint.hip', 'geometry.hip', 'pocket.hip', 'interactions.hip', 'score.hip', 'sasa.hip', 'bonds_api.cpp', 'likelihood.hip', 'loss.hip', 'egnn.hip', 'prop.hip', 'prop_bwd.hip', 'prop_api.cpp']
+SOURCES = ['entry.cpp', 'pack.cpp', 'plan.cpp', 'forward.cpp', 'session.cpp', 'graph.hip', 'node.hip', 'gate.hip', 'edge16.hip', 'misc.hip', 'guidance.hip', 'quality.hip', 'quality_api.cpp', 'bonds.hip', 'rings.hip', 'fingerprint.hip', 'geometry.hip', 'pocket.hip', 'interactions.hip', 'score.hip', 'relax.hip', 'sasa.hip', 'bonds_api.cpp', 'likelihood.hip', 'loss.hip', 'egnn.hip', 'prop.hip', 'prop_bwd.hip', 'prop_api.cpp']
 ARCH = 'gfx950'
 # NB: the kNN distance uses __fmul_rn/__fadd_rn explicitly (td_dist2), so the default fp contraction is safe.
 # -fvisibility=hidden: only the extern "C" entry points of include/targetdiff_hip.h (visibility push(default)) are exported

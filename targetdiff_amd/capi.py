@@ -108,6 +108,9 @@ SIGNATURES = {
                                         _P, _P, _P, _P, _P]),
     'td_score_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), _P, _P, _P, _P, c_int64,
                                   c_int32, ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double), _P, c_int64, _P, _P, _P, _P, _P, _P]),
+    'td_score_minimize': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), _P, _P, _P, _P, c_int64,
+                                    c_int32, ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double), _P, c_int64, _P, POINTER(ctypes.c_double),
+                                    c_int32, c_int32, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_sasa_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, _P, c_int64, POINTER(ctypes.c_double),
                                  POINTER(ctypes.c_double), _P, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -1383,6 +1386,69 @@ def score_report(pos, v, ligand_ptr, class_z, class_aromatic, protein_pos, prote
                                    rs.ctypes.data_as(POINTER(ctypes.c_double)), _ptr(bond_ptr, torch.int64, 'bond_ptr'), nb,
                                    _ptr(bond_ring, torch.int16, 'bond_ring') if nb else None, _ptr(out['protein_role']), _ptr(out['terms']),
                                    _ptr(out['n_pairs']), _ptr(out['n_rot']), _stream(dev)), 'td_score_report')
+    return out
+
+
+RELAX_MAX_STEPS, RELAX_MAX_SHIFT, RELAX_LIST_CAPACITY = 64, 3.0, 4096       # the conventions; TD_RELAX_LIST_CAPACITY (csrc/td_internal.h)
+RELAX_KEYS = ('protein_role', 'n_rot', 'pos', 'terms_in', 'terms', 'n_pairs', 'n_steps', 'n_evals', 'status', 'transform', 'grad_in')
+RELAX_CONVERGED, RELAX_OUT_OF_BUDGET, RELAX_AT_CAP = 1, 2, 4                  # the bits of status
+
+
+def _relax_inputs(weights, max_steps, max_evals, max_shift):
+    """The optimiser's side of a score_minimize call.  Returns (the weights as float64 numpy [5], max_steps, max_evals, max_shift);
+    ``max_evals`` None: 4 max_steps + 1, the initial evaluation and four per step."""
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape != (SCORE_TERMS,) or not np.isfinite(w).all():
+        raise ValueError(f'the weights are {SCORE_TERMS} finite numbers: {", ".join(SCORE_TERM_NAMES)}')
+    if int(max_steps) != max_steps or int(max_steps) < 0 or int(max_steps) > 0x3fffffff:
+        raise ValueError(f'max_steps must be an integer >= 0 (got {max_steps})')
+    if max_evals is None:
+        max_evals = 4 * int(max_steps) + 1
+    if int(max_evals) != max_evals or int(max_evals) < 1 or int(max_evals) > 0x7fffffff:
+        raise ValueError(f'max_evals must be an integer >= 1 (got {max_evals})')
+    if not (np.isfinite(float(max_shift)) and float(max_shift) > 0.0):
+        raise ValueError(f'max_shift must be finite and > 0 (got {max_shift})')
+    return np.ascontiguousarray(w), int(max_steps), int(max_evals), float(max_shift)
+
+
+def score_minimize(pos, v, ligand_ptr, class_z, class_aromatic, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, rsum, weights,
+                   cutoff=8.0, hetero_cutoff=1.75, bond_ptr=None, bond_ring=None, max_steps=RELAX_MAX_STEPS, max_evals=None,
+                   max_shift=RELAX_MAX_SHIFT, check=True, _list_capacity=None):
+    """The rigid-body relaxation of S frames of B molecules in one pocket under ``inter = weights . terms`` of score_report
+    (td_score_minimize, include/targetdiff_hip.h): one persistent workgroup per molecule runs BFGS with a backtracking line search on
+    three translations and three rotations.  It is a local optimisation under this project's heuristic score, not AutoDock Vina's
+    ``minimize``, and it is rigid-body only: three translations and three rotations, no torsions.  The arguments up to ``bond_ring``
+    as score_report's (validated alike); ``weights`` five finite numbers; ``max_steps`` accepted steps, ``max_evals`` evaluations (None:
+    4 max_steps + 1), ``max_shift`` the cap on the shift of the centre in Angstrom.
+    Returns a dict of device tensors: protein_role [N_p] int32 and n_rot [S, B] int32 (of the input pose; None without the bond
+    arguments) as score_report's, pos [S, N_l, 3] fp32 the relaxed poses, terms_in / terms [S, B, 5] int64 in units of 2^-24 at the
+    input and at the relaxed pose, n_pairs [S, B] int32 at the relaxed pose, n_steps, n_evals, status [S, B] int32 (bits
+    ``RELAX_CONVERGED``, ``RELAX_OUT_OF_BUDGET``, ``RELAX_AT_CAP``), transform [S, B, 7] float64 (the unit quaternion, then the shift of
+    the centre) and grad_in [S, B, 6] int64, the gradient at the input pose in units of 2^-24.  An oversize molecule, refused under
+    ``check``, keeps its positions and gets -1 / INT64_MIN."""
+    S, Nl, B, cz, aro, _ = _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, None, (), check)
+    Np, rs, nb = _score_inputs(pos, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, rsum, cutoff, hetero_cutoff, bond_ptr,
+                               bond_ring, S, B, check)
+    w, max_steps, max_evals, max_shift = _relax_inputs(weights, max_steps, max_evals, max_shift)
+    lib = load_library()
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
+    dev = pos.device
+    i32, _, i64 = _allocators(dev)
+    out = dict(protein_role=i32(Np), n_rot=i32(S, B) if bond_ptr is not None else None, pos=torch.empty_like(pos),
+               terms_in=i64(S, B, SCORE_TERMS), terms=i64(S, B, SCORE_TERMS), n_pairs=i32(S, B), n_steps=i32(S, B), n_evals=i32(S, B),
+               status=i32(S, B), transform=torch.empty(S, B, 7, dtype=torch.float64, device=dev), grad_in=i64(S, B, 6))
+    args = (*pack, _aromatic_arg(aro), _ptr(protein_pos, torch.float32, 'protein_pos'), _ptr(protein_elem, torch.int32, 'protein_elem'),
+            _ptr(protein_kind, torch.int32, 'protein_kind'), _ptr(protein_role, torch.int32, 'protein_role'), Np, int(n_kinds), float(cutoff),
+            float(hetero_cutoff), rs.ctypes.data_as(POINTER(ctypes.c_double)), _ptr(bond_ptr, torch.int64, 'bond_ptr'), nb,
+            _ptr(bond_ring, torch.int16, 'bond_ring') if nb else None, w.ctypes.data_as(POINTER(ctypes.c_double)), max_steps, max_evals,
+            max_shift, *(_ptr(out[k]) for k in RELAX_KEYS), _stream(dev))
+    with _on(dev):
+        if _list_capacity is None:
+            _check(lib.td_score_minimize(*args), 'td_score_minimize')
+        else:                                                                    # the tests' door to the walk in global memory
+            fn = lib.td_internal_score_minimize_capacity
+            fn.restype, fn.argtypes = c_int32, SIGNATURES['td_score_minimize'][1] + [c_int32]
+            _check(fn(*args, int(_list_capacity)), 'td_score_minimize')
     return out
 
 

@@ -1,7 +1,7 @@
 // C ABI of libtargetdiff_hip.so: the bond graph of ligand frames, its rings, its fingerprints, its local geometry and the contacts with
 // the pocket, the typed interactions with it, the docking-style score and the surface it buries (td_bond_graph, td_bond_list,
 // td_ring_report, td_fingerprint, td_fingerprint_similarity, td_geometry_report, td_pocket_report, td_interaction_report,
-// td_score_report, td_sasa_report).  See
+// td_score_report, td_score_minimize, td_sasa_report).  See
 // include/targetdiff_hip.h for the contract.
 #include <cmath>
 #include <initializer_list>
@@ -314,14 +314,14 @@ extern "C" int td_interaction_report(const float *d_pos, const int64_t *d_v, con
     return td_launch_interaction_report(g, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int td_score_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
-                               const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
-                               const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p,
-                               int32_t n_kinds, double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr,
-                               int64_t n_bonds, const uint16_t *d_bond_ring, int32_t *d_protein_role_out, int64_t *d_terms,
-                               int32_t *d_n_pairs, int32_t *d_n_rot, void *stream) {
-    const char *who = "td_score_report";
-    TdScoreArgs g;
+namespace {
+// What td_score_report and td_score_minimize share: the pack, the pocket, the cutoffs, the radius sums and the rotor inputs checked and
+// filled into g, and the protein roles resolved on the stream.  The outputs of each (beyond d_protein_role_out and d_n_rot) are its own.
+int score_side(const char *who, TdScoreArgs &g, const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l,
+               int64_t B, const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+               const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds,
+               double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds,
+               const uint16_t *d_bond_ring, int32_t *d_protein_role_out, int32_t *d_n_rot, hipStream_t stream) {
     if (const int rc = bond_pack(who, g.b, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, n_bonds)) return rc;
     if (N_p < 0 || N_p > 0x7fffffff / TD_BOND_MAX_ATOMS) {                      // a molecule's pairs are counted in an int32
         td_set_error("%s: bad argument (N_p = %lld; 512 N_p must fit 31 bits)", who, (long long)N_p);
@@ -351,7 +351,7 @@ extern "C" int td_score_report(const float *d_pos, const int64_t *d_v, const int
         return TD_EINVAL;
     }
     if ((N_p > 0 && (!d_protein_pos || !d_protein_elem || !d_protein_kind || !d_protein_role || !d_protein_role_out)) ||
-        (S > 0 && B > 0 && (!d_terms || !d_n_pairs || (rotors && !d_n_rot)))) {
+        (S > 0 && B > 0 && rotors && !d_n_rot)) {
         td_set_error("%s: null pointer", who);
         return TD_EINVAL;
     }
@@ -360,13 +360,104 @@ extern "C" int td_score_report(const float *d_pos, const int64_t *d_v, const int
     p.ppos = d_protein_pos; p.pelem = d_protein_elem; p.pkind = d_protein_kind;
     p.Np = (int)N_p; p.W = (int)((N_p + 63) / 64); p.n_kinds = n_kinds;
     roles.prole = d_protein_role; roles.hetero_cutoff = hetero_cutoff; roles.role_out = d_protein_role_out;
-    if (const int rc = td_launch_protein_roles(roles, static_cast<hipStream_t>(stream))) return rc;
+    if (const int rc = td_launch_protein_roles(roles, stream)) return rc;
     g.p = p;
     g.role = d_protein_role_out;
     g.cutoff = cutoff;
     g.b.bond_ptr = const_cast<int64_t *>(d_bond_ptr); g.b.bond_ring = const_cast<uint16_t *>(d_bond_ring);
-    g.terms = reinterpret_cast<long long *>(d_terms); g.n_pairs = d_n_pairs; g.n_rot = d_n_rot;
+    g.n_rot = d_n_rot;
+    return TD_OK;
+}
+}  // namespace
+
+extern "C" int td_score_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                               const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+                               const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p,
+                               int32_t n_kinds, double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr,
+                               int64_t n_bonds, const uint16_t *d_bond_ring, int32_t *d_protein_role_out, int64_t *d_terms,
+                               int32_t *d_n_pairs, int32_t *d_n_rot, void *stream) {
+    const char *who = "td_score_report";
+    if (S > 0 && B > 0 && (!d_terms || !d_n_pairs)) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
+    TdScoreArgs g;
+    if (const int rc = score_side(who, g, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos,
+                                  d_protein_elem, d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr,
+                                  n_bonds, d_bond_ring, d_protein_role_out, d_n_rot, static_cast<hipStream_t>(stream)))
+        return rc;
+    g.terms = reinterpret_cast<long long *>(d_terms); g.n_pairs = d_n_pairs;
     return td_launch_score_report(g, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+int score_minimize(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                   const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+                   const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds,
+                   double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds,
+                   const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals, double max_shift,
+                   int32_t list_capacity, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in,
+                   int64_t *d_terms_out, int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status,
+                   double *d_transform, int64_t *d_grad_in, void *stream) {
+    const char *who = "td_score_minimize";
+    if (max_steps < 0 || max_evals < 1 || list_capacity < 0) {
+        td_set_error("%s: bad argument (max_steps = %d must be >= 0, max_evals = %d must be >= 1)", who, (int)max_steps, (int)max_evals);
+        return TD_EINVAL;
+    }
+    if (!std::isfinite(max_shift) || !(max_shift > 0.0)) {
+        td_set_error("%s: max_shift must be finite and > 0", who);
+        return TD_EINVAL;
+    }
+    if (!weights) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
+    TdRelaxArgs g;
+    for (int k = 0; k < TD_SCORE_TERMS; ++k) {
+        if (!std::isfinite(weights[k])) { td_set_error("%s: the weights must be finite (weight %d)", who, k); return TD_EINVAL; }
+        g.w[k] = weights[k];
+    }
+    if ((S > 0 && N_l > 0 && (!d_pos_out || d_pos_out == d_pos)) ||
+        (S > 0 && B > 0 && (!d_terms_in || !d_terms_out || !d_n_pairs_out || !d_n_steps || !d_n_evals || !d_status || !d_transform || !d_grad_in))) {
+        td_set_error("%s: null pointer (d_pos_out may not be d_pos)", who);
+        return TD_EINVAL;
+    }
+    if (const int rc = score_side(who, g.sc, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos,
+                                  d_protein_elem, d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr,
+                                  n_bonds, d_bond_ring, d_protein_role_out, d_n_rot, static_cast<hipStream_t>(stream)))
+        return rc;
+    g.max_steps = max_steps; g.max_evals = max_evals; g.max_shift = max_shift; g.list_capacity = list_capacity;
+    g.pos_out = d_pos_out;
+    g.terms_in = reinterpret_cast<long long *>(d_terms_in); g.terms_out = reinterpret_cast<long long *>(d_terms_out);
+    g.n_pairs_out = d_n_pairs_out; g.n_steps = d_n_steps; g.n_evals = d_n_evals; g.status = d_status;
+    g.transform = d_transform; g.grad_in = reinterpret_cast<long long *>(d_grad_in);
+    return td_launch_score_minimize(g, static_cast<hipStream_t>(stream));
+}
+}  // namespace
+
+extern "C" int td_score_minimize(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                                 const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+                                 const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p,
+                                 int32_t n_kinds, double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr,
+                                 int64_t n_bonds, const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals,
+                                 double max_shift, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in,
+                                 int64_t *d_terms_out, int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status,
+                                 double *d_transform, int64_t *d_grad_in, void *stream) {
+    return score_minimize(d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos, d_protein_elem,
+                          d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring, weights,
+                          max_steps, max_evals, max_shift, TD_RELAX_LIST_CAPACITY, d_protein_role_out, d_n_rot, d_pos_out, d_terms_in,
+                          d_terms_out, d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform, d_grad_in, stream);
+}
+
+// td_score_minimize with the capacity of the LDS list as an argument (0 .. TD_RELAX_LIST_CAPACITY; 0: every molecule walks the pocket in
+// global memory): for the tests that show the two walks give the same bytes.  Not part of the public ABI (no declaration in
+// include/targetdiff_hip.h).
+extern "C" __attribute__((visibility("default"))) int td_internal_score_minimize_capacity(
+    const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B, const int32_t *class_atomic_number,
+    int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos, const int32_t *d_protein_elem, const int32_t *d_protein_kind,
+    const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds, double cutoff, double hetero_cutoff, const double *rsum,
+    const int64_t *d_bond_ptr, int64_t n_bonds, const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals,
+    double max_shift, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in, int64_t *d_terms_out,
+    int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status, double *d_transform, int64_t *d_grad_in, void *stream,
+    int32_t list_capacity) {
+    return score_minimize(d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos, d_protein_elem,
+                          d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring, weights,
+                          max_steps, max_evals, max_shift, list_capacity, d_protein_role_out, d_n_rot, d_pos_out, d_terms_in, d_terms_out,
+                          d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform, d_grad_in, stream);
 }
 
 extern "C" int td_sasa_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,

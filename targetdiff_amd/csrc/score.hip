@@ -15,14 +15,9 @@
 //                   whose index in td_bond_list's order is the scan of the upward-bond counts plus the rank of j (geometry.hip).
 // Every loop is bounded by the molecule's size or the pocket's.  All outputs are integers: nothing depends on the grid or on the order
 // of arrival.  No floating-point atomic.  The answer to an oversize molecule (-1, INT64_MIN) is that of bonds.hip.
-#include "td_pocket_walk.h"
+#include "td_score_terms.h"
 
 #include <climits>
-
-constexpr int SC_T = PW_T, SC_TERMS = TD_SCORE_TERMS, SC_PE = TD_POCKET_ELEMENTS;
-
-// a term value in units of 2^-24: ldexp is exact, llrint rounds to nearest, ties to even
-__device__ __forceinline__ long long sc_fixed(double value) { return llrint(ldexp(value, TD_SCORE_FRAC_BITS)); }
 
 __global__ __launch_bounds__(SC_T) void score_kernel(TdScoreArgs g) {
     const TdBondArgs &a = g.b;
@@ -78,15 +73,7 @@ __global__ __launch_bounds__(SC_T) void score_kernel(TdScoreArgs g) {
             if (!(rr < g.cutoff)) continue;
             const double d = td_add_rn64(rr, -s_rsum[__float_as_int(q.w) * SC_PE + pe]);
             ++pairs;
-            const double t = td_mul_rn64(d, 2.0);
-            acc[0] += sc_fixed(exp(-td_mul_rn64(t, t)));
-            const double u = td_add_rn64(d, -3.0) / 2.0;
-            acc[1] += sc_fixed(exp(-td_mul_rn64(u, u)));
-            if (d < 0.0) acc[2] += sc_fixed(td_mul_rn64(d, d));
-            if ((lr & TD_ROLE_HYDROPHOBIC) && (pr & TD_ROLE_HYDROPHOBIC) && d < 1.5)
-                acc[3] += sc_fixed(d < 0.5 ? 1.0 : td_add_rn64(1.5, -d));
-            const bool hb = ((lr & TD_ROLE_DONOR) && (pr & TD_ROLE_ACCEPTOR)) || ((lr & TD_ROLE_ACCEPTOR) && (pr & TD_ROLE_DONOR));
-            if (hb && d < 0.0) acc[4] += sc_fixed(d < -0.7 ? 1.0 : (-d) / 0.7);
+            sc_pair_terms(d, lr, pr, acc);                                      // td_score_terms.h: the copy relax.hip minimises
         }
     }
 #pragma unroll
@@ -177,6 +164,12 @@ int td_launch_score_report(const TdScoreArgs &args, hipStream_t s) {
     if (M == 0) return TD_OK;
     score_kernel<<<dim3((unsigned)M), dim3(SC_T), 0, s>>>(g);
     TD_CHECK_HIP(hipGetLastError());
-    if (g.b.bond_ptr) return bg_launch_pair(rotor_kernel<BG_SMALL>, rotor_kernel<BG_MAX>, g, M, s);
-    return TD_OK;
+    return td_launch_rotors(g, s);
+}
+
+// the rotor kernel alone, where the pack comes with its bond list (relax.hip counts the rotors of the input pose with it)
+int td_launch_rotors(const TdScoreArgs &g, hipStream_t s) {
+    const int64_t M = (int64_t)g.b.S * g.b.B;
+    if (M == 0 || !g.b.bond_ptr) return TD_OK;
+    return bg_launch_pair(rotor_kernel<BG_SMALL>, rotor_kernel<BG_MAX>, g, M, s);
 }

@@ -574,6 +574,27 @@ struct TdScoreArgs {
     int32_t *n_rot = nullptr;                // [S,B], written when bond_ptr
 };
 int td_launch_score_report(const TdScoreArgs &a, hipStream_t s);
+int td_launch_rotors(const TdScoreArgs &a, hipStream_t s);      // the rotor kernel alone; nothing without bond_ptr
+// relax.hip (td_score_minimize, DESIGN.md section 3, "Pose relaxation"): `sc` as td_launch_score_report takes it, of which terms and
+// n_pairs are not used (n_rot is written by the rotor kernel when bond_ptr).  list_capacity: the entries of the LDS list of protein
+// atoms, 0 .. TD_RELAX_LIST_CAPACITY; a molecule with more candidates walks the pocket in global memory, with the same integers.  The
+// launcher copies the positions to pos_out on the stream first; the kernel writes the molecules that moved.
+constexpr int TD_RELAX_LIST_CAPACITY = 4096, TD_RELAX_TRIALS = 10, TD_RELAX_DOF = 6;
+constexpr double TD_RELAX_ARMIJO = 1e-4;
+struct TdRelaxArgs {
+    TdScoreArgs sc;
+    double w[TD_SCORE_TERMS] = {};
+    int max_steps = 0, max_evals = 0, list_capacity = TD_RELAX_LIST_CAPACITY;
+    double max_shift = 0.0;
+    float *pos_out = nullptr;                // [S,N_l,3]
+    long long *terms_in = nullptr, *terms_out = nullptr;                         // [S,B,TD_SCORE_TERMS]
+    int32_t *n_pairs_out = nullptr, *n_steps = nullptr, *n_evals = nullptr, *status = nullptr;   // [S,B]
+    double *transform = nullptr;             // [S,B,7]: q (w, x, y, z), c - c0
+    long long *grad_in = nullptr;            // [S,B,TD_RELAX_DOF]
+};
+int td_launch_score_minimize(const TdRelaxArgs &a, hipStream_t s);
+// bonds_api.cpp also exports td_internal_score_minimize_capacity: td_score_minimize with list_capacity as a last argument, for the tests
+// that hold the two walks to identical bytes.  It is not declared in include/targetdiff_hip.h and is no part of the public ABI.
 // sasa.hip (td_sasa_report, DESIGN.md section 3, "Solvent-accessible surface"): the pack and the include bytes in `b` (none of b's
 // outputs is used); the pocket as TdProteinSide holds it, without kinds, in fields of its own (its kernels keep the argument block they
 // were measured with: EXPERIMENTS.md "Pocket reports").  lig_R over H C N O F P S Cl and prot_R over H C N O S Se: the

@@ -378,7 +378,7 @@ class SamplePack:
         self.sizes, self.S = sizes, S
         self.class_z, self.aromatic = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
         self._checked = self._sized = False
-        self._stable = self._graph = self._bond_ring = self._ref = None
+        self._stable = self._graph = self._bond_ring = self._ref = self.relaxed_pos = None
 
     @property
     def _args(self):
@@ -558,6 +558,32 @@ class SamplePack:
         raw = {k: r[k].cpu().numpy() for k in ('terms', 'n_pairs', 'n_rot')}
         heavy = _heavy_atoms(self.v.cpu().numpy(), self.class_z, self.sizes)
         return ScoreReport.from_outputs(raw, self._included(mask), heavy, weights, rot_weight, ref_score)
+
+    def relax(self, data, include='all', reference_ligand=None, weights=None, max_steps=None, max_shift=None, cutoff=None, rot_weight=None):
+        """``sample_relax`` of the pack; ``data`` as ``pocket``.  The rotatable bonds are those of the input poses, counted on the pack's
+        bond graph and ring sizes; the relaxed coordinates of the last call stay in ``relaxed_pos`` [S, N_l, 3] on the device."""
+        weights = SCORE_WEIGHTS if weights is None else weights
+        rot_weight = SCORE_ROT_WEIGHT if rot_weight is None else rot_weight
+        side = self._side(data)
+        kind, names = side.kinds()
+        mask = self.mask(include)
+        pocket = (side.pos, side.elem, kind, side.roles(), len(names), score_radius_sums(), weights, SCORE_CUTOFF if cutoff is None else cutoff,
+                  DEFAULT_HETERO_CUTOFF)
+        budget = dict(max_steps=RELAX_MAX_STEPS if max_steps is None else max_steps, max_shift=RELAX_MAX_SHIFT if max_shift is None else max_shift)
+        keys = ('pos', 'terms_in', 'terms', 'n_rot', 'n_steps', 'n_evals', 'status', 'transform')
+        ref_scores = None
+        if reference_ligand is not None:
+            ref = self._reference(reference_ligand)
+            bond_ptr = capi.bond_graph(*ref, self.aromatic, (), None, False, True)['bond_ptr']
+            ring = capi.ring_report(*ref, self.aromatic, None, bond_ptr, False)['bond_ring']
+            q = capi.score_minimize(*ref, self.aromatic, *pocket, bond_ptr, ring, **budget)
+            if int(q['status'][0, 0]) >= 0:
+                _, before, after, _ = _relax_scores({k: q[k].cpu().numpy() for k in keys}, weights, rot_weight)
+                ref_scores = (float(before[0, 0]), float(after[0, 0]))
+        r = capi.score_minimize(*self._args, self.aromatic, *pocket, self.graph['bond_ptr'], self.bond_ring, **budget, check=self._check())
+        self.relaxed_pos = r['pos']
+        raw = {k: r[k].cpu().numpy() for k in keys}
+        return RelaxReport.from_outputs(raw, self._included(mask), self.pos.cpu().numpy(), self.sizes, weights, rot_weight, ref_scores)
 
     def sasa(self, data, include='all', reference_ligand=None, probe=1.4, points=96):
         """``sample_sasa`` of the pack; ``data`` as ``pocket``"""
@@ -1832,6 +1858,178 @@ def sample_score(result, eval_step=-1, include='all', reference_ligand=None, wei
     without a pocket is refused.  Returns a ``ScoreReport``."""
     return SamplePack(result, eval_step, atom_enc_mode, device).score(_pocket_data(result, 'score'), include, reference_ligand, weights,
                                                                       rot_weight, cutoff)
+
+
+# ---- pose relaxation (``td_score_minimize``, csrc/relax.hip; DESIGN.md section 3, "Pose relaxation")
+# The pose of every molecule after a local optimisation of ``inter`` over rigid motions, by one persistent workgroup per molecule: the
+# reference's ``vina_score`` / ``vina_min`` pair on this project's typing.  It is a local optimisation under this project's heuristic
+# score, not AutoDock Vina's ``minimize``, and it is rigid-body only: three translations and three rotations, no torsions.  No global
+# search (``vina_dock``), no intramolecular term, no hydrogens.
+RELAX_MAX_STEPS, RELAX_MAX_SHIFT = capi.RELAX_MAX_STEPS, capi.RELAX_MAX_SHIFT
+
+
+def _moved(pos_in, pos_out, sizes):
+    """[S, B] float64: per molecule the RMSD between two sets of coordinates [S, N_l, 3] (numpy), 0 for an empty molecule"""
+    d2 = ((np.asarray(pos_out, dtype=np.float64) - np.asarray(pos_in, dtype=np.float64)) ** 2).sum(-1)
+    ptr = np.cumsum([0] + [int(n) for n in sizes])
+    run = np.concatenate([np.zeros((d2.shape[0], 1)), np.cumsum(d2, axis=1)], axis=1)
+    n = np.asarray(sizes, dtype=np.float64)[None, :]
+    return np.sqrt(np.divide(run[:, ptr[1:]] - run[:, ptr[:-1]], n, out=np.zeros((d2.shape[0], len(sizes))), where=n > 0))
+
+
+def _relax_scores(raw, weights, rot_weight):
+    """(bad [S, B], score before, score after, the shift of the centre) of the numpy outputs of capi.score_minimize; the rotatable
+    bonds are the input pose's for both scores"""
+    bad = np.asarray(raw['status']) < 0
+    n_rot = None if raw.get('n_rot') is None else np.where(bad, 0, raw['n_rot'])
+    before = score_energies(np.where(bad[..., None], 0, raw['terms_in']), n_rot, weights, rot_weight)[2]
+    after = score_energies(np.where(bad[..., None], 0, raw['terms']), n_rot, weights, rot_weight)[2]
+    return bad, before, after, np.sqrt((np.asarray(raw['transform'], dtype=np.float64)[..., 4:] ** 2).sum(-1))
+
+
+class Relaxed:
+    """The rigid-body relaxation of S frames of B molecules in one pocket (``pocket_relax``).  ``pos`` [S, N_l, 3] fp32 on the device,
+    the relaxed poses; numpy, frame axis first: ``raw_terms_in`` / ``raw_terms`` [S, B, 5] int64 (the kernel's integers at the input and
+    at the relaxed pose), ``n_pairs``, ``n_steps``, ``n_evals``, ``status`` [S, B] int32 (bits ``capi.RELAX_CONVERGED``,
+    ``RELAX_OUT_OF_BUDGET``, ``RELAX_AT_CAP``), ``n_rot`` [S, B] int32 of the input pose or None, ``transform`` [S, B, 7] float64 (unit
+    quaternion, shift of the centre), ``grad_in`` [S, B, 6] int64, and ``score_in`` / ``score`` [S, B] float64 = inter / (1 + rot_weight
+    n_rot) before and after, ``rmsd`` [S, B] the RMSD moved over all atoms and ``shift`` [S, B] the shift of the centre.  A molecule the
+    kernel refused (status -1) has NaN scores.  A local optimisation under this
+    project's heuristic score, not AutoDock Vina's ``minimize``; rigid-body only: three translations and three rotations, no torsions
+    (``pocket_relax``)."""
+
+    def __init__(self, r, pos_in, ligand_ptr, weights, rot_weight):
+        self.pos, self.protein_role, self.ligand_ptr = r['pos'], r['protein_role'], ligand_ptr
+        raw = {k: r[k].cpu().numpy() for k in ('terms_in', 'terms', 'n_pairs', 'n_steps', 'n_evals', 'status', 'transform', 'grad_in')}
+        raw['n_rot'] = None if r['n_rot'] is None else r['n_rot'].cpu().numpy()
+        self.raw_terms_in, self.raw_terms = raw['terms_in'], raw['terms']
+        for k in ('n_pairs', 'n_steps', 'n_evals', 'status', 'transform', 'grad_in', 'n_rot'):
+            setattr(self, k, raw[k])
+        bad, self.score_in, self.score, self.shift = _relax_scores(raw, weights, rot_weight)
+        self.score_in[bad], self.score[bad] = np.nan, np.nan
+        self.rmsd = _moved(pos_in.cpu().numpy(), self.pos.cpu().numpy(), ligand_ptr.cpu().to(torch.int64).diff().tolist())
+
+
+def pocket_relax(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic', weights=SCORE_WEIGHTS,
+                 rot_weight=SCORE_ROT_WEIGHT, cutoff=SCORE_CUTOFF, hetero_cutoff=DEFAULT_HETERO_CUTOFF, max_steps=RELAX_MAX_STEPS,
+                 max_evals=None, max_shift=RELAX_MAX_SHIFT, ligand_radii=None, protein_radii=None, hydrogens=False, rotors=True, device=None):
+    """The pose of every molecule of one frame ``[N_l, 3]`` or of a stack ``[S, N_l, 3]`` (arguments as ``pocket_score``) after a local
+    optimisation of ``inter`` = ``weights`` . terms of ``pocket_score`` over rigid motions of the molecule in the pocket: BFGS with a
+    backtracking line search on three translations and three rotations, at most ``max_steps`` accepted steps and ``max_evals``
+    evaluations (None: 4 max_steps + 1), the centre never more than ``max_shift`` Angstrom from where it was; one persistent workgroup
+    per molecule (``td_score_minimize``), with the roles and the rotatable bonds of the input pose.  It is a local optimisation under this
+    project's heuristic score, not AutoDock Vina's ``minimize``, and it is rigid-body only: three translations and three rotations, no
+    torsions; no global search, no intramolecular term, no hydrogens.  Returns a ``Relaxed``."""
+    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
+    side = PocketSide((protein_pos, protein_feat), pos.device)
+    (kind, names), elem = side.kinds('residue', hydrogens), side.elem
+    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
+    bond_ptr = bond_ring = None
+    if rotors:
+        bond_ptr = capi.bond_graph(pos, v, ligand_ptr, cz, aro, (), None, False, True)['bond_ptr']
+        bond_ring = capi.ring_report(pos, v, ligand_ptr, cz, aro, None, bond_ptr, False, check=False)['bond_ring']
+    r = capi.score_minimize(pos, v, ligand_ptr, cz, aro, side.pos, elem, kind, side.roles(hydrogens), len(names),
+                            score_radius_sums(ligand_radii, protein_radii), weights, cutoff, hetero_cutoff, bond_ptr, bond_ring, max_steps,
+                            max_evals, max_shift, check=not rotors)
+    return Relaxed(r, pos, ligand_ptr, weights, rot_weight)
+
+
+class RelaxReport(_SumReport):
+    """Per frame (axis 0), over the included molecules that the kernel relaxed (``n_included`` [S] of ``n_samples``; a molecule with
+    status -1 is excluded everywhere): ``scores_in`` and ``scores`` [S, B] float64 with ``scored`` [S, B] bool, the per-molecule scores
+    before and after (the reference's ``vina_score`` / ``vina_min`` pair on this typing; joined along the molecule axis by ``merged``);
+    ``sum_rmsd`` and ``sum_shift`` [S] float64, the RMSD moved and the shift of the centre; ``n_converged``, ``n_out_of_budget``,
+    ``n_at_cap`` [S], the molecules with each status bit; ``sum_steps``, ``sum_evals`` [S] int64.  With a reference ligand relaxed through
+    the same kernel ``sum_ref`` [S, 3] -- per pocket its score before and after and the share of molecules whose minimised score is
+    below its minimised score -- over the ``n_ref`` [S] pockets that have them.  A local optimisation under this
+    project's heuristic score, not AutoDock Vina's ``minimize``; rigid-body only: three translations and three rotations, no torsions
+    (``pocket_relax``)."""
+
+    FIELDS = (('n_included', 'i64'), ('scores_in', 'per_mol'), ('scores', 'per_mol'), ('scored', 'per_mol'), ('sum_rmsd', 'f64'),
+              ('sum_shift', 'f64'), ('n_converged', 'i64'), ('n_out_of_budget', 'i64'), ('n_at_cap', 'i64'), ('sum_steps', 'i64'),
+              ('sum_evals', 'i64'), ('n_samples', 'int_sum'), ('sum_ref', 'ref_f64'), ('n_ref', 'ref_i64'))
+    OPTIONAL, MISMATCH = 2, 'the reports differ in their frames or in whether they have a reference ligand'
+
+    def _merge_key(self):
+        return self.n_included.shape, self.sum_ref is None
+
+    @classmethod
+    def from_outputs(cls, raw, included, pos_in, sizes, weights=SCORE_WEIGHTS, rot_weight=SCORE_ROT_WEIGHT, ref_scores=None):
+        """One pocket: ``raw`` the numpy outputs of capi.score_minimize (pos, terms_in, terms, n_rot, n_steps, n_evals, status,
+        transform), ``included`` [S, B] bool, ``pos_in`` [S, N_l, 3] the input poses, ``sizes`` the molecules' atom counts;
+        ``ref_scores``: the known ligand's (score, minimised score) or None"""
+        bad, before, after, shift = _relax_scores(raw, weights, rot_weight)
+        inc = np.asarray(included, dtype=bool) & ~bad
+        status = np.asarray(raw['status'], dtype=np.int64)
+        rmsd = _moved(pos_in, raw['pos'], sizes)
+        tot = lambda x: np.where(inc, x, 0).sum(1)
+        sum_ref = n_ref = None
+        if ref_scores is not None:
+            S = inc.shape[0]
+            sum_ref, n_ref = np.zeros((S, 3)), np.zeros(S, np.int64)
+            for s in range(S):
+                if inc[s].any():
+                    sum_ref[s] = (ref_scores[0], ref_scores[1], float((after[s][inc[s]] < ref_scores[1]).sum()) / float(inc[s].sum()))
+                    n_ref[s] = 1
+        return cls(inc.sum(1), np.where(inc, before, np.nan), np.where(inc, after, np.nan), inc, tot(rmsd), tot(shift),
+                   tot((status & capi.RELAX_CONVERGED) != 0), tot((status & capi.RELAX_OUT_OF_BUDGET) != 0),
+                   tot((status & capi.RELAX_AT_CAP) != 0), tot(np.asarray(raw['n_steps'], dtype=np.int64)),
+                   tot(np.asarray(raw['n_evals'], dtype=np.int64)), inc.shape[1], sum_ref, n_ref)
+
+    def _of(self, frame, after):
+        return (self.scores if after else self.scores_in)[frame][self.scored[frame]]
+
+    def mean_score(self, frame=-1, after=True):
+        x = self._of(frame, after)
+        return float(x.sum()) / x.size if x.size else float('nan')
+
+    def median_score(self, frame=-1, after=True):
+        x = self._of(frame, after)
+        return float(np.median(x)) if x.size else float('nan')
+
+    def best_score(self, frame=-1, after=True):
+        """the lowest score of the frame"""
+        x = self._of(frame, after)
+        return float(x.min()) if x.size else float('nan')
+
+    def mean_gain(self, frame=-1):
+        """the mean of score before - score after"""
+        x = self._of(frame, False) - self._of(frame, True)
+        return float(x.sum()) / x.size if x.size else float('nan')
+
+    def share_negative(self, frame=-1):
+        return self._mean((self._of(frame, True) < 0.0).sum(), self.n_included[frame])
+
+    def reference(self, frame=-1):
+        """{'ref_score', 'ref_score_min', 'better_than_ref_min'}: the known ligand's score before and after its own relaxation and the
+        share of molecules whose minimised score is below its minimised score (means over the pockets of a merged report), or {}"""
+        if self.sum_ref is None:
+            return {}
+        keys = ('ref_score', 'ref_score_min', 'better_than_ref_min')
+        return {k: self._mean(self.sum_ref[frame, c], self.n_ref[frame]) for c, k in enumerate(keys)}
+
+    def summary(self, frame=-1):
+        n = self.n_included[frame]
+        return dict(mean_score=self.mean_score(frame, False), median_score=self.median_score(frame, False),
+                    best_score=self.best_score(frame, False), mean_score_min=self.mean_score(frame), median_score_min=self.median_score(frame),
+                    best_score_min=self.best_score(frame), mean_gain=self.mean_gain(frame), share_negative_min=self.share_negative(frame),
+                    mean_rmsd=self._mean(self.sum_rmsd[frame], n), mean_shift=self._mean(self.sum_shift[frame], n),
+                    converged=self._mean(self.n_converged[frame], n), out_of_budget=self._mean(self.n_out_of_budget[frame], n),
+                    at_cap=self._mean(self.n_at_cap[frame], n), mean_steps=self._mean(self.sum_steps[frame], n),
+                    mean_evals=self._mean(self.sum_evals[frame], n), **self.reference(frame))
+
+
+def sample_relax(result, eval_step=-1, include='all', reference_ligand=None, weights=SCORE_WEIGHTS, rot_weight=SCORE_ROT_WEIGHT,
+                 max_steps=RELAX_MAX_STEPS, max_shift=RELAX_MAX_SHIFT, cutoff=SCORE_CUTOFF, atom_enc_mode='add_aromatic', device='cuda'):
+    """The rigid-body relaxation of the samples of one pocket (``result``, ``eval_step``, ``include`` and the packing as
+    ``sample_score``): per frame the mean, the median and the best score before and after (the reference's ``vina_score`` / ``vina_min``
+    pair, on this typing), the mean gain, the share of negative scores after, the mean RMSD moved and shift of the centre, the shares
+    converged, out of budget and at the cap, the mean steps and evaluations; with ``reference_ligand`` ``(pos [n, 3], v [n])``, relaxed
+    through the same kernel, its two scores and the share of samples whose minimised score is below its minimised score.  It is a local
+    optimisation under this project's heuristic score, not AutoDock Vina's ``minimize``, and it is rigid-body only: three translations
+    and three rotations, no torsions (``pocket_relax``).  A result without a pocket is refused.  Returns a ``RelaxReport``."""
+    return SamplePack(result, eval_step, atom_enc_mode, device).relax(_pocket_data(result, 'relax'), include, reference_ligand, weights,
+                                                                      max_steps, max_shift, cutoff, rot_weight)
 
 
 # ---- solvent-accessible surface (``td_sasa_report``, csrc/sasa.hip; DESIGN.md section 3, "Solvent-accessible surface")

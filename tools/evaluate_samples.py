@@ -48,6 +48,14 @@ heavy atom, the share of poses with no pair inside the cutoff and, with the know
 the share of samples that score below it (the reference's "high affinity").  It is a Vina-style score on this project's heuristic typing
 -- no hydrogens are placed, the roles come from valence deficits, there is no intramolecular term -- and NOT AutoDock Vina's number:
 it compares between runs of this tool, not with published tables.  QED and SA are still not here.
+``--minimize [--min_steps 64] [--max_shift 3.0]`` adds the same score after a rigid-body relaxation of every sample in its pocket
+(quality.sample_relax: one persistent GPU workgroup per molecule, BFGS with a backtracking line search), alongside ``--score``: the
+mean, the median and the best score before and after (the reference's ``vina_score`` / ``vina_min`` pair, on this typing), the mean
+gain, the share of negative scores after, the mean RMSD moved and shift of the centre, the shares converged, out of budget and at
+the cap, the mean steps and evaluations and, with the known ligand relaxed through the same kernel, its two scores and the share of
+samples whose minimised score is below its minimised score.  It is a local optimisation under this project's heuristic score, not
+AutoDock Vina's ``minimize``, and it is rigid-body only: three translations and three rotations, no torsions; no global search
+(``vina_dock``), no intramolecular term, no hydrogens.
 The fingerprint is this project's own circular one over its bond graph, not RDKit's RDKFingerprint: the numbers compare between
 runs of this tool, not with published tables.  The Jensen-Shannon distances need the reference's empirical distributions: they are
 loaded from ``utils.evaluation`` when the tool runs inside the reference repository (or with it on PYTHONPATH), or from
@@ -91,9 +99,13 @@ def nan_none(d):
     return {k: (None if x != x else x) for k, x in d.items()}
 
 
+METHODS = {'minimize': 'relax'}                       # the flags whose SamplePack method has another name
+
+
 def pocket_sections(args):
     """The reports against the pocket that ``args`` asks for, as (flag -- also the name of the SamplePack method and of the JSON
-    section --, report class, the method's arguments after the reference ligand, extra JSON fields of the merged report)"""
+    section, but for ``METHODS`` --, report class, the method's arguments after the reference ligand, extra JSON fields of the merged
+    report)"""
     every = (
         ('pocket', quality.PocketReport, (args.contact_cutoff, args.clash_tolerance),
          lambda r: dict(contact_cutoff=args.contact_cutoff, clash_tolerance=args.clash_tolerance, contact_profile=r.contact_profile(-1),
@@ -104,7 +116,10 @@ def pocket_sections(args):
         ('sasa', quality.SasaReport, (args.probe, args.sasa_points), lambda r: dict(probe=args.probe, points=args.sasa_points)),
         ('score', quality.ScoreReport, (None, None, args.score_cutoff),
          lambda r: dict(score_cutoff=args.score_cutoff, weights=dict(zip(quality.SCORE_TERM_NAMES, quality.SCORE_WEIGHTS)),
-                        rot_weight=quality.SCORE_ROT_WEIGHT)))
+                        rot_weight=quality.SCORE_ROT_WEIGHT)),
+        ('minimize', quality.RelaxReport, (None, args.min_steps, args.max_shift, args.score_cutoff),
+         lambda r: dict(score_cutoff=args.score_cutoff, max_steps=args.min_steps, max_shift=args.max_shift,
+                        weights=dict(zip(quality.SCORE_TERM_NAMES, quality.SCORE_WEIGHTS)), rot_weight=quality.SCORE_ROT_WEIGHT)))
     return [section for section in every if getattr(args, section[0])]
 
 
@@ -140,7 +155,13 @@ def main(argv=None):
                     "data): a Vina-style score on this project's heuristic typing, NOT AutoDock Vina's number -- comparable between runs "
                     'of this tool, not with published tables')
     ap.add_argument('--score_cutoff', type=float, default=quality.SCORE_CUTOFF, help='--score: a pair counts when it is closer than this')
-    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity, --pocket, --interactions, --sasa, --score: a known ligand, the first V2000 record of '
+    ap.add_argument('--minimize', action='store_true', help="also the score after a rigid-body relaxation of every sample in its pocket: a "
+                    "local optimisation under this project's heuristic score, not AutoDock Vina's minimize; rigid-body only: three "
+                    'translations and three rotations, no torsions')
+    ap.add_argument('--min_steps', type=int, default=quality.RELAX_MAX_STEPS, help='--minimize: accepted steps at most')
+    ap.add_argument('--max_shift', type=float, default=quality.RELAX_MAX_SHIFT, help='--minimize: the centre of a molecule moves at most '
+                    'this far, in Angstrom')
+    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity, --pocket, --interactions, --sasa, --score, --minimize: a known ligand, the first V2000 record of '
                     'FILE; --geometry: known ligands, every record of FILE')
     ap.add_argument('--reference_npz', type=str, default=None)
     ap.add_argument('--device', type=str, default='cuda')
@@ -189,7 +210,7 @@ def main(argv=None):
                 raise SystemExit(f'{name} carries no pocket (no data): --{flag} needs the files of a sampling driver')
             try:
                 side = side or quality.PocketSide(result['data'], args.device)
-                against_pocket[flag].append(getattr(pack, flag)(side, graph_include, reference_ligand, *extra))
+                against_pocket[flag].append(getattr(pack, METHODS.get(flag, flag))(side, graph_include, reference_ligand, *extra))
             except ValueError as e:
                 if flag != 'sasa':
                     raise

@@ -2,7 +2,7 @@
 
     python tools/export_sdf.py --sample_path DIR --out DIR [--eval_step -1] [--only-complete] [--largest-fragment] [--ring-aromatic]
                                 [--unique] [--clash-free] [--pocket-clash-free] [--min-hbonds N]
-                                [--min-buried-share X] [--max-score X] [--sort-by-score]
+                                [--min-buried-share X] [--max-score X] [--sort-by-score] [--relaxed]
 
 Reads the ``result_{i}.pt`` files a sampling driver wrote (sorted as tools/evaluate_samples.py sorts them), takes the frame
 ``--eval_step`` of every sample (default -1: the final poses), builds the bond graph on the GPU (quality.bond_graph: bonds from the
@@ -32,6 +32,10 @@ probe; DESIGN.md section 3, "Solvent-accessible surface"); it combines with the 
 Vina-style score on this project's heuristic typing -- no hydrogens, roles from valence deficits, no intramolecular term -- and NOT
 AutoDock Vina's number; DESIGN.md section 3, "Docking-style score"); it combines with the four above and applies before ``--unique``.
 ``--sort-by-score`` writes the samples of a file best (lowest) score first.  With either, every record carries a ``> <score>`` data item.
+``--relaxed`` writes the coordinates after a rigid-body relaxation of every sample in the file's pocket (quality.pocket_relax; DESIGN.md
+section 3, "Pose relaxation") and a ``> <score_min>`` data item next to ``> <score>``, the score before.  The bonds, the filters and the
+order are those of the sampled poses: a rigid motion changes no bond.  It is a local optimisation under this project's heuristic score,
+not AutoDock Vina's ``minimize``, and it is rigid-body only: three translations and three rotations, no torsions.
 Prints one line per file and returns the counts.
 """
 from __future__ import annotations
@@ -71,6 +75,9 @@ def main(argv=None):
     ap.add_argument('--max-score', type=float, default=None, help="only the samples with a docking-style score of at most this (the file's "
                     "data; a Vina-style score on this project's heuristic typing, NOT AutoDock Vina's number)")
     ap.add_argument('--sort-by-score', action='store_true', help='the samples of a file best (lowest) docking-style score first')
+    ap.add_argument('--relaxed', action='store_true', help="the coordinates after a rigid-body relaxation in the file's pocket, with a "
+                    "score_min data item: a local optimisation under this project's heuristic score, not AutoDock Vina's minimize; "
+                    'rigid-body only: three translations and three rotations, no torsions')
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
     if args.min_buried_share is not None and not 0.0 <= args.min_buried_share <= 1.0:
@@ -124,16 +131,25 @@ def main(argv=None):
             good_score = torch.from_numpy(score <= args.max_score).to(pos.device)
             chosen = good_score if chosen is None else chosen & good_score
             select = good_score.cpu().numpy() & (True if select is None else select)
+        relaxed = None
+        if args.relaxed:
+            if not isinstance(result, dict) or result.get('data') is None:
+                raise SystemExit(f'{name} carries no pocket (no data): --relaxed needs the files of a sampling driver')
+            relaxed = quality.pocket_relax(*quality.pocket_of(result['data']), pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode,
+                                           device=args.device)
+            score = relaxed.score_in[0] if score is None else score
         if args.unique:
             fp = quality.fingerprints(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, device=args.device)
             first = fp.similarity(include=None if chosen is None else chosen[None])['first_equal'][0].cpu().numpy()
             select = (first == np.arange(len(sizes))) & (True if select is None else select)
-        mols = molfile.molecules_from_graph(g, pos, v, args.atom_enc_mode, 0, args.only_complete, args.largest_fragment,
+        mols = molfile.molecules_from_graph(g, pos if relaxed is None else relaxed.pos, v, args.atom_enc_mode, 0, args.only_complete, args.largest_fragment,
                                             categories=g.ring_category if args.ring_aromatic else None, select=select)
         if score is not None:
             of = lambda m: float(score[int(m['name'].rsplit('_', 1)[1])])          # molecules_from_graph names them sample_{g}
             for m in mols:
                 m['properties']['score'] = f'{of(m):.4f}'
+                if relaxed is not None:
+                    m['properties']['score_min'] = f"{float(relaxed.score[0][int(m['name'].rsplit('_', 1)[1])]):.4f}"
             if args.sort_by_score:
                 mols.sort(key=of)
         stem = os.path.basename(name)[:-3]

@@ -611,6 +611,46 @@ int td_score_minimize(const float *d_pos, const int64_t *d_v, const int32_t *d_l
                       int64_t *d_terms_out, int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status,
                       double *d_transform, int64_t *d_grad_in, void *stream);
 
+/* ---- docking search of ligand frames under the docking-style score ("Docking search"): per (frame, molecule) the
+ *      best pose that n_chains independent Monte-Carlo chains of n_rounds + 1 mutate-and-relax rounds find.  It is a rigid-body global
+ *      search under this project's heuristic score, NOT AutoDock Vina's `dock`: three translations and three rotations, no torsions.
+ *      No intramolecular term, no hydrogens; the search box is the ball of max_shift around the input centroid.  Inputs as
+ *      td_score_minimize takes them (max_steps and max_evals are the budget of ONE round), plus n_chains in 1 .. 64, n_rounds in
+ *      0 .. 256, amplitude and temperature finite and > 0 (2.0 Angstrom and 1.2 by convention), else TD_EINVAL, and d_draws
+ *      [S,B,n_chains,n_rounds+1,7] float64 in [0, 1), the caller's uniforms: there is no random number generator on the device.
+ *      Typing, state, pose, evaluation and the local optimisation (one "descent") are td_score_minimize's, from the same code.
+ *      A chain keeps a current state (q, t), at first the identity.  Round r of chain c with u = d_draws[s, b, c, r, :]:
+ *      Chain 0, round 0: no mutation; the descent starts at the input pose: exactly td_score_minimize.
+ *      Every other (chain, round) mutates the current state first, every operation rounded on its own: s_k = 2 u_k - 1 (k < 6);
+ *      t_k += amplitude s_k; h_k = 0.5 ((amplitude s_{3+k}) sqrt(hr)), hr = 1 / mean |x0|^2 over the scored atoms (1 without any);
+ *      the increment d = (1, h) / sqrt(1 + ((hx hx + hy hy) + hz hz)) composed on the left, w = ((dw qw - dx qx) - dy qy) - dz qz,
+ *      x = ((dw qx + dx qw) + dy qz) - dz qy, y = ((dw qy - dx qz) + dy qw) + dz qx, z = ((dw qz + dx qy) - dy qx) + dz qw, divided by
+ *      sqrt(((ww + xx) + yy) + zz).  Then, where |t| = sqrt((tx tx + ty ty) + tz tz) > max_shift, t_k *= (max_shift / |t|)
+ *      (1 - 2^-40), and status bit 4 is set.  No sin or cos runs on the device.  The descent starts there with a fresh H0.
+ *      Metropolis on e = inter of the descent's end: a chain's first round is accepted; a later one when e < e_cur or
+ *      u_6 < exp((e_cur - e) / temperature); an accepted round's end state becomes the current state.  The chain remembers the round
+ *      with the lowest e (the first of equals): its state, terms, pairs and status.
+ *      Selection, in a second launch: the chain with the lowest inter = (((w0 T0 + w1 T1) + w2 T2) + w3 T3) + w4 T4 of its integer
+ *      terms; on a tie the lowest chain index.  Its pose is rebuilt from its transform as td_score_minimize builds a pose; the
+ *      identity keeps the input's bytes.
+ *      Outputs: those of td_score_minimize for the winning pose (d_status the winning round's; d_terms_in and d_grad_in of the input
+ *      pose; d_n_steps and d_n_evals summed over the chains), plus d_best_chain [S,B] int32, d_chain_terms [S,B,n_chains,5] int64 and
+ *      d_chain_transform [S,B,n_chains,7] float64 (each chain's best), d_chain_accepts and d_chain_evals [S,B,n_chains] int32.
+ *      With n_chains = 1 and n_rounds = 0 every shared output is td_score_minimize's.  An oversize molecule, an empty one and N_p = 0
+ *      answer as td_score_minimize does (INT64_MIN in d_chain_terms, identities in d_chain_transform for the first).  Every loop is
+ *      bounded by (n_rounds + 1) max_evals; no floating-point atomic, no spin, no grid-wide synchronisation.  Two runs give identical
+ *      bytes.  (An addition: TD_ABI_VERSION stays 5.) */
+int td_score_dock(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                  const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+                  const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p,
+                  int32_t n_kinds, double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds,
+                  const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals, double max_shift,
+                  int32_t n_chains, int32_t n_rounds, double amplitude, double temperature, const double *d_draws,
+                  int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in, int64_t *d_terms_out,
+                  int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status, double *d_transform,
+                  int64_t *d_grad_in, int32_t *d_best_chain, int64_t *d_chain_terms, double *d_chain_transform,
+                  int32_t *d_chain_accepts, int32_t *d_chain_evals, void *stream);
+
 /* ---- solvent-accessible surface of ligand frames by Shrake-Rupley point counting ("Solvent-accessible
  *      surface"): every output is a count of sphere points; areas are formed by the caller.  One pocket and one pack per call; the
  *      pack, the class table and d_include as td_pocket_report takes them.  d_protein_pos [N_p,3] fp32; d_protein_elem [N_p] int32, an

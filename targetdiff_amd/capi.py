@@ -111,6 +111,10 @@ SIGNATURES = {
     'td_score_minimize': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), _P, _P, _P, _P, c_int64,
                                     c_int32, ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double), _P, c_int64, _P, POINTER(ctypes.c_double),
                                     c_int32, c_int32, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'td_score_dock': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), _P, _P, _P, _P, c_int64,
+                                c_int32, ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double), _P, c_int64, _P, POINTER(ctypes.c_double),
+                                c_int32, c_int32, ctypes.c_double, c_int32, c_int32, ctypes.c_double, ctypes.c_double, _P,
+                                _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_sasa_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, _P, c_int64, POINTER(ctypes.c_double),
                                  POINTER(ctypes.c_double), _P, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -1452,7 +1456,84 @@ def score_minimize(pos, v, ligand_ptr, class_z, class_aromatic, protein_pos, pro
     return out
 
 
-SASA_MAX_POINTS, SASA_CHUNK = 256, 512                                      # TD_SASA_* (csrc/td_internal.h)
+DOCK_CHAINS, DOCK_ROUNDS, DOCK_AMPLITUDE, DOCK_TEMPERATURE = 16, 16, 2.0, 1.2   # the conventions
+DOCK_MAX_CHAINS, DOCK_MAX_ROUNDS, DOCK_DRAWS = 64, 256, 7                       # TD_DOCK_* (csrc/td_internal.h)
+DOCK_KEYS = RELAX_KEYS + ('best_chain', 'chain_terms', 'chain_transform', 'chain_accepts', 'chain_evals')
+
+
+def _dock_inputs(n_chains, n_rounds, amplitude, temperature, seed, draws, S, B, device, check=True):
+    """The search's side of a score_dock call.  Returns (n_chains, n_rounds, amplitude, temperature, the draws as a contiguous float64
+    tensor [S, B, n_chains, n_rounds + 1, 7] on ``device``); ``draws`` None: torch.rand from a generator on the device seeded by ``seed``."""
+    if int(n_chains) != n_chains or not 1 <= int(n_chains) <= DOCK_MAX_CHAINS:
+        raise ValueError(f'n_chains must be an integer in 1 .. {DOCK_MAX_CHAINS} (got {n_chains})')
+    if int(n_rounds) != n_rounds or not 0 <= int(n_rounds) <= DOCK_MAX_ROUNDS:
+        raise ValueError(f'n_rounds must be an integer in 0 .. {DOCK_MAX_ROUNDS} (got {n_rounds})')
+    if not (np.isfinite(float(amplitude)) and float(amplitude) > 0.0):
+        raise ValueError(f'amplitude must be finite and > 0 (got {amplitude})')
+    if not (np.isfinite(float(temperature)) and float(temperature) > 0.0):
+        raise ValueError(f'temperature must be finite and > 0 (got {temperature})')
+    shape = (S, B, int(n_chains), int(n_rounds) + 1, DOCK_DRAWS)
+    if draws is None:
+        gen = torch.Generator(device=device)
+        gen.manual_seed(int(seed))
+        draws = torch.rand(shape, dtype=torch.float64, device=device, generator=gen)
+    else:
+        if not torch.is_tensor(draws) or draws.dtype != torch.float64 or tuple(draws.shape) != shape or draws.device != device:
+            raise ValueError(f'draws is a float64 tensor {list(shape)} on the device of pos')
+        draws = draws.contiguous()
+        if check and draws.numel() and not bool(((draws >= 0.0) & (draws < 1.0)).all()):
+            raise ValueError('draws must lie in [0, 1)')
+    return int(n_chains), int(n_rounds), float(amplitude), float(temperature), draws
+
+
+def score_dock(pos, v, ligand_ptr, class_z, class_aromatic, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, rsum, weights,
+               cutoff=8.0, hetero_cutoff=1.75, bond_ptr=None, bond_ring=None, max_steps=RELAX_MAX_STEPS, max_evals=None,
+               max_shift=RELAX_MAX_SHIFT, n_chains=DOCK_CHAINS, n_rounds=DOCK_ROUNDS, amplitude=DOCK_AMPLITUDE, temperature=DOCK_TEMPERATURE,
+               seed=0, draws=None, check=True, _list_capacity=None):
+    """The docking search of S frames of B molecules in one pocket under ``inter = weights . terms`` of score_report (td_score_dock,
+    include/targetdiff_hip.h): per molecule ``n_chains`` independent Monte-Carlo chains, one persistent workgroup each, run
+    ``n_rounds`` + 1 rounds of a random rigid move (shift up to ``amplitude`` Angstrom per axis, a turn to match) followed by
+    score_minimize's local optimisation, with a Metropolis rule at ``temperature`` on inter; a second small launch takes the best chain.
+    Chain 0 starts with the plain relaxation of the input pose.  It is a rigid-body global search under this project's heuristic score,
+    not AutoDock Vina's ``dock``: three translations and three rotations, no torsions.  No intramolecular term, no hydrogens; the search
+    box is the ball of ``max_shift`` around the input centroid.  The arguments up to ``max_shift`` as score_minimize's (validated alike;
+    ``max_steps`` and ``max_evals`` are one round's budget).  The uniforms are the caller's: ``draws`` float64
+    [S, B, n_chains, n_rounds + 1, 7] in [0, 1) on the device, or None for torch.rand from a generator seeded by ``seed``.
+    Returns score_minimize's dict for the winning pose (n_steps and n_evals summed over the chains), plus best_chain [S, B] int32,
+    chain_terms [S, B, C, 5] int64 and chain_transform [S, B, C, 7] float64 (each chain's best), chain_accepts and chain_evals
+    [S, B, C] int32, and ``draws``."""
+    S, Nl, B, cz, aro, _ = _bond_inputs(pos, v, ligand_ptr, class_z, class_aromatic, None, (), check)
+    Np, rs, nb = _score_inputs(pos, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, rsum, cutoff, hetero_cutoff, bond_ptr,
+                               bond_ring, S, B, check)
+    w, max_steps, max_evals, max_shift = _relax_inputs(weights, max_steps, max_evals, max_shift)
+    dev = pos.device
+    C, n_rounds, amplitude, temperature, draws = _dock_inputs(n_chains, n_rounds, amplitude, temperature, seed, draws, S, B, dev, check)
+    lib = load_library()
+    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
+    i32, _, i64 = _allocators(dev)
+    out = dict(protein_role=i32(Np), n_rot=i32(S, B) if bond_ptr is not None else None, pos=torch.empty_like(pos),
+               terms_in=i64(S, B, SCORE_TERMS), terms=i64(S, B, SCORE_TERMS), n_pairs=i32(S, B), n_steps=i32(S, B), n_evals=i32(S, B),
+               status=i32(S, B), transform=torch.empty(S, B, 7, dtype=torch.float64, device=dev), grad_in=i64(S, B, 6),
+               best_chain=i32(S, B), chain_terms=i64(S, B, C, SCORE_TERMS), chain_transform=torch.empty(S, B, C, 7, dtype=torch.float64, device=dev),
+               chain_accepts=i32(S, B, C), chain_evals=i32(S, B, C))
+    args = (*pack, _aromatic_arg(aro), _ptr(protein_pos, torch.float32, 'protein_pos'), _ptr(protein_elem, torch.int32, 'protein_elem'),
+            _ptr(protein_kind, torch.int32, 'protein_kind'), _ptr(protein_role, torch.int32, 'protein_role'), Np, int(n_kinds), float(cutoff),
+            float(hetero_cutoff), rs.ctypes.data_as(POINTER(ctypes.c_double)), _ptr(bond_ptr, torch.int64, 'bond_ptr'), nb,
+            _ptr(bond_ring, torch.int16, 'bond_ring') if nb else None, w.ctypes.data_as(POINTER(ctypes.c_double)), max_steps, max_evals,
+            max_shift, C, n_rounds, amplitude, temperature, _ptr(draws, torch.float64, 'draws'), *(_ptr(out[k]) for k in DOCK_KEYS),
+            _stream(dev))
+    with _on(dev):
+        if _list_capacity is None:
+            _check(lib.td_score_dock(*args), 'td_score_dock')
+        else:                                                                    # the tests' door to the walk in global memory
+            fn = lib.td_internal_score_dock_capacity
+            fn.restype, fn.argtypes = c_int32, SIGNATURES['td_score_dock'][1] + [c_int32]
+            _check(fn(*args, int(_list_capacity)), 'td_score_dock')
+    out['draws'] = draws
+    return out
+
+
+SASA_MAX_POINTS, SASA_CHUNK = 256, 512                                     # TD_SASA_* (csrc/td_internal.h)
 SASA_CULL_REL, SASA_CULL_ABS = 1e-4, 1e-4                                   # TD_SASA_CULL_*: an occluder farther than (R_a + R_b) (1 + REL) + ABS is not looked at
 SASA_COORD_MAX = 1.0e5                                                      # |coordinate| the binding admits: csrc/sasa.hip's cull is proved up to it
 SASA_UNIT_TOL = 1.0e-6                                                      # | |u|^2 - 1 | the binding admits of a direction

@@ -1,13 +1,14 @@
 // C ABI of libtargetdiff_hip.so: the bond graph of ligand frames, its rings, its fingerprints, its local geometry and the contacts with
 // the pocket, the typed interactions with it, the docking-style score and the surface it buries (td_bond_graph, td_bond_list,
 // td_ring_report, td_fingerprint, td_fingerprint_similarity, td_geometry_report, td_pocket_report, td_interaction_report,
-// td_score_report, td_score_minimize, td_sasa_report).  See
+// td_score_report, td_score_minimize, td_score_dock, td_sasa_report).  See
 // include/targetdiff_hip.h for the contract.
 #include <cmath>
 #include <initializer_list>
 
 #include "td_device.h"
 #include "td_internal.h"
+#include "td_api.h"
 
 namespace {
 // the checks and the fields the entry points share: sizes, the class table, the aromatic flags and, of the entry points that take the
@@ -388,15 +389,15 @@ extern "C" int td_score_report(const float *d_pos, const int64_t *d_v, const int
 }
 
 namespace {
-int score_minimize(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
-                   const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
-                   const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds,
-                   double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds,
-                   const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals, double max_shift,
-                   int32_t list_capacity, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in,
-                   int64_t *d_terms_out, int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status,
-                   double *d_transform, int64_t *d_grad_in, void *stream) {
-    const char *who = "td_score_minimize";
+// What td_score_minimize and td_score_dock share: the optimiser's arguments and outputs checked and filled into g, then score_side.
+int relax_side(const char *who, TdRelaxArgs &g, const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l,
+               int64_t B, const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+               const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds,
+               double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds,
+               const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals, double max_shift,
+               int32_t list_capacity, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in,
+               int64_t *d_terms_out, int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status,
+               double *d_transform, int64_t *d_grad_in, void *stream) {
     if (max_steps < 0 || max_evals < 1 || list_capacity < 0) {
         td_set_error("%s: bad argument (max_steps = %d must be >= 0, max_evals = %d must be >= 1)", who, (int)max_steps, (int)max_evals);
         return TD_EINVAL;
@@ -406,7 +407,6 @@ int score_minimize(const float *d_pos, const int64_t *d_v, const int32_t *d_liga
         return TD_EINVAL;
     }
     if (!weights) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
-    TdRelaxArgs g;
     for (int k = 0; k < TD_SCORE_TERMS; ++k) {
         if (!std::isfinite(weights[k])) { td_set_error("%s: the weights must be finite (weight %d)", who, k); return TD_EINVAL; }
         g.w[k] = weights[k];
@@ -425,7 +425,64 @@ int score_minimize(const float *d_pos, const int64_t *d_v, const int32_t *d_liga
     g.terms_in = reinterpret_cast<long long *>(d_terms_in); g.terms_out = reinterpret_cast<long long *>(d_terms_out);
     g.n_pairs_out = d_n_pairs_out; g.n_steps = d_n_steps; g.n_evals = d_n_evals; g.status = d_status;
     g.transform = d_transform; g.grad_in = reinterpret_cast<long long *>(d_grad_in);
+    return TD_OK;
+}
+
+int score_minimize(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                   const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+                   const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds,
+                   double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds,
+                   const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals, double max_shift,
+                   int32_t list_capacity, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in,
+                   int64_t *d_terms_out, int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status,
+                   double *d_transform, int64_t *d_grad_in, void *stream) {
+    TdRelaxArgs g;
+    if (const int rc = relax_side("td_score_minimize", g, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos,
+                                  d_protein_elem, d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr,
+                                  n_bonds, d_bond_ring, weights, max_steps, max_evals, max_shift, list_capacity, d_protein_role_out,
+                                  d_n_rot, d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform,
+                                  d_grad_in, stream))
+        return rc;
     return td_launch_score_minimize(g, static_cast<hipStream_t>(stream));
+}
+
+int score_dock(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                   const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+                   const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds,
+                   double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds,
+                   const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals, double max_shift,
+               int32_t n_chains, int32_t n_rounds, double amplitude, double temperature, const double *d_draws, int32_t list_capacity,
+               int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in, int64_t *d_terms_out,
+               int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status, double *d_transform, int64_t *d_grad_in,
+               int32_t *d_best_chain, int64_t *d_chain_terms, double *d_chain_transform, int32_t *d_chain_accepts, int32_t *d_chain_evals,
+               void *stream) {
+    const char *who = "td_score_dock";
+    if (n_chains < 1 || n_chains > TD_DOCK_MAX_CHAINS || n_rounds < 0 || n_rounds > TD_DOCK_MAX_ROUNDS) {
+        td_set_error("%s: bad argument (n_chains = %d must be in 1 .. %d, n_rounds = %d in 0 .. %d)", who, (int)n_chains, TD_DOCK_MAX_CHAINS,
+                     (int)n_rounds, TD_DOCK_MAX_ROUNDS);
+        return TD_EINVAL;
+    }
+    if (!std::isfinite(amplitude) || !(amplitude > 0.0) || !std::isfinite(temperature) || !(temperature > 0.0)) {
+        td_set_error("%s: amplitude and temperature must be finite and > 0", who);
+        return TD_EINVAL;
+    }
+    if (S > 0 && B > 0 && (!d_draws || !d_best_chain || !d_chain_terms || !d_chain_transform || !d_chain_accepts || !d_chain_evals)) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    TdDockArgs d;
+    if (const int rc = relax_side(who, d.rx, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos,
+                                  d_protein_elem, d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr,
+                                  n_bonds, d_bond_ring, weights, max_steps, max_evals, max_shift, list_capacity, d_protein_role_out,
+                                  d_n_rot, d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform,
+                                  d_grad_in, stream))
+        return rc;
+    d.n_chains = n_chains; d.n_rounds = n_rounds; d.amplitude = amplitude; d.temperature = temperature; d.draws = d_draws;
+    d.best_chain = d_best_chain; d.chain_terms = reinterpret_cast<long long *>(d_chain_terms); d.chain_transform = d_chain_transform;
+    d.chain_accepts = d_chain_accepts; d.chain_evals = d_chain_evals;
+    tdapi::AsyncScratch scratch(static_cast<hipStream_t>(stream));               // given back in stream order, behind the selection
+    if (const int rc = scratch.take(&d.chain_aux, (size_t)S * (size_t)B * (size_t)n_chains * 3 * sizeof(int32_t), who)) return rc;
+    return td_launch_score_dock(d, static_cast<hipStream_t>(stream));
 }
 }  // namespace
 
@@ -458,6 +515,39 @@ extern "C" __attribute__((visibility("default"))) int td_internal_score_minimize
                           d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring, weights,
                           max_steps, max_evals, max_shift, list_capacity, d_protein_role_out, d_n_rot, d_pos_out, d_terms_in, d_terms_out,
                           d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform, d_grad_in, stream);
+}
+
+extern "C" int td_score_dock(
+    const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+    const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos, const int32_t *d_protein_elem,
+    const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds, double cutoff, double hetero_cutoff,
+    const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds, const uint16_t *d_bond_ring, const double *weights, int32_t max_steps,
+    int32_t max_evals, double max_shift, int32_t n_chains, int32_t n_rounds, double amplitude, double temperature, const double *d_draws,
+    int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in, int64_t *d_terms_out, int32_t *d_n_pairs_out,
+    int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status, double *d_transform, int64_t *d_grad_in, int32_t *d_best_chain,
+    int64_t *d_chain_terms, double *d_chain_transform, int32_t *d_chain_accepts, int32_t *d_chain_evals, void *stream) {
+    return score_dock(d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos, d_protein_elem, d_protein_kind,
+                      d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring, weights, max_steps, max_evals,
+                      max_shift, n_chains, n_rounds, amplitude, temperature, d_draws, TD_RELAX_LIST_CAPACITY, d_protein_role_out, d_n_rot,
+                      d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform, d_grad_in, d_best_chain,
+                      d_chain_terms, d_chain_transform, d_chain_accepts, d_chain_evals, stream);
+}
+
+// td_score_dock with the capacity of the LDS list as a last argument, as td_internal_score_minimize_capacity; not part of the public ABI.
+extern "C" __attribute__((visibility("default"))) int td_internal_score_dock_capacity(
+    const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+    const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos, const int32_t *d_protein_elem,
+    const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds, double cutoff, double hetero_cutoff,
+    const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds, const uint16_t *d_bond_ring, const double *weights, int32_t max_steps,
+    int32_t max_evals, double max_shift, int32_t n_chains, int32_t n_rounds, double amplitude, double temperature, const double *d_draws,
+    int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in, int64_t *d_terms_out, int32_t *d_n_pairs_out,
+    int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status, double *d_transform, int64_t *d_grad_in, int32_t *d_best_chain,
+    int64_t *d_chain_terms, double *d_chain_transform, int32_t *d_chain_accepts, int32_t *d_chain_evals, void *stream, int32_t list_capacity) {
+    return score_dock(d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos, d_protein_elem, d_protein_kind,
+                      d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring, weights, max_steps, max_evals,
+                      max_shift, n_chains, n_rounds, amplitude, temperature, d_draws, list_capacity, d_protein_role_out, d_n_rot,
+                      d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform, d_grad_in, d_best_chain,
+                      d_chain_terms, d_chain_transform, d_chain_accepts, d_chain_evals, stream);
 }
 
 extern "C" int td_sasa_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,

@@ -595,6 +595,23 @@ struct TdRelaxArgs {
 int td_launch_score_minimize(const TdRelaxArgs &a, hipStream_t s);
 // bonds_api.cpp also exports td_internal_score_minimize_capacity: td_score_minimize with list_capacity as a last argument, for the tests
 // that hold the two walks to identical bytes.  It is not declared in include/targetdiff_hip.h and is no part of the public ABI.
+// relax.hip (td_score_dock, DESIGN.md section 3, "Docking search"): `rx` as td_launch_score_minimize takes it, its outputs being the
+// winning chain's (n_steps and n_evals summed over the chains).  One workgroup per (frame, molecule, chain), then one per (frame,
+// molecule) that selects.  chain_aux is scratch of the caller's, on the stream: per chain the pairs and the status of its best and its
+// steps.  td_internal_score_dock_capacity is to td_score_dock what td_internal_score_minimize_capacity is to td_score_minimize.
+constexpr int TD_DOCK_MAX_CHAINS = 64, TD_DOCK_MAX_ROUNDS = 256, TD_DOCK_DRAWS = 7;
+struct TdDockArgs {
+    TdRelaxArgs rx;
+    int n_chains = 1, n_rounds = 0;
+    double amplitude = 0.0, temperature = 0.0;
+    const double *draws = nullptr;           // [S,B,n_chains,n_rounds+1,TD_DOCK_DRAWS] in [0, 1): six for the mutation, one for Metropolis
+    int32_t *best_chain = nullptr;           // [S,B]
+    long long *chain_terms = nullptr;        // [S,B,n_chains,TD_SCORE_TERMS]
+    double *chain_transform = nullptr;       // [S,B,n_chains,7]
+    int32_t *chain_accepts = nullptr, *chain_evals = nullptr;                    // [S,B,n_chains]
+    int32_t *chain_aux = nullptr;            // [S,B,n_chains,3]
+};
+int td_launch_score_dock(const TdDockArgs &a, hipStream_t s);
 // sasa.hip (td_sasa_report, DESIGN.md section 3, "Solvent-accessible surface"): the pack and the include bytes in `b` (none of b's
 // outputs is used); the pocket as TdProteinSide holds it, without kinds, in fields of its own (its kernels keep the argument block they
 // were measured with: EXPERIMENTS.md "Pocket reports").  lig_R over H C N O F P S Cl and prot_R over H C N O S Se: the

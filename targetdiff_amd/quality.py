@@ -378,7 +378,7 @@ class SamplePack:
         self.sizes, self.S = sizes, S
         self.class_z, self.aromatic = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
         self._checked = self._sized = False
-        self._stable = self._graph = self._bond_ring = self._ref = self.relaxed_pos = None
+        self._stable = self._graph = self._bond_ring = self._ref = self.relaxed_pos = self.docked_pos = None
 
     @property
     def _args(self):
@@ -584,6 +584,39 @@ class SamplePack:
         self.relaxed_pos = r['pos']
         raw = {k: r[k].cpu().numpy() for k in keys}
         return RelaxReport.from_outputs(raw, self._included(mask), self.pos.cpu().numpy(), self.sizes, weights, rot_weight, ref_scores)
+
+    def dock(self, data, include='all', reference_ligand=None, weights=None, n_chains=None, n_rounds=None, seed=0, max_steps=None,
+             max_shift=None, cutoff=None, rot_weight=None):
+        """``sample_dock`` of the pack, which must hold a single frame (ValueError otherwise: one launch would hold S B n_chains
+        long-lived workgroups); ``data`` as ``pocket``.  The relaxation alone runs beside the search, for the score it is compared with;
+        the docked coordinates of the last call stay in ``docked_pos`` [1, N_l, 3] on the device.  The known ligand's draws are seeded
+        by ``seed`` too."""
+        _single_frame(None, self.S)
+        weights = SCORE_WEIGHTS if weights is None else weights
+        rot_weight = SCORE_ROT_WEIGHT if rot_weight is None else rot_weight
+        side = self._side(data)
+        kind, names = side.kinds()
+        mask = self.mask(include)
+        pocket = (side.pos, side.elem, kind, side.roles(), len(names), score_radius_sums(), weights, SCORE_CUTOFF if cutoff is None else cutoff,
+                  DEFAULT_HETERO_CUTOFF)
+        budget = dict(max_steps=RELAX_MAX_STEPS if max_steps is None else max_steps, max_shift=RELAX_MAX_SHIFT if max_shift is None else max_shift)
+        search = dict(budget, n_chains=DOCK_CHAINS if n_chains is None else n_chains, n_rounds=DOCK_ROUNDS if n_rounds is None else n_rounds, seed=seed)
+        ref_score = None
+        if reference_ligand is not None:
+            ref = self._reference(reference_ligand)
+            bond_ptr = capi.bond_graph(*ref, self.aromatic, (), None, False, True)['bond_ptr']
+            ring = capi.ring_report(*ref, self.aromatic, None, bond_ptr, False)['bond_ring']
+            q = capi.score_dock(*ref, self.aromatic, *pocket, bond_ptr, ring, **search)
+            if int(q['status'][0, 0]) >= 0:
+                ref_score = float(_relax_scores({k: q[k].cpu().numpy() for k in ('terms_in', 'terms', 'n_rot', 'status', 'transform')}, weights,
+                                                rot_weight)[2][0, 0])
+        graph = (self.graph['bond_ptr'], self.bond_ring)
+        r_min = capi.score_minimize(*self._args, self.aromatic, *pocket, *graph, **budget, check=self._check())
+        r = capi.score_dock(*self._args, self.aromatic, *pocket, *graph, **search, check=self._check())
+        self.docked_pos = r['pos']
+        raw = {k: r[k].cpu().numpy() for k in _DOCK_RAW}
+        raw_min = {k: r_min[k].cpu().numpy() for k in ('terms_in', 'terms', 'n_rot', 'status', 'transform')}
+        return DockReport.from_outputs(raw, raw_min, self._included(mask), self.pos.cpu().numpy(), self.sizes, weights, rot_weight, ref_score)
 
     def sasa(self, data, include='all', reference_ligand=None, probe=1.4, points=96):
         """``sample_sasa`` of the pack; ``data`` as ``pocket``"""
@@ -2030,6 +2063,185 @@ def sample_relax(result, eval_step=-1, include='all', reference_ligand=None, wei
     and three rotations, no torsions (``pocket_relax``).  A result without a pocket is refused.  Returns a ``RelaxReport``."""
     return SamplePack(result, eval_step, atom_enc_mode, device).relax(_pocket_data(result, 'relax'), include, reference_ligand, weights,
                                                                       max_steps, max_shift, cutoff, rot_weight)
+
+
+# ---- docking search (``td_score_dock``, csrc/relax.hip; DESIGN.md section 3, "Docking search")
+# The best pose that independent Monte-Carlo chains of mutate-and-relax rounds find for every molecule, one persistent workgroup per
+# (molecule, chain): the reference's ``vina_dock`` next to ``vina_score`` and ``vina_min``, on this project's typing.  It is a rigid-body
+# global search under this project's heuristic score, not AutoDock Vina's ``dock``: three translations and three rotations, no torsions.
+# No intramolecular term, no hydrogens; the search box is the ball of ``max_shift`` around the input centroid.
+DOCK_CHAINS, DOCK_ROUNDS, DOCK_AMPLITUDE, DOCK_TEMPERATURE = capi.DOCK_CHAINS, capi.DOCK_ROUNDS, capi.DOCK_AMPLITUDE, capi.DOCK_TEMPERATURE
+DOCK_AGREE = 0.5                                      # a chain agrees with the winner when its best inter is within this of the winner's
+_DOCK_RAW = ('pos', 'terms_in', 'terms', 'n_rot', 'n_steps', 'n_evals', 'status', 'transform', 'best_chain', 'chain_terms')
+
+
+def _single_frame(eval_step, S=None):
+    """the docking search takes one frame: refuse a stack, and say why"""
+    if eval_step == 'all' or (S is not None and S != 1):
+        raise ValueError("the docking search takes a single frame, not eval_step='all' or a stack: one launch would hold S B n_chains "
+                         'long-lived workgroups')
+
+
+def _dock_scores(raw, raw_min, weights, rot_weight):
+    """(bad [S, B], score before, score after the relaxation, score after the search, the share of chains whose best inter is within
+    DOCK_AGREE of the winner's) of the numpy outputs of capi.score_dock and, for the middle one, of capi.score_minimize"""
+    bad, before, docked, _ = _relax_scores(raw, weights, rot_weight)
+    minimised = _relax_scores(raw_min, weights, rot_weight)[2]
+    inter = score_energies(np.where(bad[..., None, None], 0, raw['chain_terms']), None, weights, rot_weight)[1]        # [S, B, C]
+    won = np.take_along_axis(inter, np.asarray(raw['best_chain'], dtype=np.int64)[..., None], -1)
+    return bad, before, minimised, docked, (inter <= won + DOCK_AGREE).sum(-1) / float(inter.shape[-1])
+
+
+class Docked:
+    """The docking search of one frame of B molecules in one pocket (``pocket_dock``).  ``pos`` [1, N_l, 3] fp32 on the device, the
+    docked poses; numpy, frame axis first: ``raw_terms_in`` / ``raw_terms`` [1, B, 5] int64 (the kernel's integers at the input and at
+    the docked pose), ``n_pairs``, ``n_steps``, ``n_evals`` (summed over the chains), ``status`` [1, B] int32, ``n_rot`` [1, B] int32 of
+    the input pose or None, ``transform`` [1, B, 7] float64, ``best_chain`` [1, B] int32, ``chain_terms`` [1, B, C, 5] int64,
+    ``chain_transform`` [1, B, C, 7], ``chain_accepts``, ``chain_evals`` [1, B, C] int32, and ``score_in`` / ``score_min`` / ``score``
+    [1, B] float64 = inter / (1 + rot_weight n_rot) of the input pose, after the relaxation alone and after the search, ``rmsd`` [1, B]
+    the RMSD moved over all atoms, ``agree`` [1, B] the share of chains whose best inter is within ``DOCK_AGREE`` of the winner's.  A
+    molecule the kernel refused (status -1) has NaN scores.  A rigid-body global search under this project's heuristic score, not
+    AutoDock Vina's ``dock``: three translations and three rotations, no torsions (``pocket_dock``)."""
+
+    def __init__(self, r, r_min, pos_in, ligand_ptr, weights, rot_weight):
+        self.pos, self.protein_role, self.ligand_ptr, self.draws = r['pos'], r['protein_role'], ligand_ptr, r.get('draws')
+        keys = ('terms_in', 'terms', 'n_pairs', 'n_steps', 'n_evals', 'status', 'transform', 'best_chain', 'chain_terms', 'chain_transform',
+                'chain_accepts', 'chain_evals')
+        raw = {k: r[k].cpu().numpy() for k in keys}
+        raw['n_rot'] = None if r['n_rot'] is None else r['n_rot'].cpu().numpy()
+        raw_min = {k: (None if r_min[k] is None else r_min[k].cpu().numpy()) for k in ('terms_in', 'terms', 'n_rot', 'status', 'transform')}
+        self.raw_terms_in, self.raw_terms = raw['terms_in'], raw['terms']
+        for k in keys[2:] + ('n_rot',):
+            setattr(self, k, raw[k])
+        bad, self.score_in, self.score_min, self.score, self.agree = _dock_scores(raw, raw_min, weights, rot_weight)
+        for x in (self.score_in, self.score_min, self.score):
+            x[bad] = np.nan
+        self.rmsd = _moved(pos_in.cpu().numpy(), self.pos.cpu().numpy(), ligand_ptr.cpu().to(torch.int64).diff().tolist())
+
+
+def pocket_dock(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic', weights=SCORE_WEIGHTS,
+                rot_weight=SCORE_ROT_WEIGHT, cutoff=SCORE_CUTOFF, hetero_cutoff=DEFAULT_HETERO_CUTOFF, n_chains=DOCK_CHAINS, n_rounds=DOCK_ROUNDS,
+                amplitude=DOCK_AMPLITUDE, temperature=DOCK_TEMPERATURE, seed=0, draws=None, max_steps=RELAX_MAX_STEPS, max_evals=None,
+                max_shift=RELAX_MAX_SHIFT, ligand_radii=None, protein_radii=None, hydrogens=False, rotors=True, device=None):
+    """The best pose of every molecule of ONE frame ``[N_l, 3]`` (arguments as ``pocket_relax``; a stack is refused: one launch would
+    hold S B n_chains long-lived workgroups) that ``n_chains`` independent Monte-Carlo chains of ``n_rounds`` + 1 rounds find: each round
+    a random rigid move (up to ``amplitude`` Angstrom per axis and a turn to match) followed by ``pocket_relax``'s local optimisation
+    (``max_steps`` and ``max_evals`` per round), accepted by a Metropolis rule at ``temperature``; chain 0 starts with the plain
+    relaxation, so the result is never worse than ``pocket_relax``'s.  One persistent workgroup per (molecule, chain)
+    (``td_score_dock``); the uniforms are ``draws`` or torch.rand seeded by ``seed``.  It is a rigid-body global search under this project's
+    heuristic score, not AutoDock Vina's ``dock``: three translations and three rotations, no torsions.  No intramolecular term, no
+    hydrogens; the search box is the ball of ``max_shift`` around the input centroid.  Returns a ``Docked``."""
+    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
+    _single_frame(None, pos.shape[0])
+    side = PocketSide((protein_pos, protein_feat), pos.device)
+    (kind, names), elem = side.kinds('residue', hydrogens), side.elem
+    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
+    bond_ptr = bond_ring = None
+    if rotors:
+        bond_ptr = capi.bond_graph(pos, v, ligand_ptr, cz, aro, (), None, False, True)['bond_ptr']
+        bond_ring = capi.ring_report(pos, v, ligand_ptr, cz, aro, None, bond_ptr, False, check=False)['bond_ring']
+    args = (pos, v, ligand_ptr, cz, aro, side.pos, elem, kind, side.roles(hydrogens), len(names), score_radius_sums(ligand_radii, protein_radii),
+            weights, cutoff, hetero_cutoff, bond_ptr, bond_ring, max_steps, max_evals, max_shift)
+    r_min = capi.score_minimize(*args, check=not rotors)
+    r = capi.score_dock(*args, n_chains, n_rounds, amplitude, temperature, seed, draws, check=not rotors)
+    return Docked(r, r_min, pos, ligand_ptr, weights, rot_weight)
+
+
+class DockReport(_SumReport):
+    """Per frame (axis 0; the search takes one frame), over the included molecules that the kernel searched (``n_included`` [S] of
+    ``n_samples``; a molecule with status -1 is excluded everywhere): ``scores_in``, ``scores_min`` and ``scores`` [S, B] float64 with
+    ``scored`` [S, B] bool, the per-molecule scores of the input pose, after the relaxation alone and after the search (the reference's
+    ``vina_score`` / ``vina_min`` / ``vina_dock`` on this typing; joined along the molecule axis by ``merged``); ``sum_rmsd`` [S] the RMSD
+    from the input; ``sum_agree`` [S] the share of chains whose best inter is within ``DOCK_AGREE`` of the winner's, a convergence
+    indicator; ``sum_evals`` [S] int64.  With a reference ligand run through the same kernel ``sum_ref`` [S, 2] -- per pocket its docked
+    score and the share of molecules whose docked score is below it -- over the ``n_ref`` [S] pockets that have them.  A rigid-body global
+    search under this project's heuristic score, not AutoDock Vina's ``dock``: three translations and three rotations, no torsions
+    (``pocket_dock``)."""
+
+    FIELDS = (('n_included', 'i64'), ('scores_in', 'per_mol'), ('scores_min', 'per_mol'), ('scores', 'per_mol'), ('scored', 'per_mol'),
+              ('sum_rmsd', 'f64'), ('sum_agree', 'f64'), ('sum_evals', 'i64'), ('n_samples', 'int_sum'), ('sum_ref', 'ref_f64'), ('n_ref', 'ref_i64'))
+    OPTIONAL, MISMATCH = 2, 'the reports differ in their frames or in whether they have a reference ligand'
+
+    def _merge_key(self):
+        return self.n_included.shape, self.sum_ref is None
+
+    @classmethod
+    def from_outputs(cls, raw, raw_min, included, pos_in, sizes, weights=SCORE_WEIGHTS, rot_weight=SCORE_ROT_WEIGHT, ref_score=None):
+        """One pocket: ``raw`` the numpy outputs of capi.score_dock (pos, terms_in, terms, n_rot, n_evals, status, transform, best_chain,
+        chain_terms), ``raw_min`` those of capi.score_minimize on the same pack (terms_in, terms, n_rot, status, transform), ``included``
+        [S, B] bool, ``pos_in`` [S, N_l, 3] the input poses, ``sizes`` the molecules' atom counts; ``ref_score``: the known ligand's docked
+        score or None"""
+        bad, before, minimised, docked, agree = _dock_scores(raw, raw_min, weights, rot_weight)
+        inc = np.asarray(included, dtype=bool) & ~bad
+        rmsd = _moved(pos_in, raw['pos'], sizes)
+        tot = lambda x: np.where(inc, x, 0).sum(1)
+        sum_ref = n_ref = None
+        if ref_score is not None:
+            S = inc.shape[0]
+            sum_ref, n_ref = np.zeros((S, 2)), np.zeros(S, np.int64)
+            for s in range(S):
+                if inc[s].any():
+                    sum_ref[s] = (ref_score, float((docked[s][inc[s]] < ref_score).sum()) / float(inc[s].sum()))
+                    n_ref[s] = 1
+        return cls(inc.sum(1), np.where(inc, before, np.nan), np.where(inc, minimised, np.nan), np.where(inc, docked, np.nan), inc, tot(rmsd),
+                   tot(agree), tot(np.asarray(raw['n_evals'], dtype=np.int64)), inc.shape[1], sum_ref, n_ref)
+
+    def _of(self, frame, which):
+        return {'in': self.scores_in, 'min': self.scores_min, 'dock': self.scores}[which][frame][self.scored[frame]]
+
+    def mean_score(self, frame=-1, which='dock'):
+        x = self._of(frame, which)
+        return float(x.sum()) / x.size if x.size else float('nan')
+
+    def median_score(self, frame=-1, which='dock'):
+        x = self._of(frame, which)
+        return float(np.median(x)) if x.size else float('nan')
+
+    def best_score(self, frame=-1, which='dock'):
+        """the lowest score of the frame"""
+        x = self._of(frame, which)
+        return float(x.min()) if x.size else float('nan')
+
+    def mean_gain(self, frame=-1):
+        """the mean of score after the relaxation alone - score after the search"""
+        x = self._of(frame, 'min') - self._of(frame, 'dock')
+        return float(x.sum()) / x.size if x.size else float('nan')
+
+    def share_negative(self, frame=-1):
+        return self._mean((self._of(frame, 'dock') < 0.0).sum(), self.n_included[frame])
+
+    def reference(self, frame=-1):
+        """{'ref_score_dock', 'better_than_ref_dock'}: the known ligand's score after its own search and the share of molecules whose
+        docked score is below it (means over the pockets of a merged report), or {}"""
+        if self.sum_ref is None:
+            return {}
+        return {k: self._mean(self.sum_ref[frame, c], self.n_ref[frame]) for c, k in enumerate(('ref_score_dock', 'better_than_ref_dock'))}
+
+    def summary(self, frame=-1):
+        n = self.n_included[frame]
+        out = {}
+        for which, tag in (('in', ''), ('min', '_min'), ('dock', '_dock')):
+            out.update({f'mean_score{tag}': self.mean_score(frame, which), f'median_score{tag}': self.median_score(frame, which),
+                        f'best_score{tag}': self.best_score(frame, which)})
+        return dict(out, mean_gain_dock=self.mean_gain(frame), share_negative_dock=self.share_negative(frame),
+                    mean_rmsd_dock=self._mean(self.sum_rmsd[frame], n), chains_agree=self._mean(self.sum_agree[frame], n),
+                    mean_evals_dock=self._mean(self.sum_evals[frame], n), **self.reference(frame))
+
+
+def sample_dock(result, eval_step=-1, include='all', reference_ligand=None, weights=SCORE_WEIGHTS, rot_weight=SCORE_ROT_WEIGHT,
+                n_chains=DOCK_CHAINS, n_rounds=DOCK_ROUNDS, seed=0, max_steps=RELAX_MAX_STEPS, max_shift=RELAX_MAX_SHIFT, cutoff=SCORE_CUTOFF,
+                atom_enc_mode='add_aromatic', device='cuda'):
+    """The docking search of the samples of one pocket at ONE frame (``result``, ``include`` and the packing as ``sample_relax``;
+    ``eval_step='all'`` raises ValueError: one launch would hold S B n_chains long-lived workgroups): the mean, the median and the best
+    score of the input poses, after the relaxation alone and after the search (the reference's ``vina_score`` / ``vina_min`` /
+    ``vina_dock``, on this typing), the mean gain over the relaxation, the share of negative docked scores, the mean RMSD from the input,
+    the mean share of chains that agree with the winner (a convergence indicator), the mean evaluations; with ``reference_ligand``
+    ``(pos [n, 3], v [n])``, run through the same kernel, its docked score and the share of samples whose docked score is below it.  It
+    is a rigid-body global search under this project's heuristic score, not AutoDock Vina's ``dock``: three translations and three
+    rotations, no torsions (``pocket_dock``).  A result without a pocket is refused.  Returns a ``DockReport``."""
+    _single_frame(eval_step)
+    return SamplePack(result, eval_step, atom_enc_mode, device).dock(_pocket_data(result, 'dock'), include, reference_ligand, weights, n_chains,
+                                                                     n_rounds, seed, max_steps, max_shift, cutoff, rot_weight)
 
 
 # ---- solvent-accessible surface (``td_sasa_report``, csrc/sasa.hip; DESIGN.md section 3, "Solvent-accessible surface")

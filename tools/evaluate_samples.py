@@ -56,6 +56,16 @@ the cap, the mean steps and evaluations and, with the known ligand relaxed throu
 samples whose minimised score is below its minimised score.  It is a local optimisation under this project's heuristic score, not
 AutoDock Vina's ``minimize``, and it is rigid-body only: three translations and three rotations, no torsions; no global search
 (``vina_dock``), no intramolecular term, no hydrogens.
+``--dock [--dock_chains 16] [--dock_rounds 16] [--dock_seed 0]`` adds the score after a docking search of every sample in its pocket
+(quality.sample_dock: one persistent GPU workgroup per (molecule, chain); independent Monte-Carlo chains of random rigid moves, each
+followed by ``--minimize``'s relaxation and a Metropolis rule), alongside ``--score``: the mean, the median and the best score of the
+input poses, after the relaxation alone and after the search (the reference's ``vina_score`` / ``vina_min`` / ``vina_dock``, on this
+typing), the mean gain over the relaxation, the share of negative docked scores, the mean RMSD from the input, the mean share of chains
+that agree with the winner, the mean evaluations and, with the known ligand run through the same kernel, its docked score and the share
+of samples whose docked score is below it.  The final poses only: ``--eval_step all`` is refused.  It is a rigid-body global search
+under this project's heuristic score, not
+AutoDock Vina's ``dock``: three translations and three rotations, no torsions; no intramolecular term, no hydrogens, and the search
+box is the ball of ``--max_shift`` around the input centroid.
 The fingerprint is this project's own circular one over its bond graph, not RDKit's RDKFingerprint: the numbers compare between
 runs of this tool, not with published tables.  The Jensen-Shannon distances need the reference's empirical distributions: they are
 loaded from ``utils.evaluation`` when the tool runs inside the reference repository (or with it on PYTHONPATH), or from
@@ -119,6 +129,10 @@ def pocket_sections(args):
                         rot_weight=quality.SCORE_ROT_WEIGHT)),
         ('minimize', quality.RelaxReport, (None, args.min_steps, args.max_shift, args.score_cutoff),
          lambda r: dict(score_cutoff=args.score_cutoff, max_steps=args.min_steps, max_shift=args.max_shift,
+                        weights=dict(zip(quality.SCORE_TERM_NAMES, quality.SCORE_WEIGHTS)), rot_weight=quality.SCORE_ROT_WEIGHT)),
+        ('dock', quality.DockReport, (None, args.dock_chains, args.dock_rounds, args.dock_seed, args.min_steps, args.max_shift, args.score_cutoff),
+         lambda r: dict(score_cutoff=args.score_cutoff, n_chains=args.dock_chains, n_rounds=args.dock_rounds, seed=args.dock_seed,
+                        amplitude=quality.DOCK_AMPLITUDE, temperature=quality.DOCK_TEMPERATURE, max_steps=args.min_steps, max_shift=args.max_shift,
                         weights=dict(zip(quality.SCORE_TERM_NAMES, quality.SCORE_WEIGHTS)), rot_weight=quality.SCORE_ROT_WEIGHT)))
     return [section for section in every if getattr(args, section[0])]
 
@@ -159,9 +173,15 @@ def main(argv=None):
                     "local optimisation under this project's heuristic score, not AutoDock Vina's minimize; rigid-body only: three "
                     'translations and three rotations, no torsions')
     ap.add_argument('--min_steps', type=int, default=quality.RELAX_MAX_STEPS, help='--minimize: accepted steps at most')
-    ap.add_argument('--max_shift', type=float, default=quality.RELAX_MAX_SHIFT, help='--minimize: the centre of a molecule moves at most '
+    ap.add_argument('--max_shift', type=float, default=quality.RELAX_MAX_SHIFT, help='--minimize, --dock: the centre of a molecule moves at most '
                     'this far, in Angstrom')
-    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity, --pocket, --interactions, --sasa, --score, --minimize: a known ligand, the first V2000 record of '
+    ap.add_argument('--dock', action='store_true', help="also the score after a docking search of every sample in its pocket: a rigid-body "
+                    "global search under this project's heuristic score, not AutoDock Vina's dock: three translations and three rotations, "
+                    'no torsions')
+    ap.add_argument('--dock_chains', type=int, default=quality.DOCK_CHAINS, help='--dock: independent Monte-Carlo chains per molecule, 1 .. 64')
+    ap.add_argument('--dock_rounds', type=int, default=quality.DOCK_ROUNDS, help='--dock: mutate-and-relax rounds per chain after the first, 0 .. 256')
+    ap.add_argument('--dock_seed', type=int, default=0, help='--dock: the seed of the uniforms')
+    ap.add_argument('--reference_sdf', type=str, default=None, help='--diversity, --pocket, --interactions, --sasa, --score, --minimize, --dock: a known ligand, the first V2000 record of '
                     'FILE; --geometry: known ligands, every record of FILE')
     ap.add_argument('--reference_npz', type=str, default=None)
     ap.add_argument('--device', type=str, default='cuda')
@@ -212,9 +232,9 @@ def main(argv=None):
                 side = side or quality.PocketSide(result['data'], args.device)
                 against_pocket[flag].append(getattr(pack, METHODS.get(flag, flag))(side, graph_include, reference_ligand, *extra))
             except ValueError as e:
-                if flag != 'sasa':
+                if flag not in ('sasa', 'dock'):
                     raise
-                raise SystemExit(f'--sasa: {e}')
+                raise SystemExit(f'--{flag}: {e}')
         reports.append(pack.quality(args.include, reference))
     rep = quality.QualityReport.merged(reports)
     print(f'Evaluate done! {rep.n_samples} samples in total.')

@@ -2,7 +2,7 @@
 
     python tools/export_sdf.py --sample_path DIR --out DIR [--eval_step -1] [--only-complete] [--largest-fragment] [--ring-aromatic]
                                 [--unique] [--clash-free] [--pocket-clash-free] [--min-hbonds N]
-                                [--min-buried-share X] [--max-score X] [--sort-by-score] [--relaxed]
+                                [--min-buried-share X] [--max-score X] [--sort-by-score] [--relaxed | --docked]
 
 Reads the ``result_{i}.pt`` files a sampling driver wrote (sorted as tools/evaluate_samples.py sorts them), takes the frame
 ``--eval_step`` of every sample (default -1: the final poses), builds the bond graph on the GPU (quality.bond_graph: bonds from the
@@ -36,6 +36,10 @@ AutoDock Vina's number; DESIGN.md section 3, "Docking-style score"); it combines
 section 3, "Pose relaxation") and a ``> <score_min>`` data item next to ``> <score>``, the score before.  The bonds, the filters and the
 order are those of the sampled poses: a rigid motion changes no bond.  It is a local optimisation under this project's heuristic score,
 not AutoDock Vina's ``minimize``, and it is rigid-body only: three translations and three rotations, no torsions.
+``--docked [--dock_chains 16] [--dock_rounds 16] [--dock_seed 0]`` writes the coordinates after a docking search of every sample in the
+file's pocket instead (quality.pocket_dock; DESIGN.md section 3, "Docking search") and ``> <score_min>`` and ``> <score_dock>`` data items
+next to ``> <score>``: the score after the relaxation alone and after the search.  It is a rigid-body global search under this project's
+heuristic score, not AutoDock Vina's ``dock``: three translations and three rotations, no torsions.
 Prints one line per file and returns the counts.
 """
 from __future__ import annotations
@@ -78,8 +82,16 @@ def main(argv=None):
     ap.add_argument('--relaxed', action='store_true', help="the coordinates after a rigid-body relaxation in the file's pocket, with a "
                     "score_min data item: a local optimisation under this project's heuristic score, not AutoDock Vina's minimize; "
                     'rigid-body only: three translations and three rotations, no torsions')
+    ap.add_argument('--docked', action='store_true', help="the coordinates after a docking search in the file's pocket, with score_min and "
+                    "score_dock data items: a rigid-body global search under this project's heuristic score, not AutoDock Vina's dock: "
+                    'three translations and three rotations, no torsions')
+    ap.add_argument('--dock_chains', type=int, default=quality.DOCK_CHAINS, help='--docked: independent Monte-Carlo chains per molecule')
+    ap.add_argument('--dock_rounds', type=int, default=quality.DOCK_ROUNDS, help='--docked: mutate-and-relax rounds per chain after the first')
+    ap.add_argument('--dock_seed', type=int, default=0, help='--docked: the seed of the uniforms')
     ap.add_argument('--device', type=str, default='cuda')
     args = ap.parse_args(argv)
+    if args.relaxed and args.docked:
+        raise SystemExit('--relaxed and --docked both write coordinates: choose one')
     if args.min_buried_share is not None and not 0.0 <= args.min_buried_share <= 1.0:
         raise SystemExit(f'--min-buried-share is a share, 0 .. 1 (got {args.min_buried_share})')
     files = result_files(args.sample_path, args.eval_num_examples)
@@ -138,6 +150,12 @@ def main(argv=None):
             relaxed = quality.pocket_relax(*quality.pocket_of(result['data']), pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode,
                                            device=args.device)
             score = relaxed.score_in[0] if score is None else score
+        if args.docked:
+            if not isinstance(result, dict) or result.get('data') is None:
+                raise SystemExit(f'{name} carries no pocket (no data): --docked needs the files of a sampling driver')
+            relaxed = quality.pocket_dock(*quality.pocket_of(result['data']), pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode,
+                                          n_chains=args.dock_chains, n_rounds=args.dock_rounds, seed=args.dock_seed, device=args.device)
+            score = relaxed.score_in[0] if score is None else score
         if args.unique:
             fp = quality.fingerprints(pos, v, ligand_ptr=ptr, atom_enc_mode=args.atom_enc_mode, device=args.device)
             first = fp.similarity(include=None if chosen is None else chosen[None])['first_equal'][0].cpu().numpy()
@@ -149,7 +167,10 @@ def main(argv=None):
             for m in mols:
                 m['properties']['score'] = f'{of(m):.4f}'
                 if relaxed is not None:
-                    m['properties']['score_min'] = f"{float(relaxed.score[0][int(m['name'].rsplit('_', 1)[1])]):.4f}"
+                    after = relaxed.score_min if args.docked else relaxed.score
+                    m['properties']['score_min'] = f"{float(after[0][int(m['name'].rsplit('_', 1)[1])]):.4f}"
+                if args.docked:
+                    m['properties']['score_dock'] = f"{float(relaxed.score[0][int(m['name'].rsplit('_', 1)[1])]):.4f}"
             if args.sort_by_score:
                 mols.sort(key=of)
         stem = os.path.basename(name)[:-3]

@@ -66,6 +66,14 @@ ABI_VERSION = 5
 
 # every symbol include/targetdiff_hip.h declares: (restype, argtypes)
 _P = c_void_p
+# td_score_report, td_score_minimize and td_score_dock by side.  _SCORE_IN: the pack with the class table and class_aromatic, the pocket with
+# N_p and n_kinds, the two cutoffs and rsum, the rotor inputs
+_SCORE_IN = ([_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8)] + [_P, _P, _P, _P, c_int64, c_int32] +
+             [ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double)] + [_P, c_int64, _P])
+_RELAX_IN = [POINTER(ctypes.c_double), c_int32, c_int32, ctypes.c_double]   # weights, max_steps, max_evals, max_shift
+_RELAX_OUT = [_P] * 11                                                      # RELAX_KEYS
+_DOCK_IN = [c_int32, c_int32, ctypes.c_double, ctypes.c_double, _P]         # n_chains, n_rounds, amplitude, temperature, draws
+_DOCK_OUT = [_P] * 5                                                        # DOCK_KEYS beyond RELAX_KEYS
 SIGNATURES = {
     'td_abi_version': (c_int32, []),
     'td_last_error': (c_char_p, []),
@@ -106,15 +114,9 @@ SIGNATURES = {
     'td_interaction_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, _P, _P, _P, c_int64, c_int32,
                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                         _P, _P, _P, _P, _P]),
-    'td_score_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), _P, _P, _P, _P, c_int64,
-                                  c_int32, ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double), _P, c_int64, _P, _P, _P, _P, _P, _P]),
-    'td_score_minimize': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), _P, _P, _P, _P, c_int64,
-                                    c_int32, ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double), _P, c_int64, _P, POINTER(ctypes.c_double),
-                                    c_int32, c_int32, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    'td_score_dock': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, POINTER(ctypes.c_uint8), _P, _P, _P, _P, c_int64,
-                                c_int32, ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double), _P, c_int64, _P, POINTER(ctypes.c_double),
-                                c_int32, c_int32, ctypes.c_double, c_int32, c_int32, ctypes.c_double, ctypes.c_double, _P,
-                                _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'td_score_report': (c_int32, _SCORE_IN + [_P] * 4 + [_P]),              # protein_role_out, terms, n_pairs, n_rot; the stream
+    'td_score_minimize': (c_int32, _SCORE_IN + _RELAX_IN + _RELAX_OUT + [_P]),
+    'td_score_dock': (c_int32, _SCORE_IN + _RELAX_IN + _DOCK_IN + _RELAX_OUT + _DOCK_OUT + [_P]),
     'td_sasa_report': (c_int32, [_P, _P, _P, c_int64, c_int64, c_int64, POINTER(c_int32), c_int32, _P, _P, _P, c_int64, POINTER(ctypes.c_double),
                                  POINTER(ctypes.c_double), _P, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'td_posterior_step_guided': (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -1362,6 +1364,15 @@ def _score_inputs(pos, protein_pos, protein_elem, protein_kind, protein_role, n_
     return Np, np.ascontiguousarray(rs.reshape(-1)), 0 if bond_ring is None else int(bond_ring.numel())
 
 
+def _score_args(pack, aro, protein_pos, protein_elem, protein_kind, protein_role, Np, n_kinds, cutoff, hetero_cutoff, rs, bond_ptr, nb, bond_ring):
+    """The arguments td_score_report, td_score_minimize and td_score_dock begin with (``_SCORE_IN``); ``pack`` of _pack_args, ``rs`` and
+    ``nb`` of _score_inputs.  ``rs`` is the caller's: it outlives the call."""
+    return (*pack, _aromatic_arg(aro), _ptr(protein_pos, torch.float32, 'protein_pos'), _ptr(protein_elem, torch.int32, 'protein_elem'),
+            _ptr(protein_kind, torch.int32, 'protein_kind'), _ptr(protein_role, torch.int32, 'protein_role'), Np, int(n_kinds), float(cutoff),
+            float(hetero_cutoff), rs.ctypes.data_as(POINTER(ctypes.c_double)), _ptr(bond_ptr, torch.int64, 'bond_ptr'), nb,
+            _ptr(bond_ring, torch.int16, 'bond_ring') if nb else None)
+
+
 def score_report(pos, v, ligand_ptr, class_z, class_aromatic, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, rsum,
                  cutoff=8.0, hetero_cutoff=1.75, bond_ptr=None, bond_ring=None, check=True):
     """The five unweighted term sums of a Vina-style pair score of S frames of B molecules with one pocket, and their rotatable bonds
@@ -1379,17 +1390,14 @@ def score_report(pos, v, ligand_ptr, class_z, class_aromatic, protein_pos, prote
     Np, rs, nb = _score_inputs(pos, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, rsum, cutoff, hetero_cutoff, bond_ptr,
                                bond_ring, S, B, check)
     lib = load_library()
-    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
+    shared = _score_args(_pack_args(pos, v, ligand_ptr, S, Nl, B, cz), aro, protein_pos, protein_elem, protein_kind, protein_role, Np, n_kinds,
+                         cutoff, hetero_cutoff, rs, bond_ptr, nb, bond_ring)
     dev = pos.device
     i32, _, i64 = _allocators(dev)
     out = dict(protein_role=i32(Np), terms=i64(S, B, SCORE_TERMS), n_pairs=i32(S, B), n_rot=i32(S, B) if bond_ptr is not None else None)
     with _on(dev):
-        _check(lib.td_score_report(*pack, _aromatic_arg(aro), _ptr(protein_pos, torch.float32, 'protein_pos'),
-                                   _ptr(protein_elem, torch.int32, 'protein_elem'), _ptr(protein_kind, torch.int32, 'protein_kind'),
-                                   _ptr(protein_role, torch.int32, 'protein_role'), Np, int(n_kinds), float(cutoff), float(hetero_cutoff),
-                                   rs.ctypes.data_as(POINTER(ctypes.c_double)), _ptr(bond_ptr, torch.int64, 'bond_ptr'), nb,
-                                   _ptr(bond_ring, torch.int16, 'bond_ring') if nb else None, _ptr(out['protein_role']), _ptr(out['terms']),
-                                   _ptr(out['n_pairs']), _ptr(out['n_rot']), _stream(dev)), 'td_score_report')
+        _check(lib.td_score_report(*shared, _ptr(out['protein_role']), _ptr(out['terms']), _ptr(out['n_pairs']), _ptr(out['n_rot']),
+                                   _stream(dev)), 'td_score_report')
     return out
 
 
@@ -1415,6 +1423,24 @@ def _relax_inputs(weights, max_steps, max_evals, max_shift):
     return np.ascontiguousarray(w), int(max_steps), int(max_evals), float(max_shift)
 
 
+def _relax_outputs(pos, S, B, Np, rotors):
+    """the outputs ``RELAX_KEYS`` name, not initialised, on the device of ``pos``; n_rot only with the rotor inputs"""
+    dev = pos.device
+    i32, _, i64 = _allocators(dev)
+    return dict(protein_role=i32(Np), n_rot=i32(S, B) if rotors else None, pos=torch.empty_like(pos), terms_in=i64(S, B, SCORE_TERMS),
+                terms=i64(S, B, SCORE_TERMS), n_pairs=i32(S, B), n_steps=i32(S, B), n_evals=i32(S, B), status=i32(S, B),
+                transform=torch.empty(S, B, 7, dtype=torch.float64, device=dev), grad_in=i64(S, B, 6))
+
+
+def _call_with_capacity(lib, name, args, list_capacity):
+    """call the entry point ``name``, or with a ``list_capacity`` its td_internal_*_capacity twin: the tests' door to the walk in global memory"""
+    if list_capacity is None:
+        return _check(getattr(lib, name)(*args), name)
+    fn = getattr(lib, f'td_internal_{name[len("td_"):]}_capacity')
+    fn.restype, fn.argtypes = c_int32, SIGNATURES[name][1] + [c_int32]
+    _check(fn(*args, int(list_capacity)), name)
+
+
 def score_minimize(pos, v, ligand_ptr, class_z, class_aromatic, protein_pos, protein_elem, protein_kind, protein_role, n_kinds, rsum, weights,
                    cutoff=8.0, hetero_cutoff=1.75, bond_ptr=None, bond_ring=None, max_steps=RELAX_MAX_STEPS, max_evals=None,
                    max_shift=RELAX_MAX_SHIFT, check=True, _list_capacity=None):
@@ -1435,24 +1461,14 @@ def score_minimize(pos, v, ligand_ptr, class_z, class_aromatic, protein_pos, pro
                                bond_ring, S, B, check)
     w, max_steps, max_evals, max_shift = _relax_inputs(weights, max_steps, max_evals, max_shift)
     lib = load_library()
-    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
+    shared = _score_args(_pack_args(pos, v, ligand_ptr, S, Nl, B, cz), aro, protein_pos, protein_elem, protein_kind, protein_role, Np, n_kinds,
+                         cutoff, hetero_cutoff, rs, bond_ptr, nb, bond_ring)
     dev = pos.device
-    i32, _, i64 = _allocators(dev)
-    out = dict(protein_role=i32(Np), n_rot=i32(S, B) if bond_ptr is not None else None, pos=torch.empty_like(pos),
-               terms_in=i64(S, B, SCORE_TERMS), terms=i64(S, B, SCORE_TERMS), n_pairs=i32(S, B), n_steps=i32(S, B), n_evals=i32(S, B),
-               status=i32(S, B), transform=torch.empty(S, B, 7, dtype=torch.float64, device=dev), grad_in=i64(S, B, 6))
-    args = (*pack, _aromatic_arg(aro), _ptr(protein_pos, torch.float32, 'protein_pos'), _ptr(protein_elem, torch.int32, 'protein_elem'),
-            _ptr(protein_kind, torch.int32, 'protein_kind'), _ptr(protein_role, torch.int32, 'protein_role'), Np, int(n_kinds), float(cutoff),
-            float(hetero_cutoff), rs.ctypes.data_as(POINTER(ctypes.c_double)), _ptr(bond_ptr, torch.int64, 'bond_ptr'), nb,
-            _ptr(bond_ring, torch.int16, 'bond_ring') if nb else None, w.ctypes.data_as(POINTER(ctypes.c_double)), max_steps, max_evals,
-            max_shift, *(_ptr(out[k]) for k in RELAX_KEYS), _stream(dev))
+    out = _relax_outputs(pos, S, B, Np, bond_ptr is not None)
+    args = (*shared, w.ctypes.data_as(POINTER(ctypes.c_double)), max_steps, max_evals, max_shift, *(_ptr(out[k]) for k in RELAX_KEYS),
+            _stream(dev))
     with _on(dev):
-        if _list_capacity is None:
-            _check(lib.td_score_minimize(*args), 'td_score_minimize')
-        else:                                                                    # the tests' door to the walk in global memory
-            fn = lib.td_internal_score_minimize_capacity
-            fn.restype, fn.argtypes = c_int32, SIGNATURES['td_score_minimize'][1] + [c_int32]
-            _check(fn(*args, int(_list_capacity)), 'td_score_minimize')
+        _call_with_capacity(lib, 'td_score_minimize', args, _list_capacity)
     return out
 
 
@@ -1509,26 +1525,15 @@ def score_dock(pos, v, ligand_ptr, class_z, class_aromatic, protein_pos, protein
     dev = pos.device
     C, n_rounds, amplitude, temperature, draws = _dock_inputs(n_chains, n_rounds, amplitude, temperature, seed, draws, S, B, dev, check)
     lib = load_library()
-    pack = _pack_args(pos, v, ligand_ptr, S, Nl, B, cz)
+    shared = _score_args(_pack_args(pos, v, ligand_ptr, S, Nl, B, cz), aro, protein_pos, protein_elem, protein_kind, protein_role, Np, n_kinds,
+                         cutoff, hetero_cutoff, rs, bond_ptr, nb, bond_ring)
     i32, _, i64 = _allocators(dev)
-    out = dict(protein_role=i32(Np), n_rot=i32(S, B) if bond_ptr is not None else None, pos=torch.empty_like(pos),
-               terms_in=i64(S, B, SCORE_TERMS), terms=i64(S, B, SCORE_TERMS), n_pairs=i32(S, B), n_steps=i32(S, B), n_evals=i32(S, B),
-               status=i32(S, B), transform=torch.empty(S, B, 7, dtype=torch.float64, device=dev), grad_in=i64(S, B, 6),
-               best_chain=i32(S, B), chain_terms=i64(S, B, C, SCORE_TERMS), chain_transform=torch.empty(S, B, C, 7, dtype=torch.float64, device=dev),
-               chain_accepts=i32(S, B, C), chain_evals=i32(S, B, C))
-    args = (*pack, _aromatic_arg(aro), _ptr(protein_pos, torch.float32, 'protein_pos'), _ptr(protein_elem, torch.int32, 'protein_elem'),
-            _ptr(protein_kind, torch.int32, 'protein_kind'), _ptr(protein_role, torch.int32, 'protein_role'), Np, int(n_kinds), float(cutoff),
-            float(hetero_cutoff), rs.ctypes.data_as(POINTER(ctypes.c_double)), _ptr(bond_ptr, torch.int64, 'bond_ptr'), nb,
-            _ptr(bond_ring, torch.int16, 'bond_ring') if nb else None, w.ctypes.data_as(POINTER(ctypes.c_double)), max_steps, max_evals,
-            max_shift, C, n_rounds, amplitude, temperature, _ptr(draws, torch.float64, 'draws'), *(_ptr(out[k]) for k in DOCK_KEYS),
-            _stream(dev))
+    out = dict(_relax_outputs(pos, S, B, Np, bond_ptr is not None), best_chain=i32(S, B), chain_terms=i64(S, B, C, SCORE_TERMS),
+               chain_transform=torch.empty(S, B, C, 7, dtype=torch.float64, device=dev), chain_accepts=i32(S, B, C), chain_evals=i32(S, B, C))
+    args = (*shared, w.ctypes.data_as(POINTER(ctypes.c_double)), max_steps, max_evals, max_shift, C, n_rounds, amplitude, temperature,
+            _ptr(draws, torch.float64, 'draws'), *(_ptr(out[k]) for k in DOCK_KEYS), _stream(dev))
     with _on(dev):
-        if _list_capacity is None:
-            _check(lib.td_score_dock(*args), 'td_score_dock')
-        else:                                                                    # the tests' door to the walk in global memory
-            fn = lib.td_internal_score_dock_capacity
-            fn.restype, fn.argtypes = c_int32, SIGNATURES['td_score_dock'][1] + [c_int32]
-            _check(fn(*args, int(_list_capacity)), 'td_score_dock')
+        _call_with_capacity(lib, 'td_score_dock', args, _list_capacity)
     out['draws'] = draws
     return out
 

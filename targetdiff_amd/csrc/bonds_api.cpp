@@ -316,57 +316,126 @@ extern "C" int td_interaction_report(const float *d_pos, const int64_t *d_v, con
 }
 
 namespace {
-// What td_score_report and td_score_minimize share: the pack, the pocket, the cutoffs, the radius sums and the rotor inputs checked and
-// filled into g, and the protein roles resolved on the stream.  The outputs of each (beyond d_protein_role_out and d_n_rot) are its own.
-int score_side(const char *who, TdScoreArgs &g, const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l,
-               int64_t B, const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
-               const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds,
-               double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds,
-               const uint16_t *d_bond_ring, int32_t *d_protein_role_out, int32_t *d_n_rot, hipStream_t stream) {
-    if (const int rc = bond_pack(who, g.b, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, n_bonds)) return rc;
-    if (N_p < 0 || N_p > 0x7fffffff / TD_BOND_MAX_ATOMS) {                      // a molecule's pairs are counted in an int32
-        td_set_error("%s: bad argument (N_p = %lld; 512 N_p must fit 31 bits)", who, (long long)N_p);
+// The arguments of td_score_report, td_score_minimize and td_score_dock by side, the members in the order of the C argument lists: an
+// exported symbol brace-initialises them from its flat list, once, and everything below it passes the structs.  ScoreSide: the inputs the
+// three share (the pack, the aromatic flags, the pocket, the cutoffs, the radius sums, the rotor inputs) and the two outputs score_side
+// fills; RelaxSide: the optimiser's; DockSide: the search's.
+struct ScoreSide {
+    const float *d_pos; const int64_t *d_v; const int32_t *d_ligand_ptr; int64_t S, N_l, B; const int32_t *class_atomic_number; int32_t K;
+    const uint8_t *class_aromatic; const float *d_protein_pos; const int32_t *d_protein_elem, *d_protein_kind, *d_protein_role; int64_t N_p;
+    int32_t n_kinds; double cutoff, hetero_cutoff; const double *rsum; const int64_t *d_bond_ptr; int64_t n_bonds; const uint16_t *d_bond_ring;
+    int32_t *d_protein_role_out, *d_n_rot;
+};
+struct RelaxSide {
+    const double *weights; int32_t max_steps, max_evals; double max_shift; int32_t list_capacity; float *d_pos_out; int64_t *d_terms_in;
+    int64_t *d_terms_out; int32_t *d_n_pairs_out, *d_n_steps, *d_n_evals, *d_status; double *d_transform; int64_t *d_grad_in;
+};
+struct DockSide {
+    int32_t n_chains, n_rounds; double amplitude, temperature; const double *d_draws; int32_t *d_best_chain; int64_t *d_chain_terms;
+    double *d_chain_transform; int32_t *d_chain_accepts, *d_chain_evals;
+};
+
+// What the three entry points share: the pack, the pocket, the cutoffs, the radius sums and the rotor inputs checked and filled into g,
+// and the protein roles resolved on the stream.  The outputs of each (beyond d_protein_role_out and d_n_rot) are its own.
+int score_side(const char *who, TdScoreArgs &g, const ScoreSide &in, hipStream_t stream) {
+    if (const int rc = bond_pack(who, g.b, in.d_pos, in.d_v, in.d_ligand_ptr, in.S, in.N_l, in.B, in.class_atomic_number, in.K,
+                                 in.class_aromatic, in.n_bonds)) return rc;
+    if (in.N_p < 0 || in.N_p > 0x7fffffff / TD_BOND_MAX_ATOMS) {                // a molecule's pairs are counted in an int32
+        td_set_error("%s: bad argument (N_p = %lld; 512 N_p must fit 31 bits)", who, (long long)in.N_p);
         return TD_EINVAL;
     }
-    if (n_kinds < 1 || n_kinds > TD_POCKET_MAX_KINDS) {
-        td_set_error("%s: 1 .. %d kinds of protein atoms (got %d)", who, TD_POCKET_MAX_KINDS, (int)n_kinds);
+    if (in.n_kinds < 1 || in.n_kinds > TD_POCKET_MAX_KINDS) {
+        td_set_error("%s: 1 .. %d kinds of protein atoms (got %d)", who, TD_POCKET_MAX_KINDS, (int)in.n_kinds);
         return TD_EINVAL;
     }
-    for (const double c : {cutoff, hetero_cutoff})
+    for (const double c : {in.cutoff, in.hetero_cutoff})
         if (!std::isfinite(c) || !(c > 0.0)) {
             td_set_error("%s: the cutoff and the hetero cutoff must be finite and > 0", who);
             return TD_EINVAL;
         }
-    if (!rsum) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
+    if (!in.rsum) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
     for (int k = 0; k < 8 * TD_POCKET_ELEMENTS; ++k) {
-        if (!std::isfinite(rsum[k]) || !(rsum[k] > 0.0) || !(rsum[k] <= 6.0)) {
+        if (!std::isfinite(in.rsum[k]) || !(in.rsum[k] > 0.0) || !(in.rsum[k] <= 6.0)) {
             td_set_error("%s: every radius sum must be in (0, 6] (entry %d)", who, k);
             return TD_EINVAL;
         }
-        g.rsum[k] = rsum[k];
+        g.rsum[k] = in.rsum[k];
     }
     // the rotor inputs come together: the offsets of td_bond_graph, the length of the list and, where it has entries, the ring sizes
-    const bool rotors = d_bond_ptr != nullptr;
-    if ((!rotors && (d_bond_ring || n_bonds != 0)) || (rotors && n_bonds > 0 && !d_bond_ring)) {
+    const bool rotors = in.d_bond_ptr != nullptr;
+    if ((!rotors && (in.d_bond_ring || in.n_bonds != 0)) || (rotors && in.n_bonds > 0 && !in.d_bond_ring)) {
         td_set_error("%s: d_bond_ptr, n_bonds and d_bond_ring are given together or not at all", who);
         return TD_EINVAL;
     }
-    if ((N_p > 0 && (!d_protein_pos || !d_protein_elem || !d_protein_kind || !d_protein_role || !d_protein_role_out)) ||
-        (S > 0 && B > 0 && rotors && !d_n_rot)) {
+    if ((in.N_p > 0 && (!in.d_protein_pos || !in.d_protein_elem || !in.d_protein_kind || !in.d_protein_role || !in.d_protein_role_out)) ||
+        (in.S > 0 && in.B > 0 && rotors && !in.d_n_rot)) {
         td_set_error("%s: null pointer", who);
         return TD_EINVAL;
     }
     TdInteractionArgs roles;
     TdProteinSide &p = roles.p;
-    p.ppos = d_protein_pos; p.pelem = d_protein_elem; p.pkind = d_protein_kind;
-    p.Np = (int)N_p; p.W = (int)((N_p + 63) / 64); p.n_kinds = n_kinds;
-    roles.prole = d_protein_role; roles.hetero_cutoff = hetero_cutoff; roles.role_out = d_protein_role_out;
+    p.ppos = in.d_protein_pos; p.pelem = in.d_protein_elem; p.pkind = in.d_protein_kind;
+    p.Np = (int)in.N_p; p.W = (int)((in.N_p + 63) / 64); p.n_kinds = in.n_kinds;
+    roles.prole = in.d_protein_role; roles.hetero_cutoff = in.hetero_cutoff; roles.role_out = in.d_protein_role_out;
     if (const int rc = td_launch_protein_roles(roles, stream)) return rc;
     g.p = p;
-    g.role = d_protein_role_out;
-    g.cutoff = cutoff;
-    g.b.bond_ptr = const_cast<int64_t *>(d_bond_ptr); g.b.bond_ring = const_cast<uint16_t *>(d_bond_ring);
-    g.n_rot = d_n_rot;
+    g.role = in.d_protein_role_out;
+    g.cutoff = in.cutoff;
+    g.b.bond_ptr = const_cast<int64_t *>(in.d_bond_ptr); g.b.bond_ring = const_cast<uint16_t *>(in.d_bond_ring);
+    g.n_rot = in.d_n_rot;
+    return TD_OK;
+}
+
+// What td_score_minimize and td_score_dock share: the optimiser's arguments and outputs checked and filled into g, then score_side.
+int relax_side(const char *who, TdRelaxArgs &g, const ScoreSide &in, const RelaxSide &rx, hipStream_t stream) {
+    if (rx.max_steps < 0 || rx.max_evals < 1 || rx.list_capacity < 0) {
+        td_set_error("%s: bad argument (max_steps = %d must be >= 0, max_evals = %d must be >= 1)", who, (int)rx.max_steps, (int)rx.max_evals);
+        return TD_EINVAL;
+    }
+    if (!std::isfinite(rx.max_shift) || !(rx.max_shift > 0.0)) {
+        td_set_error("%s: max_shift must be finite and > 0", who);
+        return TD_EINVAL;
+    }
+    if (!rx.weights) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
+    for (int k = 0; k < TD_SCORE_TERMS; ++k) {
+        if (!std::isfinite(rx.weights[k])) { td_set_error("%s: the weights must be finite (weight %d)", who, k); return TD_EINVAL; }
+        g.w[k] = rx.weights[k];
+    }
+    if ((in.S > 0 && in.N_l > 0 && (!rx.d_pos_out || rx.d_pos_out == in.d_pos)) ||
+        (in.S > 0 && in.B > 0 && (!rx.d_terms_in || !rx.d_terms_out || !rx.d_n_pairs_out || !rx.d_n_steps || !rx.d_n_evals || !rx.d_status ||
+                                  !rx.d_transform || !rx.d_grad_in))) {
+        td_set_error("%s: null pointer (d_pos_out may not be d_pos)", who);
+        return TD_EINVAL;
+    }
+    if (const int rc = score_side(who, g.sc, in, stream)) return rc;
+    g.max_steps = rx.max_steps; g.max_evals = rx.max_evals; g.max_shift = rx.max_shift; g.list_capacity = rx.list_capacity;
+    g.pos_out = rx.d_pos_out;
+    g.terms_in = reinterpret_cast<long long *>(rx.d_terms_in); g.terms_out = reinterpret_cast<long long *>(rx.d_terms_out);
+    g.n_pairs_out = rx.d_n_pairs_out; g.n_steps = rx.d_n_steps; g.n_evals = rx.d_n_evals; g.status = rx.d_status;
+    g.transform = rx.d_transform; g.grad_in = reinterpret_cast<long long *>(rx.d_grad_in);
+    return TD_OK;
+}
+
+// td_score_dock's own: the search's arguments and outputs checked and filled into d, then relax_side.
+int dock_side(const char *who, TdDockArgs &d, const ScoreSide &in, const RelaxSide &rx, const DockSide &dk, hipStream_t stream) {
+    if (dk.n_chains < 1 || dk.n_chains > TD_DOCK_MAX_CHAINS || dk.n_rounds < 0 || dk.n_rounds > TD_DOCK_MAX_ROUNDS) {
+        td_set_error("%s: bad argument (n_chains = %d must be in 1 .. %d, n_rounds = %d in 0 .. %d)", who, (int)dk.n_chains, TD_DOCK_MAX_CHAINS,
+                     (int)dk.n_rounds, TD_DOCK_MAX_ROUNDS);
+        return TD_EINVAL;
+    }
+    if (!std::isfinite(dk.amplitude) || !(dk.amplitude > 0.0) || !std::isfinite(dk.temperature) || !(dk.temperature > 0.0)) {
+        td_set_error("%s: amplitude and temperature must be finite and > 0", who);
+        return TD_EINVAL;
+    }
+    if (in.S > 0 && in.B > 0 &&
+        (!dk.d_draws || !dk.d_best_chain || !dk.d_chain_terms || !dk.d_chain_transform || !dk.d_chain_accepts || !dk.d_chain_evals)) {
+        td_set_error("%s: null pointer", who);
+        return TD_EINVAL;
+    }
+    if (const int rc = relax_side(who, d.rx, in, rx, stream)) return rc;
+    d.n_chains = dk.n_chains; d.n_rounds = dk.n_rounds; d.amplitude = dk.amplitude; d.temperature = dk.temperature; d.draws = dk.d_draws;
+    d.best_chain = dk.d_best_chain; d.chain_terms = reinterpret_cast<long long *>(dk.d_chain_terms); d.chain_transform = dk.d_chain_transform;
+    d.chain_accepts = dk.d_chain_accepts; d.chain_evals = dk.d_chain_evals;
     return TD_OK;
 }
 }  // namespace
@@ -378,126 +447,14 @@ extern "C" int td_score_report(const float *d_pos, const int64_t *d_v, const int
                                int64_t n_bonds, const uint16_t *d_bond_ring, int32_t *d_protein_role_out, int64_t *d_terms,
                                int32_t *d_n_pairs, int32_t *d_n_rot, void *stream) {
     const char *who = "td_score_report";
+    const ScoreSide in{d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos, d_protein_elem,
+                       d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring,
+                       d_protein_role_out, d_n_rot};
     if (S > 0 && B > 0 && (!d_terms || !d_n_pairs)) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
     TdScoreArgs g;
-    if (const int rc = score_side(who, g, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos,
-                                  d_protein_elem, d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr,
-                                  n_bonds, d_bond_ring, d_protein_role_out, d_n_rot, static_cast<hipStream_t>(stream)))
-        return rc;
+    if (const int rc = score_side(who, g, in, static_cast<hipStream_t>(stream))) return rc;
     g.terms = reinterpret_cast<long long *>(d_terms); g.n_pairs = d_n_pairs;
     return td_launch_score_report(g, static_cast<hipStream_t>(stream));
-}
-
-namespace {
-// What td_score_minimize and td_score_dock share: the optimiser's arguments and outputs checked and filled into g, then score_side.
-int relax_side(const char *who, TdRelaxArgs &g, const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l,
-               int64_t B, const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
-               const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds,
-               double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds,
-               const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals, double max_shift,
-               int32_t list_capacity, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in,
-               int64_t *d_terms_out, int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status,
-               double *d_transform, int64_t *d_grad_in, void *stream) {
-    if (max_steps < 0 || max_evals < 1 || list_capacity < 0) {
-        td_set_error("%s: bad argument (max_steps = %d must be >= 0, max_evals = %d must be >= 1)", who, (int)max_steps, (int)max_evals);
-        return TD_EINVAL;
-    }
-    if (!std::isfinite(max_shift) || !(max_shift > 0.0)) {
-        td_set_error("%s: max_shift must be finite and > 0", who);
-        return TD_EINVAL;
-    }
-    if (!weights) { td_set_error("%s: null pointer", who); return TD_EINVAL; }
-    for (int k = 0; k < TD_SCORE_TERMS; ++k) {
-        if (!std::isfinite(weights[k])) { td_set_error("%s: the weights must be finite (weight %d)", who, k); return TD_EINVAL; }
-        g.w[k] = weights[k];
-    }
-    if ((S > 0 && N_l > 0 && (!d_pos_out || d_pos_out == d_pos)) ||
-        (S > 0 && B > 0 && (!d_terms_in || !d_terms_out || !d_n_pairs_out || !d_n_steps || !d_n_evals || !d_status || !d_transform || !d_grad_in))) {
-        td_set_error("%s: null pointer (d_pos_out may not be d_pos)", who);
-        return TD_EINVAL;
-    }
-    if (const int rc = score_side(who, g.sc, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos,
-                                  d_protein_elem, d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr,
-                                  n_bonds, d_bond_ring, d_protein_role_out, d_n_rot, static_cast<hipStream_t>(stream)))
-        return rc;
-    g.max_steps = max_steps; g.max_evals = max_evals; g.max_shift = max_shift; g.list_capacity = list_capacity;
-    g.pos_out = d_pos_out;
-    g.terms_in = reinterpret_cast<long long *>(d_terms_in); g.terms_out = reinterpret_cast<long long *>(d_terms_out);
-    g.n_pairs_out = d_n_pairs_out; g.n_steps = d_n_steps; g.n_evals = d_n_evals; g.status = d_status;
-    g.transform = d_transform; g.grad_in = reinterpret_cast<long long *>(d_grad_in);
-    return TD_OK;
-}
-
-int score_minimize(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
-                   const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
-                   const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds,
-                   double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds,
-                   const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals, double max_shift,
-                   int32_t list_capacity, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in,
-                   int64_t *d_terms_out, int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status,
-                   double *d_transform, int64_t *d_grad_in, void *stream) {
-    TdRelaxArgs g;
-    if (const int rc = relax_side("td_score_minimize", g, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos,
-                                  d_protein_elem, d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr,
-                                  n_bonds, d_bond_ring, weights, max_steps, max_evals, max_shift, list_capacity, d_protein_role_out,
-                                  d_n_rot, d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform,
-                                  d_grad_in, stream))
-        return rc;
-    return td_launch_score_minimize(g, static_cast<hipStream_t>(stream));
-}
-
-int score_dock(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
-                   const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
-                   const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds,
-                   double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds,
-                   const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals, double max_shift,
-               int32_t n_chains, int32_t n_rounds, double amplitude, double temperature, const double *d_draws, int32_t list_capacity,
-               int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in, int64_t *d_terms_out,
-               int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status, double *d_transform, int64_t *d_grad_in,
-               int32_t *d_best_chain, int64_t *d_chain_terms, double *d_chain_transform, int32_t *d_chain_accepts, int32_t *d_chain_evals,
-               void *stream) {
-    const char *who = "td_score_dock";
-    if (n_chains < 1 || n_chains > TD_DOCK_MAX_CHAINS || n_rounds < 0 || n_rounds > TD_DOCK_MAX_ROUNDS) {
-        td_set_error("%s: bad argument (n_chains = %d must be in 1 .. %d, n_rounds = %d in 0 .. %d)", who, (int)n_chains, TD_DOCK_MAX_CHAINS,
-                     (int)n_rounds, TD_DOCK_MAX_ROUNDS);
-        return TD_EINVAL;
-    }
-    if (!std::isfinite(amplitude) || !(amplitude > 0.0) || !std::isfinite(temperature) || !(temperature > 0.0)) {
-        td_set_error("%s: amplitude and temperature must be finite and > 0", who);
-        return TD_EINVAL;
-    }
-    if (S > 0 && B > 0 && (!d_draws || !d_best_chain || !d_chain_terms || !d_chain_transform || !d_chain_accepts || !d_chain_evals)) {
-        td_set_error("%s: null pointer", who);
-        return TD_EINVAL;
-    }
-    TdDockArgs d;
-    if (const int rc = relax_side(who, d.rx, d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos,
-                                  d_protein_elem, d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr,
-                                  n_bonds, d_bond_ring, weights, max_steps, max_evals, max_shift, list_capacity, d_protein_role_out,
-                                  d_n_rot, d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform,
-                                  d_grad_in, stream))
-        return rc;
-    d.n_chains = n_chains; d.n_rounds = n_rounds; d.amplitude = amplitude; d.temperature = temperature; d.draws = d_draws;
-    d.best_chain = d_best_chain; d.chain_terms = reinterpret_cast<long long *>(d_chain_terms); d.chain_transform = d_chain_transform;
-    d.chain_accepts = d_chain_accepts; d.chain_evals = d_chain_evals;
-    tdapi::AsyncScratch scratch(static_cast<hipStream_t>(stream));               // given back in stream order, behind the selection
-    if (const int rc = scratch.take(&d.chain_aux, (size_t)S * (size_t)B * (size_t)n_chains * 3 * sizeof(int32_t), who)) return rc;
-    return td_launch_score_dock(d, static_cast<hipStream_t>(stream));
-}
-}  // namespace
-
-extern "C" int td_score_minimize(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
-                                 const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
-                                 const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p,
-                                 int32_t n_kinds, double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr,
-                                 int64_t n_bonds, const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals,
-                                 double max_shift, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in,
-                                 int64_t *d_terms_out, int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status,
-                                 double *d_transform, int64_t *d_grad_in, void *stream) {
-    return score_minimize(d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos, d_protein_elem,
-                          d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring, weights,
-                          max_steps, max_evals, max_shift, TD_RELAX_LIST_CAPACITY, d_protein_role_out, d_n_rot, d_pos_out, d_terms_in,
-                          d_terms_out, d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform, d_grad_in, stream);
 }
 
 // td_score_minimize with the capacity of the LDS list as an argument (0 .. TD_RELAX_LIST_CAPACITY; 0: every molecule walks the pocket in
@@ -511,26 +468,29 @@ extern "C" __attribute__((visibility("default"))) int td_internal_score_minimize
     double max_shift, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in, int64_t *d_terms_out,
     int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status, double *d_transform, int64_t *d_grad_in, void *stream,
     int32_t list_capacity) {
-    return score_minimize(d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos, d_protein_elem,
-                          d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring, weights,
-                          max_steps, max_evals, max_shift, list_capacity, d_protein_role_out, d_n_rot, d_pos_out, d_terms_in, d_terms_out,
-                          d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform, d_grad_in, stream);
+    const ScoreSide in{d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos, d_protein_elem,
+                       d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring,
+                       d_protein_role_out, d_n_rot};
+    const RelaxSide rx{weights, max_steps, max_evals, max_shift, list_capacity, d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out, d_n_steps,
+                       d_n_evals, d_status, d_transform, d_grad_in};
+    TdRelaxArgs g;
+    if (const int rc = relax_side("td_score_minimize", g, in, rx, static_cast<hipStream_t>(stream))) return rc;
+    return td_launch_score_minimize(g, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int td_score_dock(
-    const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
-    const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos, const int32_t *d_protein_elem,
-    const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds, double cutoff, double hetero_cutoff,
-    const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds, const uint16_t *d_bond_ring, const double *weights, int32_t max_steps,
-    int32_t max_evals, double max_shift, int32_t n_chains, int32_t n_rounds, double amplitude, double temperature, const double *d_draws,
-    int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in, int64_t *d_terms_out, int32_t *d_n_pairs_out,
-    int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status, double *d_transform, int64_t *d_grad_in, int32_t *d_best_chain,
-    int64_t *d_chain_terms, double *d_chain_transform, int32_t *d_chain_accepts, int32_t *d_chain_evals, void *stream) {
-    return score_dock(d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos, d_protein_elem, d_protein_kind,
-                      d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring, weights, max_steps, max_evals,
-                      max_shift, n_chains, n_rounds, amplitude, temperature, d_draws, TD_RELAX_LIST_CAPACITY, d_protein_role_out, d_n_rot,
-                      d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform, d_grad_in, d_best_chain,
-                      d_chain_terms, d_chain_transform, d_chain_accepts, d_chain_evals, stream);
+extern "C" int td_score_minimize(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+                                 const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos,
+                                 const int32_t *d_protein_elem, const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p,
+                                 int32_t n_kinds, double cutoff, double hetero_cutoff, const double *rsum, const int64_t *d_bond_ptr,
+                                 int64_t n_bonds, const uint16_t *d_bond_ring, const double *weights, int32_t max_steps, int32_t max_evals,
+                                 double max_shift, int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in,
+                                 int64_t *d_terms_out, int32_t *d_n_pairs_out, int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status,
+                                 double *d_transform, int64_t *d_grad_in, void *stream) {
+    return td_internal_score_minimize_capacity(d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos,
+                                               d_protein_elem, d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum,
+                                               d_bond_ptr, n_bonds, d_bond_ring, weights, max_steps, max_evals, max_shift, d_protein_role_out,
+                                               d_n_rot, d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out, d_n_steps, d_n_evals, d_status,
+                                               d_transform, d_grad_in, stream, TD_RELAX_LIST_CAPACITY);
 }
 
 // td_score_dock with the capacity of the LDS list as a last argument, as td_internal_score_minimize_capacity; not part of the public ABI.
@@ -543,11 +503,36 @@ extern "C" __attribute__((visibility("default"))) int td_internal_score_dock_cap
     int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in, int64_t *d_terms_out, int32_t *d_n_pairs_out,
     int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status, double *d_transform, int64_t *d_grad_in, int32_t *d_best_chain,
     int64_t *d_chain_terms, double *d_chain_transform, int32_t *d_chain_accepts, int32_t *d_chain_evals, void *stream, int32_t list_capacity) {
-    return score_dock(d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos, d_protein_elem, d_protein_kind,
-                      d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring, weights, max_steps, max_evals,
-                      max_shift, n_chains, n_rounds, amplitude, temperature, d_draws, list_capacity, d_protein_role_out, d_n_rot,
-                      d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out, d_n_steps, d_n_evals, d_status, d_transform, d_grad_in, d_best_chain,
-                      d_chain_terms, d_chain_transform, d_chain_accepts, d_chain_evals, stream);
+    const char *who = "td_score_dock";
+    const ScoreSide in{d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos, d_protein_elem,
+                       d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr, n_bonds, d_bond_ring,
+                       d_protein_role_out, d_n_rot};
+    const RelaxSide rx{weights, max_steps, max_evals, max_shift, list_capacity, d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out, d_n_steps,
+                       d_n_evals, d_status, d_transform, d_grad_in};
+    const DockSide dk{n_chains, n_rounds, amplitude, temperature, d_draws, d_best_chain, d_chain_terms, d_chain_transform, d_chain_accepts,
+                      d_chain_evals};
+    TdDockArgs d;
+    if (const int rc = dock_side(who, d, in, rx, dk, static_cast<hipStream_t>(stream))) return rc;
+    tdapi::AsyncScratch scratch(static_cast<hipStream_t>(stream));               // given back in stream order, behind the selection
+    if (const int rc = scratch.take(&d.chain_aux, (size_t)S * (size_t)B * (size_t)n_chains * 3 * sizeof(int32_t), who)) return rc;
+    return td_launch_score_dock(d, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int td_score_dock(
+    const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,
+    const int32_t *class_atomic_number, int32_t K, const uint8_t *class_aromatic, const float *d_protein_pos, const int32_t *d_protein_elem,
+    const int32_t *d_protein_kind, const int32_t *d_protein_role, int64_t N_p, int32_t n_kinds, double cutoff, double hetero_cutoff,
+    const double *rsum, const int64_t *d_bond_ptr, int64_t n_bonds, const uint16_t *d_bond_ring, const double *weights, int32_t max_steps,
+    int32_t max_evals, double max_shift, int32_t n_chains, int32_t n_rounds, double amplitude, double temperature, const double *d_draws,
+    int32_t *d_protein_role_out, int32_t *d_n_rot, float *d_pos_out, int64_t *d_terms_in, int64_t *d_terms_out, int32_t *d_n_pairs_out,
+    int32_t *d_n_steps, int32_t *d_n_evals, int32_t *d_status, double *d_transform, int64_t *d_grad_in, int32_t *d_best_chain,
+    int64_t *d_chain_terms, double *d_chain_transform, int32_t *d_chain_accepts, int32_t *d_chain_evals, void *stream) {
+    return td_internal_score_dock_capacity(d_pos, d_v, d_ligand_ptr, S, N_l, B, class_atomic_number, K, class_aromatic, d_protein_pos,
+                                           d_protein_elem, d_protein_kind, d_protein_role, N_p, n_kinds, cutoff, hetero_cutoff, rsum, d_bond_ptr,
+                                           n_bonds, d_bond_ring, weights, max_steps, max_evals, max_shift, n_chains, n_rounds, amplitude,
+                                           temperature, d_draws, d_protein_role_out, d_n_rot, d_pos_out, d_terms_in, d_terms_out, d_n_pairs_out,
+                                           d_n_steps, d_n_evals, d_status, d_transform, d_grad_in, d_best_chain, d_chain_terms,
+                                           d_chain_transform, d_chain_accepts, d_chain_evals, stream, TD_RELAX_LIST_CAPACITY);
 }
 
 extern "C" int td_sasa_report(const float *d_pos, const int64_t *d_v, const int32_t *d_ligand_ptr, int64_t S, int64_t N_l, int64_t B,

@@ -537,52 +537,58 @@ class SamplePack:
         raw = {k: r[k].cpu().numpy() for k in keys if r[k] is not None}
         return InteractionReport.from_outputs(raw, self._included(mask), self.sizes, names, ref_sizes)
 
-    def score(self, data, include='all', reference_ligand=None, weights=None, rot_weight=None, cutoff=None):
-        """``sample_score`` of the pack; ``data`` as ``pocket``.  The rotatable bonds are counted on the pack's bond graph and ring sizes."""
+    def _pose_setup(self, data, include, weights, rot_weight, cutoff, max_steps=None, max_shift=None):
+        """What ``score``, ``relax`` and ``dock`` share, said once: the conventions for what is None, ``include`` as a mask and the
+        pocket.  Returns (weights, rot_weight, mask, the pocket's arguments of the three bindings up to the radius sums, (cutoff, hetero
+        cutoff), the optimiser's budget as keywords)."""
         weights = SCORE_WEIGHTS if weights is None else weights
         rot_weight = SCORE_ROT_WEIGHT if rot_weight is None else rot_weight
         side = self._side(data)
         kind, names = side.kinds()
         mask = self.mask(include)
-        pocket = (side.pos, side.elem, kind, side.roles(), len(names), score_radius_sums(), SCORE_CUTOFF if cutoff is None else cutoff,
-                  DEFAULT_HETERO_CUTOFF)
+        pocket = (side.pos, side.elem, kind, side.roles(), len(names), score_radius_sums())
+        cutoffs = (SCORE_CUTOFF if cutoff is None else cutoff, DEFAULT_HETERO_CUTOFF)
+        budget = dict(max_steps=RELAX_MAX_STEPS if max_steps is None else max_steps, max_shift=RELAX_MAX_SHIFT if max_shift is None else max_shift)
+        return weights, rot_weight, mask, pocket, cutoffs, budget
+
+    @property
+    def _rotors(self):
+        """the rotor inputs of the pack: ``bond_ptr`` of its plain bond graph and ``bond_ring``"""
+        return self.graph['bond_ptr'], self.bond_ring
+
+    def _reference_rotors(self, reference_ligand):
+        """(the known ligand as ``_reference`` packs it, its rotor inputs): its own bond graph and ring sizes"""
+        ref = self._reference(reference_ligand)
+        bond_ptr = capi.bond_graph(*ref, self.aromatic, (), None, False, True)['bond_ptr']
+        return ref, (bond_ptr, capi.ring_report(*ref, self.aromatic, None, bond_ptr, False)['bond_ring'])
+
+    def score(self, data, include='all', reference_ligand=None, weights=None, rot_weight=None, cutoff=None):
+        """``sample_score`` of the pack; ``data`` as ``pocket``.  The rotatable bonds are counted on the pack's bond graph and ring sizes."""
+        weights, rot_weight, mask, pocket, cutoffs, _ = self._pose_setup(data, include, weights, rot_weight, cutoff)
         ref_score = None
         if reference_ligand is not None:
-            ref = self._reference(reference_ligand)
-            bond_ptr = capi.bond_graph(*ref, self.aromatic, (), None, False, True)['bond_ptr']
-            ring = capi.ring_report(*ref, self.aromatic, None, bond_ptr, False)['bond_ring']
-            q = capi.score_report(*ref, self.aromatic, *pocket, bond_ptr, ring)
+            ref, rotors = self._reference_rotors(reference_ligand)
+            q = capi.score_report(*ref, self.aromatic, *pocket, *cutoffs, *rotors)
             if int(q['n_pairs'][0, 0]) >= 0:
                 ref_score = float(score_energies(q['terms'].cpu().numpy(), q['n_rot'].cpu().numpy(), weights, rot_weight)[2][0, 0])
-        r = capi.score_report(*self._args, self.aromatic, *pocket, self.graph['bond_ptr'], self.bond_ring, check=self._check())
-        raw = {k: r[k].cpu().numpy() for k in ('terms', 'n_pairs', 'n_rot')}
+        r = capi.score_report(*self._args, self.aromatic, *pocket, *cutoffs, *self._rotors, check=self._check())
         heavy = _heavy_atoms(self.v.cpu().numpy(), self.class_z, self.sizes)
-        return ScoreReport.from_outputs(raw, self._included(mask), heavy, weights, rot_weight, ref_score)
+        return ScoreReport.from_outputs(_numpy(r, ('terms', 'n_pairs', 'n_rot')), self._included(mask), heavy, weights, rot_weight, ref_score)
 
     def relax(self, data, include='all', reference_ligand=None, weights=None, max_steps=None, max_shift=None, cutoff=None, rot_weight=None):
         """``sample_relax`` of the pack; ``data`` as ``pocket``.  The rotatable bonds are those of the input poses, counted on the pack's
         bond graph and ring sizes; the relaxed coordinates of the last call stay in ``relaxed_pos`` [S, N_l, 3] on the device."""
-        weights = SCORE_WEIGHTS if weights is None else weights
-        rot_weight = SCORE_ROT_WEIGHT if rot_weight is None else rot_weight
-        side = self._side(data)
-        kind, names = side.kinds()
-        mask = self.mask(include)
-        pocket = (side.pos, side.elem, kind, side.roles(), len(names), score_radius_sums(), weights, SCORE_CUTOFF if cutoff is None else cutoff,
-                  DEFAULT_HETERO_CUTOFF)
-        budget = dict(max_steps=RELAX_MAX_STEPS if max_steps is None else max_steps, max_shift=RELAX_MAX_SHIFT if max_shift is None else max_shift)
-        keys = ('pos', 'terms_in', 'terms', 'n_rot', 'n_steps', 'n_evals', 'status', 'transform')
+        weights, rot_weight, mask, pocket, cutoffs, budget = self._pose_setup(data, include, weights, rot_weight, cutoff, max_steps, max_shift)
         ref_scores = None
         if reference_ligand is not None:
-            ref = self._reference(reference_ligand)
-            bond_ptr = capi.bond_graph(*ref, self.aromatic, (), None, False, True)['bond_ptr']
-            ring = capi.ring_report(*ref, self.aromatic, None, bond_ptr, False)['bond_ring']
-            q = capi.score_minimize(*ref, self.aromatic, *pocket, bond_ptr, ring, **budget)
+            ref, rotors = self._reference_rotors(reference_ligand)
+            q = capi.score_minimize(*ref, self.aromatic, *pocket, weights, *cutoffs, *rotors, **budget)
             if int(q['status'][0, 0]) >= 0:
-                _, before, after, _ = _relax_scores({k: q[k].cpu().numpy() for k in keys}, weights, rot_weight)
+                _, before, after, _ = _relax_scores(_numpy(q, _SCORES_RAW), weights, rot_weight)
                 ref_scores = (float(before[0, 0]), float(after[0, 0]))
-        r = capi.score_minimize(*self._args, self.aromatic, *pocket, self.graph['bond_ptr'], self.bond_ring, **budget, check=self._check())
+        r = capi.score_minimize(*self._args, self.aromatic, *pocket, weights, *cutoffs, *self._rotors, **budget, check=self._check())
         self.relaxed_pos = r['pos']
-        raw = {k: r[k].cpu().numpy() for k in keys}
+        raw = _numpy(r, ('pos', 'n_steps', 'n_evals') + _SCORES_RAW)
         return RelaxReport.from_outputs(raw, self._included(mask), self.pos.cpu().numpy(), self.sizes, weights, rot_weight, ref_scores)
 
     def dock(self, data, include='all', reference_ligand=None, weights=None, n_chains=None, n_rounds=None, seed=0, max_steps=None,
@@ -592,31 +598,20 @@ class SamplePack:
         the docked coordinates of the last call stay in ``docked_pos`` [1, N_l, 3] on the device.  The known ligand's draws are seeded
         by ``seed`` too."""
         _single_frame(None, self.S)
-        weights = SCORE_WEIGHTS if weights is None else weights
-        rot_weight = SCORE_ROT_WEIGHT if rot_weight is None else rot_weight
-        side = self._side(data)
-        kind, names = side.kinds()
-        mask = self.mask(include)
-        pocket = (side.pos, side.elem, kind, side.roles(), len(names), score_radius_sums(), weights, SCORE_CUTOFF if cutoff is None else cutoff,
-                  DEFAULT_HETERO_CUTOFF)
-        budget = dict(max_steps=RELAX_MAX_STEPS if max_steps is None else max_steps, max_shift=RELAX_MAX_SHIFT if max_shift is None else max_shift)
+        weights, rot_weight, mask, pocket, cutoffs, budget = self._pose_setup(data, include, weights, rot_weight, cutoff, max_steps, max_shift)
         search = dict(budget, n_chains=DOCK_CHAINS if n_chains is None else n_chains, n_rounds=DOCK_ROUNDS if n_rounds is None else n_rounds, seed=seed)
         ref_score = None
         if reference_ligand is not None:
-            ref = self._reference(reference_ligand)
-            bond_ptr = capi.bond_graph(*ref, self.aromatic, (), None, False, True)['bond_ptr']
-            ring = capi.ring_report(*ref, self.aromatic, None, bond_ptr, False)['bond_ring']
-            q = capi.score_dock(*ref, self.aromatic, *pocket, bond_ptr, ring, **search)
+            ref, rotors = self._reference_rotors(reference_ligand)
+            q = capi.score_dock(*ref, self.aromatic, *pocket, weights, *cutoffs, *rotors, **search)
             if int(q['status'][0, 0]) >= 0:
-                ref_score = float(_relax_scores({k: q[k].cpu().numpy() for k in ('terms_in', 'terms', 'n_rot', 'status', 'transform')}, weights,
-                                                rot_weight)[2][0, 0])
-        graph = (self.graph['bond_ptr'], self.bond_ring)
-        r_min = capi.score_minimize(*self._args, self.aromatic, *pocket, *graph, **budget, check=self._check())
-        r = capi.score_dock(*self._args, self.aromatic, *pocket, *graph, **search, check=self._check())
+                ref_score = float(_relax_scores(_numpy(q, _SCORES_RAW), weights, rot_weight)[2][0, 0])
+        rotors = self._rotors
+        r_min = capi.score_minimize(*self._args, self.aromatic, *pocket, weights, *cutoffs, *rotors, **budget, check=self._check())
+        r = capi.score_dock(*self._args, self.aromatic, *pocket, weights, *cutoffs, *rotors, **search, check=self._check())
         self.docked_pos = r['pos']
-        raw = {k: r[k].cpu().numpy() for k in _DOCK_RAW}
-        raw_min = {k: r_min[k].cpu().numpy() for k in ('terms_in', 'terms', 'n_rot', 'status', 'transform')}
-        return DockReport.from_outputs(raw, raw_min, self._included(mask), self.pos.cpu().numpy(), self.sizes, weights, rot_weight, ref_score)
+        return DockReport.from_outputs(_numpy(r, _DOCK_RAW), _numpy(r_min, _SCORES_RAW), self._included(mask), self.pos.cpu().numpy(), self.sizes,
+                                       weights, rot_weight, ref_score)
 
     def sasa(self, data, include='all', reference_ligand=None, probe=1.4, points=96):
         """``sample_sasa`` of the pack; ``data`` as ``pocket``"""
@@ -1758,6 +1753,82 @@ def _heavy_atoms(v, class_z, sizes):
     return run[:, ptr[1:]] - run[:, ptr[:-1]]
 
 
+def _pose_inputs(protein_pos, protein_feat, pos, v, batch_ligand, ligand_ptr, atom_enc_mode, ligand_radii, protein_radii, hydrogens, rotors,
+                 device, single_frame=False):
+    """What ``pocket_score``, ``pocket_relax`` and ``pocket_dock`` open with, as they pass it to the bindings: (the pack with the class
+    tables, the pocket up to the radius sums, (bond_ptr, bond_ring)).  With ``rotors`` this runs ``td_bond_graph`` and
+    ``td_ring_report`` -- the host's look at the pack is the bond graph's --, otherwise both are None."""
+    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
+    if single_frame:
+        _single_frame(None, pos.shape[0])
+    side = PocketSide((protein_pos, protein_feat), pos.device)
+    (kind, names), elem = side.kinds('residue', hydrogens), side.elem
+    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
+    bond_ptr = bond_ring = None
+    if rotors:
+        bond_ptr = capi.bond_graph(pos, v, ligand_ptr, cz, aro, (), None, False, True)['bond_ptr']
+        bond_ring = capi.ring_report(pos, v, ligand_ptr, cz, aro, None, bond_ptr, False, check=False)['bond_ring']
+    pocket = (side.pos, elem, kind, side.roles(hydrogens), len(names), score_radius_sums(ligand_radii, protein_radii))
+    return (pos, v, ligand_ptr, cz, aro), pocket, (bond_ptr, bond_ring)
+
+
+def _numpy(r, keys):
+    """``keys`` of a binding's dict of device tensors as numpy; None stays None"""
+    return {k: None if r[k] is None else r[k].cpu().numpy() for k in keys}
+
+
+def _reference_rows(inc, score, ref):
+    """(``sum_ref`` [S, len(ref) + 1], ``n_ref`` [S]) of one pocket: for every frame with an included molecule (``inc`` [S, B]) the
+    known ligand's values ``ref`` and the share of the included molecules whose ``score`` [S, B] is below the last of them; (None,
+    None) without ``ref``"""
+    if ref is None:
+        return None, None
+    S = inc.shape[0]
+    sum_ref, n_ref = np.zeros((S, len(ref) + 1)), np.zeros(S, np.int64)
+    for s in range(S):
+        if inc[s].any():
+            sum_ref[s] = (*ref, float((score[s][inc[s]] < ref[-1]).sum()) / float(inc[s].sum()))
+            n_ref[s] = 1
+    return sum_ref, n_ref
+
+
+class _PoseReport(_SumReport):
+    """What ``ScoreReport``, ``RelaxReport`` and ``DockReport`` share beyond ``_SumReport``: ``n_included`` first and ``sum_ref`` /
+    ``n_ref`` last among the ``FIELDS``, the statistics over a per-molecule score column -- a class's ``_of(frame, ...)`` gives the
+    scored molecules' values of the column that the arguments after ``frame`` choose, by default its final one -- and ``reference``
+    from the names ``REF_KEYS`` of the columns of ``sum_ref``."""
+    OPTIONAL, MISMATCH = 2, 'the reports differ in their frames or in whether they have a reference ligand'
+    REF_KEYS = ()
+
+    def _merge_key(self):
+        return self.n_included.shape, self.sum_ref is None
+
+    @staticmethod
+    def _mean_of(x):
+        return float(x.sum()) / x.size if x.size else float('nan')
+
+    def mean_score(self, frame=-1, *column, **kw):
+        return self._mean_of(self._of(frame, *column, **kw))
+
+    def median_score(self, frame=-1, *column, **kw):
+        x = self._of(frame, *column, **kw)
+        return float(np.median(x)) if x.size else float('nan')
+
+    def best_score(self, frame=-1, *column, **kw):
+        """the lowest score of the frame"""
+        x = self._of(frame, *column, **kw)
+        return float(x.min()) if x.size else float('nan')
+
+    def share_negative(self, frame=-1):
+        return self._mean((self._of(frame) < 0.0).sum(), self.n_included[frame])
+
+    def reference(self, frame=-1):
+        """``REF_KEYS`` with their values (means over the pockets of a merged report), or {} without a reference ligand"""
+        if self.sum_ref is None:
+            return {}
+        return {k: self._mean(self.sum_ref[frame, c], self.n_ref[frame]) for c, k in enumerate(self.REF_KEYS)}
+
+
 class Score:
     """The docking-style score of S frames of B molecules with one pocket (``pocket_score``).  ``protein_role`` [N_p] int32 on the
     device; numpy, frame axis first: ``terms`` [S, B, 5] float64 (the unweighted sums, ``SCORE_TERM_NAMES``), ``n_pairs`` [S, B] int32,
@@ -1790,21 +1861,15 @@ def pocket_score(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_pt
     ``td_score_report``.  This is NOT AutoDock Vina's number: no hydrogens are placed, the roles are a valence-deficit heuristic and
     there is no intramolecular term; it compares between runs of this tool, not with published tables.  Molecules of more than 512
     atoms are refused.  Returns a ``Score``."""
-    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
-    side = PocketSide((protein_pos, protein_feat), pos.device)
-    (kind, names), elem = side.kinds('residue', hydrogens), side.elem
-    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
-    bond_ptr = bond_ring = None
-    if rotors:
-        bond_ptr = capi.bond_graph(pos, v, ligand_ptr, cz, aro, (), None, False, True)['bond_ptr']
-        bond_ring = capi.ring_report(pos, v, ligand_ptr, cz, aro, None, bond_ptr, False, check=False)['bond_ring']
-    r = capi.score_report(pos, v, ligand_ptr, cz, aro, side.pos, elem, kind, side.roles(hydrogens), len(names),
-                          score_radius_sums(ligand_radii, protein_radii), cutoff, hetero_cutoff, bond_ptr, bond_ring, check=not rotors)
+    pack, pocket, rotor_graph = _pose_inputs(protein_pos, protein_feat, pos, v, batch_ligand, ligand_ptr, atom_enc_mode, ligand_radii,
+                                             protein_radii, hydrogens, rotors, device)
+    r = capi.score_report(*pack, *pocket, cutoff, hetero_cutoff, *rotor_graph, check=not rotors)
+    _, v, ligand_ptr, cz, _ = pack
     sizes = ligand_ptr.cpu().to(torch.int64).diff().tolist()
     return Score(r, ligand_ptr, _heavy_atoms(v.cpu().numpy(), cz, sizes), weights, rot_weight)
 
 
-class ScoreReport(_SumReport):
+class ScoreReport(_PoseReport):
     """Per frame (axis 0), over the included molecules that the kernel scored (``n_included`` [S] of ``n_samples``; a molecule with
     n_pairs = -1 is excluded everywhere): ``sum_inter`` [S] and ``sum_terms`` [S, 5] float64, the weighted terms; ``sum_rotors`` and
     ``sum_pairs`` [S] int64; ``n_no_pairs`` [S], the poses with no pair inside the cutoff; ``sum_efficiency`` [S] over the
@@ -1816,10 +1881,7 @@ class ScoreReport(_SumReport):
     FIELDS = (('n_included', 'i64'), ('sum_inter', 'f64'), ('sum_terms', 'f64'), ('sum_rotors', 'i64'), ('sum_pairs', 'i64'),
               ('n_no_pairs', 'i64'), ('sum_efficiency', 'f64'), ('n_efficiency', 'i64'), ('scores', 'per_mol'), ('scored', 'per_mol'),
               ('n_samples', 'int_sum'), ('sum_ref', 'ref_f64'), ('n_ref', 'ref_i64'))
-    OPTIONAL, MISMATCH = 2, 'the reports differ in their frames or in whether they have a reference ligand'
-
-    def _merge_key(self):
-        return self.n_included.shape, self.sum_ref is None
+    REF_KEYS = ('ref_score', 'better_than_ref')         # the known ligand's score and the share of molecules that score below it
 
     @classmethod
     def from_outputs(cls, raw, included, heavy, weights=SCORE_WEIGHTS, rot_weight=SCORE_ROT_WEIGHT, ref_score=None):
@@ -1833,43 +1895,12 @@ class ScoreReport(_SumReport):
         has = inc & (heavy > 0)
         eff = np.divide(score, heavy, out=np.zeros(score.shape), where=has)
         tot = lambda x: np.where(inc, x, 0).sum(1)
-        sum_ref = n_ref = None
-        if ref_score is not None:
-            S = inc.shape[0]
-            sum_ref, n_ref = np.zeros((S, 2)), np.zeros(S, np.int64)
-            for s in range(S):
-                if inc[s].any():
-                    sum_ref[s] = (ref_score, float((score[s][inc[s]] < ref_score).sum()) / float(inc[s].sum()))
-                    n_ref[s] = 1
         return cls(inc.sum(1), tot(inter), np.where(inc[..., None], terms * np.asarray(weights, dtype=np.float64), 0.0).sum(1), tot(n_rot),
                    tot(n_pairs), (inc & (n_pairs == 0)).sum(1), np.where(has, eff, 0.0).sum(1), has.sum(1), np.where(inc, score, np.nan), inc,
-                   inc.shape[1], sum_ref, n_ref)
+                   inc.shape[1], *_reference_rows(inc, score, None if ref_score is None else (ref_score,)))
 
-    def _scores(self, frame):
+    def _of(self, frame):
         return self.scores[frame][self.scored[frame]]
-
-    def mean_score(self, frame=-1):
-        x = self._scores(frame)
-        return float(x.sum()) / x.size if x.size else float('nan')
-
-    def median_score(self, frame=-1):
-        x = self._scores(frame)
-        return float(np.median(x)) if x.size else float('nan')
-
-    def best_score(self, frame=-1):
-        """the lowest score of the frame"""
-        x = self._scores(frame)
-        return float(x.min()) if x.size else float('nan')
-
-    def share_negative(self, frame=-1):
-        return self._mean((self._scores(frame) < 0.0).sum(), self.n_included[frame])
-
-    def reference(self, frame=-1):
-        """{'ref_score', 'better_than_ref'}: the known ligand's score and the share of molecules that score below it (means over the
-        pockets of a merged report), or {} without a reference ligand"""
-        if self.sum_ref is None:
-            return {}
-        return {k: self._mean(self.sum_ref[frame, c], self.n_ref[frame]) for c, k in enumerate(('ref_score', 'better_than_ref'))}
 
     def summary(self, frame=-1):
         n = self.n_included[frame]
@@ -1920,7 +1951,26 @@ def _relax_scores(raw, weights, rot_weight):
     return bad, before, after, np.sqrt((np.asarray(raw['transform'], dtype=np.float64)[..., 4:] ** 2).sum(-1))
 
 
-class Relaxed:
+_SCORES_RAW = ('terms_in', 'terms', 'n_rot', 'status', 'transform')         # what _relax_scores reads
+_RELAXED_RAW = ('terms_in', 'terms', 'n_pairs', 'n_steps', 'n_evals', 'status', 'transform')
+
+
+class _Pose:
+    """what ``Relaxed`` and ``Docked`` share: the conversion of the raw outputs of capi.score_minimize / score_dock"""
+
+    def _take(self, r, pos_in, ligand_ptr, more):
+        """Sets ``pos``, ``protein_role`` and ``ligand_ptr``, as numpy ``raw_terms_in`` / ``raw_terms``, the rest of ``_RELAXED_RAW``, the
+        keys ``more`` and ``n_rot`` under their own names, and ``rmsd``.  Returns the numpy outputs as a dict."""
+        self.pos, self.protein_role, self.ligand_ptr = r['pos'], r['protein_role'], ligand_ptr
+        raw = _numpy(r, _RELAXED_RAW + more + ('n_rot',))
+        self.raw_terms_in, self.raw_terms = raw['terms_in'], raw['terms']
+        for k in tuple(raw)[2:]:
+            setattr(self, k, raw[k])
+        self.rmsd = _moved(pos_in.cpu().numpy(), self.pos.cpu().numpy(), ligand_ptr.cpu().to(torch.int64).diff().tolist())
+        return raw
+
+
+class Relaxed(_Pose):
     """The rigid-body relaxation of S frames of B molecules in one pocket (``pocket_relax``).  ``pos`` [S, N_l, 3] fp32 on the device,
     the relaxed poses; numpy, frame axis first: ``raw_terms_in`` / ``raw_terms`` [S, B, 5] int64 (the kernel's integers at the input and
     at the relaxed pose), ``n_pairs``, ``n_steps``, ``n_evals``, ``status`` [S, B] int32 (bits ``capi.RELAX_CONVERGED``,
@@ -1932,15 +1982,9 @@ class Relaxed:
     (``pocket_relax``)."""
 
     def __init__(self, r, pos_in, ligand_ptr, weights, rot_weight):
-        self.pos, self.protein_role, self.ligand_ptr = r['pos'], r['protein_role'], ligand_ptr
-        raw = {k: r[k].cpu().numpy() for k in ('terms_in', 'terms', 'n_pairs', 'n_steps', 'n_evals', 'status', 'transform', 'grad_in')}
-        raw['n_rot'] = None if r['n_rot'] is None else r['n_rot'].cpu().numpy()
-        self.raw_terms_in, self.raw_terms = raw['terms_in'], raw['terms']
-        for k in ('n_pairs', 'n_steps', 'n_evals', 'status', 'transform', 'grad_in', 'n_rot'):
-            setattr(self, k, raw[k])
+        raw = self._take(r, pos_in, ligand_ptr, ('grad_in',))
         bad, self.score_in, self.score, self.shift = _relax_scores(raw, weights, rot_weight)
         self.score_in[bad], self.score[bad] = np.nan, np.nan
-        self.rmsd = _moved(pos_in.cpu().numpy(), self.pos.cpu().numpy(), ligand_ptr.cpu().to(torch.int64).diff().tolist())
 
 
 def pocket_relax(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic', weights=SCORE_WEIGHTS,
@@ -1953,21 +1997,13 @@ def pocket_relax(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_pt
     per molecule (``td_score_minimize``), with the roles and the rotatable bonds of the input pose.  It is a local optimisation under this
     project's heuristic score, not AutoDock Vina's ``minimize``, and it is rigid-body only: three translations and three rotations, no
     torsions; no global search, no intramolecular term, no hydrogens.  Returns a ``Relaxed``."""
-    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
-    side = PocketSide((protein_pos, protein_feat), pos.device)
-    (kind, names), elem = side.kinds('residue', hydrogens), side.elem
-    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
-    bond_ptr = bond_ring = None
-    if rotors:
-        bond_ptr = capi.bond_graph(pos, v, ligand_ptr, cz, aro, (), None, False, True)['bond_ptr']
-        bond_ring = capi.ring_report(pos, v, ligand_ptr, cz, aro, None, bond_ptr, False, check=False)['bond_ring']
-    r = capi.score_minimize(pos, v, ligand_ptr, cz, aro, side.pos, elem, kind, side.roles(hydrogens), len(names),
-                            score_radius_sums(ligand_radii, protein_radii), weights, cutoff, hetero_cutoff, bond_ptr, bond_ring, max_steps,
-                            max_evals, max_shift, check=not rotors)
-    return Relaxed(r, pos, ligand_ptr, weights, rot_weight)
+    pack, pocket, rotor_graph = _pose_inputs(protein_pos, protein_feat, pos, v, batch_ligand, ligand_ptr, atom_enc_mode, ligand_radii,
+                                             protein_radii, hydrogens, rotors, device)
+    r = capi.score_minimize(*pack, *pocket, weights, cutoff, hetero_cutoff, *rotor_graph, max_steps, max_evals, max_shift, check=not rotors)
+    return Relaxed(r, pack[0], pack[2], weights, rot_weight)
 
 
-class RelaxReport(_SumReport):
+class RelaxReport(_PoseReport):
     """Per frame (axis 0), over the included molecules that the kernel relaxed (``n_included`` [S] of ``n_samples``; a molecule with
     status -1 is excluded everywhere): ``scores_in`` and ``scores`` [S, B] float64 with ``scored`` [S, B] bool, the per-molecule scores
     before and after (the reference's ``vina_score`` / ``vina_min`` pair on this typing; joined along the molecule axis by ``merged``);
@@ -1981,10 +2017,9 @@ class RelaxReport(_SumReport):
     FIELDS = (('n_included', 'i64'), ('scores_in', 'per_mol'), ('scores', 'per_mol'), ('scored', 'per_mol'), ('sum_rmsd', 'f64'),
               ('sum_shift', 'f64'), ('n_converged', 'i64'), ('n_out_of_budget', 'i64'), ('n_at_cap', 'i64'), ('sum_steps', 'i64'),
               ('sum_evals', 'i64'), ('n_samples', 'int_sum'), ('sum_ref', 'ref_f64'), ('n_ref', 'ref_i64'))
-    OPTIONAL, MISMATCH = 2, 'the reports differ in their frames or in whether they have a reference ligand'
-
-    def _merge_key(self):
-        return self.n_included.shape, self.sum_ref is None
+    # the known ligand's score before and after its own relaxation and the share of molecules whose minimised score is below its
+    # minimised score
+    REF_KEYS = ('ref_score', 'ref_score_min', 'better_than_ref_min')
 
     @classmethod
     def from_outputs(cls, raw, included, pos_in, sizes, weights=SCORE_WEIGHTS, rot_weight=SCORE_ROT_WEIGHT, ref_scores=None):
@@ -1996,50 +2031,17 @@ class RelaxReport(_SumReport):
         status = np.asarray(raw['status'], dtype=np.int64)
         rmsd = _moved(pos_in, raw['pos'], sizes)
         tot = lambda x: np.where(inc, x, 0).sum(1)
-        sum_ref = n_ref = None
-        if ref_scores is not None:
-            S = inc.shape[0]
-            sum_ref, n_ref = np.zeros((S, 3)), np.zeros(S, np.int64)
-            for s in range(S):
-                if inc[s].any():
-                    sum_ref[s] = (ref_scores[0], ref_scores[1], float((after[s][inc[s]] < ref_scores[1]).sum()) / float(inc[s].sum()))
-                    n_ref[s] = 1
         return cls(inc.sum(1), np.where(inc, before, np.nan), np.where(inc, after, np.nan), inc, tot(rmsd), tot(shift),
                    tot((status & capi.RELAX_CONVERGED) != 0), tot((status & capi.RELAX_OUT_OF_BUDGET) != 0),
                    tot((status & capi.RELAX_AT_CAP) != 0), tot(np.asarray(raw['n_steps'], dtype=np.int64)),
-                   tot(np.asarray(raw['n_evals'], dtype=np.int64)), inc.shape[1], sum_ref, n_ref)
+                   tot(np.asarray(raw['n_evals'], dtype=np.int64)), inc.shape[1], *_reference_rows(inc, after, ref_scores))
 
-    def _of(self, frame, after):
+    def _of(self, frame, after=True):
         return (self.scores if after else self.scores_in)[frame][self.scored[frame]]
-
-    def mean_score(self, frame=-1, after=True):
-        x = self._of(frame, after)
-        return float(x.sum()) / x.size if x.size else float('nan')
-
-    def median_score(self, frame=-1, after=True):
-        x = self._of(frame, after)
-        return float(np.median(x)) if x.size else float('nan')
-
-    def best_score(self, frame=-1, after=True):
-        """the lowest score of the frame"""
-        x = self._of(frame, after)
-        return float(x.min()) if x.size else float('nan')
 
     def mean_gain(self, frame=-1):
         """the mean of score before - score after"""
-        x = self._of(frame, False) - self._of(frame, True)
-        return float(x.sum()) / x.size if x.size else float('nan')
-
-    def share_negative(self, frame=-1):
-        return self._mean((self._of(frame, True) < 0.0).sum(), self.n_included[frame])
-
-    def reference(self, frame=-1):
-        """{'ref_score', 'ref_score_min', 'better_than_ref_min'}: the known ligand's score before and after its own relaxation and the
-        share of molecules whose minimised score is below its minimised score (means over the pockets of a merged report), or {}"""
-        if self.sum_ref is None:
-            return {}
-        keys = ('ref_score', 'ref_score_min', 'better_than_ref_min')
-        return {k: self._mean(self.sum_ref[frame, c], self.n_ref[frame]) for c, k in enumerate(keys)}
+        return self._mean_of(self._of(frame, False) - self._of(frame, True))
 
     def summary(self, frame=-1):
         n = self.n_included[frame]
@@ -2092,7 +2094,7 @@ def _dock_scores(raw, raw_min, weights, rot_weight):
     return bad, before, minimised, docked, (inter <= won + DOCK_AGREE).sum(-1) / float(inter.shape[-1])
 
 
-class Docked:
+class Docked(_Pose):
     """The docking search of one frame of B molecules in one pocket (``pocket_dock``).  ``pos`` [1, N_l, 3] fp32 on the device, the
     docked poses; numpy, frame axis first: ``raw_terms_in`` / ``raw_terms`` [1, B, 5] int64 (the kernel's integers at the input and at
     the docked pose), ``n_pairs``, ``n_steps``, ``n_evals`` (summed over the chains), ``status`` [1, B] int32, ``n_rot`` [1, B] int32 of
@@ -2104,19 +2106,11 @@ class Docked:
     AutoDock Vina's ``dock``: three translations and three rotations, no torsions (``pocket_dock``)."""
 
     def __init__(self, r, r_min, pos_in, ligand_ptr, weights, rot_weight):
-        self.pos, self.protein_role, self.ligand_ptr, self.draws = r['pos'], r['protein_role'], ligand_ptr, r.get('draws')
-        keys = ('terms_in', 'terms', 'n_pairs', 'n_steps', 'n_evals', 'status', 'transform', 'best_chain', 'chain_terms', 'chain_transform',
-                'chain_accepts', 'chain_evals')
-        raw = {k: r[k].cpu().numpy() for k in keys}
-        raw['n_rot'] = None if r['n_rot'] is None else r['n_rot'].cpu().numpy()
-        raw_min = {k: (None if r_min[k] is None else r_min[k].cpu().numpy()) for k in ('terms_in', 'terms', 'n_rot', 'status', 'transform')}
-        self.raw_terms_in, self.raw_terms = raw['terms_in'], raw['terms']
-        for k in keys[2:] + ('n_rot',):
-            setattr(self, k, raw[k])
-        bad, self.score_in, self.score_min, self.score, self.agree = _dock_scores(raw, raw_min, weights, rot_weight)
+        raw = self._take(r, pos_in, ligand_ptr, ('best_chain', 'chain_terms', 'chain_transform', 'chain_accepts', 'chain_evals'))
+        self.draws = r.get('draws')
+        bad, self.score_in, self.score_min, self.score, self.agree = _dock_scores(raw, _numpy(r_min, _SCORES_RAW), weights, rot_weight)
         for x in (self.score_in, self.score_min, self.score):
             x[bad] = np.nan
-        self.rmsd = _moved(pos_in.cpu().numpy(), self.pos.cpu().numpy(), ligand_ptr.cpu().to(torch.int64).diff().tolist())
 
 
 def pocket_dock(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_ptr=None, atom_enc_mode='add_aromatic', weights=SCORE_WEIGHTS,
@@ -2131,23 +2125,15 @@ def pocket_dock(protein_pos, protein_feat, pos, v, batch_ligand=None, ligand_ptr
     (``td_score_dock``); the uniforms are ``draws`` or torch.rand seeded by ``seed``.  It is a rigid-body global search under this project's
     heuristic score, not AutoDock Vina's ``dock``: three translations and three rotations, no torsions.  No intramolecular term, no
     hydrogens; the search box is the ball of ``max_shift`` around the input centroid.  Returns a ``Docked``."""
-    pos, v, ligand_ptr = _pack(pos, v, batch_ligand, ligand_ptr, device)
-    _single_frame(None, pos.shape[0])
-    side = PocketSide((protein_pos, protein_feat), pos.device)
-    (kind, names), elem = side.kinds('residue', hydrogens), side.elem
-    cz, aro = class_atomic_numbers(atom_enc_mode), class_aromatic(atom_enc_mode)
-    bond_ptr = bond_ring = None
-    if rotors:
-        bond_ptr = capi.bond_graph(pos, v, ligand_ptr, cz, aro, (), None, False, True)['bond_ptr']
-        bond_ring = capi.ring_report(pos, v, ligand_ptr, cz, aro, None, bond_ptr, False, check=False)['bond_ring']
-    args = (pos, v, ligand_ptr, cz, aro, side.pos, elem, kind, side.roles(hydrogens), len(names), score_radius_sums(ligand_radii, protein_radii),
-            weights, cutoff, hetero_cutoff, bond_ptr, bond_ring, max_steps, max_evals, max_shift)
+    pack, pocket, rotor_graph = _pose_inputs(protein_pos, protein_feat, pos, v, batch_ligand, ligand_ptr, atom_enc_mode, ligand_radii,
+                                             protein_radii, hydrogens, rotors, device, single_frame=True)
+    args = (*pack, *pocket, weights, cutoff, hetero_cutoff, *rotor_graph, max_steps, max_evals, max_shift)
     r_min = capi.score_minimize(*args, check=not rotors)
     r = capi.score_dock(*args, n_chains, n_rounds, amplitude, temperature, seed, draws, check=not rotors)
-    return Docked(r, r_min, pos, ligand_ptr, weights, rot_weight)
+    return Docked(r, r_min, pack[0], pack[2], weights, rot_weight)
 
 
-class DockReport(_SumReport):
+class DockReport(_PoseReport):
     """Per frame (axis 0; the search takes one frame), over the included molecules that the kernel searched (``n_included`` [S] of
     ``n_samples``; a molecule with status -1 is excluded everywhere): ``scores_in``, ``scores_min`` and ``scores`` [S, B] float64 with
     ``scored`` [S, B] bool, the per-molecule scores of the input pose, after the relaxation alone and after the search (the reference's
@@ -2160,10 +2146,8 @@ class DockReport(_SumReport):
 
     FIELDS = (('n_included', 'i64'), ('scores_in', 'per_mol'), ('scores_min', 'per_mol'), ('scores', 'per_mol'), ('scored', 'per_mol'),
               ('sum_rmsd', 'f64'), ('sum_agree', 'f64'), ('sum_evals', 'i64'), ('n_samples', 'int_sum'), ('sum_ref', 'ref_f64'), ('n_ref', 'ref_i64'))
-    OPTIONAL, MISMATCH = 2, 'the reports differ in their frames or in whether they have a reference ligand'
-
-    def _merge_key(self):
-        return self.n_included.shape, self.sum_ref is None
+    # the known ligand's score after its own search and the share of molecules whose docked score is below it
+    REF_KEYS = ('ref_score_dock', 'better_than_ref_dock')
 
     @classmethod
     def from_outputs(cls, raw, raw_min, included, pos_in, sizes, weights=SCORE_WEIGHTS, rot_weight=SCORE_ROT_WEIGHT, ref_score=None):
@@ -2175,47 +2159,16 @@ class DockReport(_SumReport):
         inc = np.asarray(included, dtype=bool) & ~bad
         rmsd = _moved(pos_in, raw['pos'], sizes)
         tot = lambda x: np.where(inc, x, 0).sum(1)
-        sum_ref = n_ref = None
-        if ref_score is not None:
-            S = inc.shape[0]
-            sum_ref, n_ref = np.zeros((S, 2)), np.zeros(S, np.int64)
-            for s in range(S):
-                if inc[s].any():
-                    sum_ref[s] = (ref_score, float((docked[s][inc[s]] < ref_score).sum()) / float(inc[s].sum()))
-                    n_ref[s] = 1
         return cls(inc.sum(1), np.where(inc, before, np.nan), np.where(inc, minimised, np.nan), np.where(inc, docked, np.nan), inc, tot(rmsd),
-                   tot(agree), tot(np.asarray(raw['n_evals'], dtype=np.int64)), inc.shape[1], sum_ref, n_ref)
+                   tot(agree), tot(np.asarray(raw['n_evals'], dtype=np.int64)), inc.shape[1],
+                   *_reference_rows(inc, docked, None if ref_score is None else (ref_score,)))
 
-    def _of(self, frame, which):
+    def _of(self, frame, which='dock'):
         return {'in': self.scores_in, 'min': self.scores_min, 'dock': self.scores}[which][frame][self.scored[frame]]
-
-    def mean_score(self, frame=-1, which='dock'):
-        x = self._of(frame, which)
-        return float(x.sum()) / x.size if x.size else float('nan')
-
-    def median_score(self, frame=-1, which='dock'):
-        x = self._of(frame, which)
-        return float(np.median(x)) if x.size else float('nan')
-
-    def best_score(self, frame=-1, which='dock'):
-        """the lowest score of the frame"""
-        x = self._of(frame, which)
-        return float(x.min()) if x.size else float('nan')
 
     def mean_gain(self, frame=-1):
         """the mean of score after the relaxation alone - score after the search"""
-        x = self._of(frame, 'min') - self._of(frame, 'dock')
-        return float(x.sum()) / x.size if x.size else float('nan')
-
-    def share_negative(self, frame=-1):
-        return self._mean((self._of(frame, 'dock') < 0.0).sum(), self.n_included[frame])
-
-    def reference(self, frame=-1):
-        """{'ref_score_dock', 'better_than_ref_dock'}: the known ligand's score after its own search and the share of molecules whose
-        docked score is below it (means over the pockets of a merged report), or {}"""
-        if self.sum_ref is None:
-            return {}
-        return {k: self._mean(self.sum_ref[frame, c], self.n_ref[frame]) for c, k in enumerate(('ref_score_dock', 'better_than_ref_dock'))}
+        return self._mean_of(self._of(frame, 'min') - self._of(frame, 'dock'))
 
     def summary(self, frame=-1):
         n = self.n_included[frame]

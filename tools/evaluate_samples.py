@@ -116,6 +116,7 @@ def pocket_sections(args):
     """The reports against the pocket that ``args`` asks for, as (flag -- also the name of the SamplePack method and of the JSON
     section, but for ``METHODS`` --, report class, the method's arguments after the reference ligand, extra JSON fields of the merged
     report)"""
+    scoring = dict(weights=dict(zip(quality.SCORE_TERM_NAMES, quality.SCORE_WEIGHTS)), rot_weight=quality.SCORE_ROT_WEIGHT)
     every = (
         ('pocket', quality.PocketReport, (args.contact_cutoff, args.clash_tolerance),
          lambda r: dict(contact_cutoff=args.contact_cutoff, clash_tolerance=args.clash_tolerance, contact_profile=r.contact_profile(-1),
@@ -125,15 +126,13 @@ def pocket_sections(args):
                         kind_hist={t: dict(zip(r.names, r.kind_hist[-1, k].tolist())) for k, t in enumerate(quality.INTERACTION_NAMES)})),
         ('sasa', quality.SasaReport, (args.probe, args.sasa_points), lambda r: dict(probe=args.probe, points=args.sasa_points)),
         ('score', quality.ScoreReport, (None, None, args.score_cutoff),
-         lambda r: dict(score_cutoff=args.score_cutoff, weights=dict(zip(quality.SCORE_TERM_NAMES, quality.SCORE_WEIGHTS)),
-                        rot_weight=quality.SCORE_ROT_WEIGHT)),
+         lambda r: dict(score_cutoff=args.score_cutoff, **scoring)),
         ('minimize', quality.RelaxReport, (None, args.min_steps, args.max_shift, args.score_cutoff),
-         lambda r: dict(score_cutoff=args.score_cutoff, max_steps=args.min_steps, max_shift=args.max_shift,
-                        weights=dict(zip(quality.SCORE_TERM_NAMES, quality.SCORE_WEIGHTS)), rot_weight=quality.SCORE_ROT_WEIGHT)),
+         lambda r: dict(score_cutoff=args.score_cutoff, max_steps=args.min_steps, max_shift=args.max_shift, **scoring)),
         ('dock', quality.DockReport, (None, args.dock_chains, args.dock_rounds, args.dock_seed, args.min_steps, args.max_shift, args.score_cutoff),
          lambda r: dict(score_cutoff=args.score_cutoff, n_chains=args.dock_chains, n_rounds=args.dock_rounds, seed=args.dock_seed,
                         amplitude=quality.DOCK_AMPLITUDE, temperature=quality.DOCK_TEMPERATURE, max_steps=args.min_steps, max_shift=args.max_shift,
-                        weights=dict(zip(quality.SCORE_TERM_NAMES, quality.SCORE_WEIGHTS)), rot_weight=quality.SCORE_ROT_WEIGHT)))
+                        **scoring)))
     return [section for section in every if getattr(args, section[0])]
 
 

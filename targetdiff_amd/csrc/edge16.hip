@@ -2527,24 +2527,27 @@ template <class F> static int with_graph_fl(bool chunked, bool fl, F f) {
     return fl ? f(Int<0>{}, Int<1>{}) : f(Int<0>{}, Int<0>{});
 }
 
-// cptr (general graphs): chunks of dst node i = cptr[i] .. cptr[i+1]-1 of nbr / ew / alpha; nullptr: one 32-slot row per node.
-// lig_rows / lig_count / cpn_p (x2h on general graphs): the ligand rows among `rows` (all of them) and the chunks per protein row.  With one
-// chunk per protein row (`hybrid`) the protein rows run as on the default graph and the ligand rows in a second, chunk-walking launch.
-int td_launch_edge_key16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const int32_t *nbr, const float *ew,
-                         const float *P, const float *q, const int32_t *rows, const int32_t *count_ptr, int64_t count,
-                         float *alpha, hipStream_t s, bool h2x_stage, const int32_t *cptr, const int32_t *lig_rows, int64_t lig_count, int cpn_p) {
-    if (count == 0) return TD_OK;
+// what every attention launch takes of the table and the row selection
+static Args16 args16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const TdGraphTab &gt, const float *P, const TdRows &rows) {
     Args16 a = {};
-    a.x4 = x4; a.nbr = nbr; a.ew = ew; a.P = P; a.q = q; a.rows = rows; a.count_ptr = count_ptr; a.h = nullptr;
-    a.alpha = alpha; a.x4_out = nullptr; a.count = count; a.mlp = mlp; a.offsets = L.offsets; a.coeff = L.coeff; a.p_off = 0;
-    a.cptr = cptr;
+    a.x4 = x4; a.nbr = gt.nbr; a.P = P; a.rows = rows.rows; a.count_ptr = rows.count_ptr; a.alpha = gt.alpha; a.count = rows.count;
+    a.mlp = mlp; a.offsets = L.offsets; a.coeff = L.coeff; a.cptr = gt.cptr;
+    return a;
+}
+
+// Key pass into gt.alpha.  `lig` is read on a `hybrid` graph only (see TdGraphTab::cpn_p).
+int td_launch_edge_key16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const TdGraphTab &gt, const float *P, const float *q,
+                         const TdRows &rows, const TdRows &lig, bool h2x_stage, hipStream_t s) {
+    if (rows.count == 0) return TD_OK;
+    Args16 a = args16(mlp, L, x4, gt, P, rows);
+    a.ew = gt.ew; a.q = q; a.p_off = 0;
     const bool h2x = h2x_stage;      // h2x key pass (unfused form): STAGE tag 1, contiguous shares, no workgroup trace
     if (!h2x) a.trace = wg_trace_slot(0);
     a.deal = h2x ? 0 : mlp.deal_rows;
-    const bool chunked = cptr != nullptr;
+    const bool chunked = gt.cptr != nullptr;
     const bool fl = mlp.l1_f16;                              // first layer on f16 piece pairs (else: exact bf16 piece triples)
     const int l2 = l2_variant(mlp);
-    const bool hybrid = chunked && cpn_p == 1;
+    const bool hybrid = chunked && gt.cpn_p == 1;
     if (!mlp.use_split) {                                     // fp32 first layer: 16 waves, fp32 logits
         if (h2x) return chunked ? launch_key16<false, K16_WAVES, 1, 1, false>(a, s) : launch_key16<false, K16_WAVES, 1, 0, false>(a, s);
         return chunked ? launch_key16<false, K16_WAVES, 0, 1, false>(a, s) : launch_key16<false, K16_WAVES, 0, 0, false>(a, s);
@@ -2554,21 +2557,18 @@ int td_launch_edge_key16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x
     if (!chunked) return launch_key16_x2h<0>(l2, fl, a, s);
     if (!hybrid) return launch_key16_walk(l2, fl, a, s);
     const int rc = launch_key16_x2h<2>(l2, fl, a, s);
-    if (rc != TD_OK || !lig_rows || lig_count <= 0) return rc;
-    a.rows = lig_rows; a.count_ptr = nullptr; a.count = lig_count; a.trace = nullptr;
+    if (rc != TD_OK || !lig.rows || lig.count <= 0) return rc;
+    a.rows = lig.rows; a.count_ptr = nullptr; a.count = lig.count; a.trace = nullptr;
     return launch_key16_walk(l2, fl, a, s);
 }
 
-// h2x value pass (xv MLP + coordinate update) on the listed ligand rows; reads alpha written by the h2x key pass.
-int td_launch_edge_xv16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4_in, float4 *x4_out, const int32_t *nbr,
-                        const float *P, const int32_t *rows, int64_t count, const float *alpha, hipStream_t s,
-                        const int32_t *cptr) {
-    if (count == 0) return TD_OK;
-    Args16 a = {};
-    a.x4 = x4_in; a.nbr = nbr; a.ew = nullptr; a.P = P; a.q = nullptr; a.rows = rows; a.count_ptr = nullptr; a.h = nullptr;
-    a.alpha = const_cast<float *>(alpha); a.x4_out = x4_out; a.count = count; a.mlp = mlp; a.offsets = L.offsets;
-    a.coeff = L.coeff; a.p_off = 2 * TD_H; a.cptr = cptr;
-    const bool chunked = cptr != nullptr;
+// h2x value pass (xv MLP + coordinate update) on the listed ligand rows (a list of rows.count rows); reads gt.alpha written by the h2x key pass.
+int td_launch_edge_xv16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4_in, float4 *x4_out, const TdGraphTab &gt, const float *P,
+                        const TdRows &rows, hipStream_t s) {
+    if (rows.count == 0) return TD_OK;
+    Args16 a = args16(mlp, L, x4_in, gt, P, rows);
+    a.count_ptr = nullptr; a.x4_out = x4_out; a.p_off = 2 * TD_H;
+    const bool chunked = gt.cptr != nullptr;
     if (!mlp.use_split) return chunked ? launch_key16<true, XV16_WAVES, 1, 1, false>(a, s) : launch_key16<true, XV16_WAVES, 1, 0, false>(a, s);
     return with_graph_fl(chunked, mlp.l1_f16, [&](auto GR, auto FL) { return launch_key16<true, XV16_WAVES, 1, GR, true, 0, FL>(a, s); });
 }
@@ -2588,25 +2588,23 @@ template <bool VIA> static int launch_value16t(int l2, bool fl, int G, const Arg
     });
 }
 
-// lig_rows / lig_count: the ligand rows among `rows` (all of them: every row list of a forward pass or sampling step holds
-// the ligand atoms); nullptr / 0 for a list without ligand rows.  General graphs: cptr, the chunks per protein row and the
-// chunks of all ligand rows together (the class split of the bf16 kernel is sized from chunk counts).
-int td_launch_edge_value16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const int32_t *nbr, const float *P,
-                           const int32_t *rows, const int32_t *count_ptr, int64_t count, float *h, const float *alpha,
-                           const int32_t *lig_rows, int64_t lig_count, hipStream_t s, const int32_t *cptr, int cpn_p,
-                           int64_t lig_chunks, const int32_t *mixed_count, float *out, const float *gate_m) {
+// Value pass from gt.alpha into h (or `out`).  General graphs: the class split of the bf16 kernel is sized from chunk counts (gt.cpn_p, gt.NCl).
+// ew_net_type 'm' (L.gate_m): the gate from the value vector.
+int td_launch_edge_value16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const TdGraphTab &gt, const float *P, const TdRows &rows,
+                           const TdRows &lig, float *h, float *out, hipStream_t s) {
+    const int64_t count = rows.count, lig_count = lig.count;
+    const int32_t *lig_rows = lig.rows;
+    const float *gate_m = L.gate_m;
     if (count == 0) return TD_OK;
-    Args16 a = {};
-    a.x4 = x4; a.nbr = nbr; a.ew = nullptr; a.P = P; a.q = nullptr; a.rows = rows; a.count_ptr = count_ptr; a.h = h;
-    a.alpha = const_cast<float *>(alpha); a.x4_out = nullptr; a.count = count; a.mlp = mlp; a.offsets = L.offsets;
-    a.coeff = L.coeff; a.p_off = 2 * TD_H; a.cptr = cptr; a.cpn_p = cpn_p > 0 ? cpn_p : 1; a.lig_chunks = lig_chunks;
-    a.mixed_count = mixed_count;
+    Args16 a = args16(mlp, L, x4, gt, P, rows);
+    a.h = h; a.p_off = 2 * TD_H; a.cpn_p = gt.cpn_p > 0 ? gt.cpn_p : 1; a.lig_chunks = lig_rows ? gt.NCl : 0;
+    a.mixed_count = gt.mixed;
     a.out = out;
-    a.gate_m = cptr ? nullptr : gate_m;          // (ew_net_type 'm' is accepted on the default graph only)
+    a.gate_m = gt.cptr ? nullptr : gate_m;          // (ew_net_type 'm' is accepted on the default graph only)
     int G = grid16(count, V16_WAVES);
     a.trace = wg_trace_slot(1);
     a.deal = mlp.deal_rows;
-    const bool chunked = cptr != nullptr;
+    const bool chunked = gt.cptr != nullptr;
     const bool fl = mlp.l1_f16;
     const int l2 = l2_variant(mlp);
     const bool hybrid = chunked && a.cpn_p == 1;
@@ -2636,16 +2634,16 @@ int td_launch_edge_value16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 
     return launch_value16_split<false>(l2, fl, G, a, s);
 }
 
-// Fused h2x stage (keys + softmax + xv + coordinate update) on the listed ligand rows.
+// Fused h2x stage (keys + softmax + xv + coordinate update) on the listed ligand rows (a list of rows.count rows).
 int td_launch_edge_h2x16(const TdEdgeMlp &mlp_k, const TdEdgeMlp &mlp_v, const TdLayer &L, const float4 *x4_in, float4 *x4_out,
-                         const int32_t *nbr, const float *ew, const float *P, const float *q, const int32_t *rows,
-                         int64_t count, hipStream_t s, const int32_t *cptr, float *alpha) {
+                         const TdGraphTab &gt, const float *P, const float *q, const TdRows &rows, hipStream_t s) {
+    const int64_t count = rows.count;
+    const int32_t *cptr = gt.cptr;
     if (count == 0) return TD_OK;
     ArgsH2x ar = {};
     Args16 &a = ar.a;
-    a.x4 = x4_in; a.nbr = nbr; a.ew = ew; a.P = P; a.q = q; a.rows = rows; a.count_ptr = nullptr; a.h = nullptr;
-    a.alpha = alpha; a.x4_out = x4_out; a.count = count; a.mlp = mlp_k; a.offsets = L.offsets; a.coeff = L.coeff; a.p_off = 0;
-    a.cptr = cptr;
+    a = args16(mlp_k, L, x4_in, gt, P, rows);
+    a.ew = gt.ew; a.q = q; a.count_ptr = nullptr; a.x4_out = x4_out; a.p_off = 0;
     ar.mlp_v = mlp_v;
     a.trace = cptr ? nullptr : wg_trace_slot(2);
     const dim3 grid(grid16(count, H2X16_WAVES)), block(H2X16_WAVES * 64);
@@ -2661,10 +2659,11 @@ int td_launch_edge_h2x16(const TdEdgeMlp &mlp_k, const TdEdgeMlp &mlp_v, const T
 }
 
 // ---- edge gate ------------------------------------------------------------------------------------------------------
-int td_launch_gate16(const TdGate &g, const float4 *x4, const int32_t *nbr, int64_t N, const int32_t *rows,
-                     const int32_t *count_ptr, float *ew, hipStream_t s, const int32_t *chunk_node) {
+int td_launch_gate16(const TdGate &g, const float4 *x4, const TdGraphTab &gt, const TdRows &rows, hipStream_t s) {
+    const int64_t N = rows.count;
     if (N == 0) return TD_OK;
     int64_t G = (N + G16_WAVES - 1) / G16_WAVES;
     if (G > TD_GATE_WGS) G = TD_GATE_WGS;              // workgroups per CU x 256
-    return td_launch<edge_gate16_kernel>(dim3((unsigned)G), dim3(G16_WAVES * 64), G16_LDS_BYTES, s, g, x4, nbr, N, rows, count_ptr, chunk_node, ew);
+    return td_launch<edge_gate16_kernel>(dim3((unsigned)G), dim3(G16_WAVES * 64), G16_LDS_BYTES, s, g, x4, gt.nbr, N, rows.rows, rows.count_ptr,
+                                         gt.chunk_node, gt.ew);
 }

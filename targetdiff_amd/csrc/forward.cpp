@@ -40,7 +40,8 @@ extern "C" int td_knn(const float *d_x, const int32_t *d_node_ptr, int64_t N, in
     // the ligand flag (.w) is irrelevant for the search: pack with an all-zero mask (gid is zero-filled scratch)
     rc = td_launch_pack_x(d_x, reinterpret_cast<const uint8_t *>(gid), N, x4, s);
     if (rc == TD_OK) rc = td_launch_node_gid(d_node_ptr, N, B, gid, s);
-    if (rc == TD_OK && k == TD_K) rc = td_launch_knn(x4, d_node_ptr, gid, N, max_graph_nodes, d_out_nbr, s);
+    TdNodes nodes{x4, d_node_ptr, nullptr, gid, N, B, max_graph_nodes};
+    if (rc == TD_OK && k == TD_K) rc = td_launch_knn(nodes, d_out_nbr, TD_K, s);
     else if (rc == TD_OK) {
         // any other k: through the chunked table of the general-graph path (every node counts as "protein": one row kind)
         td_config c = {};
@@ -53,8 +54,8 @@ extern "C" int td_knn(const float *d_x, const int32_t *d_node_ptr, int64_t N, in
         else rc = plan_create(c, hp.data(), hl.data(), B, s, &p);
         if (rc == TD_OK) {
             rc = plan_layout(p, d_node_ptr, gid, s);
-            if (rc == TD_OK) rc = td_launch_graph_general(TD_CUTOFF_KNN, x4, d_node_ptr, p.pptr, gid, nullptr, 0, nullptr, 0, N, k, 0.f,
-                                                          max_graph_nodes, p.cptr, p.cnbr, p.NC, s);
+            nodes.pptr = p.pptr;
+            if (rc == TD_OK) rc = td_launch_graph_general(TD_CUTOFF_KNN, nodes, TdRows{}, TdRows{}, k, 0.f, plan_tab(p), s);
             if (rc == TD_OK) rc = td_launch_slots_to_dense(p.cptr, p.cnbr, N, k, d_out_nbr, s);
             plan_destroy(p, s);
         }
@@ -85,8 +86,9 @@ extern "C" int td_graph_build(const td_model *m, const float *d_x, const uint8_t
     if (rc == TD_OK) rc = plan_from_mask(m->cfg, d_mask_ligand, d_node_ptr, N, B, s, &p, &nl);
     if (rc == TD_OK) {
         rc = plan_layout(p, d_node_ptr, gid, s);
-        if (rc == TD_OK) rc = td_launch_graph_general(p.mode, x4, d_node_ptr, p.pptr, gid, p.prot_node, p.Np, lig, nl, N, p.k, p.radius,
-                                                      max_graph_nodes, p.cptr, p.cnbr, p.NC, s);
+        const TdNodes nodes{x4, d_node_ptr, p.pptr, gid, N, B, max_graph_nodes};
+        if (rc == TD_OK) rc = td_launch_graph_general(p.mode, nodes, TdRows{p.prot_node, nullptr, p.Np}, TdRows{lig, nullptr, nl}, p.k, p.radius,
+                                                      plan_tab(p), s);
         if (rc == TD_OK) rc = td_launch_slots_to_dense(p.cptr, p.cnbr, N, width, d_out_nbr, s);
         plan_destroy(p, s);
     }
@@ -171,7 +173,7 @@ extern "C" int td_model_forward(const td_model *m, const float *d_protein_pos, c
     {
         ProfScope ps(PC_COMPOSE, s);
         if ((rc = td_launch_compose(m, d_protein_pos, d_protein_v, d_protein_ptr, N_p, d_ligand_pos, d_ligand_v, d_ligand_ptr, N_l, B, h,
-                                    w.x4a, w.node_ptr, w.gid, w.lig_node, plan.p.prot_node, s, d_ligand_graph_bias)) != TD_OK) return rc;
+                                    w.x4a, w.node_ptr, w.gid, w.lig_node, plan.p.prot_node, d_ligand_graph_bias, s)) != TD_OK) return rc;
     }
     if (general && (rc = plan_layout(plan.p, w.node_ptr, w.gid, s)) != TD_OK) return rc;
     float4 *xf = nullptr;
@@ -461,8 +463,8 @@ extern "C" int td_egnn_forward(const td_egnn *m, const float *d_h, const float *
     float4 *xc = w.x4a, *xn = w.x4b;
     for (int l = 0; l < m->num_layers; ++l) {
         const TdEgnnLayer &L = m->layers[l];
-        if ((rc = td_launch_knn(xc, d_node_ptr, w.gid, N, max_graph_nodes, w.nbr, s)) != TD_OK) return rc;
-        if ((rc = td_launch_node_proj(L.proj, d_out_h, N, nullptr, 0x03, w.P, w.P, s)) != TD_OK) return rc;
+        if ((rc = td_launch_knn(TdNodes{xc, d_node_ptr, nullptr, w.gid, N, B, max_graph_nodes}, w.nbr, TD_K, s)) != TD_OK) return rc;
+        if ((rc = td_launch_node_proj(L.proj, d_out_h, TdRows{nullptr, nullptr, N}, 0x03, TdRows{}, 0, w.P, w.P, s)) != TD_OK) return rc;
         if ((rc = td_launch_egnn_edge(L, xc, xn, w.nbr, w.P, w.mi, N, s)) != TD_OK) return rc;
         if ((rc = td_launch_egnn_node(L, w.mi, d_out_h, N, s)) != TD_OK) return rc;
         float4 *t = xc; xc = xn; xn = t;
@@ -553,7 +555,8 @@ extern "C" int td_debug_node_stage(const td_model *m, int32_t layer, int32_t sta
         return TD_EINVAL;
     }
     const TdLayer &L = m->layers[layer];
-    return td_launch_node_proj(stage == 0 ? L.nodeX2h : L.nodeH2x, d_h, N, nullptr, 0x1f, d_P, d_q, static_cast<hipStream_t>(stream));
+    return td_launch_node_proj(stage == 0 ? L.nodeX2h : L.nodeH2x, d_h, TdRows{nullptr, nullptr, N}, 0x1f, TdRows{}, 0, d_P, d_q,
+                               static_cast<hipStream_t>(stream));
 }
 
 extern "C" int td_debug_fail_alloc(int32_t nth) {

@@ -81,13 +81,12 @@ __global__ __launch_bounds__(256, 2) void edge_gate_kernel(TdGate g, const float
     }
 }
 
-int td_launch_gate(const TdGate &g, const float4 *x4, const int32_t *nbr, int64_t N, const int32_t *rows,
-                   const int32_t *count_ptr, float *ew, hipStream_t s, const int32_t *chunk_node) {
-    if (N == 0) return TD_OK;
-    if (g.use_split) return td_launch_gate16(g, x4, nbr, N, rows, count_ptr, ew, s, chunk_node);
-    int64_t blocks = (N + 3) / 4;
+int td_launch_gate(const TdGate &g, const float4 *x4, const TdGraphTab &gt, const TdRows &rows, hipStream_t s) {
+    if (rows.count == 0) return TD_OK;
+    if (g.use_split) return td_launch_gate16(g, x4, gt, rows, s);
+    int64_t blocks = (rows.count + 3) / 4;
     if (blocks > 2048) blocks = 2048;
-    edge_gate_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(g, x4, nbr, N, rows, count_ptr, chunk_node, ew);
+    edge_gate_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(g, x4, gt.nbr, rows.count, rows.rows, rows.count_ptr, gt.chunk_node, gt.ew);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
@@ -120,11 +119,13 @@ __global__ void layer_gate_kernel(const float *__restrict__ w, const float *__re
     ew[t] = 1.0f / (1.0f + expf(-logit));
 }
 
-int td_launch_layer_gate(const float *w, const float *offsets, float coeff, const float4 *x4, const int32_t *nbr, int64_t N, float *ew,
+// (the kernel takes row == node and every row: the default graph; rows.count = N)
+int td_launch_layer_gate(const float *w, const float *offsets, float coeff, const float4 *x4, const TdGraphTab &gt, const TdRows &rows,
                          hipStream_t s) {
+    const int64_t N = rows.count;
     if (N == 0) return TD_OK;
     const int64_t total = N * TD_K;
-    layer_gate_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s>>>(w, offsets, coeff, x4, nbr, N, ew);
+    layer_gate_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s>>>(w, offsets, coeff, x4, gt.nbr, N, gt.ew);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }

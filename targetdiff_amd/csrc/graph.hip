@@ -169,38 +169,45 @@ __global__ __launch_bounds__(256) void knn_kernel(const float4 *__restrict__ x4,
     knn_body<CH, STATIC>(blockIdx.x, x4, ptr, gid, rows, N, k, nbr, skeys);
 }
 
+// Candidates per lane (the kernels' CH) for graphs of up to max_graph_nodes nodes, as a template argument: f(std::integral_constant<int, CH>).
+// SMALL4: the kernel family has the 4-candidate form (the general-graph kernels do not)
+template <bool SMALL4, class F>
+static void td_dispatch_ch(int max_graph_nodes, F &&f) {
+    if (SMALL4 && max_graph_nodes > 0 && max_graph_nodes <= 256) {
+        if constexpr (SMALL4) f(std::integral_constant<int, 4>{});
+    } else if (max_graph_nodes > 0 && max_graph_nodes <= 384) {
+        f(std::integral_constant<int, 6>{});
+    } else if (max_graph_nodes <= 704) {         // also the "unknown" (0) default
+        f(std::integral_constant<int, 11>{});
+    } else {
+        f(std::integral_constant<int, 17>{});
+    }
+}
+
 template <bool STATIC>
-static int launch_knn_t(const float4 *x4, const int32_t *node_ptr, const int32_t *gid, const int32_t *rows, int64_t N,
-                        int max_graph_nodes, int k, int32_t *nbr, unsigned long long *skeys, hipStream_t s) {
+static int launch_knn_t(const TdNodes &nd, const TdRows &rows, int k, int32_t *nbr, unsigned long long *skeys, hipStream_t s) {
+    const int64_t N = rows.count;
     if (N == 0) return TD_OK;
     dim3 grid((unsigned)((N + 3) / 4)), block(256);
-    if (max_graph_nodes > 0 && max_graph_nodes <= 256)
-        knn_kernel<4, STATIC><<<grid, block, 0, s>>>(x4, node_ptr, gid, rows, N, k, nbr, skeys);
-    else if (max_graph_nodes > 0 && max_graph_nodes <= 384)
-        knn_kernel<6, STATIC><<<grid, block, 0, s>>>(x4, node_ptr, gid, rows, N, k, nbr, skeys);
-    else if (max_graph_nodes <= 704)         // also the "unknown" (0) default
-        knn_kernel<11, STATIC><<<grid, block, 0, s>>>(x4, node_ptr, gid, rows, N, k, nbr, skeys);
-    else
-        knn_kernel<17, STATIC><<<grid, block, 0, s>>>(x4, node_ptr, gid, rows, N, k, nbr, skeys);
+    td_dispatch_ch<true>(nd.max_graph_nodes, [&](auto CH) {
+        knn_kernel<decltype(CH)::value, STATIC><<<grid, block, 0, s>>>(nd.x4, nd.node_ptr, nd.gid, rows.rows, N, k, nbr, skeys);
+    });
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
 
-int td_launch_knn(const float4 *x4, const int32_t *node_ptr, const int32_t *gid, int64_t N, int max_graph_nodes,
-                  int32_t *nbr, hipStream_t s, int k) {
-    return launch_knn_t<false>(x4, node_ptr, gid, nullptr, N, max_graph_nodes, k, nbr, nullptr, s);
+int td_launch_knn(const TdNodes &nd, int32_t *nbr, int k, hipStream_t s) {
+    return launch_knn_t<false>(nd, TdRows{nullptr, nullptr, nd.N}, k, nbr, nullptr, s);
 }
 
 // kNN of the listed query rows only (ligand atoms of a session step): full search over the query's graph.
-int td_launch_knn_rows(const float4 *x4, const int32_t *node_ptr, const int32_t *gid, const int32_t *rows, int64_t count,
-                       int max_graph_nodes, int32_t *nbr, hipStream_t s, int k) {
-    return launch_knn_t<false>(x4, node_ptr, gid, rows, count, max_graph_nodes, k, nbr, nullptr, s);
+int td_launch_knn_rows(const TdNodes &nd, const TdRows &rows, int32_t *nbr, int k, hipStream_t s) {
+    return launch_knn_t<false>(nd, rows, k, nbr, nullptr, s);
 }
 
 // Protein-only neighbour lists + their sorted keys for the listed (protein) rows.
-int td_launch_knn_static(const float4 *x4, const int32_t *node_ptr, const int32_t *gid, const int32_t *rows, int64_t count,
-                         int max_graph_nodes, int32_t *nbr, unsigned long long *skeys, hipStream_t s, int k) {
-    return launch_knn_t<true>(x4, node_ptr, gid, rows, count, max_graph_nodes, k, nbr, skeys, s);
+int td_launch_knn_static(const TdNodes &nd, const TdRows &rows, int32_t *nbr, unsigned long long *skeys, int k, hipStream_t s) {
+    return launch_knn_t<true>(nd, rows, k, nbr, skeys, s);
 }
 
 // ------------------------------------------------------------------------------------------ session step: kNN merge
@@ -209,10 +216,7 @@ int td_launch_knn_static(const float4 *x4, const int32_t *node_ptr, const int32_
 // list.  If no ligand atom beats the 32nd static neighbour the row is unchanged ("clean"): its gate row and its
 // layer-0 output are step-invariant too and are copied from the session cache instead of being recomputed.
 // One wave per protein row.  Ligand rows of a graph are contiguous: [node_ptr[g] + n_prot(g), node_ptr[g+1]).
-// cgraph / cbase (a session that shares its static tables between the replicas of a pocket, session.cpp): graph g's protein block is a bitwise
-// copy of graph cgraph[g]'s (the first such graph of the batch: cgraph[g] <= g), whose rows sit at cbase[g] .. in the COMPACT static tables
-// skeys / snbr / ews / h0 / h1s; row i of graph g reads compact row cbase[g] + (i - ptr[g]) and shifts the node indices it finds there (they
-// are the canonical graph's) by ptr[g] - ptr[cgraph[g]].  nullptr: the tables are indexed by node.
+// cgraph / cbase: the compact per-pocket form of the static tables (TdStaticTabs, td_internal.h).
 struct TdMergeArgs {
     const float4 *x4; const int32_t *ptr, *pptr, *gid, *prot_rows; int64_t Np;
     const unsigned long long *skeys; const int32_t *snbr; const float *h0, *h1s, *ews; int32_t *nbr; float *h, *ew;
@@ -357,22 +361,18 @@ __global__ __launch_bounds__(256) void knn_step_kernel(TdMergeArgs ma, unsigned 
     else knn_merge_body(blockIdx.x - GB, ma);
 }
 
-int td_launch_knn_merge(const float4 *x4, const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid,
-                        const int32_t *prot_rows, int64_t Np, const unsigned long long *skeys, const int32_t *snbr,
-                        const float *h0, const float *h1s, const float *ews, int32_t *nbr, float *h, float *ew,
-                        uint8_t *clean, uint8_t *flags2, hipStream_t s, int k, const int32_t *lig_rows, int64_t Nl,
-                        int max_graph_nodes, const int32_t *cgraph, const int32_t *cbase) {
-    const TdMergeArgs ma{x4, node_ptr, pptr, gid, prot_rows, Np, skeys, snbr, h0, h1s, ews, nbr, h, ew, clean, flags2, k, cgraph, cbase};
-    const unsigned GA = (unsigned)((Np + 3) / 4), GB = lig_rows ? (unsigned)((Nl + 3) / 4) : 0u;
+int td_launch_knn_merge(const TdNodes &nd, const TdRows &prot, const TdRows &lig, const TdStaticTabs &tabs, const TdGraphTab &gt, float *h,
+                        uint8_t *clean, uint8_t *flags2, int k, hipStream_t s) {
+    const TdMergeArgs ma{nd.x4, nd.node_ptr, nd.pptr, nd.gid, prot.rows, prot.count, tabs.skeys, tabs.snbr, tabs.h0, tabs.h1s, tabs.ews,
+                         gt.nbr, h, gt.ew, clean, flags2, k, tabs.cgraph, tabs.cbase};
+    const unsigned GA = (unsigned)((prot.count + 3) / 4), GB = lig.rows ? (unsigned)((lig.count + 3) / 4) : 0u;
     if (GA + GB == 0) return TD_OK;
     if (GB == 0) {
         knn_merge_kernel<<<dim3(GA), dim3(256), 0, s>>>(ma);
-    } else {           // (the same candidates-per-lane variants as launch_knn_t)
-        const dim3 grid(GA + GB), block(256);
-        if (max_graph_nodes > 0 && max_graph_nodes <= 256) knn_step_kernel<4><<<grid, block, 0, s>>>(ma, GB, lig_rows, Nl, nbr);
-        else if (max_graph_nodes > 0 && max_graph_nodes <= 384) knn_step_kernel<6><<<grid, block, 0, s>>>(ma, GB, lig_rows, Nl, nbr);
-        else if (max_graph_nodes <= 704) knn_step_kernel<11><<<grid, block, 0, s>>>(ma, GB, lig_rows, Nl, nbr);       // also the "unknown" (0) default
-        else knn_step_kernel<17><<<grid, block, 0, s>>>(ma, GB, lig_rows, Nl, nbr);
+    } else {
+        td_dispatch_ch<true>(nd.max_graph_nodes, [&](auto CH) {
+            knn_step_kernel<decltype(CH)::value><<<dim3(GA + GB), dim3(256), 0, s>>>(ma, GB, lig.rows, lig.count, gt.nbr);
+        });
     }
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
@@ -452,13 +452,13 @@ __global__ __launch_bounds__(256) void knn_merge_general_kernel(
     }
 }
 
-int td_launch_knn_merge_general(const float4 *x4, const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid,
-                                const int32_t *prot_rows, int64_t Np, const unsigned long long *skeys, const int32_t *snbr,
-                                const float *h0, const float *h1s, const float *ews, const int32_t *cptr, int cpn, int32_t *nbr,
-                                float *h, float *ew, uint8_t *clean, uint8_t *flags2, hipStream_t s, int k) {
-    if (Np == 0) return TD_OK;
-    knn_merge_general_kernel<<<dim3((unsigned)((Np + 3) / 4)), dim3(256), 0, s>>>(x4, node_ptr, pptr, gid, prot_rows, Np, skeys, snbr,
-                                                                                h0, h1s, ews, cptr, cpn, nbr, h, ew, clean, flags2, k);
+// (the ligand rows of a general graph take a launch of their own, td_launch_ligand_rows_general)
+int td_launch_knn_merge_general(const TdNodes &nd, const TdRows &prot, const TdStaticTabs &tabs, const TdGraphTab &gt, float *h,
+                                uint8_t *clean, uint8_t *flags2, int k, hipStream_t s) {
+    if (prot.count == 0) return TD_OK;
+    knn_merge_general_kernel<<<dim3((unsigned)((prot.count + 3) / 4)), dim3(256), 0, s>>>(
+        nd.x4, nd.node_ptr, nd.pptr, nd.gid, prot.rows, prot.count, tabs.skeys, tabs.snbr, tabs.h0, tabs.h1s, tabs.ews, gt.cptr, gt.cpn_p, gt.nbr,
+        h, gt.ew, clean, flags2, k);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
@@ -571,11 +571,10 @@ __global__ void restore_rows_kernel(const int32_t *__restrict__ rows, const int3
     h[i * 32 + (t & 31)] = hs[c * 32 + (t & 31)];
 }
 
-int td_launch_restore_rows(const int32_t *rows, const int32_t *count_ptr, int64_t max_rows, const float *hs, float *h,
-                           hipStream_t s, const int32_t *gid, const int32_t *node_ptr, const int32_t *cbase) {
-    if (max_rows == 0) return TD_OK;
-    restore_rows_kernel<<<dim3((unsigned)((max_rows * 32 + 255) / 256)), dim3(256), 0, s>>>(
-        rows, count_ptr, reinterpret_cast<const float4 *>(hs), reinterpret_cast<float4 *>(h), gid, node_ptr, cbase);
+int td_launch_restore_rows(const TdRows &rows, const float *hs, float *h, const TdNodes &nd, const TdStaticTabs &tabs, hipStream_t s) {
+    if (rows.count == 0) return TD_OK;
+    restore_rows_kernel<<<dim3((unsigned)((rows.count * 32 + 255) / 256)), dim3(256), 0, s>>>(
+        rows.rows, rows.count_ptr, reinterpret_cast<const float4 *>(hs), reinterpret_cast<float4 *>(h), nd.gid, nd.node_ptr, tabs.cbase);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
@@ -691,8 +690,10 @@ __global__ __launch_bounds__(256) void compact_levels_kernel(const uint8_t *__re
 
 // rows: [levels][N] row lists, counts: [levels] device-side lengths
 // `zeroed`: flags and counts were already cleared earlier in the step (compact_split_kernel / ligand_update_kernel)
-int td_launch_hop_levels(const int32_t *lig_node, int64_t Nl, const int32_t *nbr, int64_t N, uint8_t *flags,
-                         int32_t *rows, int32_t *counts, int levels, hipStream_t s, bool zeroed) {
+int td_launch_hop_levels(const TdRows &lig, const TdGraphTab &gt, int64_t N, uint8_t *flags, int32_t *rows, int32_t *counts, int levels,
+                         bool zeroed, hipStream_t s) {
+    const int32_t *lig_node = lig.rows, *nbr = gt.nbr;
+    const int64_t Nl = lig.count;
     if (N == 0 || levels <= 0) return TD_OK;
     if (levels > TD_HOP_LEVELS) levels = TD_HOP_LEVELS;
     if (!zeroed) {
@@ -853,17 +854,16 @@ __global__ __launch_bounds__(TD_LISTS_THREADS) void step_lists_kernel(const uint
 
 // `max_nodes`: an upper bound on the nodes of one graph (exact, not a hint: it sizes the LDS flag arrays).  Counters are zeroed
 // by the step's first kernel.  Returns TD_EINVAL when a graph is too large for LDS (the caller then uses the separate kernels).
-int td_launch_step_lists(const uint8_t *clean, const float4 *x4, const int32_t *nbr, const int32_t *node_ptr, int64_t N,
-                         int64_t B, int max_nodes, const TdStepLists &out, hipStream_t s, const int32_t *cptr,
-                         const int32_t *chunk_node) {
-    if (N == 0 || B == 0) return TD_OK;
+int td_launch_step_lists(const uint8_t *clean, const TdNodes &nd, const TdGraphTab &gt, int max_nodes, const TdStepLists &out, hipStream_t s) {
+    if (nd.N == 0 || nd.B == 0) return TD_OK;
     const int cap = (max_nodes + 15) & ~15;
     const size_t bytes = (size_t)4 * cap;
     if (bytes > 48 * 1024 || out.levels > TD_HOP_LEVELS) return TD_EINVAL;
-    if (cptr)
-        step_lists_kernel<true><<<dim3((unsigned)B), dim3(TD_LISTS_THREADS), bytes, s>>>(clean, x4, nbr, node_ptr, cptr, chunk_node, N, cap, out);
+    const dim3 grid((unsigned)nd.B), block(TD_LISTS_THREADS);
+    if (gt.cptr)
+        step_lists_kernel<true><<<grid, block, bytes, s>>>(clean, nd.x4, gt.nbr, nd.node_ptr, gt.cptr, gt.chunk_node, nd.N, cap, out);
     else
-        step_lists_kernel<false><<<dim3((unsigned)B), dim3(TD_LISTS_THREADS), bytes, s>>>(clean, x4, nbr, node_ptr, nullptr, nullptr, N, cap, out);
+        step_lists_kernel<false><<<grid, block, bytes, s>>>(clean, nd.x4, gt.nbr, nd.node_ptr, nullptr, nullptr, nd.N, cap, out);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
@@ -972,7 +972,7 @@ __global__ void node_ptr_kernel(const int32_t *__restrict__ pptr, const int32_t 
 int td_launch_compose(const td_model *m, const float *ppos, const float *pv, const int32_t *pptr, int64_t Np,
                       const float *lpos, const int64_t *lv, const int32_t *lptr, int64_t Nl, int64_t B,
                       float *h, float4 *x4, int32_t *node_ptr, int32_t *gid, int32_t *lig_node, int32_t *prot_node,
-                      hipStream_t s, const float *gbias) {
+                      const float *gbias, hipStream_t s) {
     node_ptr_kernel<<<dim3((unsigned)((B + 1 + 255) / 256)), dim3(256), 0, s>>>(pptr, lptr, (int)B, node_ptr);
     TD_CHECK_HIP(hipGetLastError());
     if (Np > 0) {
@@ -992,9 +992,10 @@ int td_launch_compose(const td_model *m, const float *ppos, const float *pv, con
     return TD_OK;
 }
 
-int td_launch_ligand_update(const td_model *m, const float *lpos, const int64_t *lv, const int32_t *lig_node, int64_t Nl,
-                            float *h, float4 *x4, hipStream_t s, const TdStepReset *reset, const float *gbias,
-                            const int32_t *gid) {
+int td_launch_ligand_update(const td_model *m, const float *lpos, const int64_t *lv, const TdRows &lig, float *h, float4 *x4,
+                            const TdStepReset *reset, const float *gbias, const int32_t *gid, hipStream_t s) {
+    const int32_t *lig_node = lig.rows;
+    const int64_t Nl = lig.count;
     if (Nl == 0) return TD_OK;
     unsigned nb = (unsigned)((Nl + TD_COMPOSE_ATOMS - 1) / TD_COMPOSE_ATOMS);
     const TdStepReset rs = reset ? *reset : TdStepReset{};
@@ -1111,10 +1112,10 @@ __global__ void hybrid_ligand_kernel(const int32_t *__restrict__ ptr, const int3
     }
 }
 
-int td_launch_hybrid_ligand_half(const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid, const int32_t *lig_node,
-                                 int64_t Nl, const int32_t *cptr, int32_t *cnbr, hipStream_t s) {
-    if (Nl == 0) return TD_OK;
-    hybrid_ligand_kernel<<<dim3((unsigned)((Nl + 3) / 4)), dim3(256), 0, s>>>(node_ptr, pptr, gid, lig_node, Nl, cptr, cnbr);
+int td_launch_hybrid_ligand_half(const TdNodes &nd, const TdRows &lig, const TdGraphTab &gt, hipStream_t s) {
+    if (lig.count == 0) return TD_OK;
+    hybrid_ligand_kernel<<<dim3((unsigned)((lig.count + 3) / 4)), dim3(256), 0, s>>>(nd.node_ptr, nd.pptr, nd.gid, lig.rows, lig.count, gt.cptr,
+                                                                                   gt.nbr);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
@@ -1146,57 +1147,49 @@ __global__ __launch_bounds__(256) void radius_kernel(const float4 *__restrict__ 
     }
 }
 
+// the rows `rows` of the chunked table gt (its cptr and nbr); skeys: MODE 2 only
 template <int MODE>
-static int launch_knn_general(const float4 *x4, const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid,
-                              const int32_t *rows, int64_t count, int k, int max_graph_nodes, const int32_t *cptr,
-                              int32_t *cnbr, hipStream_t s, unsigned long long *skeys = nullptr) {
-    if (count == 0) return TD_OK;
-    dim3 grid((unsigned)((count + 3) / 4)), block(256);
-    if (max_graph_nodes > 0 && max_graph_nodes <= 384)
-        knn_general_kernel<6, MODE><<<grid, block, 0, s>>>(x4, node_ptr, pptr, gid, rows, count, k, cptr, cnbr, skeys);
-    else if (max_graph_nodes <= 704)
-        knn_general_kernel<11, MODE><<<grid, block, 0, s>>>(x4, node_ptr, pptr, gid, rows, count, k, cptr, cnbr, skeys);
-    else
-        knn_general_kernel<17, MODE><<<grid, block, 0, s>>>(x4, node_ptr, pptr, gid, rows, count, k, cptr, cnbr, skeys);
+static int launch_knn_general(const TdNodes &nd, const TdRows &rows, int k, const TdGraphTab &gt, unsigned long long *skeys, hipStream_t s) {
+    if (rows.count == 0) return TD_OK;
+    dim3 grid((unsigned)((rows.count + 3) / 4)), block(256);
+    td_dispatch_ch<false>(nd.max_graph_nodes, [&](auto CH) {
+        knn_general_kernel<decltype(CH)::value, MODE><<<grid, block, 0, s>>>(nd.x4, nd.node_ptr, nd.pptr, nd.gid, rows.rows, rows.count, k, gt.cptr,
+                                                                           gt.nbr, skeys);
+    });
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }
 
-// Session of a general k-NN / hybrid graph: the protein-only lists (sorted keys kept) of the listed protein rows
-int td_launch_knn_general_static(const float4 *x4, const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid,
-                                 const int32_t *prot_rows, int64_t Np, int k, int max_graph_nodes, const int32_t *cptr,
-                                 int32_t *snbr, unsigned long long *skeys, hipStream_t s) {
-    return launch_knn_general<2>(x4, node_ptr, pptr, gid, prot_rows, Np, k, max_graph_nodes, cptr, snbr, s, skeys);
+// Session of a general k-NN / hybrid graph: the protein-only lists (into gt.nbr; sorted keys kept) of the listed protein rows
+int td_launch_knn_general_static(const TdNodes &nd, const TdRows &prot, int k, const TdGraphTab &gt, unsigned long long *skeys, hipStream_t s) {
+    return launch_knn_general<2>(nd, prot, k, gt, skeys, s);
 }
 
 // Per-step neighbour rows of the ligand atoms on a general graph: k-NN rows over the whole graph, or (hybrid) the k nearest
 // protein atoms behind the other ligand atoms of the graph (that half is step-invariant and written once by
 // td_launch_hybrid_ligand_half).  The rows' slots must hold -1 where nothing is written (k-NN: fewer than k candidates).
-int td_launch_ligand_rows_general(int mode, const float4 *x4, const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid,
-                                  const int32_t *lig_node, int64_t Nl, int k, int max_graph_nodes, const int32_t *cptr,
-                                  int32_t *cnbr, hipStream_t s) {
-    if (mode == 1) return launch_knn_general<1>(x4, node_ptr, pptr, gid, lig_node, Nl, k, max_graph_nodes, cptr, cnbr, s);
-    return launch_knn_general<0>(x4, node_ptr, pptr, gid, lig_node, Nl, k, max_graph_nodes, cptr, cnbr, s);
+int td_launch_ligand_rows_general(int mode, const TdNodes &nd, const TdRows &lig, int k, const TdGraphTab &gt, hipStream_t s) {
+    if (mode == 1) return launch_knn_general<1>(nd, lig, k, gt, nullptr, s);
+    return launch_knn_general<0>(nd, lig, k, gt, nullptr, s);
 }
 
 // Fill the chunk table of a general graph.  mode 0: k-NN (any k <= 64) on every row; 1: hybrid (protein rows: k-NN over
-// the whole graph; ligand rows: the other ligand atoms + the k nearest protein atoms); 2: radius r with fan-out cap.
-int td_launch_graph_general(int mode, const float4 *x4, const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid,
-                            const int32_t *prot_node, int64_t Np, const int32_t *lig_node, int64_t Nl, int64_t N, int k,
-                            float radius, int max_graph_nodes, const int32_t *cptr, int32_t *cnbr, int64_t NC, hipStream_t s) {
-    TD_CHECK_HIP(hipMemsetAsync(cnbr, 0xff, (size_t)NC * TD_K * sizeof(int32_t), s));
+// the whole graph; ligand rows: the other ligand atoms + the k nearest protein atoms); 2: radius r with fan-out cap k.
+int td_launch_graph_general(int mode, const TdNodes &nd, const TdRows &prot, const TdRows &lig, int k, float radius, const TdGraphTab &gt,
+                            hipStream_t s) {
+    TD_CHECK_HIP(hipMemsetAsync(gt.nbr, 0xff, (size_t)gt.NC * TD_K * sizeof(int32_t), s));
     int rc = TD_OK;
     if (mode == 0) {
-        rc = launch_knn_general<0>(x4, node_ptr, pptr, gid, nullptr, N, k, max_graph_nodes, cptr, cnbr, s);
+        rc = launch_knn_general<0>(nd, TdRows{nullptr, nullptr, nd.N}, k, gt, nullptr, s);
     } else if (mode == 1) {
-        rc = launch_knn_general<0>(x4, node_ptr, pptr, gid, prot_node, Np, k, max_graph_nodes, cptr, cnbr, s);
-        if (rc == TD_OK && Nl > 0) {
-            rc = td_launch_hybrid_ligand_half(node_ptr, pptr, gid, lig_node, Nl, cptr, cnbr, s);
-            if (rc == TD_OK) rc = launch_knn_general<1>(x4, node_ptr, pptr, gid, lig_node, Nl, k, max_graph_nodes, cptr, cnbr, s);
+        rc = launch_knn_general<0>(nd, prot, k, gt, nullptr, s);
+        if (rc == TD_OK && lig.count > 0) {
+            rc = td_launch_hybrid_ligand_half(nd, lig, gt, s);
+            if (rc == TD_OK) rc = launch_knn_general<1>(nd, lig, k, gt, nullptr, s);
         }
     } else {
-        if (N > 0) {
-            radius_kernel<<<dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s>>>(x4, node_ptr, gid, N, radius * radius, k, cptr, cnbr);
+        if (nd.N > 0) {
+            radius_kernel<<<dim3((unsigned)((nd.N + 3) / 4)), dim3(256), 0, s>>>(nd.x4, nd.node_ptr, nd.gid, nd.N, radius * radius, k, gt.cptr, gt.nbr);
             TD_CHECK_HIP(hipGetLastError());
         }
     }
@@ -1222,11 +1215,10 @@ int td_launch_slots_to_dense(const int32_t *cptr, const int32_t *cnbr, int64_t N
 }
 
 // radius graph with a fan-out cap <= 32 straight into the 32-slot neighbour table of the fast path
-int td_launch_radius32(const float4 *x4, const int32_t *node_ptr, const int32_t *gid, int64_t N, float radius, int cap,
-                       int32_t *nbr, hipStream_t s) {
-    if (N == 0) return TD_OK;
-    TD_CHECK_HIP(hipMemsetAsync(nbr, 0xff, (size_t)N * TD_K * sizeof(int32_t), s));
-    radius_kernel<<<dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s>>>(x4, node_ptr, gid, N, radius * radius, cap, nullptr, nbr);
+int td_launch_radius32(const TdNodes &nd, float radius, int cap, int32_t *nbr, hipStream_t s) {
+    if (nd.N == 0) return TD_OK;
+    TD_CHECK_HIP(hipMemsetAsync(nbr, 0xff, (size_t)nd.N * TD_K * sizeof(int32_t), s));
+    radius_kernel<<<dim3((unsigned)((nd.N + 3) / 4)), dim3(256), 0, s>>>(nd.x4, nd.node_ptr, nd.gid, nd.N, radius * radius, cap, nullptr, nbr);
     TD_CHECK_HIP(hipGetLastError());
     return TD_OK;
 }

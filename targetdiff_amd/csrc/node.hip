@@ -510,28 +510,28 @@ static int np_launch(const NpArgs &a, const float *h, unsigned total_blocks, hip
     return td_launch<node_proj_kernel>(grid, block, NP_LDS_BYTES, s, a, h);
 }
 
-int td_launch_node_proj(const TdNodeStage &st, const float *h, int64_t N, const int32_t *rows, unsigned mat_mask,
-                        float *P, float *q, hipStream_t s, const int32_t *count_ptr, const int32_t *rows2, int64_t N2,
-                        unsigned mask2) {
+int td_launch_node_proj(const TdNodeStage &st, const float *h, const TdRows &rows, unsigned mat_mask, const TdRows &rows2, unsigned mask2,
+                        float *P, float *q, hipStream_t s) {
+    const int64_t N = rows.count;
     if (N == 0 || mat_mask == 0) return TD_OK;
-    if (!rows2 || N2 == 0 || (mask2 & 0x1fu) == 0) { rows2 = nullptr; N2 = 0; mask2 = 0; }
+    const bool second = rows2.rows && rows2.count != 0 && (mask2 & 0x1fu) != 0;
     NpArgs a;
     a.nseg = 0;
     unsigned total = 0;
     // a small batch (N bounds the device-side count) cannot fill the chip with one workgroup per 128 rows walking through
     // all six GEMMs: one workgroup per (128 rows, matrix unit) instead -- 5x the parallelism, same arithmetic
-    total += np_fill(a.seg[a.nseg++], st, rows, count_ptr, N, mat_mask, P, q, N <= TD_SMALL_BATCH_ROWS, 128);
-    if (rows2) total += np_fill(a.seg[a.nseg++], st, rows2, nullptr, N2, mask2, P, q, true, 128);
+    total += np_fill(a.seg[a.nseg++], st, rows.rows, rows.count_ptr, N, mat_mask, P, q, N <= TD_SMALL_BATCH_ROWS, 128);
+    if (second) total += np_fill(a.seg[a.nseg++], st, rows2.rows, nullptr, rows2.count, mask2, P, q, true, 128);
     return np_launch(a, h, total, s);
 }
 
-// The h2x-stage projections of layer l (stage `hx`: src-side units on `hop_rows`, dst-side units + queries on the ligand
-// rows, into Px / qx) and the x2h-stage projections of layer l + 1 (stage `nx`, all units on `rows` or every node, into
-// P / q) in one launch: both read the features the value pass of layer l just wrote.
-int td_launch_node_proj_pair(const TdNodeStage &hx, const int32_t *hop_rows, const int32_t *hop_count,
-                             const int32_t *lig_rows, int64_t Nl, float *Px, float *qx, const TdNodeStage &nx,
-                             const int32_t *rows, const int32_t *count_ptr, float *P, float *q, const float *h, int64_t N,
-                             hipStream_t s) {
+// The h2x-stage projections of layer l (stage `hx`: src-side units on `hop`, dst-side units + queries on the ligand
+// rows, into Px / qx) and the x2h-stage projections of layer l + 1 (stage `nx`, all units on `rows`, into
+// P / q) in one launch: both read the features the value pass of layer l just wrote.  hop and rows are lists with device counts or
+// every node: both bounded by the N nodes of the batch (rows.count).
+int td_launch_node_proj_pair(const TdNodeStage &hx, const TdRows &hop, const TdRows &lig, float *Px, float *qx, const TdNodeStage &nx,
+                             const TdRows &rows, float *P, float *q, const float *h, hipStream_t s) {
+    const int64_t N = rows.count;
     if (N == 0) return TD_OK;
     NpArgs a;
     a.nseg = 0;
@@ -543,9 +543,9 @@ int td_launch_node_proj_pair(const TdNodeStage &hx, const int32_t *hop_rows, con
     // (projections 0.765 -> 0.729 ms per C2 step).  Over many rounds (C3: 8,140 long workgroups) the second tile load costs
     // throughput instead (+2.5 %): both units in one workgroup.
     const bool one_round = (N + 127) / 128 <= 512;
-    total += np_fill(a.seg[a.nseg++], nx, rows, rows ? count_ptr : nullptr, N, 0x1f, P, q, N <= TD_SMALL_BATCH_ROWS, 128);
-    if (Nl > 0) total += np_fill(a.seg[a.nseg++], hx, lig_rows, nullptr, Nl, 0x15, Px, qx, true, 128);
-    total += np_fill(a.seg[a.nseg++], hx, hop_rows, hop_rows ? hop_count : nullptr, N, 0x0a, Px, qx, one_round, 128);
+    total += np_fill(a.seg[a.nseg++], nx, rows.rows, rows.rows ? rows.count_ptr : nullptr, N, 0x1f, P, q, N <= TD_SMALL_BATCH_ROWS, 128);
+    if (lig.count > 0) total += np_fill(a.seg[a.nseg++], hx, lig.rows, nullptr, lig.count, 0x15, Px, qx, true, 128);
+    total += np_fill(a.seg[a.nseg++], hx, hop.rows, hop.rows ? hop.count_ptr : nullptr, N, 0x0a, Px, qx, one_round, 128);
     return np_launch(a, h, total, s);
 }
 

@@ -38,36 +38,25 @@ Workspace carve(char *base, int64_t N, int64_t B, int64_t Nl) {
     return w;
 }
 
-// lig / Nl (x2h passes): the ligand rows of the batch, all of them among the selected rows (every row list of a step contains the ligand atoms)
-int key_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const float *P, const float *q, const RowSel &r,
-             hipStream_t s, const int32_t *lig, int64_t Nl, bool h2x_stage) {
-    return td_launch_edge_key16(mlp, L, x4, gt.nbr, gt.ew, P, q, r.rows, r.count_ptr, r.count, gt.alpha, s, h2x_stage, gt.cptr, lig, Nl, gt.cpn_p);
-}
-int value_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const float *P, const RowSel &r, float *h,
-               const int32_t *lig, int64_t Nl, hipStream_t s, float *out) {
-    return td_launch_edge_value16(mlp, L, x4, gt.nbr, P, r.rows, r.count_ptr, r.count, h, gt.alpha, lig, Nl, s, gt.cptr, gt.cpn_p,
-                                  lig ? gt.NCl : 0, gt.mixed, out, L.gate_m);
-}
-
 // One x2h stage of layer L on the rows a.rows: the projections (unless they are in place), the stage's own gate (ew_net_type 'r' / none:
 // from the layer's coordinates, every row), key pass, value pass into h, node_output (x2h_out_fc) on every row.
-int x2h_stage(const TdLayer &L, const GraphTab &gt, const float4 *xc, float *h, int64_t N, const X2hStage &a, hipStream_t s) {
+int x2h_stage(const TdLayer &L, const TdGraphTab &gt, const float4 *xc, float *h, int64_t N, const X2hStage &a, hipStream_t s) {
     int rc;
     const float *h_in = a.h_in ? a.h_in : h;
     if (a.project) {
         ProfScope ps(PC_NODE, s, a.scoped);
-        if ((rc = td_launch_node_proj(L.nodeX2h, h_in, a.proj.count, a.proj.rows, 0x1f, a.P, a.q, s, a.proj.count_ptr)) != TD_OK) return rc;
+        if ((rc = td_launch_node_proj(L.nodeX2h, h_in, a.proj, 0x1f, TdRows{}, 0, a.P, a.q, s)) != TD_OK) return rc;
     }
     if (L.ew_x2h) {
         ProfScope ps(PC_GATE, s, a.scoped);
-        if ((rc = td_launch_layer_gate(L.ew_x2h, L.offsets, L.coeff, xc, gt.nbr, N, gt.ew, s)) != TD_OK) return rc;
+        if ((rc = td_launch_layer_gate(L.ew_x2h, L.offsets, L.coeff, xc, gt, TdRows{nullptr, nullptr, N}, s)) != TD_OK) return rc;
     }
-    { ProfScope ps(PC_X2H_K, s, a.scoped); if ((rc = key_pass(L.hk, L, xc, gt, a.P, a.q, a.rows, s, a.lig, a.Nl)) != TD_OK) return rc; }
+    { ProfScope ps(PC_X2H_K, s, a.scoped); if ((rc = td_launch_edge_key16(L.hk, L, xc, gt, a.P, a.q, a.rows, a.lig, false, s)) != TD_OK) return rc; }
     if (h_in != h) TD_CHECK_HIP(hipMemcpyAsync(h, h_in, (size_t)N * TD_H * sizeof(float), hipMemcpyDeviceToDevice, s));
     // x2h_out_fc: the attention output goes to q (the queries are spent once the key pass is done) without the residual, and
     // node_output([output | h]) + h follows on every row
     float *att_out = L.nodeOut.B ? a.q : nullptr;
-    { ProfScope ps(PC_X2H_V, s, a.scoped); if ((rc = value_pass(L.hv, L, xc, gt, a.P, a.rows, h, a.lig, a.Nl, s, att_out)) != TD_OK) return rc; }
+    { ProfScope ps(PC_X2H_V, s, a.scoped); if ((rc = td_launch_edge_value16(L.hv, L, xc, gt, a.P, a.rows, a.lig, h, att_out, s)) != TD_OK) return rc; }
     if (att_out) {
         ProfScope ps(PC_NODE, s, a.scoped);
         if ((rc = td_launch_node_output(L.nodeOut, att_out, h, N, s)) != TD_OK) return rc;
@@ -78,27 +67,28 @@ int x2h_stage(const TdLayer &L, const GraphTab &gt, const float4 *xc, float *h, 
 // h2x stage, projections in one launch: src-side (k_j, v_j) of the nodes a ligand atom can see -- `hop` (the ligand atoms and their
 // neighbours, fixed for the step) when the caller has the list, every node otherwise -- plus, as a second segment, the dst-side
 // projections and queries of the ligand atoms
-int h2x_project(const TdLayer &L, Workspace &w, float *h, int64_t Nl, float *P, float *q, const RowSel &hop, hipStream_t s) {
+int h2x_project(const TdLayer &L, Workspace &w, float *h, int64_t Nl, float *P, float *q, const TdRows &hop, hipStream_t s) {
     ProfScope ps(PC_NODE, s);
-    return td_launch_node_proj(L.nodeH2x, h, hop.count, hop.rows, 0x0a, P, q, s, hop.count_ptr, w.lig_node, Nl, 0x15);
+    return td_launch_node_proj(L.nodeH2x, h, hop, 0x0a, TdRows{w.lig_node, nullptr, Nl}, 0x15, P, q, s);
 }
 
 // attention over the ligand atoms' edges and the coordinate update xc -> xn.  Rows of several chunks (general graphs) take the
 // two-launch form (keys + softmax over all chunks of a row -> alpha in memory -> xv); one 32-slot row per node: fused.
-int h2x_attend(const td_model *m, const TdLayer &L, Workspace &w, const GraphTab &gt, int64_t Nl, float4 *xc, float4 *xn, float *P,
+int h2x_attend(const td_model *m, const TdLayer &L, Workspace &w, const TdGraphTab &gt, int64_t Nl, float4 *xc, float4 *xn, float *P,
                float *q, hipStream_t s) {
     int rc;
+    const TdRows lig{w.lig_node, nullptr, Nl};
     if (m->opt.h2x_fused && (!gt.cptr || (L.xk.use_split && L.xv.use_split))) {
         // (general graphs: the chunk-walking fused form exists for the bf16 first layer; alpha holds the logits between its two sweeps)
         ProfScope ps(PC_H2X_K, s);
-        return td_launch_edge_h2x16(L.xk, L.xv, L, xc, xn, gt.nbr, gt.ew, P, q, w.lig_node, Nl, s, gt.cptr, gt.alpha);
+        return td_launch_edge_h2x16(L.xk, L.xv, L, xc, xn, gt, P, q, lig, s);
     }
     {
         ProfScope ps(PC_H2X_K, s);
-        if ((rc = key_pass(L.xk, L, xc, gt, P, q, RowSel{w.lig_node, nullptr, Nl}, s, nullptr, 0, true)) != TD_OK) return rc;
+        if ((rc = td_launch_edge_key16(L.xk, L, xc, gt, P, q, lig, TdRows{}, true, s)) != TD_OK) return rc;
     }
     ProfScope ps(PC_H2X_V, s);
-    return td_launch_edge_xv16(L.xv, L, xc, xn, gt.nbr, P, w.lig_node, Nl, gt.alpha, s, gt.cptr);
+    return td_launch_edge_xv16(L.xv, L, xc, xn, gt, P, lig, s);
 }
 
 // A layer is NX x2h stages, one after the other on the layer's start coordinates, then NH h2x stages, each on the coordinates the previous one
@@ -106,15 +96,15 @@ int h2x_attend(const td_model *m, const TdLayer &L, Workspace &w, const GraphTab
 // stage of each kind (M == 1, the live architecture) projections are fused across stages -- the h2x stage of a layer and the x2h stage of
 // the next project the same h: one pair launch; sync_twoup: both stages of a layer project its input features -- and a caching session's
 // row lists prune the layers from the end.  Several stages per layer: every stage takes its own projections, every row.
-int run_backbone(const td_model *m, Workspace &w, const GraphTab &gt, float *h, int64_t N, int64_t Nl, int fix_x, float4 **x_final,
+int run_backbone(const td_model *m, Workspace &w, const TdGraphTab &gt, float *h, int64_t N, int64_t Nl, int fix_x, float4 **x_final,
                  hipStream_t s, const CachedStep &cs) {
     int rc;
     const int Lc = m->cfg.num_layers, NX = num_x2h(m->cfg), NH = num_h2x(m->cfg), M = stage_rows(m->cfg);
     const bool one = M == 1, sync = one && m->cfg.sync_twoup != 0;
     const int32_t *hop_rows = one ? cs.hop_rows : nullptr;
     // row list of receptive-field level k (1-based); every row without one
-    const RowSel every{nullptr, nullptr, N};
-    auto level = [&](int k) { return (hop_rows && k <= cs.hop_levels) ? RowSel{hop_rows + (size_t)(k - 1) * N, cs.hop_count + (k - 1), N} : every; };
+    const TdRows every{nullptr, nullptr, N}, lig{w.lig_node, nullptr, Nl};
+    auto level = [&](int k) { return (hop_rows && k <= cs.hop_levels) ? TdRows{hop_rows + (size_t)(k - 1) * N, cs.hop_count + (k - 1), N} : every; };
     // Sampling session: only ligand outputs are consumed, so the layer e from the end updates receptive-field level e + 1
     // only, and its projections are needed on level e + 2 (those rows and their neighbours).
     auto att_rows = [&](int l) { return l > 0 ? level(Lc - 1 - l + 1) : every; };
@@ -122,12 +112,11 @@ int run_backbone(const td_model *m, Workspace &w, const GraphTab &gt, float *h, 
     float4 *xc = w.x4a, *xn = w.x4b;
     const bool do_h2x = !fix_x && Nl > 0;
     if (do_h2x && cs.init_xn) TD_CHECK_HIP(hipMemcpyAsync(xn, xc, (size_t)N * sizeof(float4), hipMemcpyDeviceToDevice, s));
-    const RowSel hop1 = level(1);
+    const TdRows hop1 = level(1);
     // the projections of an h2x stage (hx) and of an x2h stage (nx, on the rows pr) from the same h: one launch
-    auto project_pair = [&](const TdLayer &hx, const TdLayer &nx, const RowSel &pr) {
+    auto project_pair = [&](const TdLayer &hx, const TdLayer &nx, const TdRows &pr) {
         ProfScope ps(PC_NODE, s);
-        return td_launch_node_proj_pair(hx.nodeH2x, hop1.rows, hop1.count_ptr, w.lig_node, Nl, w.Px, w.qx, nx.nodeX2h, pr.rows, pr.count_ptr,
-                                        w.P, w.q, h, N, s);
+        return td_launch_node_proj_pair(hx.nodeH2x, hop1, lig, w.Px, w.qx, nx.nodeX2h, pr, w.P, w.q, h, s);
     };
     bool proj_done = false;        // this layer's x2h-stage projections rode in the previous layer's paired launch
     for (int l = 0; l < Lc; ++l) {
@@ -135,18 +124,18 @@ int run_backbone(const td_model *m, Workspace &w, const GraphTab &gt, float *h, 
             if (l == 0 && one && cs.layer0_x2h_done) continue;
             const TdLayer &L = m->layers[(size_t)l * M + i];
             X2hStage a;
-            a.P = w.P; a.q = w.q; a.lig = w.lig_node; a.Nl = Nl;
+            a.P = w.P; a.q = w.q; a.lig = lig;
             a.rows = att_rows(l);
             a.proj = proj_rows(l);
             const bool use_fwd = one && cs.fwd && l == 1 && !a.rows.rows;
-            if (use_fwd) a.rows = RowSel{cs.fwd->rows, cs.fwd->counts, N};
+            if (use_fwd) a.rows = cs.fwd->rows;
             // sync_twoup: the h2x stage reads the layer's input features, i.e. the h this stage's projections are taken from: both
             // stages' projections in one launch, before the value pass overwrites h
             if (sync && do_h2x && (rc = project_pair(L, L, a.proj)) != TD_OK) return rc;
             a.project = !proj_done && !(sync && do_h2x);
             proj_done = false;
             if ((rc = x2h_stage(L, gt, xc, h, N, a, s)) != TD_OK) return rc;
-            if (use_fwd && (rc = td_launch_restore_rows(cs.fwd->rest, cs.fwd->counts + 1, N, cs.fwd->hs, h, s, w.gid, w.node_ptr, cs.fwd->cbase)) != TD_OK) return rc;
+            if (use_fwd && (rc = td_launch_restore_rows(cs.fwd->rest, cs.fwd->hs, h, cs.fwd->nodes, cs.fwd->tabs, s)) != TD_OK) return rc;
         }
         if (!do_h2x) continue;
         for (int j = 0; j < NH; ++j) {
@@ -162,7 +151,7 @@ int run_backbone(const td_model *m, Workspace &w, const GraphTab &gt, float *h, 
             }
             if (L.ew_h2x) {              // the h2x stage's own gate, from the same (not yet updated) coordinates
                 ProfScope ps(PC_GATE, s);
-                if ((rc = td_launch_layer_gate(L.ew_h2x, L.offsets, L.coeff, xc, gt.nbr, N, gt.ew, s)) != TD_OK) return rc;
+                if ((rc = td_launch_layer_gate(L.ew_h2x, L.offsets, L.coeff, xc, gt, every, s)) != TD_OK) return rc;
             }
             if ((rc = h2x_attend(m, L, w, gt, Nl, xc, xn, w.Px, w.qx, s)) != TD_OK) return rc;
             std::swap(xc, xn);
@@ -173,19 +162,19 @@ int run_backbone(const td_model *m, Workspace &w, const GraphTab &gt, float *h, 
 }
 
 // graph + edge gate of a composed batch on the default graph (32-slot rows: k-NN with k <= 32, radius with cap <= 32)
-int build_default_graph(const td_model *m, Workspace &w, int64_t N, int max_graph_nodes, hipStream_t s) {
+int build_default_graph(const td_model *m, const TdGraphTab &gt, const TdNodes &nodes, hipStream_t s) {
     int rc;
     {
         ProfScope ps(PC_KNN, s);
         if (m->cfg.cutoff_mode == TD_CUTOFF_RADIUS)
-            rc = td_launch_radius32(w.x4a, w.node_ptr, w.gid, N, m->cfg.radius, m->cfg.max_num_neighbors, w.nbr, s);
+            rc = td_launch_radius32(nodes, m->cfg.radius, m->cfg.max_num_neighbors, gt.nbr, s);
         else
-            rc = td_launch_knn(w.x4a, w.node_ptr, w.gid, N, max_graph_nodes, w.nbr, s, m->cfg.knn);
+            rc = td_launch_knn(nodes, gt.nbr, m->cfg.knn, s);
         if (rc != TD_OK) return rc;
     }
     if (m->cfg.ew_net_type != 0) return TD_OK;          // 'r' / none: every stage computes its own gate (run_backbone)
     ProfScope ps(PC_GATE, s);
-    return td_launch_gate(m->gate, w.x4a, w.nbr, N, nullptr, nullptr, w.ew, s);
+    return td_launch_gate(m->gate, nodes.x4, gt, table_rows(gt, nodes.N), s);
 }
 
 // td_debug_fail_alloc: the n-th stream-ordered allocation from now fails (fault injection for the error paths)
@@ -260,15 +249,15 @@ int plan_layout(GraphPlan &p, const int32_t *node_ptr, const int32_t *gid, hipSt
 }
 
 // graph + edge gate of a composed batch on a general graph (chunked table of the plan)
-int build_general_graph(const td_model *m, GraphPlan &p, Workspace &w, int64_t N, int64_t Nl, int max_graph_nodes, hipStream_t s) {
+int build_general_graph(const td_model *m, GraphPlan &p, Workspace &w, const TdGraphTab &gt, const TdNodes &nodes, int64_t Nl, hipStream_t s) {
     int rc;
     {
         ProfScope ps(PC_KNN, s);
-        if ((rc = td_launch_graph_general(p.mode, w.x4a, w.node_ptr, p.pptr, w.gid, p.prot_node, p.Np, w.lig_node, Nl, N, p.k,
-                                          p.radius, max_graph_nodes, p.cptr, p.cnbr, p.NC, s)) != TD_OK) return rc;
+        if ((rc = td_launch_graph_general(p.mode, nodes, TdRows{p.prot_node, nullptr, p.Np}, TdRows{w.lig_node, nullptr, Nl}, p.k, p.radius, gt,
+                                          s)) != TD_OK) return rc;
     }
     ProfScope ps(PC_GATE, s);
-    return td_launch_gate(m->gate, w.x4a, p.cnbr, p.NC, nullptr, nullptr, p.ew, s, p.chunk_node);
+    return td_launch_gate(m->gate, nodes.x4, gt, table_rows(gt, nodes.N), s);
 }
 
 // Every block of one denoiser evaluation (models/uni_transformer.py:306-323): graph + gate from the current coordinates (in w.x4a), then
@@ -277,9 +266,10 @@ int build_general_graph(const td_model *m, GraphPlan &p, Workspace &w, int64_t N
 int run_blocks(const td_model *m, Workspace &w, GraphPlan *plan, float *h, int64_t N, int64_t Nl, int fix_x, int max_graph_nodes,
                float4 **x_final, hipStream_t s) {
     int rc;
-    const GraphTab gt = plan ? plan_tab(*plan) : default_tab(w);
+    const TdGraphTab gt = plan ? plan_tab(*plan) : default_tab(w);
     for (int blk = 0; blk < num_blocks(m->cfg); ++blk) {
-        rc = plan ? build_general_graph(m, *plan, w, N, Nl, max_graph_nodes, s) : build_default_graph(m, w, N, max_graph_nodes, s);
+        const TdNodes nodes{w.x4a, w.node_ptr, plan ? plan->pptr : nullptr, w.gid, N, plan ? plan->B : 0, max_graph_nodes};          // (x4a changes hands between blocks)
+        rc = plan ? build_general_graph(m, *plan, w, gt, nodes, Nl, s) : build_default_graph(m, gt, nodes, s);
         if (rc != TD_OK) return rc;
         if ((rc = run_backbone(m, w, gt, h, N, Nl, fix_x, x_final, s)) != TD_OK) return rc;
         if (*x_final == w.x4b) std::swap(w.x4a, w.x4b);

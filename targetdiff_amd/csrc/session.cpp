@@ -37,10 +37,10 @@ struct td_session {
     char *block;
     hipStream_t last_stream;     // stream of the latest call: the block is freed in its order
     Workspace w;                 // per-step buffers (x4a/x4b, gid, nbr, lig_node, node_ptr, ew, P, q, h, alpha)
-    int32_t *prot_node, *pptr, *lptr, *snbr, *dirty_rows, *dirty_count, *hop_rows, *hop_count, *dirty_chunks;
+    int32_t *prot_node, *pptr, *lptr, *dirty_rows, *dirty_count, *hop_rows, *hop_count, *dirty_chunks;
     int hop_levels;
-    unsigned long long *skeys;
-    float *ews, *h0, *h1s, *h2s, *P0, *q0;
+    TdStaticTabs tabs;           // static protein tables (skeys, snbr, h0, h1s, ews; cgraph / cbase when they are shared per pocket)
+    float *h2s, *P0, *q0;
     uint8_t *flags2;
     int32_t *fwd_rows, *fwd_rest, *fwd_counts;
     bool use_fwd;
@@ -48,11 +48,9 @@ struct td_session {
     float *setup_lpos; int64_t *setup_lv; int32_t *canon_rows;          // set-up only: zero ligand atoms for the first compose, the canonical graphs' protein rows
     int graph_nodes_max;         // exact size of the largest graph -- sizes the LDS flags of td_launch_step_lists
     // Per-pocket sharing of the static tables (CACHING, default graph; model option session_share_pockets): all samples of a pocket carry the
-    // same protein block (scripts/sample_diffusion.py:42 replicates one pocket n_data times), so skeys / snbr / ews / h0 / h1s / h2s are kept
-    // ONCE per distinct block -- `static_rows` compact rows, the canonical graphs' protein atoms back to back -- and graph g reads the rows of
-    // cgraph[g], the first graph of the batch with the same block, from cbase[g] on.  P0 / q0 (the layer-0 projections the attention passes
-    // gather through the neighbour index) stay per node.  nullptr: tables indexed by node.
-    int32_t *cgraph = nullptr, *cbase = nullptr;
+    // same protein block (scripts/sample_diffusion.py:42 replicates one pocket n_data times), so `tabs` and h2s are kept ONCE per distinct
+    // block -- `static_rows` compact rows, the canonical graphs' protein atoms back to back (TdStaticTabs::cgraph / cbase).  P0 / q0 (the
+    // layer-0 projections the attention passes gather through the neighbour index) stay per node.
     int64_t static_rows = 0;
     int pocket_groups = 0;
     bool caching;                // static-protein caching + receptive-field pruning (false: PLAIN)
@@ -82,10 +80,14 @@ struct td_session {
 namespace tdapi {
 constexpr int TD_STEP_LISTS_MAX_NODES = 12288;       // LDS flags of step_lists_kernel: 4 bytes per node of a graph, 48 KiB
 
-GraphTab session_tab(td_session *S) {
-    GraphTab gt = S->chunked ? plan_tab(S->plan) : default_tab(S->w);
+TdGraphTab session_tab(td_session *S) {
+    TdGraphTab gt = S->chunked ? plan_tab(S->plan) : default_tab(S->w);
     if (S->caching) gt.mixed = S->dirty_count;
     return gt;
+}
+// the session's batch as the graph launchers of a CACHING session read it (a general graph knows its largest graph exactly)
+TdNodes session_nodes(const td_session *S) {
+    return TdNodes{S->w.x4a, S->w.node_ptr, S->pptr, S->w.gid, S->N, S->B, S->chunked ? S->graph_nodes_max : S->max_graph_nodes};
 }
 
 // stream-ordered free with a fallback: the stream may have been destroyed by the caller in the meantime (a C-ABI user with its own
@@ -189,12 +191,12 @@ size_t session_layout(td_session *S, char *base, bool share) {
     const size_t C = S->caching ? 1 : 0;                            // (a PLAIN session keeps none of the caching tables)
     S->prot_node = c.take<int32_t>(np);
     S->pptr = c.take<int32_t>(nb + 1); S->lptr = c.take<int32_t>(nb + 1);
-    S->h0 = c.take<float>(ns * TD_H);
+    S->tabs.h0 = c.take<float>(ns * TD_H);
     S->setup_lpos = c.take<float>(nl * 3); S->setup_lv = c.take<int64_t>(nl);
-    S->snbr = c.take<int32_t>(C * ncs * TD_K);
-    S->skeys = c.take<unsigned long long>(C * ns * ks);
-    S->ews = c.take<float>(C * ncs * TD_K);
-    S->h1s = c.take<float>(C * ns * TD_H); S->h2s = c.take<float>(C * ns * TD_H);
+    S->tabs.snbr = c.take<int32_t>(C * ncs * TD_K);
+    S->tabs.skeys = c.take<unsigned long long>(C * ns * ks);
+    S->tabs.ews = c.take<float>(C * ncs * TD_K);
+    S->tabs.h1s = c.take<float>(C * ns * TD_H); S->h2s = c.take<float>(C * ns * TD_H);
     S->flags2 = c.take<uint8_t>(C * n);
     S->fwd_rows = c.take<int32_t>(C * n); S->fwd_rest = c.take<int32_t>(C * n); S->fwd_counts = c.take<int32_t>(64);
     S->P0 = c.take<float>(C * n * 4 * TD_H); S->q0 = c.take<float>(C * n * TD_H);
@@ -203,9 +205,9 @@ size_t session_layout(td_session *S, char *base, bool share) {
     S->hop_rows = c.take<int32_t>(C * n * TD_HOP_LEVELS); S->hop_count = c.take<int32_t>(64);
     S->dirty_chunks = c.take<int32_t>(S->chunked ? C * nc : 0);
     S->pred_pos = c.take<float>(nl * 3); S->pred_v = c.take<float>(nl * TD_MAXC);
-    S->cgraph = c.take<int32_t>(share ? nb : 0); S->cbase = c.take<int32_t>(share ? nb : 0);
+    S->tabs.cgraph = c.take<int32_t>(share ? nb : 0); S->tabs.cbase = c.take<int32_t>(share ? nb : 0);
     S->canon_rows = c.take<int32_t>(share ? ns : 0);
-    if (!share) S->cgraph = S->cbase = S->canon_rows = nullptr;          // (nullptr: tables indexed by node)
+    if (!share) S->tabs.cgraph = S->tabs.cbase = S->canon_rows = nullptr;          // (nullptr: tables indexed by node)
     return S->w.bytes + c.off;
 }
 
@@ -218,7 +220,8 @@ int session_build_static(td_session *S, const float *d_protein_pos, const float 
     const td_model *m = S->m;
     const int64_t N = S->N, N_p = S->Np, N_l = S->Nl, B = S->B;
     const size_t n = (size_t)N, nb = (size_t)B;
-    const bool share = S->cgraph != nullptr;
+    const bool share = S->tabs.cgraph != nullptr;
+    const TdStaticTabs &T = S->tabs;
     Workspace &w = S->w;
     int rc;
     TD_CHECK_HIP(hipMemcpyAsync(S->pptr, d_protein_ptr, (nb + 1) * 4, hipMemcpyDeviceToDevice, s));
@@ -226,9 +229,9 @@ int session_build_static(td_session *S, const float *d_protein_pos, const float 
     TD_CHECK_HIP(hipMemsetAsync(S->setup_lpos, 0, (size_t)N_l * 12, s));
     TD_CHECK_HIP(hipMemsetAsync(S->setup_lv, 0, (size_t)N_l * 8, s));
     AsyncScratch scratch(s);          // (goes back in stream order when this function returns: after the compaction, or on an error)
-    unsigned long long *skeys_f = S->skeys;
-    int32_t *snbr_f = S->snbr;
-    float *ews_f = S->ews, *h0_f = S->h0, *h1_f = S->h1s, *h2_f = S->h2s;
+    unsigned long long *skeys_f = T.skeys;
+    int32_t *snbr_f = T.snbr;
+    float *ews_f = T.ews, *h0_f = T.h0, *h1_f = T.h1s, *h2_f = S->h2s;
     if (share) {
         auto layout = [&](char *base) {
             Carver c{base};
@@ -240,15 +243,15 @@ int session_build_static(td_session *S, const float *d_protein_pos, const float 
         char *block = nullptr;
         if ((rc = scratch.take(&block, layout(nullptr), "td_session_create")) != TD_OK) return rc;
         layout(block);
-        TD_CHECK_HIP(hipMemcpyAsync(S->cgraph, pg.cgraph.data(), nb * 4, hipMemcpyHostToDevice, s));
-        TD_CHECK_HIP(hipMemcpyAsync(S->cbase, pg.cbase.data(), nb * 4, hipMemcpyHostToDevice, s));
+        TD_CHECK_HIP(hipMemcpyAsync(T.cgraph, pg.cgraph.data(), nb * 4, hipMemcpyHostToDevice, s));
+        TD_CHECK_HIP(hipMemcpyAsync(T.cbase, pg.cbase.data(), nb * 4, hipMemcpyHostToDevice, s));
         TD_CHECK_HIP(hipMemcpyAsync(S->canon_rows, pg.canon_rows.data(), pg.canon_rows.size() * 4, hipMemcpyHostToDevice, s));
         TD_CHECK_HIP(hipStreamSynchronize(s));          // (the host vectors go out of scope with td_session_create)
     }
     // embeddings + packed order, protein row list
     int32_t *prot_out = S->chunked ? S->plan.prot_node : S->prot_node;
     if ((rc = td_launch_compose(m, d_protein_pos, d_protein_v, S->pptr, N_p, S->setup_lpos, S->setup_lv, S->lptr, N_l, B, h0_f, w.x4a,
-                                w.node_ptr, w.gid, w.lig_node, prot_out, s)) != TD_OK) return rc;
+                                w.node_ptr, w.gid, w.lig_node, prot_out, nullptr, s)) != TD_OK) return rc;
     if (S->chunked) {
         S->prot_node = S->plan.prot_node;
         if ((rc = plan_layout(S->plan, w.node_ptr, w.gid, s)) != TD_OK) return rc;
@@ -256,30 +259,32 @@ int session_build_static(td_session *S, const float *d_protein_pos, const float 
     TD_CHECK_HIP(hipMemcpyAsync(w.x4b, w.x4a, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
     if (!S->caching) return TD_OK;
     // ---- protein-only graph, its gate rows, layer-0 projections / queries, layer-0 x2h output
-    const int32_t *set_rows = share ? S->canon_rows : S->prot_node;
-    const int64_t set_count = share ? S->static_rows : N_p;
+    const TdRows set{share ? S->canon_rows : S->prot_node, nullptr, share ? S->static_rows : N_p};          // the rows of the static tables
+    const int32_t *set_rows = set.rows;
+    const int64_t set_count = set.count;
     const size_t nc = S->chunked ? (size_t)S->plan.NC : n;
-    GraphTab st = session_tab(S);                  // the static table: its own nbr / ew, the step's alpha as scratch
+    const TdNodes nodes = session_nodes(S);
+    const TdGraphTab gt = session_tab(S);
+    TdGraphTab st = gt;                            // the static table: its own nbr / ew, the step's alpha as scratch
     st.nbr = snbr_f; st.ew = ews_f;
     TD_CHECK_HIP(hipMemsetAsync(snbr_f, 0xff, nc * TD_K * 4, s));
     if (S->chunked) {
-        if ((rc = td_launch_knn_general_static(w.x4a, w.node_ptr, S->pptr, w.gid, S->prot_node, N_p, m->cfg.knn, S->graph_nodes_max,
-                                               S->plan.cptr, S->snbr, S->skeys, s)) != TD_OK) return rc;
-        if ((rc = td_launch_gate(m->gate, w.x4a, S->snbr, S->plan.NC, nullptr, nullptr, S->ews, s, S->plan.chunk_node)) != TD_OK) return rc;
+        if ((rc = td_launch_knn_general_static(nodes, set, m->cfg.knn, st, skeys_f, s)) != TD_OK) return rc;
+        if ((rc = td_launch_gate(m->gate, w.x4a, st, table_rows(st, N), s)) != TD_OK) return rc;
         // the step's table: ligand rows start as all pads; hybrid: their ligand half never changes
-        TD_CHECK_HIP(hipMemsetAsync(S->plan.cnbr, 0xff, nc * TD_K * 4, s));
-        TD_CHECK_HIP(hipMemsetAsync(S->plan.ew, 0, nc * TD_K * 4, s));
+        TD_CHECK_HIP(hipMemsetAsync(gt.nbr, 0xff, nc * TD_K * 4, s));
+        TD_CHECK_HIP(hipMemsetAsync(gt.ew, 0, nc * TD_K * 4, s));
         if (m->cfg.cutoff_mode == TD_CUTOFF_HYBRID &&
-            (rc = td_launch_hybrid_ligand_half(w.node_ptr, S->pptr, w.gid, w.lig_node, N_l, S->plan.cptr, S->plan.cnbr, s)) != TD_OK) return rc;
+            (rc = td_launch_hybrid_ligand_half(nodes, TdRows{w.lig_node, nullptr, N_l}, gt, s)) != TD_OK) return rc;
     } else {
-        if ((rc = td_launch_knn_static(w.x4a, w.node_ptr, w.gid, set_rows, set_count, S->max_graph_nodes, snbr_f, skeys_f, s, m->cfg.knn)) != TD_OK) return rc;
-        if ((rc = td_launch_gate(m->gate, w.x4a, snbr_f, set_count, set_rows, nullptr, ews_f, s)) != TD_OK) return rc;
+        if ((rc = td_launch_knn_static(nodes, set, st.nbr, skeys_f, m->cfg.knn, s)) != TD_OK) return rc;
+        if ((rc = td_launch_gate(m->gate, w.x4a, st, set, s)) != TD_OK) return rc;
     }
     // (no profile scopes: set-up; the rows' input features stay -- h0 / h1s are tables of their own)
     X2hStage a;
     a.P = S->P0; a.q = S->q0; a.scoped = false;
-    a.proj = RowSel{nullptr, nullptr, N};
-    a.rows = RowSel{set_rows, nullptr, set_count};
+    a.proj = TdRows{nullptr, nullptr, N};
+    a.rows = set;
     a.h_in = h0_f;
     if ((rc = x2h_stage(m->layers[0], st, w.x4a, h1_f, N, a, s)) != TD_OK) return rc;
     if (S->use_fwd) {      // layer-1 x2h output of the protein-only graph (valid wherever the ligand is two hops away)
@@ -287,11 +292,11 @@ int session_build_static(td_session *S, const float *d_protein_pos, const float 
         if ((rc = x2h_stage(m->layers[1], st, w.x4a, h2_f, N, a, s)) != TD_OK) return rc;
     }
     if (share) {           // the canonical rows of the scratch tables -> the compact shared tables
-        if ((rc = td_launch_compact_rows(skeys_f, set_rows, set_count, TD_K * 8, S->skeys, s)) != TD_OK) return rc;
-        if ((rc = td_launch_compact_rows(snbr_f, set_rows, set_count, TD_K * 4, S->snbr, s)) != TD_OK) return rc;
-        if ((rc = td_launch_compact_rows(ews_f, set_rows, set_count, TD_K * 4, S->ews, s)) != TD_OK) return rc;
-        if ((rc = td_launch_compact_rows(h0_f, set_rows, set_count, TD_H * 4, S->h0, s)) != TD_OK) return rc;
-        if ((rc = td_launch_compact_rows(h1_f, set_rows, set_count, TD_H * 4, S->h1s, s)) != TD_OK) return rc;
+        if ((rc = td_launch_compact_rows(skeys_f, set_rows, set_count, TD_K * 8, T.skeys, s)) != TD_OK) return rc;
+        if ((rc = td_launch_compact_rows(snbr_f, set_rows, set_count, TD_K * 4, T.snbr, s)) != TD_OK) return rc;
+        if ((rc = td_launch_compact_rows(ews_f, set_rows, set_count, TD_K * 4, T.ews, s)) != TD_OK) return rc;
+        if ((rc = td_launch_compact_rows(h0_f, set_rows, set_count, TD_H * 4, T.h0, s)) != TD_OK) return rc;
+        if ((rc = td_launch_compact_rows(h1_f, set_rows, set_count, TD_H * 4, T.h1s, s)) != TD_OK) return rc;
         if (S->use_fwd && (rc = td_launch_compact_rows(h2_f, set_rows, set_count, TD_H * 4, S->h2s, s)) != TD_OK) return rc;
     }
     return TD_OK;
@@ -360,14 +365,18 @@ extern "C" int td_session_forward(td_session *S, const float *d_ligand_pos, cons
     S->last_stream = s;
     const td_model *m = S->m;
     Workspace &w = S->w;
-    const int64_t N = S->N, Nl = S->Nl, Np = S->Np;
-    const GraphTab gt = session_tab(S);
+    const int64_t N = S->N, Nl = S->Nl;
+    const TdGraphTab gt = session_tab(S);
+    const TdNodes nodes = session_nodes(S);
+    const TdRows prot{S->prot_node, nullptr, S->Np}, lig{w.lig_node, nullptr, Nl};
+    const TdRows dirty{S->dirty_rows, S->dirty_count, N};
+    uint8_t *const flags2 = S->use_fwd ? S->flags2 : nullptr;          // forward-reach flags, cleared by the step's first launches
     int rc;
     if (!S->caching) {
         {
             ProfScope ps(PC_COMPOSE, s);
-            TD_CHECK_HIP(hipMemcpyAsync(w.h, S->h0, (size_t)N * TD_H * sizeof(float), hipMemcpyDeviceToDevice, s));
-            if ((rc = td_launch_ligand_update(m, d_ligand_pos, d_ligand_v, w.lig_node, Nl, w.h, w.x4a, s, nullptr, d_ligand_graph_bias, w.gid)) != TD_OK) return rc;
+            TD_CHECK_HIP(hipMemcpyAsync(w.h, S->tabs.h0, (size_t)N * TD_H * sizeof(float), hipMemcpyDeviceToDevice, s));
+            if ((rc = td_launch_ligand_update(m, d_ligand_pos, d_ligand_v, lig, w.h, w.x4a, nullptr, d_ligand_graph_bias, w.gid, s)) != TD_OK) return rc;
         }
         float4 *xg = nullptr;
         Workspace wb = w;             // (the block loop swaps x4a / x4b of its workspace: the session's own stays as it is)
@@ -383,8 +392,8 @@ extern "C" int td_session_forward(td_session *S, const float *d_ligand_pos, cons
         rs.c0 = S->dirty_count; rs.n0 = 2;
         rs.c1 = S->fwd_counts; rs.n1 = 2;
         rs.c2 = S->hop_count; rs.n2 = TD_HOP_LEVELS;
-        rs.flags2 = S->use_fwd ? S->flags2 : nullptr;
-        if ((rc = td_launch_ligand_update(m, d_ligand_pos, d_ligand_v, w.lig_node, Nl, w.h, w.x4a, s, &rs, d_ligand_graph_bias, w.gid)) != TD_OK) return rc;
+        rs.flags2 = flags2;
+        if ((rc = td_launch_ligand_update(m, d_ligand_pos, d_ligand_v, lig, w.h, w.x4a, &rs, d_ligand_graph_bias, w.gid, s)) != TD_OK) return rc;
     }
     bool lists_done = false;
     {
@@ -393,28 +402,20 @@ extern "C" int td_session_forward(td_session *S, const float *d_ligand_pos, cons
                                 S->hop_rows, S->hop_count, S->hop_levels, S->chunked ? S->dirty_chunks : nullptr,
                                 S->chunked ? S->dirty_count + 1 : nullptr};
         if (S->chunked) {
-            const GraphPlan &p = S->plan;
-            if ((rc = td_launch_knn_merge_general(w.x4a, w.node_ptr, S->pptr, w.gid, S->prot_node, Np, S->skeys, S->snbr, S->h0,
-                                                  S->h1s, S->ews, p.cptr, p.cpn_p, p.cnbr, w.h, p.ew, S->clean,
-                                                  S->use_fwd ? S->flags2 : nullptr, s, m->cfg.knn)) != TD_OK) return rc;
-            if ((rc = td_launch_ligand_rows_general(p.mode, w.x4a, w.node_ptr, S->pptr, w.gid, w.lig_node, Nl, p.k, S->graph_nodes_max,
-                                                    p.cptr, p.cnbr, s)) != TD_OK) return rc;
+            if ((rc = td_launch_knn_merge_general(nodes, prot, S->tabs, gt, w.h, S->clean, flags2, m->cfg.knn, s)) != TD_OK) return rc;
+            if ((rc = td_launch_ligand_rows_general(S->plan.mode, nodes, lig, S->plan.k, gt, s)) != TD_OK) return rc;
             // every row list of the step in one launch (the session is CACHING only when every graph fits its LDS flags)
-            if ((rc = td_launch_step_lists(S->clean, w.x4a, p.cnbr, w.node_ptr, N, S->B, S->graph_nodes_max, lists, s, p.cptr,
-                                           p.chunk_node)) != TD_OK) {
+            if ((rc = td_launch_step_lists(S->clean, nodes, gt, S->graph_nodes_max, lists, s)) != TD_OK) {
                 if (rc == TD_EINVAL) td_set_error("td_session_forward: a graph of %d nodes does not fit the row-list kernel", S->graph_nodes_max);
                 return rc;
             }
             lists_done = true;
         } else {
             // the protein rows' merge and the ligand rows' full search: independent, one launch
-            if ((rc = td_launch_knn_merge(w.x4a, w.node_ptr, S->pptr, w.gid, S->prot_node, Np, S->skeys, S->snbr, S->h0,
-                                          S->h1s, S->ews, w.nbr, w.h, w.ew, S->clean, S->use_fwd ? S->flags2 : nullptr, s, m->cfg.knn,
-                                          w.lig_node, Nl, S->max_graph_nodes, S->cgraph, S->cbase)) != TD_OK) return rc;
+            if ((rc = td_launch_knn_merge(nodes, prot, lig, S->tabs, gt, w.h, S->clean, flags2, m->cfg.knn, s)) != TD_OK) return rc;
             // every row list of the step (dirty rows, forward reach, receptive-field levels) in one launch, one workgroup per graph;
             // graphs too large for its LDS flags take the separate kernels
-            rc = (m->opt.session_step_lists && S->graph_nodes_max > 0) ? td_launch_step_lists(S->clean, w.x4a, w.nbr, w.node_ptr, N, S->B, S->graph_nodes_max, lists, s)
-                                        : TD_EINVAL;
+            rc = (m->opt.session_step_lists && S->graph_nodes_max > 0) ? td_launch_step_lists(S->clean, nodes, gt, S->graph_nodes_max, lists, s) : TD_EINVAL;
             lists_done = rc == TD_OK;
             if (rc != TD_OK && rc != TD_EINVAL) return rc;
             if (!lists_done) {
@@ -432,23 +433,21 @@ extern "C" int td_session_forward(td_session *S, const float *d_ligand_pos, cons
     }
     {
         ProfScope ps(PC_GATE, s);
-        if (S->chunked)
-            rc = td_launch_gate(m->gate, w.x4a, gt.nbr, S->plan.NC, S->dirty_chunks, S->dirty_count + 1, gt.ew, s, S->plan.chunk_node);
-        else
-            rc = td_launch_gate(m->gate, w.x4a, gt.nbr, N, S->dirty_rows, S->dirty_count, gt.ew, s);
-        if (rc != TD_OK) return rc;
+        // the gate rows of the dirty rows: their chunks on a general graph
+        const TdRows gate_rows = S->chunked ? TdRows{S->dirty_chunks, S->dirty_count + 1, gt.NC} : dirty;
+        if ((rc = td_launch_gate(m->gate, w.x4a, gt, gate_rows, s)) != TD_OK) return rc;
     }
     {   // layer 0, x2h: only ligand rows need new projections, only dirty rows need the attention passes
         X2hStage a;
-        a.P = S->P0; a.q = S->q0; a.lig = w.lig_node; a.Nl = Nl;
-        a.proj = RowSel{w.lig_node, nullptr, Nl};
-        a.rows = RowSel{S->dirty_rows, S->dirty_count, N};
+        a.P = S->P0; a.q = S->q0; a.lig = lig;
+        a.proj = lig;
+        a.rows = dirty;
         if ((rc = x2h_stage(m->layers[0], gt, w.x4a, w.h, N, a, s)) != TD_OK) return rc;
     }
     // rows the last layer still has to update (S->clean is free again after the dirty-row compaction: reuse as flags)
-    if (!lists_done && (rc = td_launch_hop_levels(w.lig_node, Nl, w.nbr, N, S->clean, S->hop_rows, S->hop_count, S->hop_levels, s, true)) != TD_OK) return rc;
+    if (!lists_done && (rc = td_launch_hop_levels(lig, gt, N, S->clean, S->hop_rows, S->hop_count, S->hop_levels, true, s)) != TD_OK) return rc;
     float4 *xf = nullptr;
-    const FwdReach fwd{S->fwd_rows, S->fwd_rest, S->fwd_counts, S->h2s, S->cbase};
+    const FwdReach fwd{TdRows{S->fwd_rows, S->fwd_counts, N}, TdRows{S->fwd_rest, S->fwd_counts + 1, N}, S->h2s, nodes, S->tabs};
     CachedStep cs;
     cs.init_xn = false; cs.layer0_x2h_done = true;
     cs.hop_rows = S->hop_rows; cs.hop_count = S->hop_count; cs.hop_levels = S->hop_levels;
@@ -630,8 +629,8 @@ extern "C" int td_session_row_counts(td_session *S, int32_t *host_counts, int32_
     if (n_counts > 2 + TD_HOP_LEVELS && S->use_fwd)
         TD_CHECK_HIP(hipMemcpyAsync(host_counts + 2 + TD_HOP_LEVELS, S->fwd_counts, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     // rows of the static tables and distinct protein blocks of the batch (per-pocket sharing; -1: tables indexed by node)
-    if (n_counts > 3 + TD_HOP_LEVELS) host_counts[3 + TD_HOP_LEVELS] = S->cgraph ? (int32_t)S->static_rows : -1;
-    if (n_counts > 4 + TD_HOP_LEVELS) host_counts[4 + TD_HOP_LEVELS] = S->cgraph ? (int32_t)S->pocket_groups : -1;
+    if (n_counts > 3 + TD_HOP_LEVELS) host_counts[3 + TD_HOP_LEVELS] = S->tabs.cgraph ? (int32_t)S->static_rows : -1;
+    if (n_counts > 4 + TD_HOP_LEVELS) host_counts[4 + TD_HOP_LEVELS] = S->tabs.cgraph ? (int32_t)S->pocket_groups : -1;
     TD_CHECK_HIP(hipStreamSynchronize(s));
     return TD_OK;
 }

@@ -137,30 +137,13 @@ struct Workspace {
     size_t bytes;
 };
 
-// Neighbour table and per-slot buffers of one batch.  Default graph: cptr == nullptr, one 32-slot row per node (the
-// workspace's nbr / ew / alpha).  General graphs: chunk-indexed buffers of a GraphPlan, cptr[i] .. cptr[i+1]-1 = chunks of node i.
-struct GraphTab {
-    const int32_t *cptr;
-    int32_t *nbr;
-    float *ew, *alpha;
-    int cpn_p;               // chunks per protein row
-    int64_t NCl;             // chunks of all ligand rows together
-    const int32_t *mixed;    // device count of the rows that see both source classes (a session's dirty rows), or nullptr
-};
-
-// The rows a launch works on: a device list with its device count (at most `count` rows), a list of `count` rows (count_ptr == nullptr),
-// or every row 0 .. count - 1 (rows == nullptr).
-struct RowSel {
-    const int32_t *rows, *count_ptr;
-    int64_t count;
-};
-
 // Sampling session, layer 1: rows outside the ligand's one-hop forward reach keep the protein-only graph's layer-1
 // output (`hs`), so the attention passes run on `rows` only and `rest` is restored from the cache afterwards.
 struct FwdReach {
-    const int32_t *rows, *rest, *counts;     // counts[0] = |rows|, counts[1] = |rest|
+    TdRows rows, rest;                       // device lists with device counts
     const float *hs;
-    const int32_t *cbase = nullptr;          // hs is a compact per-pocket table (session.cpp): row i of graph g = cbase[g] + (i - node_ptr[g])
+    TdNodes nodes;                           // the batch, and the session's static tables: hs is indexed like them (compact per pocket, or by node)
+    TdStaticTabs tabs;
 };
 
 // What only a caching session's step sets on the layer sequence; default-constructed: the stateless call.
@@ -177,13 +160,12 @@ struct CachedStep {
 // One x2h stage (x2h_stage, plan.cpp): where its projections live and which rows it works on.
 struct X2hStage {
     float *P, *q;                            // the projection buffer pair
-    RowSel rows;                             // rows of the attention passes
+    TdRows rows;                             // rows of the attention passes
     bool project = true;                     // false: the projections are in place (a pair launch took them, or the session's cache)
-    RowSel proj;                             // rows to project
+    TdRows proj;                             // rows to project
     const float *h_in = nullptr;             // features the projections are taken from when they are not h itself: h then starts as a
                                              // copy of them, made between the two passes (a session's static tables keep every layer's h)
-    const int32_t *lig = nullptr;            // the ligand rows of the batch, all of them among `rows` (nullptr: a protein-only graph)
-    int64_t Nl = 0;
+    TdRows lig;                              // the ligand rows of the batch, all of them among `rows` (empty: a protein-only graph)
     bool scoped = true;                      // take the profile scopes
 };
 
@@ -201,22 +183,18 @@ struct GraphPlan {
 };
 
 Workspace carve(char *base, int64_t N, int64_t B, int64_t Nl);
-inline GraphTab default_tab(Workspace &w) { return GraphTab{nullptr, w.nbr, w.ew, w.alpha, 1, 0, nullptr}; }
-inline GraphTab plan_tab(const GraphPlan &p) { return GraphTab{p.cptr, p.cnbr, p.ew, p.alpha, p.cpn_p, p.NCl, nullptr}; }
+inline TdGraphTab default_tab(Workspace &w) { return TdGraphTab{nullptr, w.nbr, w.ew, w.alpha, 1, 0, nullptr, nullptr, 0}; }
+inline TdGraphTab plan_tab(const GraphPlan &p) { return TdGraphTab{p.cptr, p.cnbr, p.ew, p.alpha, p.cpn_p, p.NCl, nullptr, p.chunk_node, p.NC}; }
+// every row of the table gt, for a launch over slots (the edge gates): its chunks on a general graph, the N nodes on the default graph
+inline TdRows table_rows(const TdGraphTab &gt, int64_t N) { return TdRows{nullptr, nullptr, gt.cptr ? gt.NC : N}; }
 inline int num_blocks(const td_config &c) { return c.num_blocks > 1 ? c.num_blocks : 1; }
-// the attention passes of one stage on the table gt (its nbr / ew / alpha; chunked: cptr, cpn_p, NCl); lig / Nl (x2h passes): the ligand
-// rows of the batch, all of them among the selected rows
-int key_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const float *P, const float *q, const RowSel &r,
-             hipStream_t s, const int32_t *lig = nullptr, int64_t Nl = 0, bool h2x_stage = false);
-int value_pass(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const GraphTab &gt, const float *P, const RowSel &r, float *h,
-               const int32_t *lig, int64_t Nl, hipStream_t s, float *out = nullptr);
-int x2h_stage(const TdLayer &L, const GraphTab &gt, const float4 *xc, float *h, int64_t N, const X2hStage &a, hipStream_t s);
-int h2x_project(const TdLayer &L, Workspace &w, float *h, int64_t Nl, float *P, float *q, const RowSel &hop, hipStream_t s);
-int h2x_attend(const td_model *m, const TdLayer &L, Workspace &w, const GraphTab &gt, int64_t Nl, float4 *xc, float4 *xn, float *P,
+int x2h_stage(const TdLayer &L, const TdGraphTab &gt, const float4 *xc, float *h, int64_t N, const X2hStage &a, hipStream_t s);
+int h2x_project(const TdLayer &L, Workspace &w, float *h, int64_t Nl, float *P, float *q, const TdRows &hop, hipStream_t s);
+int h2x_attend(const td_model *m, const TdLayer &L, Workspace &w, const TdGraphTab &gt, int64_t Nl, float4 *xc, float4 *xn, float *P,
                float *q, hipStream_t s);
 // num_layers x (x2h stages, h2x stages) on a composed batch whose graph (gt.nbr) and edge gate (gt.ew) are in place.  h is updated in
 // place; returns the buffer holding the final coordinates through *x_final.
-int run_backbone(const td_model *m, Workspace &w, const GraphTab &gt, float *h, int64_t N, int64_t Nl, int fix_x, float4 **x_final,
+int run_backbone(const td_model *m, Workspace &w, const TdGraphTab &gt, float *h, int64_t N, int64_t Nl, int fix_x, float4 **x_final,
                  hipStream_t s, const CachedStep &cs = CachedStep());
 // num_blocks x (graph + gate from w.x4a, run_backbone, buffer swap); plan == nullptr: the default graph
 int run_blocks(const td_model *m, Workspace &w, GraphPlan *plan, float *h, int64_t N, int64_t Nl, int fix_x, int max_graph_nodes,

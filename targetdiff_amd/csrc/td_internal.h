@@ -214,28 +214,69 @@ struct td_model {
     int fold_fp32_mlps = 0;      // attention MLPs kept off the f16 piece pairs by TdEdgeMlp::f16_safe (read-only option "fold_fp32_mlps")
 };
 
+// ---- argument blocks of the graph, gate, projection and attention launchers ---------------------------
+// Read on the host only: a launcher fills its kernel's own argument list from them.  Every member is value-initialised ({}: null, 0).
+// The rows a launch works on.
+struct TdRows {
+    const int32_t *rows{};              // row ids; null: every row 0 .. count - 1
+    const int32_t *count_ptr{};         // device-side length of `rows` (at most `count`); null: exactly `count` rows
+    int64_t count{};                    // 0: an empty selection, nothing is launched for it
+};
+// Neighbour table and per-slot buffers of one batch, 32 slots per row (-1 padded).  Default graph: one row per node.  General graphs: the
+// chunk-indexed buffers of a GraphPlan.
+struct TdGraphTab {
+    const int32_t *cptr{};              // general graphs: the in-edges of dst node i are the chunks cptr[i] .. cptr[i+1]-1 of nbr / ew / alpha;
+                                        // null: the default graph (chunk == node)
+    int32_t *nbr{};                     // [rows,32] src node of every slot
+    float *ew{}, *alpha{};              // [rows,32] edge gate, [rows,16 heads,32] attention weights
+    int cpn_p{};                        // chunks per protein row (default graph: 1).  A general graph with 1 (`hybrid`) runs the x2h passes of its
+                                        // protein rows as on the default graph and those of its ligand rows in a second, chunk-walking launch
+    int64_t NCl{};                      // chunks of all ligand rows together (default graph: 0)
+    const int32_t *mixed{};             // device count of the rows that see both source classes (a session's dirty rows); null: none known
+    const int32_t *chunk_node{};        // general graphs: dst node of every chunk; null: row == node
+    int64_t NC{};                       // general graphs: chunks of the table (default graph: 0, the table has one row per node)
+};
+// The composed batch every graph builder reads.
+struct TdNodes {
+    const float4 *x4{};                 // [N] (x, y, z, ligand flag)
+    const int32_t *node_ptr{};          // [B + 1] nodes of every graph, protein rows first
+    const int32_t *pptr{};              // [B + 1] protein atoms of every graph; null where the launch makes no protein / ligand difference
+    const int32_t *gid{};               // [N] graph of every node
+    int64_t N{};
+    int64_t B{};                        // graphs (read by the row-list launch of a session step; a stateless call on the default graph leaves 0)
+    int max_graph_nodes{};              // upper bound on the nodes of one graph (selects the candidates-per-lane kernel form); 0: unknown
+};
+// Static protein tables of a caching session (session.cpp), read by the step's merge and restore launches.
+struct TdStaticTabs {
+    unsigned long long *skeys{};        // sorted keys of the protein-only k-NN rows: [rows,32], general graphs [N,64]
+    int32_t *snbr{};                    // the protein-only neighbour rows
+    float *h0{}, *h1s{}, *ews{};        // embeddings, layer-0 x2h outputs and gate rows of the protein-only graph
+    // A session that shares its tables between the replicas of a pocket: graph g's protein block is a bitwise copy of graph cgraph[g]'s (the first
+    // such graph of the batch: cgraph[g] <= g), whose rows sit at cbase[g] .. in the COMPACT tables above; row i of graph g reads compact row
+    // cbase[g] + (i - node_ptr[g]) and shifts the node indices it finds there (they are the canonical graph's) by node_ptr[g] - node_ptr[cgraph[g]].
+    int32_t *cgraph{}, *cbase{};        // null: the tables are indexed by node
+};
+
 // ---- kernel launchers (each defined next to its kernels) --------------------------------------------
 // graph.hip
 int td_launch_graph_ptr(const int64_t *batch, int64_t N, int64_t B, int32_t *ptr, hipStream_t s);
 int td_launch_node_gid(const int32_t *node_ptr, int64_t N, int64_t B, int32_t *gid, hipStream_t s);
 int td_launch_pack_x(const float *x3, const uint8_t *mask, int64_t N, float4 *x4, hipStream_t s);
 int td_launch_unpack_x(const float4 *x4, int64_t N, float *x3, hipStream_t s);
-// k <= TD_K neighbours per 32-slot row (slots >= k are -1): every fan-in up to 32 runs on the 32-slot fast path
-int td_launch_knn(const float4 *x4, const int32_t *node_ptr, const int32_t *gid, int64_t N, int max_graph_nodes,
-                  int32_t *nbr, hipStream_t s, int k = TD_K);
+// k <= TD_K neighbours per 32-slot row (slots >= k are -1): every fan-in up to 32 runs on the 32-slot fast path.  _rows: the listed query
+// rows only; _static: protein-only lists of the listed (protein) rows and their sorted keys
+int td_launch_knn(const TdNodes &nd, int32_t *nbr, int k, hipStream_t s);
+int td_launch_knn_rows(const TdNodes &nd, const TdRows &rows, int32_t *nbr, int k, hipStream_t s);
+int td_launch_knn_static(const TdNodes &nd, const TdRows &rows, int32_t *nbr, unsigned long long *skeys, int k, hipStream_t s);
+// gbias: optional [B,128] per-graph bias of the ligand embeddings (null: none)
 int td_launch_compose(const td_model *m, const float *ppos, const float *pv, const int32_t *pptr, int64_t Np,
                       const float *lpos, const int64_t *lv, const int32_t *lptr, int64_t Nl, int64_t B,
                       float *h, float4 *x4, int32_t *node_ptr, int32_t *gid, int32_t *lig_node, int32_t *prot_node,
-                      hipStream_t s, const float *gbias = nullptr);
-int td_launch_knn_rows(const float4 *x4, const int32_t *node_ptr, const int32_t *gid, const int32_t *rows, int64_t count,
-                       int max_graph_nodes, int32_t *nbr, hipStream_t s, int k = TD_K);
-int td_launch_knn_static(const float4 *x4, const int32_t *node_ptr, const int32_t *gid, const int32_t *rows, int64_t count,
-                         int max_graph_nodes, int32_t *nbr, unsigned long long *skeys, hipStream_t s, int k = TD_K);
-int td_launch_knn_merge(const float4 *x4, const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid,
-                        const int32_t *prot_rows, int64_t Np, const unsigned long long *skeys, const int32_t *snbr,
-                        const float *h0, const float *h1s, const float *ews, int32_t *nbr, float *h, float *ew,
-                        uint8_t *clean, uint8_t *flags2, hipStream_t s, int k = TD_K, const int32_t *lig_rows = nullptr, int64_t Nl = 0,
-                        int max_graph_nodes = 0, const int32_t *cgraph = nullptr, const int32_t *cbase = nullptr);
+                      const float *gbias, hipStream_t s);
+// a session step's neighbour search: the protein rows `prot` merge the graph's ligand atoms into their static lists and take h / gt.ew from
+// the tables where the row stays clean; `lig` (default graph; empty: none) are searched in full by the same launch.  flags2 null: not cleared
+int td_launch_knn_merge(const TdNodes &nd, const TdRows &prot, const TdRows &lig, const TdStaticTabs &tabs, const TdGraphTab &gt, float *h,
+                        uint8_t *clean, uint8_t *flags2, int k, hipStream_t s);
 // per-pocket sharing of a session's static tables (graph.hip, session.cpp)
 int td_launch_pocket_hash(const float *ppos, const float *pv, const int32_t *pptr, int64_t B, int F, unsigned long long *out, hipStream_t s);
 int td_launch_pocket_verify(const float *ppos, const float *pv, const int32_t *pptr, int64_t B, int F, const int32_t *cand, int32_t *flags,
@@ -245,14 +286,14 @@ int td_launch_compact_dirty(const uint8_t *clean, const float4 *x4, int64_t N, i
                             hipStream_t s);
 int td_launch_forward_reach(const uint8_t *clean, const float4 *x4, const int32_t *nbr, int64_t N, uint8_t *flags2,
                             int32_t *rows_on, int32_t *rows_off, int32_t *counts2, uint8_t *clean_to_zero, hipStream_t s);
-int td_launch_restore_rows(const int32_t *rows, const int32_t *count_ptr, int64_t max_rows, const float *hs, float *h,
-                           hipStream_t s, const int32_t *gid = nullptr, const int32_t *node_ptr = nullptr, const int32_t *cbase = nullptr);
+// h[i] = hs[i] for the listed rows (a device-side count), hs indexed like the tables of `tabs`
+int td_launch_restore_rows(const TdRows &rows, const float *hs, float *h, const TdNodes &nd, const TdStaticTabs &tabs, hipStream_t s);
 constexpr int TD_HOP_LEVELS = 4;
-int td_launch_hop_levels(const int32_t *lig_node, int64_t Nl, const int32_t *nbr, int64_t N, uint8_t *flags,
-                         int32_t *rows, int32_t *counts, int levels, hipStream_t s, bool zeroed = false);
+// rows: [levels][N] row lists, counts: [levels] device-side lengths; zeroed: flags and counts were cleared earlier in the step
+int td_launch_hop_levels(const TdRows &lig, const TdGraphTab &gt, int64_t N, uint8_t *flags, int32_t *rows, int32_t *counts, int levels,
+                         bool zeroed, hipStream_t s);
 // edge gate on 16 x 16 tiles with the bf16 first layer (edge16.hip); td_launch_gate (gate.hip) dispatches to it
-int td_launch_gate16(const TdGate &g, const float4 *x4, const int32_t *nbr, int64_t N, const int32_t *rows,
-                     const int32_t *count_ptr, float *ew, hipStream_t s, const int32_t *chunk_node);
+int td_launch_gate16(const TdGate &g, const float4 *x4, const TdGraphTab &gt, const TdRows &rows, hipStream_t s);
 // all row lists of a sampling step in one launch (graph.hip); TD_EINVAL when a graph does not fit the LDS flag arrays
 struct TdStepLists {
     int32_t *dirty_rows, *dirty_count;
@@ -261,74 +302,57 @@ struct TdStepLists {
     int levels;
     int32_t *dirty_chunks = nullptr, *dirty_chunk_count = nullptr;     // general graphs: the chunks of the dirty rows
 };
-// cptr / chunk_node (general graphs): chunk-indexed neighbour table
-int td_launch_step_lists(const uint8_t *clean, const float4 *x4, const int32_t *nbr, const int32_t *node_ptr, int64_t N,
-                         int64_t B, int max_nodes, const TdStepLists &out, hipStream_t s, const int32_t *cptr = nullptr,
-                         const int32_t *chunk_node = nullptr);
+// max_nodes: the exact size of the largest graph (it sizes the LDS flag arrays; nd.max_graph_nodes is not read)
+int td_launch_step_lists(const uint8_t *clean, const TdNodes &nd, const TdGraphTab &gt, int max_nodes, const TdStepLists &out, hipStream_t s);
 // bookkeeping a session step resets in its first kernel: up to three counter arrays and the ligand rows' forward-reach flags
 struct TdStepReset {
     int32_t *c0 = nullptr, *c1 = nullptr, *c2 = nullptr;
     int n0 = 0, n1 = 0, n2 = 0;
     uint8_t *flags2 = nullptr;
 };
-int td_launch_ligand_update(const td_model *m, const float *lpos, const int64_t *lv, const int32_t *lig_node, int64_t Nl,
-                            float *h, float4 *x4, hipStream_t s, const TdStepReset *reset = nullptr, const float *gbias = nullptr,
-                            const int32_t *gid = nullptr);
+// reset: null: nothing to reset; gbias / gid: as td_launch_compose, gid read only with gbias
+int td_launch_ligand_update(const td_model *m, const float *lpos, const int64_t *lv, const TdRows &lig, float *h, float4 *x4,
+                            const TdStepReset *reset, const float *gbias, const int32_t *gid, hipStream_t s);
 int td_launch_ligand_list(const uint8_t *mask, int64_t N, int32_t *lig_node, int32_t *count, hipStream_t s);
 // node.hip
-// rows: optional list of node ids (N = its length); mat_mask bits 0..3 = [k_i, k_j, v_i, v_j] projections, bit 4 = query MLP
-int td_launch_node_proj(const TdNodeStage &st, const float *h, int64_t N, const int32_t *rows, unsigned mat_mask,
-                        float *P, float *q, hipStream_t s, const int32_t *count_ptr = nullptr,
-                        const int32_t *rows2 = nullptr, int64_t N2 = 0, unsigned mask2 = 0);
-int td_launch_node_proj_pair(const TdNodeStage &hx, const int32_t *hop_rows, const int32_t *hop_count,
-                             const int32_t *lig_rows, int64_t Nl, float *Px, float *qx, const TdNodeStage &nx,
-                             const int32_t *rows, const int32_t *count_ptr, float *P, float *q, const float *h, int64_t N,
-                             hipStream_t s);
+// mat_mask bits 0..3 = [k_i, k_j, v_i, v_j] projections, bit 4 = query MLP, on `rows`; rows2 / mask2: a second segment of the same stage
+// (empty: none)
+int td_launch_node_proj(const TdNodeStage &st, const float *h, const TdRows &rows, unsigned mat_mask, const TdRows &rows2, unsigned mask2,
+                        float *P, float *q, hipStream_t s);
+// stage hx: src-side units on `hop`, dst-side units + queries on `lig`, into Px / qx; stage nx: all units on `rows`, into P / q
+int td_launch_node_proj_pair(const TdNodeStage &hx, const TdRows &hop, const TdRows &lig, float *Px, float *qx, const TdNodeStage &nx,
+                             const TdRows &rows, float *P, float *q, const float *h, hipStream_t s);
 int td_launch_node_output(const TdNodeOut &no, const float *out, float *h, int64_t N, hipStream_t s);
-int td_launch_layer_gate(const float *w, const float *offsets, float coeff, const float4 *x4, const int32_t *nbr, int64_t N, float *ew,
+// gate.hip -- rows: rows of gt.nbr / gt.ew (chunks on a general graph), all of them or a list
+int td_launch_layer_gate(const float *w, const float *offsets, float coeff, const float4 *x4, const TdGraphTab &gt, const TdRows &rows,
                          hipStream_t s);
-// gate.hip -- rows: optional row list; chunk_node: dst node of every row of nbr / ew on general graphs (nullptr: row == node)
-int td_launch_gate(const TdGate &g, const float4 *x4, const int32_t *nbr, int64_t N, const int32_t *rows,
-                   const int32_t *count_ptr, float *ew, hipStream_t s, const int32_t *chunk_node = nullptr);
-// edge16.hip.  cptr (general graphs): the in-edges of dst node i are the chunks cptr[i] .. cptr[i+1]-1 (32 slots each) of
-// nbr / ew / alpha; nullptr on the default graph (one 32-slot row per node, chunk == node)
-int td_launch_edge_key16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const int32_t *nbr, const float *ew,
-                         const float *P, const float *q, const int32_t *rows, const int32_t *count_ptr, int64_t count,
-                         float *alpha, hipStream_t s, bool h2x_stage, const int32_t *cptr = nullptr, const int32_t *lig_rows = nullptr,
-                         int64_t lig_count = 0, int cpn_p = 0);
+int td_launch_gate(const TdGate &g, const float4 *x4, const TdGraphTab &gt, const TdRows &rows, hipStream_t s);
+// edge16.hip.  lig (x2h passes): the ligand rows of the batch, all of them among `rows` (every row list of a forward pass or sampling step
+// holds the ligand atoms); empty: a list without ligand rows.  h2x_stage: the unfused h2x key pass.  out: null: the value pass adds into h
+int td_launch_edge_key16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const TdGraphTab &gt, const float *P, const float *q,
+                         const TdRows &rows, const TdRows &lig, bool h2x_stage, hipStream_t s);
+int td_launch_edge_value16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const TdGraphTab &gt, const float *P, const TdRows &rows,
+                           const TdRows &lig, float *h, float *out, hipStream_t s);
+int td_launch_edge_xv16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4_in, float4 *x4_out, const TdGraphTab &gt, const float *P,
+                        const TdRows &rows, hipStream_t s);
 int td_launch_edge_h2x16(const TdEdgeMlp &mlp_k, const TdEdgeMlp &mlp_v, const TdLayer &L, const float4 *x4_in, float4 *x4_out,
-                         const int32_t *nbr, const float *ew, const float *P, const float *q, const int32_t *rows,
-                         int64_t count, hipStream_t s, const int32_t *cptr = nullptr, float *alpha = nullptr);
-int td_launch_edge_xv16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4_in, float4 *x4_out, const int32_t *nbr,
-                        const float *P, const int32_t *rows, int64_t count, const float *alpha, hipStream_t s,
-                        const int32_t *cptr = nullptr);
-int td_launch_edge_value16(const TdEdgeMlp &mlp, const TdLayer &L, const float4 *x4, const int32_t *nbr, const float *P,
-                           const int32_t *rows, const int32_t *count_ptr, int64_t count, float *h, const float *alpha, const int32_t *lig_rows, int64_t lig_count,
-                           hipStream_t s, const int32_t *cptr = nullptr, int cpn_p = 1, int64_t lig_chunks = 0,
-                           const int32_t *mixed_count = nullptr, float *out = nullptr, const float *gate_m = nullptr);
+                         const TdGraphTab &gt, const float *P, const float *q, const TdRows &rows, hipStream_t s);
 int td_set_wg_trace(unsigned long long *buf, int slots);
 bool td_wg_trace_armed();
 // graph.hip, general graphs
 int td_launch_layout(const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid, const int32_t *g_cbase,
                      const int32_t *g_cl, const int32_t *g_lbase, int cpn_p, int64_t N, int32_t *cptr, int32_t *chunk_node,
                      int32_t *lig_chunks, int32_t total_chunks, hipStream_t s);
-int td_launch_graph_general(int mode, const float4 *x4, const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid,
-                            const int32_t *prot_node, int64_t Np, const int32_t *lig_node, int64_t Nl, int64_t N, int k,
-                            float radius, int max_graph_nodes, const int32_t *cptr, int32_t *cnbr, int64_t NC, hipStream_t s);
-int td_launch_knn_general_static(const float4 *x4, const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid,
-                                 const int32_t *prot_rows, int64_t Np, int k, int max_graph_nodes, const int32_t *cptr,
-                                 int32_t *snbr, unsigned long long *skeys, hipStream_t s);
-int td_launch_ligand_rows_general(int mode, const float4 *x4, const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid,
-                                  const int32_t *lig_node, int64_t Nl, int k, int max_graph_nodes, const int32_t *cptr,
-                                  int32_t *cnbr, hipStream_t s);
-int td_launch_hybrid_ligand_half(const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid, const int32_t *lig_node,
-                                 int64_t Nl, const int32_t *cptr, int32_t *cnbr, hipStream_t s);
-int td_launch_knn_merge_general(const float4 *x4, const int32_t *node_ptr, const int32_t *pptr, const int32_t *gid,
-                                const int32_t *prot_rows, int64_t Np, const unsigned long long *skeys, const int32_t *snbr,
-                                const float *h0, const float *h1s, const float *ews, const int32_t *cptr, int cpn, int32_t *nbr,
-                                float *h, float *ew, uint8_t *clean, uint8_t *flags2, hipStream_t s, int k);
-int td_launch_radius32(const float4 *x4, const int32_t *node_ptr, const int32_t *gid, int64_t N, float radius, int cap,
-                       int32_t *nbr, hipStream_t s);
+// prot / lig: the protein / ligand rows of the batch (lists of exactly `count` rows); gt: the chunked table whose nbr is written (cptr, NC)
+int td_launch_graph_general(int mode, const TdNodes &nd, const TdRows &prot, const TdRows &lig, int k, float radius, const TdGraphTab &gt,
+                            hipStream_t s);
+int td_launch_knn_general_static(const TdNodes &nd, const TdRows &prot, int k, const TdGraphTab &gt, unsigned long long *skeys, hipStream_t s);
+int td_launch_ligand_rows_general(int mode, const TdNodes &nd, const TdRows &lig, int k, const TdGraphTab &gt, hipStream_t s);
+int td_launch_hybrid_ligand_half(const TdNodes &nd, const TdRows &lig, const TdGraphTab &gt, hipStream_t s);
+// the protein rows' merge of td_launch_knn_merge on the chunked table (the ligand rows: td_launch_ligand_rows_general)
+int td_launch_knn_merge_general(const TdNodes &nd, const TdRows &prot, const TdStaticTabs &tabs, const TdGraphTab &gt, float *h,
+                                uint8_t *clean, uint8_t *flags2, int k, hipStream_t s);
+int td_launch_radius32(const TdNodes &nd, float radius, int cap, int32_t *nbr, hipStream_t s);
 int td_launch_slots_to_dense(const int32_t *cptr, const int32_t *cnbr, int64_t N, int width, int32_t *out, hipStream_t s);
 // misc.hip
 int td_launch_head(const TdHead &hd, const float *h, const float4 *x4, const int32_t *lig_node, int64_t Nl,
